@@ -134,6 +134,10 @@ def parse_args(argv=None):
                     help="TEST HOOK (tests/test_host_cpu.py): no GPU work at all -- every rank stands in for its step with a host-side "
                          "gradient bucket, so that the launcher, the rendezvous, the all-reduce, the max-over-ranks timing and the JSON "
                          "schema of the N > 1 path can be exercised on a machine without GPUs (backend gloo)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last of them computed -- image, alpha, radii, loss terms and the parameters "
+                         "AdamW left -- as DIR/<name>.npy (float32; integer arrays as float64), at most 64 MB in all: two builds run with "
+                         "the same arguments can be compared output for output")
     return ap.parse_args(argv)
 
 
@@ -328,7 +332,7 @@ class Harness:
                     self.opt.step()
             # detached: holding an output with a grad_fn would keep this step's autograd graph (and its AccumulateGrad nodes,
             # bound to the stream they were created on) alive into the next step / into graph capture
-            return {"radii": out["radii"]}
+            return {"radii": out["radii"], "render": out["render"].detach(), "alpha": out["render_alpha"].detach()}
 
         self.compute = compute
         self.step = self.eager_step
@@ -609,6 +613,8 @@ def main(argv=None):
         # really did the work; an overflowed frame would have produced a background image and is an error here
         h.ctx.check_status()
         assert h.ctx.last_needed > 0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, h, out)          # (reads only: the passes below restore and replay from the snapshot)
     exchange_rep = h.exchange_report() if (world > 1 and h.n_exchange) else None
     dom_in_region = None
     replicas_identical = None
@@ -1295,6 +1301,40 @@ def eval_block(dev, scene, cam, bg, lbs_T, n=200):
     res["stages_us_training_forward"] = {k: round(1e3 * v[0] / v[1], 1) for k, v in _lib.profile_read().items() if v[1]}
     _lib.profile_enable([])
     return res
+
+
+DUMP_BUDGET_BYTES = 60 << 20                # (the 64 MB of --dump-outputs, with room for the .npy headers)
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(out_dir, h, out):
+    """--dump-outputs: what the LAST timed step computed, one DIR/<name>.npy per array -- the step's own outputs (image, alpha, radii),
+    the [loss, L1, SSIM, mask L2] block it wrote and every parameter tensor after its AdamW update.  Floating-point arrays as float32,
+    integer ones as float64 (exact).  Above DUMP_BUDGET_BYTES in all, the per-Gaussian arrays keep the same fixed, seeded sample of rows."""
+    import numpy as np
+    import torch
+    loss_terms = h.sharded.loss_terms if h.sharded is not None else h.bucket.loss_terms
+    arrays = {"image": out["render"], "alpha": out["alpha"], "radii": out["radii"], "loss_terms": loss_terms}
+    for group in h.pc.param_groups():
+        arrays["param_" + group["name"]] = group["params"][0]
+    arrays = {k: v.detach().to(torch.float32 if v.is_floating_point() else torch.float64).cpu().numpy() for k, v in arrays.items()}
+    P = arrays["radii"].shape[0]
+    per_row = [k for k, a in arrays.items() if a.ndim and a.shape[0] == P]
+    total = sum(a.nbytes for a in arrays.values())
+    sampled = None
+    if total > DUMP_BUDGET_BYTES:
+        row_bytes = sum(arrays[k].nbytes // P for k in per_row)
+        n = (DUMP_BUDGET_BYTES - (total - sum(arrays[k].nbytes for k in per_row))) // row_bytes
+        assert n > 0, "--dump-outputs: the per-frame arrays alone exceed the budget"
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(P, n, replace=False))
+        for k in per_row:
+            arrays[k] = arrays[k][rows]
+        sampled = f"{n} of {P} rows (seed {DUMP_SAMPLE_SEED}) of {', '.join(per_row)}"
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    print(f"[bench] --dump-outputs: {len(arrays)} arrays, {sum(a.nbytes for a in arrays.values()) / 2**20:.1f} MB in {out_dir}"
+          + (f"; sampled {sampled}" if sampled else ""), file=sys.stderr)
 
 
 def densify_side(pc, out):

@@ -623,33 +623,76 @@ def test_unfuse_rearms_the_flat_step(hip_lib):
         o2.step(skip_word=torch.zeros(1, dtype=torch.int32))
 
 
-def test_moss_side_patches_apply(tmp_path):
-    """patches/*.diff (the MOSS-side edits of INTEGRATION.md section 3) apply cleanly to the reference's two binding files -- checked
-    wherever a reference checkout is present (this container; not on the GPU box), and the patched files still compile."""
-    import shutil
-    import subprocess
-    ref = "/root/reference"
-    if not os.path.isdir(os.path.join(ref, "gaussian_renderer")) or shutil.which("patch") is None:
-        pytest.skip("no reference checkout / no patch(1) here")
-    os.makedirs(tmp_path / "gaussian_renderer")
-    shutil.copy(os.path.join(ref, "gaussian_renderer", "__init__.py"), tmp_path / "gaussian_renderer" / "__init__.py")
-    shutil.copy(os.path.join(ref, "train_ZJU.py"), tmp_path / "train_ZJU.py")
-    os.makedirs(tmp_path / "scene")
-    shutil.copy(os.path.join(ref, "scene", "gaussian_model.py"), tmp_path / "scene" / "gaussian_model.py")
+def _diff_hunks(path):
+    """(target file, [(old_start, old_lines, new_start, new_lines), ...]) of a unified diff.  Lines keep their CR: the target files
+    have CRLF line endings and the diffs carry them."""
+    lines = open(path, "rb").read().decode().split("\n")
+    target, hunks, i = None, [], 0
+    while i < len(lines):
+        if lines[i].startswith("+++ b/"):
+            target = lines[i][6:].rstrip("\r")
+        m = re.match(r"@@ -(\d+),(\d+) \+(\d+),(\d+) @@", lines[i])
+        i += 1
+        if not m:
+            continue
+        o0, on, n0, nn = map(int, m.groups())
+        old, new = [], []
+        while len(old) < on or len(new) < nn:
+            tag, s = lines[i][:1], lines[i][1:]
+            assert tag in (" ", "-", "+"), f"{os.path.basename(path)}:{i + 1}: {lines[i]!r}"
+            if tag != "+":
+                old.append(s)
+            if tag != "-":
+                new.append(s)
+            i += 1
+        assert (len(old), len(new)) == (on, nn), f"{os.path.basename(path)}: hunk at -{o0} miscounted"
+        hunks.append((o0, old, n0, new))
+    assert target and hunks, path
+    return target, hunks
+
+
+def _apply_exactly(text, hunks):
+    """``text``: the lines of a file, None where no hunk has shown the line yet.  Each hunk must sit exactly where its header says --
+    no offset, no fuzz: the new-side start is the old-side start plus what the hunks before it added -- and its context and removed
+    lines must be the lines found there (a line still unknown is taken from the hunk).  Returns the patched lines."""
+    text, out, pos, delta = list(text), [], 0, 0
+    for o0, old, n0, new in hunks:
+        assert n0 == o0 + delta, (o0, n0, delta)
+        start = o0 - 1 if old else o0
+        assert start >= pos, "hunks overlap or are out of order"
+        text += [None] * (start + len(old) - len(text))
+        for j, s in enumerate(old):
+            if text[start + j] is None:
+                text[start + j] = s
+            assert text[start + j] == s, f"line {start + j + 1}: {text[start + j]!r} != {s!r}"
+        out += text[pos:start] + new
+        pos = start + len(old)
+        delta += len(new) - len(old)
+    return out + text[pos:]
+
+
+def test_moss_side_patches_apply(hip_lib):
+    """patches/*.diff (the MOSS-side edits of INTEGRATION.md section 3) are well-formed and apply in their documented order -- the
+    three, then train_ZJU_one_call_loss.diff on top of train_ZJU.diff -- each hunk exactly at its line (no offset, no fuzz).  The lines
+    of the MOSS files come from the diffs themselves (context and removed lines): where two diffs touch the same lines, the later one
+    must find what the earlier one left.  The patched lines say what the integration needs, and what they call exists."""
+    files = {}
     for name in ("gaussian_renderer.diff", "train_ZJU.diff", "gaussian_model.diff", "train_ZJU_one_call_loss.diff"):
-        with open(os.path.join(ROOT, "patches", name), "rb") as f:
-            r = subprocess.run(["patch", "-p1", "--binary"], cwd=tmp_path, stdin=f, capture_output=True, text=True)
-        assert r.returncode == 0, r.stdout + r.stderr
+        target, hunks = _diff_hunks(os.path.join(ROOT, "patches", name))
+        try:
+            files[target] = _apply_exactly(files.get(target, []), hunks)
+        except AssertionError as e:
+            raise AssertionError(f"{name} does not apply to {target}: {e}") from None
+    assert set(files) == {"gaussian_renderer/__init__.py", "train_ZJU.py", "scene/gaussian_model.py"}
+    files = {k: "\n".join(s for s in v if s is not None) for k, v in files.items()}
     for rel in ("gaussian_renderer/__init__.py", "train_ZJU.py"):
-        src = open(tmp_path / rel, newline="").read()
-        compile(src, rel, "exec")
+        src = files[rel]
         assert "transforms_in_op" in src
         assert "raw_parameters_in_op" in src               # set by the train_ZJU patch AND read by the renderer patch (ADVICE r4)
-    assert "pc._opacity, pc._scaling, pc._rotation, 7" in open(tmp_path / "gaussian_renderer" / "__init__.py", newline="").read()
-    src = open(tmp_path / "scene" / "gaussian_model.py", newline="").read()
-    compile(src, "scene/gaussian_model.py", "exec")
+    assert "pc._opacity, pc._scaling, pc._rotation, 7" in files["gaussian_renderer/__init__.py"]
+    src = files["scene/gaussian_model.py"]
     assert "from moss_amd.optim import AdamW as _AdamW" in src and "torch.optim.AdamW(l, lr=0.0, eps=1e-15)" not in src
-    src = open(tmp_path / "train_ZJU.py", newline="").read()
+    src = files["train_ZJU.py"]
     assert "ssim_fused as ssim" in src
     # the optional fourth diff (on top of train_ZJU.diff): lines 111-119 and the first three terms of :131 as ONE call
     assert "training_loss_moss_fused(image, alpha, gt_image, bkgd_mask, viewpoint_cam.moss_region, terms_out=raster_terms)" in src
