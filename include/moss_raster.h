@@ -383,6 +383,43 @@ typedef struct moss_adamw_multi_args {
 int moss_adamw_multi(const moss_adamw_multi_args* args, void* stream);
 
 /*
+ * Evaluation metrics of a split (additive in ABI 6; no existing entry point changes): the per-view lines of MOSS's training_report,
+ * train_ZJU.py:244-253 --
+ *     image = clamp(render, 0, 1); gt = clamp(gt, 0, 1); image.permute(1,2,0)[bound_mask[0]==0] = 0 if bg.sum() == 0 else 1
+ *     l1_test += l1_loss(image, gt).mean().double()         (utils/loss_utils.py:41-42: mean over all C*H*W elements)
+ *     psnr_test += psnr(image, gt).mean().double()          (utils/image_utils.py:19-21: the MEAN of the C per-channel PSNRs;
+ *                                                            an exact match gives +inf)
+ *     ssim_test += ssim(image, gt).mean().double()          (utils/loss_utils.py:47-87: 11x11 window, sigma 1.5, fp32-normalised,
+ *                                                            C1 = 0.01^2, C2 = 0.03^2, zero padding at the FULL frame's edge)
+ * -- and render_ZJU.py:73-94 (render_set: the same metrics without a mask).  Up to eight views of one size per call.
+ *   image[v], gt[v]: (C,H,W) fp32 device arrays, C = 1..4; bound[v]: (H,W) bytes, 0 = fill the render there (the view's bound_mask
+ *     selection, moss_amd.loss.ViewRegion.bound), or NULL = no fill; out_image[v]: (C,H,W) fp32 receiving the clamped and filled
+ *     render (what the caller's LPIPS is given), or NULL.  fill: 0 or 1, decided ONCE by the caller from its background colour.
+ *   state: MOSS_METRICS_STATE_BYTES zero-initialised device bytes, 8-byte aligned: double [0] sum of l1, [1] sum of psnr, [2] sum of
+ *     ssim, int64 [3] the number of views added; doubles [4..7] are never touched (the caller's, e.g. an LPIPS sum).  The views'
+ *     float32 values are added in view order, one float64 rounding each: the reference's accumulation bit for bit.  Zero it to reset.
+ *   per_view (optional): (per_view_capacity, 3) float32 {l1, psnr, ssim}; the view added as the n-th since the reset is written to
+ *     row n while n < per_view_capacity.
+ *   workspace: moss_metrics_workspace_bytes(num_views, C, H, W) device bytes (host-side function).
+ * Two launches on `stream`, no host synchronisation, no allocation, deterministic (no float atomics): capturable in a hipGraph. */
+#define MOSS_METRICS_STATE_BYTES 64
+typedef struct moss_eval_metrics_args {
+    int32_t num_views;                       /* 1..8 */
+    int32_t C, H, W;
+    const float* image[8];
+    const float* gt[8];
+    const unsigned char* bound[8];
+    float* out_image[8];
+    float fill;
+    void* state;
+    float* per_view; int32_t per_view_capacity;
+    char* workspace; size_t workspace_bytes;
+} moss_eval_metrics_args;
+size_t moss_metrics_workspace_bytes(int num_views, int C, int H, int W);
+size_t moss_metrics_state_bytes(void);
+int moss_eval_metrics(const moss_eval_metrics_args* args, void* stream);
+
+/*
  * k nearest reference points of every query point, 3-D, exact, k = 1..4: replaces the third-party
  * `knn_cuda.KNN(k, transpose_mode=True)(ref, query)` MOSS calls at scene/gaussian_model.py:85-86,586,657,759,827 (a CUDA-only
  * binary wheel, not in the repository; parity unpinned by the reference).

@@ -124,6 +124,12 @@ def _declare(lib):
     lib.moss_photometric_loss_weighted.argtypes = [_i, _i, _i, _p, _p, _p, _p, _f, _f, _f, _p, _p, _p, _p, C.c_size_t, _p]
     lib.moss_adamw_multi.restype = _i
     lib.moss_adamw_multi.argtypes = [_p, _p]
+    lib.moss_metrics_workspace_bytes.restype = C.c_size_t
+    lib.moss_metrics_workspace_bytes.argtypes = [_i, _i, _i, _i]
+    lib.moss_metrics_state_bytes.restype = C.c_size_t
+    lib.moss_metrics_state_bytes.argtypes = []
+    lib.moss_eval_metrics.restype = _i
+    lib.moss_eval_metrics.argtypes = [_p, _p]
     lib.moss_photometric_loss_roi.restype = _i
     lib.moss_photometric_loss_roi.argtypes = [_i, _i, _i, _p, _p, _p, _p, _p, _p, _f, _f, _f, _p, _p, _p, _p, C.c_size_t, _p]
     lib.moss_adamw_flat.restype = _i
@@ -172,6 +178,14 @@ class AdamWMultiArgs(C.Structure):
     _fields_ = [("num_tensors", C.c_int32), ("numel", C.c_longlong * 8), ("params", C.c_void_p * 8), ("grads", C.c_void_p * 8),
                 ("exp_avg", C.c_void_p * 8), ("exp_avg_sq", C.c_void_p * 8), ("lr", C.c_float * 8), ("step", C.c_int32 * 8),
                 ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_float), ("weight_decay", C.c_float)]
+
+
+class EvalMetricsArgs(C.Structure):
+    """``moss_eval_metrics_args`` of include/moss_raster.h (``moss_eval_metrics``: the evaluation metrics of up to eight views, one call)."""
+    _fields_ = [("num_views", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("image", C.c_void_p * 8),
+                ("gt", C.c_void_p * 8), ("bound", C.c_void_p * 8), ("out_image", C.c_void_p * 8), ("fill", C.c_float),
+                ("state", C.c_void_p), ("per_view", C.c_void_p), ("per_view_capacity", C.c_int32), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_size_t)]
 
 
 OPT_BITS = {"means3D": 1, "sh": 2, "opacity": 4, "scales": 8, "rotations": 16}      # MOSS_OPT_*; position = index in the struct's arrays

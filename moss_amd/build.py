@@ -37,6 +37,7 @@ SOURCES = {
     "binning.hip": [],
     "blend.hip": [],
     "loss.hip": [],
+    "metrics.hip": [],
     "optim.hip": [],
     "activations.hip": [],
     "densify.hip": [],
