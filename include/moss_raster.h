@@ -39,7 +39,10 @@ extern "C" {
  * traffic: coefficients above the highest degree ever active are never read or written when they are known to be zero);
  * moss_photometric_loss_roi (MOSS's own loss expression: bound_mask selection, bounding-rectangle crop) and moss_adamw_multi (up to eight
  * tensors with buffers of their own in one launch) are new entry points. */
-#define MOSS_ABI_VERSION 6
+/* ABI 7: the rasterizer's positional variants collapse into moss_raster_forward_ex / moss_raster_backward_ex (one argument block per
+ * direction; capacity 0 is refused), and the positional flat AdamW forms into moss_adamw_flat_ex (the map of the
+ * removed names).  moss_raster_forward / moss_raster_backward keep the reference's signatures. */
+#define MOSS_ABI_VERSION 7
 /* Version 3 (round 4): EVERY forward / backward entry point takes the `debug` bit set (version 2: only moss_raster_forward /
  * moss_raster_backward did, so MOSS_DEBUG_NO_BLOCK_CULL was silently dropped on the _async / _tf / _raw paths: last argument before
  * `stream`); moss_adamw_flat_guarded (an optimizer step that a dropped frame turns into a no-op); MOSS_RAW_POSE and the
@@ -104,7 +107,7 @@ const char* moss_last_error(void);
  * training forward's BIT FOR BIT (the blend folds its sums at the same list positions); what is not produced is the state only the
  * backward reads: depth-segment cuts, per-block tails, gradient-record cells and their validity bits.  The binning buffer then holds
  * ids, block masks, the 48-byte records and the 8-byte sort keys only: moss_raster_binning_bytes_forward_only(R), 62 B per instance
- * (training: ~370 B).  With a capacity (asynchronous variants) the keys go through the scan -> scatter chain into exact ranges -- six
+ * (training: ~370 B).  With a capacity (asynchronous forward) the keys go through the scan -> scatter chain into exact ranges -- six
  * launches -- because the per-tile key buckets of the four-launch training forward live in the record pool's address space.
  * A backward call over such buffers is a no-op that returns ZERO gradients and takes no optimizer step (status flag
  * MOSS_STATUS_FORWARD_ONLY; the kernels check it on the device, like a capacity overflow): never out-of-bounds. */
@@ -137,16 +140,16 @@ int moss_raster_forward(
     void* stream);
 
 /*
- * Asynchronous variant of moss_raster_forward for launch-bound training loops and hipGraph capture: NO host read-back.
- * The caller states an upper bound `capacity` on the number of (Gaussian, tile) instances (e.g. 2x the value a previous,
- * synchronous call returned); scratch buffers and launch grids are sized for it and every kernel bounds itself with the
- * device-side count.  Returns `capacity` (>= 0) -- pass that as R to moss_raster_backward -- or a negative error code.
+ * The asynchronous forward (moss_raster_forward_ex with capacity > 0, below) for launch-bound training loops and hipGraph capture: NO
+ * host read-back.  The caller states an upper bound `capacity` on the number of (Gaussian, tile) instances (e.g. 2x the value a previous,
+ * synchronous call returned); scratch buffers and launch grids are sized for it and every kernel bounds itself with the device-side
+ * count.  Returns `capacity` -- pass that as R to the backward -- or a negative error code.
  * If a frame needs more instances than `capacity`, nothing is rendered (outputs = background, gradients = 0) and the
  * overflow bit is set in the status words; poll them with moss_raster_read_status once the stream has advanced.
  * `debug`: MOSS_DEBUG_NO_BLOCK_CULL is honoured; MOSS_DEBUG_SYNC is refused (MOSS_ERR_INVALID_ARG: it synchronises by definition).
  *
  * `frame_state` (optional, may be NULL; no counterpart in the reference, which memsets its buffers in every forward): a caller-owned
- * device block of moss_raster_frame_state_bytes(width, height) bytes, zero-initialised ONCE.  With it this call keeps the per-frame
+ * device block of moss_raster_frame_state_bytes(width, height) bytes, zero-initialised ONCE.  With it the call keeps the per-frame
  * counters its kernels add to (tile histogram, tile cursors, error flags) in that block instead of in the image buffer and returns
  * the block all-zero again (its sort kernel re-zeroes it; error paths clean it too), so no clear kernel runs in front of the
  * preprocess kernel -- one launch less per frame (4 us inside a captured graph).  One block per concurrent user (stream); the same
@@ -159,17 +162,6 @@ int moss_raster_forward(
  */
 #define MOSS_FRAME_STATE_DROPPED_WORD 4
 size_t moss_raster_frame_state_bytes(int width, int height);
-int moss_raster_forward_async(
-    moss_alloc_fn geometry_alloc, void* geometry_user,
-    moss_alloc_fn binning_alloc, void* binning_user,
-    moss_alloc_fn image_alloc, void* image_user,
-    int P, int D, int M,
-    const float* background, int width, int height,
-    const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
-    const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
-    const float* viewmatrix, const float* projmatrix, const float* cam_pos,
-    float tan_fovx, float tan_fovy, int prefiltered,
-    float* out_color, float* out_depth, float* out_alpha, int* radii, int capacity, char* frame_state, int debug, void* stream);
 
 /* Enqueue (on `stream`) a copy of the forward's 8 status words from the image buffer to pinned host memory:
  * [0] instances rendered  [1] longest tile list  [2] flags: bit0 prefiltered-point culled, bit1 capacity overflow
@@ -285,72 +277,50 @@ int moss_photometric_loss_roi(int C, int H, int W, const float* image, const flo
                               float* loss_out, float* dL_dimage, float* dL_dalpha, char* workspace, size_t workspace_bytes, void* stream);
 
 /*
- * Flat fused AdamW (torch.optim.AdamW semantics, amsgrad off) over `n` contiguous fp32 parameters with their gradients and
- * moments; up to 8 learning-rate segments: parameter i belongs to the first segment s with i < segment_end[s] (host arrays).
- * Replaces the per-group optimizer step of scene/gaussian_model.py:215-226 for the Gaussian parameters.  `step` counts from 1.
- * Optional periodic pattern per segment (all three arrays NULL = none): where segment_period[s] > 0, element j of segment s uses
- * segment_lr[s] if j % segment_period[s] < segment_split[s], else segment_lr2[s] -- e.g. the SH coefficients stored as ONE
- * (P,16,3) tensor with the DC term's learning rate on the first 3 of every 48 floats and lr/20 on the rest (the reference's
- * separate f_dc / f_rest groups, without the per-step torch.cat of get_features).
- */
-int moss_adamw_flat(long long n, float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
-                    int num_segments, const long long* segment_end, const float* segment_lr,
-                    const int* segment_period, const int* segment_split, const float* segment_lr2,
-                    double beta1, double beta2, float eps, float weight_decay, int step, void* stream);
-/* Same update with the step counter kept on the device: `step_state` is moss_adamw_state_bytes() (= MOSS_ADAMW_STATE_BYTES of the
- * header the library was built from; ask the library, a binding's copy of the constant can be stale) zero-initialised device bytes
- * (32-bit words: [0] = int step, advanced by one per call by the update kernel itself; [8..11] = the bias corrections of the
- * current / next step, double-buffered by step parity; [64] and [128 + 64 g], g < 32 = its two-level block-completion counters,
- * each on a 256-byte line of its own).  n must be > 0.  Nothing in the call depends on a host-side
- * counter, so a captured hipGraph of a training step replays correctly.
- * LEARNING RATES ON THE DEVICE (ABI 4): when word MOSS_ADAMW_LR_VALID_WORD of the block is non-zero, every kernel that is given the
- * block (the _devstep / _range / _guarded updates and moss_raster_backward_raw_adamw) takes segment s's learning rate from float
- * word MOSS_ADAMW_LR_WORD0 + s and its second rate (periodic pattern) from MOSS_ADAMW_LR2_WORD0 + s instead of from segment_lr /
- * segment_lr2: a schedule -- MOSS decays the position rate every iteration, scene/gaussian_model.py:263-268 -- is then a 64-byte
- * host-to-device copy between two replays of a captured step, not a re-capture. */
-#define MOSS_ADAMW_STATE_BYTES 9216
-#define MOSS_ADAMW_LR_VALID_WORD 12
-#define MOSS_ADAMW_LR_WORD0 16
-#define MOSS_ADAMW_LR2_WORD0 24
-size_t moss_adamw_state_bytes(void);
-int moss_adamw_flat_devstep(long long n, float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
-                            int num_segments, const long long* segment_end, const float* segment_lr,
-                            const int* segment_period, const int* segment_split, const float* segment_lr2,
-                            double beta1, double beta2, float eps, float weight_decay, void* step_state, void* stream);
-
-/* The same update on a SHARD of the flat buffers: the arrays hold the elements [first, first + count) (first a multiple of 4) of the
- * buffers the segment table -- global indices, as above -- describes.  step_state != NULL: device-side step counter (then `step` is
- * ignored), else `step` counts from 1.  For N ranks that reduce-scatter the gradient bucket, update their 1/N of the parameters
- * (moments memory and update time / N) and all-gather the result (moss_amd/dist.py ShardedStep). */
-int moss_adamw_flat_range(long long first, long long count, float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
-                          int num_segments, const long long* segment_end, const float* segment_lr,
-                          const int* segment_period, const int* segment_split, const float* segment_lr2,
-                          double beta1, double beta2, float eps, float weight_decay, int step, void* step_state, void* stream);
-
-/* moss_adamw_flat_range with a GUARD: if (*skip_word & skip_mask) != 0 when the kernel runs, the call is a no-op -- parameters,
- * moments and the device-side step counter stay bit for bit what they were.  `skip_word`: a device word, e.g. the frame's status word
- * (image buffer, 32-bit word 2; skip_mask = 2: the capacity-overflow bit of moss_raster_forward_async) -- a frame that overflowed
- * its capacity rendered nothing and left zero gradients, and inside a captured step nobody is there to skip the optimizer: without
- * the guard such a frame is a weight-decay-only step that also decays the moments.  Or a float that is non-zero when ANY rank
- * dropped its frame (the flag averaged with the gradient bucket, skip_mask = 0x7fffffff) so that replicas skip together.
- * Needs the device-side step counter (step_state != NULL): a host-side count cannot know about the skipped step. */
-int moss_adamw_flat_guarded(long long first, long long count, float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
-                            int num_segments, const long long* segment_end, const float* segment_lr,
-                            const int* segment_period, const int* segment_split, const float* segment_lr2,
-                            double beta1, double beta2, float eps, float weight_decay, void* step_state,
-                            const uint32_t* skip_word, uint32_t skip_mask, void* stream);
-
-/* Every form of the flat update behind one argument block (ABI 6), plus the DEGREE-AWARE update of an SH tensor: MOSS trains at SH
- * degree 0 / 1 / 2 for iterations 1-2999 and at degree 3 for the last one (train_ZJU.py:85-86, scene/gaussian_model.py:171-173); the
- * coefficients above the highest degree that has ever been active have received no gradient, so their moments are exactly zero and their
- * AdamW step is the decoupled weight decay alone.
+ * Flat fused AdamW (torch.optim.AdamW semantics, amsgrad off) over contiguous fp32 parameters with their gradients and moments, every
+ * form of the update behind one argument block (ABI 6; the positional forms of ABI 2-5 were removed in ABI 7).  Replaces the per-group
+ * optimizer step of scene/gaussian_model.py:215-226 for the Gaussian parameters.
+ *   params, grads, exp_avg, exp_avg_sq: the elements [first, first + count) (first a multiple of 4) of flat buffers that the segment
+ *     table -- global indices -- describes.  first = 0, count = n: the whole buffer.  A SHARD is for N ranks that reduce-scatter the
+ *     gradient bucket, update their 1/N of the parameters (moments memory and update time / N) and all-gather the result (SURVEY
+ *     section 8e; moss_amd/dist.py ShardedStep).
+ *   Up to 8 learning-rate segments: parameter i belongs to the first segment s with i < segment_end[s] (host arrays).
+ *   Optional periodic pattern per segment (all three arrays NULL = none): where segment_period[s] > 0, element j of segment s uses
+ *     segment_lr[s] if j % segment_period[s] < segment_split[s], else segment_lr2[s] -- e.g. the SH coefficients stored as ONE
+ *     (P,16,3) tensor with the DC term's learning rate on the first 3 of every 48 floats and lr/20 on the rest (the reference's
+ *     separate f_dc / f_rest groups, without the per-step torch.cat of get_features).
+ *   step_state NULL: `step` counts from 1.  Else the step counter is kept on the device: `step_state` is moss_adamw_state_bytes()
+ *     (= MOSS_ADAMW_STATE_BYTES of the header the library was built from; ask the library, a binding's copy of the constant can be
+ *     stale) zero-initialised device bytes (32-bit words: [0] = int step, advanced by one per call by the update kernel itself;
+ *     [8..11] = the bias corrections of the current / next step, double-buffered by step parity; [64] and [128 + 64 g], g < 32 = its
+ *     two-level block-completion counters, each on a 256-byte line of its own), count must be > 0, and nothing in the call depends
+ *     on a host-side counter, so a captured hipGraph of a training step replays correctly.
+ *   LEARNING RATES ON THE DEVICE (ABI 4): when word MOSS_ADAMW_LR_VALID_WORD of the step-state block is non-zero, every kernel that is
+ *     given the block (this update and the fused backward, moss_raster_backward_ex with `opt`) takes segment s's learning rate from
+ *     float word MOSS_ADAMW_LR_WORD0 + s and its second rate (periodic pattern) from MOSS_ADAMW_LR2_WORD0 + s instead of from
+ *     segment_lr / segment_lr2: a schedule -- MOSS decays the position rate every iteration, scene/gaussian_model.py:263-268 -- is
+ *     then a 64-byte host-to-device copy between two replays of a captured step, not a re-capture.
+ *   skip_word (needs step_state: a host-side count cannot know about the skipped step): a GUARD.  If (*skip_word & skip_mask) != 0
+ *     when the kernel runs, the call is a no-op -- parameters, moments and the device-side step counter stay bit for bit what they
+ *     were.  E.g. the frame's status word (image buffer, 32-bit word 2; skip_mask = 2: the capacity-overflow bit of the asynchronous
+ *     forward) -- a frame that overflowed its capacity rendered nothing and left zero gradients, and inside a captured step nobody is
+ *     there to skip the optimizer: without the guard such a frame is a weight-decay-only step that also decays the moments.  Or a
+ *     float that is non-zero when ANY rank dropped its frame (the flag averaged with the gradient bucket, skip_mask = 0x7fffffff) so
+ *     that replicas skip together.
+ * Plus the DEGREE-AWARE update of an SH tensor: MOSS trains at SH degree 0 / 1 / 2 for iterations 1-2999 and at degree 3 for the last
+ * one (train_ZJU.py:85-86, scene/gaussian_model.py:171-173); the coefficients above the highest degree that has ever been active have
+ * received no gradient, so their moments are exactly zero and their AdamW step is the decoupled weight decay alone.
  *   segment_active (NULL = none; else one int per segment, meaningful where segment_period[s] > 0 and a multiple of 4): of every
  *     `period` elements of segment s only the first segment_active[s] are ACTIVE (0 = all).  Inactive elements: gradient and moments are
  *     neither read nor written; the parameter takes p <- p (1 - lr wd), which is bit for bit what the full update gives for g = m = v = 0.
  *   inactive_zero != 0: the caller also knows the inactive PARAMETERS to be exactly zero (MOSS initialises features_rest with zeros,
  *     scene/gaussian_model.py:179-181, and 0 x decay = 0): they are not read or written at all.
- *   first / count as moss_adamw_flat_range; step_state NULL: `step` counts from 1, else the device-side counter; skip_word (with
- *   step_state) as moss_adamw_flat_guarded.  The results equal those of the corresponding older entry point bit for bit. */
+ */
+#define MOSS_ADAMW_STATE_BYTES 9216
+#define MOSS_ADAMW_LR_VALID_WORD 12
+#define MOSS_ADAMW_LR_WORD0 16
+#define MOSS_ADAMW_LR2_WORD0 24
+size_t moss_adamw_state_bytes(void);
 typedef struct moss_adamw_flat_args {
     long long first, count;
     float* params; const float* grads; float* exp_avg; float* exp_avg_sq;
@@ -370,14 +340,14 @@ int moss_adamw_flat_ex(const moss_adamw_flat_args* args, void* stream);
 
 /* Up to eight parameter tensors with buffers OF THEIR OWN in one launch (ABI 6): what a torch.optim-style optimizer holds -- MOSS's six
  * single-tensor Gaussian groups (scene/gaussian_model.py:215-226), each with its `exp_avg` / `exp_avg_sq` state tensors and its own
- * step count (densification surgery keeps them per tensor).  Per element the arithmetic of moss_adamw_flat with one segment and the
- * tensor's `lr` and `step`: bit-identical to num_tensors calls of it.  Pointers 16-byte aligned; an entry with numel 0 is skipped.
+ * step count (densification surgery keeps them per tensor).  Per element the arithmetic of moss_adamw_flat_ex with one segment, a
+ * host-side step and the tensor's `lr` and `step`: bit-identical to num_tensors calls of it.  Pointers 16-byte aligned; an entry with numel 0 is skipped.
  * moss_amd.optim.AdamW -- the drop-in for `torch.optim.AdamW` of patches/gaussian_model.diff -- steps its single-tensor groups with it. */
 typedef struct moss_adamw_multi_args {
     int32_t num_tensors;                     /* 1..8 */
     long long numel[8];
     float* params[8]; const float* grads[8]; float* exp_avg[8]; float* exp_avg_sq[8];
-    float lr[8]; int32_t step[8];            /* step counts from 1, like moss_adamw_flat */
+    float lr[8]; int32_t step[8];            /* step counts from 1, like moss_adamw_flat_args.step */
     double beta1, beta2; float eps, weight_decay;
 } moss_adamw_multi_args;
 int moss_adamw_multi(const moss_adamw_multi_args* args, void* stream);
@@ -461,56 +431,59 @@ int moss_neighbour_kl(int P, int Nsrc, const float* xyz, const float* rotation, 
                       const long long* pair_idx, float* kl_out, void* stream);
 
 /*
- * Extension: covariance with a per-Gaussian 3x3 transform INSIDE the op.
- * MOSS feeds cov3D_precomp = strip_symmetric(T (R S S^T R^T) T^T) built by torch ops (scene/gaussian_model.py:37-44,168-169;
- * gaussian_renderer/__init__.py:88-91) because the LBS transform T of each Gaussian changes every frame; on MI355X that Python
- * path costs more than the whole rasterizer.  These two entry points take (scales, rotations, transforms (P,3,3) row-major)
- * instead and return gradients for all three.  Same semantics otherwise as moss_raster_forward[_async] (capacity < 0:
- * synchronous sizing of the binning buffer, >= 0: asynchronous with that capacity) and moss_raster_backward; `debug` as there
- * (MOSS_DEBUG_SYNC only with capacity < 0; MOSS_DEBUG_NO_BLOCK_CULL on the forward AND the matching backward call).
+ * The rasterizer with every extension (ABI 7): one argument block per direction.  The fields are those of moss_raster_forward /
+ * moss_raster_backward plus the extensions below; NULL or 0 in an extension field means "not used".  moss_raster_forward /
+ * moss_raster_backward fill these blocks with no extension and `capacity` = -1.
+ *
+ * capacity (forward): < 0 synchronous (one host read-back sizes the binning buffer, like moss_raster_forward); > 0 asynchronous with that
+ *   capacity (above; `frame_state` is used with either).  0 is refused (MOSS_ERR_INVALID_ARG).  MOSS_DEBUG_SYNC only with capacity < 0.
+ *   The backward's R is what the forward returned.
+ *
+ * transforms: covariance with a per-Gaussian 3x3 transform INSIDE the op.  MOSS feeds cov3D_precomp =
+ *   strip_symmetric(T (R S S^T R^T) T^T) built by torch ops (scene/gaussian_model.py:37-44,168-169; gaussian_renderer/__init__.py:88-91)
+ *   because the LBS transform T of each Gaussian changes every frame; on MI355X that Python path costs more than the whole rasterizer.
+ *   transforms (P,3,3) row-major, with scales and rotations, no cov3D_precomp; the backward also needs dL_dtransforms.
  *   dL_dcov3D (P,6): gradient w.r.t. the transformed covariance (what the op stores); dL_dscale / dL_drot include the transform;
  *   dL_dtransforms (P,9): written for every Gaussian (zeros for culled ones).
- */
-int moss_raster_forward_tf(
-    moss_alloc_fn geometry_alloc, void* geometry_user, moss_alloc_fn binning_alloc, void* binning_user,
-    moss_alloc_fn image_alloc, void* image_user, int P, int D, int M, const float* background, int width, int height,
-    const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
-    const float* scales, float scale_modifier, const float* rotations, const float* transforms,
-    const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered,
-    float* out_color, float* out_depth, float* out_alpha, int* radii, int capacity, char* frame_state, int debug, void* stream);
-int moss_raster_backward_tf(
-    int P, int D, int M, int R,
-    const float* background, int width, int height,
-    const float* means3D, const float* shs, const float* colors_precomp,
-    const float* scales, float scale_modifier, const float* rotations, const float* transforms,
-    const float* viewmatrix, const float* projmatrix, const float* campos,
-    float tan_fovx, float tan_fovy,
-    char* geom_buffer, char* binning_buffer, char* image_buffer,
-    const float* dL_dpix, const float* dL_ddepths, const float* dL_dalphas,
-    float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
-    float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, float* dL_dtransforms, int debug, void* stream);
-
-/*
- * Extension (caller side of the boundary): the GaussianModel getters applied INSIDE the op.
- * MOSS hands the rasterizer get_opacity = sigmoid(_opacity), get_scaling = exp(_scaling), get_rotation = normalize(_rotation)
- * (scene/gaussian_model.py:142-161, gaussian_renderer/__init__.py:77-93): five torch ops forward and a dozen backward per step.
- * These entry points take the RAW parameters for the inputs named in raw_flags and return the gradients w.r.t. the raw
- * parameters; otherwise they are moss_raster_forward_tf / moss_raster_backward_tf (transforms may be NULL here = none).
- *   raw_flags: MOSS_RAW_OPACITY (opacities are logits) | MOSS_RAW_SCALE (scales are logarithms) | MOSS_RAW_ROTATION
- *   (rotations are not normalised; normalised as x / max(|x|, 1e-12) like torch.nn.functional.normalize).
- *   The backward needs the raw opacities again (the reference backward does not take opacities at all).
+ *
+ * raw_flags (caller side of the boundary): the GaussianModel getters applied INSIDE the op.  MOSS hands the rasterizer
+ *   get_opacity = sigmoid(_opacity), get_scaling = exp(_scaling), get_rotation = normalize(_rotation) (scene/gaussian_model.py:142-161,
+ *   gaussian_renderer/__init__.py:77-93): five torch ops forward and a dozen backward per step.  With raw_flags the op takes the RAW
+ *   parameters for the inputs named there and returns the gradients w.r.t. the raw parameters; it needs scales and rotations, no
+ *   cov3D_precomp.
+ *   MOSS_RAW_OPACITY (opacities are logits) | MOSS_RAW_SCALE (scales are logarithms) | MOSS_RAW_ROTATION (rotations are not normalised;
+ *   normalised as x / max(|x|, 1e-12) like torch.nn.functional.normalize).
+ *   The backward needs the raw `opacities` again (the reference backward does not take opacities at all).
  *   MOSS_HINT_SPATIAL_ORDER may be OR-ed in: "neighbours in index are neighbours in space" (the caller re-indexed its Gaussians along
- *   a space-filling curve, e.g. moss_amd.densify.spatial_order).  It changes no result beyond the order of some float32 sums, only how the per-Gaussian backward deals
- *   Gaussians to its workgroups (groups of 16 from places spread over the index range, so that no workgroup is all-heavy).
+ *   a space-filling curve, e.g. moss_amd.densify.spatial_order).  It changes no result beyond the order of some float32 sums, only how
+ *   the per-Gaussian backward deals Gaussians to its workgroups (groups of 16 from places spread over the index range, so that no
+ *   workgroup is all-heavy).
  *   MOSS_RAW_POSE (needs `transforms`): means3D are the CANONICAL positions x and the op poses them itself, p = T x (+ translation
  *   (P,3), may be NULL), rows of T times x summed left to right -- what MOSS's caller does with torch ops before the call
  *   (gaussian_renderer/__init__.py:74-77: torch.matmul(transforms, means3D[..., None]).squeeze(-1) + translation).  dL_dmean3D is
  *   then the gradient w.r.t. x (= T^T dL/dp: it can be written straight into the position parameter's gradient), dL_dtransforms
- *   gains dL/dp x^T, and dL_dtranslation (P,3; may be NULL) = dL/dp.
- *   MOSS_SH_GRAD_ACTIVE_ONLY (ABI 6; backward entry points): dL_dsh is written for the coefficients of the ACTIVE degree only, (D+1)^2 of
+ *   gains dL/dp x^T, and dL_dtranslation (P,3; may be NULL) = dL/dp.  translation and dL_dtranslation only with MOSS_RAW_POSE.
+ *   MOSS_SH_GRAD_ACTIVE_ONLY (ABI 6; backward only): dL_dsh is written for the coefficients of the ACTIVE degree only, (D+1)^2 of
  *   M per Gaussian; the rest of the destination is left untouched.  For a caller whose destination already holds zeros there and whose
  *   consumers never read them -- a gradient sink into a zero-initialised bucket consumed by the degree-aware flat AdamW
  *   (moss_adamw_flat_ex) and the active-degree exchange.  Without the bit every element is written (zeros above the degree), as ever.
+ *
+ * opt (backward; SURVEY section 8f row n4, ABI 4): the raw-parameter backward that also TAKES THE OPTIMIZER STEP.  The Gaussian parameters
+ *   of MOSS receive their gradients from this op alone (every loss term of train_ZJU.py:111-131 goes through the rendered image; the
+ *   exception is the position, which also feeds the LBS-weight network), and torch.optim.AdamW then streams parameter, gradient and
+ *   both moments through the device once more (scene/gaussian_model.py:215-226, train_ZJU.py:204-205).  Here the per-Gaussian backward
+ *   kernel, which holds a Gaussian's gradients in registers / LDS when it finishes, applies the AdamW update of the tensors named in
+ *   opt->tensors itself: the parameters (= the op's inputs: writable memory, although the fields are const for the calls without `opt`)
+ *   are updated in place, the moments in opt->exp_avg / exp_avg_sq, and the gradient of an updated tensor need not be written at all
+ *   (its dL_d* pointer may be NULL).
+ *   Same arithmetic, bit for bit, as moss_adamw_flat_ex with a step_state on the same values (both use csrc/adamw.h); a frame that
+ *   overflowed its capacity (asynchronous forward) takes no step, like moss_adamw_flat_ex guarded by the frame's status word.
+ *   Requirements: raw_flags contains MOSS_RAW_OPACITY | MOSS_RAW_SCALE | MOSS_RAW_ROTATION (the inputs must be the parameters
+ *   themselves, not activated copies); MOSS_OPT_SH needs M == 16 and 16-byte aligned shs / moments; MOSS_OPT_MEANS only if the
+ *   means the op sees are the parameter (no transforms, or MOSS_RAW_POSE) and nothing else contributes to its gradient.
+ *   opt->step_state: moss_adamw_state_bytes() zeroed device bytes owned by this optimizer (not shared with a moss_adamw_flat_ex call
+ *   of the same step: each launch that is given the block advances the count).
+ *   opt == NULL or opt->tensors == 0: no update.
  */
 #define MOSS_RAW_OPACITY 1
 #define MOSS_RAW_SCALE 2
@@ -518,43 +491,6 @@ int moss_raster_backward_tf(
 #define MOSS_HINT_SPATIAL_ORDER 8
 #define MOSS_RAW_POSE 16
 #define MOSS_SH_GRAD_ACTIVE_ONLY 32
-int moss_raster_forward_raw(
-    moss_alloc_fn geometry_alloc, void* geometry_user, moss_alloc_fn binning_alloc, void* binning_user,
-    moss_alloc_fn image_alloc, void* image_user, int P, int D, int M, const float* background, int width, int height,
-    const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
-    const float* scales, float scale_modifier, const float* rotations, const float* transforms, const float* translation,
-    const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered,
-    float* out_color, float* out_depth, float* out_alpha, int* radii, int raw_flags, int capacity, char* frame_state, int debug, void* stream);
-int moss_raster_backward_raw(
-    int P, int D, int M, int R,
-    const float* background, int width, int height,
-    const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
-    const float* scales, float scale_modifier, const float* rotations, const float* transforms, const float* translation,
-    const float* viewmatrix, const float* projmatrix, const float* campos,
-    float tan_fovx, float tan_fovy,
-    char* geom_buffer, char* binning_buffer, char* image_buffer,
-    const float* dL_dpix, const float* dL_ddepths, const float* dL_dalphas,
-    float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
-    float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, float* dL_dtransforms, float* dL_dtranslation,
-    int raw_flags, int debug, void* stream);
-
-/*
- * Extension (ABI 4): the raw-parameter backward that also TAKES THE OPTIMIZER STEP.  The Gaussian parameters
- * of MOSS receive their gradients from this op alone (every loss term of train_ZJU.py:111-131 goes through the rendered image; the
- * exception is the position, which also feeds the LBS-weight network), and torch.optim.AdamW then streams parameter, gradient and
- * both moments through the device once more (scene/gaussian_model.py:215-226, train_ZJU.py:204-205).  Here the per-Gaussian backward
- * kernel, which holds a Gaussian's gradients in registers / LDS when it finishes, applies the AdamW update of the tensors named in
- * opt->tensors itself: the parameters (= the op's inputs, hence not const here) are updated in place, the moments in
- * opt->exp_avg / exp_avg_sq, and the gradient of an updated tensor need not be written at all (its dL_d* pointer may be NULL).
- * Same arithmetic, bit for bit, as moss_adamw_flat_devstep on the same values (both use csrc/adamw.h); a frame that overflowed its
- * capacity (asynchronous forward) takes no step, like moss_adamw_flat_guarded on the frame's status word.
- *   Requirements: raw_flags contains MOSS_RAW_OPACITY | MOSS_RAW_SCALE | MOSS_RAW_ROTATION (the inputs must be the parameters
- *   themselves, not activated copies); MOSS_OPT_SH needs M == 16 and 16-byte aligned shs / moments; MOSS_OPT_MEANS only if the
- *   means the op sees are the parameter (no transforms, or MOSS_RAW_POSE) and nothing else contributes to its gradient.
- *   opt->step_state: moss_adamw_state_bytes() zeroed device bytes owned by this optimizer (not shared with a moss_adamw_flat_* call
- *   of the same step: each launch that is given the block advances the count).
- * opt == NULL or opt->tensors == 0: exactly moss_raster_backward_raw.
- */
 #define MOSS_OPT_MEANS 1
 #define MOSS_OPT_SH 2
 #define MOSS_OPT_OPACITY 4
@@ -580,18 +516,46 @@ typedef struct moss_fused_adamw {
     int32_t sh_inactive_zero;    /* != 0: the caller also knows those parameters to be exactly ZERO (features_rest starts as zeros,
                                   * scene/gaussian_model.py:179-181; 0 x decay = 0): they are not read or written at all */
 } moss_fused_adamw;
-int moss_raster_backward_raw_adamw(
-    int P, int D, int M, int R,
-    const float* background, int width, int height,
-    float* means3D, float* shs, const float* colors_precomp, float* opacities,
-    float* scales, float scale_modifier, float* rotations, const float* transforms, const float* translation,
-    const float* viewmatrix, const float* projmatrix, const float* campos,
-    float tan_fovx, float tan_fovy,
-    char* geom_buffer, char* binning_buffer, char* image_buffer,
-    const float* dL_dpix, const float* dL_ddepths, const float* dL_dalphas,
-    float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
-    float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, float* dL_dtransforms, float* dL_dtranslation,
-    const moss_fused_adamw* opt, int raw_flags, int debug, void* stream);
+
+typedef struct moss_raster_forward_args {
+    moss_alloc_fn geometry_alloc; void* geometry_user;
+    moss_alloc_fn binning_alloc; void* binning_user;
+    moss_alloc_fn image_alloc; void* image_user;
+    int P, D, M;
+    const float* background; int width, height;
+    const float* means3D; const float* shs; const float* colors_precomp; const float* opacities;
+    const float* scales; float scale_modifier; const float* rotations; const float* cov3D_precomp;
+    const float* viewmatrix; const float* projmatrix; const float* cam_pos;
+    float tan_fovx, tan_fovy; int prefiltered;
+    float* out_color; float* out_depth; float* out_alpha; int* radii;
+    int debug;
+    /* extensions */
+    const float* transforms; const float* translation; int raw_flags;
+    int capacity; char* frame_state;
+} moss_raster_forward_args;
+/* Returns num_rendered (capacity < 0) or `capacity` (> 0), or a negative error code. */
+int moss_raster_forward_ex(const moss_raster_forward_args* args, void* stream);
+
+typedef struct moss_raster_backward_args {
+    int P, D, M, R;
+    const float* background; int width, height;
+    const float* means3D; const float* shs; const float* colors_precomp;
+    const float* scales; float scale_modifier; const float* rotations; const float* cov3D_precomp;
+    const float* viewmatrix; const float* projmatrix; const float* campos;
+    float tan_fovx, tan_fovy;
+    char* geom_buffer; char* binning_buffer; char* image_buffer;
+    const float* dL_dpix; const float* dL_ddepths; const float* dL_dalphas;
+    float* dL_dmean2D; float* dL_dconic; float* dL_dopacity; float* dL_dcolor; float* dL_dmean3D;
+    float* dL_dcov3D; float* dL_dsh; float* dL_dscale; float* dL_drot;
+    int debug;
+    /* extensions */
+    const float* transforms; const float* translation; const float* opacities;
+    float* dL_dtransforms; float* dL_dtranslation;
+    int raw_flags;
+    const moss_fused_adamw* opt;
+} moss_raster_backward_args;
+/* Returns 0 or a negative error code. */
+int moss_raster_backward_ex(const moss_raster_backward_args* args, void* stream);
 
 /*
  * Gaussian parameter activations, forward and backward, one launch each (the rasterizer-facing getters of MOSS's GaussianModel,

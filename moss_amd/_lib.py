@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_DIR = os.path.join(_HERE, os.environ.get("MOSS_AMD_LIB_DIR", "lib"))
 LIB_PATH = os.path.join(_LIB_DIR, "libmoss_raster.so")
 EXT_PATH = os.path.join(_LIB_DIR, "_moss_C.so")          # the compiled PyTorch extension (csrc/torch_binding.cpp) over the same C ABI
-ABI_VERSION = 6                                          # include/moss_raster.h MOSS_ABI_VERSION this binding was written against
+ABI_VERSION = 7                                          # include/moss_raster.h MOSS_ABI_VERSION this binding was written against
 
 ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)
 
@@ -45,60 +45,9 @@ def _declare(lib):
     lib.moss_raster_frame_state_bytes.argtypes = [_i, _i]
     lib.moss_build_has_diagnostics.restype = _i
     lib.moss_adamw_state_bytes.restype = C.c_size_t
-    lib.moss_raster_forward.restype = _i
-    lib.moss_raster_forward.argtypes = [
-        ALLOC_FN, _p, ALLOC_FN, _p, ALLOC_FN, _p,          # geometry / binning / image allocators
-        _i, _i, _i,                                        # P, D, M
-        _p, _i, _i,                                        # background, width, height
-        _p, _p, _p, _p,                                    # means3D, shs, colors_precomp, opacities
-        _p, _f, _p, _p,                                    # scales, scale_modifier, rotations, cov3D_precomp
-        _p, _p, _p,                                        # viewmatrix, projmatrix, cam_pos
-        _f, _f, _i,                                        # tan_fovx, tan_fovy, prefiltered
-        _p, _p, _p, _p, _i, _p]                            # out_color, out_depth, out_alpha, radii, debug, stream
-    _fwd = list(lib.moss_raster_forward.argtypes)
-    lib.moss_raster_forward_async.restype = _i
-    lib.moss_raster_forward_async.argtypes = _fwd[:-1] + [_p, _p]                         # debug -> capacity (both int), frame_state, stream
-    lib.moss_raster_forward_tf.restype = _i
-    lib.moss_raster_forward_tf.argtypes = _fwd[:-1] + [_p, _p]                            # cov3D_precomp -> transforms, debug -> capacity, frame_state
-    lib.moss_raster_backward_tf.restype = _i
-    lib.moss_raster_backward_tf.argtypes = [
-        _i, _i, _i, _i,                                    # P, D, M, R
-        _p, _i, _i,                                        # background, width, height
-        _p, _p, _p,                                        # means3D, shs, colors_precomp
-        _p, _f, _p, _p,                                    # scales, scale_modifier, rotations, transforms
-        _p, _p, _p, _f, _f,                                # viewmatrix, projmatrix, campos, tan_fovx, tan_fovy
-        _p, _p, _p,                                        # geom, binning, image buffers
-        _p, _p, _p,                                        # dL_dpix, dL_ddepths, dL_dalphas
-        _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,            # dL_dmean2D .. dL_drot, dL_dtransforms
-        _p]                                                # stream
     lib.moss_raster_read_status.restype = _i
     lib.moss_raster_read_status.argtypes = [_p, _p, _p]
-    lib.moss_raster_backward.restype = _i
-    lib.moss_raster_backward.argtypes = [
-        _i, _i, _i, _i,                                    # P, D, M, R
-        _p, _i, _i,                                        # background, width, height
-        _p, _p, _p, _p,                                    # means3D, shs, colors_precomp, alphas
-        _p, _f, _p, _p,                                    # scales, scale_modifier, rotations, cov3D_precomp
-        _p, _p, _p, _f, _f,                                # viewmatrix, projmatrix, campos, tan_fovx, tan_fovy
-        _p, _p, _p, _p,                                    # radii, geom, binning, image buffers
-        _p, _p, _p,                                        # dL_dpix, dL_ddepths, dL_dalphas
-        _p, _p, _p, _p, _p, _p, _p, _p, _p,                # dL_dmean2D .. dL_drot
-        _i, _p]                                            # debug, stream
-    lib.moss_raster_forward_raw.restype = _i
-    lib.moss_raster_forward_raw.argtypes = [
-        ALLOC_FN, _p, ALLOC_FN, _p, ALLOC_FN, _p, _i, _i, _i, _p, _i, _i,
-        _p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _p, _f, _f, _i,
-        _p, _p, _p, _p, _i, _i, _p, _p]                     # ..., radii, raw_flags, capacity, frame_state, stream
-    lib.moss_raster_backward_raw.restype = _i
-    lib.moss_raster_backward_raw.argtypes = [
-        _i, _i, _i, _i, _p, _i, _i,
-        _p, _p, _p, _p, _p, _f, _p, _p,                     # means3D, shs, colors, opacities, scales, mod, rotations, transforms
-        _p, _p, _p, _f, _f,
-        _p, _p, _p, _p, _p, _p,
-        _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p]     # 10 gradient outputs, raw_flags, stream
     lib.moss_raster_mark_visible.restype = _i
-    lib.moss_raster_backward_raw_adamw.restype = _i
-    lib.moss_raster_backward_raw_adamw.argtypes = list(lib.moss_raster_backward_raw.argtypes[:-3]) + [_p] + list(lib.moss_raster_backward_raw.argtypes[-3:])
     lib.moss_raster_mark_visible.argtypes = [_i, _p, _p, _p, _p, _p]
     lib.moss_knn_workspace_bytes.restype = C.c_size_t
     lib.moss_knn_workspace_bytes.argtypes = [_i]
@@ -132,14 +81,6 @@ def _declare(lib):
     lib.moss_eval_metrics.argtypes = [_p, _p]
     lib.moss_photometric_loss_roi.restype = _i
     lib.moss_photometric_loss_roi.argtypes = [_i, _i, _i, _p, _p, _p, _p, _p, _p, _f, _f, _f, _p, _p, _p, _p, C.c_size_t, _p]
-    lib.moss_adamw_flat.restype = _i
-    lib.moss_adamw_flat.argtypes = [C.c_longlong, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _d, _d, _f, _f, _i, _p]
-    lib.moss_adamw_flat_devstep.restype = _i
-    lib.moss_adamw_flat_devstep.argtypes = [C.c_longlong, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _d, _d, _f, _f, _p, _p]
-    lib.moss_adamw_flat_range.restype = _i
-    lib.moss_adamw_flat_range.argtypes = [C.c_longlong, C.c_longlong, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _d, _d, _f, _f, _i, _p, _p]
-    lib.moss_adamw_flat_guarded.restype = _i
-    lib.moss_adamw_flat_guarded.argtypes = [C.c_longlong, C.c_longlong, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _d, _d, _f, _f, _p, _p, C.c_uint32, _p]
     lib.moss_adamw_flat_ex.restype = _i
     lib.moss_adamw_flat_ex.argtypes = [_p, _p]
     lib.moss_gaussian_activate_forward.restype = _i
@@ -157,7 +98,7 @@ def _declare(lib):
 
 
 class FusedAdamWStruct(C.Structure):
-    """``moss_fused_adamw`` of include/moss_raster.h (host struct handed to ``moss_raster_backward_raw_adamw``)."""
+    """``moss_fused_adamw`` of include/moss_raster.h (host struct handed to ``moss_raster_backward_ex`` as ``opt``, through the extension)."""
     _fields_ = [("tensors", C.c_uint32), ("exp_avg", C.c_void_p * 5), ("exp_avg_sq", C.c_void_p * 5), ("lr", C.c_float * 5),
                 ("lr_sh_rest", C.c_float), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_float), ("weight_decay", C.c_float),
                 ("step_state", C.c_void_p), ("lr_segment", C.c_int32 * 5), ("sh_active_degree", C.c_int32), ("sh_inactive_zero", C.c_int32)]

@@ -1,5 +1,5 @@
 // adamw.h -- the AdamW element update and the device-resident step counter, shared by the flat update kernel (optim.hip) and by the
-// per-Gaussian backward kernel when it applies the update itself (preprocess.hip, moss_raster_backward_raw_adamw).  Both must give
+// per-Gaussian backward kernel when it applies the update itself (preprocess.hip, moss_raster_backward_ex with `opt`).  Both must give
 // the same bits for the same inputs whatever their translation unit's contraction flags, so every rounding is spelled out.
 // Semantics = torch.optim.AdamW (amsgrad=False, maximize=False): decoupled weight decay, bias-corrected moments
 // (MOSS: scene/gaussian_model.py:215-226).

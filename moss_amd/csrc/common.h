@@ -324,7 +324,7 @@ struct BinView {
 
 // Per-call constants.  The camera matrices stay on the device (the boundary hands over device pointers, exactly
 // like the reference); kernels read them through wave-uniform (scalar) loads, so no host copy / sync is needed.
-// `raw` bits of FrameParams (moss_raster_forward_raw / _backward_raw): the GaussianModel getters applied inside preprocess
+// `raw` bits of FrameParams (moss_raster_*_args.raw_flags): the GaussianModel getters applied inside preprocess
 constexpr int RAW_OPACITY = 1;      // opacities are logits:            get_opacity  = sigmoid(_opacity)          (scene/gaussian_model.py:160-161)
 constexpr int RAW_SCALE = 2;        // scales are logarithms:           get_scaling  = exp(_scaling)              (:142-143)
 constexpr int HINT_SPATIAL_ORDER = 8; // (not a raw-parameter bit) index neighbours are spatial neighbours: include/moss_raster.h

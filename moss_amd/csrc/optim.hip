@@ -26,10 +26,10 @@ adamw_kernel(long long n, float* __restrict__ p, const float* __restrict__ g, fl
              Segs segs, AdamBetas betas, float eps, float weight_decay, float bc1, float bc2_sqrt,
              const float* __restrict__ step_state, long long first, const uint32_t* __restrict__ skip_word, uint32_t skip_mask, MoreGrads more)
 {
-    // guard (moss_adamw_flat_guarded): a dropped frame's step is a no-op -- nothing is read or written, the step counter stays
+    // guard (moss_adamw_flat_args.skip_word): a dropped frame's step is a no-op -- nothing is read or written, the step counter stays
     if (skip_word != nullptr && (*skip_word & skip_mask) != 0u) return;
     // `first`: the arrays are the elements [first, first + n) of the flat buffers the segment table indexes (a rank's shard of the
-    // bucket, moss_adamw_flat_range); a multiple of 4, so that a thread's four elements never straddle it.
+    // bucket, moss_adamw_flat_args.first); a multiple of 4, so that a thread's four elements never straddle it.
     // (the step count and the learning-rate flag are requested together: one scalar round trip at the kernel's start, not two)
     int t_prev = 0, lr_flag = 0;
     if (step_state) { t_prev = reinterpret_cast<const int*>(step_state)[0]; lr_flag = reinterpret_cast<const int*>(step_state)[ADAMW_LR_VALID_WORD]; }
@@ -185,7 +185,7 @@ int launch_adamw(long long n, float* params, const float* grads, float* exp_avg,
 // ---- SEVERAL parameter tensors with buffers of their own in ONE launch (moss_adamw_multi): the torch-state drop-in optimizer
 // (moss_amd.optim.AdamW, MOSS's six single-tensor Gaussian groups -- scene/gaussian_model.py:215-226) took one launch per tensor: six
 // launches and six host calls per step of a call pattern that is bound by the host.  Same arithmetic per element as adamw_kernel
-// (adamw_element, the same bias corrections from the tensor's own step count): bit-identical to six moss_adamw_flat calls.
+// (adamw_element, the same bias corrections from the tensor's own step count): bit-identical to six moss_adamw_flat_ex calls.
 struct MultiT {
     int n;
     float* p[8]; const float* g[8]; float* m[8]; float* v[8];
@@ -247,7 +247,7 @@ extern "C" int moss_adamw_multi(const moss_adamw_multi_args* a, void* stream)
         if ((((uintptr_t)a->params[t]) | ((uintptr_t)a->grads[t]) | ((uintptr_t)a->exp_avg[t]) | ((uintptr_t)a->exp_avg_sq[t])) & 15u) return MOSS_ERR_INVALID_ARG;
         const int k = T.n++;
         T.p[k] = a->params[t]; T.g[k] = a->grads[t]; T.m[k] = a->exp_avg[t]; T.v[k] = a->exp_avg_sq[t]; T.numel[k] = n; T.lr[k] = a->lr[t];
-        // (the corrections exactly as moss_adamw_flat forms them: doubles, rounded once)
+        // (the corrections exactly as moss_adamw_flat_ex forms them from a host-side step: doubles, rounded once)
         T.bc1[k] = (float)(1.0 - pow(a->beta1, a->step[t])); T.bc2_sqrt[k] = (float)sqrt(1.0 - pow(a->beta2, a->step[t]));
         long long b = (n / 4 + 255) / 256;
         if (b > 1024) b = 1024;
@@ -259,71 +259,12 @@ extern "C" int moss_adamw_multi(const moss_adamw_multi_args* a, void* stream)
     return hipGetLastError() == hipSuccess ? 0 : MOSS_ERR_HIP;
 }
 
-extern "C" int moss_adamw_flat(long long n, float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
-                               int num_segments, const long long* segment_end, const float* segment_lr,
-                               const int* segment_period, const int* segment_split, const float* segment_lr2,
-                               double beta1, double beta2, float eps, float weight_decay, int step, void* stream)
-{
-    if (n < 0 || num_segments < 1 || num_segments > 8 || !params || !grads || !exp_avg || !exp_avg_sq || !segment_end || !segment_lr || step < 1)
-        return MOSS_ERR_INVALID_ARG;
-    if (n == 0) return 0;
-    const double bc1 = 1.0 - pow(beta1, step), bc2 = 1.0 - pow(beta2, step);
-    return moss::launch_adamw(n, params, grads, exp_avg, exp_avg_sq, num_segments, segment_end, segment_lr, segment_period,
-                              segment_split, segment_lr2, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), nullptr,
-                              (hipStream_t)stream);
-}
-
-extern "C" int moss_adamw_flat_devstep(long long n, float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
-                                       int num_segments, const long long* segment_end, const float* segment_lr,
-                                       const int* segment_period, const int* segment_split, const float* segment_lr2,
-                                       double beta1, double beta2, float eps, float weight_decay, void* step_state, void* stream)
-{
-    if (n < 0 || num_segments < 1 || num_segments > 8 || !params || !grads || !exp_avg || !exp_avg_sq || !segment_end || !segment_lr || !step_state)
-        return MOSS_ERR_INVALID_ARG;
-    if (n == 0) return MOSS_ERR_INVALID_ARG;                 // the counter advances inside the update kernel: nothing to launch
-    return moss::launch_adamw(n, params, grads, exp_avg, exp_avg_sq, num_segments, segment_end, segment_lr, segment_period,
-                              segment_split, segment_lr2, beta1, beta2, eps, weight_decay, 1.f, 1.f, (const float*)step_state,
-                              (hipStream_t)stream);
-}
-
 static_assert(moss::ADAMW_LR_VALID_WORD == MOSS_ADAMW_LR_VALID_WORD && moss::ADAMW_LR_WORD0 == MOSS_ADAMW_LR_WORD0 && moss::ADAMW_LR2_WORD0 == MOSS_ADAMW_LR2_WORD0, "adamw.h and the header disagree");
 static_assert(moss::ADAMW_STATE_WORDS * 4 <= MOSS_ADAMW_STATE_BYTES, "the step-state block of adamw.h must fit the size the header promises");
 extern "C" size_t moss_adamw_state_bytes(void) { return MOSS_ADAMW_STATE_BYTES; }
 
-// A rank's SHARD of the flat bucket (reduce-scatter -> AdamW on 1/N of the elements -> all-gather of the parameters, moss_amd/dist.py):
-// the arrays hold the elements [first, first + count) of the flat buffers the segment table (global indices) describes.
-extern "C" int moss_adamw_flat_range(long long first, long long count, float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
-                                     int num_segments, const long long* segment_end, const float* segment_lr,
-                                     const int* segment_period, const int* segment_split, const float* segment_lr2,
-                                     double beta1, double beta2, float eps, float weight_decay, int step, void* step_state, void* stream)
-{
-    if (first < 0 || (first & 3) || count < 0 || num_segments < 1 || num_segments > 8 || !params || !grads || !exp_avg || !exp_avg_sq ||
-        !segment_end || !segment_lr || (!step_state && step < 1))
-        return MOSS_ERR_INVALID_ARG;
-    if (count == 0) return step_state ? MOSS_ERR_INVALID_ARG : 0;
-    const double bc1 = step_state ? 1.0 : 1.0 - pow(beta1, step), bc2 = step_state ? 1.0 : 1.0 - pow(beta2, step);
-    return moss::launch_adamw(count, params, grads, exp_avg, exp_avg_sq, num_segments, segment_end, segment_lr, segment_period,
-                              segment_split, segment_lr2, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2),
-                              (const float*)step_state, (hipStream_t)stream, first);
-}
-
-extern "C" int moss_adamw_flat_guarded(long long first, long long count, float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
-                                       int num_segments, const long long* segment_end, const float* segment_lr,
-                                       const int* segment_period, const int* segment_split, const float* segment_lr2,
-                                       double beta1, double beta2, float eps, float weight_decay, void* step_state,
-                                       const uint32_t* skip_word, uint32_t skip_mask, void* stream)
-{
-    if (first < 0 || (first & 3) || count <= 0 || num_segments < 1 || num_segments > 8 || !params || !grads || !exp_avg || !exp_avg_sq ||
-        !segment_end || !segment_lr || !step_state || !skip_word)
-        return MOSS_ERR_INVALID_ARG;
-    return moss::launch_adamw(count, params, grads, exp_avg, exp_avg_sq, num_segments, segment_end, segment_lr, segment_period,
-                              segment_split, segment_lr2, beta1, beta2, eps, weight_decay, 1.f, 1.f, (const float*)step_state,
-                              (hipStream_t)stream, first, skip_word, skip_mask);
-}
-
-
-// Every form of the flat update behind ONE struct (ABI 6): moss_adamw_flat (step, no step_state), _devstep (step_state), _range
-// (first / count), _guarded (skip_word) -- plus the degree-aware SH update (segment_active, inactive_zero: see Segs above).
+// Every form of the flat update behind ONE struct (ABI 6; the only one since ABI 7): host-side step or step_state, a shard (first /
+// count), the guard (skip_word) -- plus the degree-aware SH update (segment_active, inactive_zero: see Segs above).
 extern "C" int moss_adamw_flat_ex(const moss_adamw_flat_args* a, void* stream)
 {
     if (!a || a->first < 0 || (a->first & 3) || a->count < 0 || a->num_segments < 1 || a->num_segments > 8 || !a->params || !a->grads ||

@@ -828,7 +828,7 @@ __device__ __forceinline__ void coop_gather(bool is_big, uint32_t c0, uint32_t c
 constexpr int SH_ROW = 49;
 constexpr int GATHER_CAP = 320;                          // records of a wave gathered per pass (5 rows of 64; 384: no gain, round 5)
 constexpr int GATHER_WORDS = GATHER_CAP + 64 * 9;        // per wave: the descriptor list + one row of scanned values
-// FUSED: the kernel also takes the AdamW step of the parameters named in fa.tensors (moss_raster_backward_raw_adamw) -- an
+// FUSED: the kernel also takes the AdamW step of the parameters named in fa.tensors (moss_raster_backward_ex with `opt`) -- an
 // instantiation of its own, so that the plain backward keeps its code and registers and a kernel trace tells the two apart.
 // (amdgpu_waves_per_eu(2): TWO waves per SIMD = at most 256 VGPRs.  The fused instantiation needs ~254 and the register allocator's own
 // choice flips between 254 and 280-330 -- one wave per SIMD: 38 -> 54 us -- with unrelated edits of this file; stated, it is a bound)
@@ -989,7 +989,7 @@ preprocess_backward_kernel(int P, int D, int M, float tan_fovx, float tan_fovy, 
     // (likewise after a forward that was told MOSS_FORWARD_ONLY: no backward state exists, the binning buffer has no record pool)
     const bool visible = n_inst > 0 && !(hdr_flags & (ERRFLAG_OVERFLOW | ERRFLAG_FORWARD_ONLY));
     // a frame that overflowed its capacity rendered nothing: its optimizer step is a no-op (parameters, moments and the step count
-    // stay bit for bit), like moss_adamw_flat_guarded on the frame's status word
+    // stay bit for bit), like moss_adamw_flat_ex guarded by the frame's status word
     const bool fa_on = FUSED && !(hdr_flags & (ERRFLAG_OVERFLOW | ERRFLAG_FORWARD_ONLY));
 
     // Sum the Gaussian's gradient records: the cells of its run [c0, c1) in the record pool whose validity bit is set (common.h:

@@ -132,70 +132,70 @@ FrameParams make_params(int P, int D, int M, int W, int H, float tan_fovx, float
 
 }  // namespace
 
-static int forward_impl(
-    moss_alloc_fn geometry_alloc, void* geometry_user,
-    moss_alloc_fn binning_alloc, void* binning_user,
-    moss_alloc_fn image_alloc, void* image_user,
-    int P, int D, int M,
-    const float* background, int width, int height,
-    const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
-    const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
-    const float* viewmatrix, const float* projmatrix, const float* cam_pos,
-    float tan_fovx, float tan_fovy, int prefiltered,
-    float* out_color, float* out_depth, float* out_alpha, int* radii, int debug_flags, void* stream, long long capacity,
-    const float* transforms, int raw_flags = 0, char* frame_state = nullptr, const float* translation = nullptr)
+// The forward of every form of the call (include/moss_raster.h: moss_raster_forward_args).  The argument rules of the extensions are
+// checked here, once.
+static int forward_impl(const moss_raster_forward_args& a, void* stream)
 {
+    if (a.capacity == 0) return fail(MOSS_ERR_INVALID_ARG, "capacity 0: pass > 0 (asynchronous) or < 0 (synchronous)");
+    if (a.capacity > 0 && (a.debug & MOSS_DEBUG_SYNC)) return fail(MOSS_ERR_INVALID_ARG, "MOSS_DEBUG_SYNC needs the synchronous forward (capacity < 0)");
+    if (a.raw_flags & ~(RAW_OPACITY | RAW_SCALE | RAW_ROTATION | HINT_SPATIAL_ORDER | RAW_POSE)) return fail(MOSS_ERR_INVALID_ARG, "unknown raw_flags bits");
+    if (a.cov3D_precomp && (a.transforms || a.raw_flags)) return fail(MOSS_ERR_INVALID_ARG, "transforms and raw_flags exclude cov3D_precomp");
+    if (a.P > 0 && (a.transforms || a.raw_flags) && (!a.scales || !a.rotations))
+        return fail(MOSS_ERR_INVALID_ARG, "transforms and raw_flags need scales and rotations");
+    if (a.P > 0 && (a.raw_flags & RAW_POSE) && !a.transforms) return fail(MOSS_ERR_INVALID_ARG, "MOSS_RAW_POSE needs the transforms");
+    if (a.translation && !(a.raw_flags & RAW_POSE)) return fail(MOSS_ERR_INVALID_ARG, "a translation comes with MOSS_RAW_POSE");
+    const long long capacity = a.capacity < 0 ? -1 : a.capacity;
     g_err[0] = 0;
     hipStream_t s = (hipStream_t)stream;
-    const int debug = debug_flags & MOSS_DEBUG_SYNC;
-    if (P < 0 || width <= 0 || height <= 0) return fail(MOSS_ERR_INVALID_ARG, "bad sizes P=%d W=%d H=%d", P, width, height);
-    if (!out_color || !out_depth || !out_alpha || !background) return fail(MOSS_ERR_INVALID_ARG, "null output/background pointer");
-    if (!geometry_alloc || !binning_alloc || !image_alloc) return fail(MOSS_ERR_INVALID_ARG, "null allocator callback");
-    if ((width + TILE - 1) / TILE > 65535 || (height + TILE - 1) / TILE > 65535) return fail(MOSS_ERR_UNSUPPORTED, "image too large");
-    const size_t N = (size_t)width * height;
+    const int debug = a.debug & MOSS_DEBUG_SYNC;
+    if (a.P < 0 || a.width <= 0 || a.height <= 0) return fail(MOSS_ERR_INVALID_ARG, "bad sizes P=%d W=%d H=%d", a.P, a.width, a.height);
+    if (!a.out_color || !a.out_depth || !a.out_alpha || !a.background) return fail(MOSS_ERR_INVALID_ARG, "null output/background pointer");
+    if (!a.geometry_alloc || !a.binning_alloc || !a.image_alloc) return fail(MOSS_ERR_INVALID_ARG, "null allocator callback");
+    if ((a.width + TILE - 1) / TILE > 65535 || (a.height + TILE - 1) / TILE > 65535) return fail(MOSS_ERR_UNSUPPORTED, "image too large");
+    const size_t N = (size_t)a.width * a.height;
 
-    if (P == 0) {
+    if (a.P == 0) {
         // rasterize_points.cu:68-83: zero-filled outputs, nothing else happens.  (Outputs here are caller-allocated
         // and possibly uninitialised, so fill them; the background is NOT composited in the reference either.)
         // (with kernels, not hipMemsetAsync: memset nodes did not re-execute on hipGraph replay with ROCm 7.2, see launch_clear)
-        launch_zero_floats(out_color, 3 * N, s);
-        launch_zero_floats(out_depth, N, s);
-        launch_zero_floats(out_alpha, N, s);
+        launch_zero_floats(a.out_color, 3 * N, s);
+        launch_zero_floats(a.out_depth, N, s);
+        launch_zero_floats(a.out_alpha, N, s);
         HIP_TRY(hipGetLastError());
         return 0;
     }
-    if (!means3D || !opacities || !viewmatrix || !projmatrix || !cam_pos) return fail(MOSS_ERR_INVALID_ARG, "null required input");
-    if (!colors_precomp && !shs) return fail(MOSS_ERR_UNSUPPORTED, "provide SHs or precomputed colours");
-    if (!colors_precomp && (M <= 0 || (D + 1) * (D + 1) > M || D < 0 || D > 3)) return fail(MOSS_ERR_INVALID_ARG, "SH degree %d does not fit M=%d", D, M);
-    if (!cov3D_precomp && (!scales || !rotations)) return fail(MOSS_ERR_INVALID_ARG, "provide scales+rotations or cov3D_precomp");
+    if (!a.means3D || !a.opacities || !a.viewmatrix || !a.projmatrix || !a.cam_pos) return fail(MOSS_ERR_INVALID_ARG, "null required input");
+    if (!a.colors_precomp && !a.shs) return fail(MOSS_ERR_UNSUPPORTED, "provide SHs or precomputed colours");
+    if (!a.colors_precomp && (a.M <= 0 || (a.D + 1) * (a.D + 1) > a.M || a.D < 0 || a.D > 3)) return fail(MOSS_ERR_INVALID_ARG, "SH degree %d does not fit M=%d", a.D, a.M);
+    if (!a.cov3D_precomp && (!a.scales || !a.rotations)) return fail(MOSS_ERR_INVALID_ARG, "provide scales+rotations or cov3D_precomp");
 
-    char* geom_ptr = geometry_alloc(geometry_user, GeomView::bytes(P));
+    char* geom_ptr = a.geometry_alloc(a.geometry_user, GeomView::bytes(a.P));
     if (!geom_ptr) return fail(MOSS_ERR_ALLOC, "geometry allocator returned NULL");
-    char* img_ptr = image_alloc(image_user, ImageView::bytes(width, height));
+    char* img_ptr = a.image_alloc(a.image_user, ImageView::bytes(a.width, a.height));
     if (!img_ptr) return fail(MOSS_ERR_ALLOC, "image allocator returned NULL");
-    GeomView g = GeomView::at(geom_ptr, P);
-    ImageView im = ImageView::at(img_ptr, width, height);
-    FrameParams fp = make_params(P, D, M, width, height, tan_fovx, tan_fovy, scale_modifier, prefiltered,
-                                 viewmatrix, projmatrix, cam_pos, background);
-    fp.raw = cov3D_precomp ? (raw_flags & RAW_OPACITY) : raw_flags;     // scales / rotations are not read with a precomputed covariance
-    fp.no_block_cull = (debug_flags & MOSS_DEBUG_NO_BLOCK_CULL) ? 1 : 0;
-    fp.exact_math = (debug_flags & MOSS_DEBUG_EXACT_MATH) ? 1 : 0;
+    GeomView g = GeomView::at(geom_ptr, a.P);
+    ImageView im = ImageView::at(img_ptr, a.width, a.height);
+    FrameParams fp = make_params(a.P, a.D, a.M, a.width, a.height, a.tan_fovx, a.tan_fovy, a.scale_modifier, a.prefiltered,
+                                 a.viewmatrix, a.projmatrix, a.cam_pos, a.background);
+    fp.raw = a.raw_flags;
+    fp.no_block_cull = (a.debug & MOSS_DEBUG_NO_BLOCK_CULL) ? 1 : 0;
+    fp.exact_math = (a.debug & MOSS_DEBUG_EXACT_MATH) ? 1 : 0;
     // MOSS_FORWARD_ONLY: an evaluation render (render_ZJU.py:56-72) -- the caller promises that no backward follows.  Same images, bit for
     // bit; no depth-segment state, no gradient-record cells, no validity bits, and a binning buffer of 62 B per instance (ids, block
     // masks, records, sort keys) instead of ~370.  The keys then take the scan -> scatter chain into exact ranges (the per-tile buckets
     // of the training forward live in the record pool's address space, which this buffer does not have).
-    const bool fwd_only = (debug_flags & MOSS_FORWARD_ONLY) != 0;
+    const bool fwd_only = (a.debug & MOSS_FORWARD_ONLY) != 0;
     fp.forward_only = fwd_only ? 1 : 0;
-    const bool trace = (debug_flags & MOSS_DEBUG_TRACE) != 0;
+    const bool trace = (a.debug & MOSS_DEBUG_TRACE) != 0;
     const int T = fp.gx * fp.gy;
 
     // The counters kernels ADD to (tile histogram, tile cursors, error flags) must be zero here.  With the caller's frame state
     // (the `frame_state` argument: all-zero between calls, re-zeroed by the sort / merge kernel) nothing is launched for that; without it, a clear.
-    const size_t fs_bytes = ImageView::frame_state_bytes(width, height);
-    if (frame_state) im.use_frame_state(frame_state, width, height);
+    const size_t fs_bytes = ImageView::frame_state_bytes(a.width, a.height);
+    if (a.frame_state) im.use_frame_state(a.frame_state, a.width, a.height);
     else launch_clear(im.header, im.clear_bytes(), s);                   // header + tile histogram + tile cursors
     // (a forward that ends before its sort kernel has run leaves the frame state dirty: clean it on those paths)
-    auto abandon_frame_state = [&]() { if (frame_state) clear_frame_state(frame_state, fs_bytes, s); };
+    auto abandon_frame_state = [&]() { if (a.frame_state) clear_frame_state(a.frame_state, fs_bytes, s); };
     // Asynchronous forward with the tile histogram in LDS: the PREPROCESS kernel writes the sort keys itself, into per-tile buckets of the
     // key area (preprocess.hip, scatter mode) -- the binning buffer is sized for the caller's capacity, so it exists before the first
     // kernel -- the sort workgroups derive their chunk tables from the tile counts, and the scan rides along with the sort kernel as one
@@ -211,19 +211,19 @@ static int forward_impl(
     if (bucketed) {
         R = (int)capacity;
         total_chunks = (int)(capacity / 1024) + T;
-        bin_ptr = binning_alloc(binning_user, BinView::bytes(R));
+        bin_ptr = a.binning_alloc(a.binning_user, BinView::bytes(R));
         if (!bin_ptr) { abandon_frame_state(); return fail(MOSS_ERR_ALLOC, "binning allocator returned NULL"); }
         b = BinView::at(bin_ptr, R);
     }
     { StageTimer tm(MOSS_STAGE_PREPROCESS_FWD, s); TraceRange tr(trace, bucketed ? "moss:preprocess_fwd+scatter" : "moss:preprocess_fwd");
-      launch_preprocess_forward(fp, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, transforms, translation, g, im, radii, s,
+      launch_preprocess_forward(fp, a.means3D, a.shs, a.colors_precomp, a.opacities, a.scales, a.rotations, a.cov3D_precomp, a.transforms, a.translation, g, im, a.radii, s,
                                 bucketed ? b.keys : nullptr, key_stride); }
     STAGE_CHECK("preprocess");
     // (asynchronous and un-bucketed -- the MOSS_FORWARD_ONLY renders: the scan rides along with the scatter kernel, no launch of its own)
     const bool fold_scan = !bucketed && capacity >= 0 && scatter_folds_scan(fp);
     if (!bucketed) {
         if (!fold_scan) {
-            { StageTimer tm(MOSS_STAGE_SCAN, s); TraceRange tr(trace, "moss:scan"); launch_scan(P, g, im, T, capacity, s, fwd_only); }
+            { StageTimer tm(MOSS_STAGE_SCAN, s); TraceRange tr(trace, "moss:scan"); launch_scan(a.P, g, im, T, capacity, s, fwd_only); }
             STAGE_CHECK("scan");
         }
         if (capacity < 0) {
@@ -250,7 +250,7 @@ static int forward_impl(
             R = (int)capacity;
             total_chunks = (int)(capacity / 1024) + T;
         }
-        bin_ptr = binning_alloc(binning_user, BinView::bytes(R, pool_cells, fwd_only));
+        bin_ptr = a.binning_alloc(a.binning_user, BinView::bytes(R, pool_cells, fwd_only));
         if (!bin_ptr) { abandon_frame_state(); return fail(MOSS_ERR_ALLOC, "binning allocator returned NULL"); }
         b = BinView::at(bin_ptr, R, pool_cells, fwd_only);
     }
@@ -267,12 +267,12 @@ static int forward_impl(
         }
 #endif
         { StageTimer tm(MOSS_STAGE_TILE_SORT, s); TraceRange tr(trace, bucketed ? "moss:chunk_sort+scan" : "moss:chunk_sort");
-          launch_tile_sort(fp, g, im, b, R, total_chunks, s, frame_state, fs_bytes, 0, key_stride, capacity); }
+          launch_tile_sort(fp, g, im, b, R, total_chunks, s, a.frame_state, fs_bytes, 0, key_stride, capacity); }
         { StageTimer tm(MOSS_STAGE_MERGE_GATHER, s); TraceRange tr(trace, "moss:merge_gather");
-          launch_tile_sort(fp, g, im, b, R, total_chunks, s, frame_state, fs_bytes, 1, key_stride, capacity); }
+          launch_tile_sort(fp, g, im, b, R, total_chunks, s, a.frame_state, fs_bytes, 1, key_stride, capacity); }
         STAGE_CHECK("tile_sort");
     } else abandon_frame_state();                                        // (nothing rendered: no sort kernel to re-zero it)
-    { StageTimer tm(MOSS_STAGE_BLEND_FWD, s); TraceRange tr(trace, "moss:blend_fwd"); launch_blend_forward(fp, g, im, b, out_color, out_depth, out_alpha, s); }
+    { StageTimer tm(MOSS_STAGE_BLEND_FWD, s); TraceRange tr(trace, "moss:blend_fwd"); launch_blend_forward(fp, g, im, b, a.out_color, a.out_depth, a.out_alpha, s); }
     STAGE_CHECK("blend_forward");
     return R;
 }
@@ -287,44 +287,18 @@ int moss_raster_forward(
     const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered,
     float* out_color, float* out_depth, float* out_alpha, int* radii, int debug, void* stream)
 {
-    return forward_impl(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user, P, D, M, background,
-                        width, height, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp,
-                        viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color, out_depth, out_alpha, radii,
-                        debug, stream, -1, nullptr);
+    moss_raster_forward_args a = {
+        geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user, P, D, M, background, width, height,
+        means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos,
+        tan_fovx, tan_fovy, prefiltered, out_color, out_depth, out_alpha, radii, debug };
+    a.capacity = -1;                                 // synchronous; no extension
+    return forward_impl(a, stream);
 }
 
-int moss_raster_forward_async(
-    moss_alloc_fn geometry_alloc, void* geometry_user, moss_alloc_fn binning_alloc, void* binning_user,
-    moss_alloc_fn image_alloc, void* image_user, int P, int D, int M, const float* background, int width, int height,
-    const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
-    const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
-    const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered,
-    float* out_color, float* out_depth, float* out_alpha, int* radii, int capacity, char* frame_state, int debug, void* stream)
+int moss_raster_forward_ex(const moss_raster_forward_args* args, void* stream)
 {
-    if (capacity < 0) return fail(MOSS_ERR_INVALID_ARG, "capacity must be >= 0");
-    if (debug & MOSS_DEBUG_SYNC) return fail(MOSS_ERR_INVALID_ARG, "MOSS_DEBUG_SYNC needs the synchronous forward");
-    return forward_impl(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user, P, D, M, background,
-                        width, height, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp,
-                        viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color, out_depth, out_alpha, radii,
-                        debug, stream, capacity, nullptr, 0, frame_state);
-}
-
-// n2 extension: like moss_raster_forward / _async (capacity < 0: synchronous, debug off) with a per-Gaussian 3x3
-// transform applied to the scale/rotation covariance inside the op.
-int moss_raster_forward_tf(
-    moss_alloc_fn geometry_alloc, void* geometry_user, moss_alloc_fn binning_alloc, void* binning_user,
-    moss_alloc_fn image_alloc, void* image_user, int P, int D, int M, const float* background, int width, int height,
-    const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
-    const float* scales, float scale_modifier, const float* rotations, const float* transforms,
-    const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered,
-    float* out_color, float* out_depth, float* out_alpha, int* radii, int capacity, char* frame_state, int debug, void* stream)
-{
-    if (P > 0 && (!scales || !rotations || !transforms)) return fail(MOSS_ERR_INVALID_ARG, "scales, rotations and transforms are required");
-    if (capacity >= 0 && (debug & MOSS_DEBUG_SYNC)) return fail(MOSS_ERR_INVALID_ARG, "MOSS_DEBUG_SYNC needs the synchronous forward (capacity < 0)");
-    return forward_impl(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user, P, D, M, background,
-                        width, height, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, nullptr,
-                        viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color, out_depth, out_alpha, radii,
-                        debug, stream, capacity < 0 ? -1 : capacity, transforms, 0, frame_state);
+    if (!args) return fail(MOSS_ERR_INVALID_ARG, "null argument block");
+    return forward_impl(*args, stream);
 }
 
 int moss_raster_read_status(const char* image_buffer, uint32_t* host_pinned_out /* 8 words */, void* stream)
@@ -345,45 +319,42 @@ size_t moss_raster_image_bytes(int width, int height) { return ImageView::bytes(
 size_t moss_raster_binning_bytes(int R) { return BinView::bytes(R); }
 size_t moss_raster_binning_bytes_forward_only(int R) { return BinView::bytes(R, -1, true); }
 
-static int backward_impl(
-    int P, int D, int M, int R,
-    const float* background, int width, int height,
-    const float* means3D, const float* shs, const float* colors_precomp, const float* alphas,
-    const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
-    const float* viewmatrix, const float* projmatrix, const float* campos,
-    float tan_fovx, float tan_fovy, const int* radii,
-    char* geom_buffer, char* binning_buffer, char* image_buffer,
-    const float* dL_dpix, const float* dL_ddepths, const float* dL_dalphas,
-    float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
-    float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, int debug_flags, void* stream,
-    const float* transforms, float* dL_dtransforms, const float* opacities = nullptr, int raw_flags = 0,
-    const float* translation = nullptr, float* dL_dtranslation = nullptr, const moss_fused_adamw* opt = nullptr)
+// The backward of every form of the call (include/moss_raster.h: moss_raster_backward_args), with the same one-place argument rules.
+static int backward_impl(const moss_raster_backward_args& a, void* stream)
 {
-    (void)alphas; (void)radii;
-    const int debug = debug_flags & MOSS_DEBUG_SYNC;
+    if (a.raw_flags & ~(RAW_OPACITY | RAW_SCALE | RAW_ROTATION | HINT_SPATIAL_ORDER | RAW_POSE | SH_GRAD_ACTIVE_ONLY))
+        return fail(MOSS_ERR_INVALID_ARG, "unknown raw_flags bits");
+    if (a.cov3D_precomp && (a.transforms || a.raw_flags)) return fail(MOSS_ERR_INVALID_ARG, "transforms and raw_flags exclude cov3D_precomp");
+    if (a.P > 0 && (a.transforms || a.raw_flags) && (!a.scales || !a.rotations))
+        return fail(MOSS_ERR_INVALID_ARG, "transforms and raw_flags need scales and rotations");
+    if (a.P > 0 && a.transforms && !a.dL_dtransforms) return fail(MOSS_ERR_INVALID_ARG, "transforms need dL_dtransforms");
+    if (a.P > 0 && (a.raw_flags & RAW_POSE) && !a.transforms) return fail(MOSS_ERR_INVALID_ARG, "MOSS_RAW_POSE needs the transforms");
+    if ((a.translation || a.dL_dtranslation) && !(a.raw_flags & RAW_POSE)) return fail(MOSS_ERR_INVALID_ARG, "a translation comes with MOSS_RAW_POSE");
+    const moss_fused_adamw* opt = (a.opt && a.opt->tensors) ? a.opt : nullptr;
+    const int debug = a.debug & MOSS_DEBUG_SYNC;
     g_err[0] = 0;
     hipStream_t s = (hipStream_t)stream;
-    if (P < 0 || R < 0 || width <= 0 || height <= 0) return fail(MOSS_ERR_INVALID_ARG, "bad sizes");
-    if (P == 0) return 0;                                                 // rasterize_points.cu:168
-    if (!geom_buffer || !binning_buffer || !image_buffer) return fail(MOSS_ERR_INVALID_ARG, "null scratch buffer");
-    if (!dL_dpix && !dL_ddepths && !dL_dalphas) return fail(MOSS_ERR_INVALID_ARG, "all three incoming gradients are NULL");
+    if (a.P < 0 || a.R < 0 || a.width <= 0 || a.height <= 0) return fail(MOSS_ERR_INVALID_ARG, "bad sizes");
+    if (a.P == 0) return 0;                                                 // rasterize_points.cu:168
+    if (!a.geom_buffer || !a.binning_buffer || !a.image_buffer) return fail(MOSS_ERR_INVALID_ARG, "null scratch buffer");
+    if (!a.dL_dpix && !a.dL_ddepths && !a.dL_dalphas) return fail(MOSS_ERR_INVALID_ARG, "all three incoming gradients are NULL");
     // (the gradient of a tensor whose AdamW update this call applies itself may stay inside the kernel)
     const uint32_t fused = opt ? opt->tensors : 0u;
     // dL_dconic (an intermediate the reference also exposes), dL_dcolor and dL_dcov3D (gradients of the OPTIONAL inputs colors_precomp /
     // cov3D_precomp) may be NULL = not wanted: 52 bytes per Gaussian that a caller working from SH and scales / rotations never reads
-    if (!dL_dmean2D || (!dL_dopacity && !(fused & OPT_OPACITY)) || (!dL_dmean3D && !(fused & OPT_MEANS)) ||
-        (!dL_dscale && !(fused & OPT_SCALES)) || (!dL_drot && !(fused & OPT_ROTATIONS)))
+    if (!a.dL_dmean2D || (!a.dL_dopacity && !(fused & OPT_OPACITY)) || (!a.dL_dmean3D && !(fused & OPT_MEANS)) ||
+        (!a.dL_dscale && !(fused & OPT_SCALES)) || (!a.dL_drot && !(fused & OPT_ROTATIONS)))
         return fail(MOSS_ERR_INVALID_ARG, "null gradient output");
-    if (shs && !dL_dsh && !(fused & OPT_SH)) return fail(MOSS_ERR_INVALID_ARG, "dL_dsh is NULL although shs is given");
+    if (a.shs && !a.dL_dsh && !(fused & OPT_SH)) return fail(MOSS_ERR_INVALID_ARG, "dL_dsh is NULL although shs is given");
     FusedAdam fa;
     if (fused) {
         if (fused & ~(OPT_MEANS | OPT_SH | OPT_OPACITY | OPT_SCALES | OPT_ROTATIONS)) return fail(MOSS_ERR_INVALID_ARG, "unknown bits in moss_fused_adamw.tensors");
-        if ((raw_flags & (RAW_OPACITY | RAW_SCALE | RAW_ROTATION)) != (RAW_OPACITY | RAW_SCALE | RAW_ROTATION) || cov3D_precomp)
+        if ((a.raw_flags & (RAW_OPACITY | RAW_SCALE | RAW_ROTATION)) != (RAW_OPACITY | RAW_SCALE | RAW_ROTATION))
             return fail(MOSS_ERR_INVALID_ARG, "the fused AdamW update works on the raw parameters: MOSS_RAW_OPACITY | MOSS_RAW_SCALE | MOSS_RAW_ROTATION");
-        if ((fused & OPT_MEANS) && transforms && !(raw_flags & RAW_POSE))
+        if ((fused & OPT_MEANS) && a.transforms && !(a.raw_flags & RAW_POSE))
             return fail(MOSS_ERR_INVALID_ARG, "MOSS_OPT_MEANS: with transforms the position parameter is only what the op sees under MOSS_RAW_POSE");
         if (!opt->step_state) return fail(MOSS_ERR_INVALID_ARG, "moss_fused_adamw.step_state is NULL");
-        const float* params[5] = { means3D, shs, opacities, scales, rotations };
+        const float* params[5] = { a.means3D, a.shs, a.opacities, a.scales, a.rotations };
         for (int i = 0; i < 5; i++) {
             if (!(fused & (1u << i))) continue;
             if (!params[i] || !opt->exp_avg[i] || !opt->exp_avg_sq[i]) return fail(MOSS_ERR_INVALID_ARG, "a tensor named in moss_fused_adamw.tensors has a NULL parameter or moment array");
@@ -392,14 +363,14 @@ static int backward_impl(
             fa.lr_segment[i] = opt->lr_segment[i];
         }
         if (fused & OPT_SH) {
-            if (M != 16 || ((reinterpret_cast<uintptr_t>(shs) | reinterpret_cast<uintptr_t>(opt->exp_avg[1]) | reinterpret_cast<uintptr_t>(opt->exp_avg_sq[1]) |
-                             reinterpret_cast<uintptr_t>(dL_dsh)) & 15u))
+            if (a.M != 16 || ((reinterpret_cast<uintptr_t>(a.shs) | reinterpret_cast<uintptr_t>(opt->exp_avg[1]) | reinterpret_cast<uintptr_t>(opt->exp_avg_sq[1]) |
+                             reinterpret_cast<uintptr_t>(a.dL_dsh)) & 15u))
                 return fail(MOSS_ERR_INVALID_ARG, "MOSS_OPT_SH needs M == 16 and 16-byte aligned SH, moment and gradient arrays");
         }
-        if ((fused & OPT_ROTATIONS) && ((reinterpret_cast<uintptr_t>(rotations) | reinterpret_cast<uintptr_t>(opt->exp_avg[4]) | reinterpret_cast<uintptr_t>(opt->exp_avg_sq[4])) & 15u))
+        if ((fused & OPT_ROTATIONS) && ((reinterpret_cast<uintptr_t>(a.rotations) | reinterpret_cast<uintptr_t>(opt->exp_avg[4]) | reinterpret_cast<uintptr_t>(opt->exp_avg_sq[4])) & 15u))
             return fail(MOSS_ERR_INVALID_ARG, "MOSS_OPT_ROTATIONS needs 16-byte aligned rotation and moment arrays");
         {   // degree-aware SH update: float4 parts of a record that hold an ever-active coefficient (the call's own degree is the floor)
-            const int da = std::max(std::min((int)opt->sh_active_degree, 3), std::max(std::min(D, 3), 0));
+            const int da = std::max(std::min((int)opt->sh_active_degree, 3), std::max(std::min(a.D, 3), 0));
             // (eps = 0 would make the full update of an all-zero element 0 x rcp(0) = NaN: no shortcut then)
             fa.sh_active_parts = opt->eps > 0.0f ? (3 * (da + 1) * (da + 1) + 3) / 4 : 12;
             fa.sh_inactive_zero = (opt->sh_inactive_zero != 0 && fa.sh_active_parts < 12) ? 1 : 0;
@@ -408,27 +379,27 @@ static int backward_impl(
         fa.betas = AdamBetas(opt->beta1, opt->beta2); fa.eps = opt->eps; fa.weight_decay = opt->weight_decay;
         fa.step_state = reinterpret_cast<const float*>(opt->step_state);
     }
-    if (!means3D || !viewmatrix || !projmatrix || !campos || !background) return fail(MOSS_ERR_INVALID_ARG, "null required input");
+    if (!a.means3D || !a.viewmatrix || !a.projmatrix || !a.campos || !a.background) return fail(MOSS_ERR_INVALID_ARG, "null required input");
 
-    GeomView g = GeomView::at(geom_buffer, P);
-    ImageView im = ImageView::at(image_buffer, width, height);
-    BinView b = BinView::at(binning_buffer, R);
-    FrameParams fp = make_params(P, D, M, width, height, tan_fovx, tan_fovy, scale_modifier, 0,
-                                 viewmatrix, projmatrix, campos, background);
-    fp.raw = cov3D_precomp ? (raw_flags & RAW_OPACITY) : raw_flags;
-    fp.no_block_cull = (debug_flags & MOSS_DEBUG_NO_BLOCK_CULL) ? 1 : 0;
-    fp.exact_math = (debug_flags & MOSS_DEBUG_EXACT_MATH) ? 1 : 0;
-    const bool trace = (debug_flags & MOSS_DEBUG_TRACE) != 0;
-    if ((fp.raw & RAW_OPACITY) && !opacities) return fail(MOSS_ERR_INVALID_ARG, "raw opacities are required to chain through the sigmoid");
+    GeomView g = GeomView::at(a.geom_buffer, a.P);
+    ImageView im = ImageView::at(a.image_buffer, a.width, a.height);
+    BinView b = BinView::at(a.binning_buffer, a.R);
+    FrameParams fp = make_params(a.P, a.D, a.M, a.width, a.height, a.tan_fovx, a.tan_fovy, a.scale_modifier, 0,
+                                 a.viewmatrix, a.projmatrix, a.campos, a.background);
+    fp.raw = a.raw_flags;
+    fp.no_block_cull = (a.debug & MOSS_DEBUG_NO_BLOCK_CULL) ? 1 : 0;
+    fp.exact_math = (a.debug & MOSS_DEBUG_EXACT_MATH) ? 1 : 0;
+    const bool trace = (a.debug & MOSS_DEBUG_TRACE) != 0;
+    if ((fp.raw & RAW_OPACITY) && !a.opacities) return fail(MOSS_ERR_INVALID_ARG, "raw opacities are required to chain through the sigmoid");
     TraceRange tr_all(trace, "moss:raster_backward");
-    if (R > 0) {
-        { StageTimer tm(MOSS_STAGE_BLEND_BWD, s); TraceRange tr(trace, "moss:blend_bwd"); launch_blend_backward(fp, g, im, b, dL_dpix, dL_ddepths, dL_dalphas, s); }
+    if (a.R > 0) {
+        { StageTimer tm(MOSS_STAGE_BLEND_BWD, s); TraceRange tr(trace, "moss:blend_bwd"); launch_blend_backward(fp, g, im, b, a.dL_dpix, a.dL_ddepths, a.dL_dalphas, s); }
         STAGE_CHECK("blend_backward");
     }
     { StageTimer tm(MOSS_STAGE_PREPROCESS_BWD, s); TraceRange tr(trace, fused ? "moss:preprocess_bwd+adamw" : "moss:preprocess_bwd");
-      launch_preprocess_backward(fp, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, g, b, im.header, im.queues,
-                                 dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot,
-                                 transforms, dL_dtransforms, translation, dL_dtranslation, s, fused ? &fa : nullptr); }
+      launch_preprocess_backward(fp, a.means3D, a.shs, a.colors_precomp, a.opacities, a.scales, a.rotations, a.cov3D_precomp, g, b, im.header, im.queues,
+                                 a.dL_dmean2D, a.dL_dconic, a.dL_dopacity, a.dL_dcolor, a.dL_dmean3D, a.dL_dcov3D, a.dL_dsh, a.dL_dscale, a.dL_drot,
+                                 a.transforms, a.transforms ? a.dL_dtransforms : nullptr, a.translation, a.dL_dtranslation, s, fused ? &fa : nullptr); }
     STAGE_CHECK("preprocess_backward");
     return 0;
 }
@@ -445,103 +416,18 @@ int moss_raster_backward(
     float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
     float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, int debug, void* stream)
 {
-    return backward_impl(P, D, M, R, background, width, height, means3D, shs, colors_precomp, alphas, scales, scale_modifier, rotations,
-                         cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer,
-                         image_buffer, dL_dpix, dL_ddepths, dL_dalphas, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D,
-                         dL_dcov3D, dL_dsh, dL_dscale, dL_drot, debug, stream, nullptr, nullptr);
+    (void)alphas; (void)radii;                       // signature parity only (the reference ignores alphas too, backward.cu:410)
+    const moss_raster_backward_args a = {
+        P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
+        viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_ddepths, dL_dalphas,
+        dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, debug };   // no extension
+    return backward_impl(a, stream);
 }
 
-// n2 extension: backward of moss_raster_forward_tf; dL_dtransforms (P,9) is written for every Gaussian (zeros if culled).
-// dL_dcov3D is the gradient w.r.t. the TRANSFORMED covariance (as stored), dL_dscale / dL_drot already include the transform.
-int moss_raster_backward_tf(
-    int P, int D, int M, int R,
-    const float* background, int width, int height,
-    const float* means3D, const float* shs, const float* colors_precomp,
-    const float* scales, float scale_modifier, const float* rotations, const float* transforms,
-    const float* viewmatrix, const float* projmatrix, const float* campos,
-    float tan_fovx, float tan_fovy,
-    char* geom_buffer, char* binning_buffer, char* image_buffer,
-    const float* dL_dpix, const float* dL_ddepths, const float* dL_dalphas,
-    float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
-    float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, float* dL_dtransforms, int debug, void* stream)
+int moss_raster_backward_ex(const moss_raster_backward_args* args, void* stream)
 {
-    if (P > 0 && (!scales || !rotations || !transforms || !dL_dtransforms))
-        return fail(MOSS_ERR_INVALID_ARG, "scales, rotations, transforms and dL_dtransforms are required");
-    return backward_impl(P, D, M, R, background, width, height, means3D, shs, colors_precomp, nullptr, scales, scale_modifier, rotations,
-                         nullptr, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, nullptr, geom_buffer, binning_buffer,
-                         image_buffer, dL_dpix, dL_ddepths, dL_dalphas, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D,
-                         dL_dcov3D, dL_dsh, dL_dscale, dL_drot, debug, stream, transforms, dL_dtransforms);
-}
-
-// Raw-parameter variant (the getters of GaussianModel applied inside preprocess, see include/moss_raster.h).
-int moss_raster_forward_raw(
-    moss_alloc_fn geometry_alloc, void* geometry_user, moss_alloc_fn binning_alloc, void* binning_user,
-    moss_alloc_fn image_alloc, void* image_user, int P, int D, int M, const float* background, int width, int height,
-    const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
-    const float* scales, float scale_modifier, const float* rotations, const float* transforms, const float* translation,
-    const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered,
-    float* out_color, float* out_depth, float* out_alpha, int* radii, int raw_flags, int capacity, char* frame_state, int debug, void* stream)
-{
-    if (raw_flags & ~(RAW_OPACITY | RAW_SCALE | RAW_ROTATION | HINT_SPATIAL_ORDER | RAW_POSE)) return fail(MOSS_ERR_INVALID_ARG, "unknown raw_flags bits");
-    if (P > 0 && (!scales || !rotations)) return fail(MOSS_ERR_INVALID_ARG, "scales and rotations are required");
-    if (P > 0 && (raw_flags & RAW_POSE) && !transforms) return fail(MOSS_ERR_INVALID_ARG, "MOSS_RAW_POSE needs the transforms");
-    if (translation && !(raw_flags & RAW_POSE)) return fail(MOSS_ERR_INVALID_ARG, "a translation comes with MOSS_RAW_POSE");
-    if (capacity >= 0 && (debug & MOSS_DEBUG_SYNC)) return fail(MOSS_ERR_INVALID_ARG, "MOSS_DEBUG_SYNC needs the synchronous forward (capacity < 0)");
-    return forward_impl(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user, P, D, M, background,
-                        width, height, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, nullptr,
-                        viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color, out_depth, out_alpha, radii,
-                        debug, stream, capacity < 0 ? -1 : capacity, transforms, raw_flags, frame_state, translation);
-}
-
-int moss_raster_backward_raw(
-    int P, int D, int M, int R,
-    const float* background, int width, int height,
-    const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
-    const float* scales, float scale_modifier, const float* rotations, const float* transforms, const float* translation,
-    const float* viewmatrix, const float* projmatrix, const float* campos,
-    float tan_fovx, float tan_fovy,
-    char* geom_buffer, char* binning_buffer, char* image_buffer,
-    const float* dL_dpix, const float* dL_ddepths, const float* dL_dalphas,
-    float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
-    float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, float* dL_dtransforms, float* dL_dtranslation,
-    int raw_flags, int debug, void* stream)
-{
-    if (raw_flags & ~(RAW_OPACITY | RAW_SCALE | RAW_ROTATION | HINT_SPATIAL_ORDER | RAW_POSE | SH_GRAD_ACTIVE_ONLY)) return fail(MOSS_ERR_INVALID_ARG, "unknown raw_flags bits");
-    if (P > 0 && (raw_flags & RAW_POSE) && !transforms) return fail(MOSS_ERR_INVALID_ARG, "MOSS_RAW_POSE needs the transforms");
-    if ((translation || dL_dtranslation) && !(raw_flags & RAW_POSE)) return fail(MOSS_ERR_INVALID_ARG, "a translation comes with MOSS_RAW_POSE");
-    if (P > 0 && (!scales || !rotations || (transforms && !dL_dtransforms)))
-        return fail(MOSS_ERR_INVALID_ARG, "scales and rotations (and dL_dtransforms with transforms) are required");
-    return backward_impl(P, D, M, R, background, width, height, means3D, shs, colors_precomp, nullptr, scales, scale_modifier, rotations,
-                         nullptr, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, nullptr, geom_buffer, binning_buffer,
-                         image_buffer, dL_dpix, dL_ddepths, dL_dalphas, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D,
-                         dL_dcov3D, dL_dsh, dL_dscale, dL_drot, debug, stream, transforms, transforms ? dL_dtransforms : nullptr, opacities,
-                         raw_flags, translation, dL_dtranslation);
-}
-
-// The raw-parameter backward that also takes the AdamW step of the parameters named in opt->tensors (include/moss_raster.h).
-int moss_raster_backward_raw_adamw(
-    int P, int D, int M, int R,
-    const float* background, int width, int height,
-    float* means3D, float* shs, const float* colors_precomp, float* opacities,
-    float* scales, float scale_modifier, float* rotations, const float* transforms, const float* translation,
-    const float* viewmatrix, const float* projmatrix, const float* campos,
-    float tan_fovx, float tan_fovy,
-    char* geom_buffer, char* binning_buffer, char* image_buffer,
-    const float* dL_dpix, const float* dL_ddepths, const float* dL_dalphas,
-    float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
-    float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, float* dL_dtransforms, float* dL_dtranslation,
-    const moss_fused_adamw* opt, int raw_flags, int debug, void* stream)
-{
-    if (raw_flags & ~(RAW_OPACITY | RAW_SCALE | RAW_ROTATION | HINT_SPATIAL_ORDER | RAW_POSE | SH_GRAD_ACTIVE_ONLY)) return fail(MOSS_ERR_INVALID_ARG, "unknown raw_flags bits");
-    if (P > 0 && (raw_flags & RAW_POSE) && !transforms) return fail(MOSS_ERR_INVALID_ARG, "MOSS_RAW_POSE needs the transforms");
-    if ((translation || dL_dtranslation) && !(raw_flags & RAW_POSE)) return fail(MOSS_ERR_INVALID_ARG, "a translation comes with MOSS_RAW_POSE");
-    if (P > 0 && (!scales || !rotations || (transforms && !dL_dtransforms)))
-        return fail(MOSS_ERR_INVALID_ARG, "scales and rotations (and dL_dtransforms with transforms) are required");
-    return backward_impl(P, D, M, R, background, width, height, means3D, shs, colors_precomp, nullptr, scales, scale_modifier, rotations,
-                         nullptr, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, nullptr, geom_buffer, binning_buffer,
-                         image_buffer, dL_dpix, dL_ddepths, dL_dalphas, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D,
-                         dL_dcov3D, dL_dsh, dL_dscale, dL_drot, debug, stream, transforms, transforms ? dL_dtransforms : nullptr, opacities,
-                         raw_flags, translation, dL_dtranslation, (opt && opt->tensors) ? opt : nullptr);
+    if (!args) return fail(MOSS_ERR_INVALID_ARG, "null argument block");
+    return backward_impl(*args, stream);
 }
 
 int moss_raster_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix,

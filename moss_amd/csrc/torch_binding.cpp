@@ -6,10 +6,11 @@
 // resizeFunctional, rasterize_points.cu:27-33), unwraps every tensor to a raw device pointer and calls the C ABI of
 // include/moss_raster.h (libmoss_raster.so) on the CURRENT torch HIP stream of the inputs' device.  No kernel lives here and no
 // torch type crosses into the library.  The additions over the reference's signature are trailing and optional:
-//   transforms (P,3,3)   per-Gaussian covariance transforms applied inside the op          (moss_raster_forward_tf / _backward_tf)
-//   raw_flags            which of opacity / scales / rotations are raw parameters            (moss_raster_forward_raw / _backward_raw)
-//   capacity             >= 0: asynchronous forward without the host read-back of num_rendered (moss_raster_forward_async)
+//   transforms (P,3,3)   per-Gaussian covariance transforms applied inside the op
+//   raw_flags            which of opacity / scales / rotations are raw parameters
+//   capacity             >= 0: asynchronous forward without the host read-back of num_rendered (0 is refused by the library)
 //   sinks                caller-provided tensors the backward writes five of its gradients into (e.g. slices of a flat bucket)
+// A call with the reference's arguments only goes to moss_raster_forward / moss_raster_backward, every other one to the _ex form.
 #include <torch/extension.h>
 #include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
@@ -115,7 +116,6 @@ rasterize_gaussians(const torch::Tensor& background, const torch::Tensor& means3
     std::vector<torch::Tensor> keep;
     keep.reserve(16);
     void* stream = c10::hip::getCurrentHIPStream(means3D.device().index()).stream();
-    const bool use_async = capacity >= 0 && !(debug & MOSS_DEBUG_SYNC) && P > 0;   // (the reference's debug flag synchronises after every launch)
     const float* p_bg = ptr(background, "background", keep);
     const float* p_means = ptr(means3D, "means3D", keep);
     const float* p_sh = ptr(sh, "sh", keep);
@@ -134,31 +134,29 @@ rasterize_gaussians(const torch::Tensor& background, const torch::Tensor& means3
     int* p_radii = P ? reinterpret_cast<int*>(radii.data_ptr()) : nullptr;
     float *oc = reinterpret_cast<float*>(out_color.data_ptr()), *od = reinterpret_cast<float*>(out_depth.data_ptr()),
           *oa = reinterpret_cast<float*>(out_alpha.data_ptr());
-    const int cap = use_async ? static_cast<int>(capacity) : -1;
-    char* p_fs = nullptr;                                   // the caller's frame state: an argument of the asynchronous forwards (ABI 2)
-    if (use_async && frame_state.has_value() && frame_state->defined()) {
+    // capacity >= 0: the asynchronous forward, the capacity passed through (0 is the library's error); -1: synchronous (also with the
+    // reference's debug flag, which synchronises after every launch)
+    const int cap = (capacity >= 0 && !(debug & MOSS_DEBUG_SYNC) && P > 0) ? static_cast<int>(capacity) : -1;
+    char* p_fs = nullptr;                                   // the caller's frame state: an argument of the asynchronous forward (ABI 2)
+    if (cap >= 0 && frame_state.has_value() && frame_state->defined()) {
         TORCH_CHECK(frame_state->is_cuda() && frame_state->is_contiguous() && frame_state->scalar_type() == torch::kByte &&
                     frame_state->device() == means3D.device() &&
                     (size_t)frame_state->numel() >= moss_raster_frame_state_bytes(W, H), "frame_state: a zero-initialised byte tensor of moss_raster_frame_state_bytes on the GPU");
         p_fs = reinterpret_cast<char*>(frame_state->data_ptr());
     }
     int rc;
-    if (raw_flags)
-        rc = moss_raster_forward_raw(grow, &geom, grow, &binning, grow, &img, P, (int)degree, M, p_bg, W, H, p_means, p_sh, p_col, p_opa,
-                                     p_scl, (float)scale_modifier, p_rot, p_tf, p_tl, p_view, p_proj, p_cam, (float)tan_fovx, (float)tan_fovy,
-                                     prefiltered ? 1 : 0, oc, od, oa, p_radii, (int)raw_flags, cap, p_fs, (int)debug, stream);
-    else if (has_tf)
-        rc = moss_raster_forward_tf(grow, &geom, grow, &binning, grow, &img, P, (int)degree, M, p_bg, W, H, p_means, p_sh, p_col, p_opa,
-                                    p_scl, (float)scale_modifier, p_rot, p_tf, p_view, p_proj, p_cam, (float)tan_fovx, (float)tan_fovy,
-                                    prefiltered ? 1 : 0, oc, od, oa, p_radii, cap, p_fs, (int)debug, stream);
-    else if (use_async)
-        rc = moss_raster_forward_async(grow, &geom, grow, &binning, grow, &img, P, (int)degree, M, p_bg, W, H, p_means, p_sh, p_col,
-                                       p_opa, p_scl, (float)scale_modifier, p_rot, p_cov, p_view, p_proj, p_cam, (float)tan_fovx,
-                                       (float)tan_fovy, prefiltered ? 1 : 0, oc, od, oa, p_radii, cap, p_fs, (int)debug, stream);
-    else
+    if (!raw_flags && !has_tf && cap < 0) {
         rc = moss_raster_forward(grow, &geom, grow, &binning, grow, &img, P, (int)degree, M, p_bg, W, H, p_means, p_sh, p_col, p_opa,
                                  p_scl, (float)scale_modifier, p_rot, p_cov, p_view, p_proj, p_cam, (float)tan_fovx, (float)tan_fovy,
                                  prefiltered ? 1 : 0, oc, od, oa, p_radii, (int)debug, stream);
+    } else {
+        moss_raster_forward_args a = {
+            grow, &geom, grow, &binning, grow, &img, P, (int)degree, M, p_bg, W, H, p_means, p_sh, p_col, p_opa,
+            p_scl, (float)scale_modifier, p_rot, p_cov, p_view, p_proj, p_cam, (float)tan_fovx, (float)tan_fovy,
+            prefiltered ? 1 : 0, oc, od, oa, p_radii, (int)debug };
+        a.transforms = p_tf; a.translation = p_tl; a.raw_flags = (int)raw_flags; a.capacity = cap; a.frame_state = p_fs;
+        rc = moss_raster_forward_ex(&a, stream);
+    }
     if (rc < 0) raise(rc, "rasterize_gaussians");
     return std::make_tuple((int64_t)rc, out_color, out_depth, out_alpha, radii, geom, binning, img);
 }
@@ -182,8 +180,8 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
                              bool all_outputs /* false: gradients nobody can receive are not computed into memory */)
 {
     const int P = static_cast<int>(means3D.size(0));
-    // The tensors whose AdamW update the backward kernel applies itself (moss_raster_backward_raw_adamw): their gradients stay inside
-    // the kernel and come back as None.
+    // The tensors whose AdamW update the backward kernel applies itself (moss_raster_backward_ex with `opt`): their gradients stay
+    // inside the kernel and come back as None.
     const moss_fused_adamw* opt = reinterpret_cast<const moss_fused_adamw*>(static_cast<intptr_t>(fused_adamw));
     const uint32_t fused = (opt != nullptr && P != 0) ? opt->tensors : 0u;
     TORCH_CHECK(!fused || raw_flags, "the fused AdamW update needs the raw-parameter backward (raw_flags)");
@@ -236,37 +234,32 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
         const float* g_a = ptr(dL_dout_alpha, "dL_dout_alpha", keep);
         float* p_dsh = M ? f(dL_dsh) : nullptr;
         int rc;
-        if (fused) {
-            // the parameters are updated IN PLACE: they must be the caller's own contiguous float32 tensors, not copies made here
-            TORCH_CHECK(opacities.has_value() && opacities->defined(), "the raw-parameter backward needs the raw opacities");
-            for (const torch::Tensor* t : { &means3D, &sh, &*opacities, &scales, &rotations })
-                TORCH_CHECK(t->is_contiguous() && t->scalar_type() == torch::kFloat32, "fused AdamW update: the parameters must be contiguous float32 tensors");
-            rc = moss_raster_backward_raw_adamw(P, (int)degree, M, (int)R, p_bg, W, H, const_cast<float*>(p_means), const_cast<float*>(p_sh), p_col,
-                                                const_cast<float*>(ptr(*opacities, "opacity", keep)), const_cast<float*>(p_scl),
-                                                (float)scale_modifier, const_cast<float*>(p_rot), p_tf, has_tl ? ptr(*translation, "translation", keep) : nullptr,
-                                                p_view, p_proj, p_cam, (float)tan_fovx, (float)tan_fovy, p_geom,
-                                                p_bin, p_img, g_c, g_d, g_a, f(dL_dmeans2D), f(dL_dconic), f(dL_dopacity), f(dL_dcolors), f(dL_dmeans3D),
-                                                f(dL_dcov3D), p_dsh, f(dL_dscales), f(dL_drotations), has_tf ? f(dL_dtransforms) : nullptr,
-                                                has_tl ? f(dL_dtranslation) : nullptr, opt, (int)raw_flags, (int)debug, stream);
-        } else if (raw_flags) {
-            TORCH_CHECK(opacities.has_value() && opacities->defined(), "the raw-parameter backward needs the raw opacities");
-            rc = moss_raster_backward_raw(P, (int)degree, M, (int)R, p_bg, W, H, p_means, p_sh, p_col, ptr(*opacities, "opacity", keep), p_scl,
-                                          (float)scale_modifier, p_rot, p_tf, has_tl ? ptr(*translation, "translation", keep) : nullptr,
-                                          p_view, p_proj, p_cam, (float)tan_fovx, (float)tan_fovy, p_geom,
-                                          p_bin, p_img, g_c, g_d, g_a, f(dL_dmeans2D), f(dL_dconic), f(dL_dopacity), f(dL_dcolors), f(dL_dmeans3D),
-                                          f(dL_dcov3D), p_dsh, f(dL_dscales), f(dL_drotations), has_tf ? f(dL_dtransforms) : nullptr,
-                                          has_tl ? f(dL_dtranslation) : nullptr, (int)raw_flags, (int)debug, stream);
-        } else if (has_tf) {
-            rc = moss_raster_backward_tf(P, (int)degree, M, (int)R, p_bg, W, H, p_means, p_sh, p_col, p_scl, (float)scale_modifier, p_rot, p_tf,
-                                         p_view, p_proj, p_cam, (float)tan_fovx, (float)tan_fovy, p_geom, p_bin, p_img, g_c, g_d, g_a,
-                                         f(dL_dmeans2D), f(dL_dconic), f(dL_dopacity), f(dL_dcolors), f(dL_dmeans3D), f(dL_dcov3D), p_dsh,
-                                         f(dL_dscales), f(dL_drotations), f(dL_dtransforms), (int)debug, stream);
-        } else {
+        if (!fused && !raw_flags && !has_tf) {
             rc = moss_raster_backward(P, (int)degree, M, (int)R, p_bg, W, H, p_means, p_sh, p_col, ptr(alphas, "alphas", keep), p_scl,
                                       (float)scale_modifier, p_rot, p_cov, p_view, p_proj, p_cam, (float)tan_fovx, (float)tan_fovy,
                                       ptr<int>(radii, "radii", keep, torch::kInt32), p_geom, p_bin, p_img, g_c, g_d, g_a, f(dL_dmeans2D),
                                       f(dL_dconic), f(dL_dopacity), f(dL_dcolors), f(dL_dmeans3D), f(dL_dcov3D), p_dsh, f(dL_dscales),
                                       f(dL_drotations), (int)debug, stream);
+        } else {
+            if (raw_flags) TORCH_CHECK(opacities.has_value() && opacities->defined(), "the raw-parameter backward needs the raw opacities");
+            // the parameters are updated IN PLACE: they must be the caller's own contiguous float32 tensors, not copies made here
+            if (fused)
+                for (const torch::Tensor* t : { &means3D, &sh, &*opacities, &scales, &rotations })
+                    TORCH_CHECK(t->is_contiguous() && t->scalar_type() == torch::kFloat32, "fused AdamW update: the parameters must be contiguous float32 tensors");
+            // (cov3D_precomp stays NULL: the library refuses it with transforms or raw_flags, and so does the forward above)
+            moss_raster_backward_args a = {
+                P, (int)degree, M, (int)R, p_bg, W, H, p_means, p_sh, p_col, p_scl, (float)scale_modifier, p_rot, nullptr,
+                p_view, p_proj, p_cam, (float)tan_fovx, (float)tan_fovy, p_geom, p_bin, p_img, g_c, g_d, g_a, f(dL_dmeans2D),
+                f(dL_dconic), f(dL_dopacity), f(dL_dcolors), f(dL_dmeans3D), f(dL_dcov3D), p_dsh, f(dL_dscales), f(dL_drotations),
+                (int)debug };
+            a.transforms = p_tf; a.dL_dtransforms = f(dL_dtransforms);
+            if (raw_flags) {
+                a.raw_flags = (int)raw_flags;
+                a.opacities = ptr(*opacities, "opacity", keep);
+                a.translation = has_tl ? ptr(*translation, "translation", keep) : nullptr; a.dL_dtranslation = f(dL_dtranslation);
+            }
+            a.opt = fused ? opt : nullptr;
+            rc = moss_raster_backward_ex(&a, stream);
         }
         if (rc < 0) raise(rc, "rasterize_gaussians_backward");
     }

@@ -45,7 +45,7 @@ class CapacityOverflow(RuntimeError):
 class RasterContext:
     """State of ONE user of the rasterizer.
 
-    * Opt-in asynchronous forward (C ABI ``moss_raster_forward_async``): no host read-back of num_rendered.  The reference blocks in
+    * Opt-in asynchronous forward (C ABI ``moss_raster_forward_ex`` with a capacity > 0): no host read-back of num_rendered.  The reference blocks in
       every forward to size its binning buffer (rasterizer_impl.cu:283).  In a training loop R drifts slowly, so here the buffer is
       sized for ``margin x`` the last value seen; the true R stays on the device.  A frame that needs more than the capacity renders
       nothing and sets a flag, which is read back (without blocking) and raised by a later call or by :meth:`check_status`.  With no
@@ -153,7 +153,7 @@ class RasterContext:
         self._consume_status(block=True)
 
     def _frame_state(self, dev, width, height):
-        """The zero-initialised ``frame_state`` block of the asynchronous forwards (C ABI ``moss_raster_forward_async``) for this
+        """The zero-initialised ``frame_state`` block of the asynchronous forward (C ABI ``moss_raster_forward_ex``) for this
         context (one per context: its forwards are ordered on one stream); a new one when the device changes or a larger image comes
         along.  With it no clear kernel runs per forward.
 
@@ -234,7 +234,7 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
                         prefiltered, debug, transforms=None, raw_flags=0, context=None, translation=None):
     """RasterizeGaussiansCUDA, rasterize_points.cu:35-119.
     ``raw_flags`` (an addition): RAW_OPACITY | RAW_SCALE | RAW_ROTATION -- those inputs are MOSS's raw parameters and the getters
-    (sigmoid / exp / normalize) run inside the op (C ABI moss_raster_forward_raw); needs scales and rotations, no cov3D_precomp.
+    (sigmoid / exp / normalize) run inside the op (C ABI moss_raster_forward_ex with raw_flags); needs scales and rotations, no cov3D_precomp.
     ``transforms`` (an addition): (P,3,3) per-Gaussian matrices applied to the scale/rotation covariance
     inside the op (Sigma' = T Sigma T^T, what MOSS's Python get_covariance builds); needs scales and rotations, no cov3D_precomp.
     ``context`` (an addition): the :class:`RasterContext` whose asynchronous-forward policy applies (default: the shared one).

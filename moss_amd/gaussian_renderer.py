@@ -60,7 +60,7 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
     ``pipe.fused_activations`` (an addition, default off): read the activated parameters from ``pc.activate(pipe.grad_bucket)``
     -- one HIP kernel instead of the five torch getters (moss_amd/activations.py); values and gradients are the same."""
     # ``pipe.raw_parameters_in_op`` (an addition, default off): hand the rasterizer the RAW ``_opacity / _scaling / _rotation`` and let
-    # it run sigmoid / exp / normalize inside its preprocess kernels (C ABI moss_raster_forward_raw): no activation kernel either way.
+    # it run sigmoid / exp / normalize inside its preprocess kernels (C ABI moss_raster_forward_ex with raw_flags): no activation kernel either way.
     raw_flags = 0
     if (getattr(pipe, "raw_parameters_in_op", False) and not pipe.compute_cov3D_python
             and all(hasattr(pc, a) for a in ("_opacity", "_scaling", "_rotation"))):

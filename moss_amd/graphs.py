@@ -14,7 +14,7 @@ Rules the captured function must follow (``bench.py`` and tests/test_gpu_ops.py:
   EVERY frame that overflowed between two checks is counted in ``step.dropped_frames`` (the library keeps a sticky counter in the
   context's frame state; the status words alone describe only the last frame) and the step is re-captured with the grown capacity,
   not raised.  Such a frame rendered nothing and left zero gradients.  Give the captured optimizer the frame's status word --
-  ``opt.step(skip_word=frame_status_word(ctx.last_img_buffer))`` (``FlatAdamW``, C ABI ``moss_adamw_flat_guarded``) -- and a dropped
+  ``opt.step(skip_word=frame_status_word(ctx.last_img_buffer))`` (``FlatAdamW``, C ABI ``moss_adamw_flat_ex`` with a ``skip_word``) -- and a dropped
   frame is a NO-OP: parameters, moments and the device-side step counter stay bit for bit
   (tests/test_gpu_ops.py::test_dropped_frame_is_not_an_optimizer_step).  Without the guard the update kernel still runs on the
   zero gradients: a weight-decay-only step that also decays the moments (what rounds 2-3 did).

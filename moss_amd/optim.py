@@ -1,4 +1,4 @@
-"""Flat fused AdamW over the gradient bucket (C ABI ``moss_adamw_flat``, csrc/optim.hip) -- SURVEY.md section 8(f) n4.
+"""Flat fused AdamW over the gradient bucket (C ABI ``moss_adamw_flat_ex``, csrc/optim.hip) -- SURVEY.md section 8(f) n4.
 
 Same update rule as ``torch.optim.AdamW`` (which MOSS uses per parameter group, scene/gaussian_model.py:215-226), applied by
 ONE streaming kernel to all parameters: they are re-homed as views of one flat buffer, next to their flat gradients
@@ -31,7 +31,7 @@ class _FusedAdamW:
 
 class FlatAdamW:
     def __init__(self, param_groups, bucket, betas=(0.9, 0.999), eps=1e-15, weight_decay=0.01, capturable=False, shard=None):
-        """capturable=True keeps the step counter on the device (``moss_adamw_flat_devstep``) so that a hipGraph capture of
+        """capturable=True keeps the step counter on the device (``moss_adamw_flat_ex`` with a ``step_state``) so that a hipGraph capture of
         the training step replays with the right bias correction (the analogue of torch.optim.AdamW(capturable=True)).
 
         ``shard=(rank, world)``: this rank updates only its 1/world of the flat parameter buffer (the bucket's ``shard_layout``: the
@@ -112,7 +112,7 @@ class FlatAdamW:
     # ---- the update applied by the rasterizer's backward kernel itself -----------------------------------------------------------
     def fuse_into_backward(self, context, means3D=None, sh=None, opacity=None, scales=None, rotations=None, local_only=False):
         """Hand the update of the named parameters to the per-Gaussian backward kernel of the rasterizer (C ABI
-        ``moss_raster_backward_raw_adamw``): the kernel that produces a Gaussian's gradients applies its AdamW step on the spot --
+        ``moss_raster_backward_ex`` with ``opt``): the kernel that produces a Gaussian's gradients applies its AdamW step on the spot --
         parameters in place, moments in this optimizer's buffers, same bits as ``step()`` would give -- and the gradients of those
         tensors never leave it (autograd sees ``None`` for them).  Valid when the rasterizer is the ONLY source of their gradients
         (MOSS: features, opacity, scaling, rotation -- every loss term of train_ZJU.py:111-131 goes through the image; the position only
@@ -394,7 +394,7 @@ class FlatAdamW:
     def step(self, skip_word=None, skip_mask=2, extra_grads=None, grad_scale=1.0):
         """One update.  ``skip_word`` (capturable optimizers only): a one-element int32 / float32 DEVICE tensor; if
         ``skip_word & skip_mask`` is non-zero when the kernel runs, the step is a no-op on the device -- parameters, moments and the
-        step counter stay bit for bit (C ABI ``moss_adamw_flat_guarded``).  Not with ``shard``: the skip is a per-rank decision.  ``frame_status_word(img_buffer)`` of a rasterizer forward
+        step counter stay bit for bit (C ABI ``moss_adamw_flat_ex`` with a ``skip_word``).  Not with ``shard``: the skip is a per-rank decision.  ``frame_status_word(img_buffer)`` of a rasterizer forward
         with the default mask 2 skips the step of a frame that overflowed its capacity and rendered nothing (inside a captured
         hipGraph nobody else can).  ``extra_grads`` (up to three flat tensors laid out like the bucket) + ``grad_scale``: the step's
         gradient is ((bucket + extra[0]) + extra[1] ...) x grad_scale, formed inside the update kernel in that order -- B views per
@@ -455,8 +455,8 @@ class FlatAdamW:
 class AdamW(torch.optim.Optimizer):
     """Drop-in for ``torch.optim.AdamW(params, lr, betas, eps, weight_decay)`` as MOSS builds it (scene/gaussian_model.py:226:
     eight parameter groups, ``lr=0.0, eps=1e-15``): the same update rule, ONE kernel for all the single-tensor groups (C ABI
-    ``moss_adamw_multi``: up to eight tensors with their own state tensors and step counts per launch; rounds 4-5: one launch per tensor,
-    ``moss_adamw_flat``, bit-identical) instead of torch's nine ``multi_tensor_apply`` launches per group -- with MOSS's six single-tensor
+    ``moss_adamw_multi``: up to eight tensors with their own state tensors and step counts per launch; rounds 4-5: one launch per tensor of
+    the flat update, bit-identical) instead of torch's nine ``multi_tensor_apply`` launches per group -- with MOSS's six single-tensor
     Gaussian groups that is 54 launches of ~13 us per step, more than half of the patched call pattern's step (rocprofv3,
     ``profiles/r04_notes.md``).
 

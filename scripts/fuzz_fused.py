@@ -1,5 +1,5 @@
 """Randomised check of the optimizer step inside the backward kernel (FlatAdamW.fuse_into_backward, C ABI
-moss_raster_backward_raw_adamw) against backward -> bucket -> flat AdamW: random scenes (1-4000 Gaussians -- most P are no multiple of
+moss_raster_backward_ex with opt) against backward -> bucket -> flat AdamW: random scenes (1-4000 Gaussians -- most P are no multiple of
 4 or 64 --, ragged images, SH degrees 0-3, with and without per-Gaussian transforms / in-op posing, the spatial-order hint, weight
 decay on and off), three steps each; parameters, both moments and the step count must agree BIT FOR BIT.
 Usage: python scripts/fuzz_fused.py [n_cases] [first_seed]"""

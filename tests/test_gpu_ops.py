@@ -600,8 +600,9 @@ def async_mode():
 
 @pytest.mark.parametrize("raw", [False, True])
 def test_async_forward_equals_sync_forward(gpu, hip_lib, async_mode, raw):
-    """moss_raster_forward_async (no host read-back, capacity-bounded) runs the same kernels on the same data: image, alpha,
-    radii and every parameter gradient are BIT-IDENTICAL to the synchronous call (also for the raw-parameter entry points)."""
+    """The asynchronous forward (moss_raster_forward_ex with a capacity > 0: no host read-back, capacity-bounded) runs the same kernels
+    on the same data: image, alpha, radii and every parameter gradient are BIT-IDENTICAL to the synchronous call (also with raw
+    parameters).  A capacity of 0 is neither: the library refuses it before it launches anything."""
     from types import SimpleNamespace
     from moss_amd.gaussian_model import GaussianSet
     from moss_amd.gaussian_renderer import camera_view
@@ -626,6 +627,15 @@ def test_async_forward_equals_sync_forward(gpu, hip_lib, async_mode, raw):
         assert torch.equal(a, b) and torch.equal(a, c)
     for a, c in zip(ref[3], got[3]):
         assert torch.equal(a, c)
+    # capacity 0 (an extension caller's; the context policy never passes it): refused, nothing launched
+    from moss_amd._lib import ext
+    d = hp.inputs_of(scenes.config1(), "scale_rot")
+    a = hp.hip_forward(d, gpu).args
+    c = d.cam
+    with pytest.raises(RuntimeError, match="capacity 0"):
+        ext().rasterize_gaussians(
+            a["bg"], a["means3D"], a["colors"], a["opacity"], a["scales"], a["rotations"], d.scale_modifier, a["cov3D"], a["view"],
+            a["proj"], c.tanfovx, c.tanfovy, c.H, c.W, a["sh"], d.degree, a["campos"], False, 0, raw_flags=7 if raw else 0, capacity=0)
 
 
 @pytest.mark.parametrize("size", [1024, 2048])
@@ -952,9 +962,9 @@ def test_adamw_drop_in_matches_torch_optim_adamw(gpu, hip_lib):
     assert float((p64 - r64).abs().max()) < 1e-12
 
 
-def test_adamw_multi_is_bit_identical_to_one_call_per_tensor(gpu, hip_lib):
-    """C ABI moss_adamw_multi (several tensors with buffers and step counts of their own, one launch) against moss_adamw_flat called once
-    per tensor: the same bits in every parameter and moment -- ragged sizes (not multiples of 4, one element, empty), different learning
+def test_adamw_multi_is_bit_identical_to_one_flat_ex_call_per_tensor(gpu, hip_lib):
+    """C ABI moss_adamw_multi (several tensors with buffers and step counts of their own, one launch) against moss_adamw_flat_ex (one
+    segment, host-side step) called once per tensor: the same bits in every parameter and moment -- ragged sizes (not multiples of 4, one element, empty), different learning
     rates and DIFFERENT step counts (MOSS's surgery keeps the step per tensor), two steps."""
     import ctypes as C
     from moss_amd import _lib
@@ -981,9 +991,12 @@ def test_adamw_multi_is_bit_identical_to_one_call_per_tensor(gpu, hip_lib):
         for k, n in enumerate(sizes):
             if n == 0:
                 continue
-            one, lr, zi, zf = (C.c_longlong * 1)(n), (C.c_float * 1)(lrs[k]), (C.c_int * 1)(0), (C.c_float * 1)(0.0)
-            assert L.moss_adamw_flat(n, pb[k].data_ptr(), grads[k].data_ptr(), mb[k].data_ptr(), vb[k].data_ptr(), 1, one, lr, zi, zi, zf,
-                                     0.9, 0.999, 1e-15, 0.01, steps0[k] + it, stream) == 0
+            one, lr = (C.c_longlong * 1)(n), (C.c_float * 1)(lrs[k])
+            f = _lib.AdamWFlatArgs()
+            f.first, f.count, f.num_segments, f.segment_end, f.segment_lr = 0, n, 1, C.addressof(one), C.addressof(lr)
+            f.params, f.grads, f.exp_avg, f.exp_avg_sq = pb[k].data_ptr(), grads[k].data_ptr(), mb[k].data_ptr(), vb[k].data_ptr()
+            f.beta1, f.beta2, f.eps, f.weight_decay, f.step = 0.9, 0.999, 1e-15, 0.01, steps0[k] + it
+            assert L.moss_adamw_flat_ex(C.addressof(f), stream) == 0
         torch.cuda.synchronize(gpu)
         for k in range(len(sizes)):
             assert torch.equal(pa[k], pb[k]) and torch.equal(ma[k], mb[k]) and torch.equal(va[k], vb[k]), (it, k)

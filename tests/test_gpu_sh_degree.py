@@ -81,61 +81,6 @@ def test_the_degree_in_force_is_the_highest_ever_active(gpu, hip_lib):
     assert opt.sh_active_degree == 3 and not opt.sh_inactive_zero
 
 
-def test_older_flat_entry_points_equal_the_struct_entry(gpu, hip_lib):
-    """moss_adamw_flat / _devstep / _range / _guarded stay exported (ABI): the same bits as moss_adamw_flat_ex, which FlatAdamW now calls."""
-    import ctypes as C
-    L = hip_lib
-    n = 10_007
-    g = torch.Generator().manual_seed(3)
-    p0, gr = torch.randn(n, generator=g).to(gpu), torch.randn(n, generator=g).to(gpu)
-    ends, lrs = (C.c_longlong * 2)(4000, n), (C.c_float * 2)(1e-3, 5e-2)
-    zi, zf = (C.c_int * 2)(0, 0), (C.c_float * 2)(0.0, 0.0)
-    st = torch.cuda.current_stream(gpu).cuda_stream
-    from moss_amd._lib import AdamWFlatArgs
-
-    def ex(first, count, step, state, skip=None):
-        p, m, v = p0.clone(), torch.zeros(n, device=gpu), torch.zeros(n, device=gpu)
-        a = AdamWFlatArgs()
-        a.first, a.count, a.params, a.grads = first, count, p[first:].data_ptr(), gr[first:].data_ptr()
-        a.exp_avg, a.exp_avg_sq, a.num_segments = m[first:].data_ptr(), v[first:].data_ptr(), 2
-        a.segment_end, a.segment_lr = C.addressof(ends), C.addressof(lrs)
-        a.segment_period = a.segment_split = a.segment_lr2 = a.segment_active = None
-        a.beta1, a.beta2, a.eps, a.weight_decay, a.step = 0.9, 0.999, 1e-15, 0.01, step
-        a.step_state = None if state is None else state.data_ptr()
-        a.skip_word, a.skip_mask = (None, 0) if skip is None else (skip.data_ptr(), 2)
-        assert L.moss_adamw_flat_ex(C.addressof(a), st) == 0
-        return p, m, v
-    state = lambda: torch.zeros(int(L.moss_adamw_state_bytes()) // 4, dtype=torch.int32, device=gpu)
-    # host step count
-    p, m, v = p0.clone(), torch.zeros(n, device=gpu), torch.zeros(n, device=gpu)
-    assert L.moss_adamw_flat(n, p.data_ptr(), gr.data_ptr(), m.data_ptr(), v.data_ptr(), 2, ends, lrs, zi, zi, zf, 0.9, 0.999, 1e-15, 0.01, 5, st) == 0
-    for a_, b_ in zip((p, m, v), ex(0, n, 5, None)):
-        assert torch.equal(a_, b_)
-    # device step count
-    p, m, v, s1 = p0.clone(), torch.zeros(n, device=gpu), torch.zeros(n, device=gpu), state()
-    assert L.moss_adamw_flat_devstep(n, p.data_ptr(), gr.data_ptr(), m.data_ptr(), v.data_ptr(), 2, ends, lrs, zi, zi, zf, 0.9, 0.999, 1e-15, 0.01, s1.data_ptr(), st) == 0
-    s2 = state()
-    for a_, b_ in zip((p, m, v), ex(0, n, 1, s2)):
-        assert torch.equal(a_, b_)
-    assert int(s1[0]) == int(s2[0]) == 1
-    # a range
-    p, m, v = p0.clone(), torch.zeros(n, device=gpu), torch.zeros(n, device=gpu)
-    assert L.moss_adamw_flat_range(2000, 6000, p[2000:].data_ptr(), gr[2000:].data_ptr(), m[2000:].data_ptr(), v[2000:].data_ptr(), 2, ends, lrs, zi, zi, zf,
-                                   0.9, 0.999, 1e-15, 0.01, 3, None, st) == 0
-    for a_, b_ in zip((p, m, v), ex(2000, 6000, 3, None)):
-        assert torch.equal(a_, b_)
-    # the guard
-    for word in (0, 2):
-        skip = torch.tensor([word], dtype=torch.int32, device=gpu)
-        p, m, v, s1 = p0.clone(), torch.zeros(n, device=gpu), torch.zeros(n, device=gpu), state()
-        assert L.moss_adamw_flat_guarded(0, n, p.data_ptr(), gr.data_ptr(), m.data_ptr(), v.data_ptr(), 2, ends, lrs, zi, zi, zf, 0.9, 0.999, 1e-15, 0.01,
-                                         s1.data_ptr(), skip.data_ptr(), 2, st) == 0
-        s2 = state()
-        for a_, b_ in zip((p, m, v), ex(0, n, 1, s2, skip)):
-            assert torch.equal(a_, b_)
-        assert int(s1[0]) == int(s2[0]) == (0 if word else 1) and torch.equal(p, p0) == bool(word)
-
-
 class _Step(thl._BenchStep):
     """tests/test_gpu_headline.py's harness with the optimizer TOLD the active degree and -- `zero_rest` -- MOSS's own initial state."""
 

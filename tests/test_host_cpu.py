@@ -19,9 +19,12 @@ def _declared(text):
     return set(re.findall(r"\b(moss_[a-z0-9_]+)\s*\(", text)) - {"moss_alloc_fn"}
 
 
-def test_library_exports_every_declared_symbol(hip_lib):
+def test_library_exports_exactly_the_declared_symbols(hip_lib):
     """The PRODUCT library exports everything the header declares outside its ``#ifdef MOSS_DIAG`` block -- and nothing of that block
-    (diagnostics do not ship)."""
+    (diagnostics do not ship) -- and, the other way round, every ``moss_*`` symbol it exports is declared there (no
+    stale entry point left behind when one is removed from the ABI)."""
+    import subprocess
+    from moss_amd import _lib
     text = open(os.path.join(ROOT, "include", "moss_raster.h")).read()
     diag_block = re.search(r"#ifdef MOSS_DIAG\n(.*?)#endif", text, flags=re.S)
     assert diag_block
@@ -32,8 +35,11 @@ def test_library_exports_every_declared_symbol(hip_lib):
         assert hasattr(hip_lib, n), f"{n} is declared in include/moss_raster.h but not exported"
     for n in sorted(diag_names):
         assert not hasattr(hip_lib, n), f"{n} is a diagnostic entry point and must not be in the product build"
+    syms = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = set(re.findall(r"\s(moss_[A-Za-z0-9_]+)$", syms, flags=re.M))
+    assert len(exported) >= 15 and exported <= names, f"exported but not declared in include/moss_raster.h: {sorted(exported - names)}"
     assert hip_lib.moss_build_has_diagnostics() == 0
-    assert re.search(r"#define\s+MOSS_ABI_VERSION\s+6\b", text) and hip_lib.moss_abi_version() == 6
+    assert re.search(r"#define\s+MOSS_ABI_VERSION\s+7\b", text) and hip_lib.moss_abi_version() == 7
     assert hip_lib.moss_last_error() == b""
     assert hip_lib.moss_adamw_state_bytes() == int(re.search(r"#define\s+MOSS_ADAMW_STATE_BYTES\s+(\d+)", text).group(1))
 
