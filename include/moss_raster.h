@@ -281,7 +281,9 @@ int moss_photometric_loss_roi(int C, int H, int W, const float* image, const flo
  * form of the update behind one argument block (ABI 6; the positional forms of ABI 2-5 were removed in ABI 7).  Replaces the per-group
  * optimizer step of scene/gaussian_model.py:215-226 for the Gaussian parameters.
  *   params, grads, exp_avg, exp_avg_sq: the elements [first, first + count) (first a multiple of 4) of flat buffers that the segment
- *     table -- global indices -- describes.  first = 0, count = n: the whole buffer.  A SHARD is for N ranks that reduce-scatter the
+ *     table -- global indices -- describes.  Every array (grads_extra too) starts on 16 bytes: the update moves float4; a misaligned
+ *     pointer is refused (MOSS_ERR_INVALID_ARG).  Any count: arrays of 4 GB and more take a form of the kernel that loads through
+ *     64-bit pointers (and has no degree-aware shortcut: see segment_active).  first = 0, count = n: the whole buffer.  A SHARD is for N ranks that reduce-scatter the
  *     gradient bucket, update their 1/N of the parameters (moments memory and update time / N) and all-gather the result (SURVEY
  *     section 8e; moss_amd/dist.py ShardedStep).
  *   Up to 8 learning-rate segments: parameter i belongs to the first segment s with i < segment_end[s] (host arrays).
@@ -313,6 +315,9 @@ int moss_photometric_loss_roi(int C, int H, int W, const float* image, const flo
  *   segment_active (NULL = none; else one int per segment, meaningful where segment_period[s] > 0 and a multiple of 4): of every
  *     `period` elements of segment s only the first segment_active[s] are ACTIVE (0 = all).  Inactive elements: gradient and moments are
  *     neither read nor written; the parameter takes p <- p (1 - lr wd), which is bit for bit what the full update gives for g = m = v = 0.
+ *     The float4 that holds a period's last active element is read whole: its inactive gradients must be zero (the backward writes
+ *     them so).  Where the shortcut does not apply -- a segment that does not start on a multiple of 4, a period that is not a
+ *     multiple of 4, eps = 0, arrays of 4 GB and more -- every element takes the full update: inactive gradients must then be zero.
  *   inactive_zero != 0: the caller also knows the inactive PARAMETERS to be exactly zero (MOSS initialises features_rest with zeros,
  *     scene/gaussian_model.py:179-181, and 0 x decay = 0): they are not read or written at all.
  */

@@ -21,6 +21,10 @@ struct Segs { int n; long long end[8]; float lr[8]; int period[8], split[8]; flo
 // (what accumulating the views one after the other into one buffer gives), formed here instead of by B passes over the buffers
 struct MoreGrads { int n; const float* g[3]; float scale; };
 
+// WIDE: the arrays are 4 GB or more (moss_adamw_flat_ex accepts any count): the buffer loads below address with a 32-bit byte offset
+// and a 0xffffff00-byte record, so beyond that they would read zeros or wrap while the stores (64-bit pointers) land -- this form
+// loads through 64-bit pointers instead, without the degree-aware shortcut (which needs the out-of-range buffer load).
+template <bool WIDE>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80)))   // (eight waves per SIMD: the scalar file admits six at 106 SGPRs)
 adamw_kernel(long long n, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
              Segs segs, AdamBetas betas, float eps, float weight_decay, float bc1, float bc2_sqrt,
@@ -42,7 +46,7 @@ adamw_kernel(long long n, float* __restrict__ p, const float* __restrict__ g, fl
     // kernel's 165 MB are HBM time)
     const float inv_bc1 = 1.0f / bc1, inv_bc2_sqrt = 1.0f / bc2_sqrt;
     // (buffer loads: an out-of-range offset returns 0 WITHOUT a memory request -- what an element that is not to be read costs; the
-    // arrays of a launch are < 4 GB: launch_adamw falls back to treating everything as active otherwise)
+    // arrays of a launch are < 4 GB here: launch_adamw picks the WIDE form otherwise)
     constexpr uint32_t OOB = 0xffffffffu, RSRC3 = 0x00020000u;
     const __amdgpu_buffer_rsrc_t rs_p = __builtin_amdgcn_make_buffer_rsrc((void*)p, 0, 0xffffff00u, RSRC3);
     const __amdgpu_buffer_rsrc_t rs_g = __builtin_amdgcn_make_buffer_rsrc((void*)g, 0, 0xffffff00u, RSRC3);
@@ -93,7 +97,20 @@ adamw_kernel(long long n, float* __restrict__ p, const float* __restrict__ g, fl
         }
         float pv[4], gv[4], mv[4], vv[4];
         const bool full = i + 4 <= n;
-        if (full) {
+        if (WIDE && full) {
+            const float4 a = reinterpret_cast<const float4*>(p)[i4], b = reinterpret_cast<const float4*>(g)[i4];
+            const float4 c = reinterpret_cast<const float4*>(m)[i4], d = reinterpret_cast<const float4*>(v)[i4];
+            pv[0] = a.x; pv[1] = a.y; pv[2] = a.z; pv[3] = a.w; gv[0] = b.x; gv[1] = b.y; gv[2] = b.z; gv[3] = b.w;
+            mv[0] = c.x; mv[1] = c.y; mv[2] = c.z; mv[3] = c.w; vv[0] = d.x; vv[1] = d.y; vv[2] = d.z; vv[3] = d.w;
+#pragma unroll
+            for (int q = 0; q < 3; q++) if (q < more.n) {    // (the same order and roundings as below; static indices, see above)
+                const float4 e = reinterpret_cast<const float4*>(more.g[q])[i4];
+                gv[0] = __fadd_rn(gv[0], e.x); gv[1] = __fadd_rn(gv[1], e.y); gv[2] = __fadd_rn(gv[2], e.z); gv[3] = __fadd_rn(gv[3], e.w);
+            }
+            if (more.n > 0)
+                for (int k = 0; k < 4; k++) gv[k] = __fmul_rn(gv[k], more.scale);
+            dead4 = false;
+        } else if (full) {
             const uint32_t o = (uint32_t)i * 4u;
             const bool skip_all = dead4 && segs.inactive_zero != 0;
             const v4f a = __builtin_amdgcn_raw_buffer_load_b128(rs_p, skip_all ? OOB : o, 0, 0), b = __builtin_amdgcn_raw_buffer_load_b128(rs_g, dead4 ? OOB : o, 0, 0);
@@ -162,13 +179,18 @@ int launch_adamw(long long n, float* params, const float* grads, float* exp_avg,
         for (int i = 0; i < more.n; i++) more.g[i] = grads_extra[i];
     }
     Segs segs; segs.n = num_segments;
-    // (the degree-aware form addresses the arrays with 32-bit byte offsets: beyond 4 GB per array everything is treated as active)
+    // (the buffer loads address every array -- the extra gradient buffers too -- with 32-bit byte offsets into a 0xffffff00-byte
+    // record: from there on, the WIDE form; it has no degree-aware shortcut, everything is treated as active)
+    const bool wide = (n + 3) / 4 * 16 >= (long long)0xffffff00u;
     // (and eps = 0 would make the full update of an all-zero element 0 x rcp(0) = NaN: no shortcut then)
-    const bool aware = segment_active != nullptr && n < (long long)(0xffffff00u / 4u) && eps > 0.0f;
+    const bool aware = segment_active != nullptr && !wide && eps > 0.0f;
     segs.inactive_zero = aware ? inactive_zero : 0;
     for (int i = 0; i < 8; i++) {
-        segs.active[i] = (aware && i < num_segments && segment_period && segment_period[i] > 0 && segment_active[i] > 0 &&
-                          segment_active[i] < segment_period[i]) ? segment_active[i] : 0;
+        // (the shortcut decides a float4 from its first element's place in the period: that needs the segment to start on a float4 --
+        // with a period that is a multiple of 4, a float4 then never reaches into the next period)
+        const long long seg_start = i == 0 ? 0 : (i < num_segments ? segment_end[i - 1] : 0);
+        segs.active[i] = (aware && i < num_segments && segment_period && segment_period[i] > 0 && (segment_period[i] & 3) == 0 &&
+                          (seg_start & 3) == 0 && segment_active[i] > 0 && segment_active[i] < segment_period[i]) ? segment_active[i] : 0;
         segs.end[i] = i < num_segments ? segment_end[i] : first + n; segs.lr[i] = i < num_segments ? segment_lr[i] : 0.f;
         const bool pat = i < num_segments && segment_period && segment_split && segment_lr2 && segment_period[i] > 0;
         segs.period[i] = pat ? segment_period[i] : 0; segs.split[i] = pat ? segment_split[i] : 0; segs.lr2[i] = pat ? segment_lr2[i] : 0.f;
@@ -177,8 +199,13 @@ int launch_adamw(long long n, float* params, const float* grads, float* exp_avg,
     static const long long max_blocks = knob("MOSS_ADAMW_BLOCKS", 2048);
     if (blocks > max_blocks) blocks = max_blocks;            // (2048: eight 256-thread blocks per CU, all resident at once)
     if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, n, params, grads, exp_avg, exp_avg_sq,
-                       segs, AdamBetas(beta1, beta2), eps, weight_decay, bc1, bc2_sqrt, step_state, first, skip_word, skip_mask, more);
+    // (ONE launch whatever n: every launch advances the device-side step counter)
+    if (wide)
+        hipLaunchKernelGGL(adamw_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, stream, n, params, grads, exp_avg, exp_avg_sq,
+                           segs, AdamBetas(beta1, beta2), eps, weight_decay, bc1, bc2_sqrt, step_state, first, skip_word, skip_mask, more);
+    else
+        hipLaunchKernelGGL(adamw_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, stream, n, params, grads, exp_avg, exp_avg_sq,
+                           segs, AdamBetas(beta1, beta2), eps, weight_decay, bc1, bc2_sqrt, step_state, first, skip_word, skip_mask, more);
     return hipGetLastError() == hipSuccess ? 0 : MOSS_ERR_HIP;
 }
 
@@ -272,6 +299,11 @@ extern "C" int moss_adamw_flat_ex(const moss_adamw_flat_args* a, void* stream)
         a->num_grads_extra < 0 || a->num_grads_extra > 3)
         return MOSS_ERR_INVALID_ARG;
     for (int i = 0; i < a->num_grads_extra; i++) if (!a->grads_extra[i]) return MOSS_ERR_INVALID_ARG;
+    // (the kernel moves float4: 16-byte loads and stores -- at an element index that is a multiple of 4, so every array must start
+    // on 16 bytes, as moss_adamw_multi requires too)
+    uintptr_t align = (uintptr_t)a->params | (uintptr_t)a->grads | (uintptr_t)a->exp_avg | (uintptr_t)a->exp_avg_sq;
+    for (int i = 0; i < a->num_grads_extra; i++) align |= (uintptr_t)a->grads_extra[i];
+    if (align & 15u) return MOSS_ERR_INVALID_ARG;
     if (a->count == 0) return a->step_state ? MOSS_ERR_INVALID_ARG : 0;
     const double bc1 = a->step_state ? 1.0 : 1.0 - pow(a->beta1, a->step), bc2 = a->step_state ? 1.0 : 1.0 - pow(a->beta2, a->step);
     return moss::launch_adamw(a->count, a->params, a->grads, a->exp_avg, a->exp_avg_sq, a->num_segments, a->segment_end, a->segment_lr,

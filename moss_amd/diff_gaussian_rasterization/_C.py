@@ -276,6 +276,18 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
     return res
 
 
+def sh_degree_run(sh) -> int:
+    """The highest SH degree a backward of this module has differentiated the tensor ``sh`` at (-1: none).  Kept on the tensor object
+    itself -- for a training loop that is the SH parameter (``GaussianSet._features``), which ``FlatAdamW`` holds too: its degree-aware
+    update reads it, so a degree raised by ``GaussianSet.oneupSHdegree()`` without the optimizer still reaches the step."""
+    return int(getattr(sh, "_moss_sh_degree_run", -1))
+
+
+def _note_sh_degree(sh, degree):
+    if isinstance(sh, torch.Tensor) and sh.numel() != 0 and int(degree) > sh_degree_run(sh):
+        sh._moss_sh_degree_run = int(degree)
+
+
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
                                  viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_depth, dL_dout_alpha,
                                  sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, alphas, debug, transforms=None,
@@ -302,6 +314,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     sinks = [None if (fused and n in cx.fused_adamw.param_ptrs) else cx._sink(n) for n in ("means3D", "opacity", "sh", "scales", "rotations")]
     if cx.sh_grad_active_only and int(raw_flags) and sinks[2] is not None:
         raw_flags = int(raw_flags) | SH_GRAD_ACTIVE_ONLY
+    _note_sh_degree(sh, degree)
     return tuple(ext().rasterize_gaussians_backward(
         background, means3D, radii, colors, scales, rotations, float(scale_modifier), cov3D_precomp, viewmatrix, projmatrix,
         float(tan_fovx), float(tan_fovy), dL_dout_color, dL_dout_depth, dL_dout_alpha, sh, int(degree), campos, geomBuffer, int(R),

@@ -235,6 +235,24 @@ class FlatAdamW:
             self.fused.struct.sh_active_degree = int(self.sh_active_degree)
             self.fused.struct.sh_inactive_zero = int(self.sh_inactive_zero)
 
+    def _floor_sh_degree(self):
+        """Raise the active SH degree to the highest one a rasterizer backward has run with on the SH parameter
+        (``_C.sh_degree_run``): MOSS calls ``gaussians.oneupSHdegree()`` without the optimizer (train_ZJU.py:85-86), and a degree-aware
+        step below the rasterizer's degree would never read the gradients of the newly active coefficients.  (The update inside the
+        backward floors its degree with the call's own.)  Under graph capture the degree is a launch argument: a stale one is an error
+        -- call ``set_active_sh_degree`` and capture again."""
+        if self.sh_index is None or self.sh_active_degree >= 3:
+            return
+        from .diff_gaussian_rasterization._C import sh_degree_run
+        ran = sh_degree_run(self.bucket.params[self.sh_index])
+        if ran <= self.sh_active_degree:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"FlatAdamW.step() under graph capture: the rasterizer's backward ran at SH degree {ran}, but this optimizer "
+                               f"was told degree {self.sh_active_degree} -- call set_active_sh_degree({ran}) (or oneupSHdegree(optimizer)) "
+                               f"before capturing; the degree is a launch argument of the captured step")
+        self.set_active_sh_degree(ran)
+
     def _seg_active(self):
         act = (C.c_int * self.nseg)(*([0] * self.nseg))
         if self.sh_index is not None and self.sh_active_degree < 3:
@@ -423,6 +441,7 @@ class FlatAdamW:
         if count == 0:
             return
         grads = self.bucket.flat if self.shard is None else self.grad_shard
+        self._floor_sh_degree()
         # ONE entry point for every form (C ABI moss_adamw_flat_ex: host / device step count, shard range, frame guard) -- and the
         # degree-aware SH update (set_active_sh_degree)
         a = AdamWFlatArgs()

@@ -453,3 +453,72 @@ def gradient_scales(fw, bg, means3D, colors_precomp, scales, rotations, scale_mo
             acc[n] += np.abs(g[n].astype(np.float64)) * mj.reshape((P,) + (1,) * (g[n].ndim - 1))
     out.update(acc)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------- AdamW in float64
+# The independent statement of the optimizer update (csrc/optim.hip, csrc/adamw.h) that the GPU tests hold the kernels to.  Everything a
+# kernel is GIVEN in float32 (parameters, gradients, moments, learning rates, eps, weight decay) is taken as those float32 values, and
+# everything after that is evaluated in float64; betas stay the doubles of the C ABI.
+
+def adamw_step_f64(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step):
+    """One ``torch.optim.AdamW`` step (amsgrad off, maximize off) in float64: decoupled weight decay, bias-corrected moments.
+    ``lr`` is a scalar or one rate per element; ``step`` (>= 1) is the step being taken.  Returns float64 (p, m, v)."""
+    p, g, m, v = (np.asarray(a, dtype=np.float64) for a in (p, g, m, v))
+    lr = np.asarray(lr, dtype=np.float64)
+    b1, b2 = float(beta1), float(beta2)
+    bc1, bc2 = 1.0 - b1 ** int(step), 1.0 - b2 ** int(step)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        p = p * (1.0 - lr * float(weight_decay))
+        m = b1 * m + (1.0 - b1) * g
+        v = b2 * v + (1.0 - b2) * g * g
+        p = p - (lr / bc1) * (m / (np.sqrt(v) / np.sqrt(bc2) + float(eps)))
+    return p, m, v
+
+
+def adamw_lr_per_element(first, n, segment_end, segment_lr, segment_period=None, segment_split=None, segment_lr2=None):
+    """The learning rate of each element [first, first + n) of a flat buffer (``moss_adamw_flat_args``): global element j belongs to the
+    first segment s with j < segment_end[s]; where segment_period[s] > 0, element j of the segment takes segment_lr[s] if
+    (j - start_s) % period < split, else segment_lr2[s].  Float32 rates, as the kernel is given them (elements behind the last end: 0)."""
+    j = np.arange(int(first), int(first) + int(n), dtype=np.int64)
+    lr = np.zeros(j.shape, np.float32)
+    done = np.zeros(j.shape, bool)
+    start = 0
+    for s, end in enumerate(segment_end):
+        sel = ~done & (j < int(end))
+        rate = np.full(j.shape, np.float32(segment_lr[s]), np.float32)
+        if segment_period is not None and int(segment_period[s]) > 0:
+            rest = (j - start) % int(segment_period[s]) >= int(segment_split[s])
+            rate[rest] = np.float32(segment_lr2[s])
+        lr[sel] = rate[sel]
+        done |= sel
+        start = int(end)
+    return lr
+
+
+def adamw_inactive_per_element(first, n, segment_end, segment_period, segment_active):
+    """Degree-aware update (``segment_active``): True where element j of a segment with period > 0 and 0 < active < period has
+    (j - start) % period >= active.  Such an element has zero moments by contract; it takes p <- p (1 - lr wd), its moments stay, and
+    its gradient is not part of the step: the update of g = m = v = 0 (``adamw_step_f64`` with g = 0)."""
+    j = np.arange(int(first), int(first) + int(n), dtype=np.int64)
+    out = np.zeros(j.shape, bool)
+    done = np.zeros(j.shape, bool)
+    start = 0
+    for s, end in enumerate(segment_end):
+        sel = ~done & (j < int(end))
+        per, act = int(segment_period[s]) if segment_period is not None else 0, int(segment_active[s])
+        if per > 0 and 0 < act < per:
+            out |= sel & ((j - start) % per >= act)
+        done |= sel
+        start = int(end)
+    return out
+
+
+def adamw_grad_sum_f32(g, extra=(), scale=1.0):
+    """The step's gradient from several buffers (``moss_adamw_flat_args.grads_extra``): ((g + e0) + e1 ...) x scale, every operation
+    rounded to float32 in that order -- the ABI promises these bits.  No extra buffer: ``g`` as it is (the scale is ignored)."""
+    out = np.asarray(g, dtype=np.float32).copy()
+    if len(extra) == 0:
+        return out
+    for e in extra:
+        out = (out + np.asarray(e, dtype=np.float32)).astype(np.float32)
+    return (out * np.float32(scale)).astype(np.float32)

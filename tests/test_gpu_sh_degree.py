@@ -188,3 +188,52 @@ def test_sh_gradient_written_for_the_active_degree_only_on_request(gpu, hip_lib,
     assert not bool(full[:, 3 * k:].any()) and bool((part[:, n4:] == 7.5).all())
     for i in (0, 2, 3, 6, 7):                                # every other gradient is the same
         assert torch.equal(outs[False][i], outs[True][i])
+
+
+@pytest.mark.parametrize("fused", [False, True])
+@pytest.mark.parametrize("active_only", [False, True])
+def test_degree_raised_without_the_optimizer_still_reaches_the_step(gpu, hip_lib, fused, active_only):
+    """MOSS raises the SH degree with ``gaussians.oneupSHdegree()`` -- no optimizer (train_ZJU.py:85-86).  Starting at degree 0 with the
+    optimizer told so, three steps after ``oneupSHdegree()`` give bit for bit the SH parameters and moments of three steps after
+    ``oneupSHdegree(opt)``, and the degree-1 coefficients have moved (with and without MOSS_SH_GRAD_ACTIVE_ONLY; the step inside the
+    backward is the control).  Under graph capture a degree the optimizer was not told is an error, not a silent step."""
+    scene = scenes.config2()
+    raw = thl.th._raw_parameters(scene)
+    dc, dd, da = thl.hp.image_grads(scene.camera.H, scene.camera.W)
+    case = SimpleNamespace(raw=raw, T=thl.bench_transforms(scene.P), tl=None, dc=dc * 1e-3, dd=dd * 1e-3, da=da * 1e-3)
+    res = {}
+    for told in (True, False):
+        b = _Step(scene, gpu, case, fused, 0, aware=True, zero_rest=True)
+        b.ctx.sh_grad_active_only = active_only
+        assert b.opt.sh_active_degree == 0 and b.opt.sh_inactive_zero
+        b.pc.oneupSHdegree(b.opt if told else None)
+        for _ in range(3):
+            b.compute()
+        torch.cuda.synchronize(gpu)
+        off = b.bucket._offset[id(b.pc._features)]
+        sl = slice(off, off + scene.P * 48)
+        res[told] = (b.pc._features.detach().clone(), b.opt.exp_avg[sl].clone(), b.opt.exp_avg_sq[sl].clone())
+    for a, c, what in zip(res[True], res[False], ("sh", "exp_avg", "exp_avg_sq")):
+        assert torch.equal(a, c), what
+    sh, m = res[False][0], res[False][1].view(scene.P, 16, 3)
+    assert bool(sh[:, 1:4, :].any()) and bool(m[:, 1:4, :].any())      # degree 1 has moved and has moments
+    assert not bool(sh[:, 4:, :].any()) and not bool(m[:, 4:, :].any())
+    if fused:
+        return
+    # graph capture: the backward runs at degree 1 (eagerly here), the optimizer still says 0, and the step is captured
+    from moss_amd.gaussian_renderer import camera_view, render
+    b = _Step(scene, gpu, case, False, 0, aware=True, zero_rest=True)
+    b.ctx.sh_grad_active_only = active_only
+    b.pc.oneupSHdegree()
+    b.bucket.detach_grads()
+    out = render(camera_view(scene.camera, gpu), b.pc, b.pipe, scene.bg.to(gpu), transforms=b.T)
+    (out["render"].sum() + out["render_alpha"].sum()).backward()
+    b.bucket.collect()
+    torch.cuda.synchronize(gpu)
+    graph = torch.cuda.CUDAGraph()
+    with pytest.raises(RuntimeError, match="under graph capture"):
+        with torch.cuda.graph(graph):
+            b.opt.step()
+    assert b.opt.sh_active_degree == 0
+    b.opt.step()                                              # eagerly: raised to 1
+    assert b.opt.sh_active_degree == 1

@@ -415,3 +415,41 @@ def test_deterministic_expf_is_the_c_librarys_expf():
     d = hp.inputs_of(scenes.config1(), "precomp")
     a, b = hp.oracle_forward(d), hp.oracle_forward(d, det_exp=True)
     assert np.array_equal(a.n_contrib, b.n_contrib) and np.array_equal(a.final_T, b.final_T)
+
+
+# ------------------------------------------------------------------------------------------------ float64 AdamW reference
+@pytest.mark.parametrize("lr,betas,eps,wd", [(1e-3, (0.9, 0.999), 1e-8, 0.01), (1.6e-4, (0.9, 0.999), 1e-15, 0.0),
+                                             (0.05, (0.8, 0.99), 0.0, 0.01), (2.5e-3, (0.5, 0.9), 1e-3, 0.3)])
+def test_adamw_f64_reference_matches_torch_optim_adamw(lr, betas, eps, wd):
+    """oracle.adamw_step_f64 is torch.optim.AdamW: float64 CPU tensors, twelve steps, against torch's own single-tensor update."""
+    gen = np.random.default_rng(5)
+    p0 = gen.standard_normal(257) * np.exp(gen.uniform(-20, 3, 257))
+    p = torch.nn.Parameter(torch.tensor(p0, dtype=torch.float64))
+    ref = torch.optim.AdamW([p], lr=lr, betas=betas, eps=eps, weight_decay=wd, foreach=False)
+    q, m, v = p0.copy(), np.zeros(257), np.zeros(257)
+    for t in range(1, 13):
+        g = gen.standard_normal(257) * np.exp(gen.uniform(-20, 3, 257))
+        g[:3] = 0.0                                          # (zero gradients from the start: with eps = 0 both sides give 0 / 0)
+        p.grad = torch.tensor(g)
+        ref.step()
+        prev = (q, m, v)
+        q, m, v = oracle.adamw_step_f64(q, g, m, v, lr, betas[0], betas[1], eps, wd, t)
+        st = ref.state[p]
+        for mine, was, theirs in zip((q, m, v), prev, (p.detach(), st["exp_avg"], st["exp_avg_sq"])):
+            theirs = theirs.numpy()
+            assert np.array_equal(np.isnan(mine), np.isnan(theirs))
+            ok = ~np.isnan(mine)
+            # (two float64 evaluations in different orders: a few ulp of the magnitudes involved, cancellation included)
+            assert np.all(np.abs(mine - theirs)[ok] <= 1e-13 * (np.abs(was) + np.abs(mine))[ok]), t
+
+
+def test_adamw_f64_reference_learning_rate_and_gradient_rules():
+    """The segment / periodic learning-rate rule with global indices, the inactive-element rule and the float32 gradient sum."""
+    lr = oracle.adamw_lr_per_element(2, 10, [5, 9, 100], [1, 2, 3], [0, 0, 3], [0, 0, 1], [0, 0, 7])
+    np.testing.assert_array_equal(lr, [1, 1, 1, 2, 2, 2, 2, 3, 7, 7])               # elements 2..11: ends 5, 9; 9 + (0 | 1, 2 | ...)
+    ina = oracle.adamw_inactive_per_element(0, 20, [8, 20], [0, 6], [0, 2])
+    np.testing.assert_array_equal(np.flatnonzero(ina), [10, 11, 12, 13, 16, 17, 18, 19])
+    g, e0, e1 = (np.array(a, np.float32) for a in ([1.0, 2.0 ** 24], [2.0 ** -24, 1.0], [2.0 ** -24, 1.0]))
+    # ((1 + 2^-24) + 2^-24) rounds twice to 1; 2^24 + 1 + 1 rounds twice to 2^24 -- the sum in ANOTHER order would not
+    np.testing.assert_array_equal(oracle.adamw_grad_sum_f32(g, (e0, e1), 1 / 3), np.float32([1.0, 2.0 ** 24]) * np.float32(1 / 3))
+    np.testing.assert_array_equal(oracle.adamw_grad_sum_f32(g, (), 0.5), g)
