@@ -7,7 +7,10 @@ One STEP = one training iteration on one view of the `configs[2]` workload (100k
 Inputs are resident in HBM before the timed region.  N>1 is frame-parallel (one camera per rank, replicas of the
 Gaussians, weak scaling): value = N * steps / max-over-ranks time.
 
-Launch: python bench.py [--gpus N --steps K --warmup W]
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full]
+  Plain (no --full): set up, warm up, time the K steps, write --dump-outputs if given, print the headline line -- nothing else.
+  --full: the same headline, then every side measurement and check (per-kernel replays, rooflines, caller variants, evaluation path,
+  CPU baselines, the other exchanges of N > 1) in the same line.
   N > 1 without a torchrun environment: this process starts `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
   --master-addr 127.0.0.1 --master-port <free> bench.py ...` itself (BEFORE it touches a GPU), relays rank 0's JSON line and exits
   non-zero if any rank failed.  Under torchrun (RANK / WORLD_SIZE set, as the driver launches it) it is one rank of the job.
@@ -124,12 +127,17 @@ def parse_args(argv=None):
                     help="full (default, the metric's form since round 1: L1 / SSIM / mask L2 over the whole frame) or moss: MOSS's OWN expression "
                          "(train_ZJU.py:108-119: L1 and mask L2 over the view's bound_mask, SSIM on its bounding rectangle; "
                          "moss_photometric_loss_roi) -- an analysis aid: `config.loss` says which, the driver's default command is `full`")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-callers", action="store_true", help="skip the drop-in / lbs-in-op caller variants reported beside the headline")
-    ap.add_argument("--callers-only", default="", help="comma-separated names: measure only these caller variants (profiling aid, e.g. "
-                                                         "rocprofv3 --kernel-trace --stats -- python3 bench.py --callers-only patched_moss_pattern)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure and check everything else this file reports: the per-kernel replays and the "
+                         "rooflines, the long re-measurement of a short timed region, the other exchanges (N > 1), the densification "
+                         "side costs, the caller variants, the evaluation path and the CPU baselines.  Without it a run sets up, warms "
+                         "up, times the steps, writes --dump-outputs and prints the headline line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-callers", action="store_true", help="with --full: skip the drop-in / lbs-in-op caller variants reported beside the headline")
+    ap.add_argument("--callers-only", default="", help="with --full: comma-separated names: measure only these caller variants (profiling aid, e.g. "
+                                                         "rocprofv3 --kernel-trace --stats -- python3 bench.py --full --callers-only patched_moss_pattern)")
     ap.add_argument("--cpu-iters", type=int, default=20,
-                    help="iterations of the CPU oracle baseline (about 0.57 s each on one core: 20 = the 10-30 s sample the contract asks for)")
+                    help="with --full: iterations of the CPU oracle baseline (about 0.57 s each on one core: 20 = the 10-30 s sample the contract asks for)")
     ap.add_argument("--dry-run-cpu", action="store_true",
                     help="TEST HOOK (tests/test_host_cpu.py): no GPU work at all -- every rank stands in for its step with a host-side "
                          "gradient bucket, so that the launcher, the rendezvous, the all-reduce, the max-over-ranks timing and the JSON "
@@ -138,7 +146,10 @@ def parse_args(argv=None):
                     help="after the timed steps, write what the last of them computed -- image, alpha, radii, loss terms and the parameters "
                          "AdamW left -- as DIR/<name>.npy (float32; integer arrays as float64), at most 64 MB in all: two builds run with "
                          "the same arguments can be compared output for output")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.callers_only and not args.full:
+        ap.error("--callers-only measures caller variants, which only a --full run does")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -600,8 +611,8 @@ def main(argv=None):
 
     # The step trains (AdamW moves the Gaussians), so the workload drifts from iteration to iteration.  The measurement passes after
     # the timed region restore this snapshot and REPLAY THE SAME K ITERATIONS (the kernels are deterministic), so the per-kernel
-    # durations they report belong to exactly the frames the timed region rendered.
-    snap = opt.snapshot() if hasattr(opt, "snapshot") else None
+    # durations they report belong to exactly the frames the timed region rendered.  (A plain run has no such passes.)
+    snap = opt.snapshot() if (args.full and hasattr(opt, "snapshot")) else None
     h.t_phase = [0.0, 0.0, 0.0]
     h.n_exchange = 0
     note("entering timed region")
@@ -616,14 +627,31 @@ def main(argv=None):
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, h, out)          # (reads only: the passes below restore and replay from the snapshot)
     exchange_rep = h.exchange_report() if (world > 1 and h.n_exchange) else None
+    if world > 1:
+        tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
+        torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
+        elapsed = float(tt.item())
+    was_fused = h.fused_opt                  # (what the TIMED region ran: the rasterizer-only pass of --full takes the step out of the backward)
+
+    def headline_result(out):
+        """The line's headline fields, from the timed region (and, after --full's replays, from their last step: the same frame)."""
+        radii = out["radii"]
+        P = int(radii.numel()); Pv = int((radii > 0).sum().item())
+        R = int(h.ctx.last_needed if args.forward == "async" else h.ctx.last_num_rendered)
+        return _headline_result(args, h, world, elapsed, P, Pv, R, W, H, use_graph, was_fused, exchange_rep,
+                                rccl_ranks=rccl_ranks, backend=torch.distributed.get_backend() if world > 1 else None)
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline_result(out)))
+        return
+
+    # ---- --full: every measurement and check beside the headline -------------------------------------------
     dom_in_region = None
     replicas_identical = None
     if not use_graph:
         dom_in_region = _lib.profile_read()[dominant]          # hipEvent pairs recorded inside the timed region
     if world > 1:
-        tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
-        torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
-        elapsed = float(tt.item())
         # frame-parallel replicas must hold bit-identical parameters after the same sequence of averaged gradients
         if hasattr(opt, "flat_params") and h.exchange_kind != "loss_only":     # (loss_only: independent models, nothing to compare)
             chk = opt.flat_params[:bucket.n_params].double().sum().reshape(1)
@@ -696,7 +724,6 @@ def main(argv=None):
     # rasterizer's.  The same K iterations once more with the step taken by the flat kernel (bit-identical parameters: the frames are the
     # same), every kernel of the op timed: what `rasterizer_roofline` is computed from.
     raster_stage_ms = stage_ms
-    was_fused = h.fused_opt
     if h.fused_opt and snap is not None:
         opt.restore(snap)
         opt.unfuse()
@@ -715,9 +742,8 @@ def main(argv=None):
     if args.forward == "async":
         h.ctx.check_status()                 # also brings num_rendered of the last replayed frame to the host
     # ---- measured problem statistics and the roofline -------------------------------------------------------
-    radii = out["radii"]
-    P = int(radii.numel()); Pv = int((radii > 0).sum().item())
-    R = int(h.ctx.last_needed if args.forward == "async" else h.ctx.last_num_rendered)
+    result = headline_result(out)
+    P, Pv, R = (result["config"][k] for k in ("P", "visible", "num_rendered"))
     N = H * W
     tiles = ((W + 15) // 16) * ((H + 15) // 16)
     fwd_b, bwd_b = algorithmic_bytes(P, Pv, R, N, tiles, 16, args.mode in ("scale_rot", "lbs"), transforms=args.mode == "lbs",
@@ -776,35 +802,7 @@ def main(argv=None):
             stages[k]["traffic_note"] = ("writes = one 48 B gradient record per (entry, block) pair that blended, where the reference adds 36 B per visible "
                                          "Gaussian atomically; reads (traffic_reads) are below the algorithmic 44 R + 28 N")
 
-    result = {
-        "metric": "train iters/sec (fwd+bwd, 512x512, ~100k Gaussians)" if args.config == "cfg3" else f"train iters/sec ({args.config})",
-        "value": round(iters_per_s, 3), "unit": "iters/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"BASELINE configs[2]: {P} Gaussians on a synthetic capsule body, {W}x{H}, SH degree 3, "
-                               f"step = render + L1 + 0.2(1-SSIM) + 0.5 maskL2 + backward + AdamW; one view per GPU per step"
-                               + ("; MOSS's data flow (scales + rotations + a per-Gaussian LBS transform per frame, gaussian_renderer/__init__.py:88-93) "
-                                  "with the covariance product, the getters, the loss and AdamW as this library's kernels and the step replayed as one "
-                                  "hipGraph: what a maintainer gets by applying patches/*.diff; `value_dropin` in this line = the same workload "
-                                  "through the UNCHANGED MOSS call pattern (only the three packages swapped)" if headline else "")
-                   if args.config == "cfg3" else args.config,
-                   "target": args.target, "input_mode": args.mode, "index_order": args.order,
-                   "activations": "torch" if args.torch_activations else ("in_op" if h.pipe.raw_parameters_in_op else "fused"), "P": P, "visible": Pv, "num_rendered": R, "pixels": N,
-                   "parallelism": ("single GPU" if world == 1 else
-                                   (f"`value` = loss_only: frames / subjects sharded over {world} GPUs, one model per GPU, RCCL all-reduce of the "
-                                    f"16-byte loss block (configs[3] as written)" if h.exchange_kind == "loss_only" else
-                                    f"`value` = {h.exchange_kind}: dp{world}, ONE model, frames sharded over {world} GPUs, replicas kept identical by "
-                                    + ("one RCCL all-reduce (mean) of the flat gradient bucket + the full AdamW per rank" if h.exchange_kind == "allreduce"
-                                       else "reduce-scatter + AdamW on the rank's shard + all-gather") + " (SURVEY 8e)")
-                                   + "; value_allreduce / value_sharded / value_loss_only in this line: the same step under each of the three exchanges"),
-                   "forward": args.forward, "launch": h.graph_note if use_graph else "eager launches",
-                   # (was_fused: what the TIMED region ran -- the rasterizer-only pass above takes the step out of the backward afterwards)
-                   "optimizer": ("AdamW step taken by the per-Gaussian backward kernel (moss_raster_backward_raw_adamw); bit-identical to the flat "
-                                 "kernel, reported beside as callers.unfused_optimizer") if was_fused else "flat AdamW kernel over the gradient bucket",
-                   "loss": ("full frame: L1 + 0.2 (1 - SSIM) + 0.5 mask L2 (moss_photometric_loss)" if args.loss == "full" else
-                            "MOSS's own expression: L1 and mask L2 over the view's bound_mask, SSIM on its bounding rectangle (moss_photometric_loss_roi)"),
-                   "glue": "compiled PyTorch-ROCm extension moss_amd/lib/_moss_C.so over the C ABI of libmoss_raster.so",
-                   **({"debug_bits": int(args.debug_bits)} if args.debug_bits else {})},
+    result.update({
         "roofline": {"bound": "hbm", "kernel": dominant, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(achieved / HBM_PEAK_GBS, 5),
                      # the same kernel by SURVEY 8(d)'s bytes ALONE (no optimizer traffic), timed as the plain instantiation in the
@@ -843,19 +841,11 @@ def main(argv=None):
         "step_hbm_frac": round(raster_bytes * (iters_per_s / world) / (HBM_PEAK_GBS * 1e9), 5),
         "step_hbm_frac_incl_optimizer": round(total_bytes * (iters_per_s / world) / (HBM_PEAK_GBS * 1e9), 5),
         "step_algorithmic_bytes_incl_optimizer": int(total_bytes),
-    }
+    })
     if long_run is not None:
         result["long_run"] = long_run
-    if h.graphed is not None:
-        result["graph_recaptures"], result["dropped_frames"] = h.graphed.recaptures, h.graphed.dropped_frames
     if world > 1:
-        result["rccl_ranks"] = rccl_ranks
-        result["backend"] = torch.distributed.get_backend()
         result["replicas_identical"] = replicas_identical
-        result["exchange"] = h.exchange_kind
-        if exchange_rep is not None:
-            result.update({k: v for k, v in exchange_rep.items() if k.endswith("_ms")})
-            result["allreduce_bytes"] = exchange_rep["bytes_reduced"]
         result["exchange_variants"] = exchange_variants
         for kind, rec in (exchange_variants or {}).items():      # every form of the step at top level, whichever one `value` is
             result[f"value_{kind}"] = rec["value"]
@@ -904,6 +894,57 @@ def main(argv=None):
         result["cpu_baseline"] = cpu_baseline(scene, args, gt, gt_mask)
         result["cpu_baseline_autograd"] = cpu_baseline_autograd()
     print(json.dumps(result))
+
+
+def _headline_result(args, h, world, elapsed, P, Pv, R, W, H, use_graph, was_fused, exchange_rep, rccl_ranks=None, backend=None):
+    """The fields of the result line that a plain run reports: the headline figure and what it was measured on, all from the timed
+    region (P / visible / num_rendered: its last frame).  --full adds its measurements to the same dict."""
+    N = H * W
+    headline = args.config == "cfg3" and args.mode == "lbs"
+    iters_per_s = world * args.steps / elapsed
+    result = {
+        "metric": "train iters/sec (fwd+bwd, 512x512, ~100k Gaussians)" if args.config == "cfg3" else f"train iters/sec ({args.config})",
+        "value": round(iters_per_s, 3), "unit": "iters/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"BASELINE configs[2]: {P} Gaussians on a synthetic capsule body, {W}x{H}, SH degree 3, "
+                               f"step = render + L1 + 0.2(1-SSIM) + 0.5 maskL2 + backward + AdamW; one view per GPU per step"
+                               + ("; MOSS's data flow (scales + rotations + a per-Gaussian LBS transform per frame, gaussian_renderer/__init__.py:88-93) "
+                                  "with the covariance product, the getters, the loss and AdamW as this library's kernels and the step replayed as one "
+                                  "hipGraph: what a maintainer gets by applying patches/*.diff"
+                                  + ("; `value_dropin` in this line = the same workload through the UNCHANGED MOSS call pattern (only the three "
+                                     "packages swapped)" if args.full else "") if headline else "")
+                   if args.config == "cfg3" else args.config,
+                   "target": args.target, "input_mode": args.mode, "index_order": args.order,
+                   "activations": "torch" if args.torch_activations else ("in_op" if h.pipe.raw_parameters_in_op else "fused"), "P": P, "visible": Pv, "num_rendered": R, "pixels": N,
+                   "parallelism": ("single GPU" if world == 1 else
+                                   (f"`value` = loss_only: frames / subjects sharded over {world} GPUs, one model per GPU, RCCL all-reduce of the "
+                                    f"16-byte loss block (configs[3] as written)" if h.exchange_kind == "loss_only" else
+                                    f"`value` = {h.exchange_kind}: dp{world}, ONE model, frames sharded over {world} GPUs, replicas kept identical by "
+                                    + ("one RCCL all-reduce (mean) of the flat gradient bucket + the full AdamW per rank" if h.exchange_kind == "allreduce"
+                                       else "reduce-scatter + AdamW on the rank's shard + all-gather") + " (SURVEY 8e)")
+                                   + ("; value_allreduce / value_sharded / value_loss_only in this line: the same step under each of the three exchanges"
+                                      if args.full else "")),
+                   "forward": args.forward, "launch": h.graph_note if use_graph else "eager launches",
+                   # (was_fused: what the TIMED region ran -- the rasterizer-only pass of --full takes the step out of the backward afterwards)
+                   "optimizer": ("AdamW step taken by the per-Gaussian backward kernel (moss_raster_backward_raw_adamw); bit-identical to the flat "
+                                 "kernel" + (", reported beside as callers.unfused_optimizer" if args.full else "")) if was_fused else
+                                "flat AdamW kernel over the gradient bucket",
+                   "loss": ("full frame: L1 + 0.2 (1 - SSIM) + 0.5 mask L2 (moss_photometric_loss)" if args.loss == "full" else
+                            "MOSS's own expression: L1 and mask L2 over the view's bound_mask, SSIM on its bounding rectangle (moss_photometric_loss_roi)"),
+                   "glue": "compiled PyTorch-ROCm extension moss_amd/lib/_moss_C.so over the C ABI of libmoss_raster.so",
+                   **({"debug_bits": int(args.debug_bits)} if args.debug_bits else {})},
+    }
+    if h.graphed is not None:
+        result["graph_recaptures"], result["dropped_frames"] = h.graphed.recaptures, h.graphed.dropped_frames
+    if world > 1:
+        result["rccl_ranks"] = rccl_ranks
+        result["backend"] = backend
+        result["exchange"] = h.exchange_kind
+        if exchange_rep is not None:
+            result.update({k: v for k, v in exchange_rep.items() if k.endswith("_ms")})
+            result["allreduce_bytes"] = exchange_rep["bytes_reduced"]
+    return result
 
 
 def caller_variants(args, dev, scene, cam, gt, gt_mask, bg, lbs_T, steps=100, warmup=10):
@@ -1555,23 +1596,25 @@ def dry_run_cpu(args):
                 "checksum": float(flat_params[:n].double().sum())}
 
     variants[args.exchange] = run(args.exchange)
-    if world > 1:
+    if world > 1 and args.full:                  # (as the GPU path: the other exchanges are measured by --full only)
         for other in [k for k in ("allreduce", "sharded", "loss_only") if k != args.exchange]:
             variants[other] = run(other)
         assert variants["allreduce"]["checksum"] == variants["sharded"]["checksum"], "the two gradient-exchange paths left different parameters"
     head = variants[args.exchange]
     if rank == 0:
-        per_kind = {}
-        for kind, rec in variants.items():
-            per_kind[f"value_{kind}"] = rec["value"]; per_kind[f"ms_per_step_{kind}"] = rec["ms_per_step"]
-            per_kind[f"replicas_identical_{kind}"] = rec["replicas_identical"]
-        print(json.dumps({**per_kind, "metric": "train iters/sec (fwd+bwd, 512x512, ~100k Gaussians)", "value": head["value"],
-                          "unit": "iters/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-                          "ms_per_step": head["ms_per_step"], "higher_is_better": True, "scaling": "weak",
-                          "vs_baseline": None, "dtype": "f32", "data": "DRY RUN: no GPU work (launcher / collective plumbing test)",
-                          "config": {"workload": "dry run", "parallelism": f"`value` = {args.exchange}"}, "rccl_ranks": ranks, "backend": dist.get_backend() if world > 1 else None,
-                          "replicas_identical": all(v["replicas_identical"] for v in variants.values() if v["replicas_identical"] is not None), "exchange": args.exchange,
-                          "allreduce_ms": head["exchange_ms"], "adamw_ms": 0.0, "exchange_variants": variants}))
+        res = {"metric": "train iters/sec (fwd+bwd, 512x512, ~100k Gaussians)", "value": head["value"],
+               "unit": "iters/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+               "ms_per_step": head["ms_per_step"], "higher_is_better": True, "scaling": "weak",
+               "vs_baseline": None, "dtype": "f32", "data": "DRY RUN: no GPU work (launcher / collective plumbing test)",
+               "config": {"workload": "dry run", "parallelism": f"`value` = {args.exchange}"}, "rccl_ranks": ranks, "backend": dist.get_backend() if world > 1 else None,
+               "exchange": args.exchange, "allreduce_ms": head["exchange_ms"], "adamw_ms": 0.0}
+        if args.full:                            # (the replica check and every exchange beside the headline, as the GPU path reports them)
+            for kind, rec in variants.items():
+                res[f"value_{kind}"] = rec["value"]; res[f"ms_per_step_{kind}"] = rec["ms_per_step"]
+                res[f"replicas_identical_{kind}"] = rec["replicas_identical"]
+            res["replicas_identical"] = all(v["replicas_identical"] for v in variants.values() if v["replicas_identical"] is not None)
+            res["exchange_variants"] = variants
+        print(json.dumps(res))
 
 
 if __name__ == "__main__":

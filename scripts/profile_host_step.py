@@ -31,4 +31,4 @@ def spy(self, n, barrier=None):
 
 
 bench.Harness.time_steps = spy
-bench.main(["--callers-only", variant, "--no-cpu-baseline"])
+bench.main(["--full", "--callers-only", variant, "--no-cpu-baseline"])

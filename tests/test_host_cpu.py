@@ -458,7 +458,7 @@ def test_bench_starts_its_own_ranks_and_reports_the_collective(tmp_path):
     Round 5: `value` of an N > 1 line is the DATA-PARALLEL gradient all-reduce (the form that exercises
     RCCL) unless --exchange says otherwise, and every form of the step is at top level -- value_<kind>, ms_per_step_<kind>,
     replicas_identical_<kind> -- whichever one `value` is; config.parallelism says which."""
-    p, lines, json = _run_bench_dry(["--dry-run-cpu"])
+    p, lines, json = _run_bench_dry(["--dry-run-cpu", "--full"])
     assert p.returncode == 0, p.stderr[-2000:]
     assert len(lines) == 1, p.stdout
     res = json.loads(lines[0])
@@ -486,7 +486,7 @@ def test_bench_starts_its_own_ranks_and_reports_the_collective(tmp_path):
 def test_bench_dry_run_every_exchange_as_the_headline(kind):
     """`bench.py --gpus 2 --dry-run-cpu --exchange <kind>` -- each of the three forms as `value`, two ranks in the
     group that ran the collectives, replicas identical for the two gradient exchanges."""
-    p, lines, json = _run_bench_dry(["--dry-run-cpu", "--exchange", kind])
+    p, lines, json = _run_bench_dry(["--dry-run-cpu", "--full", "--exchange", kind])
     assert p.returncode == 0, p.stderr[-2000:]
     res = json.loads(lines[-1])
     assert res["rccl_ranks"] == 2 and res["n_gpus"] == 2 and res["exchange"] == kind
@@ -494,6 +494,30 @@ def test_bench_dry_run_every_exchange_as_the_headline(kind):
     assert res["replicas_identical"] is True                       # over the variants that HAVE replicas (all-reduce, sharded)
     assert res[f"replicas_identical_{kind}"] is (None if kind == "loss_only" else True)
 
+
+@pytest.mark.parametrize("kind", ["allreduce", "loss_only"])
+def test_bench_plain_run_reports_the_headline_alone(kind):
+    """Without --full a run measures its headline and nothing beside it: one exchange timed, no replica check, no other exchange's
+    fields (the dry run reports as the GPU path does)."""
+    p, lines, json = _run_bench_dry(["--dry-run-cpu", "--exchange", kind])
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert len(lines) == 1, p.stdout
+    res = json.loads(lines[0])
+    assert res["n_gpus"] == 2 and res["rccl_ranks"] == 2 and res["steps"] == 5 and res["exchange"] == kind
+    assert res["value"] > 0 and res["ms_per_step"] > 0 and res["unit"] == "iters/s" and res["higher_is_better"] is True
+    assert res["dtype"] == "f32" and kind in res["config"]["parallelism"]
+    assert "exchange_variants" not in res and "replicas_identical" not in res
+    assert not [k for k in res if k.startswith(("value_", "ms_per_step_", "replicas_identical_"))], sorted(res)
+
+
+def test_bench_full_is_off_by_default_and_gates_the_side_options():
+    import bench
+    assert bench.parse_args([]).full is False and bench.parse_args(["--full"]).full is True
+    a = bench.parse_args(["--full", "--no-callers", "--no-cpu-baseline", "--callers-only", "eval"])
+    assert a.no_callers and a.no_cpu_baseline and a.callers_only == "eval"
+    assert not bench.parse_args(["--no-callers", "--no-cpu-baseline"]).full      # (narrowing --full: harmless without it)
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--callers-only", "eval"])                               # measuring callers needs --full: an error, not a no-op
 
 def _avg_order_rank_main(rank, world, port, q):
     """Records, in program order, every collective this rank issues and every avg_supported() decision."""
