@@ -395,6 +395,76 @@ size_t moss_metrics_state_bytes(void);
 int moss_eval_metrics(const moss_eval_metrics_args* args, void* stream);
 
 /*
+ * Per-Gaussian linear blend skinning of MOSS's coarse_deform_c2source (scene/gaussian_model.py:820-923, called from
+ * gaussian_renderer/__init__.py:60,72), from the blend weights to the world-space transform, fused into one launch each way.
+ * Per Gaussian i with v = vert_ids[i] (its nearest big-pose SMPL vertex):
+ *     w = softmax(log(W[v] + 1e-9) + L[i])             (w = W[v] without L: :828-834)
+ *     [B3 | b] = sum_j w_j A_big[j][:3,:]               (:837-839)       [O3 | o] = sum_j w_j A_obs[j][:3,:]   (:904-907)
+ *     Q = B3^-1 (adjugate / determinant; torch.inverse at :841), M = R O3
+ *     T = M Q                                           (`transforms`, :844,913,917)
+ *     t = M (d[i] - Q b) + R o + Th                     (`translation`, :848-850,871,879,898,916,921)
+ *     p = T x[i] + t                                    (`world_src_pts`, :839-842,869,877,896,908-914)
+ * d[i] = (shape_off - pose_off_big + pose_off_obs)[v] is gathered by the caller (:855-898).  Shapes (fp32, contiguous): vert_ids
+ * (P) int64; W (V,J); L (P,J) or NULL; A_big, A_obs (J,4,4) (row 3 is not read); d, x (P,3); R (3,3); Th (3) -- R and Th are DEVICE
+ * pointers, so that a captured graph reads the frame's values at replay.  Outputs: T (P,3,3), t (P,3), p (P,3) (needs x) and w (P,J)
+ * (MOSS's `bweights`), each optional but T and t.  An id outside [0, V) is never dereferenced: that Gaussian's output rows are NaN.
+ * J = 1..64 (SMPL: 24), P >= 0 (0 launches nothing), V >= 1.  A singular B3 gives inf / NaN (the reference raises).
+ */
+typedef struct moss_lbs_forward_args {
+    int32_t P, J, V;
+    const int64_t* vert_ids;
+    const float* weights;                    /* W (V,J) */
+    const float* lbs_offsets;                /* L (P,J) or NULL */
+    const float* A_big;                      /* (J,4,4) */
+    const float* A_obs;                      /* (J,4,4) */
+    const float* d;                          /* (P,3) */
+    const float* R;                          /* (3,3) */
+    const float* Th;                         /* (3) */
+    const float* x;                          /* (P,3) or NULL */
+    float* T;                                /* (P,3,3) */
+    float* t;                                /* (P,3) */
+    float* p;                                /* (P,3) or NULL; needs x */
+    float* w;                                /* (P,J) or NULL */
+} moss_lbs_forward_args;
+/* One launch on `stream`; no host synchronisation, no allocation: capturable.  Returns 0 or a negative error code. */
+int moss_lbs_deform_forward(const moss_lbs_forward_args* args, void* stream);
+
+/*
+ * Backward of moss_lbs_deform_forward (the autograd of the same reference lines), given the incoming gradients g_T (P,3,3), g_t (P,3)
+ * and g_p (P,3; needs x), each NULL when zero.  The forward is recomputed per Gaussian.  Outputs, each optional:
+ *   g_L (P,J; needs L): the gradient of the LBS offsets (the softmax's backward); g_d (P,3); g_x (P,3; needs x);
+ *   g_A_obs (J,4,4): sum over the Gaussians of w_ij [gO3 | go] (row 3 written as zero) -- a two-level reduction in a fixed order
+ *     (per-workgroup sums in `workspace`, then one fold launch in workgroup order, in float64): no float atomics, bitwise reproducible.
+ *   workspace: moss_lbs_workspace_bytes(P, J) device bytes (needed with g_A_obs).
+ * A_big, R, Th and W get no gradient (constants in MOSS).  Rows of Gaussians with an out-of-range id are NaN in g_L / g_d / g_x and
+ * add nothing to g_A_obs.  Two launches on `stream` (one without g_A_obs); no host synchronisation, no allocation, no memset:
+ * capturable.  P = 0 launches nothing (g_A_obs is then not written).
+ */
+typedef struct moss_lbs_backward_args {
+    int32_t P, J, V;
+    const int64_t* vert_ids;
+    const float* weights;
+    const float* lbs_offsets;
+    const float* A_big;
+    const float* A_obs;
+    const float* d;
+    const float* R;
+    const float* Th;
+    const float* x;
+    const float* g_T;                        /* (P,3,3) or NULL */
+    const float* g_t;                        /* (P,3) or NULL */
+    const float* g_p;                        /* (P,3) or NULL; needs x */
+    float* g_L;                              /* (P,J) or NULL; needs lbs_offsets */
+    float* g_A_obs;                          /* (J,4,4) or NULL */
+    float* g_d;                              /* (P,3) or NULL */
+    float* g_x;                              /* (P,3) or NULL; needs x */
+    char* workspace; size_t workspace_bytes;
+} moss_lbs_backward_args;
+int moss_lbs_deform_backward(const moss_lbs_backward_args* args, void* stream);
+/* device bytes of the backward's workspace (host-side arithmetic); 0 for P <= 0 or J outside 1..64 */
+size_t moss_lbs_workspace_bytes(int P, int J);
+
+/*
  * k nearest reference points of every query point, 3-D, exact, k = 1..4: replaces the third-party
  * `knn_cuda.KNN(k, transpose_mode=True)(ref, query)` MOSS calls at scene/gaussian_model.py:85-86,586,657,759,827 (a CUDA-only
  * binary wheel, not in the repository; parity unpinned by the reference).

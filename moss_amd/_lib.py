@@ -79,6 +79,12 @@ def _declare(lib):
     lib.moss_metrics_state_bytes.argtypes = []
     lib.moss_eval_metrics.restype = _i
     lib.moss_eval_metrics.argtypes = [_p, _p]
+    lib.moss_lbs_workspace_bytes.restype = C.c_size_t
+    lib.moss_lbs_workspace_bytes.argtypes = [_i, _i]
+    lib.moss_lbs_deform_forward.restype = _i
+    lib.moss_lbs_deform_forward.argtypes = [_p, _p]
+    lib.moss_lbs_deform_backward.restype = _i
+    lib.moss_lbs_deform_backward.argtypes = [_p, _p]
     lib.moss_photometric_loss_roi.restype = _i
     lib.moss_photometric_loss_roi.argtypes = [_i, _i, _i, _p, _p, _p, _p, _p, _p, _f, _f, _f, _p, _p, _p, _p, C.c_size_t, _p]
     lib.moss_adamw_flat_ex.restype = _i
@@ -127,6 +133,23 @@ class EvalMetricsArgs(C.Structure):
                 ("gt", C.c_void_p * 8), ("bound", C.c_void_p * 8), ("out_image", C.c_void_p * 8), ("fill", C.c_float),
                 ("state", C.c_void_p), ("per_view", C.c_void_p), ("per_view_capacity", C.c_int32), ("workspace", C.c_void_p),
                 ("workspace_bytes", C.c_size_t)]
+
+
+_LBS_INPUTS = [("P", C.c_int32), ("J", C.c_int32), ("V", C.c_int32), ("vert_ids", C.c_void_p), ("weights", C.c_void_p),
+               ("lbs_offsets", C.c_void_p), ("A_big", C.c_void_p), ("A_obs", C.c_void_p), ("d", C.c_void_p), ("R", C.c_void_p),
+               ("Th", C.c_void_p), ("x", C.c_void_p)]
+
+
+class LbsForwardArgs(C.Structure):
+    """``moss_lbs_forward_args`` of include/moss_raster.h (``moss_lbs_deform_forward``: per-Gaussian LBS transforms of a frame)."""
+    _fields_ = _LBS_INPUTS + [("T", C.c_void_p), ("t", C.c_void_p), ("p", C.c_void_p), ("w", C.c_void_p)]
+
+
+class LbsBackwardArgs(C.Structure):
+    """``moss_lbs_backward_args`` of include/moss_raster.h (``moss_lbs_deform_backward``)."""
+    _fields_ = _LBS_INPUTS + [("g_T", C.c_void_p), ("g_t", C.c_void_p), ("g_p", C.c_void_p), ("g_L", C.c_void_p),
+                              ("g_A_obs", C.c_void_p), ("g_d", C.c_void_p), ("g_x", C.c_void_p), ("workspace", C.c_void_p),
+                              ("workspace_bytes", C.c_size_t)]
 
 
 OPT_BITS = {"means3D": 1, "sh": 2, "opacity": 4, "scales": 8, "rotations": 16}      # MOSS_OPT_*; position = index in the struct's arrays

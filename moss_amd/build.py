@@ -38,6 +38,7 @@ SOURCES = {
     "blend.hip": [],
     "loss.hip": [],
     "metrics.hip": [],
+    "lbs.hip": [],
     "optim.hip": [],
     "activations.hip": [],
     "densify.hip": [],

@@ -390,4 +390,7 @@ __device__ __forceinline__ uint32_t rect_area(uint2 r)
     return w * h;
 }
 
+// sets the text moss_last_error() returns (defined in raster_api.hip, for the entry points of the other translation units)
+int set_last_error(int code, const char* msg);
+
 }  // namespace moss

@@ -132,6 +132,13 @@ FrameParams make_params(int P, int D, int M, int W, int H, float tan_fovx, float
 
 }  // namespace
 
+// the error text of an entry point of another translation unit (moss_last_error); returns `code`
+int moss::set_last_error(int code, const char* msg)
+{
+    snprintf(g_err, sizeof(g_err), "%s", msg);
+    return code;
+}
+
 // The forward of every form of the call (include/moss_raster.h: moss_raster_forward_args).  The argument rules of the extensions are
 // checked here, once.
 static int forward_impl(const moss_raster_forward_args& a, void* stream)

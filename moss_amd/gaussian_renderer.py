@@ -2,8 +2,9 @@
 MOSS that changes when the rasterizer is swapped (north_star).  Same call signature, same settings construction
 (:36-52), same zero ``means2D`` gradient sink (:29-33), same input-mode selection (:85-109), same output keys (:124-136).
 
-Out of scope here: the LBS / pose-refinement branch (:57-72).  If ``pc`` offers
-``coarse_deform_c2source`` it is called exactly as the reference does; otherwise the Gaussians render where they are
+Out of scope here: the pose-refinement networks of the LBS branch (:57-72).  If ``pc`` offers
+``coarse_deform_c2source`` it is called exactly as the reference does (with ``pipe.lbs_in_op``: the fused HIP deformation of
+moss_amd/lbs.py instead, same arguments); otherwise the Gaussians render where they are
 (optionally moved by explicit ``transforms`` / ``translation``, the cheap branch :73-77).
 """
 from __future__ import annotations
@@ -101,6 +102,19 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
         # = torch.matmul(transforms, means3D[..., None]).squeeze(-1) (reference :74-75), written as an elementwise product + row sum:
         # a batched GEMM over 100k 3x3 matrices goes through hipBLASLt on MI355X and costs ~0.9 ms per call (and twice more backward)
         means3D = (transforms * means3D[..., None, :]).sum(-1) + (0 if translation is None else translation)
+    elif hasattr(pc, "coarse_deform_c2source") and getattr(pipe, "lbs_in_op", False):
+        # ``pipe.lbs_in_op`` (an addition, default off): the deformation runs as the fused HIP op (moss_amd/lbs.py; ``pc`` supplies
+        # SMPL_NEUTRAL and knn).  With pose_in_op + transforms_in_op the op gets the canonical x with T and t (MOSS_RAW_POSE).
+        from .lbs import coarse_deform_c2source
+        _, world, bweights, transforms, translation = coarse_deform_c2source(
+            pc, means3D[None], viewpoint_camera.smpl_param, viewpoint_camera.big_pose_smpl_param,
+            viewpoint_camera.big_pose_world_vertex[None], return_transl=True)
+        if (getattr(pipe, "pose_in_op", False) and getattr(pipe, "transforms_in_op", False) and not pipe.compute_cov3D_python
+                and not pipe.convert_SHs_python):
+            raw_flags |= 16                                  # _C.RAW_POSE
+            op_translation = translation.squeeze(0)
+        else:
+            means3D = world
     elif hasattr(pc, "coarse_deform_c2source"):
         _, means3D, bweights, transforms, translation = pc.coarse_deform_c2source(
             means3D[None], viewpoint_camera.smpl_param, viewpoint_camera.big_pose_smpl_param,
