@@ -4,8 +4,8 @@ In-tree build: the .so is git-ignored but travels to the GPU box with the repo s
 ``python -m moss_amd.build [--force] [--diag]``
 
 ``--diag`` builds the DIAGNOSTIC variant into ``moss_amd/lib_diag/`` as well: the same sources with ``-DMOSS_DIAG`` plus
-``scripts/diag/knobs.cpp`` -- MOSS_* environment knobs that select kernel variants for A/B timing (some give wrong results on
-purpose) and the stamp buffers of the timeline scripts.  The product build in ``moss_amd/lib/`` has neither and reads no environment
+``scripts/diag/knobs.cpp`` -- MOSS_* environment knobs that tune the product's kernels for A/B timing, and the stamp buffers of
+the timeline scripts.  The product build in ``moss_amd/lib/`` has neither and reads no environment
 variable; ``MOSS_AMD_LIB_DIR=lib_diag`` makes ``moss_amd._lib`` load the diagnostic pair instead (scripts/ only).
 """
 from __future__ import annotations

@@ -511,19 +511,6 @@ __device__ __forceinline__ uint32_t lds_peek(const uint32_t* p)
 }
 __device__ __forceinline__ void lds_poke(uint32_t* p, uint32_t v) { *(volatile lds_u32_t*)p = v; }
 
-// s_setprio takes an immediate
-__device__ __forceinline__ void set_wave_prio(int p)
-{
-    switch (p) {
-        case 0: __builtin_amdgcn_s_setprio(0); break;
-        case 1: __builtin_amdgcn_s_setprio(1); break;
-        case 2: __builtin_amdgcn_s_setprio(2); break;
-        default: __builtin_amdgcn_s_setprio(3); break;
-    }
-}
-// issue priority of an item by the length of its tile's list: the longest items set the kernel's duration
-__device__ __forceinline__ int prio_of_length(uint32_t n) { return n >= 2048u ? 3 : n >= 1024u ? 2 : n >= 512u ? 1 : 0; }
-
 // SCANNER of a heavy item: block masks -> hit list -> record DMAs -> `ready`.  nx = the first chapter of masks (requested by the
 // caller before it waited for the blender to release the ring).
 __device__ __forceinline__ void heavy_forward_scan(int blk, int lane, const uint2 rg, const float4* __restrict__ inst_rec,
@@ -614,7 +601,7 @@ template <bool EXACT>
 __device__ __forceinline__ void heavy_forward_blend(int W, int H, int gx, int tile, int blk, int lane, const uint2 rg,
                                                     PairRing* L, PairCtl* ctl, uint32_t seq, const float* __restrict__ bg_color,
                                                     float* __restrict__ out_color, float* __restrict__ out_depth, float* __restrict__ out_alpha,
-                                                    float* __restrict__ final_T, uint32_t* __restrict__ n_contrib, int flags,
+                                                    float* __restrict__ final_T, uint32_t* __restrict__ n_contrib,
                                                     unsigned long long* stamp_out, SegEmit& se, uint32_t* __restrict__ tail_start)
 {
     constexpr int RMASK = PairRing::RMASK;
@@ -741,33 +728,31 @@ __device__ __forceinline__ void heavy_forward_blend(int W, int H, int gx, int ti
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         n_rounds++;
-        if (!(flags & 2)) {
-            const unsigned long long t4 = STAMP();
-            if (t_first == 0) t_first = t4 - t_begin;
-            n_trips += ntrip;
-            auto get = [&](int t) -> Fetched {
-                // (C and 4t are multiples of four and wave-uniform: the ring index of the trip is a SCALAR, the slot is added without a
-                // wrap test -- one vector add for the address where `(C + 4t + slot) & RMASK` per lane was five instructions)
-                const int li = ((C + 4 * t) & RMASK) + slot;
-                Fetched f;
-                f.a = L->a[li]; f.b = L->b[li]; f.c = L->c[li];
-                f.pos1 = f.a.w;                                                             // the entry's 1-based list position (merge_gather)
-                return f;
-            };
-            Fetched f0 = get(0);
-            for (int t = 0; t < ntrip; t += 2) {
-                const Fetched f1 = get(t + 1);                                             // next trip's LDS reads under this trip
-                cut_if_due();
-                if (trip(f0)) { finished = true; break; }
-                note_cut_due(f0, C + 4 * (t + 1));
-                if (t + 1 >= ntrip) break;
-                f0 = get(t + 2);
-                cut_if_due();
-                if (trip(f1)) { finished = true; break; }
-                note_cut_due(f1, C + 4 * (t + 2));
-            }
-            d_trip += STAMP() - t4;
+        const unsigned long long t4 = STAMP();
+        if (t_first == 0) t_first = t4 - t_begin;
+        n_trips += ntrip;
+        auto get = [&](int t) -> Fetched {
+            // (C and 4t are multiples of four and wave-uniform: the ring index of the trip is a SCALAR, the slot is added without a
+            // wrap test -- one vector add for the address where `(C + 4t + slot) & RMASK` per lane was five instructions)
+            const int li = ((C + 4 * t) & RMASK) + slot;
+            Fetched f;
+            f.a = L->a[li]; f.b = L->b[li]; f.c = L->c[li];
+            f.pos1 = f.a.w;                                                             // the entry's 1-based list position (merge_gather)
+            return f;
+        };
+        Fetched f0 = get(0);
+        for (int t = 0; t < ntrip; t += 2) {
+            const Fetched f1 = get(t + 1);                                             // next trip's LDS reads under this trip
+            cut_if_due();
+            if (trip(f0)) { finished = true; break; }
+            note_cut_due(f0, C + 4 * (t + 1));
+            if (t + 1 >= ntrip) break;
+            f0 = get(t + 2);
+            cut_if_due();
+            if (trip(f1)) { finished = true; break; }
+            note_cut_due(f1, C + 4 * (t + 2));
         }
+        d_trip += STAMP() - t4;
         C += 4 * ntrip;
         if (finished) { lds_poke(&ctl->stop_seq, seq); break; }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");        // (the ring reads above are complete before the slots are given back)
@@ -835,7 +820,7 @@ __device__ __forceinline__ void heavy_backward_item(int W, int H, int gx, int ti
                                                     const float* __restrict__ final_Ts, const uint32_t* __restrict__ n_contrib,
                                                     const float* __restrict__ dL_dpixels, const float* __restrict__ dL_ddepths,
                                                     const float* __restrict__ dL_dalphas, float* __restrict__ inst_grad,
-                                                    uint32_t* __restrict__ cell_valid, int flags,
+                                                    uint32_t* __restrict__ cell_valid,
                                                     int lo, int hi_limit, const float* __restrict__ seg_state)
 {
     // Walks the list positions [lo, end) of the block back to front.  seg_state == NULL: the block's own item -- its range ends where
@@ -1039,7 +1024,7 @@ __device__ __forceinline__ void heavy_backward_item(int W, int H, int gx, int ti
         C = __builtin_amdgcn_readfirstlane(C); nlist = __builtin_amdgcn_readfirstlane(nlist);
         const int avail = nlist - C;
         const int ntrip = (avail >> 2) + ((scan_done && (avail & 3) != 0) ? 1 : 0);
-        if (ntrip > 0 && !(flags & 2)) {
+        if (ntrip > 0) {
             auto get = [&](int ring_slot) -> Fetched {                                      // (scalar ring index + slot: see the forward kernel)
                 const int li = ring_slot + slot;
                 Fetched f;
@@ -1068,17 +1053,13 @@ __device__ __forceinline__ void heavy_backward_item(int W, int H, int gx, int ti
 // algorithmic bytes).  Tiles are dealt to the queues in LPT order, rank r -> queue r % nq; of a queue's tiles the first hx are
 // heavy (16 block items each), the rest light (4 quadrant items each).
 struct WaveItem { int tile, sub, rank; bool heavy, valid; uint2 rg; };
-// The FIRST item of a wave is its own rank among the waves of its queue -- no atomic: with one returning atomic per wave at kernel
-// start the last of 1024 waves waited 2-12 us for its first item (same-line atomics serialise, see common.h).  Later items:
-// (waves of the queue) + the value of the queue head.
+// The wave's next item: the value of the queue head.
 __device__ __forceinline__ WaveItem pull_item(uint32_t* my_head, int lane, int nq, int qx, int hx, int n_work,
-                                              const uint4* __restrict__ work_table, int first_rank, int q_waves)
+                                              const uint4* __restrict__ work_table)
 {
-    int qi = first_rank;
-    if (first_rank < 0) {
-        if (lane == 0) qi = (int)atomicAdd(my_head, 1u) + q_waves;
-        qi = __builtin_amdgcn_readfirstlane(qi);
-    }
+    int qi = -1;
+    if (lane == 0) qi = (int)atomicAdd(my_head, 1u);
+    qi = __builtin_amdgcn_readfirstlane(qi);
     WaveItem it;
     it.heavy = qi < WAVE_BLOCKS * hx;
     const int k = it.heavy ? (qi >> 4) : hx + ((qi - WAVE_BLOCKS * hx) >> 2);
@@ -1092,10 +1073,14 @@ __device__ __forceinline__ WaveItem pull_item(uint32_t* my_head, int lane, int n
     return it;
 }
 
-// PAIRS = wave pairs per workgroup: 2 (256 threads, four workgroups per CU: the product configuration) or 8 (ONE 1024-thread workgroup
-// per CU, all its pairs sharing LDS: the experimental form, diagnostic builds only, MOSS_FWD_PAIRS=8).
-template <int PAIRS, bool EXACT>
-__global__ void __launch_bounds__(128 * PAIRS)
+// The forward kernel's LDS: per pair a record ring + hit list, the cuts of the block being blended, and the control words.
+constexpr size_t FWD_LDS_BYTES = (size_t)FWD_PAIRS_PER_WG * (sizeof(PairRing) + sizeof(float) * MAX_CUTS * 16 * 6 + sizeof(uint2) * MAX_CUTS + sizeof(PairCtl));
+// FWD_PAIRS_PER_WG = 2 wave pairs per 256-thread workgroup, four workgroups per CU.  (Measured, round 3: eight pairs in ONE workgroup
+// per CU -- the form in which pairs could hand work to each other through LDS -- is 47.1 us against 40.4: its sixteen waves are of one
+// age, the SIMD arbiter then shares issue slots evenly, and the longest item runs at ~760 cycles per trip for as long as its SIMD-mate
+// lives instead of at 520-610 as the older wave of two workgroups.)
+template <bool EXACT>
+__global__ void __launch_bounds__(256)
 blend_forward_wave_kernel(int W, int H, int gx, int T_tiles, const uint32_t* __restrict__ tile_order, uint32_t* __restrict__ header,
                           uint32_t* __restrict__ queue_head, const uint4* __restrict__ work_table, const float4* __restrict__ inst_rec,
                           const uint16_t* __restrict__ inst_bmask,
@@ -1103,17 +1088,16 @@ blend_forward_wave_kernel(int W, int H, int gx, int T_tiles, const uint32_t* __r
                           float* __restrict__ out_alpha, float* __restrict__ final_T, uint32_t* __restrict__ n_contrib, int flags,
                           unsigned long long* __restrict__ stamps /* optional diagnostics: 8 words per item, else NULL */,
                           uint4* __restrict__ seg_desc, float* __restrict__ seg_state, uint32_t seg_cap, int seg_hits,
-                          uint32_t* __restrict__ tail_start, uint32_t* __restrict__ seg_counts, int role_swap, int prio_mode,
+                          uint32_t* __restrict__ tail_start, uint32_t* __restrict__ seg_counts,
                           int seg_store /* 0: MOSS_FORWARD_ONLY -- cut (same image bits as the training forward) but keep nothing */)
 {
-    // Two wave PAIRS per workgroup (see PairCtl): per pair a record ring + hit list, the cuts of the block being blended, and the
-    // control words.  A light item uses 3 KB of the pair's ring per wave as its record ring.
-    // (dynamic LDS, FwdLds<PAIRS>::bytes: eight pairs are 157 KB, beyond what a static allocation may hold)
+    // Two wave PAIRS per workgroup (see PairCtl), FWD_LDS_BYTES of dynamic LDS.  A light item uses 3 KB of the pair's ring per wave as
+    // its record ring.
     extern __shared__ __attribute__((aligned(16))) char s_fwd_lds[];
     PairRing* const s_ring = reinterpret_cast<PairRing*>(s_fwd_lds);
-    float (*const s_cut_sums)[MAX_CUTS * 16 * 6] = reinterpret_cast<float (*)[MAX_CUTS * 16 * 6]>(s_ring + PAIRS);
-    uint2 (*const s_cut_pos)[MAX_CUTS] = reinterpret_cast<uint2 (*)[MAX_CUTS]>(s_cut_sums + PAIRS);
-    PairCtl* const s_ctl = reinterpret_cast<PairCtl*>(s_cut_pos + PAIRS);
+    float (*const s_cut_sums)[MAX_CUTS * 16 * 6] = reinterpret_cast<float (*)[MAX_CUTS * 16 * 6]>(s_ring + FWD_PAIRS_PER_WG);
+    uint2 (*const s_cut_pos)[MAX_CUTS] = reinterpret_cast<uint2 (*)[MAX_CUTS]>(s_cut_sums + FWD_PAIRS_PER_WG);
+    PairCtl* const s_ctl = reinterpret_cast<PairCtl*>(s_cut_pos + FWD_PAIRS_PER_WG);
     static_assert(sizeof(PairRing) >= 2 * 64 * 3 * sizeof(float4), "the light path's rings live inside the pair's ring");
     static_assert(sizeof(PairRing) % 16 == 0, "the arrays behind the rings stay 16-byte aligned");
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), pair = wv >> 1;   // (the wave's index is wave-uniform: say so)
@@ -1122,14 +1106,12 @@ blend_forward_wave_kernel(int W, int H, int gx, int T_tiles, const uint32_t* __r
     // chain of the kernel is (header | table entry) -> block masks -> records -> first trip: three round trips where round 2 had
     // five (header -> tile order -> range -> masks -> records).
     const int nq_ = min(NUM_XCD_QUEUES, (int)gridDim.x), qx_ = (int)blockIdx.x % nq_;
-    const int first_qi = ((int)blockIdx.x / nq_) * PAIRS + pair;
+    const int first_qi = ((int)blockIdx.x / nq_) * FWD_PAIRS_PER_WG + pair;
     const uint4 first_wt = work_table[min((first_qi >> 4) * nq_ + qx_, T_tiles - 1)];
     // Which wave of the pair blends: the waves of a workgroup sit on SIMD 0..3 in order, and a CU hosts several workgroups -- the roles
     // are swapped between them so that a SIMD gets blenders (busy) and scanners (mostly waiting) in equal numbers.
-    // (eight pairs in one workgroup: pairs p and p + 2 sit on the same two SIMDs -- the roles swap between them)
-    const bool is_scanner = PAIRS == 2 ? (((wv ^ role_swap ^ (int)((blockIdx.x >> 3) / 32u)) & 1) == 0)
-                                       : (((wv ^ role_swap ^ (pair >> 1)) & 1) == 0);
-    if (threadIdx.x < PAIRS * (int)(sizeof(PairCtl) / 4)) reinterpret_cast<uint32_t*>(s_ctl)[threadIdx.x] = 0u;
+    const bool is_scanner = ((wv ^ (int)((blockIdx.x >> 3) / 32u)) & 1) == 0;
+    if (threadIdx.x < FWD_PAIRS_PER_WG * (int)(sizeof(PairCtl) / 4)) reinterpret_cast<uint32_t*>(s_ctl)[threadIdx.x] = 0u;
     // header[8] = this kernel's grid: the backward kernel numbers the cuts by it (how many pairs share a segment region), whatever
     // instantiation -- product or MOSS_DEBUG_EXACT_MATH, with its own residency -- the forward call ran
     if (blockIdx.x == 0 && threadIdx.x == 0) header[8] = gridDim.x;
@@ -1141,8 +1123,8 @@ blend_forward_wave_kernel(int W, int H, int gx, int T_tiles, const uint32_t* __r
     const int nq = min(NUM_XCD_QUEUES, (int)gridDim.x), qx = (int)blockIdx.x % nq;
     const int n_heavy = (int)header[7];
     const int hx = n_heavy > qx ? (n_heavy - qx + nq - 1) / nq : 0;
-    const int q_pairs = PAIRS * (((int)gridDim.x - qx + nq - 1) / nq);                // pairs that pull from this queue
-    const int my_rank = ((int)blockIdx.x / nq) * PAIRS + pair;                        // this pair's rank among them
+    const int q_pairs = FWD_PAIRS_PER_WG * (((int)gridDim.x - qx + nq - 1) / nq);     // pairs that pull from this queue
+    const int my_rank = ((int)blockIdx.x / nq) * FWD_PAIRS_PER_WG + pair;             // this pair's rank among them
     uint32_t* const my_head = queue_head + (size_t)qx * QLINE_WORDS;
     // queue index -> item.  Of a queue's tiles the first hx are heavy (16 block items each), the rest light (4 quadrant items each).
     auto decode = [&](int qi) -> WaveItem {
@@ -1189,8 +1171,6 @@ blend_forward_wave_kernel(int W, int H, int gx, int T_tiles, const uint32_t* __r
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             if (lane == 0) lds_poke(&ctl->post_seq, seq);
             if (!heavy) { light_qi = it.valid ? qi : -1; break; }
-            if (prio_mode == 2) set_wave_prio(prio_of_length(rg.y - rg.x));
-            else if (prio_mode == 3) set_wave_prio(min(3, prio_of_length(rg.y - rg.x) + 1));
             heavy_forward_scan(it.sub, lane, rg, inst_rec, inst_bmask, L, ctl, seq, flags, nx);
             qi = pop();
         }
@@ -1215,22 +1195,14 @@ blend_forward_wave_kernel(int W, int H, int gx, int T_tiles, const uint32_t* __r
             if (lds_peek(&ctl->post_kind) == 0u) break;
             const int tile = (int)lds_peek(&ctl->post_tile), blk = (int)lds_peek(&ctl->post_blk), rank = (int)lds_peek(&ctl->post_rank);
             const uint2 rg = make_uint2(lds_peek(&ctl->rg_x), lds_peek(&ctl->rg_y));
-            // (4: every blender above every scanner; 5: additionally the blenders of the LATER dispatch rounds above those of the
-            // earlier ones -- priority outranks age, so this turns the age order of a SIMD's two blenders around; 6: all blenders 3)
-            if (prio_mode == 4) set_wave_prio(1);
-            else if (prio_mode == 5) set_wave_prio(((int)blockIdx.x * 4 / (int)gridDim.x) >= 2 ? 2 : 1);
-            else if (prio_mode == 6) set_wave_prio(3);
-            else if (prio_mode == 7) set_wave_prio(1 + ((int)blockIdx.x * 4 / (int)gridDim.x) / 2);
-            else if (prio_mode != 0) set_wave_prio(prio_of_length(rg.y - rg.x));
             heavy_forward_blend<EXACT>(W, H, gx, tile, blk, lane, rg, L, ctl, seq, bg_color, out_color, out_depth, out_alpha, final_T, n_contrib,
-                                flags, stamps ? stamps + (size_t)(rank * WAVE_BLOCKS + blk) * 8 : nullptr, se, tail_start);
+                                stamps ? stamps + (size_t)(rank * WAVE_BLOCKS + blk) * 8 : nullptr, se, tail_start);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             if (lane == 0) lds_poke(&ctl->fin_seq, seq);
         }
         // how many of its slots this pair filled (EVERY pair writes its count: the backward kernel sums them per region)
         if (lane == 0 && my_rank < MAX_FWD_QUEUE_WAVES && se.store) seg_counts[(size_t)qx * MAX_FWD_QUEUE_WAVES + my_rank] = se.count;
     }
-    if (prio_mode != 0) set_wave_prio(0);
     // ---- light phase: every wave on its own (queue indices only grow: once a pair has drawn a light item, heavy ones are gone)
     for (;;) {
         const int qi = light_qi >= 0 ? light_qi : pop();
@@ -1244,7 +1216,7 @@ blend_forward_wave_kernel(int W, int H, int gx, int T_tiles, const uint32_t* __r
     // Tiles without instances get the background only (forward.cu:374-382 with an empty range); done after the queue so that
     // the heavy items start immediately.
     const int pl = lane >> 2;
-    const int wave_id = (int)blockIdx.x * (2 * PAIRS) + wv, n_waves = (int)gridDim.x * (2 * PAIRS);
+    const int wave_id = (int)blockIdx.x * (2 * FWD_PAIRS_PER_WG) + wv, n_waves = (int)gridDim.x * (2 * FWD_PAIRS_PER_WG);
     for (int i = WAVE_BLOCKS * n_work + wave_id; i < WAVE_BLOCKS * T_tiles; i += n_waves) {
         const int tile = (int)tile_order[i >> 4], blk = i & 15;
         const int px = (tile % gx) * TILE + (blk & 3) * 4 + (pl & 3), py = (tile / gx) * TILE + (blk >> 2) * 4 + (pl >> 2);
@@ -1267,7 +1239,7 @@ blend_backward_wave_kernel(int W, int H, int gx, const uint4* __restrict__ work_
                            float* __restrict__ inst_grad /* the record pool: [cells][12] */, uint32_t* __restrict__ cell_valid,
                            int flags, unsigned long long* __restrict__ wstamps /* diagnostics: 16 words per wave, else NULL */,
                            const uint4* __restrict__ seg_desc, const float* __restrict__ seg_state, uint32_t seg_cap,
-                           const uint32_t* __restrict__ tail_start, const uint32_t* __restrict__ seg_counts, int fwd_grid, int fwd_pairs)
+                           const uint32_t* __restrict__ tail_start, const uint32_t* __restrict__ seg_counts, int fwd_grid)
 {
     __shared__ HeavyLdsBwd s_heavy[4];                       // per wave: 6.6 KB; a light item uses its first 3 KB as the record ring
     __shared__ uint16_t s_prefix[MAX_FWD_QUEUE_WAVES];       // inclusive prefix sums of the forward waves' segment counts (this XCD's region;
@@ -1294,12 +1266,12 @@ blend_backward_wave_kernel(int W, int H, int gx, const uint4* __restrict__ work_
     // those tiles are in this L2).  A wave's first segment is its rank among the queue's waves, later ones come from the region's pop head
     // (one returning atomic on the region's own cache line, AFTER the item: requesting the next one while the current item runs --
     // tried -- lets every wave sit on two items, and with fewer than two items per wave that decided the kernel's length).
-    if (!(flags & 16)) {
+    {
         // The forward waves of this XCD filled private slot ranges; their counts give every segment of the region a flat index.  Each
         // wave builds the prefix table itself (all four waves of the workgroup write the same values: no barrier needed).
         { const int g8 = (int)header[8]; if (g8 > 0) fwd_grid = g8; }     // (the forward kernel's own record of its grid)
         const int fq = min(NUM_XCD_QUEUES, fwd_grid);
-        const int f_waves = qx < fq ? fwd_pairs * ((fwd_grid - qx + fq - 1) / fq) : 0;          // forward pairs (blender waves) that fed this region
+        const int f_waves = qx < fq ? FWD_PAIRS_PER_WG * ((fwd_grid - qx + fq - 1) / fq) : 0;   // forward pairs (blender waves) that fed this region
         uint32_t total = 0u;
         if (f_waves > 0 && f_waves <= MAX_FWD_QUEUE_WAVES && seg_cap <= 65535u) {
             const uint32_t* cnt = seg_counts + (size_t)qx * MAX_FWD_QUEUE_WAVES;
@@ -1335,7 +1307,7 @@ blend_backward_wave_kernel(int W, int H, int gx, const uint4* __restrict__ work_
             // {tile | block << 28, first instance of the tile, first position, end position}: everything the item needs in ONE load
             heavy_backward_item<EXACT>(W, H, gx, (int)(d.x & 0x0fffffffu), (int)(d.x >> 28), lane, make_uint2(d.y, d.y + d.w), inst_rec, inst_bmask,
                                 &s_heavy[wv], bg_color, final_Ts, n_contrib, dL_dpixels, dL_ddepths, dL_dalphas, inst_grad,
-                                cell_valid, flags, (int)d.z, (int)d.w, (flags & 64) ? nullptr : seg_state + slot_idx * SEG_STATE_FLOATS);
+                                cell_valid, (int)d.z, (int)d.w, seg_state + slot_idx * SEG_STATE_FLOATS);
             c_seg += WSTAMP() - tp1;
             uint32_t nxt = 0u;
             if (lane == 0) nxt = atomicAdd(head, 1u) + (uint32_t)q_waves;
@@ -1347,19 +1319,17 @@ blend_backward_wave_kernel(int W, int H, int gx, const uint4* __restrict__ work_
     // are drawn from the queue (LPT order) when a wave gets here, none by rank: with 4096 waves for ~3500 segments and ~2400 block
     // items a static deal gave wave r segment r AND block item r -- the waves whose segment ended last (35 us) then still had a block
     // item of their own to do; drawn dynamically, the waves without a segment and the early finishers take the long ones first.
-    (void)first_rank;
     for (;;) {
         const unsigned long long tq0 = WSTAMP();
-        const WaveItem it = pull_item(queue_head + (size_t)qx * QLINE_WORDS, lane, nq, qx, hx, n_work, work_table, -1, 0);
+        const WaveItem it = pull_item(queue_head + (size_t)qx * QLINE_WORDS, lane, nq, qx, hx, n_work, work_table);
         const unsigned long long tq1 = WSTAMP();
         c_tailpop += tq1 - tq0;
         if (!it.valid) break;
         n_tail++;
         if (it.heavy)
             heavy_backward_item<EXACT>(W, H, gx, it.tile, it.sub, lane, it.rg, inst_rec, inst_bmask, &s_heavy[wv], bg_color, final_Ts,
-                                n_contrib, dL_dpixels, dL_ddepths, dL_dalphas, inst_grad, cell_valid, flags,
-                                (flags & 32) ? 0 : __builtin_amdgcn_readfirstlane((int)tail_start[(size_t)it.tile * WAVE_BLOCKS + it.sub]),
-                                0x7fffffff, nullptr);
+                                n_contrib, dL_dpixels, dL_ddepths, dL_dalphas, inst_grad, cell_valid,
+                                __builtin_amdgcn_readfirstlane((int)tail_start[(size_t)it.tile * WAVE_BLOCKS + it.sub]), 0x7fffffff, nullptr);
         else
             light_backward_item<EXACT>(W, H, gx, it.tile, it.sub, lane, it.rg, inst_rec, inst_bmask, ring, bg_color, final_Ts, n_contrib,
                                 dL_dpixels, dL_ddepths, dL_dalphas, inst_grad, cell_valid, flags);
@@ -1398,35 +1368,12 @@ int resident_wgs_per_cu(K kernel, const char* env, int dflt, int cap, int thread
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, threads, lds) != hipSuccess || occ < 1) occ = 1;
     return std::max(1, std::min(std::min(occ, cap), knob(env, dflt)));
 }
-template <int PAIRS> struct FwdLds { static constexpr size_t bytes = (size_t)PAIRS * (sizeof(PairRing) + sizeof(float) * MAX_CUTS * 16 * 6 + sizeof(uint2) * MAX_CUTS + sizeof(PairCtl)); };
-// wave pairs per workgroup of the forward kernel: 2 (product), or 8 = one workgroup per CU (diagnostic builds, MOSS_FWD_PAIRS=8)
-// (Measured, round 3: eight pairs in ONE workgroup per CU -- the form in which pairs could hand work to each other through LDS -- is
-// 47.1 us against 40.4: its sixteen waves are of one age, the SIMD arbiter then shares issue slots evenly, and the longest item runs
-// at ~760 cycles per trip for as long as its SIMD-mate lives instead of at 520-610 as the older wave of two workgroups.)
-int forward_pairs()
-{
-#ifdef MOSS_DIAG
-    static const int p = knob("MOSS_FWD_PAIRS", FWD_PAIRS_PER_WG) == 8 ? 8 : FWD_PAIRS_PER_WG;
-    return p;
-#else
-    return FWD_PAIRS_PER_WG;
-#endif
-}
 // (exact: the MOSS_DEBUG_EXACT_MATH instantiation has its own register count, hence its own residency)
 int forward_grid(int T, bool exact = false)
 {
-    static const int per_cu = [] {
-#ifdef MOSS_DIAG
-        if (forward_pairs() == 8) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(blend_forward_wave_kernel<8, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FwdLds<8>::bytes);
-            return resident_wgs_per_cu(blend_forward_wave_kernel<8, false>, "MOSS_BLEND_WGS_PER_CU", 1, 1, 1024, FwdLds<8>::bytes);
-        }
-#endif
-        return resident_wgs_per_cu(blend_forward_wave_kernel<2, false>, "MOSS_BLEND_WGS_PER_CU", 4, 4, 256, FwdLds<2>::bytes);
-    }();
-    static const int per_cu_exact = resident_wgs_per_cu(blend_forward_wave_kernel<2, true>, "MOSS_BLEND_WGS_PER_CU", 4, 4, 256, FwdLds<2>::bytes);
-    const bool ex = exact && forward_pairs() == FWD_PAIRS_PER_WG;
-    return min((8 / forward_pairs()) * T, device_cus() * (ex ? per_cu_exact : per_cu));
+    static const int per_cu = resident_wgs_per_cu(blend_forward_wave_kernel<false>, "MOSS_BLEND_WGS_PER_CU", 4, 4, 256, FWD_LDS_BYTES);
+    static const int per_cu_exact = resident_wgs_per_cu(blend_forward_wave_kernel<true>, "MOSS_BLEND_WGS_PER_CU", 4, 4, 256, FWD_LDS_BYTES);
+    return min(4 * T, device_cus() * (exact ? per_cu_exact : per_cu));
 }
 
 }  // anonymous namespace
@@ -1441,49 +1388,35 @@ void launch_blend_forward(const FrameParams& fp, GeomView g, ImageView im, BinVi
                           float* out_color, float* out_depth, float* out_alpha, hipStream_t s)
 {
     (void)g;
-    static const int cull_knob = knob("MOSS_BLEND_CULL", 1);
-    const int flags = fp.no_block_cull ? 0 : cull_knob;             // bit 0: use the per-instance block masks
+    const int flags = fp.no_block_cull ? 0 : 1;                        // bit 0: use the per-instance block masks
     const int T = fp.gx * fp.gy;
-    const bool exact = fp.exact_math != 0 && forward_pairs() == FWD_PAIRS_PER_WG;   // (MOSS_DEBUG_EXACT_MATH)
+    const bool exact = fp.exact_math != 0;                             // (MOSS_DEBUG_EXACT_MATH)
     const int wgs = forward_grid(T, exact);                            // 4 independent waves per workgroup, 16 items per tile
     // hits per depth segment of the backward (0 = never cut: every block is ONE backward item, the round-1 behaviour)
     static const int seg_hits_env = [] { const int v = knob("MOSS_SEG_HITS", 64); return (v > 0 && (v & (v - 1)) == 0 && v >= 4) ? v : 0; }();
     const int seg_hits = T < (1 << 28) ? seg_hits_env : 0;             // (a descriptor packs the tile index into 28 bits)
-    static const int role_swap = knob("MOSS_FWD_ROLE_SWAP", 0) & 1, prio_mode = knob("MOSS_FWD_PRIO", 0);
-#ifdef MOSS_DIAG
-    if (forward_pairs() == 8)
-        MOSS_LAUNCH_TIMED((blend_forward_wave_kernel<8, false>), dim3(wgs), dim3(1024), FwdLds<8>::bytes, s, fp.W, fp.H, fp.gx, T, im.tile_order, im.header,
-                          im.queues + (size_t)Q_FWD * QLINE_WORDS, im.work_table, b.inst_rec, b.inst_bmask, fp.bg_dev, out_color, out_depth, out_alpha,
-                          im.final_T, im.n_contrib, flags, g_stamps, b.seg_desc, b.seg_state, b.seg_cap, seg_hits, im.tail_start, im.seg_counts,
-                          role_swap, prio_mode, fp.forward_only ? 0 : 1);
-    else
-#endif
     if (exact)
-        MOSS_LAUNCH_TIMED((blend_forward_wave_kernel<2, true>), dim3(wgs), dim3(256), FwdLds<2>::bytes, s, fp.W, fp.H, fp.gx, T, im.tile_order, im.header,
+        MOSS_LAUNCH_TIMED(blend_forward_wave_kernel<true>, dim3(wgs), dim3(256), FWD_LDS_BYTES, s, fp.W, fp.H, fp.gx, T, im.tile_order, im.header,
                           im.queues + (size_t)Q_FWD * QLINE_WORDS, im.work_table, b.inst_rec, b.inst_bmask, fp.bg_dev, out_color, out_depth, out_alpha,
                           im.final_T, im.n_contrib, flags, g_stamps, b.seg_desc, b.seg_state, b.seg_cap, seg_hits, im.tail_start, im.seg_counts,
-                          role_swap, prio_mode, fp.forward_only ? 0 : 1);
+                          fp.forward_only ? 0 : 1);
     else
-        MOSS_LAUNCH_TIMED((blend_forward_wave_kernel<2, false>), dim3(wgs), dim3(256), FwdLds<2>::bytes, s, fp.W, fp.H, fp.gx, T, im.tile_order, im.header,
+        MOSS_LAUNCH_TIMED(blend_forward_wave_kernel<false>, dim3(wgs), dim3(256), FWD_LDS_BYTES, s, fp.W, fp.H, fp.gx, T, im.tile_order, im.header,
                           im.queues + (size_t)Q_FWD * QLINE_WORDS, im.work_table, b.inst_rec, b.inst_bmask, fp.bg_dev, out_color, out_depth, out_alpha,
                           im.final_T, im.n_contrib, flags, g_stamps, b.seg_desc, b.seg_state, b.seg_cap, seg_hits, im.tail_start, im.seg_counts,
-                          role_swap, prio_mode, fp.forward_only ? 0 : 1);
+                          fp.forward_only ? 0 : 1);
 }
 
 void launch_blend_backward(const FrameParams& fp, GeomView g, ImageView im, BinView b,
                            const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha, hipStream_t s)
 {
     (void)g;
-    static const int cull_knob = knob("MOSS_BLEND_CULL", 1);
-    // diagnostics, MOSS_DIAG builds only (results are wrong with any of them): 16 = skip the segment items, 32 = block items ignore
-    // the cuts, 64 = segment items start from (T_final, 0)
-    static const int dbg = knob("MOSS_BWD_DEBUG", 0) & (16 | 32 | 64);
-    const int flags = (fp.no_block_cull ? 0 : cull_knob) | dbg;
+    const int flags = fp.no_block_cull ? 0 : 1;                        // bit 0: use the per-instance block masks
     const int T = fp.gx * fp.gy;
     static const int bwd_wgs_per_cu = resident_wgs_per_cu(blend_backward_wave_kernel<false>, "MOSS_BWD_WGS_PER_CU", 4, 5);   // 27 KB of LDS each
     static const int bwd_wgs_per_cu_exact = resident_wgs_per_cu(blend_backward_wave_kernel<true>, "MOSS_BWD_WGS_PER_CU", 4, 5);
     // (MOSS_DEBUG_EXACT_MATH must be given to the forward AND the backward call: the forward's grid -- how its cuts are numbered -- follows it)
-    const bool exact = fp.exact_math != 0 && forward_pairs() == FWD_PAIRS_PER_WG;
+    const bool exact = fp.exact_math != 0;
     const int wgs = min(4 * T, device_cus() * (exact ? bwd_wgs_per_cu_exact : bwd_wgs_per_cu));
     // the queue heads are zero here: cleared by the forward, rewound after each backward (preprocess_backward_kernel)
     if (exact)
@@ -1491,13 +1424,13 @@ void launch_blend_backward(const FrameParams& fp, GeomView g, ImageView im, BinV
                            im.queues + (size_t)Q_BWD * QLINE_WORDS, b.inst_rec, b.inst_bmask, fp.bg_dev, im.final_T, im.n_contrib, dL_dpix,
                            dL_ddepth, dL_dalpha, reinterpret_cast<float*>(b.inst_grad), b.cell_valid,
                            flags, g_bwd_stamps, b.seg_desc, b.seg_state, b.seg_cap, im.tail_start, im.seg_counts,
-                           forward_grid(T, true) /* the forward kernel's grid */, forward_pairs());
+                           forward_grid(T, true) /* the forward kernel's grid */);
     else
         MOSS_LAUNCH_TIMED(blend_backward_wave_kernel<false>, dim3(wgs), dim3(256), 0, s, fp.W, fp.H, fp.gx, im.work_table, im.header,
                            im.queues + (size_t)Q_BWD * QLINE_WORDS, b.inst_rec, b.inst_bmask, fp.bg_dev, im.final_T, im.n_contrib, dL_dpix,
                            dL_ddepth, dL_dalpha, reinterpret_cast<float*>(b.inst_grad), b.cell_valid,
                            flags, g_bwd_stamps, b.seg_desc, b.seg_state, b.seg_cap, im.tail_start, im.seg_counts,
-                           forward_grid(T, false) /* the forward kernel's grid */, forward_pairs());
+                           forward_grid(T, false) /* the forward kernel's grid */);
 }
 
 }  // namespace moss

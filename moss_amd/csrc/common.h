@@ -256,7 +256,8 @@ extern thread_local StageEvents g_stage_events;          // raster_api.hip
 // ---- tuning knobs and diagnostics.  The PRODUCT build has neither: knob(name, dflt) is the constant dflt, the stamp buffers are
 // null constants, and no translation unit under csrc/ reads the environment.  A build with -DMOSS_DIAG (python -m moss_amd.build --diag ->
 // moss_amd/lib_diag/, used by scripts/ only) reads MOSS_* environment variables through knob() and exports the
-// moss_raster_debug_set_*stamps entry points; some of its knobs produce WRONG results on purpose (timing experiments).
+// moss_raster_debug_set_*stamps entry points.  Its knobs tune a parameter of a path the product runs or force one of two paths the
+// product chooses between by input; none changes what is computed beyond that choice.
 #ifdef MOSS_DIAG
 int knob(const char* name, int dflt);                  // scripts/diag/knobs.cpp: the integer value of an environment variable, else dflt
 extern unsigned long long* g_stamps;                   // optional forward-blend phase stamps, blend.hip

@@ -51,11 +51,6 @@ __device__ __forceinline__ Crop load_crop(const int* __restrict__ rect, int W, i
 }
 __device__ __forceinline__ bool in_crop(const Crop& r, int x, int y) { return x >= r.x0 && x < r.x1 && y >= r.y0 && y < r.y1; }
 
-__device__ __forceinline__ float ld0(const float* __restrict__ p, int x, int y, int W, int H)
-{
-    return (x >= 0 && x < W && y >= 0 && y < H) ? p[(size_t)y * W + x] : 0.0f;
-}
-
 
 // XCD-aware tile order.  Workgroups are dealt round-robin to the 8 XCDs (linear id % 8), each with its own L2: with the natural
 // order, a tile's four neighbours -- which re-read its 5-pixel halo -- run on four other XCDs and every halo is fetched from HBM

@@ -538,7 +538,7 @@ preprocess_forward_kernel(int P, int D, int M, int W, int H, int gx, int gy,
         __syncthreads();
         for (int i = threadIdx.x; i < T; i += blockDim.x) {
             const uint32_t v = s_hist[i];
-            if (v && !(raw & 0x100)) atomicAdd(&tile_count[i], v);        // (0x100: timing experiment, MOSS_EXPERIMENT=1 -- wrong counts)
+            if (v) atomicAdd(&tile_count[i], v);
         }
     }
     FSTAMP(5);
@@ -1077,8 +1077,9 @@ preprocess_backward_kernel(int P, int D, int M, float tan_fovx, float tan_fovy, 
         // (61 vs 24 us).
         const uint32_t passes = (W_all + (uint32_t)GATHER_CAP - 1u) / (uint32_t)GATHER_CAP;
         const uint32_t direct_trips = ((bmax & 0xffu) + 1u) / 2u + (((bmax >> 8) & 0xffu) + 1u) / 2u + (((bmax >> 16) & 0xffu) + 1u) / 2u + ((bmax >> 24) + 1u) / 2u;
+        // (wave-uniform by construction; saying so keeps the choice a scalar branch -- as a vector condition the fused kernels spill)
         const bool balanced = LPG_L2 == 4 ? true :           // (the group's lanes hold one word each: only the list form sums a Gaussian's records)
-                              (raw & 0x200) ? false : (raw & 0x400) ? true : (passes == 1u ? direct_trips >= 5u : passes * 8u < direct_trips);     // (0x200 / 0x400: diagnostics, MOSS_GATHER=1 / 2)
+                              __builtin_amdgcn_readfirstlane((int)(passes == 1u ? direct_trips >= 5u : passes * 8u < direct_trips)) != 0;
         if (!balanced) {
 #pragma unroll
         for (int kb = 0; kb < (int)COOP_WORDS; kb += 4) {
@@ -1572,7 +1573,7 @@ void launch_preprocess_forward(const FrameParams& fp, const float* means3D, cons
                        fp.P, fp.D, fp.M, fp.W, fp.H, fp.gx, fp.gy, fp.tan_fovx, fp.tan_fovy, fp.focal_x, fp.focal_y,
                        fp.scale_modifier, fp.prefiltered, means3D, shs, colors_precomp, opacities, scales, rotations,
                        cov3D_precomp, fp.view_dev, fp.proj_dev, fp.campos_dev, g, im.tile_count, im.flags_acc, radii_out, lds_hist, stage_sh,
-                       transforms, fp.raw | ((knob("MOSS_EXPERIMENT", 0) & 1) ? 0x100 : 0),
+                       transforms, fp.raw,
                        (g_stamps && knob("MOSS_SORT_STAMPS", 0)) ? g_stamps + 131072 + 32768 : nullptr, translation, scatter_keys, key_stride);
 }
 
@@ -1606,7 +1607,6 @@ void launch_preprocess_backward(const FrameParams& fp, const float* means3D, con
     // coalescing (stress case with image-covering Gaussians 91.5 -> 99.3 us), and once the grid runs in several rounds the dispatcher
     // does the balancing while the shared cache lines of 64 neighbours count for more (configs[4]: 81 us consecutive, 87-95 in groups).
     static const int gl2_env = knob("MOSS_PREBWD_GROUP_LOG2", 0);
-    static const int gather_knob = knob("MOSS_GATHER", 0) == 1 ? 0x200 : knob("MOSS_GATHER", 0) == 2 ? 0x400 : 0;
     // (the fused update of the SH records works on the staged rows: raster_api.hip refuses it unless M == 16 and the arrays are aligned)
     const bool stage = fp.M == 16 && shs != nullptr && (dL_dsh != nullptr || (fa.tensors & OPT_SH)) && (size_t)fp.P * 192u < 0xffffff00u &&
                        (knob("MOSS_PREBWD_STAGE", 1) || (fa.tensors & OPT_SH)) &&
@@ -1630,7 +1630,7 @@ void launch_preprocess_backward(const FrameParams& fp, const float* means3D, con
                        fp.P, fp.D, fp.M, fp.tan_fovx, fp.tan_fovy, fp.focal_x, fp.focal_y, -0.5f * (float)fp.W, -0.5f * (float)fp.H, fp.scale_modifier, \
                        means3D, shs, scales, rotations, cov3D_precomp, fp.view_dev, fp.proj_dev, fp.campos_dev,                 \
                        g, b.inst_grad, b.cell_valid, header, dL_dmean2D, dL_dconic, \
-                       dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, transforms, dL_dtransforms, opacities, fp.raw | gather_knob | (gl2 << 12), g_stamps, queues, translation, dL_dtranslation, fa)
+                       dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, transforms, dL_dtransforms, opacities, fp.raw | (gl2 << 12), g_stamps, queues, translation, dL_dtranslation, fa)
     // (lanes per Gaussian: instantiated for the staged-SH kernels -- MOSS's case, M = 16 -- only)
     if (stage && lpg_l2 == 4) { if (fa.tensors != 0u) LAUNCH_PB(true, true, 4); else LAUNCH_PB(true, false, 4); }
     else if (fa.tensors != 0u) { if (stage) LAUNCH_PB(true, true, 0); else LAUNCH_PB(false, true, 0); }

@@ -267,12 +267,6 @@ static int forward_impl(const moss_raster_forward_args& a, void* stream)
             { StageTimer tm(MOSS_STAGE_SCATTER, s); TraceRange tr(trace, fold_scan ? "moss:scatter+scan" : "moss:scatter"); launch_scatter(fp, g, im, b, s, fold_scan, capacity); }
             STAGE_CHECK("scatter");
         }
-#ifdef MOSS_DIAG
-        {   // timing experiment (scripts/exp_atomics.py): with the scatter's reservation atomics off the keys are garbage -- stop here
-            static const bool stop = (knob("MOSS_EXPERIMENT", 0) & 2) != 0;
-            if (stop) { abandon_frame_state(); return R; }
-        }
-#endif
         { StageTimer tm(MOSS_STAGE_TILE_SORT, s); TraceRange tr(trace, bucketed ? "moss:chunk_sort+scan" : "moss:chunk_sort");
           launch_tile_sort(fp, g, im, b, R, total_chunks, s, a.frame_state, fs_bytes, 0, key_stride, capacity); }
         { StageTimer tm(MOSS_STAGE_MERGE_GATHER, s); TraceRange tr(trace, "moss:merge_gather");

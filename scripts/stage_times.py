@@ -37,4 +37,4 @@ wall = (time.perf_counter() - t0) / args.iters * 1e3
 prof = _lib.profile_read()
 out = {k: round(v[0] / max(v[1], 1), 4) for k, v in prof.items()}
 out["sum"] = round(sum(out.values()), 4); out["wall_ms_per_iter"] = round(wall, 4); out["R"] = t.R
-print(args.config, os.environ.get("MOSS_BLEND_CULL", "1"), json.dumps(out))
+print(args.config, json.dumps(out))
