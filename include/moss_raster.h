@@ -465,6 +465,25 @@ int moss_lbs_deform_backward(const moss_lbs_backward_args* args, void* stream);
 size_t moss_lbs_workspace_bytes(int P, int J);
 
 /*
+ * MOSS's S3IM term and its gradient (additive in ABI 7): s3im_loss = s3im_fun(img_pred, img_gt) (train_ZJU.py:123, weighted 0.3 at
+ * :131; utils/loss_utils.py:17-38).  MOSS hands it two (1,C,h,w) crops, so every randperm(1) is [0] and the term is deterministic:
+ *     s3im = 1 - ssim(x~, y~),   x~ = the crop with every pixel repeated `repeat` times along a row (width repeat * w)
+ * with the reference's ssim (utils/loss_utils.py:57-87: 11x11 window, sigma 1.5, fp32-normalised, zero padding at the crop's edges,
+ * per channel, C1 = 0.01^2, C2 = 0.03^2, mean over C * h * repeat * w).  The widened images are never formed: HBM traffic per source
+ * pixel-channel does not depend on `repeat`.
+ *   image, gt (C,H,W) fp32; rect: 5 DEVICE ints as moss_photometric_loss_roi's (x, y, w, h of the crop; the fifth is not read), clipped
+ *     to the frame the same way, or NULL = the whole image; repeat: 1..16 (MOSS: 10);
+ *   loss_out: 2 device floats {1 - ssim, ssim}; dL_dimage (C,H,W): d(1 - ssim)/d image, written everywhere, zero off the crop;
+ *   workspace: moss_s3im_workspace_bytes(C, H, W) device bytes (any repeat).
+ * An empty crop gives NaN values (0 / 0) and a zero gradient.  Two launches on `stream`, no host synchronisation, no allocation: a
+ * captured step changes view by rewriting `rect`.  Sums in a fixed order, no atomics: bitwise reproducible.  Bad arguments (sizes
+ * <= 0, repeat outside 1..16, a short workspace, a NULL output) return MOSS_ERR_INVALID_ARG with moss_last_error() set.
+ */
+size_t moss_s3im_workspace_bytes(int C, int H, int W);  /* 0 for a size <= 0 */
+int moss_s3im_loss(int C, int H, int W, const float* image, const float* gt, const int* rect, int repeat, float* loss_out,
+                   float* dL_dimage, char* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * k nearest reference points of every query point, 3-D, exact, k = 1..4: replaces the third-party
  * `knn_cuda.KNN(k, transpose_mode=True)(ref, query)` MOSS calls at scene/gaussian_model.py:85-86,586,657,759,827 (a CUDA-only
  * binary wheel, not in the repository; parity unpinned by the reference).

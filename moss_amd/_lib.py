@@ -85,6 +85,10 @@ def _declare(lib):
     lib.moss_lbs_deform_forward.argtypes = [_p, _p]
     lib.moss_lbs_deform_backward.restype = _i
     lib.moss_lbs_deform_backward.argtypes = [_p, _p]
+    lib.moss_s3im_workspace_bytes.restype = C.c_size_t
+    lib.moss_s3im_workspace_bytes.argtypes = [_i, _i, _i]
+    lib.moss_s3im_loss.restype = _i
+    lib.moss_s3im_loss.argtypes = [_i, _i, _i, _p, _p, _p, _i, _p, _p, _p, C.c_size_t, _p]
     lib.moss_photometric_loss_roi.restype = _i
     lib.moss_photometric_loss_roi.argtypes = [_i, _i, _i, _p, _p, _p, _p, _p, _p, _f, _f, _f, _p, _p, _p, _p, C.c_size_t, _p]
     lib.moss_adamw_flat_ex.restype = _i

@@ -37,6 +37,7 @@ SOURCES = {
     "binning.hip": [],
     "blend.hip": [],
     "loss.hip": [],
+    "s3im.hip": [],
     "metrics.hip": [],
     "lbs.hip": [],
     "optim.hip": [],

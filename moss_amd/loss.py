@@ -264,3 +264,81 @@ def training_loss_moss_fused(image, alpha, gt_image, bkgd_mask, region, lambda_d
     :111-119 (patches/train_ZJU.diff keeps them and swaps only ``ssim``; this is the one-call form).  The remaining terms of :131 (lpips,
     s3im, nll) are other subsystems' and are added to the returned loss by the caller."""
     return _FusedMossLoss.apply(image, alpha, gt_image, bkgd_mask, region, lambda_dssim, lambda_mask, terms_out)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------- S3IM
+def s3im(src_vec, tar_vec, repeat_time=10):
+    """The reference's ``s3im_fun`` (utils/loss_utils.py:17-38) in torch, any device and dtype: the rows of the (b, C*h*w) images are
+    gathered in the order [0 .. b-1] followed by ``repeat_time - 1`` draws of ``torch.randperm(b)`` (the default generator, as the
+    reference draws them), laid side by side as a (1, C, h, w * repeat_time) image each, and the loss is ``1 - ssim`` of the two.
+    At b = 1 -- MOSS's call, two (1,3,h,w) crops -- every permutation is [0] and nothing is drawn: each pixel appears ``repeat_time``
+    times along its row.  At b > 1 the permutations are drawn like the reference's, and, like the reference's reshape, the call then
+    fails: the gathered rows hold b times the elements of one (1, C, h, w * repeat_time) image."""
+    b, channel, h, w = src_vec.shape
+    order = torch.cat([torch.arange(b)] + [torch.randperm(b) for _ in range(repeat_time - 1)])
+    if b != 1:
+        raise RuntimeError(f"s3im: {b * repeat_time} gathered rows of {channel * h * w} values do not form one "
+                           f"(1, {channel}, {h}, {w * repeat_time}) image (the reference's reshape fails the same way for a batch > 1)")
+
+    def widen(v):
+        return v.reshape(b, -1)[order].t().reshape(1, channel, h, w * repeat_time)
+
+    return 1.0 - ssim(widen(src_vec), widen(tar_vec))
+
+
+class _FusedS3IM(torch.autograd.Function):
+    """C ABI moss_s3im_loss: ``1 - ssim`` of the widened images and its gradient w.r.t. ``image`` (the ground truth gets none)."""
+
+    @staticmethod
+    def forward(ctx, image, gt_image, rect, repeat_time):
+        from ._lib import check, lib
+        L = lib()
+        C, H, W = image.shape
+        a, b = image.contiguous(), gt_image.contiguous()
+        out = torch.empty(2, dtype=torch.float32, device=a.device)
+        d_img = torch.empty((C, H, W), dtype=torch.float32, device=a.device)
+        nbytes = int(L.moss_s3im_workspace_bytes(C, H, W))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=a.device)
+        with torch.cuda.device(a.device):
+            rc = L.moss_s3im_loss(C, H, W, a.data_ptr(), b.data_ptr(), None if rect is None else rect.data_ptr(), int(repeat_time),
+                                  out.data_ptr(), d_img.data_ptr(), ws.data_ptr(), nbytes, torch.cuda.current_stream(a.device).cuda_stream)
+        check(rc, "s3im_loss")
+        ctx.save_for_backward(d_img)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (d_img,) = ctx.saved_tensors
+        unit = _UNIT.get(d_img.device)          # (the unit gradient of backward_from_loss: no scaling kernel)
+        return (d_img if (unit is not None and grad_out.data_ptr() == unit.data_ptr()) else grad_out * d_img), None, None, None
+
+
+def _check_s3im_inputs(image, gt_image, what):
+    if not image.is_cuda or image.dtype != torch.float32 or gt_image.dtype != torch.float32:
+        raise RuntimeError(f"{what} needs float32 GPU tensors (the product path has no CPU fallback; moss_amd.loss.s3im is the torch form)")
+    if gt_image.shape != image.shape or gt_image.device != image.device:
+        raise RuntimeError(f"{what}: the two images differ in shape or device")
+
+
+def s3im_fused(src_vec, tar_vec, repeat_time=10):
+    """Drop-in for the reference's ``s3im_fun`` (utils/loss_utils.py:17-38) as MOSS calls it (train_ZJU.py:123: two (1,3,h,w) crops):
+    the same value, the gradient w.r.t. ``src_vec``, from two HIP kernels (C ABI moss_s3im_loss) instead of the torch graph on a
+    tensor ``repeat_time`` times the crop's width.  float32 GPU tensors, (1,C,h,w) or (C,h,w); ``repeat_time`` 1..16; the target gets no
+    gradient (MOSS's is the ground truth).  A batch > 1 goes to :func:`s3im`, the reference's semantics."""
+    if src_vec.dim() == 4:
+        if src_vec.shape[0] != 1:
+            return s3im(src_vec, tar_vec, repeat_time)
+        src_vec, tar_vec = src_vec[0], tar_vec[0]
+    _check_s3im_inputs(src_vec, tar_vec, "s3im_fused")
+    return _FusedS3IM.apply(src_vec, tar_vec.detach(), None, repeat_time)
+
+
+def s3im_loss_roi_fused(image, gt_image, region, repeat_time=10):
+    """``s3im_fun(image[:, y:y+h, x:x+w][None], gt_image[...][None])`` for ``(x, y, w, h) = region.xywh`` (train_ZJU.py:115-123), taken
+    on the FULL frames: the crop is read from ``region.rect`` on the device -- no host read, no crop copies -- and the gradient is
+    written for the whole ``image`` (zero off the crop).  Capturable in a graph; the view changes by ``region.copy_``."""
+    _check_s3im_inputs(image, gt_image, "s3im_loss_roi_fused")
+    C, H, W = image.shape
+    if tuple(region.bound.shape) != (H, W) or region.rect.device != image.device:
+        raise RuntimeError("s3im_loss_roi_fused: the view's region does not belong to this image")
+    return _FusedS3IM.apply(image, gt_image.detach(), region.rect, repeat_time)
