@@ -484,6 +484,73 @@ int moss_s3im_loss(int C, int H, int W, const float* image, const float* gt, con
                    float* dL_dimage, char* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * MOSS's pose-refinement head and its matrix-Fisher loss term (additive in ABI 7), one launch each way:
+ *   pc.auto_regression(smpl_param['poses'])   gaussian_renderer/__init__.py:66-71 -> nets/mlp_delta_body_pose.py:56-82 (Autoregression.forward)
+ *   matrix_fisher_nll(F, U, S, V, target_R)   train_ZJU.py:125-129 -> utils/loss_utils.py:283-317, LogMFNormConstant :222-280
+ * Forward, for the 23 non-root joints (joint j here is joint j + 1 of `parents`):
+ *     h = W4 relu(W2 relu(W0 poses[3:72] + b0) + b2) + b4               the MLP 69 -> 128 -> 128 -> 69 (:57), h viewed as (23,3)
+ *     r_j = fc_j [h_j, h_a1, h_a2, ...] + c_j                            a1, a2, ... the non-root ancestors of j, parent first (:62-71, :41-54)
+ *     Rs_j = n n^T (1 - cos th) + cos th I + sin th [n]x,  th = sqrt(1e-5 + |r_j|^2), n = r_j / th     RodriguesModule (:258-284)
+ *     Rs_j = U diag(s) V^T (one-sided Jacobi, s descending);  S_j = (s1, s2, s3 det(U V^T))            torch.svd (:75), loss_utils.py:310-313
+ *     log c(S) = log(1/2 int_-1^1 I0~((S2 - S3)(1 - u)/2) I0~((S2 + S3)(1 + u)/2) exp((S3 + S1)(u - 1)) du) + S1 + S2 + S3
+ *                512-point trapezoid, I0~(x) = exp(-|x|) I0(x) by two polynomials split at |x| <= 3.75 (:98-184, :245-258)
+ *     nll_j = -<Rs_j, target_R_j> + overreg log c(S_j)                  (:315-317)
+ * Backward, from g_Rs (23,3,3) and g_nll (23), each NULL when zero: dlog c / dS_k = (the same integral with a factor u, over the
+ * cyclic shift that puts S_k first) / c~ (:187-219, :261-280); dL/dRs = g_Rs - g_nll target_R + overreg g_nll U diag(dlog c/dS . (1, 1, det)) V^T;
+ * then back through Rodrigues, the joint layers (each scatters into h of its joint and of its ancestors: gathered per element in joint
+ * order) and the MLP.  The gradient of EVERY parameter tensor is written (never accumulated into).  poses and target_R get none.
+ *   params / grads: the 52 tensors in state_dict order -- block_mlps.{0,2,4}.{weight,bias}, then fc_pose.{0..22}.0.{weight,bias} --
+ *     fp32, contiguous, (out,in) row-major as torch.nn.Linear stores them; fc_in[j] = the input width of fc_pose.j, which must be
+ *     3 (1 + number of non-root ancestors of j) by `parents`;
+ *   parents: 24 ints by value, parents[0] = -1 and 0 <= parents[i] < i (SMPL's kintree); poses (72), target_R (23,3,3): DEVICE
+ *     pointers, so that a captured graph reads the frame's values at replay;
+ *   Rs (23,3,3), S (23,3), nll (23): outputs; saved: MOSS_POSE_HEAD_SAVED_FLOATS device floats the backward reads (activations, r,
+ *     U, V, det, c~) -- with S it must reach the backward unchanged.
+ * U and V are not outputs: Rs is within 1e-5 of a rotation, its singular vectors are not unique; only S, det(U V^T) and the product
+ * U diag(.) V^T enter any result.  One workgroup, sums in a fixed order, no atomics: bitwise reproducible.  No host synchronisation,
+ * no allocation: capturable.  Bad arguments return MOSS_ERR_INVALID_ARG with moss_last_error() set.
+ */
+#define MOSS_POSE_JOINTS 23
+#define MOSS_POSE_PARAMS 52
+#define MOSS_POSE_HEAD_SAVED_FLOATS 896
+typedef struct moss_pose_head_args {
+    const float* poses;                      /* (72); the first 3 are not read */
+    const float* target_R;                   /* (23,3,3) */
+    const float* params[MOSS_POSE_PARAMS];
+    int32_t parents[MOSS_POSE_JOINTS + 1];
+    int32_t fc_in[MOSS_POSE_JOINTS];
+    float overreg;                           /* MOSS: 1.005 */
+    float* Rs;                               /* (23,3,3) */
+    float* S;                                /* (23,3) proper singular values */
+    float* nll;                              /* (23) */
+    float* saved;                            /* MOSS_POSE_HEAD_SAVED_FLOATS */
+} moss_pose_head_args;
+int moss_pose_head_forward(const moss_pose_head_args* args, void* stream);
+
+typedef struct moss_pose_head_backward_args {
+    const float* poses;
+    const float* target_R;
+    const float* params[MOSS_POSE_PARAMS];
+    int32_t parents[MOSS_POSE_JOINTS + 1];
+    int32_t fc_in[MOSS_POSE_JOINTS];
+    float overreg;
+    const float* S;                          /* as the forward wrote it */
+    const float* saved;                      /* as the forward wrote it */
+    const float* g_Rs;                       /* (23,3,3) or NULL */
+    const float* g_nll;                      /* (23) or NULL */
+    float* grads[MOSS_POSE_PARAMS];          /* every one written, shaped as params */
+} moss_pose_head_backward_args;
+int moss_pose_head_backward(const moss_pose_head_backward_args* args, void* stream);
+
+/*
+ * The loss term alone for n general 3x3 matrices (utils/loss_utils.py:283-317 with the torch.svd of its caller): the same SVD and
+ * quadrature code, one wave per matrix.  F, target_R (n,3,3); nll_out (n); dF_out (n,3,3) or NULL: d nll_i / d F_i =
+ * -target_R_i + overreg U diag(dlog c/dS . (1, 1, det)) V^T.  Right for any F: either determinant sign, distinct or coinciding
+ * singular values (tested to S = 80).  n = 0 launches nothing.  One launch, no host synchronisation, no allocation.
+ */
+int moss_matrix_fisher_nll(int n, const float* F, const float* target_R, float overreg, float* nll_out, float* dF_out, void* stream);
+
+/*
  * k nearest reference points of every query point, 3-D, exact, k = 1..4: replaces the third-party
  * `knn_cuda.KNN(k, transpose_mode=True)(ref, query)` MOSS calls at scene/gaussian_model.py:85-86,586,657,759,827 (a CUDA-only
  * binary wheel, not in the repository; parity unpinned by the reference).

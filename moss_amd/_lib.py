@@ -89,6 +89,12 @@ def _declare(lib):
     lib.moss_s3im_workspace_bytes.argtypes = [_i, _i, _i]
     lib.moss_s3im_loss.restype = _i
     lib.moss_s3im_loss.argtypes = [_i, _i, _i, _p, _p, _p, _i, _p, _p, _p, C.c_size_t, _p]
+    lib.moss_pose_head_forward.restype = _i
+    lib.moss_pose_head_forward.argtypes = [_p, _p]
+    lib.moss_pose_head_backward.restype = _i
+    lib.moss_pose_head_backward.argtypes = [_p, _p]
+    lib.moss_matrix_fisher_nll.restype = _i
+    lib.moss_matrix_fisher_nll.argtypes = [_i, _p, _p, _f, _p, _p, _p]
     lib.moss_photometric_loss_roi.restype = _i
     lib.moss_photometric_loss_roi.argtypes = [_i, _i, _i, _p, _p, _p, _p, _p, _p, _f, _f, _f, _p, _p, _p, _p, C.c_size_t, _p]
     lib.moss_adamw_flat_ex.restype = _i
@@ -154,6 +160,22 @@ class LbsBackwardArgs(C.Structure):
     _fields_ = _LBS_INPUTS + [("g_T", C.c_void_p), ("g_t", C.c_void_p), ("g_p", C.c_void_p), ("g_L", C.c_void_p),
                               ("g_A_obs", C.c_void_p), ("g_d", C.c_void_p), ("g_x", C.c_void_p), ("workspace", C.c_void_p),
                               ("workspace_bytes", C.c_size_t)]
+
+
+POSE_HEAD_SAVED_FLOATS = 896                             # MOSS_POSE_HEAD_SAVED_FLOATS
+_POSE_INPUTS = [("poses", C.c_void_p), ("target_R", C.c_void_p), ("params", C.c_void_p * 52), ("parents", C.c_int32 * 24),
+                ("fc_in", C.c_int32 * 23), ("overreg", C.c_float)]
+
+
+class PoseHeadArgs(C.Structure):
+    """``moss_pose_head_args`` of include/moss_raster.h (``moss_pose_head_forward``: MOSS's pose-refinement head + matrix-Fisher NLL)."""
+    _fields_ = _POSE_INPUTS + [("Rs", C.c_void_p), ("S", C.c_void_p), ("nll", C.c_void_p), ("saved", C.c_void_p)]
+
+
+class PoseHeadBackwardArgs(C.Structure):
+    """``moss_pose_head_backward_args`` of include/moss_raster.h (``moss_pose_head_backward``)."""
+    _fields_ = _POSE_INPUTS + [("S", C.c_void_p), ("saved", C.c_void_p), ("g_Rs", C.c_void_p), ("g_nll", C.c_void_p),
+                               ("grads", C.c_void_p * 52)]
 
 
 OPT_BITS = {"means3D": 1, "sh": 2, "opacity": 4, "scales": 8, "rotations": 16}      # MOSS_OPT_*; position = index in the struct's arrays

@@ -40,6 +40,7 @@ SOURCES = {
     "s3im.hip": [],
     "metrics.hip": [],
     "lbs.hip": [],
+    "pose_head.hip": [],
     "optim.hip": [],
     "activations.hip": [],
     "densify.hip": [],

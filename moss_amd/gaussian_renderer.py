@@ -2,7 +2,9 @@
 MOSS that changes when the rasterizer is swapped (north_star).  Same call signature, same settings construction
 (:36-52), same zero ``means2D`` gradient sink (:29-33), same input-mode selection (:85-109), same output keys (:124-136).
 
-Out of scope here: the pose-refinement networks of the LBS branch (:57-72).  If ``pc`` offers
+Out of scope here: the LBS-weight network of the pose branch (:70; ``pc.cross_attention_lbs`` is
+called as the reference calls it).  With ``pipe.pose_head_in_op`` (and ``pipe.lbs_in_op``) the branch itself runs (:65-72) with the
+refinement head and the matrix-Fisher term as one fused HIP op (moss_amd/pose.py).  If ``pc`` offers
 ``coarse_deform_c2source`` it is called exactly as the reference does (with ``pipe.lbs_in_op``: the fused HIP deformation of
 moss_amd/lbs.py instead, same arguments); otherwise the Gaussians render where they are
 (optionally moved by explicit ``transforms`` / ``translation``, the cheap branch :73-77).
@@ -106,9 +108,19 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
         # ``pipe.lbs_in_op`` (an addition, default off): the deformation runs as the fused HIP op (moss_amd/lbs.py; ``pc`` supplies
         # SMPL_NEUTRAL and knn).  With pose_in_op + transforms_in_op the op gets the canonical x with T and t (MOSS_RAW_POSE).
         from .lbs import coarse_deform_c2source
+        lbs_weights = None
+        if (getattr(pipe, "pose_head_in_op", False) and getattr(pc, "motion_offset_flag", False)
+                and hasattr(pc, "auto_regression") and hasattr(pc, "cross_attention_lbs")):
+            # ``pipe.pose_head_in_op`` (an addition, default off): MOSS's pose branch (reference :65-72) with the refinement head and
+            # the matrix-Fisher term as the fused HIP op (moss_amd/pose.py); cross_attention_lbs stays the caller's torch module
+            from .pose import pose_head_fused
+            pose_out = pose_head_fused(pc.auto_regression, viewpoint_camera.smpl_param['poses'], viewpoint_camera.smpl_param['pose_rotmats'])
+            lbs_weights = pc.cross_attention_lbs(means3D[None], pose_out["Rs"])
+            correct_Rs = pose_out["Rs"].reshape(1, 23, 3, 3)
         _, world, bweights, transforms, translation = coarse_deform_c2source(
             pc, means3D[None], viewpoint_camera.smpl_param, viewpoint_camera.big_pose_smpl_param,
-            viewpoint_camera.big_pose_world_vertex[None], return_transl=True)
+            viewpoint_camera.big_pose_world_vertex[None], return_transl=True,
+            **({} if pose_out is None else {"lbs_weights": lbs_weights, "correct_Rs": correct_Rs}))
         if (getattr(pipe, "pose_in_op", False) and getattr(pipe, "transforms_in_op", False) and not pipe.compute_cov3D_python
                 and not pipe.convert_SHs_python):
             raw_flags |= 16                                  # _C.RAW_POSE
