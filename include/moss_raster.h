@@ -551,6 +551,59 @@ int moss_pose_head_backward(const moss_pose_head_backward_args* args, void* stre
 int moss_matrix_fisher_nll(int n, const float* F, const float* target_R, float overreg, float* nll_out, float* dF_out, void* stream);
 
 /*
+ * MOSS's LBS-weight network (additive in ABI 7): pc.cross_attention_lbs(means3D[None], correct_Rs), gaussian_renderer/__init__.py:72 ->
+ * CrossAttention_lbs.forward, nets/mlp_delta_weight_lbs.py:31-54 (the embedding: get_embedder(10), :87-133).  Per point x (3), with
+ * the refined rotations Rs (23,3,3):
+ *     e (63)  = [x, sin(x 2^0), cos(x 2^0), ..., sin(x 2^9), cos(x 2^9)]      the input first, per frequency three sines then three cosines
+ *     h0 = relu(W0 e + b0), h1 = relu(W1 h0 + b1), h2 = relu(W2 h1 + b2), h3 = relu(W3 [e ; h2] + b3)     (:35-38; the skip puts e FIRST)
+ *     q0 (24) = Wfc h3 + bfc (:39);  Q (24) = Wq q0 + bq (:46)
+ *     M (24,9) = a row of nine ONES, then Rs[j] flattened (:43);  K = M Wk^T + bk,  V = M Wv^T + bv   (24,9) (:47-48)
+ *     s (9) = sum_i Q[i] K[i,:] / sqrt(24);  a = softmax(s);  out[j] = sum_c a[c] V[j,c]   (24) (:49-52)
+ * out_layer, gate_proj and num_heads are not read by that forward and cross no boundary.
+ *   params / grads: the 16 tensors bw_linears.{0,1,2,3}.{weight,bias}, bw_fc.{weight,bias}, query.{weight,bias}, key.{weight,bias},
+ *     value.{weight,bias} -- fp32, contiguous, (out,in) row-major (a Conv1d(k=1) weight (out,in,1) is exactly that);
+ *   x (P,3), Rs (23,3,3), out (P,24), g_out (P,24), g_x (P,3), g_Rs (23,3,3): fp32 device arrays;
+ *   saved: moss_lbs_weight_net_saved_bytes(P) bytes the forward writes (e, the four hidden activations, q0, Q, a per point:
+ *     MOSS_LBS_WEIGHT_NET_SAVED_FLOATS each) and the backward reads; NULL in the forward = nothing is kept (no backward follows);
+ *   workspace: moss_lbs_weight_net_workspace_bytes(P) bytes of scratch for the backward (contents irrelevant before, garbage after).
+ * Forward: ONE launch, 32 points per workgroup, every layer on the f32-input matrix cores (exact float32).  Backward: THREE launches
+ * -- the data gradients per tile of points (writes g_x and every layer's pre-activation gradient to the workspace), the weight
+ * gradients as matrix products over the points with a FIXED split into MOSS_LBS_WEIGHT_NET_SPLITS ranges, and a fold of the partial
+ * sums in split order that also forms the gradients of key / value and Rs.  Every output and gradient element is WRITTEN (no buffer
+ * needs a zero fill), every sum has a fixed order and there is no atomic: bitwise reproducible.  No host synchronisation, no
+ * allocation: capturable.  P = 0 is a no-op.  Bad arguments (a NULL required pointer, P < 0, a short workspace) return
+ * MOSS_ERR_INVALID_ARG with moss_last_error() set.
+ */
+#define MOSS_LBS_WEIGHT_NET_PARAMS 16
+#define MOSS_LBS_WEIGHT_NET_SAVED_FLOATS 640
+#define MOSS_LBS_WEIGHT_NET_SPLITS 64
+typedef struct moss_lbs_weight_net_args {
+    int32_t P;
+    const float* x;                          /* (P,3) */
+    const float* Rs;                         /* (23,3,3) */
+    const float* params[MOSS_LBS_WEIGHT_NET_PARAMS];
+    float* out;                              /* (P,24) */
+    float* saved;                            /* moss_lbs_weight_net_saved_bytes(P), or NULL */
+} moss_lbs_weight_net_args;
+int moss_lbs_weight_net_forward(const moss_lbs_weight_net_args* args, void* stream);   /* nets/mlp_delta_weight_lbs.py:31-54 */
+
+typedef struct moss_lbs_weight_net_backward_args {
+    int32_t P;
+    const float* Rs;
+    const float* params[MOSS_LBS_WEIGHT_NET_PARAMS];
+    const float* saved;                      /* as the forward wrote it */
+    const float* g_out;                      /* (P,24) */
+    float* g_x;                              /* (P,3) */
+    float* g_Rs;                             /* (23,3,3) */
+    float* grads[MOSS_LBS_WEIGHT_NET_PARAMS];/* every one written, shaped as params */
+    char* workspace;
+    size_t workspace_bytes;
+} moss_lbs_weight_net_backward_args;
+int moss_lbs_weight_net_backward(const moss_lbs_weight_net_backward_args* args, void* stream);   /* the adjoint of nets/mlp_delta_weight_lbs.py:31-54 */
+size_t moss_lbs_weight_net_workspace_bytes(int P);  /* scratch of the backward of nets/mlp_delta_weight_lbs.py:31-54; 0 for P <= 0 */
+size_t moss_lbs_weight_net_saved_bytes(int P);      /* what its forward keeps for the backward; 0 for P <= 0 */
+
+/*
  * k nearest reference points of every query point, 3-D, exact, k = 1..4: replaces the third-party
  * `knn_cuda.KNN(k, transpose_mode=True)(ref, query)` MOSS calls at scene/gaussian_model.py:85-86,586,657,759,827 (a CUDA-only
  * binary wheel, not in the repository; parity unpinned by the reference).

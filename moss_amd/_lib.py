@@ -95,6 +95,14 @@ def _declare(lib):
     lib.moss_pose_head_backward.argtypes = [_p, _p]
     lib.moss_matrix_fisher_nll.restype = _i
     lib.moss_matrix_fisher_nll.argtypes = [_i, _p, _p, _f, _p, _p, _p]
+    lib.moss_lbs_weight_net_forward.restype = _i
+    lib.moss_lbs_weight_net_forward.argtypes = [_p, _p]
+    lib.moss_lbs_weight_net_backward.restype = _i
+    lib.moss_lbs_weight_net_backward.argtypes = [_p, _p]
+    lib.moss_lbs_weight_net_workspace_bytes.restype = C.c_size_t
+    lib.moss_lbs_weight_net_workspace_bytes.argtypes = [_i]
+    lib.moss_lbs_weight_net_saved_bytes.restype = C.c_size_t
+    lib.moss_lbs_weight_net_saved_bytes.argtypes = [_i]
     lib.moss_photometric_loss_roi.restype = _i
     lib.moss_photometric_loss_roi.argtypes = [_i, _i, _i, _p, _p, _p, _p, _p, _p, _f, _f, _f, _p, _p, _p, _p, C.c_size_t, _p]
     lib.moss_adamw_flat_ex.restype = _i
@@ -176,6 +184,19 @@ class PoseHeadBackwardArgs(C.Structure):
     """``moss_pose_head_backward_args`` of include/moss_raster.h (``moss_pose_head_backward``)."""
     _fields_ = _POSE_INPUTS + [("S", C.c_void_p), ("saved", C.c_void_p), ("g_Rs", C.c_void_p), ("g_nll", C.c_void_p),
                                ("grads", C.c_void_p * 52)]
+
+
+class LbsWeightNetArgs(C.Structure):
+    """``moss_lbs_weight_net_args`` of include/moss_raster.h (``moss_lbs_weight_net_forward``: MOSS's CrossAttention_lbs)."""
+    _fields_ = [("P", C.c_int32), ("x", C.c_void_p), ("Rs", C.c_void_p), ("params", C.c_void_p * 16), ("out", C.c_void_p),
+                ("saved", C.c_void_p)]
+
+
+class LbsWeightNetBackwardArgs(C.Structure):
+    """``moss_lbs_weight_net_backward_args`` of include/moss_raster.h (``moss_lbs_weight_net_backward``)."""
+    _fields_ = [("P", C.c_int32), ("Rs", C.c_void_p), ("params", C.c_void_p * 16), ("saved", C.c_void_p), ("g_out", C.c_void_p),
+                ("g_x", C.c_void_p), ("g_Rs", C.c_void_p), ("grads", C.c_void_p * 16), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_size_t)]
 
 
 OPT_BITS = {"means3D": 1, "sh": 2, "opacity": 4, "scales": 8, "rotations": 16}      # MOSS_OPT_*; position = index in the struct's arrays

@@ -41,6 +41,7 @@ SOURCES = {
     "metrics.hip": [],
     "lbs.hip": [],
     "pose_head.hip": [],
+    "lbs_weight_net.hip": [],
     "optim.hip": [],
     "activations.hip": [],
     "densify.hip": [],

@@ -1,0 +1,571 @@
+// lbs_weight_net.hip -- MOSS's LBS-weight network, CrossAttention_lbs.forward (nets/mlp_delta_weight_lbs.py:31-54), and its adjoint
+// (include/moss_raster.h moss_lbs_weight_net_forward / _backward).
+//
+// Per point x (3), with the frame's refined rotations Rs (23,3,3):
+//     e (63)  = [x, sin(x 2^0), cos(x 2^0), ..., sin(x 2^9), cos(x 2^9)]           (accurate sincosf: the arguments reach +-512)
+//     h0 = relu(W0 e + b0), h1 = relu(W1 h0 + b1), h2 = relu(W2 h1 + b2), h3 = relu(W3 [e ; h2] + b3)
+//     q0 = Wfc h3 + bfc (24),  Q = Wq q0 + bq (24)
+//     M (24,9) = a row of ONES, then Rs[j] flattened;  K = M Wk^T + bk,  V = M Wv^T + bv
+//     s = Q . K / sqrt(24) (9),  a = softmax(s),  out[j] = sum_c a[c] V[j,c] (24)
+// MOSS runs this as ~40 torch launches over all P Gaussians (MIOpen / hipBLASLt GEMMs, every hidden activation through HBM several
+// times).  Here every product with a 128-wide side runs on the f32-input matrix cores (v_mfma_f32_32x32x2_f32: exact float32, an
+// ordered fmaf chain), a 32x32 output block per wave:
+//   forward, ONE launch: a workgroup of 4 waves owns 32 points.  The activations of the tile live in LDS (A operand: lane = point),
+//     the weights are read from L2 as the B operand (lane = output channel; wave w owns channels 32 w ...).  A lane reads FOUR
+//     consecutive k of its row at once and the four MFMAs that follow take k = k0 + 4 (lane / 32) + s from both operands: the order
+//     of the contraction index is free as long as A and B agree.  bw_fc (24 outputs: one block) is split over the four waves by k and
+//     summed in wave order.  Q, the scores, the softmax and the output: eight threads per point.  K and V are formed by every
+//     workgroup.  Per point the kernel reads x and writes out and -- for a backward -- one row of `saved`.
+//   backward, THREE launches (the activations are SAVED, not recomputed: DESIGN 4.14):
+//     1. data gradients, per tile of 32 points: softmax / attention adjoint, then d(pre-activation) of bw_fc and the four layers
+//        back to front (B operand = the weight rows as stored: coalesced), each written to the workspace; g_x from d e.
+//     2. weight gradients: dW[n][k] = sum_p dz[p][n] in[p][k], a matrix product over the POINTS.  Both operands are read straight
+//        from global memory in the layout the MFMA wants (lane = column).  A wave owns one (32 x 64) block of one tensor and one of
+//        MOSS_LBS_WEIGHT_NET_SPLITS fixed ranges of points; it writes its partial block.  The biases are the column sums of dz
+//        (a VALU add beside the MFMAs); d K and d V (24 x 9, sums over the points too) are two more blocks of the same machinery.
+//     3. fold: the partial blocks are summed in split order into the 12 gradient tensors; one more workgroup folds d K, d V and
+//        forms the gradients of key.*, value.* and Rs from them.
+// Every sum has a fixed order and there is no atomic: results are bitwise reproducible.  Every output element is written.
+#include "common.h"
+
+namespace moss {
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int NPAR = MOSS_LBS_WEIGHT_NET_PARAMS;
+constexpr int T = 32;                      // points per workgroup
+constexpr int WG = 256;                    // 4 waves
+constexpr int NE = 63, NH = 128, NF = 24, NC = 9, NR = 24, NFREQ = 10;
+constexpr int W3_LD = NE + NH;             // 191
+// parameter indices (the state_dict order of the header)
+enum { P_W0, P_B0, P_W1, P_B1, P_W2, P_B2, P_W3, P_B3, P_WFC, P_BFC, P_WQ, P_BQ, P_WK, P_BK, P_WV, P_BV };
+// a row of `saved` (floats): [e, one zero, h2] is contiguous, as layer 3 reads it
+constexpr int SV_H0 = 0, SV_H1 = 128, SV_E = 256, SV_H2 = 320, SV_H3 = 448, SV_Q0 = 576, SV_Q = 600, SV_A = 624, SV_ROW = 640;
+static_assert(SV_ROW == MOSS_LBS_WEIGHT_NET_SAVED_FLOATS, "saved row");
+// a row of the backward's workspace (floats): d pre-activations of the four layers, d q0, d Q, d s / sqrt(24)
+constexpr int WS_DZ0 = 0, WS_DZ1 = 128, WS_DZ2 = 256, WS_DZ3 = 384, WS_DQ0 = 512, WS_DQ = 536, WS_DS = 560, WS_ROW = 576;
+// the flat gradient vector of a split: the 12 tensors of the network in order, then d K and d V (24 x 9 each)
+constexpr int G_W0 = 0, G_B0 = G_W0 + NH * NE, G_W1 = G_B0 + NH, G_B1 = G_W1 + NH * NH, G_W2 = G_B1 + NH, G_B2 = G_W2 + NH * NH,
+              G_W3 = G_B2 + NH, G_B3 = G_W3 + NH * W3_LD, G_WFC = G_B3 + NH, G_BFC = G_WFC + NF * NH, G_WQ = G_BFC + NF,
+              G_BQ = G_WQ + NF * NF, G_NET = G_BQ + NF, G_DK = G_NET, G_DV = G_DK + NR * NC, G_ALL = G_DV + NR * NC;
+static_assert(G_NET == 69488, "flat gradient layout");
+constexpr int SPLITS = MOSS_LBS_WEIGHT_NET_SPLITS;
+// LDS row strides (floats): = 4 mod 64, so that the 32 lanes of a half wave read their float4 from 32 different bank groups
+constexpr int H_LD = 132, EH_LD = 196, Q_LD = 36;
+
+__device__ __forceinline__ int acc_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }   // C/D: col = lane & 31
+
+__device__ __forceinline__ f32x16 splat(float v)
+{
+    f32x16 r;
+#pragma unroll
+    for (int i = 0; i < 16; i++) r[i] = v;
+    return r;
+}
+
+#define MOSS_MFMA4(acc, av, bv)                                                  \
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv[0], acc, 0, 0, 0);       \
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv[1], acc, 0, 0, 0);       \
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv[2], acc, 0, 0, 0);       \
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv[3], acc, 0, 0, 0)
+
+// acc[pt][n] += sum_{k in [kbase, kbase + K)} A[pt][k] W[n][k]: A in LDS (a_row = this lane's point), W (out, LD) row-major in
+// global memory.  SKIP: A is [e (63), 0, h2 (128)] and W is W3 (LD = 191): column 63 of A has no weight.
+template <int K, int LD, bool SKIP>
+__device__ __forceinline__ f32x16 gemm_wt(const float* __restrict__ W, int n, bool n_ok, const float* a_row, int half, f32x16 acc,
+                                          int kbase = 0)
+{
+    const float* w = W + (size_t)(n_ok ? n : 0) * LD;
+#pragma unroll 2
+    for (int k0 = kbase; k0 < kbase + K; k0 += 8) {
+        const int kk = k0 + 4 * half;
+        const float4 av = *reinterpret_cast<const float4*>(a_row + kk);
+        float bv[4];
+#pragma unroll
+        for (int s = 0; s < 4; s++) {
+            const int k = kk + s;
+            const bool ok = n_ok && (SKIP ? k != NE : k < LD);
+            const int kw = SKIP ? (k < NE ? k : k - 1) : k;
+            bv[s] = ok ? w[kw] : 0.0f;
+        }
+        MOSS_MFMA4(acc, av, bv);
+    }
+    return acc;
+}
+
+// acc[pt][col] = sum_{k < K} A[pt][k] W[k][col] (rows k >= kvalid and a column that is not ok count as zero): the adjoint products
+template <int K>
+__device__ __forceinline__ f32x16 gemm_w(const float* __restrict__ W, int ld, int kvalid, int col, bool col_ok, const float* a_row, int half)
+{
+    f32x16 acc = splat(0.0f);
+    const float* w = W + (col_ok ? col : 0);
+#pragma unroll 2
+    for (int k0 = 0; k0 < K; k0 += 8) {
+        const int kk = k0 + 4 * half;
+        const float4 av = *reinterpret_cast<const float4*>(a_row + kk);
+        float bv[4];
+#pragma unroll
+        for (int s = 0; s < 4; s++) bv[s] = (col_ok && kk + s < kvalid) ? w[(size_t)(kk + s) * ld] : 0.0f;
+        MOSS_MFMA4(acc, av, bv);
+    }
+    return acc;
+}
+
+// relu(acc) -> LDS [row][col] and, with `saved`, the rows of the points that exist
+__device__ __forceinline__ void store_act(const f32x16& acc, float* lds, int ld, int col, int half, float* saved, int sv_col, int p0, int P)
+{
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int row = acc_row(r, half);
+        const float v = fmaxf(acc[r], 0.0f);
+        lds[row * ld + col] = v;
+        if (saved && p0 + row < P) saved[(size_t)(p0 + row) * SV_ROW + sv_col] = v;
+    }
+}
+
+// K = M Wk^T + bk, V = M Wv^T + bv (24 x 9) and a copy of Wq, into LDS (no barrier inside)
+__device__ __forceinline__ void head_constants(const float* __restrict__ Rs, const float* const* par, float* s_K, float* s_V, float* s_Wq, int tid)
+{
+    if (tid < NR * NC) {
+        const int r = tid / NC, c = tid % NC;
+        float k = par[P_BK][c], v = par[P_BV][c];
+#pragma unroll
+        for (int i = 0; i < NC; i++) {
+            const float m = r == 0 ? 1.0f : Rs[(r - 1) * NC + i];
+            k = __fmaf_rn(m, par[P_WK][c * NC + i], k);
+            v = __fmaf_rn(m, par[P_WV][c * NC + i], v);
+        }
+        s_K[tid] = k;
+        s_V[tid] = v;
+    }
+    for (int i = tid; i < NF * NF; i += WG) s_Wq[i] = par[P_WQ][i];
+}
+
+__global__ void __launch_bounds__(WG)
+lbs_weight_net_forward_kernel(const moss_lbs_weight_net_args a)
+{
+    __shared__ __attribute__((aligned(16))) float s_eh[T * EH_LD];      // [e (63), 0, h2 (128)]
+    __shared__ __attribute__((aligned(16))) float s_a[T * H_LD], s_b[T * H_LD];
+    __shared__ float s_K[NR * NC], s_V[NR * NC], s_Wq[NF * NF], s_q0[T][NF], s_Q[T][NF], s_s[T][12];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, half = lane >> 5;
+    const int p0 = blockIdx.x * T, P = a.P;
+    const float* const* par = a.params;
+    float* saved = a.saved;
+
+    head_constants(a.Rs, par, s_K, s_V, s_Wq, tid);
+    for (int i = tid; i < T * 3 * NFREQ; i += WG) {
+        const int pt = i / (3 * NFREQ), r = i % (3 * NFREQ), f = r / 3, d = r % 3;
+        const float xv = p0 + pt < P ? a.x[(size_t)(p0 + pt) * 3 + d] : 0.0f;
+        float sn, cs;
+        sincosf(xv * (float)(1 << f), &sn, &cs);
+        float* e = s_eh + pt * EH_LD;
+        e[3 + 6 * f + d] = sn;
+        e[6 + 6 * f + d] = cs;
+        if (f == 0) e[d] = xv;
+        if (r == 0) e[NE] = 0.0f;
+    }
+    __syncthreads();
+    if (saved)
+        for (int i = tid; i < T * 64; i += WG) {
+            const int pt = i >> 6, k = i & 63;
+            if (p0 + pt < P) saved[(size_t)(p0 + pt) * SV_ROW + SV_E + k] = s_eh[pt * EH_LD + k];
+        }
+
+    const int n = 32 * wave + j;                                        // this lane's output channel in the 128-wide layers
+    f32x16 acc = gemm_wt<64, NE, false>(par[P_W0], n, true, s_eh + j * EH_LD, half, splat(par[P_B0][n]));
+    store_act(acc, s_a, H_LD, n, half, saved, SV_H0 + n, p0, P);
+    __syncthreads();
+    acc = gemm_wt<NH, NH, false>(par[P_W1], n, true, s_a + j * H_LD, half, splat(par[P_B1][n]));
+    store_act(acc, s_b, H_LD, n, half, saved, SV_H1 + n, p0, P);
+    __syncthreads();
+    acc = gemm_wt<NH, NH, false>(par[P_W2], n, true, s_b + j * H_LD, half, splat(par[P_B2][n]));
+    store_act(acc, s_eh, EH_LD, 64 + n, half, saved, SV_H2 + n, p0, P);
+    __syncthreads();
+    acc = gemm_wt<64 + NH, W3_LD, true>(par[P_W3], n, true, s_eh + j * EH_LD, half, splat(par[P_B3][n]));
+    store_act(acc, s_a, H_LD, n, half, saved, SV_H3 + n, p0, P);
+    __syncthreads();
+    // bw_fc: one 32 x 32 block (24 channels), the k range split over the waves; the four partial blocks go to s_b
+    acc = gemm_wt<NH / 4, NH, false>(par[P_WFC], j, j < NF, s_a + j * H_LD, half, splat(0.0f), (NH / 4) * wave);
+#pragma unroll
+    for (int r = 0; r < 16; r++) s_b[wave * 1024 + acc_row(r, half) * 32 + j] = acc[r];
+    __syncthreads();
+
+    // the head: eight threads per point
+    const int pt = tid >> 3, sub = tid & 7;
+    const bool live = p0 + pt < P;
+    float* sv = saved && live ? saved + (size_t)(p0 + pt) * SV_ROW : nullptr;
+#pragma unroll
+    for (int k = sub; k < NF; k += 8) {
+        const float* q = s_b + pt * 32 + k;
+        const float v = (((q[0] + q[1024]) + q[2048]) + q[3072]) + par[P_BFC][k];
+        s_q0[pt][k] = v;
+        if (sv) sv[SV_Q0 + k] = v;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = sub; i < NF; i += 8) {
+        float v = par[P_BQ][i];
+#pragma unroll
+        for (int k = 0; k < NF; k++) v = __fmaf_rn(s_Wq[i * NF + k], s_q0[pt][k], v);
+        s_Q[pt][i] = v;
+        if (sv) sv[SV_Q + i] = v;
+    }
+    __syncthreads();
+    for (int c = sub; c < NC; c += 8) {
+        float v = 0.0f;
+#pragma unroll
+        for (int i = 0; i < NF; i++) v = __fmaf_rn(s_Q[pt][i], s_K[i * NC + c], v);
+        s_s[pt][c] = v / sqrtf((float)NF);
+    }
+    __syncthreads();
+    float att[NC], m = s_s[pt][0], sum = 0.0f;
+#pragma unroll
+    for (int c = 1; c < NC; c++) m = fmaxf(m, s_s[pt][c]);
+#pragma unroll
+    for (int c = 0; c < NC; c++) { att[c] = expf(s_s[pt][c] - m); sum += att[c]; }
+#pragma unroll
+    for (int c = 0; c < NC; c++) att[c] /= sum;
+    if (sv) {
+        if (sub == 0) {
+#pragma unroll
+            for (int c = 0; c < NC; c++) sv[SV_A + c] = att[c];
+        } else if (sub == 1) {
+#pragma unroll
+            for (int c = NC; c < SV_ROW - SV_A; c++) sv[SV_A + c] = 0.0f;      // (the row's padding: defined, never read)
+        }
+    }
+    if (live) {
+#pragma unroll
+        for (int o = sub; o < NR; o += 8) {
+            float v = 0.0f;
+#pragma unroll
+            for (int c = 0; c < NC; c++) v = __fmaf_rn(att[c], s_V[o * NC + c], v);
+            a.out[(size_t)(p0 + pt) * NR + o] = v;
+        }
+    }
+}
+
+// backward 1: the data gradients of a tile of points
+__global__ void __launch_bounds__(WG)
+lbs_weight_net_backward_data_kernel(const moss_lbs_weight_net_backward_args a, float* __restrict__ ws)
+{
+    __shared__ __attribute__((aligned(16))) float s_x[T * H_LD], s_y[T * H_LD], s_z[T * H_LD], s_dq0[T * Q_LD];
+    __shared__ float s_K[NR * NC], s_V[NR * NC], s_Wq[NF * NF], s_g[T][NR], s_att[T][12], s_da[T][12], s_ds[T][12], s_dQ[T][NF];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, half = lane >> 5;
+    const int p0 = blockIdx.x * T, P = a.P;
+    const float* const* par = a.params;
+    const float* saved = a.saved;
+
+    head_constants(a.Rs, par, s_K, s_V, s_Wq, tid);
+    for (int i = tid; i < T * NR; i += WG) {
+        const int pt = i / NR;
+        s_g[pt][i % NR] = p0 + pt < P ? a.g_out[(size_t)p0 * NR + i] : 0.0f;
+    }
+    for (int i = tid; i < T * NC; i += WG) {
+        const int pt = i / NC, c = i % NC;
+        s_att[pt][c] = p0 + pt < P ? saved[(size_t)(p0 + pt) * SV_ROW + SV_A + c] : 0.0f;
+    }
+    for (int i = tid; i < T * (Q_LD - NF); i += WG) s_dq0[(i / (Q_LD - NF)) * Q_LD + NF + i % (Q_LD - NF)] = 0.0f;
+    __syncthreads();
+
+    const int pt = tid >> 3, sub = tid & 7;
+    const bool live = p0 + pt < P;
+    float* wrow = live ? ws + (size_t)(p0 + pt) * WS_ROW : nullptr;
+    for (int c = sub; c < NC; c += 8) {
+        float v = 0.0f;
+#pragma unroll
+        for (int o = 0; o < NR; o++) v = __fmaf_rn(s_g[pt][o], s_V[o * NC + c], v);
+        s_da[pt][c] = v;
+    }
+    __syncthreads();
+    {
+        float dot = 0.0f;
+#pragma unroll
+        for (int c = 0; c < NC; c++) dot = __fmaf_rn(s_att[pt][c], s_da[pt][c], dot);
+        for (int c = sub; c < NC; c += 8) {
+            const float v = s_att[pt][c] * (s_da[pt][c] - dot) / sqrtf((float)NF);
+            s_ds[pt][c] = v;
+            if (wrow) wrow[WS_DS + c] = v;
+        }
+        if (wrow && sub == 7)
+            for (int c = NC; c < WS_ROW - WS_DS; c++) wrow[WS_DS + c] = 0.0f;   // (the row's padding: defined, never read)
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = sub; i < NF; i += 8) {
+        float v = 0.0f;
+#pragma unroll
+        for (int c = 0; c < NC; c++) v = __fmaf_rn(s_ds[pt][c], s_K[i * NC + c], v);
+        s_dQ[pt][i] = v;
+        if (wrow) wrow[WS_DQ + i] = v;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = sub; k < NF; k += 8) {
+        float v = 0.0f;
+#pragma unroll
+        for (int i = 0; i < NF; i++) v = __fmaf_rn(s_Wq[i * NF + k], s_dQ[pt][i], v);
+        s_dq0[pt * Q_LD + k] = v;
+        if (wrow) wrow[WS_DQ0 + k] = v;
+    }
+    __syncthreads();
+
+    const int n = 32 * wave + j;
+    // d z = (h > 0) * acc -> LDS and the workspace
+    auto store_dz = [&](const f32x16& acc, float* lds, int sv_col, int ws_col) {
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const int row = acc_row(r, half);
+            const bool ok = p0 + row < P;
+            const float h = ok ? saved[(size_t)(p0 + row) * SV_ROW + sv_col + n] : 0.0f;
+            const float v = h > 0.0f ? acc[r] : 0.0f;
+            lds[row * H_LD + n] = v;
+            if (ok) ws[(size_t)(p0 + row) * WS_ROW + ws_col + n] = v;
+        }
+    };
+    f32x16 acc = gemm_w<32>(par[P_WFC], NH, NF, n, true, s_dq0 + j * Q_LD, half);
+    store_dz(acc, s_x, SV_H3, WS_DZ3);
+    __syncthreads();
+    acc = gemm_w<NH>(par[P_W3], W3_LD, NH, NE + n, true, s_x + j * H_LD, half);
+    store_dz(acc, s_y, SV_H2, WS_DZ2);
+    __syncthreads();
+    acc = gemm_w<NH>(par[P_W2], NH, NH, n, true, s_y + j * H_LD, half);
+    store_dz(acc, s_z, SV_H1, WS_DZ1);
+    __syncthreads();
+    acc = gemm_w<NH>(par[P_W1], NH, NH, n, true, s_z + j * H_LD, half);
+    store_dz(acc, s_y, SV_H0, WS_DZ0);                                  // (d z2 in s_y was last read before the barrier above)
+    __syncthreads();
+    // d e = d z3 . W3[:, :63] + d z0 . W0: two blocks of 32 columns each, one product per wave, the two halves into s_z
+    {
+        const int col = 32 * (wave & 1) + j;
+        acc = (wave >> 1) == 0 ? gemm_w<NH>(par[P_W3], W3_LD, NH, col, col < NE, s_x + j * H_LD, half)
+                               : gemm_w<NH>(par[P_W0], NE, NH, col, col < NE, s_y + j * H_LD, half);
+#pragma unroll
+        for (int r = 0; r < 16; r++) s_z[acc_row(r, half) * H_LD + 64 * (wave >> 1) + col] = acc[r];
+    }
+    __syncthreads();
+    if (tid < T * 3) {
+        const int q = tid / 3, d = tid % 3;
+        if (p0 + q < P) {
+            const float* z = s_z + q * H_LD;
+            const float* e = saved + (size_t)(p0 + q) * SV_ROW + SV_E;
+            float v = z[d] + z[64 + d];
+#pragma unroll
+            for (int f = 0; f < NFREQ; f++) {
+                const int is = 3 + 6 * f + d, ic = is + 3;
+                const float dsn = z[is] + z[64 + is], dcs = z[ic] + z[64 + ic];
+                v += (float)(1 << f) * (e[ic] * dsn - e[is] * dcs);
+            }
+            a.g_x[(size_t)(p0 + q) * 3 + d] = v;
+        }
+    }
+}
+
+// backward 2: one (32 x 64) block of one weight gradient over one range of points, per wave
+struct WgItem { int a_src, a_off, a_ld, a_n, b_src, b_off, b_ld, b_n, out_off, out_ld, bias_off; };
+constexpr int MAX_ITEMS = 40;
+struct WgItems { int count; WgItem it[MAX_ITEMS]; };
+
+__global__ void __launch_bounds__(WG)
+lbs_weight_net_backward_weights_kernel(int P, int chunk, const float* __restrict__ saved, const float* __restrict__ ws,
+                                       const float* __restrict__ g_out, float* __restrict__ partial, const WgItems items)
+{
+    const int lane = threadIdx.x & 63, j = lane & 31, half = lane >> 5;
+    const int id = blockIdx.x * (WG / 64) + (threadIdx.x >> 6);
+    if (id >= items.count * SPLITS) return;
+    const int split = id / items.count;
+    const WgItem it = items.it[id % items.count];
+    const float* src[3] = {saved, ws, g_out};
+    const float* A = src[it.a_src] + it.a_off + j;
+    const float* B = src[it.b_src] + it.b_off + j;
+    const bool a_ok = j < it.a_n, b0_ok = j < it.b_n, b1_ok = j + 32 < it.b_n;
+    const int pbeg = min(P, split * chunk), pend = min(P, pbeg + chunk);
+    f32x16 acc0 = splat(0.0f), acc1 = splat(0.0f);
+    float bsum = 0.0f;
+    const bool wide = it.b_n > 32;                                      // (wave-uniform)
+    for (int q = pbeg; q < pend; q += 8) {                              // four MFMA steps of two points; the loads first
+        float av[4], b0[4], b1[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const int p = q + 2 * u + half;
+            const bool ok = p < pend;
+            av[u] = ok && a_ok ? A[(size_t)p * it.a_ld] : 0.0f;
+            b0[u] = ok && b0_ok ? B[(size_t)p * it.b_ld] : 0.0f;
+            b1[u] = ok && b1_ok ? B[(size_t)p * it.b_ld + 32] : 0.0f;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], b0[u], acc0, 0, 0, 0);
+            if (wide) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], b1[u], acc1, 0, 0, 0);
+            bsum += av[u];
+        }
+    }
+    float* out = partial + (size_t)split * G_ALL;
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int row = acc_row(r, half);
+        if (row < it.a_n) {
+            if (b0_ok) out[it.out_off + row * it.out_ld + j] = acc0[r];
+            if (b1_ok) out[it.out_off + row * it.out_ld + 32 + j] = acc1[r];
+        }
+    }
+    bsum += __shfl_xor(bsum, 32);
+    if (it.bias_off >= 0 && half == 0 && a_ok) out[it.bias_off + j] = bsum;
+}
+
+struct GradPtrs { float* g[NPAR]; };
+
+// backward 3: the partial sums in split order; the last workgroup: d K, d V -> the gradients of key.*, value.* and Rs
+__global__ void __launch_bounds__(WG)
+lbs_weight_net_backward_fold_kernel(const float* __restrict__ partial, const float* __restrict__ Rs, const float* __restrict__ Wk,
+                                    const float* __restrict__ Wv, const GradPtrs grads, float* __restrict__ g_Rs)
+{
+    const int tid = threadIdx.x;
+    if (blockIdx.x + 1 < gridDim.x) {
+        const int idx = blockIdx.x * WG + tid;
+        if (idx >= G_NET) return;
+        float v = 0.0f;
+        for (int s = 0; s < SPLITS; s++) v += partial[(size_t)s * G_ALL + idx];
+        constexpr int first[13] = {G_W0, G_B0, G_W1, G_B1, G_W2, G_B2, G_W3, G_B3, G_WFC, G_BFC, G_WQ, G_BQ, G_NET};
+        int t = 0;
+#pragma unroll
+        for (int i = 1; i < 12; i++) t += idx >= first[i];
+        int base = 0;
+#pragma unroll
+        for (int i = 1; i < 12; i++) base = idx >= first[i] ? first[i] : base;
+        grads.g[t][idx - base] = v;
+        return;
+    }
+    __shared__ float s_dK[NR * NC], s_dV[NR * NC];
+    for (int i = tid; i < 2 * NR * NC; i += WG) {
+        float v = 0.0f;
+        for (int s = 0; s < SPLITS; s++) v += partial[(size_t)s * G_ALL + G_DK + i];
+        (i < NR * NC ? s_dK[i] : s_dV[i - NR * NC]) = v;
+    }
+    __syncthreads();
+    if (tid < NR * NC) {
+        // d M = d K Wk + d V Wv; rows 1..23 are d Rs
+        const int r = tid / NC, c = tid % NC;
+        if (r > 0) {
+            float v = 0.0f;
+#pragma unroll
+            for (int o = 0; o < NC; o++) v = __fmaf_rn(s_dK[r * NC + o], Wk[o * NC + c], v);
+#pragma unroll
+            for (int o = 0; o < NC; o++) v = __fmaf_rn(s_dV[r * NC + o], Wv[o * NC + c], v);
+            g_Rs[(r - 1) * NC + c] = v;
+        }
+    }
+    if (tid < NC * NC) {
+        // d Wk[o][c] = sum_r d K[r][o] M[r][c]
+        const int o = tid / NC, c = tid % NC;
+        float k = 0.0f, v = 0.0f;
+        for (int r = 0; r < NR; r++) {
+            const float m = r == 0 ? 1.0f : Rs[(r - 1) * NC + c];
+            k = __fmaf_rn(s_dK[r * NC + o], m, k);
+            v = __fmaf_rn(s_dV[r * NC + o], m, v);
+        }
+        grads.g[P_WK][tid] = k;
+        grads.g[P_WV][tid] = v;
+    } else if (tid >= 128 && tid < 128 + NC) {
+        const int o = tid - 128;
+        float k = 0.0f, v = 0.0f;
+        for (int r = 0; r < NR; r++) { k += s_dK[r * NC + o]; v += s_dV[r * NC + o]; }
+        grads.g[P_BK][o] = k;
+        grads.g[P_BV][o] = v;
+    }
+}
+
+void add_items(WgItems& w, int a_src, int a_off, int a_cols, int b_src, int b_off, int b_cols, int out_base, int out_ld, int bias_base)
+{
+    const int ld[3] = {SV_ROW, WS_ROW, NR};
+    for (int n0 = 0; n0 < a_cols; n0 += 32)
+        for (int k0 = 0; k0 < b_cols; k0 += 64) {
+            WgItem& it = w.it[w.count++];
+            it.a_src = a_src; it.a_off = a_off + n0; it.a_ld = ld[a_src]; it.a_n = std::min(32, a_cols - n0);
+            it.b_src = b_src; it.b_off = b_off + k0; it.b_ld = ld[b_src]; it.b_n = std::min(64, b_cols - k0);
+            it.out_off = out_base + n0 * out_ld + k0; it.out_ld = out_ld;
+            it.bias_off = (k0 == 0 && bias_base >= 0) ? bias_base + n0 : -1;
+        }
+}
+
+const WgItems& weight_items()
+{
+    static const WgItems items = [] {
+        WgItems w{};
+        enum { SAVED, WS, GOUT };
+        add_items(w, WS, WS_DZ0, NH, SAVED, SV_E, NE, G_W0, NE, G_B0);
+        add_items(w, WS, WS_DZ1, NH, SAVED, SV_H0, NH, G_W1, NH, G_B1);
+        add_items(w, WS, WS_DZ2, NH, SAVED, SV_H1, NH, G_W2, NH, G_B2);
+        add_items(w, WS, WS_DZ3, NH, SAVED, SV_E, NE, G_W3, W3_LD, G_B3);
+        add_items(w, WS, WS_DZ3, NH, SAVED, SV_H2, NH, G_W3 + NE, W3_LD, -1);
+        add_items(w, WS, WS_DQ0, NF, SAVED, SV_H3, NH, G_WFC, NH, G_BFC);
+        add_items(w, WS, WS_DQ, NF, SAVED, SV_Q0, NF, G_WQ, NF, G_BQ);
+        add_items(w, SAVED, SV_Q, NF, WS, WS_DS, NC, G_DK, NC, -1);       // d K[i][c] = sum_p Q[i] d s[c] / sqrt(24)
+        add_items(w, GOUT, 0, NR, SAVED, SV_A, NC, G_DV, NC, -1);         // d V[j][c] = sum_p g[j] a[c]
+        return w;
+    }();
+    return items;
+}
+
+size_t ws_rows_bytes(int P) { return align_up((size_t)P * WS_ROW * sizeof(float)); }
+
+int net_err(const char* msg) { return set_last_error(MOSS_ERR_INVALID_ARG, msg); }
+
+}  // namespace
+
+}  // namespace moss
+
+using namespace moss;
+
+extern "C" size_t moss_lbs_weight_net_workspace_bytes(int P)
+{
+    return P <= 0 ? 0 : ws_rows_bytes(P) + (size_t)SPLITS * G_ALL * sizeof(float);
+}
+
+extern "C" size_t moss_lbs_weight_net_saved_bytes(int P) { return P <= 0 ? 0 : (size_t)P * SV_ROW * sizeof(float); }
+
+// CrossAttention_lbs.forward, nets/mlp_delta_weight_lbs.py:31-54
+extern "C" int moss_lbs_weight_net_forward(const moss_lbs_weight_net_args* a, void* stream)
+{
+    if (!a) return net_err("moss_lbs_weight_net_forward: null argument block");
+    if (a->P < 0) return net_err("moss_lbs_weight_net_forward: P must be >= 0");
+    if (a->P == 0) return 0;
+    if (!a->x || !a->Rs || !a->out) return net_err("moss_lbs_weight_net_forward: null x, Rs or out");
+    for (int i = 0; i < NPAR; i++)
+        if (!a->params[i]) return net_err("moss_lbs_weight_net_forward: null parameter tensor (all 16 are read)");
+    static_assert(MAX_ITEMS >= 37, "item table");
+    hipLaunchKernelGGL(lbs_weight_net_forward_kernel, dim3((a->P + T - 1) / T), dim3(WG), 0, (hipStream_t)stream, *a);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : set_last_error(MOSS_ERR_HIP, hipGetErrorString(e));
+}
+
+// the adjoint of CrossAttention_lbs.forward, nets/mlp_delta_weight_lbs.py:31-54
+extern "C" int moss_lbs_weight_net_backward(const moss_lbs_weight_net_backward_args* a, void* stream)
+{
+    if (!a) return net_err("moss_lbs_weight_net_backward: null argument block");
+    if (a->P < 0) return net_err("moss_lbs_weight_net_backward: P must be >= 0");
+    if (a->P == 0) return 0;
+    if (!a->Rs || !a->saved || !a->g_out) return net_err("moss_lbs_weight_net_backward: null Rs, saved (the forward's) or g_out");
+    if (!a->g_x || !a->g_Rs) return net_err("moss_lbs_weight_net_backward: null g_x or g_Rs (both are written)");
+    for (int i = 0; i < NPAR; i++)
+        if (!a->params[i] || !a->grads[i]) return net_err("moss_lbs_weight_net_backward: null parameter or gradient tensor (all 16 are written)");
+    if (!a->workspace || a->workspace_bytes < moss_lbs_weight_net_workspace_bytes(a->P))
+        return net_err("moss_lbs_weight_net_backward: the workspace is null or smaller than moss_lbs_weight_net_workspace_bytes(P)");
+    const int P = a->P;
+    hipStream_t s = (hipStream_t)stream;
+    float* ws = reinterpret_cast<float*>(a->workspace);
+    float* partial = reinterpret_cast<float*>(a->workspace + ws_rows_bytes(P));
+    const WgItems& items = weight_items();
+    const int chunk = ((P + SPLITS - 1) / SPLITS + 1) & ~1;           // points per split, even: an MFMA step takes two
+    GradPtrs gp;
+    for (int i = 0; i < NPAR; i++) gp.g[i] = a->grads[i];
+    hipLaunchKernelGGL(lbs_weight_net_backward_data_kernel, dim3((P + T - 1) / T), dim3(WG), 0, s, *a, ws);
+    hipLaunchKernelGGL(lbs_weight_net_backward_weights_kernel, dim3((items.count * SPLITS + WG / 64 - 1) / (WG / 64)), dim3(WG), 0, s,
+                       P, chunk, a->saved, (const float*)ws, a->g_out, partial, items);
+    hipLaunchKernelGGL(lbs_weight_net_backward_fold_kernel, dim3((G_NET + WG - 1) / WG + 1), dim3(WG), 0, s, (const float*)partial,
+                       a->Rs, a->params[P_WK], a->params[P_WV], gp, a->g_Rs);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : set_last_error(MOSS_ERR_HIP, hipGetErrorString(e));
+}

@@ -112,10 +112,16 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
         if (getattr(pipe, "pose_head_in_op", False) and getattr(pc, "motion_offset_flag", False)
                 and hasattr(pc, "auto_regression") and hasattr(pc, "cross_attention_lbs")):
             # ``pipe.pose_head_in_op`` (an addition, default off): MOSS's pose branch (reference :65-72) with the refinement head and
-            # the matrix-Fisher term as the fused HIP op (moss_amd/pose.py); cross_attention_lbs stays the caller's torch module
+            # the matrix-Fisher term as the fused HIP op (moss_amd/pose.py); cross_attention_lbs stays the caller's torch module unless
+            # ``pipe.lbs_weights_in_op`` (an addition, default off) is set: then it runs as the fused HIP op of moss_amd/lbs_weights.py
+            # on the module's parameters (a module of another layout than MOSS's CrossAttention_lbs raises: there is no fallback)
             from .pose import pose_head_fused
             pose_out = pose_head_fused(pc.auto_regression, viewpoint_camera.smpl_param['poses'], viewpoint_camera.smpl_param['pose_rotmats'])
-            lbs_weights = pc.cross_attention_lbs(means3D[None], pose_out["Rs"])
+            if getattr(pipe, "lbs_weights_in_op", False):
+                from .lbs_weights import cross_attention_lbs_fused
+                lbs_weights = cross_attention_lbs_fused(pc.cross_attention_lbs, means3D[None], pose_out["Rs"])
+            else:
+                lbs_weights = pc.cross_attention_lbs(means3D[None], pose_out["Rs"])
             correct_Rs = pose_out["Rs"].reshape(1, 23, 3, 3)
         _, world, bweights, transforms, translation = coarse_deform_c2source(
             pc, means3D[None], viewpoint_camera.smpl_param, viewpoint_camera.big_pose_smpl_param,

@@ -1,0 +1,190 @@
+"""MOSS's LBS-weight network (``CrossAttention_lbs.forward``, nets/mlp_delta_weight_lbs.py:31-54) on the device.
+
+MOSS calls ``pc.cross_attention_lbs(means3D[None], correct_Rs)`` in every training iteration of its pose branch
+(gaussian_renderer/__init__.py:72), for all P Gaussians: a 63-channel positional embedding (21 torch ops and a ``cat``), four
+``Conv1d(k=1)`` layers of width 128 with a skip, ``Conv1d(128, 24)``, three ``Linear`` layers, two batched matmuls and a softmax.  Here:
+
+* :func:`cross_attention_lbs_fused` -- all of it as ONE HIP launch forward and three backward (C ABI ``moss_lbs_weight_net_forward``
+  / ``_backward``, moss_amd/csrc/lbs_weight_net.hip), every layer on the f32-input matrix cores: no host read, no device allocation
+  inside the op, capturable, bitwise reproducible.  ``xyz``, ``Rs`` and the 16 parameters the forward reads are inputs of one
+  ``autograd.Function``; their ``.grad`` is filled as usual.
+* :func:`cross_attention_lbs_torch` -- the same mathematics in plain torch (any dtype or device, nothing read back to the host): the
+  float64 yardstick of the tests, pinned to the reference's own numbers by tests/golden/lbs_weights_*.npz, and the stand-in for MOSS's
+  module in scripts/lbs_weight_net_times.py.  Not a fallback: the fused op has no CPU path.
+* :func:`lbs_weight_module` -- a module with the reference's parameter layout, for tests, the timing script and callers without a MOSS
+  checkout.
+
+Everything here imports without a GPU.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import torch
+
+__all__ = ["cross_attention_lbs_fused", "cross_attention_lbs_torch", "lbs_weight_module", "net_parameters", "PARAM_NAMES",
+           "PARAM_SHAPES", "UNUSED_NAMES", "NUM_FREQS", "FEATURE_DIM"]
+
+NUM_FREQS = 10
+FEATURE_DIM = 24
+ROT_DIM = 9
+WIDTH = 128
+EMBED_DIM = 3 + 6 * NUM_FREQS                                # 63
+
+# the order in which the 16 parameter tensors cross the C ABI: the state_dict keys of MOSS's CrossAttention_lbs that its forward reads
+PARAM_NAMES = tuple(f"{m}.{w}" for m in ("bw_linears.0", "bw_linears.1", "bw_linears.2", "bw_linears.3", "bw_fc", "query", "key", "value")
+                    for w in ("weight", "bias"))
+# as they cross it (a Conv1d(k=1) weight (out, in, 1) is the row-major (out, in) matrix)
+PARAM_SHAPES = ((WIDTH, EMBED_DIM), (WIDTH,), (WIDTH, WIDTH), (WIDTH,), (WIDTH, WIDTH), (WIDTH,), (WIDTH, EMBED_DIM + WIDTH), (WIDTH,),
+                (FEATURE_DIM, WIDTH), (FEATURE_DIM,), (FEATURE_DIM, FEATURE_DIM), (FEATURE_DIM,), (ROT_DIM, ROT_DIM), (ROT_DIM,),
+                (ROT_DIM, ROT_DIM), (ROT_DIM,))
+# constructed by the reference, never read by its forward: they cross no boundary and their .grad stays None
+UNUSED_NAMES = ("out_layer.weight", "out_layer.bias", "gate_proj.weight", "gate_proj.bias")
+
+
+# ---- the torch form ---------------------------------------------------------------------------------------------------------------
+
+def _embed(x):
+    """``xyz_embedder`` (get_embedder(10), :87-133): the input, then per frequency 2^k three sines followed by three cosines."""
+    parts = [x]
+    for k in range(NUM_FREQS):
+        parts += [torch.sin(x * float(2 ** k)), torch.cos(x * float(2 ** k))]
+    return torch.cat(parts, -1)
+
+
+def _matrix(w):
+    return w.reshape(w.shape[0], w.shape[1])                 # Conv1d (out, in, 1) or Linear (out, in)
+
+
+def cross_attention_lbs_torch(params, xyz, Rs):
+    """``CrossAttention_lbs.forward(xyz, Rs)`` in plain torch.  ``params``: a mapping with the module's ``state_dict`` keys
+    (:data:`PARAM_NAMES`; others are ignored); ``xyz`` (1,P,3) or (P,3); ``Rs`` (23,3,3) or (1,23,3,3).  Returns (1,P,24)."""
+    x = xyz.reshape(-1, 3)
+    e = _embed(x)
+    h = e
+    for i in range(4):
+        h = torch.relu(h @ _matrix(params[f"bw_linears.{i}.weight"]).t() + params[f"bw_linears.{i}.bias"])
+        if i == 2:
+            h = torch.cat((e, h), -1)
+    q0 = h @ _matrix(params["bw_fc.weight"]).t() + params["bw_fc.bias"]
+    M = torch.cat([torch.ones(1, ROT_DIM, dtype=x.dtype, device=x.device), Rs.reshape(-1, ROT_DIM)], 0)      # (24,9)
+    Q = q0 @ params["query.weight"].t() + params["query.bias"]
+    K = M @ params["key.weight"].t() + params["key.bias"]
+    V = M @ params["value.weight"].t() + params["value.bias"]
+    att = torch.softmax((Q @ K) / (FEATURE_DIM ** 0.5), -1)
+    return (att @ V.t())[None]
+
+
+def lbs_weight_module():
+    """A module with the parameter layout (and ``state_dict`` keys) of MOSS's ``CrossAttention_lbs``, the four tensors its forward never
+    reads included, default torch initialisation; ``forward(query, key)`` is :func:`cross_attention_lbs_torch` on its own parameters."""
+    from torch import nn
+
+    class LbsWeightNet(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.bw_linears = nn.ModuleList([nn.Conv1d(EMBED_DIM, WIDTH, 1), nn.Conv1d(WIDTH, WIDTH, 1), nn.Conv1d(WIDTH, WIDTH, 1),
+                                             nn.Conv1d(WIDTH + EMBED_DIM, WIDTH, 1)])
+            self.bw_fc = nn.Conv1d(WIDTH, FEATURE_DIM, 1)
+            self.query = nn.Linear(FEATURE_DIM, FEATURE_DIM)
+            self.key = nn.Linear(ROT_DIM, ROT_DIM)
+            self.value = nn.Linear(ROT_DIM, ROT_DIM)
+            self.out_layer = nn.Linear(FEATURE_DIM, FEATURE_DIM)
+            self.gate_proj = nn.Linear(FEATURE_DIM, FEATURE_DIM)
+
+        def forward(self, query, key):
+            return cross_attention_lbs_torch(dict(self.named_parameters()), query, key)
+
+    return LbsWeightNet()
+
+
+# ---- the fused op -----------------------------------------------------------------------------------------------------------------
+
+def net_parameters(net):
+    """The 16 parameter tensors of a ``CrossAttention_lbs``-shaped module in :data:`PARAM_NAMES` order; raises if one is missing."""
+    named = dict(net.named_parameters())
+    missing = [k for k in PARAM_NAMES if k not in named]
+    if missing:
+        raise ValueError(f"cross_attention_lbs_fused: the module has no parameter {missing[0]} (it needs the layout of MOSS's "
+                         "CrossAttention_lbs: bw_linears.0-3, bw_fc, query, key, value)")
+    return [named[k] for k in PARAM_NAMES]
+
+
+def _stream(dev):
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+class _LbsWeightNet(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, Rs, *params):
+        from ._lib import LbsWeightNetArgs, check, lib
+        dev, P = x.device, int(x.shape[0])
+        out = torch.empty((1, P, FEATURE_DIM), dtype=torch.float32, device=dev)
+        keep = any(ctx.needs_input_grad)
+        saved = torch.empty(lib().moss_lbs_weight_net_saved_bytes(P) // 4 if keep else 0, dtype=torch.float32, device=dev)
+        if P > 0:
+            a = LbsWeightNetArgs()
+            a.P, a.x, a.Rs, a.out, a.saved = P, x.data_ptr(), Rs.data_ptr(), out.data_ptr(), (saved.data_ptr() if keep else None)
+            for i, p in enumerate(params):
+                a.params[i] = p.data_ptr()
+            with torch.cuda.device(dev):
+                check(lib().moss_lbs_weight_net_forward(ctypes.byref(a), _stream(dev)), "lbs_weight_net forward")
+        ctx.save_for_backward(x, Rs, saved, *params)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        from ._lib import LbsWeightNetBackwardArgs, check, lib
+        x, Rs, saved, *params = ctx.saved_tensors
+        dev, P = x.device, int(x.shape[0])
+        sizes = [3 * P, 23 * 9] + [p.numel() for p in params]
+        if P == 0:
+            flat = torch.zeros(sum(sizes), dtype=torch.float32, device=dev)
+        else:
+            flat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)             # every element is written by the kernels
+        g_x, g_Rs, *grads = flat.split(sizes)
+        if P > 0:
+            g_out = g_out.reshape(P, FEATURE_DIM).float().contiguous()
+            nbytes = lib().moss_lbs_weight_net_workspace_bytes(P)
+            workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            a = LbsWeightNetBackwardArgs()
+            a.P, a.Rs, a.saved, a.g_out = P, Rs.data_ptr(), saved.data_ptr(), g_out.data_ptr()
+            a.g_x, a.g_Rs, a.workspace, a.workspace_bytes = g_x.data_ptr(), g_Rs.data_ptr(), workspace.data_ptr(), nbytes
+            for i, (p, g) in enumerate(zip(params, grads)):
+                a.params[i], a.grads[i] = p.data_ptr(), g.data_ptr()
+            with torch.cuda.device(dev):
+                check(lib().moss_lbs_weight_net_backward(ctypes.byref(a), _stream(dev)), "lbs_weight_net backward")
+        return (g_x.view(P, 3), g_Rs.view(23, 3, 3), *[g.view(p.shape) for g, p in zip(grads, params)])
+
+
+def cross_attention_lbs_fused(net, xyz, Rs):
+    """MOSS's ``pc.cross_attention_lbs(xyz, Rs)`` as the fused HIP op: one launch forward, three backward.
+
+    ``net``: MOSS's ``CrossAttention_lbs`` instance or anything with the same parameter names and shapes (float32, contiguous, on the
+    GPU); ``xyz`` (1,P,3) or (P,3); ``Rs`` (23,3,3) or (1,23,3,3).  Returns (1,P,24).  Gradients flow to ``xyz``, ``Rs`` and the 16
+    parameters the forward reads (``out_layer`` / ``gate_proj`` are not read: their ``.grad`` stays ``None``, as with MOSS)."""
+    params = net_parameters(net)
+    for name, t in (("xyz", xyz), ("Rs", Rs), *zip(PARAM_NAMES, params)):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise RuntimeError(f"cross_attention_lbs_fused runs the HIP kernels of the LBS-weight network: {name} must be a tensor on a "
+                               "GPU (cross_attention_lbs_torch is the torch form)")
+    dev = xyz.device
+    if xyz.shape[-1:] != (3,) or xyz.dim() not in (2, 3) or (xyz.dim() == 3 and xyz.shape[0] != 1):
+        raise ValueError(f"cross_attention_lbs_fused: xyz must be (P,3) or (1,P,3), got {tuple(xyz.shape)}")
+    if tuple(Rs.shape) not in ((23, 3, 3), (1, 23, 3, 3)):
+        raise ValueError(f"cross_attention_lbs_fused: Rs must be (23,3,3) or (1,23,3,3), got {tuple(Rs.shape)}")
+    for name, t in (("xyz", xyz), ("Rs", Rs)):
+        if t.dtype != torch.float32 or t.device != dev:
+            raise ValueError(f"cross_attention_lbs_fused: {name} must be float32 on {dev}, got {t.dtype} on {t.device}")
+    for name, p, shape in zip(PARAM_NAMES, params, PARAM_SHAPES):
+        if tuple(p.shape[:2]) != shape or p.numel() != _numel(shape) or p.dtype != torch.float32 or p.device != dev or not p.is_contiguous():
+            raise ValueError(f"cross_attention_lbs_fused: {name} must be a contiguous float32 tensor of shape {shape} (a Conv1d weight: "
+                             f"{shape + (1,)}) on {dev}, got {tuple(p.shape)} {p.dtype} on {p.device}")
+    return _LbsWeightNet.apply(xyz.reshape(-1, 3).contiguous(), Rs.reshape(23, 3, 3).contiguous(), *params)
+
+
+def _numel(shape):
+    n = 1
+    for s in shape:
+        n *= s
+    return n
