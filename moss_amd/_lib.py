@@ -9,6 +9,8 @@ import ctypes as C
 import os
 import threading
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # "lib" = the product build.  MOSS_AMD_LIB_DIR=lib_diag selects the DIAGNOSTIC build (python -m moss_amd.build --diag: -DMOSS_DIAG,
 # environment knobs that pick kernel variants, stamp buffers) -- for the A/B scripts under scripts/, never for results.
@@ -239,7 +241,6 @@ def ext():
                 lib()                                        # libmoss_raster.so first: _moss_C.so links against it
                 import importlib.machinery
                 import importlib.util
-                import torch  # noqa: F401  (libtorch must be loaded before the extension)
                 loader = importlib.machinery.ExtensionFileLoader("_moss_C", EXT_PATH)
                 spec = importlib.util.spec_from_loader("_moss_C", loader)
                 mod = importlib.util.module_from_spec(spec)
@@ -277,3 +278,21 @@ def check(rc: int, what: str) -> int:
         msg = lib().moss_last_error().decode(errors="replace")
         raise RuntimeError(f"{what}: {ERR_NAMES.get(rc, rc)}: {msg}")
     return rc
+
+
+def ptr(t):
+    """The device address of tensor ``t``; None (NULL across the boundary) for None."""
+    return None if t is None else t.data_ptr()
+
+
+def stream(dev):
+    """The handle of the current stream of ``dev``: the last argument of every entry point that enqueues work."""
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+def call(name: str, dev, *args) -> int:
+    """``lib().<name>(*args, <the current stream of dev>)`` with ``dev`` as the current device, checked: THE way an op enqueues one
+    entry point.  (A site that makes several calls under one device guard writes the guard itself and uses :func:`stream` and
+    :func:`check`.)"""
+    with torch.cuda.device(dev):
+        return check(getattr(lib(), name)(*args, stream(dev)), name)

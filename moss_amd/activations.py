@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import torch
 
-from ._lib import check, lib
+from ._lib import call, ptr
 
 
 class _ActivateGaussians(torch.autograd.Function):
@@ -37,13 +37,9 @@ class _ActivateGaussians(torch.autograd.Function):
         o_opa = torch.empty_like(opacity)
         o_scl = torch.empty_like(scaling)
         o_rot = torch.empty_like(rotation)
-        ptr = lambda t: None if t is None else t.data_ptr()
-        with torch.cuda.device(dev):
-            rc = lib().moss_gaussian_activate_forward(
-                P, K, xyz.data_ptr(), ptr(features_dc), ptr(features_rest) if K > 1 else None, opacity.data_ptr(),
-                scaling.data_ptr(), rotation.data_ptr(), o_xyz.data_ptr(), ptr(o_feat), o_opa.data_ptr(), o_scl.data_ptr(),
-                o_rot.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-        check(rc, "gaussian_activate_forward")
+        call("moss_gaussian_activate_forward", dev,
+             P, K, xyz.data_ptr(), ptr(features_dc), ptr(features_rest) if K > 1 else None, opacity.data_ptr(),
+             scaling.data_ptr(), rotation.data_ptr(), o_xyz.data_ptr(), ptr(o_feat), o_opa.data_ptr(), o_scl.data_ptr(), o_rot.data_ptr())
         ctx.save_for_backward(rotation, o_opa, o_scl)
         ctx.meta = (P, K, [None if t is None else t.shape for t in ins])
         ctx.sink = sink
@@ -66,14 +62,11 @@ class _ActivateGaussians(torch.autograd.Function):
                 continue
             d = ctx.sink[i]() if ctx.sink is not None and ctx.sink[i] is not None else None
             dests.append(d if d is not None else torch.empty(shape, dtype=torch.float32, device=dev))
-        ptr = lambda t: None if t is None else t.data_ptr()
-        with torch.cuda.device(dev):
-            rc = lib().moss_gaussian_activate_backward(
-                P, K, rotation.data_ptr(), o_opa.data_ptr(), o_scl.data_ptr(),
-                ptr(gs[0]), ptr(gs[1]), ptr(gs[2]), ptr(gs[3]), ptr(gs[4]),
-                dests[0].data_ptr(), ptr(dests[1]), ptr(dests[2]) if K > 1 else None, dests[3].data_ptr(),
-                dests[4].data_ptr(), dests[5].data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-        check(rc, "gaussian_activate_backward")
+        call("moss_gaussian_activate_backward", dev,
+             P, K, rotation.data_ptr(), o_opa.data_ptr(), o_scl.data_ptr(),
+             ptr(gs[0]), ptr(gs[1]), ptr(gs[2]), ptr(gs[3]), ptr(gs[4]),
+             dests[0].data_ptr(), ptr(dests[1]), ptr(dests[2]) if K > 1 else None, dests[3].data_ptr(),
+             dests[4].data_ptr(), dests[5].data_ptr())
         out = tuple(d if (need and d is not None) else None for d, need in zip(dests, ctx.needs_input_grad[:6]))
         del dests
         return out + (None,)

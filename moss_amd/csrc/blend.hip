@@ -1346,18 +1346,6 @@ blend_backward_wave_kernel(int W, int H, int gx, const uint4* __restrict__ work_
     // every wave increments on its way out was 1024 serialised atomics at the very end of the kernel)
 }
 
-int device_cus()
-{
-    static const int n = [] {
-        int dev = 0; hipDeviceProp_t prop;
-        int cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-            cus = prop.multiProcessorCount;
-        return cus;
-    }();
-    return n;
-}
-
 // Resident workgroups of the persistent blend kernels: a fixed number per CU (dynamic balancing does the rest), never more than fit
 // together -- a wave's FIRST work item is its rank in its queue (no atomic), so a workgroup that only started once another one had
 // left would sit on its items until then (measured: +10 us when 4 were launched where 3 fit).

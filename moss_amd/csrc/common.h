@@ -391,7 +391,15 @@ __device__ __forceinline__ uint32_t rect_area(uint2 r)
     return w * h;
 }
 
-// sets the text moss_last_error() returns (defined in raster_api.hip, for the entry points of the other translation units)
+// ---- host helpers of every entry point (defined in raster_api.hip) ----------------------------------------
+#define MOSS_INTERNAL __attribute__((visibility("hidden")))      // shared by the translation units, not exported by the library
+// sets the text moss_last_error() returns; returns `code`
 int set_last_error(int code, const char* msg);
+// `entry_point` refuses its arguments: MOSS_ERR_INVALID_ARG with "<entry point>: <condition>" as the text
+MOSS_INTERNAL int invalid_arg(const char* entry_point, const char* condition);
+// the status of the launches `entry_point` has just made: 0, or MOSS_ERR_HIP with "<entry point>: <HIP's text for the error>"
+MOSS_INTERNAL int launch_status(const char* entry_point);
+// compute units of the current device (read once; 256 where it cannot be read)
+MOSS_INTERNAL int device_cus();
 
 }  // namespace moss

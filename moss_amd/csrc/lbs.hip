@@ -353,8 +353,6 @@ lbs_fold_kernel(int J, int nblocks, const float* __restrict__ partials, float* _
     if (lane == 0) gA[o] = (float)acc;
 }
 
-int lbs_err(const char* msg) { return set_last_error(MOSS_ERR_INVALID_ARG, msg); }
-
 // the instantiation for J: 24 with 16-byte row accesses when the rows are 16-byte aligned, else J rounded up to a multiple of 8
 template <template <int, bool> class F, typename... Args>
 void lbs_dispatch(int J, bool vec, Args... args)
@@ -393,12 +391,12 @@ bool aligned16(const void* p) { return p == nullptr || (reinterpret_cast<uintptr
 template <typename A>
 int lbs_check_common(const A* a)
 {
-    if (!a) return lbs_err("lbs: null argument block");
-    if (a->P < 0) return lbs_err("lbs: P must be >= 0");
-    if (a->J < 1 || a->J > LBS_MAX_J) return lbs_err("lbs: J must be 1..64");
-    if (a->V < 1) return lbs_err("lbs: V must be >= 1");
+    if (!a) return invalid_arg("lbs", "null argument block");
+    if (a->P < 0) return invalid_arg("lbs", "P must be >= 0");
+    if (a->J < 1 || a->J > LBS_MAX_J) return invalid_arg("lbs", "J must be 1..64");
+    if (a->V < 1) return invalid_arg("lbs", "V must be >= 1");
     if (!a->vert_ids || !a->weights || !a->A_big || !a->A_obs || !a->d || !a->R || !a->Th)
-        return lbs_err("lbs: null required input (vert_ids, weights, A_big, A_obs, d, R, Th)");
+        return invalid_arg("lbs", "null required input (vert_ids, weights, A_big, A_obs, d, R, Th)");
     return 0;
 }
 
@@ -424,24 +422,23 @@ extern "C" size_t moss_lbs_workspace_bytes(int P, int J)
 extern "C" int moss_lbs_deform_forward(const moss_lbs_forward_args* a, void* stream)
 {
     if (int rc = lbs_check_common(a)) return rc;
-    if (!a->T || !a->t) return lbs_err("lbs forward: null T or t");
-    if (a->p && !a->x) return lbs_err("lbs forward: p needs x");
+    if (!a->T || !a->t) return invalid_arg("lbs forward", "null T or t");
+    if (a->p && !a->x) return invalid_arg("lbs forward", "p needs x");
     if (a->P == 0) return 0;
     const bool vec = aligned16(a->weights) && aligned16(a->lbs_offsets) && aligned16(a->w);
     const dim3 grid((a->P + LBS_FWD_BLOCK - 1) / LBS_FWD_BLOCK);
     lbs_dispatch<LaunchFwd>(a->J, vec, grid, (hipStream_t)stream, lbs_in(a), a->T, a->t, a->p, a->w);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : set_last_error(MOSS_ERR_HIP, hipGetErrorString(e));
+    return launch_status("moss_lbs_deform_forward");
 }
 
 extern "C" int moss_lbs_deform_backward(const moss_lbs_backward_args* a, void* stream)
 {
     if (int rc = lbs_check_common(a)) return rc;
-    if ((a->g_p || a->g_x) && !a->x) return lbs_err("lbs backward: g_p and g_x need x");
-    if (a->g_L && !a->lbs_offsets) return lbs_err("lbs backward: g_L needs lbs_offsets");
+    if ((a->g_p || a->g_x) && !a->x) return invalid_arg("lbs backward", "g_p and g_x need x");
+    if (a->g_L && !a->lbs_offsets) return invalid_arg("lbs backward", "g_L needs lbs_offsets");
     if (a->P == 0) return 0;
     if (a->g_A_obs && (!a->workspace || a->workspace_bytes < moss_lbs_workspace_bytes(a->P, a->J)))
-        return lbs_err("lbs backward: g_A_obs needs moss_lbs_workspace_bytes(P, J) bytes of workspace");
+        return invalid_arg("lbs backward", "g_A_obs needs moss_lbs_workspace_bytes(P, J) bytes of workspace");
     const bool vec = aligned16(a->weights) && aligned16(a->lbs_offsets) && aligned16(a->g_L);
     const int nblocks = (a->P + LBS_BWD_BLOCK - 1) / LBS_BWD_BLOCK;
     hipStream_t s = (hipStream_t)stream;
@@ -451,6 +448,5 @@ extern "C" int moss_lbs_deform_backward(const moss_lbs_backward_args* a, void* s
     if (a->g_A_obs)
         hipLaunchKernelGGL(lbs_fold_kernel, dim3((a->J * 16 + LBS_FOLD_WAVES - 1) / LBS_FOLD_WAVES), dim3(64 * LBS_FOLD_WAVES), 0, s,
                            a->J, nblocks, (const float*)partials, a->g_A_obs);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : set_last_error(MOSS_ERR_HIP, hipGetErrorString(e));
+    return launch_status("moss_lbs_deform_backward");
 }

@@ -511,8 +511,6 @@ const WgItems& weight_items()
 
 size_t ws_rows_bytes(int P) { return align_up((size_t)P * WS_ROW * sizeof(float)); }
 
-int net_err(const char* msg) { return set_last_error(MOSS_ERR_INVALID_ARG, msg); }
-
 }  // namespace
 
 }  // namespace moss
@@ -529,30 +527,29 @@ extern "C" size_t moss_lbs_weight_net_saved_bytes(int P) { return P <= 0 ? 0 : (
 // CrossAttention_lbs.forward, nets/mlp_delta_weight_lbs.py:31-54
 extern "C" int moss_lbs_weight_net_forward(const moss_lbs_weight_net_args* a, void* stream)
 {
-    if (!a) return net_err("moss_lbs_weight_net_forward: null argument block");
-    if (a->P < 0) return net_err("moss_lbs_weight_net_forward: P must be >= 0");
+    if (!a) return invalid_arg("moss_lbs_weight_net_forward", "null argument block");
+    if (a->P < 0) return invalid_arg("moss_lbs_weight_net_forward", "P must be >= 0");
     if (a->P == 0) return 0;
-    if (!a->x || !a->Rs || !a->out) return net_err("moss_lbs_weight_net_forward: null x, Rs or out");
+    if (!a->x || !a->Rs || !a->out) return invalid_arg("moss_lbs_weight_net_forward", "null x, Rs or out");
     for (int i = 0; i < NPAR; i++)
-        if (!a->params[i]) return net_err("moss_lbs_weight_net_forward: null parameter tensor (all 16 are read)");
+        if (!a->params[i]) return invalid_arg("moss_lbs_weight_net_forward", "null parameter tensor (all 16 are read)");
     static_assert(MAX_ITEMS >= 37, "item table");
     hipLaunchKernelGGL(lbs_weight_net_forward_kernel, dim3((a->P + T - 1) / T), dim3(WG), 0, (hipStream_t)stream, *a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : set_last_error(MOSS_ERR_HIP, hipGetErrorString(e));
+    return launch_status("moss_lbs_weight_net_forward");
 }
 
 // the adjoint of CrossAttention_lbs.forward, nets/mlp_delta_weight_lbs.py:31-54
 extern "C" int moss_lbs_weight_net_backward(const moss_lbs_weight_net_backward_args* a, void* stream)
 {
-    if (!a) return net_err("moss_lbs_weight_net_backward: null argument block");
-    if (a->P < 0) return net_err("moss_lbs_weight_net_backward: P must be >= 0");
+    if (!a) return invalid_arg("moss_lbs_weight_net_backward", "null argument block");
+    if (a->P < 0) return invalid_arg("moss_lbs_weight_net_backward", "P must be >= 0");
     if (a->P == 0) return 0;
-    if (!a->Rs || !a->saved || !a->g_out) return net_err("moss_lbs_weight_net_backward: null Rs, saved (the forward's) or g_out");
-    if (!a->g_x || !a->g_Rs) return net_err("moss_lbs_weight_net_backward: null g_x or g_Rs (both are written)");
+    if (!a->Rs || !a->saved || !a->g_out) return invalid_arg("moss_lbs_weight_net_backward", "null Rs, saved (the forward's) or g_out");
+    if (!a->g_x || !a->g_Rs) return invalid_arg("moss_lbs_weight_net_backward", "null g_x or g_Rs (both are written)");
     for (int i = 0; i < NPAR; i++)
-        if (!a->params[i] || !a->grads[i]) return net_err("moss_lbs_weight_net_backward: null parameter or gradient tensor (all 16 are written)");
+        if (!a->params[i] || !a->grads[i]) return invalid_arg("moss_lbs_weight_net_backward", "null parameter or gradient tensor (all 16 are written)");
     if (!a->workspace || a->workspace_bytes < moss_lbs_weight_net_workspace_bytes(a->P))
-        return net_err("moss_lbs_weight_net_backward: the workspace is null or smaller than moss_lbs_weight_net_workspace_bytes(P)");
+        return invalid_arg("moss_lbs_weight_net_backward", "the workspace is null or smaller than moss_lbs_weight_net_workspace_bytes(P)");
     const int P = a->P;
     hipStream_t s = (hipStream_t)stream;
     float* ws = reinterpret_cast<float*>(a->workspace);
@@ -566,6 +563,5 @@ extern "C" int moss_lbs_weight_net_backward(const moss_lbs_weight_net_backward_a
                        P, chunk, a->saved, (const float*)ws, a->g_out, partial, items);
     hipLaunchKernelGGL(lbs_weight_net_backward_fold_kernel, dim3((G_NET + WG - 1) / WG + 1), dim3(WG), 0, s, (const float*)partial,
                        a->Rs, a->params[P_WK], a->params[P_WV], gp, a->g_Rs);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : set_last_error(MOSS_ERR_HIP, hipGetErrorString(e));
+    return launch_status("moss_lbs_weight_net_backward");
 }

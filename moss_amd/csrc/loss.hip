@@ -389,16 +389,64 @@ extern "C" size_t moss_loss_workspace_bytes(int C, int H, int W)
     return align_up(3 * (size_t)C * H * W * 4) + align_up(gx * gy * C * 2 * 4) + align_up(gx * gy * 4);
 }
 
-extern "C" int moss_photometric_loss_weighted(int C, int H, int W, const float* image, const float* gt, const float* alpha, const float* mask,
-                                              float lambda_l1, float lambda_dssim, float lambda_mask, float* loss_out, float* dL_dimage,
-                                              float* dL_dalpha, char* workspace, size_t workspace_bytes, void* stream);
+namespace {
+
+// The arguments of the three entry points (bound, rect: the ROI form's, NULL on the full frame).
+struct LossCall {
+    int C, H, W;
+    const float *image, *gt, *alpha, *mask;
+    const unsigned char* bound; const int* rect;
+    float lambda_l1, lambda_dssim, lambda_mask;
+    float *loss_out, *dL_dimage, *dL_dalpha;
+};
+
+template <bool SKIP_EMPTY, bool ROI>
+void launch_passes(const LossCall& a, const Win& win, float* dmap, float* partials, float* mask_partials, unsigned long long* stamps, dim3 grid, hipStream_t s)
+{
+    hipLaunchKernelGGL((ssim_pass1_kernel<SKIP_EMPTY, ROI>), grid, dim3(256), 0, s, a.C, a.H, a.W, a.image, a.gt, win, dmap, partials, a.alpha, a.mask,
+                       a.lambda_mask, a.dL_dalpha, mask_partials, stamps, a.bound, a.rect);
+    hipLaunchKernelGGL((ssim_pass2_kernel<SKIP_EMPTY, ROI>), grid, dim3(256), 0, s, a.C, a.H, a.W, a.image, a.gt, a.alpha, a.mask, win, dmap, partials,
+                       (int)(grid.x * grid.y * grid.z), a.lambda_dssim, a.lambda_mask, a.dL_dimage, a.dL_dalpha, mask_partials, a.loss_out, a.lambda_l1,
+                       stamps ? stamps + 8 * 4096 : nullptr, a.bound, a.rect);
+}
+
+// The host side of all three entry points (`who`: the one called, for the error text; `roi`: moss_photometric_loss_roi).
+int photometric_loss(const char* who, bool roi, const LossCall& a, char* workspace, size_t workspace_bytes, void* stream)
+{
+    if (a.C <= 0 || a.H <= 0 || a.W <= 0) return invalid_arg(who, "C, H and W must be positive");
+    if (!a.image || !a.gt || !a.loss_out || !a.dL_dimage || !workspace) return invalid_arg(who, "a required pointer is NULL (image, gt, loss_out, dL_dimage, workspace)");
+    if (roi && !a.rect) return invalid_arg(who, "rect is NULL (five ints in device memory)");
+    if ((a.alpha == nullptr) != (a.mask == nullptr)) return invalid_arg(who, "alpha and mask come together or not at all");
+    if (a.alpha && !a.dL_dalpha) return invalid_arg(who, "alpha needs dL_dalpha");
+    if (workspace_bytes < moss_loss_workspace_bytes(a.C, a.H, a.W)) return invalid_arg(who, "workspace too small (moss_loss_workspace_bytes)");
+    hipStream_t s = (hipStream_t)stream;
+    const int gx = (a.W + LT - 1) / LT, gy = (a.H + LT - 1) / LT;
+    char* p = workspace;
+    float* dmap = carve<float>(p, 3 * (size_t)a.C * a.H * a.W);
+    float* partials = carve<float>(p, (size_t)gx * gy * a.C * 2);
+    float* mask_partials = carve<float>(p, (size_t)gx * gy);
+    static const Win win = make_window();
+    // (the stamps: the full-frame path only; product build: constant NULL)
+    unsigned long long* const stamps = (!roi && g_stamps && knob("MOSS_LOSS_STAMPS", 0)) ? g_stamps : nullptr;
+    const dim3 grid(gx, gy, a.C);
+    // more workgroups than are resident at once (three per CU: 42 KB of LDS each): the instantiations that let empty tiles leave early.
+    // Only where the grid takes more than one residency round -- at 512 x 512 every workgroup is resident and the block-wide OR costs
+    // more than it saves: 19.2 -> 18.x us, scripts/loss_times_roi.py
+    const bool skip_empty = (size_t)gx * gy * a.C > (size_t)3 * device_cus();
+    auto* const launch = !roi ? (skip_empty ? launch_passes<true, false> : launch_passes<false, false>)
+                              : (skip_empty ? launch_passes<true, true> : launch_passes<false, true>);
+    launch(a, win, dmap, partials, mask_partials, stamps, grid, s);
+    return launch_status(who);
+}
+
+}  // namespace
 
 extern "C" int moss_photometric_loss(int C, int H, int W, const float* image, const float* gt, const float* alpha, const float* mask,
                                      float lambda_dssim, float lambda_mask, float* loss_out, float* dL_dimage, float* dL_dalpha,
                                      char* workspace, size_t workspace_bytes, void* stream)
 {
-    return moss_photometric_loss_weighted(C, H, W, image, gt, alpha, mask, 1.0f, lambda_dssim, lambda_mask, loss_out, dL_dimage, dL_dalpha,
-                                          workspace, workspace_bytes, stream);
+    return photometric_loss("moss_photometric_loss", false, {C, H, W, image, gt, alpha, mask, nullptr, nullptr, 1.0f, lambda_dssim, lambda_mask,
+                                                             loss_out, dL_dimage, dL_dalpha}, workspace, workspace_bytes, stream);
 }
 
 // The same two kernels with a weight on the L1 term as well: total = lambda_l1 L1 + lambda_mask maskL2 + lambda_dssim (1 - SSIM).
@@ -408,33 +456,8 @@ extern "C" int moss_photometric_loss_weighted(int C, int H, int W, const float* 
                                               float lambda_l1, float lambda_dssim, float lambda_mask, float* loss_out, float* dL_dimage,
                                               float* dL_dalpha, char* workspace, size_t workspace_bytes, void* stream)
 {
-    if (C <= 0 || H <= 0 || W <= 0 || !image || !gt || !loss_out || !dL_dimage || !workspace) return MOSS_ERR_INVALID_ARG;
-    if ((alpha == nullptr) != (mask == nullptr) || (alpha && !dL_dalpha)) return MOSS_ERR_INVALID_ARG;
-    if (workspace_bytes < moss_loss_workspace_bytes(C, H, W)) return MOSS_ERR_INVALID_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    const int gx = (W + LT - 1) / LT, gy = (H + LT - 1) / LT;
-    char* p = workspace;
-    float* dmap = carve<float>(p, 3 * (size_t)C * H * W);
-    float* partials = carve<float>(p, (size_t)gx * gy * C * 2);
-    float* mask_partials = carve<float>(p, (size_t)gx * gy);
-    static const Win win = make_window();
-    unsigned long long* const loss_stamps = (g_stamps && knob("MOSS_LOSS_STAMPS", 0)) ? g_stamps : nullptr;      // (product build: constant NULL)
-    const dim3 grid(gx, gy, C);
-    // more workgroups than are resident at once (three per CU: 42 KB of LDS each): the instantiations that let empty tiles leave early
-    if ((size_t)gx * gy * C > (size_t)3 * loss_device_cus()) {
-        hipLaunchKernelGGL((ssim_pass1_kernel<true, false>), grid, dim3(256), 0, s, C, H, W, image, gt, win, dmap, partials, alpha, mask, lambda_mask, dL_dalpha, mask_partials, loss_stamps,
-                           (const unsigned char*)nullptr, (const int*)nullptr);
-        hipLaunchKernelGGL((ssim_pass2_kernel<true, false>), grid, dim3(256), 0, s, C, H, W, image, gt, alpha, mask, win, dmap, partials, gx * gy * C,
-                           lambda_dssim, lambda_mask, dL_dimage, dL_dalpha, mask_partials, loss_out, lambda_l1, loss_stamps ? loss_stamps + 8 * 4096 : nullptr,
-                           (const unsigned char*)nullptr, (const int*)nullptr);
-    } else {
-        hipLaunchKernelGGL((ssim_pass1_kernel<false, false>), grid, dim3(256), 0, s, C, H, W, image, gt, win, dmap, partials, alpha, mask, lambda_mask, dL_dalpha, mask_partials, loss_stamps,
-                           (const unsigned char*)nullptr, (const int*)nullptr);
-        hipLaunchKernelGGL((ssim_pass2_kernel<false, false>), grid, dim3(256), 0, s, C, H, W, image, gt, alpha, mask, win, dmap, partials, gx * gy * C,
-                           lambda_dssim, lambda_mask, dL_dimage, dL_dalpha, mask_partials, loss_out, lambda_l1, loss_stamps ? loss_stamps + 8 * 4096 : nullptr,
-                           (const unsigned char*)nullptr, (const int*)nullptr);
-    }
-    return hipGetLastError() == hipSuccess ? 0 : MOSS_ERR_HIP;
+    return photometric_loss("moss_photometric_loss_weighted", false, {C, H, W, image, gt, alpha, mask, nullptr, nullptr, lambda_l1, lambda_dssim,
+                                                                      lambda_mask, loss_out, dL_dimage, dL_dalpha}, workspace, workspace_bytes, stream);
 }
 
 // MOSS's own loss expression (train_ZJU.py:108-119,131): Ll1 = l1_loss(image[bound], gt[bound]), mask_loss = l2_loss(alpha[bound], mask[bound]),
@@ -446,29 +469,6 @@ extern "C" int moss_photometric_loss_roi(int C, int H, int W, const float* image
                                          const unsigned char* bound, const int* rect, float lambda_l1, float lambda_dssim, float lambda_mask,
                                          float* loss_out, float* dL_dimage, float* dL_dalpha, char* workspace, size_t workspace_bytes, void* stream)
 {
-    if (C <= 0 || H <= 0 || W <= 0 || !image || !gt || !loss_out || !dL_dimage || !workspace || !rect) return MOSS_ERR_INVALID_ARG;
-    if ((alpha == nullptr) != (mask == nullptr) || (alpha && !dL_dalpha)) return MOSS_ERR_INVALID_ARG;
-    if (workspace_bytes < moss_loss_workspace_bytes(C, H, W)) return MOSS_ERR_INVALID_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    const int gx = (W + LT - 1) / LT, gy = (H + LT - 1) / LT;
-    char* p = workspace;
-    float* dmap = carve<float>(p, 3 * (size_t)C * H * W);
-    float* partials = carve<float>(p, (size_t)gx * gy * C * 2);
-    float* mask_partials = carve<float>(p, (size_t)gx * gy);
-    static const Win win = make_window();
-    const dim3 grid(gx, gy, C);
-    // (as for the full frame: the instantiations that let empty tiles leave early only where the grid takes more than one residency round --
-    // at 512 x 512 every workgroup is resident and the block-wide OR costs more than it saves: 19.2 -> 18.x us, scripts/loss_times_roi.py)
-    if ((size_t)gx * gy * C > (size_t)3 * loss_device_cus()) {
-        hipLaunchKernelGGL((ssim_pass1_kernel<true, true>), grid, dim3(256), 0, s, C, H, W, image, gt, win, dmap, partials, alpha, mask, lambda_mask, dL_dalpha,
-                           mask_partials, (unsigned long long*)nullptr, bound, rect);
-        hipLaunchKernelGGL((ssim_pass2_kernel<true, true>), grid, dim3(256), 0, s, C, H, W, image, gt, alpha, mask, win, dmap, partials, gx * gy * C,
-                           lambda_dssim, lambda_mask, dL_dimage, dL_dalpha, mask_partials, loss_out, lambda_l1, (unsigned long long*)nullptr, bound, rect);
-    } else {
-        hipLaunchKernelGGL((ssim_pass1_kernel<false, true>), grid, dim3(256), 0, s, C, H, W, image, gt, win, dmap, partials, alpha, mask, lambda_mask, dL_dalpha,
-                           mask_partials, (unsigned long long*)nullptr, bound, rect);
-        hipLaunchKernelGGL((ssim_pass2_kernel<false, true>), grid, dim3(256), 0, s, C, H, W, image, gt, alpha, mask, win, dmap, partials, gx * gy * C,
-                           lambda_dssim, lambda_mask, dL_dimage, dL_dalpha, mask_partials, loss_out, lambda_l1, (unsigned long long*)nullptr, bound, rect);
-    }
-    return hipGetLastError() == hipSuccess ? 0 : MOSS_ERR_HIP;
+    return photometric_loss("moss_photometric_loss_roi", true, {C, H, W, image, gt, alpha, mask, bound, rect, lambda_l1, lambda_dssim, lambda_mask,
+                                                                loss_out, dL_dimage, dL_dalpha}, workspace, workspace_bytes, stream);
 }

@@ -277,22 +277,22 @@ matrix_fisher_nll_kernel(int n, const float* __restrict__ Fm, const float* __res
     }
 }
 
-int pose_err(const char* msg) { return set_last_error(MOSS_ERR_INVALID_ARG, msg); }
-
 // the checks both directions share; `who` prefixes the message
 template <typename A>
-int pose_check(const A* a, const char* null_msg, const char* parents_msg, const char* width_msg)
+int pose_check(const A* a, const char* who)
 {
-    if (!a || !a->poses || !a->target_R) return pose_err(null_msg);
+    const char* const null_msg = "null argument block, poses, target_R or parameter";
+    const char* const parents_msg = "parents[0] must be -1 and 0 <= parents[i] < i";
+    if (!a || !a->poses || !a->target_R) return invalid_arg(who, null_msg);
     for (int i = 0; i < NP; i++)
-        if (!a->params[i]) return pose_err(null_msg);
-    if (a->parents[0] != -1) return pose_err(parents_msg);
+        if (!a->params[i]) return invalid_arg(who, null_msg);
+    if (a->parents[0] != -1) return invalid_arg(who, parents_msg);
     for (int i = 1; i <= NJ; i++)
-        if (a->parents[i] < 0 || a->parents[i] >= i) return pose_err(parents_msg);
+        if (a->parents[i] < 0 || a->parents[i] >= i) return invalid_arg(who, parents_msg);
     for (int j = 0; j < NJ; j++) {
         int nodes = 0;
         for (int node = j + 1; node > 0; node = a->parents[node]) nodes++;
-        if (a->fc_in[j] != 3 * nodes) return pose_err(width_msg);
+        if (a->fc_in[j] != 3 * nodes) return invalid_arg(who, "fc_in[j] must be 3 * (1 + the number of non-root ancestors of joint j)");
     }
     return 0;
 }
@@ -305,38 +305,29 @@ using namespace moss;
 
 extern "C" int moss_pose_head_forward(const moss_pose_head_args* a, void* stream)
 {
-    if (int rc = pose_check(a, "moss_pose_head_forward: null argument block, poses, target_R or parameter",
-                            "moss_pose_head_forward: parents[0] must be -1 and 0 <= parents[i] < i",
-                            "moss_pose_head_forward: fc_in[j] must be 3 * (1 + the number of non-root ancestors of joint j)"))
-        return rc;
-    if (!a->Rs || !a->S || !a->nll || !a->saved) return pose_err("moss_pose_head_forward: null output (Rs, S, nll, saved)");
+    if (int rc = pose_check(a, "moss_pose_head_forward")) return rc;
+    if (!a->Rs || !a->S || !a->nll || !a->saved) return invalid_arg("moss_pose_head_forward", "null output (Rs, S, nll, saved)");
     hipLaunchKernelGGL(pose_head_forward_kernel, dim3(1), dim3(WG), 0, (hipStream_t)stream, *a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : set_last_error(MOSS_ERR_HIP, hipGetErrorString(e));
+    return launch_status("moss_pose_head_forward");
 }
 
 extern "C" int moss_pose_head_backward(const moss_pose_head_backward_args* a, void* stream)
 {
-    if (int rc = pose_check(a, "moss_pose_head_backward: null argument block, poses, target_R or parameter",
-                            "moss_pose_head_backward: parents[0] must be -1 and 0 <= parents[i] < i",
-                            "moss_pose_head_backward: fc_in[j] must be 3 * (1 + the number of non-root ancestors of joint j)"))
-        return rc;
-    if (!a->S || !a->saved) return pose_err("moss_pose_head_backward: null S or saved (the forward's)");
+    if (int rc = pose_check(a, "moss_pose_head_backward")) return rc;
+    if (!a->S || !a->saved) return invalid_arg("moss_pose_head_backward", "null S or saved (the forward's)");
     for (int i = 0; i < NP; i++)
-        if (!a->grads[i]) return pose_err("moss_pose_head_backward: null gradient tensor (all 52 are written)");
+        if (!a->grads[i]) return invalid_arg("moss_pose_head_backward", "null gradient tensor (all 52 are written)");
     hipLaunchKernelGGL(pose_head_backward_kernel, dim3(1), dim3(WG), 0, (hipStream_t)stream, *a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : set_last_error(MOSS_ERR_HIP, hipGetErrorString(e));
+    return launch_status("moss_pose_head_backward");
 }
 
 extern "C" int moss_matrix_fisher_nll(int n, const float* F, const float* target_R, float overreg, float* nll_out, float* dF_out,
                                       void* stream)
 {
-    if (n < 0) return pose_err("moss_matrix_fisher_nll: n must be >= 0");
+    if (n < 0) return invalid_arg("moss_matrix_fisher_nll", "n must be >= 0");
     if (n == 0) return 0;
-    if (!F || !target_R || !nll_out) return pose_err("moss_matrix_fisher_nll: null F, target_R or nll_out");
+    if (!F || !target_R || !nll_out) return invalid_arg("moss_matrix_fisher_nll", "null F, target_R or nll_out");
     hipLaunchKernelGGL(matrix_fisher_nll_kernel, dim3((n + NLL_PER_WG - 1) / NLL_PER_WG), dim3(WG), 0, (hipStream_t)stream, n, F,
                        target_R, overreg, nll_out, dF_out);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : set_last_error(MOSS_ERR_HIP, hipGetErrorString(e));
+    return launch_status("moss_matrix_fisher_nll");
 }

@@ -1537,17 +1537,6 @@ export_geometry_kernel(int P, GeomView g, float* depths, float* means2D, float* 
 
 }  // anonymous namespace
 
-static int device_cus()
-{
-    static const int n = [] {
-        int dev = 0; hipDeviceProp_t prop;
-        return (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-                   ? prop.multiProcessorCount : 256;
-    }();
-    return n;
-}
-
-
 void launch_preprocess_forward(const FrameParams& fp, const float* means3D, const float* shs, const float* colors_precomp,
                                const float* opacities, const float* scales, const float* rotations, const float* cov3D_precomp,
                                const float* transforms, const float* translation, GeomView g, ImageView im, int* radii_out, hipStream_t s,

@@ -10,6 +10,7 @@
 #include <cstring>
 #include <dlfcn.h>
 #include <mutex>
+#include <string>
 #include <vector>
 
 using namespace moss;
@@ -137,6 +138,27 @@ int moss::set_last_error(int code, const char* msg)
 {
     snprintf(g_err, sizeof(g_err), "%s", msg);
     return code;
+}
+
+int moss::invalid_arg(const char* entry_point, const char* condition)
+{
+    return set_last_error(MOSS_ERR_INVALID_ARG, (std::string(entry_point) + ": " + condition).c_str());
+}
+
+int moss::launch_status(const char* entry_point)
+{
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : set_last_error(MOSS_ERR_HIP, (std::string(entry_point) + ": " + hipGetErrorString(e)).c_str());
+}
+
+int moss::device_cus()
+{
+    static const int n = [] {
+        int dev = 0; hipDeviceProp_t prop;
+        return (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
+                   ? prop.multiProcessorCount : 256;
+    }();
+    return n;
 }
 
 // The forward of every form of the call (include/moss_raster.h: moss_raster_forward_args).  The argument rules of the extensions are

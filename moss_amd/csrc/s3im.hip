@@ -271,8 +271,6 @@ PhaseTaps make_phase_taps(const Win& win, int R)
     return t;
 }
 
-int s3im_err(const char* msg) { return set_last_error(MOSS_ERR_INVALID_ARG, msg); }
-
 size_t s3im_partials(int C, int H, int W, int tw) { return (size_t)((W + tw - 1) / tw) * ((H + P1_TH - 1) / P1_TH) * C; }
 
 template <int KH>
@@ -301,10 +299,10 @@ extern "C" size_t moss_s3im_workspace_bytes(int C, int H, int W)
 extern "C" int moss_s3im_loss(int C, int H, int W, const float* image, const float* gt, const int* rect, int repeat, float* loss_out,
                               float* dL_dimage, char* workspace, size_t workspace_bytes, void* stream)
 {
-    if (C <= 0 || H <= 0 || W <= 0) return s3im_err("moss_s3im_loss: C, H and W must be positive");
-    if (!image || !gt || !loss_out || !dL_dimage || !workspace) return s3im_err("moss_s3im_loss: a required pointer is NULL");
-    if (repeat < 1 || repeat > S3_MAX_R) return s3im_err("moss_s3im_loss: repeat must be 1..16");
-    if (workspace_bytes < moss_s3im_workspace_bytes(C, H, W)) return s3im_err("moss_s3im_loss: workspace too small (moss_s3im_workspace_bytes)");
+    if (C <= 0 || H <= 0 || W <= 0) return invalid_arg("moss_s3im_loss", "C, H and W must be positive");
+    if (!image || !gt || !loss_out || !dL_dimage || !workspace) return invalid_arg("moss_s3im_loss", "a required pointer is NULL");
+    if (repeat < 1 || repeat > S3_MAX_R) return invalid_arg("moss_s3im_loss", "repeat must be 1..16");
+    if (workspace_bytes < moss_s3im_workspace_bytes(C, H, W)) return invalid_arg("moss_s3im_loss", "workspace too small (moss_s3im_workspace_bytes)");
     static const Win win = make_window();
     static PhaseTaps taps_by_r[S3_MAX_R + 1];
     static bool taps_ready = [] { for (int r = 1; r <= S3_MAX_R; r++) taps_by_r[r] = make_phase_taps(win, r); return true; }();
@@ -320,6 +318,5 @@ extern "C" int moss_s3im_loss(int C, int H, int W, const float* image, const flo
     case 2: launch_s3im<2>(C, H, W, repeat, image, gt, rect, loss_out, dL_dimage, gmap, partials, win, t, s); break;
     default: launch_s3im<1>(C, H, W, repeat, image, gt, rect, loss_out, dL_dimage, gmap, partials, win, t, s); break;
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : set_last_error(MOSS_ERR_HIP, hipGetErrorString(e));
+    return launch_status("moss_s3im_loss");
 }

@@ -84,16 +84,6 @@ __device__ __forceinline__ TileId roi_tile(const Crop& cr)
     return id;
 }
 
-int loss_device_cus()
-{
-    static const int n = [] {
-        int dev = 0; hipDeviceProp_t prop;
-        return (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-                   ? prop.multiProcessorCount : 256;
-    }();
-    return n;
-}
-
 Win make_window()
 {
     // utils/loss_utils.py:47-49: gauss = Tensor([exp(-(x-5)^2 / (2*1.5^2))]) / sum, evaluated in fp32 like torch.Tensor

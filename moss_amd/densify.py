@@ -13,13 +13,9 @@ from __future__ import annotations
 
 import torch
 
-from ._lib import check, lib
+from ._lib import call
 
 __all__ = ["DensifyStats", "densify_stats_update", "neighbour_kl", "cal_kl"]
-
-
-def _stream(device):
-    return torch.cuda.current_stream(device).cuda_stream
 
 
 class DensifyStats:
@@ -42,10 +38,8 @@ class DensifyStats:
             raise RuntimeError("DensifyStats.add: expected radii (P) int32 and viewspace_grad (P, >=2) float32")
         if viewspace_grad.stride(1) != 1:
             viewspace_grad = viewspace_grad.contiguous()
-        with torch.cuda.device(radii.device):
-            check(lib().moss_densify_stats(P, radii.contiguous().data_ptr(), viewspace_grad.data_ptr(), viewspace_grad.stride(0),
-                                           self.xyz_gradient_accum.data_ptr(), self.denom.data_ptr(), self.max_radii2D.data_ptr(),
-                                           _stream(radii.device)), "densify_stats")
+        call("moss_densify_stats", radii.device, P, radii.contiguous().data_ptr(), viewspace_grad.data_ptr(), viewspace_grad.stride(0),
+             self.xyz_gradient_accum.data_ptr(), self.denom.data_ptr(), self.max_radii2D.data_ptr())
 
     def sync(self, group=None) -> None:
         """Combine the ranks' locally accumulated statistics (sum, sum, max).  No-op without an initialised process group."""
@@ -109,9 +103,7 @@ def neighbour_kl(xyz: torch.Tensor, rotation: torch.Tensor, scaling: torch.Tenso
     P = pair_idx.shape[0]
     out = torch.empty((P,), dtype=torch.float32, device=xyz.device)
     x, r, s = (t.detach().float().contiguous() for t in (xyz, rotation, scaling))
-    with torch.cuda.device(xyz.device):
-        check(lib().moss_neighbour_kl(P, N, x.data_ptr(), r.data_ptr(), s.data_ptr(), pair_idx.contiguous().data_ptr(),
-                                      out.data_ptr(), _stream(xyz.device)), "neighbour_kl")
+    call("moss_neighbour_kl", xyz.device, P, N, x.data_ptr(), r.data_ptr(), s.data_ptr(), pair_idx.contiguous().data_ptr(), out.data_ptr())
     return out
 
 

@@ -17,7 +17,7 @@ import os
 import torch
 import torch.nn as nn
 
-from .._lib import check, lib
+from .._lib import call, check, lib, stream
 
 __all__ = ["KNN", "KnnGrid", "knn"]
 
@@ -47,9 +47,7 @@ class KnnGrid:
         ref_c = ref.detach().float().contiguous()
         self._bytes = int(lib().moss_knn_grid_workspace_bytes(self.Nr))
         self._ws = torch.empty(self._bytes, dtype=torch.uint8, device=ref.device)
-        with torch.cuda.device(ref.device):
-            check(lib().moss_knn_grid_build(self.Nr, ref_c.data_ptr(), self._ws.data_ptr(), self._bytes,
-                                            torch.cuda.current_stream(ref.device).cuda_stream), "knn_grid_build")
+        call("moss_knn_grid_build", ref.device, self.Nr, ref_c.data_ptr(), self._ws.data_ptr(), self._bytes)
 
     def query(self, points: torch.Tensor, k: int, dist: torch.Tensor = None, idx: torch.Tensor = None):
         if points.dim() != 2 or points.shape[1] != 3 or points.device != self.device:
@@ -64,9 +62,7 @@ class KnnGrid:
             dist = torch.empty((Nq, k), dtype=torch.float32, device=self.device)
         if idx is None:
             idx = torch.empty((Nq, k), dtype=torch.int64, device=self.device)
-        with torch.cuda.device(self.device):
-            check(lib().moss_knn_grid_query(self.Nr, Nq, k, self._ws.data_ptr(), self._bytes, pts.data_ptr(), dist.data_ptr(),
-                                            idx.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream), "knn_grid_query")
+        call("moss_knn_grid_query", self.device, self.Nr, Nq, k, self._ws.data_ptr(), self._bytes, pts.data_ptr(), dist.data_ptr(), idx.data_ptr())
         return dist, idx
 
 
@@ -85,13 +81,13 @@ def knn(ref: torch.Tensor, query: torch.Tensor, k: int, impl: str = None):
     dist = torch.empty((B, Nq, k), dtype=torch.float32, device=ref.device)
     idx = torch.empty((B, Nq, k), dtype=torch.int64, device=ref.device)
     with torch.cuda.device(ref.device):
-        stream = torch.cuda.current_stream(ref.device).cuda_stream
+        s = stream(ref.device)
         for b in range(B):
             if _impl(Nr, impl) == "grid":
                 KnnGrid(ref_c[b]).query(query_c[b], k, dist[b], idx[b])
                 continue
             check(lib().moss_knn_query(Nr, Nq, k, ref_c[b].data_ptr(), query_c[b].data_ptr(), dist[b].data_ptr(), idx[b].data_ptr(),
-                                       stream), "knn_query")
+                                       s), "knn_query")
     return dist, idx
 
 

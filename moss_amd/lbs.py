@@ -24,6 +24,8 @@ import torch
 import torch.nn.functional as F
 from torch.utils.weak import WeakIdKeyDictionary
 
+from ._lib import LbsBackwardArgs, LbsForwardArgs, call, lib, ptr
+
 __all__ = ["lbs_deform", "smpl_joint_transforms", "vertex_offsets", "coarse_deform_c2source", "deform_torch", "synthetic_body_model",
            "batch_rodrigues", "MAX_JOINTS", "SMPL_PARENTS"]
 
@@ -46,20 +48,15 @@ def _need(t, name, shape, dtype, device):
         raise ValueError(f"lbs_deform: {name} must be contiguous")
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
 def _fill_inputs(a, ids, W, L, A_big, A_obs, d, R, Th, x):
     a.P, a.J, a.V = int(ids.shape[0]), int(W.shape[1]), int(W.shape[0])
-    a.vert_ids, a.weights, a.lbs_offsets = ids.data_ptr(), W.data_ptr(), _ptr(L)
-    a.A_big, a.A_obs, a.d, a.R, a.Th, a.x = A_big.data_ptr(), A_obs.data_ptr(), d.data_ptr(), R.data_ptr(), Th.data_ptr(), _ptr(x)
+    a.vert_ids, a.weights, a.lbs_offsets = ids.data_ptr(), W.data_ptr(), ptr(L)
+    a.A_big, a.A_obs, a.d, a.R, a.Th, a.x = A_big.data_ptr(), A_obs.data_ptr(), d.data_ptr(), R.data_ptr(), Th.data_ptr(), ptr(x)
 
 
 class _LbsDeform(torch.autograd.Function):
     @staticmethod
     def forward(ctx, ids, W, L, A_big, A_obs, d, R, Th, x, want_weights):
-        from ._lib import LbsForwardArgs, check, lib
         P, J = int(ids.shape[0]), int(W.shape[1])
         dev = W.device
         T = torch.empty((P, 3, 3), dtype=torch.float32, device=dev)
@@ -69,9 +66,8 @@ class _LbsDeform(torch.autograd.Function):
         if P > 0:
             a = LbsForwardArgs()
             _fill_inputs(a, ids, W, L, A_big, A_obs, d, R, Th, x)
-            a.T, a.t, a.p, a.w = T.data_ptr(), t.data_ptr(), _ptr(p), _ptr(w)
-            with torch.cuda.device(dev):
-                check(lib().moss_lbs_deform_forward(ctypes.byref(a), torch.cuda.current_stream(dev).cuda_stream), "lbs_deform forward")
+            a.T, a.t, a.p, a.w = T.data_ptr(), t.data_ptr(), ptr(p), ptr(w)
+            call("moss_lbs_deform_forward", dev, ctypes.byref(a))
         if w is not None:
             ctx.mark_non_differentiable(w)
         ctx.save_for_backward(ids, W, L, A_big, A_obs, d, R, Th, x)
@@ -80,7 +76,6 @@ class _LbsDeform(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gT, gt, gp, _gw):
-        from ._lib import LbsBackwardArgs, check, lib
         ids, W, L, A_big, A_obs, d, R, Th, x = ctx.saved_tensors
         L = L if ctx.has_L else None
         x = x if ctx.has_x else None
@@ -98,15 +93,14 @@ class _LbsDeform(torch.autograd.Function):
             gT = None if gT is None else gT.float().contiguous()
             gt = None if gt is None else gt.float().contiguous()
             gp = None if (gp is None or x is None) else gp.float().contiguous()
-            a.g_T, a.g_t, a.g_p = _ptr(gT), _ptr(gt), _ptr(gp)
-            a.g_L, a.g_A_obs, a.g_d, a.g_x = _ptr(gL), _ptr(gA), _ptr(gd), _ptr(gx)
+            a.g_T, a.g_t, a.g_p = ptr(gT), ptr(gt), ptr(gp)
+            a.g_L, a.g_A_obs, a.g_d, a.g_x = ptr(gL), ptr(gA), ptr(gd), ptr(gx)
             ws = None
             if gA is not None:
                 nbytes = int(lib().moss_lbs_workspace_bytes(P, J))
                 ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
                 a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
-            with torch.cuda.device(dev):
-                check(lib().moss_lbs_deform_backward(ctypes.byref(a), torch.cuda.current_stream(dev).cuda_stream), "lbs_deform backward")
+            call("moss_lbs_deform_backward", dev, ctypes.byref(a))
         return None, None, gL, None, gA, gd, None, None, gx, None
 
 

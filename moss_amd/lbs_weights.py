@@ -110,14 +110,10 @@ def net_parameters(net):
     return [named[k] for k in PARAM_NAMES]
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 class _LbsWeightNet(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, Rs, *params):
-        from ._lib import LbsWeightNetArgs, check, lib
+        from ._lib import LbsWeightNetArgs, call, lib
         dev, P = x.device, int(x.shape[0])
         out = torch.empty((1, P, FEATURE_DIM), dtype=torch.float32, device=dev)
         keep = any(ctx.needs_input_grad)
@@ -127,14 +123,13 @@ class _LbsWeightNet(torch.autograd.Function):
             a.P, a.x, a.Rs, a.out, a.saved = P, x.data_ptr(), Rs.data_ptr(), out.data_ptr(), (saved.data_ptr() if keep else None)
             for i, p in enumerate(params):
                 a.params[i] = p.data_ptr()
-            with torch.cuda.device(dev):
-                check(lib().moss_lbs_weight_net_forward(ctypes.byref(a), _stream(dev)), "lbs_weight_net forward")
+            call("moss_lbs_weight_net_forward", dev, ctypes.byref(a))
         ctx.save_for_backward(x, Rs, saved, *params)
         return out
 
     @staticmethod
     def backward(ctx, g_out):
-        from ._lib import LbsWeightNetBackwardArgs, check, lib
+        from ._lib import LbsWeightNetBackwardArgs, call, lib
         x, Rs, saved, *params = ctx.saved_tensors
         dev, P = x.device, int(x.shape[0])
         sizes = [3 * P, 23 * 9] + [p.numel() for p in params]
@@ -152,8 +147,7 @@ class _LbsWeightNet(torch.autograd.Function):
             a.g_x, a.g_Rs, a.workspace, a.workspace_bytes = g_x.data_ptr(), g_Rs.data_ptr(), workspace.data_ptr(), nbytes
             for i, (p, g) in enumerate(zip(params, grads)):
                 a.params[i], a.grads[i] = p.data_ptr(), g.data_ptr()
-            with torch.cuda.device(dev):
-                check(lib().moss_lbs_weight_net_backward(ctypes.byref(a), _stream(dev)), "lbs_weight_net backward")
+            call("moss_lbs_weight_net_backward", dev, ctypes.byref(a))
         return (g_x.view(P, 3), g_Rs.view(23, 3, 3), *[g.view(p.shape) for g, p in zip(grads, params)])
 
 

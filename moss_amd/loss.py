@@ -86,32 +86,66 @@ def training_loss(image, alpha, gt_image, gt_mask, lambda_dssim=0.2, lambda_mask
     return ll1 + lambda_mask * mask_loss + lambda_dssim * (1.0 - s)
 
 
-class _FusedSSIM(torch.autograd.Function):
-    """mean SSIM(img1, img2) and its gradient w.r.t. img1 from the two loss kernels (C ABI moss_photometric_loss_weighted with
-    lambda_l1 = 0, lambda_dssim = 1, no mask term: total = 1 - SSIM, so d SSIM / d img1 = -dL_dimage)."""
+_UNIT = {}
+
+
+def backward_from_loss(loss):
+    """``loss.backward()`` without the two minimal kernels autograd would launch for a root loss (ones_like fill + scaling of the
+    loss gradients by 1.0): the unit gradient is a cached constant that the fused loss recognises."""
+    one = _UNIT.get(loss.device)
+    if one is None:
+        one = _UNIT[loss.device] = torch.ones((), dtype=loss.dtype, device=loss.device)
+    torch.autograd.backward(loss, grad_tensors=one)
+
+
+def _is_unit(grad_out):
+    """The loss is normally the root of the graph: its incoming gradient is then the constant 1 handed to backward() by
+    :func:`backward_from_loss`, recognised by identity -- multiplying by exactly 1.0 would be a no-op kernel."""
+    unit = _UNIT.get(grad_out.device)
+    return unit is not None and grad_out.data_ptr() == unit.data_ptr()
+
+
+class _FusedPhotometricLoss(torch.autograd.Function):
+    """The two loss kernels (C ABI moss_photometric_loss_weighted; with a ``region`` moss_photometric_loss_roi, MOSS's own
+    expression): the four terms [loss, L1, SSIM, mask L2] and the gradient of the loss w.r.t. image and alpha come out of the forward;
+    backward only scales the gradient by the incoming one.  Returns term ``term``: 0, the loss, or 2, the mean SSIM (under
+    ``lambdas`` = (0, 1, 0) and no alpha the loss is 1 - SSIM, so d SSIM / d image = -dL_dimage)."""
 
     @staticmethod
-    def forward(ctx, img1, img2):
-        from ._lib import check, lib
-        L = lib()
-        C, H, W = img1.shape
-        a, b = img1.contiguous(), img2.contiguous()
-        out = torch.empty(4, dtype=torch.float32, device=a.device)
-        d_img = torch.empty((C, H, W), dtype=torch.float32, device=a.device)
-        nbytes = int(L.moss_loss_workspace_bytes(C, H, W))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=a.device)
-        with torch.cuda.device(a.device):
-            rc = L.moss_photometric_loss_weighted(C, H, W, a.data_ptr(), b.data_ptr(), None, None, 0.0, 1.0, 0.0, out.data_ptr(),
-                                                  d_img.data_ptr(), None, ws.data_ptr(), nbytes,
-                                                  torch.cuda.current_stream(a.device).cuda_stream)
-        check(rc, "photometric_loss_weighted")
-        ctx.save_for_backward(d_img)
-        return out[2]
+    def forward(ctx, image, alpha, gt_image, mask, region, lambdas, terms_out, term):
+        from ._lib import call, lib, ptr
+        C, H, W = image.shape
+        dev = image.device
+        image_c, gt_c = image.contiguous(), gt_image.contiguous()
+        alpha_c, mask_c = (None, None) if alpha is None else (alpha.contiguous(), mask.contiguous())
+        if terms_out is not None:
+            if terms_out.shape != (4,) or terms_out.dtype != torch.float32 or terms_out.device != dev or not terms_out.is_contiguous():
+                raise RuntimeError("fused loss: terms_out must be 4 contiguous float32 values on the image's device")
+            out = terms_out
+        else:
+            out = torch.empty(4, dtype=torch.float32, device=dev)
+        # both gradient images in one buffer: backward scales them by the incoming gradient with ONE kernel
+        d_both = torch.empty((C if alpha is None else C + 1, H, W), dtype=torch.float32, device=dev)
+        nbytes = int(lib().moss_loss_workspace_bytes(C, H, W))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        # (the ROI form takes the region's two pointers after the mask, and is otherwise the weighted form)
+        name, where = ("moss_photometric_loss_weighted", ()) if region is None else \
+            ("moss_photometric_loss_roi", (region.bound.data_ptr(), region.rect.data_ptr()))
+        call(name, dev, C, H, W, image_c.data_ptr(), gt_c.data_ptr(), ptr(alpha_c), ptr(mask_c), *where, *lambdas, out.data_ptr(),
+             d_both.data_ptr(), None if alpha is None else d_both[C:].data_ptr(), ws.data_ptr(), nbytes)
+        ctx.save_for_backward(d_both)
+        ctx.C, ctx.alpha_shape, ctx.negate = C, None if alpha is None else alpha.shape, term == 2
+        return out[term]
 
     @staticmethod
     def backward(ctx, grad_out):
-        (d_img,) = ctx.saved_tensors
-        return -grad_out * d_img, None
+        (d_both,) = ctx.saved_tensors
+        if ctx.negate:
+            scaled = -grad_out * d_both
+        else:
+            scaled = d_both if _is_unit(grad_out) else grad_out * d_both
+        d_alpha = None if ctx.alpha_shape is None else scaled[ctx.C:].reshape(ctx.alpha_shape)
+        return scaled[:ctx.C], d_alpha, None, None, None, None, None, None
 
 
 def ssim_fused(img1, img2, window_size=11, size_average=True):
@@ -128,71 +162,16 @@ def ssim_fused(img1, img2, window_size=11, size_average=True):
         img1, img2 = img1[0], img2[0]
     if not img1.is_cuda or img1.dtype != torch.float32 or img2.dtype != torch.float32:
         raise RuntimeError("ssim_fused needs float32 GPU tensors (the product path has no CPU fallback; moss_amd.loss.ssim is the torch form)")
-    return _FusedSSIM.apply(img1, img2.detach())
-
-
-class _FusedPhotometricLoss(torch.autograd.Function):
-    """HIP implementation of :func:`training_loss` (include/moss_raster.h: moss_photometric_loss): the loss and its
-    gradient w.r.t. image and alpha come out of two fused kernels; backward only scales them by the incoming gradient."""
-
-    @staticmethod
-    def forward(ctx, image, alpha, gt_image, gt_mask, lambda_dssim, lambda_mask, terms_out=None):
-        from ._lib import check, lib
-        L = lib()
-        if not image.is_cuda:
-            raise RuntimeError("fused loss needs GPU tensors; use training_loss() for the torch reference on CPU")
-        C, H, W = image.shape
-        image_c, gt_c = image.contiguous(), gt_image.contiguous()
-        alpha_c, mask_c = alpha.contiguous(), gt_mask.contiguous()
-        if terms_out is not None:
-            if terms_out.shape != (4,) or terms_out.dtype != torch.float32 or terms_out.device != image.device or not terms_out.is_contiguous():
-                raise RuntimeError("fused loss: terms_out must be 4 contiguous float32 values on the image's device")
-            out = terms_out
-        else:
-            out = torch.empty(4, dtype=torch.float32, device=image.device)
-        # both gradient images in one buffer: backward scales them by the incoming gradient with ONE kernel
-        d_both = torch.empty((C + 1, H, W), dtype=torch.float32, device=image.device)
-        d_img, d_alpha = d_both[:C], d_both[C:]
-        nbytes = int(L.moss_loss_workspace_bytes(C, H, W))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=image.device)
-        with torch.cuda.device(image.device):
-            rc = L.moss_photometric_loss(C, H, W, image_c.data_ptr(), gt_c.data_ptr(), alpha_c.data_ptr(), mask_c.data_ptr(),
-                                         float(lambda_dssim), float(lambda_mask), out.data_ptr(), d_img.data_ptr(),
-                                         d_alpha.data_ptr(), ws.data_ptr(), nbytes,
-                                         torch.cuda.current_stream(image.device).cuda_stream)
-        check(rc, "photometric_loss")
-        ctx.save_for_backward(d_both)
-        ctx.C, ctx.alpha_shape = C, alpha.shape
-        ctx.terms = out
-        return out[0]
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        (d_both,) = ctx.saved_tensors
-        # the loss is normally the root of the graph: its incoming gradient is then the constant 1 handed to backward() by
-        # `backward_from_loss` below, recognised by identity -- multiplying by exactly 1.0 would be a no-op kernel
-        unit = _UNIT.get(d_both.device)
-        scaled = d_both if (unit is not None and grad_out.data_ptr() == unit.data_ptr()) else grad_out * d_both
-        return scaled[:ctx.C], scaled[ctx.C:].reshape(ctx.alpha_shape), None, None, None, None, None
-
-
-_UNIT = {}
-
-
-def backward_from_loss(loss):
-    """``loss.backward()`` without the two minimal kernels autograd would launch for a root loss (ones_like fill + scaling of the
-    loss gradients by 1.0): the unit gradient is a cached constant that the fused loss recognises."""
-    one = _UNIT.get(loss.device)
-    if one is None:
-        one = _UNIT[loss.device] = torch.ones((), dtype=loss.dtype, device=loss.device)
-    torch.autograd.backward(loss, grad_tensors=one)
+    return _FusedPhotometricLoss.apply(img1, None, img2.detach(), None, None, (0.0, 1.0, 0.0), None, 2)
 
 
 def training_loss_fused(image, alpha, gt_image, gt_mask, lambda_dssim=0.2, lambda_mask=0.5, terms_out=None):
     """Same value and gradients as :func:`training_loss`, computed by the fused HIP kernels.  ``terms_out`` (optional, 4 floats):
     where the kernels write [loss, L1, SSIM, mask L2] -- e.g. ``GradBucket.loss_terms``, so that the loss travels with the
     gradients in the one all-reduce without a copy; the returned loss is then ``terms_out[0]``."""
-    return _FusedPhotometricLoss.apply(image, alpha, gt_image, gt_mask, lambda_dssim, lambda_mask, terms_out)
+    if not image.is_cuda:
+        raise RuntimeError("fused loss needs GPU tensors; use training_loss() for the torch reference on CPU")
+    return _FusedPhotometricLoss.apply(image, alpha, gt_image, gt_mask, None, (1.0, float(lambda_dssim), float(lambda_mask)), terms_out, 0)
 
 
 class ViewRegion:
@@ -215,55 +194,18 @@ class ViewRegion:
         return self
 
 
-class _FusedMossLoss(torch.autograd.Function):
-    """C ABI moss_photometric_loss_roi: value and gradients of :func:`training_loss_moss` from the two loss kernels."""
-
-    @staticmethod
-    def forward(ctx, image, alpha, gt_image, bkgd_mask, region, lambda_dssim, lambda_mask, terms_out=None):
-        from ._lib import check, lib
-        L = lib()
-        if not image.is_cuda or image.dtype != torch.float32:
-            raise RuntimeError("fused loss needs float32 GPU tensors; training_loss_moss() is the torch form")
-        C, H, W = image.shape
-        if tuple(region.bound.shape) != (H, W) or region.bound.device != image.device:
-            raise RuntimeError("fused loss: the view's region does not belong to this image")
-        image_c, gt_c = image.contiguous(), gt_image.contiguous()
-        alpha_c, mask_c = alpha.contiguous(), bkgd_mask.to(torch.float32).contiguous()
-        if terms_out is not None:
-            if terms_out.shape != (4,) or terms_out.dtype != torch.float32 or terms_out.device != image.device or not terms_out.is_contiguous():
-                raise RuntimeError("fused loss: terms_out must be 4 contiguous float32 values on the image's device")
-            out = terms_out
-        else:
-            out = torch.empty(4, dtype=torch.float32, device=image.device)
-        d_both = torch.empty((C + 1, H, W), dtype=torch.float32, device=image.device)
-        d_img, d_alpha = d_both[:C], d_both[C:]
-        nbytes = int(L.moss_loss_workspace_bytes(C, H, W))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=image.device)
-        with torch.cuda.device(image.device):
-            rc = L.moss_photometric_loss_roi(C, H, W, image_c.data_ptr(), gt_c.data_ptr(), alpha_c.data_ptr(), mask_c.data_ptr(),
-                                             region.bound.data_ptr(), region.rect.data_ptr(), 1.0, float(lambda_dssim), float(lambda_mask),
-                                             out.data_ptr(), d_img.data_ptr(), d_alpha.data_ptr(), ws.data_ptr(), nbytes,
-                                             torch.cuda.current_stream(image.device).cuda_stream)
-        check(rc, "photometric_loss_roi")
-        ctx.save_for_backward(d_both)
-        ctx.C, ctx.alpha_shape = C, alpha.shape
-        return out[0]
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        (d_both,) = ctx.saved_tensors
-        unit = _UNIT.get(d_both.device)
-        scaled = d_both if (unit is not None and grad_out.data_ptr() == unit.data_ptr()) else grad_out * d_both
-        return scaled[:ctx.C], scaled[ctx.C:].reshape(ctx.alpha_shape), None, None, None, None, None, None
-
-
 def training_loss_moss_fused(image, alpha, gt_image, bkgd_mask, region, lambda_dssim=0.2, lambda_mask=0.5, terms_out=None):
     """``Ll1 + lambda_mask * mask_loss + lambda_dssim * (1 - ssim_loss)`` with the three terms EXACTLY as MOSS forms them
     (train_ZJU.py:108-119,131: bound_mask selection, boundingRect crop) -- :func:`training_loss_moss` -- from two HIP kernels.  ``region``:
     the view's :class:`ViewRegion` (made once per view: the rectangle and the pixel count are host reads).  In MOSS this replaces lines
     :111-119 (patches/train_ZJU.diff keeps them and swaps only ``ssim``; this is the one-call form).  The remaining terms of :131 (lpips,
     s3im, nll) are other subsystems' and are added to the returned loss by the caller."""
-    return _FusedMossLoss.apply(image, alpha, gt_image, bkgd_mask, region, lambda_dssim, lambda_mask, terms_out)
+    if not image.is_cuda or image.dtype != torch.float32:
+        raise RuntimeError("fused loss needs float32 GPU tensors; training_loss_moss() is the torch form")
+    if tuple(region.bound.shape) != tuple(image.shape[1:]) or region.bound.device != image.device:
+        raise RuntimeError("fused loss: the view's region does not belong to this image")
+    return _FusedPhotometricLoss.apply(image, alpha, gt_image, bkgd_mask.to(torch.float32), region,
+                                       (1.0, float(lambda_dssim), float(lambda_mask)), terms_out, 0)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------- S3IM
@@ -291,26 +233,22 @@ class _FusedS3IM(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, image, gt_image, rect, repeat_time):
-        from ._lib import check, lib
-        L = lib()
+        from ._lib import call, lib, ptr
         C, H, W = image.shape
         a, b = image.contiguous(), gt_image.contiguous()
         out = torch.empty(2, dtype=torch.float32, device=a.device)
         d_img = torch.empty((C, H, W), dtype=torch.float32, device=a.device)
-        nbytes = int(L.moss_s3im_workspace_bytes(C, H, W))
+        nbytes = int(lib().moss_s3im_workspace_bytes(C, H, W))
         ws = torch.empty(nbytes, dtype=torch.uint8, device=a.device)
-        with torch.cuda.device(a.device):
-            rc = L.moss_s3im_loss(C, H, W, a.data_ptr(), b.data_ptr(), None if rect is None else rect.data_ptr(), int(repeat_time),
-                                  out.data_ptr(), d_img.data_ptr(), ws.data_ptr(), nbytes, torch.cuda.current_stream(a.device).cuda_stream)
-        check(rc, "s3im_loss")
+        call("moss_s3im_loss", a.device, C, H, W, a.data_ptr(), b.data_ptr(), ptr(rect), int(repeat_time), out.data_ptr(), d_img.data_ptr(),
+             ws.data_ptr(), nbytes)
         ctx.save_for_backward(d_img)
         return out[0]
 
     @staticmethod
     def backward(ctx, grad_out):
         (d_img,) = ctx.saved_tensors
-        unit = _UNIT.get(d_img.device)          # (the unit gradient of backward_from_loss: no scaling kernel)
-        return (d_img if (unit is not None and grad_out.data_ptr() == unit.data_ptr()) else grad_out * d_img), None, None, None
+        return (d_img if _is_unit(grad_out) else grad_out * d_img), None, None, None
 
 
 def _check_s3im_inputs(image, gt_image, what):

@@ -95,10 +95,8 @@ class QualityReport:
 
     def add_many(self, views):
         """Queue views given as tuples ``(image, gt[, region[, out_image]])``, eight per launch, in order."""
-        from ._lib import EvalMetricsArgs, check, lib
-        L = lib()
+        from ._lib import EvalMetricsArgs, call
         views = list(views)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
         for k in range(0, len(views), MAX_VIEWS_PER_LAUNCH):
             chunk = views[k:k + MAX_VIEWS_PER_LAUNCH]
             a = EvalMetricsArgs()
@@ -121,8 +119,7 @@ class QualityReport:
             a.per_view = self._per_view.data_ptr() if self.per_view_capacity > 0 else None
             a.per_view_capacity = self.per_view_capacity
             a.workspace, a.workspace_bytes = self.workspace.data_ptr(), self.workspace_bytes
-            with torch.cuda.device(self.device):
-                check(L.moss_eval_metrics(ctypes.byref(a), stream), "eval_metrics")
+            call("moss_eval_metrics", self.device, ctypes.byref(a))
 
     def _read(self):
         s = self.state.cpu()                                  # the one host read

@@ -9,7 +9,7 @@ import ctypes as C
 
 import torch
 
-from ._lib import check, lib
+from ._lib import call, check, lib, ptr, stream
 
 
 class _FusedAdamW:
@@ -455,8 +455,7 @@ class FlatAdamW:
         a.segment_active, a.inactive_zero = C.addressof(act), int(self.sh_inactive_zero)
         a.beta1, a.beta2, a.eps, a.weight_decay = float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay)
         a.step = max(self.t, 1)
-        a.step_state = None if self.step_state is None else self.step_state.data_ptr()
-        a.skip_word = None if skip_word is None else skip_word.data_ptr()
+        a.step_state, a.skip_word = ptr(self.step_state), ptr(skip_word)
         a.skip_mask = int(skip_mask) & 0xffffffff
         extra = list(extra_grads or [])
         if len(extra) > 3:
@@ -466,9 +465,7 @@ class FlatAdamW:
             if e.numel() < grads.numel() or e.dtype != torch.float32 or e.device != grads.device or not e.is_contiguous():
                 raise ValueError("an extra gradient buffer must be a contiguous float32 tensor laid out like the bucket")
             a.grads_extra[i] = e[first:].data_ptr() if self.shard is None else e.data_ptr()
-        with torch.cuda.device(dev):
-            rc = lib().moss_adamw_flat_ex(C.addressof(a), torch.cuda.current_stream(dev).cuda_stream)
-        check(rc, "adamw_flat_ex")
+        call("moss_adamw_flat_ex", dev, C.addressof(a))
 
 
 class AdamW(torch.optim.Optimizer):
@@ -572,12 +569,12 @@ class AdamW(torch.optim.Optimizer):
             for (dev, beta1, beta2, eps, wd), items in batches.items():
                 a.beta1, a.beta2, a.eps, a.weight_decay = beta1, beta2, eps, wd
                 with torch.cuda.device(dev):
-                    stream = torch.cuda.current_stream(dev).cuda_stream
+                    s = stream(dev)
                     for i0 in range(0, len(items), 8):
                         part = items[i0:i0 + 8]
                         a.num_tensors = len(part)
                         for k, (p, g, m, v, lr, t) in enumerate(part):
                             a.numel[k], a.params[k], a.grads[k], a.exp_avg[k], a.exp_avg_sq[k] = p.numel(), p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr()
                             a.lr[k], a.step[k] = lr, t
-                        check(L.moss_adamw_multi(C.addressof(a), stream), "adamw_multi")
+                        check(L.moss_adamw_multi(C.addressof(a), s), "adamw_multi")
         return loss

@@ -187,14 +187,10 @@ def _param_shapes(anc):
     return shapes
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 class _PoseHead(torch.autograd.Function):
     @staticmethod
     def forward(ctx, poses, target_R, overreg, parents, *params):
-        from ._lib import POSE_HEAD_SAVED_FLOATS, PoseHeadArgs, check, lib
+        from ._lib import POSE_HEAD_SAVED_FLOATS, PoseHeadArgs, call
         dev = poses.device
         nj = NUM_JOINTS
         buf = torch.empty(nj * 13 + POSE_HEAD_SAVED_FLOATS, dtype=torch.float32, device=dev)      # one allocation for every output
@@ -202,8 +198,7 @@ class _PoseHead(torch.autograd.Function):
         a = PoseHeadArgs()
         _fill_head(a, poses, target_R, overreg, parents, params)
         a.Rs, a.S, a.nll, a.saved = Rs.data_ptr(), S.data_ptr(), nll.data_ptr(), saved.data_ptr()
-        with torch.cuda.device(dev):
-            check(lib().moss_pose_head_forward(ctypes.byref(a), _stream(dev)), "pose_head forward")
+        call("moss_pose_head_forward", dev, ctypes.byref(a))
         ctx.mark_non_differentiable(S)
         ctx.save_for_backward(poses, target_R, buf, *params)
         ctx.overreg, ctx.parents = overreg, parents
@@ -211,7 +206,7 @@ class _PoseHead(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_Rs, _g_S, g_nll):
-        from ._lib import PoseHeadBackwardArgs, check, lib
+        from ._lib import PoseHeadBackwardArgs, call, ptr
         poses, target_R, buf, *params = ctx.saved_tensors
         dev = poses.device
         nj = NUM_JOINTS
@@ -223,11 +218,10 @@ class _PoseHead(torch.autograd.Function):
         a = PoseHeadBackwardArgs()
         _fill_head(a, poses, target_R, ctx.overreg, ctx.parents, params)
         a.S, a.saved = buf[nj * 9:].data_ptr(), buf[nj * 13:].data_ptr()
-        a.g_Rs, a.g_nll = (None if g_Rs is None else g_Rs.data_ptr()), (None if g_nll is None else g_nll.data_ptr())
+        a.g_Rs, a.g_nll = ptr(g_Rs), ptr(g_nll)
         for i, g in enumerate(grads):
             a.grads[i] = g.data_ptr()
-        with torch.cuda.device(dev):
-            check(lib().moss_pose_head_backward(ctypes.byref(a), _stream(dev)), "pose_head backward")
+        call("moss_pose_head_backward", dev, ctypes.byref(a))
         return (None, None, None, None, *grads)
 
 
@@ -279,15 +273,13 @@ def pose_head_fused(net, poses, target_R, overreg=1.005, parents=SMPL_PARENTS):
 class _MatrixFisherNLL(torch.autograd.Function):
     @staticmethod
     def forward(ctx, F, target_R, overreg):
-        from ._lib import check, lib
+        from ._lib import call, ptr
         n, dev = int(F.shape[0]), F.device
         want = ctx.needs_input_grad[0]
         nll = torch.empty(n, dtype=torch.float32, device=dev)
         dF = torch.empty((n, 3, 3), dtype=torch.float32, device=dev) if want else None
         if n > 0:
-            with torch.cuda.device(dev):
-                check(lib().moss_matrix_fisher_nll(n, F.data_ptr(), target_R.data_ptr(), overreg, nll.data_ptr(),
-                                                   None if dF is None else dF.data_ptr(), _stream(dev)), "matrix_fisher_nll")
+            call("moss_matrix_fisher_nll", dev, n, F.data_ptr(), target_R.data_ptr(), overreg, nll.data_ptr(), ptr(dF))
         if want:
             ctx.save_for_backward(dF)
         return nll

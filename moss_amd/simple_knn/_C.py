@@ -3,7 +3,7 @@ from __future__ import annotations
 
 import torch
 
-from .._lib import check, lib
+from .._lib import call, lib
 
 lib()   # fail at import time if the HIP library is missing: there is no fallback
 
@@ -22,8 +22,5 @@ def distCUDA2(points: torch.Tensor) -> torch.Tensor:
     pts = points.contiguous()
     nbytes = int(L.moss_knn_workspace_bytes(P))
     workspace = torch.empty((nbytes,), dtype=torch.uint8, device=points.device)
-    with torch.cuda.device(points.device):
-        rc = L.moss_knn_dist2(P, pts.data_ptr(), means.data_ptr(), workspace.data_ptr(), nbytes,
-                              torch.cuda.current_stream(points.device).cuda_stream)
-    check(rc, "distCUDA2")
+    call("moss_knn_dist2", points.device, P, pts.data_ptr(), means.data_ptr(), workspace.data_ptr(), nbytes)
     return means

@@ -112,6 +112,39 @@ def test_scratch_size_functions_are_host_only_and_monotonic(hip_lib):
     assert hip_lib.moss_loss_workspace_bytes(3, 512, 512) >= 3 * 3 * 512 * 512 * 4
 
 
+def test_refused_loss_calls_say_which_entry_point_and_why(hip_lib):
+    """Every refusal of the three photometric-loss entry points sets the text of moss_last_error(): it names the entry point, and it
+    is not what an earlier refused call of another op left behind.  All of these calls are refused before anything is dereferenced
+    or launched (the non-null pointers are dummy addresses)."""
+    INVALID = -1                                               # MOSS_ERR_INVALID_ARG
+    p = 0x1000                                                 # a pointer that only has to be non-null
+    C, H, W = 3, 64, 48
+    need = hip_lib.moss_loss_workspace_bytes(C, H, W)
+
+    def plain(C=C, image=p, alpha=p, mask=p, nbytes=need):
+        return hip_lib.moss_photometric_loss(C, H, W, image, p, alpha, mask, 0.2, 0.5, p, p, p, p, nbytes, None)
+
+    def weighted(C=C, image=p, alpha=p, mask=p, nbytes=need):
+        return hip_lib.moss_photometric_loss_weighted(C, H, W, image, p, alpha, mask, 1.0, 0.2, 0.5, p, p, p, p, nbytes, None)
+
+    def roi(C=C, image=p, alpha=p, mask=p, nbytes=need, rect=p):
+        return hip_lib.moss_photometric_loss_roi(C, H, W, image, p, alpha, mask, p, rect, 1.0, 0.2, 0.5, p, p, p, p, nbytes, None)
+
+    refusals = [dict(C=0), dict(image=None), dict(mask=None), dict(nbytes=need - 1)]
+    for name, fn, cases in (("moss_photometric_loss", plain, refusals), ("moss_photometric_loss_weighted", weighted, refusals),
+                            ("moss_photometric_loss_roi", roi, refusals + [dict(rect=None)])):
+        texts = []
+        for kw in cases:
+            assert hip_lib.moss_s3im_loss(0, H, W, p, p, None, 10, p, p, p, 0, None) == INVALID      # refused at its first check
+            sentinel = hip_lib.moss_last_error()
+            assert b"moss_s3im_loss" in sentinel
+            assert fn(**kw) == INVALID, (name, kw)
+            text = hip_lib.moss_last_error()
+            assert text != sentinel and text.split(b":")[0] == name.encode(), (name, kw, text)
+            texts.append(text)
+        assert len(set(texts)) == len(texts), texts           # a text per condition
+
+
 def test_missing_library_is_an_import_error_not_a_fallback(monkeypatch):
     from moss_amd import _lib
     monkeypatch.setattr(_lib, "_lib", None)
