@@ -465,6 +465,79 @@ int moss_lbs_deform_backward(const moss_lbs_backward_args* args, void* stream);
 size_t moss_lbs_workspace_bytes(int P, int J);
 
 /*
+ * The per-frame, per-subject part of MOSS's coarse_deform_c2source (additive in ABI 7): what scene/gaussian_model.py:835-901 computes
+ * before and between the per-Gaussian steps, with get_transform_params_torch / get_rigid_transformation_torch (:965-1031) and
+ * batch_rodrigues_torch (:945-963).  It feeds moss_lbs_deform_forward (A_big, A_obs, d) and takes its gradients back.
+ *     rot_big = Rodrigues(poses_big), rot = Rodrigues(poses)      angle = |r + 1e-8|, R = I + sin K + (1 - cos) K K    (:859,883,945-963)
+ *     rot[1:] = rot[1:] correct_Rs                                 with correct_Rs                                       (:885-888)
+ *     joints_s = J_regressor (v_template + shapedirs[..., :nb_s] beta_s)   for s = big (shapes_big), obs (shapes)         (:1004-1007,1021)
+ *     G_0 = [rot_0 | joints_0], G_j = G_parent[j] [rot_j | joints_j - joints_parent[j]], A_j = [G_j.R | G_j.t - G_j.R joints_j]   (:965-995)
+ *     D = shapedirs[..., :nb] beta_obs + posedirs ((rot[1:] - I) - (rot_big[1:] - I))   (V,3): ONE pass over posedirs       (:855-899)
+ *     d = D[vert_ids]                                               (P,3)                                                  (:863,872,894)
+ * Shapes (fp32, contiguous): v_template (V,3); shapedirs (V,3,shapedirs_stride), of which the first num_betas_big / num_betas enter;
+ * posedirs (V,3,9(J-1)); J_regressor (J,V); poses_big, poses (3J); shapes_big (num_betas_big), shapes (num_betas); correct_Rs
+ * (J-1,3,3) or NULL; vert_ids (P) int64 -- all DEVICE pointers, so that a captured graph reads the frame's values at replay.
+ * parents: by value, parents[j] in [0, j) for j >= 1 (parents[0] is not read); J = 1..MOSS_SMPL_FRAME_MAX_JOINTS.
+ * Outputs: A_big, A_obs (J,4,4) (row 3 = 0 0 0 1); d (P,3), a NaN row for an id outside [0, V) (never dereferenced); rot_mats (J,3,3),
+ * the frame's rotations after correct_Rs; saved: MOSS_SMPL_FRAME_SAVED_FLOATS_PER_JOINT * J floats for the backward, or NULL.
+ * workspace: moss_smpl_frame_workspace_bytes(max(P, 1), V, J) device bytes (D and the regressor shares; garbage afterwards).
+ * Two launches on `stream`.  Every sum is formed in float64 in a fixed order, no atomics: bitwise reproducible.  No host
+ * synchronisation, no allocation, no memset: capturable.  Bad arguments return MOSS_ERR_INVALID_ARG with moss_last_error() set.
+ */
+#define MOSS_SMPL_FRAME_MAX_JOINTS 64
+#define MOSS_SMPL_FRAME_SAVED_FLOATS_PER_JOINT 33
+typedef struct moss_smpl_frame_args {
+    int32_t P, V, J;
+    int32_t num_betas_big, num_betas, shapedirs_stride;
+    int32_t parents[MOSS_SMPL_FRAME_MAX_JOINTS];
+    const float* v_template;
+    const float* shapedirs;
+    const float* posedirs;                   /* may be NULL for J = 1 */
+    const float* J_regressor;
+    const float* poses_big;
+    const float* shapes_big;
+    const float* poses;
+    const float* shapes;
+    const float* correct_Rs;                 /* (J-1,3,3) or NULL */
+    const int64_t* vert_ids;
+    float* A_big;
+    float* A_obs;
+    float* d;
+    float* rot_mats;
+    float* saved;                            /* or NULL: no backward will follow */
+    char* workspace; size_t workspace_bytes;
+} moss_smpl_frame_args;
+int moss_smpl_frame_forward(const moss_smpl_frame_args* args, void* stream);   /* scene/gaussian_model.py:835-901, :945-1031 */
+
+/*
+ * Backward of moss_smpl_frame_forward to correct_Rs (the autograd of scene/gaussian_model.py:885-901 and :965-995; poses, shapes, the
+ * body model and the big pose are data in MOSS and get no gradient).  g_A_obs (J,4,4) and g_d (P,3) are what moss_lbs_deform_backward
+ * hands back, each NULL when zero; g_correct_Rs (J-1,3,3) is written, never accumulated into.
+ *     g_feat[k] = sum_i sum_c posedirs[vert_ids[i], c, k] g_d[i, c]: every workgroup owns a fixed run of Gaussians and walks it in index
+ *       order, the workgroups' vectors are folded in workgroup order (g_D (V,3) is never formed; coinciding ids cost nothing extra;
+ *       a Gaussian with an id outside [0, V) adds nothing);
+ *     the chain's adjoint as a reverse walk of the tree: gGR_j = g_A_j[:3,:3] - g_A_j[:3,3] joints_j^T, gGt_j = g_A_j[:3,3];
+ *       for j = J-1 .. 1, p = parents[j]: g_rot_j = G_p.R^T gGR_j, gGR_p += gGR_j rot_j^T + gGt_j rel_j^T, gGt_p += gGt_j;
+ *     g_correct_Rs[q] = rot_raw[q+1]^T (g_rot[q+1] + g_feat[9q .. 9q+8]).
+ * saved: as the forward wrote it.  workspace: moss_smpl_frame_workspace_bytes(P, V, J) device bytes (needed with g_d).  Three launches
+ * on `stream` (one without g_d or with P = 0), float64 sums in a fixed order, no atomics: bitwise reproducible; capturable.
+ */
+typedef struct moss_smpl_frame_backward_args {
+    int32_t P, V, J;
+    int32_t parents[MOSS_SMPL_FRAME_MAX_JOINTS];
+    const float* posedirs;
+    const int64_t* vert_ids;
+    const float* saved;
+    const float* g_A_obs;                    /* (J,4,4) or NULL; row 3 is not read */
+    const float* g_d;                        /* (P,3) or NULL */
+    float* g_correct_Rs;                     /* (J-1,3,3) */
+    char* workspace; size_t workspace_bytes;
+} moss_smpl_frame_backward_args;
+int moss_smpl_frame_backward(const moss_smpl_frame_backward_args* args, void* stream);   /* the adjoint of scene/gaussian_model.py:885-901, :965-995 */
+/* device bytes of either call's workspace (host-side arithmetic, monotonic); 0 for a size <= 0 or J outside 1..64 (gaussian_model.py:835-901) */
+size_t moss_smpl_frame_workspace_bytes(int P, int V, int J);
+
+/*
  * MOSS's S3IM term and its gradient (additive in ABI 7): s3im_loss = s3im_fun(img_pred, img_gt) (train_ZJU.py:123, weighted 0.3 at
  * :131; utils/loss_utils.py:17-38).  MOSS hands it two (1,C,h,w) crops, so every randperm(1) is [0] and the term is deterministic:
  *     s3im = 1 - ssim(x~, y~),   x~ = the crop with every pixel repeated `repeat` times along a row (width repeat * w)

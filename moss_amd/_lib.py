@@ -87,6 +87,12 @@ def _declare(lib):
     lib.moss_lbs_deform_forward.argtypes = [_p, _p]
     lib.moss_lbs_deform_backward.restype = _i
     lib.moss_lbs_deform_backward.argtypes = [_p, _p]
+    lib.moss_smpl_frame_workspace_bytes.restype = C.c_size_t
+    lib.moss_smpl_frame_workspace_bytes.argtypes = [_i, _i, _i]
+    lib.moss_smpl_frame_forward.restype = _i
+    lib.moss_smpl_frame_forward.argtypes = [_p, _p]
+    lib.moss_smpl_frame_backward.restype = _i
+    lib.moss_smpl_frame_backward.argtypes = [_p, _p]
     lib.moss_s3im_workspace_bytes.restype = C.c_size_t
     lib.moss_s3im_workspace_bytes.argtypes = [_i, _i, _i]
     lib.moss_s3im_loss.restype = _i
@@ -170,6 +176,27 @@ class LbsBackwardArgs(C.Structure):
     _fields_ = _LBS_INPUTS + [("g_T", C.c_void_p), ("g_t", C.c_void_p), ("g_p", C.c_void_p), ("g_L", C.c_void_p),
                               ("g_A_obs", C.c_void_p), ("g_d", C.c_void_p), ("g_x", C.c_void_p), ("workspace", C.c_void_p),
                               ("workspace_bytes", C.c_size_t)]
+
+
+SMPL_FRAME_MAX_JOINTS = 64                               # MOSS_SMPL_FRAME_MAX_JOINTS
+SMPL_FRAME_SAVED_FLOATS_PER_JOINT = 33                   # MOSS_SMPL_FRAME_SAVED_FLOATS_PER_JOINT
+
+
+class SmplFrameArgs(C.Structure):
+    """``moss_smpl_frame_args`` of include/moss_raster.h (``moss_smpl_frame_forward``: the per-frame SMPL skeleton and offsets)."""
+    _fields_ = [("P", C.c_int32), ("V", C.c_int32), ("J", C.c_int32), ("num_betas_big", C.c_int32), ("num_betas", C.c_int32),
+                ("shapedirs_stride", C.c_int32), ("parents", C.c_int32 * 64), ("v_template", C.c_void_p), ("shapedirs", C.c_void_p),
+                ("posedirs", C.c_void_p), ("J_regressor", C.c_void_p), ("poses_big", C.c_void_p), ("shapes_big", C.c_void_p),
+                ("poses", C.c_void_p), ("shapes", C.c_void_p), ("correct_Rs", C.c_void_p), ("vert_ids", C.c_void_p),
+                ("A_big", C.c_void_p), ("A_obs", C.c_void_p), ("d", C.c_void_p), ("rot_mats", C.c_void_p), ("saved", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+class SmplFrameBackwardArgs(C.Structure):
+    """``moss_smpl_frame_backward_args`` of include/moss_raster.h (``moss_smpl_frame_backward``)."""
+    _fields_ = [("P", C.c_int32), ("V", C.c_int32), ("J", C.c_int32), ("parents", C.c_int32 * 64), ("posedirs", C.c_void_p),
+                ("vert_ids", C.c_void_p), ("saved", C.c_void_p), ("g_A_obs", C.c_void_p), ("g_d", C.c_void_p),
+                ("g_correct_Rs", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
 POSE_HEAD_SAVED_FLOATS = 896                             # MOSS_POSE_HEAD_SAVED_FLOATS

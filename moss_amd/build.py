@@ -40,6 +40,7 @@ SOURCES = {
     "s3im.hip": [],
     "metrics.hip": [],
     "lbs.hip": [],
+    "smpl_frame.hip": [],
     "pose_head.hip": [],
     "lbs_weight_net.hip": [],
     "optim.hip": [],

@@ -126,6 +126,8 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
         _, world, bweights, transforms, translation = coarse_deform_c2source(
             pc, means3D[None], viewpoint_camera.smpl_param, viewpoint_camera.big_pose_smpl_param,
             viewpoint_camera.big_pose_world_vertex[None], return_transl=True,
+            # ``pipe.smpl_frame_in_op`` (an addition, default off): the per-frame skeleton and offsets as the fused HIP op too
+            fused_frame=bool(getattr(pipe, "smpl_frame_in_op", False)),
             **({} if pose_out is None else {"lbs_weights": lbs_weights, "correct_Rs": correct_Rs}))
         if (getattr(pipe, "pose_in_op", False) and getattr(pipe, "transforms_in_op", False) and not pipe.compute_cov3D_python
                 and not pipe.convert_SHs_python):

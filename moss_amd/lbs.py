@@ -7,8 +7,11 @@ weights (softmax over ``log(W + 1e-9) + lbs_weights`` with the pose refiner on),
 * :func:`lbs_deform` -- the per-Gaussian part, one HIP kernel each way (C ABI ``moss_lbs_deform_forward`` / ``_backward``,
   moss_amd/csrc/lbs.hip): weights, both blends, the 3x3 inverse (adjugate), ``T``, ``t`` and the posed positions ``p``.  Gradients go
   to the LBS offsets, ``A_obs`` (a deterministic reduction over the Gaussians), the gathered offsets ``d`` and the positions ``x``.
-* :func:`smpl_joint_transforms`, :func:`vertex_offsets` -- the per-frame, per-subject part in torch (24 joints, two GEMVs): small,
-  differentiable, no host synchronisation.
+* :func:`smpl_joint_transforms`, :func:`vertex_offsets` -- the per-frame, per-subject part in torch (24 joints, two GEMVs): small in
+  bytes, about 320 launches per training step; differentiable, no host synchronisation.
+* :func:`smpl_frame_fused` -- the same per-frame part as a fused HIP op (C ABI ``moss_smpl_frame_forward`` / ``_backward``,
+  moss_amd/csrc/smpl_frame.hip): both Rodrigues, both chains, the offset table in one pass over ``posedirs`` and its gather, two
+  launches forward and three backward.  The gradient goes to ``correct_Rs``.
 * :func:`coarse_deform_c2source` -- the drop-in: same arguments, same 5-tuple as the reference.
 * :func:`deform_torch` -- the same per-Gaussian math in plain torch (any dtype or device): the float64 yardstick of the tests and the
   float32 stand-in for MOSS's chain in scripts/lbs_times.py.  It is not a fallback; :func:`lbs_deform` has no CPU path.
@@ -24,10 +27,11 @@ import torch
 import torch.nn.functional as F
 from torch.utils.weak import WeakIdKeyDictionary
 
-from ._lib import LbsBackwardArgs, LbsForwardArgs, call, lib, ptr
+from ._lib import (LbsBackwardArgs, LbsForwardArgs, SMPL_FRAME_SAVED_FLOATS_PER_JOINT, SmplFrameArgs, SmplFrameBackwardArgs, call, lib,
+                   ptr)
 
-__all__ = ["lbs_deform", "smpl_joint_transforms", "vertex_offsets", "coarse_deform_c2source", "deform_torch", "synthetic_body_model",
-           "batch_rodrigues", "MAX_JOINTS", "SMPL_PARENTS"]
+__all__ = ["lbs_deform", "smpl_joint_transforms", "vertex_offsets", "smpl_frame_fused", "coarse_deform_c2source", "deform_torch",
+           "synthetic_body_model", "batch_rodrigues", "MAX_JOINTS", "SMPL_PARENTS"]
 
 MAX_JOINTS = 64
 SMPL_PARENTS = (-1, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9, 9, 12, 13, 14, 16, 17, 18, 19, 20, 21)
@@ -252,13 +256,150 @@ def vertex_offsets(body, params, t_params, rot_mats):
     return shape_off - _pose_offsets(body, big) + _pose_offsets(body, rot_mats)
 
 
-def coarse_deform_c2source(model, query_pts, params, t_params, t_vertices, lbs_weights=None, correct_Rs=None, return_transl=False):
+# ---- the per-frame part as a fused op -------------------------------------------------------------------------------------------
+
+class _SmplFrame(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, cR, par, vt, sd, pd, jr, poses_big, shapes_big, poses, shapes, ids):
+        V, J, P = int(vt.shape[0]), int(jr.shape[0]), int(ids.shape[0])
+        dev = vt.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        A_big, A_obs = torch.empty((J, 4, 4), **f32), torch.empty((J, 4, 4), **f32)
+        d, rot = torch.empty((P, 3), **f32), torch.empty((J, 3, 3), **f32)
+        saved = torch.empty(SMPL_FRAME_SAVED_FLOATS_PER_JOINT * J, **f32) if cR is not None else None
+        nbytes = int(lib().moss_smpl_frame_workspace_bytes(max(P, 1), V, J))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        a = SmplFrameArgs()
+        a.P, a.V, a.J = P, V, J
+        a.num_betas_big, a.num_betas, a.shapedirs_stride = int(shapes_big.shape[0]), int(shapes.shape[0]), int(sd.shape[2])
+        a.parents[:J] = par
+        a.v_template, a.shapedirs, a.posedirs, a.J_regressor = vt.data_ptr(), sd.data_ptr(), pd.data_ptr(), jr.data_ptr()
+        a.poses_big, a.shapes_big, a.poses, a.shapes = poses_big.data_ptr(), shapes_big.data_ptr(), poses.data_ptr(), shapes.data_ptr()
+        a.correct_Rs, a.vert_ids = ptr(cR), ids.data_ptr()
+        a.A_big, a.A_obs, a.d, a.rot_mats, a.saved = A_big.data_ptr(), A_obs.data_ptr(), d.data_ptr(), rot.data_ptr(), ptr(saved)
+        a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+        call("moss_smpl_frame_forward", dev, ctypes.byref(a))
+        ctx.mark_non_differentiable(A_big, rot)
+        ctx.set_materialize_grads(False)                        # (no zero-fill launches for the cotangents nobody formed)
+        if cR is not None:
+            ctx.save_for_backward(pd, ids, saved)
+        ctx.par, ctx.V = par, V
+        return A_big, A_obs, d, rot
+
+    @staticmethod
+    def backward(ctx, _gA_big, gA_obs, gd, _grot):
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 11
+        pd, ids, saved = ctx.saved_tensors
+        J, P, V = len(ctx.par), int(ids.shape[0]), ctx.V
+        dev = pd.device
+        g = torch.empty((J - 1, 3, 3), dtype=torch.float32, device=dev)
+        if J > 1:
+            a = SmplFrameBackwardArgs()
+            a.P, a.V, a.J = P, V, J
+            a.parents[:J] = ctx.par
+            a.posedirs, a.vert_ids, a.saved = pd.data_ptr(), ids.data_ptr(), saved.data_ptr()
+            gA_obs = None if gA_obs is None else gA_obs.float().contiguous()
+            gd = None if (gd is None or P == 0) else gd.float().contiguous()
+            a.g_A_obs, a.g_d, a.g_correct_Rs = ptr(gA_obs), ptr(gd), g.data_ptr()
+            if gd is not None:
+                nbytes = int(lib().moss_smpl_frame_workspace_bytes(P, V, J))
+                ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+                a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+            call("moss_smpl_frame_backward", dev, ctypes.byref(a))
+        return (g,) + (None,) * 10
+
+
+def _need_frame(t, name, shape, dtype=torch.float32):
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"smpl_frame_fused: {name} must be a tensor")
+    if t.dtype != dtype:
+        raise ValueError(f"smpl_frame_fused: {name} must be {dtype}, got {t.dtype}")
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"smpl_frame_fused: {name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"smpl_frame_fused: {name} must be contiguous")
+
+
+def smpl_frame_fused(body, params, t_params, vert_ids, correct_Rs=None):
+    """The per-frame, per-subject part of ``coarse_deform_c2source`` as one fused op on the device (C ABI ``moss_smpl_frame_forward`` /
+    ``_backward``; formulas in include/moss_raster.h): ``(A_big (J,4,4), A_obs (J,4,4), d (P,3), rot_mats (J,3,3))`` -- what
+    :func:`smpl_joint_transforms` of ``t_params`` and of ``params`` (with ``rot[1:] @ correct_Rs``), :func:`vertex_offsets` gathered at
+    ``vert_ids``, and the frame's refined rotations give, in two launches.  ``D`` is formed in one pass over ``posedirs``
+    (``P f_obs - P f_big = P (f_obs - f_big)``) and every sum in float64, so the rounding differs from the torch form's within the
+    float32 bar of the tests.
+
+    ``body``: ``v_template`` (V,3), ``shapedirs`` (V,3,B), ``posedirs`` (V,3,9(J-1)), ``J_regressor`` (J,V), ``weights`` (V,J) (its
+    width is J), ``kintree_table`` (2,J) with ``parent[j] < j`` (read on the host once per table, never inside a capture).
+    ``params`` / ``t_params``: ``poses`` (3J elements), ``shapes`` (at most B elements).  ``vert_ids`` (P,) int64; ``correct_Rs``
+    (J-1,3,3) or None.  All float32, contiguous, on one GPU; J = 1..64.  The gradient flows to ``correct_Rs`` (from ``A_obs`` and
+    ``d``); ``A_big`` and ``rot_mats`` come out detached, and ``poses``, ``shapes`` and the body model are data: one that requires
+    grad raises ValueError.  Ids outside [0, V) give NaN rows of ``d``.  There is no CPU path."""
+    for key in ("v_template", "shapedirs", "posedirs", "J_regressor", "weights", "kintree_table"):
+        if not isinstance(body.get(key), torch.Tensor):
+            raise ValueError(f"smpl_frame_fused: body['{key}'] must be a tensor")
+    vt, sd, pd, jr = body["v_template"], body["shapedirs"], body["posedirs"], body["J_regressor"]
+    J = int(body["weights"].shape[-1])
+    if not 1 <= J <= MAX_JOINTS:
+        raise ValueError(f"smpl_frame_fused: J = {J} joints; the kernels take 1..{MAX_JOINTS}")
+    if vt.dim() != 2 or vt.shape[0] < 1:
+        raise ValueError("smpl_frame_fused: v_template must be (V, 3) with V >= 1")
+    V = int(vt.shape[0])
+    if sd.dim() != 3:
+        raise ValueError("smpl_frame_fused: shapedirs must be (V, 3, B)")
+    if not isinstance(vert_ids, torch.Tensor) or vert_ids.dim() != 1:
+        raise ValueError("smpl_frame_fused: vert_ids must be a (P,) tensor")
+    for name, p in (("params", params), ("t_params", t_params)):
+        for key in ("poses", "shapes"):
+            if not isinstance(p.get(key), torch.Tensor):
+                raise ValueError(f"smpl_frame_fused: {name}['{key}'] must be a tensor")
+    data = {"v_template": vt, "shapedirs": sd, "posedirs": pd, "J_regressor": jr, "params['poses']": params["poses"],
+            "params['shapes']": params["shapes"], "t_params['poses']": t_params["poses"], "t_params['shapes']": t_params["shapes"]}
+    for name, t in data.items():
+        if t.requires_grad:
+            raise ValueError(f"smpl_frame_fused: {name} requires grad, but it is data of the deformation (no gradient is formed for "
+                             "it); detach it")
+    nb_big, nb = int(t_params["shapes"].numel()), int(params["shapes"].numel())
+    if max(nb_big, nb) > sd.shape[2]:
+        raise ValueError(f"smpl_frame_fused: {max(nb_big, nb)} shape coefficients, but shapedirs stores {sd.shape[2]}")
+    _need_frame(vt, "v_template", (V, 3))
+    _need_frame(sd, "shapedirs", (V, 3, sd.shape[2]))
+    _need_frame(pd, "posedirs", (V, 3, 9 * (J - 1)))
+    _need_frame(jr, "J_regressor", (J, V))
+    _need_frame(vert_ids, "vert_ids", (vert_ids.shape[0],), torch.int64)
+    flat = {}
+    for name, t, n in (("t_params['poses']", t_params["poses"], 3 * J), ("t_params['shapes']", t_params["shapes"], nb_big),
+                       ("params['poses']", params["poses"], 3 * J), ("params['shapes']", params["shapes"], nb)):
+        if t.numel() != n:
+            raise ValueError(f"smpl_frame_fused: {name} must have {n} elements, got {t.numel()}")
+        _need_frame(t, name, t.shape)
+        flat[name] = t.reshape(-1)
+    if correct_Rs is not None:
+        _need_frame(correct_Rs, "correct_Rs", (J - 1, 3, 3))
+    dev = vt.device
+    if dev.type != "cuda":
+        raise ValueError("smpl_frame_fused runs the HIP per-frame kernels: its tensors must be on a GPU (smpl_joint_transforms and "
+                         "vertex_offsets are the torch form)")
+    for name, t in list(data.items()) + [("vert_ids", vert_ids)] + ([] if correct_Rs is None else [("correct_Rs", correct_Rs)]):
+        if t.device != dev:
+            raise ValueError(f"smpl_frame_fused: {name} must be on {dev}, got {t.device}")
+    par = _parents(body, dev)[0]
+    if len(par) != J or any(not 0 <= par[j] < j for j in range(1, J)):
+        raise ValueError("smpl_frame_fused: kintree_table[0] must list J parents with 0 <= parent[j] < j for j >= 1")
+    par = [-1] + list(par[1:])                                 # (SMPL files store joint 0's parent as 2^32 - 1; it is not read)
+    return _SmplFrame.apply(correct_Rs, par, vt, sd, pd, jr, flat["t_params['poses']"], flat["t_params['shapes']"],
+                            flat["params['poses']"], flat["params['shapes']"], vert_ids)
+
+
+def coarse_deform_c2source(model, query_pts, params, t_params, t_vertices, lbs_weights=None, correct_Rs=None, return_transl=False,
+                           fused_frame=False):
     """Drop-in for ``GaussianModel.coarse_deform_c2source`` (scene/gaussian_model.py:820-923): same arguments, same
     ``(smpl_src_pts, world_src_pts, bweights, transforms, translation)`` of shapes (1,P,3), (1,P,3), (1,P,J), (1,P,3,3), (1,P,3) --
     ``translation`` only with ``return_transl``, else None.  ``model`` supplies ``SMPL_NEUTRAL`` (the body model, on the GPU) and
     ``knn`` (``moss_amd.knn_cuda.KNN(k=1, transpose_mode=True)``), as MOSS's ``GaussianModel`` does.  The per-Gaussian work is
-    :func:`lbs_deform`; the kinematic chain and the blend shapes are torch.  ``bweights`` carries no gradient (MOSS only
-    accumulates it for densification).  Batch size 1, as MOSS renders."""
+    :func:`lbs_deform`; the kinematic chain and the blend shapes are torch, or with ``fused_frame`` (an addition, default off) the
+    fused op :func:`smpl_frame_fused`.  ``bweights`` carries no gradient (MOSS only accumulates it for densification).  Batch size 1,
+    as MOSS renders."""
     if query_pts.dim() != 3 or query_pts.shape[0] != 1:
         raise ValueError("coarse_deform_c2source: query_pts must be (1, P, 3)")
     body = model.SMPL_NEUTRAL
@@ -267,6 +408,13 @@ def coarse_deform_c2source(model, query_pts, params, t_params, t_vertices, lbs_w
     P = query_pts.shape[1]
     _, vert_ids = model.knn(t_vertices.float(), query_pts.float())
     ids = vert_ids.reshape(P)
+    if fused_frame:
+        c32 = lambda t: t.float().contiguous()                                        # noqa: E731
+        A_big, A_obs, d, _ = smpl_frame_fused(
+            body, {"poses": c32(params["poses"]), "shapes": c32(params["shapes"])},
+            {"poses": c32(t_params["poses"]), "shapes": c32(t_params["shapes"])}, ids.contiguous(),
+            correct_Rs=None if correct_Rs is None else c32(correct_Rs.reshape(J - 1, 3, 3)))
+        return _deform_frame(query_pts, ids, W, lbs_weights, A_big, A_obs, d, params["R"], params["Th"], return_transl)
     A_big, _, _ = smpl_joint_transforms(body, t_params)
     rot_mats = batch_rodrigues(params["poses"].reshape(-1, 3).to(W)).reshape(J, 3, 3)
     if correct_Rs is not None:
@@ -274,10 +422,16 @@ def coarse_deform_c2source(model, query_pts, params, t_params, t_vertices, lbs_w
     A_obs, R, Th = smpl_joint_transforms(body, params, rot_mats=rot_mats)
     D = vertex_offsets(body, params, t_params, rot_mats)
     d = D[ids]
+    return _deform_frame(query_pts, ids, W, lbs_weights, A_big[0].detach(), A_obs[0], d, R, Th, return_transl)
+
+
+def _deform_frame(query_pts, ids, W, lbs_weights, A_big, A_obs, d, R, Th, return_transl):
+    """The per-Gaussian half of :func:`coarse_deform_c2source`, from the frame's ``A_big``, ``A_obs`` (J,4,4) and ``d`` (P,3)."""
+    P, J = ids.shape[0], W.shape[-1]
     L = None if lbs_weights is None else lbs_weights.reshape(P, J).float().contiguous()
     R = R.reshape(3, 3).float().contiguous()
     Th = Th.reshape(3).float().contiguous()
-    T, t, p, w = lbs_deform(ids.contiguous(), W.contiguous(), L, A_big[0].detach().contiguous(), A_obs[0].contiguous(),
+    T, t, p, w = lbs_deform(ids.contiguous(), W.contiguous(), L, A_big.contiguous(), A_obs.contiguous(),
                             d.contiguous(), R, Th, x=query_pts[0].float().contiguous(), want_weights=True)
     smpl_src = (p - Th) @ R                                    # R^T (p - Th): the reference's smpl_src_pts
     return smpl_src[None], p[None], w[None], T[None], (t[None] if return_transl else None)
