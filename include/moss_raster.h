@@ -677,6 +677,71 @@ size_t moss_lbs_weight_net_workspace_bytes(int P);  /* scratch of the backward o
 size_t moss_lbs_weight_net_saved_bytes(int P);      /* what its forward keeps for the backward; 0 for P <= 0 */
 
 /*
+ * MOSS's LPIPS term (additive in ABI 7): loss_fn_vgg(img_pred, img_gt), train_ZJU.py:121 (weighted 0.5 at :131) and :256 ->
+ * LPIPS.forward with net_type='vgg', lpipsPyTorch/modules/lpips.py:31-37 (BaseNet.forward networks.py:49-62, VGG16 :87-95,
+ * normalize_activation utils.py:5-7):
+ *     z = (img - shift) / scale                                    per channel
+ *     VGG16 features[0:30]: 13 x (conv 3x3, padding 1, bias, ReLU), widths 64 64 | 128 128 | 256 256 256 | 512 512 512 | 512 512 512,
+ *                           a 2x2 stride-2 max-pool (floor) between the groups
+ *     tap l = the activations after ReLU 1_2, 2_2, 3_3, 4_3, 5_3:   n = f / (sqrt(sum_c f^2) + 1e-10) per pixel
+ *     term_l = mean over pixels of sum_c lin_l[c] (nx - ny)^2;   out = sum_l term_l
+ * Both images run as one batch of two; the weights are frozen and y gets no gradient, so the backward is the data gradient w.r.t. x.
+ *   x, y: (3,frame_H,frame_W) fp32 planes; the term is taken on the crop of H x W pixels whose corner is rect[0] (x), rect[1] (y) --
+ *     DEVICE ints as moss_photometric_loss_roi's, moved so that the crop fits the frame -- or (0,0) with rect NULL; frame_H = frame_W
+ *     = 0 means the frame is the crop.  H, W >= 16, H * W <= 2^22; neither needs to be a multiple of anything.
+ *   weights / biases: per convolution, packed by moss_lpips_vgg_pack_weights (`fwd`); lin: 5 arrays of 64, 128, 256, 512, 512 floats;
+ *     shift, scale: 3 device floats each.  weights_bwd: the `bwd` arrays of the same packing.
+ *   out: 1 device float; terms: 5 device floats or NULL; saved: moss_lpips_vgg_saved_bytes(H, W) bytes the forward writes for the
+ *     backward -- one sign bit per activation of x, two bits per pooled activation (which of the four won), and per tap d term_l / d fx
+ *     -- or NULL: nothing is kept (an evaluation call);
+ *   g_out: the upstream gradient of `out`, 1 DEVICE float; dL_dx (3,frame_H,frame_W): written everywhere, zero off the crop;
+ *   workspace: moss_lpips_vgg_workspace_bytes(H, W) bytes of scratch for either call (monotonic in H * W: one sized for the frame
+ *     serves every crop), contents irrelevant before, garbage after.
+ * Every convolution but the first runs on the f32-input matrix cores in exact float32.  No host synchronisation, no allocation:
+ * capturable; a captured step changes view by rewriting `rect`.  Every sum has a fixed order and there is no atomic: bitwise
+ * reproducible.  Bad arguments (a NULL required pointer, a size outside the range, a short workspace) return MOSS_ERR_INVALID_ARG
+ * with moss_last_error() set.
+ */
+#define MOSS_LPIPS_VGG_CONVS 13
+#define MOSS_LPIPS_VGG_TAPS 5
+typedef struct moss_lpips_vgg_args {
+    const float* x;                          /* (3,frame_H,frame_W) */
+    const float* y;
+    int32_t H, W;                            /* the crop */
+    int32_t frame_H, frame_W;                /* 0, 0 = H, W */
+    const int* rect;                         /* device ints {x, y, ...} or NULL */
+    const float* weights[MOSS_LPIPS_VGG_CONVS];
+    const float* biases[MOSS_LPIPS_VGG_CONVS];
+    const float* lin[MOSS_LPIPS_VGG_TAPS];
+    const float* shift;
+    const float* scale;
+    float* out;
+    float* terms;                            /* 5 floats, or NULL */
+    char* saved;                             /* moss_lpips_vgg_saved_bytes(H, W), or NULL */
+    char* workspace;
+    size_t workspace_bytes;
+} moss_lpips_vgg_args;
+int moss_lpips_vgg_forward(const moss_lpips_vgg_args* args, void* stream);   /* lpipsPyTorch/modules/lpips.py:31-37 */
+
+typedef struct moss_lpips_vgg_backward_args {
+    int32_t H, W;
+    int32_t frame_H, frame_W;
+    const int* rect;
+    const float* weights_bwd[MOSS_LPIPS_VGG_CONVS];
+    const float* scale;
+    const char* saved;                       /* as the forward wrote it */
+    const float* g_out;                      /* 1 device float */
+    float* dL_dx;                            /* (3,frame_H,frame_W) */
+    char* workspace;
+    size_t workspace_bytes;
+} moss_lpips_vgg_backward_args;
+int moss_lpips_vgg_backward(const moss_lpips_vgg_backward_args* args, void* stream);   /* the adjoint of lpipsPyTorch/modules/lpips.py:31-37 w.r.t. x */
+size_t moss_lpips_vgg_workspace_bytes(int H, int W);  /* scratch of either call; 0 for a size outside the range */
+size_t moss_lpips_vgg_saved_bytes(int H, int W);      /* what the forward keeps for the backward; 0 for a size outside the range */
+/* w (cout,cin,3,3) fp32 -> fwd [cout][tap][cin] and bwd [cin][8 - tap][cout] (cout * cin * 9 floats each): once, the weights are frozen */
+int moss_lpips_vgg_pack_weights(int cin, int cout, const float* w, float* fwd, float* bwd, void* stream);
+
+/*
  * k nearest reference points of every query point, 3-D, exact, k = 1..4: replaces the third-party
  * `knn_cuda.KNN(k, transpose_mode=True)(ref, query)` MOSS calls at scene/gaussian_model.py:85-86,586,657,759,827 (a CUDA-only
  * binary wheel, not in the repository; parity unpinned by the reference).

@@ -111,6 +111,16 @@ def _declare(lib):
     lib.moss_lbs_weight_net_workspace_bytes.argtypes = [_i]
     lib.moss_lbs_weight_net_saved_bytes.restype = C.c_size_t
     lib.moss_lbs_weight_net_saved_bytes.argtypes = [_i]
+    lib.moss_lpips_vgg_forward.restype = _i
+    lib.moss_lpips_vgg_forward.argtypes = [_p, _p]
+    lib.moss_lpips_vgg_backward.restype = _i
+    lib.moss_lpips_vgg_backward.argtypes = [_p, _p]
+    lib.moss_lpips_vgg_workspace_bytes.restype = C.c_size_t
+    lib.moss_lpips_vgg_workspace_bytes.argtypes = [_i, _i]
+    lib.moss_lpips_vgg_saved_bytes.restype = C.c_size_t
+    lib.moss_lpips_vgg_saved_bytes.argtypes = [_i, _i]
+    lib.moss_lpips_vgg_pack_weights.restype = _i
+    lib.moss_lpips_vgg_pack_weights.argtypes = [_i, _i, _p, _p, _p, _p]
     lib.moss_photometric_loss_roi.restype = _i
     lib.moss_photometric_loss_roi.argtypes = [_i, _i, _i, _p, _p, _p, _p, _p, _p, _f, _f, _f, _p, _p, _p, _p, C.c_size_t, _p]
     lib.moss_adamw_flat_ex.restype = _i
@@ -226,6 +236,21 @@ class LbsWeightNetBackwardArgs(C.Structure):
     _fields_ = [("P", C.c_int32), ("Rs", C.c_void_p), ("params", C.c_void_p * 16), ("saved", C.c_void_p), ("g_out", C.c_void_p),
                 ("g_x", C.c_void_p), ("g_Rs", C.c_void_p), ("grads", C.c_void_p * 16), ("workspace", C.c_void_p),
                 ("workspace_bytes", C.c_size_t)]
+
+
+class LpipsVggArgs(C.Structure):
+    """``moss_lpips_vgg_args`` of include/moss_raster.h (``moss_lpips_vgg_forward``: MOSS's LPIPS term, VGG16)."""
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32), ("frame_H", C.c_int32), ("frame_W", C.c_int32),
+                ("rect", C.c_void_p), ("weights", C.c_void_p * 13), ("biases", C.c_void_p * 13), ("lin", C.c_void_p * 5),
+                ("shift", C.c_void_p), ("scale", C.c_void_p), ("out", C.c_void_p), ("terms", C.c_void_p), ("saved", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+class LpipsVggBackwardArgs(C.Structure):
+    """``moss_lpips_vgg_backward_args`` of include/moss_raster.h (``moss_lpips_vgg_backward``)."""
+    _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("frame_H", C.c_int32), ("frame_W", C.c_int32), ("rect", C.c_void_p),
+                ("weights_bwd", C.c_void_p * 13), ("scale", C.c_void_p), ("saved", C.c_void_p), ("g_out", C.c_void_p),
+                ("dL_dx", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
 OPT_BITS = {"means3D": 1, "sh": 2, "opacity": 4, "scales": 8, "rotations": 16}      # MOSS_OPT_*; position = index in the struct's arrays

@@ -43,6 +43,7 @@ SOURCES = {
     "smpl_frame.hip": [],
     "pose_head.hip": [],
     "lbs_weight_net.hip": [],
+    "lpips.hip": [],
     "optim.hip": [],
     "activations.hip": [],
     "densify.hip": [],

@@ -1,0 +1,615 @@
+// lpips.hip -- MOSS's LPIPS term, LPIPS.forward with net_type='vgg' (lpipsPyTorch/modules/lpips.py:31-37, networks.py:49-62,87-95,
+// utils.py:5-7), and its gradient w.r.t. the first image (include/moss_raster.h moss_lpips_vgg_forward / _backward).
+//
+//     z = (img - shift) / scale;  VGG16 features[0:30]: 13 x (conv 3x3 pad 1 + bias + ReLU), a 2x2 max-pool after conv 1_2, 2_2, 3_3, 4_3
+//     tap l (after ReLU 1_2, 2_2, 3_3, 4_3, 5_3):  n = f / (sqrt(sum_c f^2) + 1e-10),  term_l = mean_p sum_c lin_l[c] (nx - ny)^2
+//     out = sum_l term_l
+// The weights are frozen and the second image is the ground truth, so the only gradient is d out / d x, and it needs no layer input:
+// a ReLU passes its gradient where its output was positive (one BIT per activation), a pool where its winner sat (two bits per
+// pooled activation), and the five tap terms enter through d term_l / d fx, which the forward's tap kernel writes itself while it
+// has fx and fy in registers (one tensor per tap, of x's size: the feature maps of y are never kept).
+//
+// Activations are channels-last, both images one batch of two: row m = img * H W + y W + x, C floats per row.
+//   conv3x3_mfma_kernel -- THE convolution, an implicit GEMM (M = rows, N = Cout, K = 9 Cin ordered tap-major) on the f32-input matrix
+//     cores (v_mfma_f32_32x32x2_f32: exact float32, an ordered fmaf chain).  It runs the twelve wide layers forward (epilogue: bias,
+//     ReLU, the sign bits by one ballot per accumulator register) and, on weights flipped and transposed once at construction, their
+//     data gradients (epilogue: the ReLU bits of the layer below, or nothing where a pool follows below).  A workgroup of four waves
+//     stages a 64-deep slice of K -- one tap, 64 consecutive channels: 256 contiguous bytes per row -- of both operands in LDS (row
+//     stride 68 floats = 4 mod 64: the float4 reads of 32 lanes hit 32 different bank groups) while the NEXT slice is already on its
+//     way from L2 into registers; a wave owns a 32 x 64 block (two accumulators share every A read).  Two shapes: 128 rows x 64
+//     channels per workgroup (a wave per 32 rows), and, for the deep layers whose few rows would leave most CUs idle, 32 rows x 64
+//     channels with the four waves splitting every K slice, their partial blocks summed in wave order through LDS.
+//   conv_first_kernel / conv_first_backward_kernel -- conv 1_1 (Cin = 3, K = 27) and its adjoint on the VALU, with the z-score, the
+//     crop offset read from the device and the planar (3,H,W) layout of the public tensors.
+//   pool_kernel, tap_kernel, unpool_tap_kernel, reduce_kernel -- see each.
+// Every sum has a fixed order and there is no atomic: results are bitwise reproducible.  Every element of dL_dx is written.
+#include "common.h"
+
+namespace moss {
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int NCONV = MOSS_LPIPS_VGG_CONVS, NTAP = MOSS_LPIPS_VGG_TAPS;
+constexpr int CONV_COUT[NCONV] = {64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512};
+constexpr int CONV_LEVEL[NCONV] = {0, 0, 1, 1, 2, 2, 2, 3, 3, 3, 4, 4, 4};
+constexpr int TAP_CONV[NTAP] = {1, 3, 6, 9, 12};
+constexpr int TAP_C[NTAP] = {64, 128, 256, 512, 512};
+constexpr int WG = 256;
+constexpr int KC = 64, LD = KC + 4, BN = 64;             // K slice, LDS row stride (floats), output channels per workgroup
+constexpr float NORM_EPS = 1e-10f;
+enum { MODE_FWD, MODE_BWD_MASK, MODE_BWD_PLAIN };
+
+__device__ __forceinline__ int acc_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }   // C/D: col = lane & 31
+
+__device__ __forceinline__ f32x16 splat(float v)
+{
+    f32x16 r;
+#pragma unroll
+    for (int i = 0; i < 16; i++) r[i] = v;
+    return r;
+}
+
+#define MOSS_MFMA4(acc, av, bv)                                                 \
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, acc, 0, 0, 0);       \
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.y, acc, 0, 0, 0);       \
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv.z, acc, 0, 0, 0);       \
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, acc, 0, 0, 0)
+
+// where the crop starts in the frame: the rectangle's corner, moved so that the crop fits
+__device__ __forceinline__ int2 crop_origin(const int* __restrict__ rect, int H, int W, int FH, int FW)
+{
+    int2 o = make_int2(0, 0);
+    if (rect) {
+        o.x = min(max(rect[0], 0), FW - W);
+        o.y = min(max(rect[1], 0), FH - H);
+    }
+    return o;
+}
+
+// ---- the weights, once ---------------------------------------------------------------------------------------------------------------
+// w (Cout,Cin,3,3) -> fwd [Cout][tap][Cin] and bwd [Cin][flipped tap][Cout]: d in[q][ci] = sum d out[q + (ky' - 1, kx' - 1)][co] bwd[ci][ky' kx'][co]
+__global__ void __launch_bounds__(WG)
+pack_weights_kernel(int cin, int cout, const float* __restrict__ w, float* __restrict__ fwd, float* __restrict__ bwd)
+{
+    const int idx = blockIdx.x * WG + threadIdx.x;
+    if (idx >= cout * cin * 9) return;
+    const int tap = idx % 9, i = (idx / 9) % cin, o = idx / (9 * cin);
+    const float v = w[idx];
+    fwd[((size_t)o * 9 + tap) * cin + i] = v;
+    bwd[((size_t)i * 9 + (8 - tap)) * cout + o] = v;
+}
+
+// ---- conv 1_1 --------------------------------------------------------------------------------------------------------------------------
+// Two threads per output row, 32 channels each.  x, y: (3,FH,FW) planes; the crop (H,W) starts at crop_origin.
+__global__ void __launch_bounds__(WG)
+conv_first_kernel(const float* __restrict__ x, const float* __restrict__ y, const int* __restrict__ rect, int FH, int FW, int H, int W,
+                  const float* __restrict__ wf, const float* __restrict__ bias, const float* __restrict__ shift,
+                  const float* __restrict__ scale, float* __restrict__ out, uint32_t* __restrict__ mask)
+{
+    __shared__ __attribute__((aligned(16))) float s_w[27 * 64];          // [k = tap * 3 + c][channel]
+    for (int i = threadIdx.x; i < 27 * 64; i += WG) s_w[(i % 27) * 64 + i / 27] = wf[i];
+    __syncthreads();
+    const int HW = H * W;
+    const int t = blockIdx.x * WG + threadIdx.x, m = t >> 1, g = t & 1;
+    if (m >= 2 * HW) return;
+    const int img = m >= HW, p = m - img * HW, py = p / W, px = p - py * W;
+    const int2 o = crop_origin(rect, H, W, FH, FW);
+    const float* src = img ? y : x;
+    float in[27];
+#pragma unroll
+    for (int tap = 0; tap < 9; tap++) {
+        const int yy = py + tap / 3 - 1, xx = px + tap % 3 - 1;
+        const bool ok = yy >= 0 && yy < H && xx >= 0 && xx < W;
+#pragma unroll
+        for (int c = 0; c < 3; c++)
+            in[tap * 3 + c] = ok ? (src[((size_t)c * FH + o.y + yy) * FW + o.x + xx] - shift[c]) / scale[c] : 0.0f;
+    }
+    float acc[32];
+#pragma unroll
+    for (int i = 0; i < 32; i++) acc[i] = bias[32 * g + i];
+#pragma unroll
+    for (int k = 0; k < 27; k++) {
+#pragma unroll
+        for (int i = 0; i < 32; i += 4) {
+            const float4 wv = *reinterpret_cast<const float4*>(s_w + k * 64 + 32 * g + i);
+            acc[i] = __fmaf_rn(in[k], wv.x, acc[i]);
+            acc[i + 1] = __fmaf_rn(in[k], wv.y, acc[i + 1]);
+            acc[i + 2] = __fmaf_rn(in[k], wv.z, acc[i + 2]);
+            acc[i + 3] = __fmaf_rn(in[k], wv.w, acc[i + 3]);
+        }
+    }
+    uint32_t bits = 0;
+    float* dst = out + (size_t)m * 64 + 32 * g;
+#pragma unroll
+    for (int i = 0; i < 32; i += 4) {
+        float4 v;
+        v.x = fmaxf(acc[i], 0.0f); v.y = fmaxf(acc[i + 1], 0.0f); v.z = fmaxf(acc[i + 2], 0.0f); v.w = fmaxf(acc[i + 3], 0.0f);
+        bits |= (uint32_t)(acc[i] > 0.0f) << i | (uint32_t)(acc[i + 1] > 0.0f) << (i + 1) | (uint32_t)(acc[i + 2] > 0.0f) << (i + 2) |
+                (uint32_t)(acc[i + 3] > 0.0f) << (i + 3);
+        *reinterpret_cast<float4*>(dst + i) = v;
+    }
+    if (mask && img == 0) mask[(size_t)m * 2 + g] = bits;
+}
+
+// d x[c][Y][X] = g / scale[c] * sum_{tap', co} d z[q + tap'][co] wb[c][tap'][co] inside the crop, 0 outside: one thread per FRAME pixel
+__global__ void __launch_bounds__(WG)
+conv_first_backward_kernel(const float* __restrict__ dz, const int* __restrict__ rect, int FH, int FW, int H, int W,
+                           const float* __restrict__ wb, const float* __restrict__ scale, const float* __restrict__ g_out,
+                           float* __restrict__ dx)
+{
+    __shared__ __attribute__((aligned(16))) float s_w[3 * 9 * 64];
+    for (int i = threadIdx.x; i < 3 * 9 * 64; i += WG) s_w[i] = wb[i];
+    __syncthreads();
+    const int t = blockIdx.x * WG + threadIdx.x;
+    if (t >= FH * FW) return;
+    const int Y = t / FW, X = t - Y * FW;
+    const int2 o = crop_origin(rect, H, W, FH, FW);
+    const int py = Y - o.y, px = X - o.x;
+    const bool inside = py >= 0 && py < H && px >= 0 && px < W;
+    float acc[3] = {0.0f, 0.0f, 0.0f};
+    if (inside) {
+        for (int tap = 0; tap < 9; tap++) {
+            const int yy = py + tap / 3 - 1, xx = px + tap % 3 - 1;
+            if (yy < 0 || yy >= H || xx < 0 || xx >= W) continue;
+            const float* row = dz + ((size_t)yy * W + xx) * 64;
+#pragma unroll
+            for (int co = 0; co < 64; co += 4) {
+                const float4 v = *reinterpret_cast<const float4*>(row + co);
+#pragma unroll
+                for (int c = 0; c < 3; c++) {
+                    const float4 wv = *reinterpret_cast<const float4*>(s_w + (c * 9 + tap) * 64 + co);
+                    acc[c] = __fmaf_rn(v.x, wv.x, acc[c]);
+                    acc[c] = __fmaf_rn(v.y, wv.y, acc[c]);
+                    acc[c] = __fmaf_rn(v.z, wv.z, acc[c]);
+                    acc[c] = __fmaf_rn(v.w, wv.w, acc[c]);
+                }
+            }
+        }
+    }
+    const float g = g_out[0];
+#pragma unroll
+    for (int c = 0; c < 3; c++) dx[((size_t)c * FH + Y) * FW + X] = inside ? g * acc[c] / scale[c] : 0.0f;
+}
+
+// ---- the wide convolutions ---------------------------------------------------------------------------------------------------------
+struct ConvArgs {
+    const float* in;           // (M rows, Cin) channels-last; row m = img * H * W + y * W + x
+    const float* w;            // (Cout, 9 Cin): [n][tap][ci]
+    const float* bias;         // MODE_FWD
+    float* out;                // (M, Cout)
+    const uint32_t* mask_in;   // MODE_BWD_MASK: the sign bits of the layer this gradient arrives at, (M, Cout / 32) words
+    uint32_t* mask_out;        // MODE_FWD: where this layer's sign bits go (rows < mask_rows), or null
+    int M, mask_rows, H, W, Cin, Cout;
+};
+
+// WM waves along the rows, WK waves along K (WM * WK = 4)
+template <int WM, int WK, int MODE>
+__global__ void __launch_bounds__(WG)
+conv3x3_mfma_kernel(const ConvArgs a)
+{
+    static_assert(WM * WK == 4 && (WK == 1 || WM == 1), "four waves");
+    constexpr int BM = 32 * WM, A_F4 = BM * (KC / 4) / WG, B_F4 = BN * (KC / 4) / WG;
+    __shared__ __attribute__((aligned(16))) float s_A[BM * LD], s_B[BN * LD];
+    static_assert(BN * LD >= 4 * 32 * 32, "s_B doubles as the buffer of the four partial blocks");
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, half = lane >> 5;
+    const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
+    const int H = a.H, W = a.W, HW = H * W, Cin = a.Cin, Cout = a.Cout, M = a.M;
+    const int K9 = 9 * Cin, nchunks = K9 / KC, mask_rows = a.mask_rows;
+    const float* __restrict__ in = a.in;                                 // (locals: the lambdas below must not take the address of `a`)
+    const float* __restrict__ bias = a.bias;
+    float* __restrict__ out = a.out;
+    const uint32_t* __restrict__ mask_in = a.mask_in;
+    uint32_t* __restrict__ mask_out = a.mask_out;
+
+    // the rows and float4 columns this thread stages: rows r0 + 16 i, column c4
+    const int c4 = tid & 15, r0 = tid >> 4;
+    int rpix[A_F4], ryx[A_F4];
+#pragma unroll
+    for (int i = 0; i < A_F4; i++) {
+        const int m = m0 + r0 + 16 * i;
+        rpix[i] = -1; ryx[i] = 0;
+        if (m < M) {
+            const int p = m % HW, y = p / W;
+            rpix[i] = m; ryx[i] = (y << 16) | (p - y * W);
+        }
+    }
+    const float* wbase = a.w + (size_t)(n0 + r0) * K9 + 4 * c4;
+    f32x4 ra[A_F4], rb[B_F4];
+    auto gload = [&](int kc) __attribute__((always_inline)) {
+        const int k0 = kc * KC, tap = k0 / Cin, ci0 = k0 - tap * Cin, dy = tap / 3 - 1, dx = tap % 3 - 1;
+#pragma unroll
+        for (int i = 0; i < A_F4; i++) {
+            const int yy = (ryx[i] >> 16) + dy, xx = (ryx[i] & 0xffff) + dx;
+            const bool ok = rpix[i] >= 0 && yy >= 0 && yy < H && xx >= 0 && xx < W;
+            ra[i] = ok ? *reinterpret_cast<const f32x4*>(in + (size_t)(rpix[i] + dy * W + dx) * Cin + ci0 + 4 * c4)
+                       : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        }
+#pragma unroll
+        for (int i = 0; i < B_F4; i++) rb[i] = *reinterpret_cast<const f32x4*>(wbase + (size_t)(16 * i) * K9 + k0);
+    };
+    auto sstore = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < A_F4; i++) *reinterpret_cast<f32x4*>(s_A + (r0 + 16 * i) * LD + 4 * c4) = ra[i];
+#pragma unroll
+        for (int i = 0; i < B_F4; i++) *reinterpret_cast<f32x4*>(s_B + (r0 + 16 * i) * LD + 4 * c4) = rb[i];
+    };
+
+    f32x16 acc0 = splat(0.0f), acc1 = splat(0.0f);
+    const float* a_row = s_A + ((WK == 1 ? 32 * wave : 0) + j) * LD + 4 * half;
+    const float* b_row = s_B + j * LD + 4 * half;
+    gload(0);
+    sstore();
+    __syncthreads();
+    for (int kc = 0; kc < nchunks; kc++) {
+        if (kc + 1 < nchunks) gload(kc + 1);                             // in flight during the MFMAs of this slice
+#pragma unroll
+        for (int step = (WK == 1 ? 0 : wave); step < KC / 8; step += WK) {
+            const f32x4 av = *reinterpret_cast<const f32x4*>(a_row + 8 * step);
+            const f32x4 b0 = *reinterpret_cast<const f32x4*>(b_row + 8 * step);
+            const f32x4 b1 = *reinterpret_cast<const f32x4*>(b_row + 32 * LD + 8 * step);
+            MOSS_MFMA4(acc0, av, b0);
+            MOSS_MFMA4(acc1, av, b1);
+        }
+        __syncthreads();
+        if (kc + 1 < nchunks) {
+            sstore();
+            __syncthreads();
+        }
+    }
+
+    // one output element per lane and call; every lane of the wave calls it (the ballot): row m, channel n = 32-aligned base + j
+    auto emit = [&](float v, int m, int n) __attribute__((always_inline)) {
+        const bool valid = m < M;
+        if (MODE == MODE_FWD) {
+            v += bias[n];
+            const bool pos = v > 0.0f;
+            if (valid) out[(size_t)m * Cout + n] = pos ? v : 0.0f;
+            if (mask_out) {
+                const unsigned long long b = __ballot(pos);
+                if (j == 0 && m < mask_rows) mask_out[(size_t)m * (Cout >> 5) + (n >> 5)] = (uint32_t)(half ? b >> 32 : b);
+            }
+        } else if (MODE == MODE_BWD_MASK) {
+            if (valid) {
+                const uint32_t word = mask_in[(size_t)m * (Cout >> 5) + (n >> 5)];
+                out[(size_t)m * Cout + n] = (word >> j) & 1u ? v : 0.0f;
+            }
+        } else {
+            if (valid) out[(size_t)m * Cout + n] = v;
+        }
+    };
+    if (WK == 1) {
+#pragma unroll
+        for (int r = 0; r < 16; r++) emit(acc0[r], m0 + 32 * wave + acc_row(r, half), n0 + j);
+#pragma unroll
+        for (int r = 0; r < 16; r++) emit(acc1[r], m0 + 32 * wave + acc_row(r, half), n0 + 32 + j);
+    } else {
+        // the four partial 32 x 32 blocks through LDS (s_B: every wave is past its last read), summed in wave order
+#pragma unroll
+        for (int b = 0; b < 2; b++) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) s_B[wave * 1024 + acc_row(r, half) * 32 + j] = b ? acc1[r] : acc0[r];
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const int row = (tid >> 5) + 8 * i;                      // (tid >> 5) & 1 == half, tid & 31 == j
+                const float* q = s_B + row * 32 + j;
+                emit(((q[0] + q[1024]) + q[2048]) + q[3072], m0 + row, n0 + 32 * b + j);
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// ---- 2x2 max-pool, stride 2, floor ---------------------------------------------------------------------------------------------------
+// One thread per pooled row and 16 channels.  The winner (first maximum in the order (0,0) (0,1) (1,0) (1,1)), two bits per channel,
+// is kept for the first image when `win` is given: (pooled row, C / 16) words.
+__global__ void __launch_bounds__(WG)
+pool_kernel(const float* __restrict__ in, float* __restrict__ out, uint32_t* __restrict__ win, int nimg, int H, int W, int C)
+{
+    const int Hp = H >> 1, Wp = W >> 1, G = C >> 4;
+    const long long t = (long long)blockIdx.x * WG + threadIdx.x;
+    if (t >= (long long)nimg * Hp * Wp * G) return;
+    const int g = (int)(t % G);
+    const int q = (int)(t / G), img = q / (Hp * Wp), pp = q - img * (Hp * Wp), py = pp / Wp, px = pp - py * Wp;
+    const float* base = in + (((size_t)img * H + 2 * py) * W + 2 * px) * C + 16 * g;
+    float* dst = out + (size_t)q * C + 16 * g;
+    uint32_t word = 0;
+#pragma unroll
+    for (int quad = 0; quad < 4; quad++) {
+        const float4 v0 = *reinterpret_cast<const float4*>(base + 4 * quad);
+        const float4 v1 = *reinterpret_cast<const float4*>(base + C + 4 * quad);
+        const float4 v2 = *reinterpret_cast<const float4*>(base + (size_t)W * C + 4 * quad);
+        const float4 v3 = *reinterpret_cast<const float4*>(base + (size_t)W * C + C + 4 * quad);
+        const float c0[4] = {v0.x, v0.y, v0.z, v0.w}, c1[4] = {v1.x, v1.y, v1.z, v1.w}, c2[4] = {v2.x, v2.y, v2.z, v2.w},
+                    c3[4] = {v3.x, v3.y, v3.z, v3.w};
+        float best[4];
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            uint32_t idx = 0;
+            best[e] = c0[e];
+            if (c1[e] > best[e]) { best[e] = c1[e]; idx = 1; }
+            if (c2[e] > best[e]) { best[e] = c2[e]; idx = 2; }
+            if (c3[e] > best[e]) { best[e] = c3[e]; idx = 3; }
+            word |= idx << (2 * (4 * quad + e));
+        }
+        *reinterpret_cast<float4*>(dst + 4 * quad) = make_float4(best[0], best[1], best[2], best[3]);
+    }
+    if (win && img == 0) win[(size_t)pp * G + g] = word;
+}
+
+__device__ __forceinline__ float wave_sum(float v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);       // (a butterfly: every lane ends with the same bits)
+    return v;
+}
+
+// ---- a tap: one wave per pixel ---------------------------------------------------------------------------------------------------------
+// f: the tapped activations of both images ((2, HW, C): y's follow x's).  partial[p] = sum_c lin[c] (nx - ny)^2; with G also
+// G[p][c] = d term / d fx[p][c] for term = mean_p partial[p]:  a = 2 lin (nx - ny) / HW,  G = a / (s + eps) - fx (a . fx) / (s (s + eps)^2).
+__global__ void __launch_bounds__(WG)
+tap_kernel(const float* __restrict__ f, int HW, int C, const float* __restrict__ lin, float* __restrict__ partial, float* __restrict__ G)
+{
+    const int lane = threadIdx.x & 63, p = blockIdx.x * (WG / 64) + (threadIdx.x >> 6);
+    if (p >= HW) return;
+    const int n = C >> 6;
+    const float* rx = f + (size_t)p * C + lane;
+    const float* ry = rx + (size_t)HW * C;
+    float fx[8], fy[8], w[8], sx2 = 0.0f, sy2 = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        fx[i] = fy[i] = w[i] = 0.0f;
+        if (i < n) {
+            fx[i] = rx[64 * i]; fy[i] = ry[64 * i]; w[i] = lin[lane + 64 * i];
+            sx2 = __fmaf_rn(fx[i], fx[i], sx2);
+            sy2 = __fmaf_rn(fy[i], fy[i], sy2);
+        }
+    }
+    const float sx = sqrtf(wave_sum(sx2)), sy = sqrtf(wave_sum(sy2)), ex = sx + NORM_EPS, ey = sy + NORM_EPS;
+    float av[8], t = 0.0f, dot = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        av[i] = 0.0f;
+        if (i < n) {
+            const float d = fx[i] / ex - fy[i] / ey;
+            t = __fmaf_rn(w[i] * d, d, t);
+            av[i] = 2.0f * w[i] * d / (float)HW;
+            dot = __fmaf_rn(av[i], fx[i], dot);
+        }
+    }
+    t = wave_sum(t);
+    if (lane == 0) partial[p] = t;
+    if (G) {
+        dot = wave_sum(dot);
+        const float k = sx > 0.0f ? dot / (sx * ex * ex) : 0.0f;
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+            if (i < n) G[(size_t)p * C + lane + 64 * i] = av[i] / ex - fx[i] * k;
+    }
+}
+
+struct ReduceArgs { int off[NTAP], cnt[NTAP]; };
+
+// the five spatial means and their sum: one workgroup, float64 sums in a fixed order
+__global__ void __launch_bounds__(1024)
+reduce_kernel(const float* __restrict__ partial, const ReduceArgs r, float* __restrict__ out, float* __restrict__ terms)
+{
+    __shared__ double s[1024];
+    const int tid = threadIdx.x;
+    double total = 0.0;
+    for (int l = 0; l < NTAP; l++) {
+        double v = 0.0;
+        for (int p = tid; p < r.cnt[l]; p += 1024) v += (double)partial[r.off[l] + p];
+        s[tid] = v;
+        __syncthreads();
+        for (int st = 512; st > 0; st >>= 1) {
+            if (tid < st) s[tid] += s[tid + st];
+            __syncthreads();
+        }
+        const double term = s[0] / (double)r.cnt[l];
+        if (tid == 0 && terms) terms[l] = (float)term;
+        total += term;
+        __syncthreads();
+    }
+    if (tid == 0) out[0] = (float)total;
+}
+
+// ---- backward through a tap and the pool above it -----------------------------------------------------------------------------------
+// d z[p][c] = relu bit ? G[p][c] + (the pooled gradient where (p, c) won its 2x2 window) : 0.  One thread per row and 4 channels.
+// dpool null: the last tap, nothing comes from above.
+__global__ void __launch_bounds__(WG)
+unpool_tap_kernel(const float* __restrict__ G, const float* __restrict__ dpool, const uint32_t* __restrict__ win,
+                  const uint32_t* __restrict__ mask, float* __restrict__ out, int H, int W, int C)
+{
+    const int Q = C >> 2;
+    const long long t = (long long)blockIdx.x * WG + threadIdx.x;
+    if (t >= (long long)H * W * Q) return;
+    const int c = 4 * (int)(t % Q), p = (int)(t / Q), y = p / W, x = p - y * W;
+    const float4 g = *reinterpret_cast<const float4*>(G + (size_t)p * C + c);
+    float v[4] = {g.x, g.y, g.z, g.w};
+    const int Hp = H >> 1, Wp = W >> 1;
+    if (dpool && (y >> 1) < Hp && (x >> 1) < Wp) {
+        const int pp = (y >> 1) * Wp + (x >> 1);
+        const uint32_t pos = (uint32_t)((y & 1) * 2 + (x & 1));
+        const uint32_t word = win[(size_t)pp * (C >> 4) + (c >> 4)] >> (2 * (c & 15));
+        const float4 d = *reinterpret_cast<const float4*>(dpool + (size_t)pp * C + c);
+        const float dv[4] = {d.x, d.y, d.z, d.w};
+#pragma unroll
+        for (int e = 0; e < 4; e++)
+            if (((word >> (2 * e)) & 3u) == pos) v[e] += dv[e];
+    }
+    const uint32_t bits = mask[(size_t)p * (C >> 5) + (c >> 5)] >> (c & 31);
+#pragma unroll
+    for (int e = 0; e < 4; e++)
+        if (!((bits >> e) & 1u)) v[e] = 0.0f;
+    *reinterpret_cast<float4*>(out + (size_t)p * C + c) = make_float4(v[0], v[1], v[2], v[3]);
+}
+
+// ---- host ------------------------------------------------------------------------------------------------------------------------------
+struct Geo {
+    int H[NTAP], W[NTAP];
+    size_t mask_off[NCONV], win_off[NTAP - 1], g_off[NTAP], saved_bytes;          // byte offsets into `saved`
+    size_t buf_bytes, partial_off[NTAP], workspace_bytes;                           // partial_off: floats into the partial array
+};
+
+Geo geometry(int H, int W)
+{
+    Geo g{};
+    for (int l = 0; l < NTAP; l++) { g.H[l] = H >> l; g.W[l] = W >> l; }
+    size_t off = 0;
+    for (int i = 0; i < NCONV; i++) {
+        const int l = CONV_LEVEL[i];
+        g.mask_off[i] = off;
+        off += align_up((size_t)g.H[l] * g.W[l] * (CONV_COUT[i] / 32) * sizeof(uint32_t));
+    }
+    for (int l = 0; l + 1 < NTAP; l++) {
+        g.win_off[l] = off;
+        off += align_up((size_t)g.H[l + 1] * g.W[l + 1] * (TAP_C[l] / 16) * sizeof(uint32_t));
+    }
+    for (int l = 0; l < NTAP; l++) {
+        g.g_off[l] = off;
+        off += align_up((size_t)g.H[l] * g.W[l] * TAP_C[l] * sizeof(float));
+    }
+    g.saved_bytes = off;
+    g.buf_bytes = align_up((size_t)2 * H * W * 64 * sizeof(float));                // the largest activation: 64 channels at full size, two images
+    size_t n = 0;
+    for (int l = 0; l < NTAP; l++) { g.partial_off[l] = n; n += (size_t)g.H[l] * g.W[l]; }
+    g.workspace_bytes = 2 * g.buf_bytes + align_up(n * sizeof(float));
+    return g;
+}
+
+bool size_ok(int H, int W) { return H >= 16 && W >= 16 && (long long)H * W <= (1ll << 22); }   // (32-bit element indices: 2 H W 64 < 2^31)
+
+template <int MODE>
+void launch_conv(const ConvArgs& a, hipStream_t s)
+{
+    const int big = (a.M + 127) / 128 * (a.Cout / BN);
+    if (big >= device_cus())
+        hipLaunchKernelGGL((conv3x3_mfma_kernel<4, 1, MODE>), dim3((a.M + 127) / 128, a.Cout / BN), dim3(WG), 0, s, a);
+    else
+        hipLaunchKernelGGL((conv3x3_mfma_kernel<1, 4, MODE>), dim3((a.M + 31) / 32, a.Cout / BN), dim3(WG), 0, s, a);
+}
+
+int grid_for(long long threads) { return (int)((threads + WG - 1) / WG); }
+
+}  // namespace
+
+}  // namespace moss
+
+using namespace moss;
+
+extern "C" size_t moss_lpips_vgg_workspace_bytes(int H, int W) { return size_ok(H, W) ? geometry(H, W).workspace_bytes : 0; }
+
+extern "C" size_t moss_lpips_vgg_saved_bytes(int H, int W) { return size_ok(H, W) ? geometry(H, W).saved_bytes : 0; }
+
+extern "C" int moss_lpips_vgg_pack_weights(int cin, int cout, const float* w, float* fwd, float* bwd, void* stream)
+{
+    if (cin <= 0 || cout <= 0 || !w || !fwd || !bwd) return invalid_arg("moss_lpips_vgg_pack_weights", "sizes <= 0 or a null pointer");
+    hipLaunchKernelGGL(pack_weights_kernel, dim3(grid_for((long long)cin * cout * 9)), dim3(WG), 0, (hipStream_t)stream, cin, cout, w, fwd, bwd);
+    return launch_status("moss_lpips_vgg_pack_weights");
+}
+
+static const char* check_frame(int H, int W, int& FH, int& FW)
+{
+    if (!size_ok(H, W)) return "H and W must be >= 16 (four 2x2 pools) and H * W <= 2^22";
+    if (FH == 0 && FW == 0) { FH = H; FW = W; }
+    if (FH < H || FW < W) return "the frame is smaller than the crop";
+    return nullptr;
+}
+
+// LPIPS.forward, lpipsPyTorch/modules/lpips.py:31-37 (net_type='vgg')
+extern "C" int moss_lpips_vgg_forward(const moss_lpips_vgg_args* a, void* stream)
+{
+    const char* me = "moss_lpips_vgg_forward";
+    if (!a) return invalid_arg(me, "null argument block");
+    int FH = a->frame_H, FW = a->frame_W;
+    if (const char* why = check_frame(a->H, a->W, FH, FW)) return invalid_arg(me, why);
+    if (!a->x || !a->y || !a->out || !a->shift || !a->scale) return invalid_arg(me, "null x, y, out, shift or scale");
+    for (int i = 0; i < NCONV; i++)
+        if (!a->weights[i] || !a->biases[i]) return invalid_arg(me, "null weight or bias (13 of each, packed by moss_lpips_vgg_pack_weights)");
+    for (int l = 0; l < NTAP; l++)
+        if (!a->lin[l]) return invalid_arg(me, "null lin weight (5)");
+    const Geo g = geometry(a->H, a->W);
+    if (!a->workspace || a->workspace_bytes < g.workspace_bytes)
+        return invalid_arg(me, "the workspace is null or smaller than moss_lpips_vgg_workspace_bytes(H, W)");
+    hipStream_t s = (hipStream_t)stream;
+    float* cur = reinterpret_cast<float*>(a->workspace);
+    float* nxt = reinterpret_cast<float*>(a->workspace + g.buf_bytes);
+    float* partial = reinterpret_cast<float*>(a->workspace + 2 * g.buf_bytes);
+    char* sv = a->saved;
+    auto mask_at = [&](int i) { return sv ? reinterpret_cast<uint32_t*>(sv + g.mask_off[i]) : nullptr; };
+
+    const int HW0 = a->H * a->W;
+    hipLaunchKernelGGL(conv_first_kernel, dim3(grid_for(4ll * HW0)), dim3(WG), 0, s, a->x, a->y, a->rect, FH, FW, a->H, a->W,
+                       a->weights[0], a->biases[0], a->shift, a->scale, cur, mask_at(0));
+    int tap = 0;
+    ReduceArgs red{};
+    for (int i = 1; i < NCONV; i++) {
+        const int l = CONV_LEVEL[i], HW = g.H[l] * g.W[l];
+        ConvArgs c{};
+        c.in = cur; c.w = a->weights[i]; c.bias = a->biases[i]; c.out = nxt; c.mask_out = mask_at(i);
+        c.M = 2 * HW; c.mask_rows = HW; c.H = g.H[l]; c.W = g.W[l]; c.Cin = CONV_COUT[i - 1]; c.Cout = CONV_COUT[i];
+        launch_conv<MODE_FWD>(c, s);
+        std::swap(cur, nxt);
+        if (i != TAP_CONV[tap]) continue;
+        const int C = TAP_C[tap];
+        hipLaunchKernelGGL(tap_kernel, dim3((HW + 3) / 4), dim3(WG), 0, s, (const float*)cur, HW, C, a->lin[tap],
+                           partial + g.partial_off[tap], sv ? reinterpret_cast<float*>(sv + g.g_off[tap]) : nullptr);
+        red.off[tap] = (int)g.partial_off[tap];
+        red.cnt[tap] = HW;
+        if (tap + 1 < NTAP) {
+            hipLaunchKernelGGL(pool_kernel, dim3(grid_for(2ll * g.H[l + 1] * g.W[l + 1] * (C / 16))), dim3(WG), 0, s, (const float*)cur, nxt,
+                               sv ? reinterpret_cast<uint32_t*>(sv + g.win_off[tap]) : nullptr, 2, g.H[l], g.W[l], C);
+            std::swap(cur, nxt);
+        }
+        tap++;
+    }
+    hipLaunchKernelGGL(reduce_kernel, dim3(1), dim3(1024), 0, s, (const float*)partial, red, a->out, a->terms);
+    return launch_status(me);
+}
+
+// the adjoint of LPIPS.forward (lpipsPyTorch/modules/lpips.py:31-37) w.r.t. x
+extern "C" int moss_lpips_vgg_backward(const moss_lpips_vgg_backward_args* a, void* stream)
+{
+    const char* me = "moss_lpips_vgg_backward";
+    if (!a) return invalid_arg(me, "null argument block");
+    int FH = a->frame_H, FW = a->frame_W;
+    if (const char* why = check_frame(a->H, a->W, FH, FW)) return invalid_arg(me, why);
+    if (!a->saved || !a->g_out || !a->dL_dx || !a->scale) return invalid_arg(me, "null saved (the forward's), g_out, dL_dx or scale");
+    for (int i = 0; i < NCONV; i++)
+        if (!a->weights_bwd[i]) return invalid_arg(me, "null backward weight (13, packed by moss_lpips_vgg_pack_weights)");
+    const Geo g = geometry(a->H, a->W);
+    if (!a->workspace || a->workspace_bytes < g.workspace_bytes)
+        return invalid_arg(me, "the workspace is null or smaller than moss_lpips_vgg_workspace_bytes(H, W)");
+    hipStream_t s = (hipStream_t)stream;
+    float* cur = reinterpret_cast<float*>(a->workspace);
+    float* nxt = reinterpret_cast<float*>(a->workspace + g.buf_bytes);
+    const char* sv = a->saved;
+    auto mask_at = [&](int i) { return reinterpret_cast<const uint32_t*>(sv + g.mask_off[i]); };
+
+    // `cur` holds d z (the gradient w.r.t. the pre-activation) of convolution i at the top of each round
+    const float* from_above = nullptr;
+    for (int i = NCONV - 1; i >= 1; i--) {
+        const int l = CONV_LEVEL[i];
+        if (i == TAP_CONV[l]) {
+            hipLaunchKernelGGL(unpool_tap_kernel, dim3(grid_for((long long)g.H[l] * g.W[l] * (TAP_C[l] / 4))), dim3(WG), 0, s,
+                               reinterpret_cast<const float*>(sv + g.g_off[l]), from_above,
+                               from_above ? reinterpret_cast<const uint32_t*>(sv + g.win_off[l]) : nullptr, mask_at(i), nxt, g.H[l], g.W[l],
+                               TAP_C[l]);
+            std::swap(cur, nxt);
+        }
+        const bool pooled_below = CONV_LEVEL[i - 1] != l;                // the input of convolution i is a pool's output
+        ConvArgs c{};
+        c.in = cur; c.w = a->weights_bwd[i]; c.out = nxt; c.mask_in = pooled_below ? nullptr : mask_at(i - 1);
+        c.M = g.H[l] * g.W[l]; c.H = g.H[l]; c.W = g.W[l]; c.Cin = CONV_COUT[i]; c.Cout = CONV_COUT[i - 1];
+        if (pooled_below) launch_conv<MODE_BWD_PLAIN>(c, s); else launch_conv<MODE_BWD_MASK>(c, s);
+        std::swap(cur, nxt);
+        from_above = pooled_below ? cur : nullptr;
+    }
+    hipLaunchKernelGGL(conv_first_backward_kernel, dim3(grid_for((long long)FH * FW)), dim3(WG), 0, s, (const float*)cur, a->rect, FH, FW,
+                       a->H, a->W, a->weights_bwd[0], a->scale, a->g_out, a->dL_dx);
+    return launch_status(me);
+}

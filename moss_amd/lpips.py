@@ -1,0 +1,312 @@
+"""MOSS's LPIPS term (``loss_fn_vgg(img_pred, img_gt)``, train_ZJU.py:121 and :256; lpipsPyTorch/modules/lpips.py:31-37 with
+``net_type='vgg'``) on the device.
+
+A frozen VGG16 (``features[0:30]``: 13 convolutions 3x3 with bias and ReLU, four 2x2 max-pools) is run on both images, the
+activations after ReLU 1_2, 2_2, 3_3, 4_3 and 5_3 are normalised per pixel over the channels, and per tap the squared difference goes
+through a non-trainable 1x1 convolution to one channel and a spatial mean; the five numbers are summed.  Here:
+
+* :class:`LpipsVGG` -- the frozen weights in the two layouts the kernels read (packed once: forward, and flipped / transposed for the
+  data gradient), built from tensors (:meth:`LpipsVGG.from_tensors`) or from the caller's module (:meth:`LpipsVGG.from_module`).
+* :func:`lpips_vgg_fused` -- the term as HIP kernels (C ABI ``moss_lpips_vgg_forward`` / ``_backward``, moss_amd/csrc/lpips.hip): both
+  images as one batch of two, every wide convolution on the f32-input matrix cores in exact float32, gradient to ``x`` only.  The
+  backward reads sign masks, pool winners and the tap gradients the forward left, never a layer input.  No host read, no atomics,
+  bitwise reproducible, capturable.
+* :func:`lpips_vgg_roi_fused` -- the same on the ``ViewRegion`` rectangle of two full frames (no crop copies; the offset is read on the
+  device).
+* :func:`lpips_vgg_torch` -- the same mathematics in plain torch (any dtype or device): the yardstick of the tests and of
+  scripts/lpips_times.py.  Not a fallback: the fused op has no CPU path.
+* :func:`synthetic_weights` -- VGG16-shaped weights from a seed (a frozen ``numpy.random.RandomState`` stream), for tests, the timing
+  script and callers without the 59 MB of pretrained weights.
+
+Everything here imports without a GPU.
+"""
+from __future__ import annotations
+
+import ctypes
+import hashlib
+
+import torch
+
+__all__ = ["LpipsVGG", "lpips_vgg_fused", "lpips_vgg_roi_fused", "lpips_vgg_torch", "synthetic_weights", "weights_sha256",
+           "CONV_SHAPES", "TAP_CHANNELS", "TAP_AFTER_CONV", "POOL_AFTER_CONV", "SHIFT", "SCALE", "MIN_SIZE"]
+
+_WIDTHS = (64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512)
+CONV_SHAPES = tuple((co, ci, 3, 3) for ci, co in zip((3,) + _WIDTHS[:-1], _WIDTHS))
+POOL_AFTER_CONV = (1, 3, 6, 9)                            # a 2x2 max-pool follows the ReLU of these convolutions (0-based)
+TAP_AFTER_CONV = (1, 3, 6, 9, 12)                         # ReLU 1_2, 2_2, 3_3, 4_3, 5_3: target_layers = [4, 9, 16, 23, 30]
+TAP_CHANNELS = (64, 128, 256, 512, 512)
+SHIFT = (-0.030, -0.088, -0.188)                          # BaseNet.mean (lpipsPyTorch/modules/networks.py:40-43)
+SCALE = (0.458, 0.448, 0.450)                             # BaseNet.std
+MIN_SIZE = 16                                             # four pools: the last tap is at least 1x1
+EPS = 1e-10                                               # normalize_activation (lpipsPyTorch/modules/utils.py:5-7)
+
+
+# ---- the torch form ---------------------------------------------------------------------------------------------------------------
+
+def lpips_vgg_torch(params, x, y, return_terms=False):
+    """``LPIPS.forward(x, y)`` for ``net_type='vgg'`` in plain torch.  ``params``: a mapping with ``conv_weights`` (13 tensors
+    (Cout,Cin,3,3)), ``conv_biases`` (13), ``lin_weights`` (5 tensors of C, any shape), ``shift`` and ``scale`` (3 each), all of the
+    images' dtype and device; ``x``, ``y`` (3,H,W) or (1,3,H,W).  Returns (1,1,1,1); with ``return_terms`` also the five per-tap
+    terms as a (5,) tensor."""
+    import torch.nn.functional as F
+    shift = params["shift"].reshape(1, 3, 1, 1)
+    scale = params["scale"].reshape(1, 3, 1, 1)
+
+    def features(img):
+        h = (img.reshape(1, 3, img.shape[-2], img.shape[-1]) - shift) / scale
+        taps = []
+        for i, (w, b) in enumerate(zip(params["conv_weights"], params["conv_biases"])):
+            h = torch.relu(F.conv2d(h, w, b, padding=1))
+            if i in TAP_AFTER_CONV:
+                taps.append(h / (torch.sqrt(torch.sum(h ** 2, dim=1, keepdim=True)) + EPS))
+            if i in POOL_AFTER_CONV:
+                h = F.max_pool2d(h, 2, 2)
+        return taps
+
+    fx, fy = features(x), features(y)
+    terms = [F.conv2d((a - b) ** 2, lw.reshape(1, -1, 1, 1)).mean((2, 3), True) for a, b, lw in zip(fx, fy, params["lin_weights"])]
+    total = torch.sum(torch.cat(terms, 0), 0, True)
+    return (total, torch.cat(terms, 0).reshape(5)) if return_terms else total
+
+
+def synthetic_weights(seed=0):
+    """VGG16-shaped LPIPS weights from ``numpy.random.RandomState(seed)``, drawn in this order: per convolution the weight (He-normal,
+    std ``sqrt(2 / (9 Cin))``) then the bias (0.05 x normal); then per tap the lin weight (``|normal| / C``).  float32 CPU tensors in
+    the mapping :func:`lpips_vgg_torch` takes."""
+    import numpy as np
+    rs = np.random.RandomState(seed)
+    cw, cb, lw = [], [], []
+    for co, ci, _, _ in CONV_SHAPES:
+        cw.append(torch.from_numpy((rs.standard_normal((co, ci, 3, 3)) * np.sqrt(2.0 / (9 * ci))).astype(np.float32)))
+        cb.append(torch.from_numpy((0.05 * rs.standard_normal(co)).astype(np.float32)))
+    for c in TAP_CHANNELS:
+        lw.append(torch.from_numpy((np.abs(rs.standard_normal(c)) / c).astype(np.float32)))
+    return {"conv_weights": cw, "conv_biases": cb, "lin_weights": lw, "shift": torch.tensor(SHIFT, dtype=torch.float32),
+            "scale": torch.tensor(SCALE, dtype=torch.float32)}
+
+
+def weights_sha256(params):
+    """SHA-256 over the float32 bytes of the convolution weights and biases (interleaved, in layer order) and the lin weights."""
+    h = hashlib.sha256()
+    for w, b in zip(params["conv_weights"], params["conv_biases"]):
+        h.update(w.detach().float().cpu().contiguous().numpy().tobytes())
+        h.update(b.detach().float().cpu().contiguous().numpy().tobytes())
+    for w in params["lin_weights"]:
+        h.update(w.detach().float().cpu().contiguous().numpy().tobytes())
+    return h.hexdigest()
+
+
+def cast_params(params, dtype=None, device=None):
+    """The mapping of :func:`lpips_vgg_torch` with every tensor in another dtype / on another device."""
+    conv = lambda t: t.to(dtype=dtype, device=device)
+    return {k: ([conv(t) for t in v] if isinstance(v, (list, tuple)) else conv(v)) for k, v in params.items()}
+
+
+# ---- the frozen network as the kernels read it ---------------------------------------------------------------------------------------
+
+def _is_conv(m, k):
+    w = getattr(m, "weight", None)
+    return isinstance(w, torch.Tensor) and w.dim() == 4 and tuple(w.shape[2:]) == (k, k)
+
+
+class LpipsVGG:
+    """The frozen LPIPS-VGG16 weights on a GPU, packed once into the two layouts of moss_amd/csrc/lpips.hip: per convolution
+    ``[Cout][tap][Cin]`` for the forward and ``[Cin][flipped tap][Cout]`` for the data gradient.  The packed copies are this object's
+    own; the tensors or the module they came from are only read (:meth:`refresh` reads them again)."""
+
+    def __init__(self, conv_weights, conv_biases, lin_weights, shift, scale):
+        self._src = (list(conv_weights), list(conv_biases), list(lin_weights), shift, scale)
+        cw, cb, lw = self._src[:3]
+        if len(cw) != 13 or len(cb) != 13 or len(lw) != 5:
+            raise ValueError(f"LpipsVGG: expected 13 convolution weights, 13 biases and 5 lin weights, got {len(cw)}, {len(cb)}, {len(lw)}")
+        for i, (w, b, shape) in enumerate(zip(cw, cb, CONV_SHAPES)):
+            if tuple(w.shape) != shape or tuple(b.shape) != shape[:1]:
+                raise ValueError(f"LpipsVGG: convolution {i} must have weight {shape} and bias {shape[:1]}, got {tuple(w.shape)} and "
+                                 f"{tuple(b.shape)} (VGG16 features[0:30])")
+        for i, (w, c) in enumerate(zip(lw, TAP_CHANNELS)):
+            if w.numel() != c or (w.dim() == 4 and tuple(w.shape) != (1, c, 1, 1)):
+                raise ValueError(f"LpipsVGG: lin weight {i} must hold {c} values ((1,{c},1,1)), got {tuple(w.shape)}")
+        if shift.numel() != 3 or scale.numel() != 3:
+            raise ValueError("LpipsVGG: shift and scale must hold three values each")
+        self.device = cw[0].device
+        if self.device.type != "cuda":
+            raise RuntimeError("LpipsVGG holds the weights of the HIP kernels: the tensors must be on a GPU (lpips_vgg_torch is the "
+                               "torch form)")
+        for t in cw + cb + lw + [shift, scale]:
+            if t.device != self.device:
+                raise ValueError(f"LpipsVGG: every tensor must be on {self.device}, got one on {t.device}")
+        self.refresh()
+
+    @classmethod
+    def from_tensors(cls, conv_weights, conv_biases, lin_weights, shift, scale):
+        """13 weights (Cout,Cin,3,3), 13 biases, 5 lin weights ((1,C,1,1) or (C,)), shift and scale (3 values each), on one GPU."""
+        return cls(conv_weights, conv_biases, lin_weights, shift, scale)
+
+    @classmethod
+    def from_module(cls, module):
+        """An :class:`LpipsVGG` of the weights :meth:`find_tensors` finds in the caller's module.  The module stays the caller's: it is
+        only read, its ``state_dict`` and checkpoints are untouched."""
+        return cls(*cls.find_tensors(module))
+
+    @staticmethod
+    def find_tensors(module):
+        """``(conv_weights, conv_biases, lin_weights, shift, scale)`` of the caller's LPIPS module.  Finds the weights in the caller's LPIPS module by duck typing, in module order: the 13 convolutions 3x3 and the shift / scale
+        buffers under ``module.net`` (``.net.mean`` / ``.net.std`` -- the layout of lpipsPyTorch.LPIPS: ``.net.layers``, ``.lin[i][1]``)
+        or under ``module.scaling_layer`` (``.shift`` / ``.scale`` -- the layout of the pip package's ``lpips.LPIPS(net='vgg')``:
+        ``.net.slice1..5``, ``.lin0..4.model[-1]``), and the five convolutions 1x1 anywhere else in the module.  The pip package is
+        not available where this project is tested, so only the first layout is exercised by the tests; the second follows the
+        package's published attribute names.  Anything that is not exactly 13 + 5 convolutions of the expected shapes raises."""
+        net = getattr(module, "net", None)
+        if net is None or not hasattr(net, "modules"):
+            raise ValueError("LpipsVGG.from_module: the module has no .net (expected lpipsPyTorch.LPIPS or lpips.LPIPS(net='vgg'))")
+        convs = [m for m in net.modules() if _is_conv(m, 3)]
+        inside = set(id(m) for m in net.modules())
+        lins = [m for m in module.modules() if _is_conv(m, 1) and id(m) not in inside]
+        if len(convs) != 13 or len(lins) != 5:
+            raise ValueError(f"LpipsVGG.from_module: found {len(convs)} convolutions 3x3 under .net and {len(lins)} convolutions 1x1 "
+                             "outside it; the VGG16 variant of LPIPS has exactly 13 and 5")
+        if any(m.bias is None for m in convs) or any(m.bias is not None for m in lins):
+            raise ValueError("LpipsVGG.from_module: the 3x3 convolutions need a bias and the lin layers must have none")
+        if hasattr(net, "mean") and hasattr(net, "std"):
+            shift, scale = net.mean, net.std
+        elif hasattr(module, "scaling_layer") and hasattr(module.scaling_layer, "shift") and hasattr(module.scaling_layer, "scale"):
+            shift, scale = module.scaling_layer.shift, module.scaling_layer.scale
+        else:
+            raise ValueError("LpipsVGG.from_module: neither .net.mean / .net.std nor .scaling_layer.shift / .scale")
+        return [m.weight for m in convs], [m.bias for m in convs], [m.weight for m in lins], shift, scale
+
+    def refresh(self):
+        """Pack the source tensors again (a caller who reloaded its weights)."""
+        from ._lib import call
+        cw, cb, lw, shift, scale = self._src
+        f32 = lambda t: t.detach().to(torch.float32).contiguous()
+        self.biases = [f32(b).clone() for b in cb]
+        self.lin = [f32(w).reshape(-1).clone() for w in lw]
+        self.shift, self.scale = f32(shift).reshape(3).clone(), f32(scale).reshape(3).clone()
+        self.w_fwd, self.w_bwd = [], []
+        for i, w in enumerate(cw):
+            w = f32(w)
+            co, ci = int(w.shape[0]), int(w.shape[1])
+            fwd = torch.empty(w.numel(), dtype=torch.float32, device=self.device)
+            bwd = torch.empty(w.numel(), dtype=torch.float32, device=self.device)
+            call("moss_lpips_vgg_pack_weights", self.device, ci, co, w.data_ptr(), fwd.data_ptr(), bwd.data_ptr())
+            self.w_fwd.append(fwd)
+            self.w_bwd.append(bwd)
+        return self
+
+    def params(self):
+        """The source tensors as the mapping :func:`lpips_vgg_torch` takes (not copies)."""
+        cw, cb, lw, shift, scale = self._src
+        return {"conv_weights": cw, "conv_biases": cb, "lin_weights": lw, "shift": shift, "scale": scale}
+
+
+# ---- the fused op -----------------------------------------------------------------------------------------------------------------
+
+def _fill_common(a, net, h, w, frame, rect):
+    a.H, a.W = h, w
+    a.frame_H, a.frame_W = frame
+    a.rect = None if rect is None else rect.data_ptr()
+
+
+class _LpipsVGG(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, net, crop, rect):
+        from ._lib import LpipsVggArgs, call, lib
+        dev = x.device
+        FH, FW = int(x.shape[-2]), int(x.shape[-1])
+        h, w = (FH, FW) if crop is None else crop
+        keep = ctx.needs_input_grad[0]
+        L = lib()
+        out = torch.empty((1, 1, 1, 1), dtype=torch.float32, device=dev)
+        terms = torch.empty(5, dtype=torch.float32, device=dev)
+        nbytes = int(L.moss_lpips_vgg_workspace_bytes(FH, FW))                        # (sized for the frame: any crop of it fits)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        saved = torch.empty(int(L.moss_lpips_vgg_saved_bytes(h, w)) if keep else 0, dtype=torch.uint8, device=dev)
+        a = LpipsVggArgs()
+        a.x, a.y = x.data_ptr(), y.data_ptr()
+        _fill_common(a, net, h, w, (FH, FW), rect)
+        for i in range(13):
+            a.weights[i], a.biases[i] = net.w_fwd[i].data_ptr(), net.biases[i].data_ptr()
+        for i in range(5):
+            a.lin[i] = net.lin[i].data_ptr()
+        a.shift, a.scale = net.shift.data_ptr(), net.scale.data_ptr()
+        a.out, a.terms = out.data_ptr(), terms.data_ptr()
+        a.saved = saved.data_ptr() if keep else None
+        a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+        call("moss_lpips_vgg_forward", dev, ctypes.byref(a))
+        ctx.net, ctx.crop, ctx.frame = net, (h, w), (FH, FW)
+        ctx.save_for_backward(saved, rect if rect is not None else torch.empty(0, dtype=torch.int32, device=dev))
+        ctx.mark_non_differentiable(terms)
+        return out, terms
+
+    @staticmethod
+    def backward(ctx, g_out, _g_terms):
+        from ._lib import LpipsVggBackwardArgs, call, lib
+        saved, rect = ctx.saved_tensors
+        net, (h, w), (FH, FW) = ctx.net, ctx.crop, ctx.frame
+        dev = saved.device
+        g = g_out.reshape(1).to(torch.float32).contiguous()
+        d_x = torch.empty((3, FH, FW), dtype=torch.float32, device=dev)             # every element is written by the kernels
+        nbytes = int(lib().moss_lpips_vgg_workspace_bytes(FH, FW))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        a = LpipsVggBackwardArgs()
+        _fill_common(a, net, h, w, (FH, FW), rect if rect.numel() else None)
+        for i in range(13):
+            a.weights_bwd[i] = net.w_bwd[i].data_ptr()
+        a.scale, a.saved, a.g_out, a.dL_dx = net.scale.data_ptr(), saved.data_ptr(), g.data_ptr(), d_x.data_ptr()
+        a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+        call("moss_lpips_vgg_backward", dev, ctypes.byref(a))
+        return d_x, None, None, None, None
+
+
+def _check_images(what, net, x, y):
+    if not isinstance(net, LpipsVGG):
+        raise TypeError(f"{what}: net must be an LpipsVGG (LpipsVGG.from_tensors / from_module), got {type(net).__name__}")
+    for name, t in (("x", x), ("y", y)):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise RuntimeError(f"{what} runs the HIP kernels of the LPIPS term: {name} must be a tensor on a GPU (lpips_vgg_torch is "
+                               "the torch form)")
+        if t.dtype != torch.float32 or t.device != net.device:
+            raise ValueError(f"{what}: {name} must be float32 on {net.device}, got {t.dtype} on {t.device}")
+        if t.dim() == 4 and t.shape[0] != 1:
+            raise ValueError(f"{what}: the batch must be 1, got {tuple(t.shape)}")
+        if t.dim() not in (3, 4) or t.shape[-3] != 3:
+            raise ValueError(f"{what}: {name} must be (3,H,W) or (1,3,H,W), got {tuple(t.shape)}")
+    if x.shape[-2:] != y.shape[-2:]:
+        raise ValueError(f"{what}: the two images differ in size: {tuple(x.shape)} and {tuple(y.shape)}")
+    if y.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError(f"{what}: y is the ground truth and gets no gradient; detach it")
+
+
+def _apply(net, x, y, crop, rect, return_terms):
+    shape = x.shape
+    x3 = x.reshape(3, shape[-2], shape[-1]).contiguous()
+    y3 = y.detach().reshape(3, shape[-2], shape[-1]).contiguous()
+    value, terms = _LpipsVGG.apply(x3, y3, net, crop, rect)
+    return (value, terms) if return_terms else value
+
+
+def lpips_vgg_fused(net, x, y, return_terms=False):
+    """MOSS's ``loss_fn_vgg(x, y)`` as the fused HIP op.  ``net``: an :class:`LpipsVGG`; ``x``, ``y``: (3,H,W) or (1,3,H,W) float32 on
+    the GPU, H, W >= 16.  Returns (1,1,1,1) float32 (with ``return_terms`` also the five per-tap terms, no gradient).  The gradient
+    goes to ``x`` only; a ``y`` that requires grad raises.  Under ``torch.no_grad()``, or when ``x`` needs no gradient, the forward
+    keeps nothing."""
+    _check_images("lpips_vgg_fused", net, x, y)
+    if min(x.shape[-2:]) < MIN_SIZE:
+        raise ValueError(f"lpips_vgg_fused: H and W must be >= {MIN_SIZE} (four 2x2 pools), got {tuple(x.shape[-2:])}")
+    return _apply(net, x, y, None, None, return_terms)
+
+
+def lpips_vgg_roi_fused(net, image, gt_image, region, return_terms=False):
+    """``loss_fn_vgg(image[:, y:y+h, x:x+w], gt_image[...])`` for ``(x, y, w, h) = region.xywh`` (train_ZJU.py:115-121) on the FULL
+    frames: the crop's size is the region's, its offset is read from ``region.rect`` on the device -- no host read, no crop copies --
+    and the gradient is written for the whole ``image`` (zero off the crop).  Capturable; a replay changes view by ``region.copy_``
+    among views of one crop size."""
+    _check_images("lpips_vgg_roi_fused", net, image, gt_image)
+    H, W = image.shape[-2:]
+    if tuple(region.bound.shape) != (H, W) or region.rect.device != image.device:
+        raise RuntimeError("lpips_vgg_roi_fused: the view's region does not belong to this image")
+    _, _, w, h = region.xywh
+    if min(h, w) < MIN_SIZE or h > H or w > W:
+        raise ValueError(f"lpips_vgg_roi_fused: the crop must be at least {MIN_SIZE}x{MIN_SIZE} and fit the frame, got {h}x{w}")
+    return _apply(net, image, gt_image, (int(h), int(w)), region.rect, return_terms)

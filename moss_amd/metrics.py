@@ -14,8 +14,8 @@ again in render_ZJU.py; per view (train_ZJU.py:244-253):
 :func:`quality_torch` is that composition in torch (CPU or GPU, any float dtype).  :class:`QualityReport` computes the same three
 numbers with two HIP kernels for up to eight views per launch (C ABI ``moss_eval_metrics``) and keeps the float64 sums on the device:
 ``add`` / ``add_many`` only queue work (no host read, no allocation: capturable in a hipGraph); ``means()`` reads once.
-:func:`evaluate_views` drives a whole split.  LPIPS (pretrained VGG weights) stays the caller's: ``out_image`` receives the clamped
-and filled render it is computed on.
+:func:`evaluate_views` drives a whole split; with ``lpips=`` (a :class:`moss_amd.lpips.LpipsVGG` of the caller's pretrained weights) it
+adds the per-view LPIPS from the fused op, else ``out_image`` receives the clamped and filled render a caller's own LPIPS runs on.
 """
 from __future__ import annotations
 
@@ -143,18 +143,25 @@ class QualityReport:
         return self._per_view[:min(n, self.per_view_capacity)].cpu()
 
 
-def evaluate_views(pc, cameras, gts, regions, bg, transforms=None, translation=None, lpips_fn=None):
+def evaluate_views(pc, cameras, gts, regions, bg, transforms=None, translation=None, lpips_fn=None, lpips=None):
     """MOSS's ``training_report`` over one split (train_ZJU.py:238-262), the metric part on the device: every view rendered with
     ``render()`` under ``torch.no_grad()`` (the forward-only path), its L1 / PSNR / SSIM added to a :class:`QualityReport`, and -- with
     ``lpips_fn`` -- ``lpips_fn(image, gt_image)`` on the clamped and filled render and the clamped ground truth, accumulated in float64
     on the device.  ``gts``: (3,H,W) float32 images; ``regions``: a :class:`moss_amd.loss.ViewRegion` per view or None (no fill);
     ``transforms`` / ``translation``: one LBS table for all views or a list.  No host read inside the loop; one at the end.
-    Returns ``{"l1", "psnr", "ssim", "lpips", "n"}``: the reference's four set means (``lpips`` None without ``lpips_fn``)."""
+    ``lpips``: a :class:`moss_amd.lpips.LpipsVGG` instead of ``lpips_fn`` -- the term from the fused HIP op
+    (:func:`moss_amd.lpips.lpips_vgg_fused`, its forward that keeps nothing), summed in float64 in view order like the others.
+    Returns ``{"l1", "psnr", "ssim", "lpips", "n"}``: the reference's four set means (``lpips`` None without ``lpips_fn`` / ``lpips``)."""
     from types import SimpleNamespace
 
     from .diff_gaussian_rasterization import RasterContext
     from .diff_gaussian_rasterization._C import CapacityOverflow
     from .gaussian_renderer import render
+    if lpips is not None:
+        if lpips_fn is not None:
+            raise ValueError("evaluate_views: give lpips_fn or lpips, not both")
+        from .lpips import lpips_vgg_fused
+        lpips_fn = lambda image, gt: lpips_vgg_fused(lpips, image, gt)      # noqa: E731
     cameras, gts = list(cameras), list(gts)
     n = len(cameras)
     regions = list(regions) if regions is not None else [None] * n
