@@ -783,6 +783,109 @@ int moss_neighbour_kl(int P, int Nsrc, const float* xyz, const float* rotation, 
                       const long long* pair_idx, float* kl_out, void* stream);
 
 /*
+ * The KL densify-and-prune DECISION of MOSS (GaussianModel.densify_and_prune, scene/gaussian_model.py:621-666, and the three phase
+ * functions it calls: kl_densify_and_clone :495-526, kl_densify_and_split :528-571, kl_merge :573-619), additive in ABI 7.  The
+ * surface-change test of the clone (:503-507) is an INPUT (surface_mask).  All tensors fp32 and contiguous unless said otherwise; every
+ * entry point enqueues on `stream`, allocates nothing and reads nothing back on the host.  Bad arguments (a NULL required pointer, a
+ * negative size, a short workspace, an unknown mode) return MOSS_ERR_INVALID_ARG with moss_last_error() set and launch nothing.
+ *
+ * moss_densify_joint_table (:624-640): ONE launch, one lane per joint.  F_j = joint_F_sum[j] / denom[0] (denom[0] is read on the
+ *   device), its 3x3 SVD (one-sided Jacobi, csrc/pose_math.h), the sign rule U[:,2] *= det U, V[:,2] *= det V (:628-633), rot = U V^T.
+ *   table (24,12): row 0 is twelve ONES (torch.ones(1,3,3) and torch.ones(1,3) at :637,640 -- not the identity); row j+1 holds the
+ *   nine floats of rot_j row-major and the three singular values in descending order.  A joint whose F has a non-finite element
+ *   (denom[0] == 0) gets twelve NaNs.
+ *
+ * moss_densify_select: the selection mask of one phase, its ascending index list and its count.
+ *   grad_i = xyz_gradient_accum[i] / denom[i] with NaN -> 0 (:622,642) for i < n_grads and 0 beyond (the zero padding of :540-541);
+ *   smax_i = max_k exp(scaling[i,k]);  KL_i = kl_div of Gaussian ids[i,0] against ids[i,1] (moss_neighbour_kl's arithmetic on
+ *   exp(scaling)); an index of ids outside [0,P) unselects i (its KL is NaN).
+ *   MOSS_DENSIFY_CLONE (:499-509): |grad| >= max_grad && smax <= scale_limit && KL > kl_threshold && surface_mask[i] (NULL = all set)
+ *   MOSS_DENSIFY_SPLIT (:540-549):  grad  >= max_grad && smax >  scale_limit && KL > kl_threshold
+ *   MOSS_DENSIFY_MERGE (:579-602):  grad  >= max_grad && smax <= scale_limit && KL < kl_threshold
+ *   MOSS_DENSIFY_PRUNE (:650-662): sigmoid(opacity[i]) < min_opacity || (use_screen_size && (max_radii2D[i] > max_screen_size ||
+ *     smax > world_scale_limit)) || vertex_dist[i] > vertex_dist_limit      (vertex_dist: the k = 1 query against the SMPL vertices)
+ *   scale_limit = percent_dense * extent, world_scale_limit = 0.1 * extent: formed by the caller.
+ *   mask (P) bytes 0/1; index (>= count) int32: the selected i in ASCENDING order (the row order of boolean indexing), entries beyond
+ *   the count untouched, may be NULL; count: one device int32; count_host: one int32 of PINNED host memory that receives the count by
+ *   an asynchronous copy on `stream` (may be NULL) -- the caller's single host read per phase; kl_out (P), may be NULL: KL_i, bit
+ *   for bit what moss_neighbour_kl returns for the scales THIS library activates (the device expf of its kernels: what
+ *   moss_gaussian_activate_forward writes as out_scaling); nothing is promised about another library's exp.
+ *   The KL is computed by moss_neighbour_kl's OWN kernel on exp(scaling) (one launch to activate the scales, one for the KL):
+ *   the same machine code, so the same bits.  Then the ordered compaction in TWO launches: flags + per-workgroup totals (wave
+ *   ballots, an LDS sum), then the offsets (each workgroup sums the totals before it -- integers, no atomic) and the ranks (ballot +
+ *   popcount in the wave, wave totals through LDS).  Bitwise reproducible.  PRUNE: the two compaction launches only.
+ *   workspace: moss_densify_select_workspace_bytes(P) bytes (per-workgroup totals, activated scales, the KL); PRUNE needs only the
+ *   first 4 * ceil(P / 256) of them, the totals.
+ *
+ * moss_densify_emit: the new rows of one phase from the index list (n_sel = the count the caller read).  Features: features_dc /
+ *   features_rest point at the 3 / rest_floats floats of a row, rows dc_stride / rest_stride floats apart (two tensors: 3 and
+ *   rest_floats; views of one (P,16,3) tensor: 48 and 48); copies run with the lanes along a row's 3 + rest_floats floats.
+ *   R(q) = build_rotation (utils/general_utils.py:79-100); noise (n_new,3): standard normal draws, row r uses noise[r]
+ *   (torch.normal(mean, std) = mean + std * noise).
+ *   CLONE (:511-524), n_new = n_sel, i = index[r]:  w = lbs_weights[i,:] / denom[0] (24);  rot_joint = w . table[:, :9],
+ *     scl_joint = w . table[:, 9:] (the table is held in LDS; nothing of size (P,3,3) exists);  std = scl_joint * exp(scaling[i]);
+ *     new_xyz = (rot_joint R(q_i)) (std * noise[r]) + xyz[i];  new_scaling = log(exp(scaling[i]) * scl_joint);
+ *     new_rotation = matrix_to_quaternion(rot_joint) * rotation[i] ELEMENTWISE (what :520 computes); matrix_to_quaternion as in
+ *     pytorch3d (real part first, the candidate of the largest component, no sign standardisation); features, opacity copied.
+ *   SPLIT (:551-566), n_new = 2 n_sel, i = index[r mod n_sel] (the repeat(2,1) layout):  new_xyz = R(q_i)(exp(scaling[i]) * noise[r])
+ *     + xyz[i];  new_scaling = log(exp(scaling[i]) / 1.6);  everything else copied.
+ *   MERGE (:606-616), n_new = n_sel, (a,b) = ids[index[r],:]:  means of the pair for xyz, both feature tensors and the raw opacity;
+ *     new_scaling = log(exp(scaling[a]) / 0.8);  new_rotation = rotation[a];  prune_mask[b] = 1 (bytes; the select's mask).
+ *   An index outside [0,P) (a stale list) writes a row of zeros and reads nothing.
+ */
+#define MOSS_DENSIFY_CLONE 0
+#define MOSS_DENSIFY_SPLIT 1
+#define MOSS_DENSIFY_MERGE 2
+#define MOSS_DENSIFY_PRUNE 3
+#define MOSS_DENSIFY_JOINTS 24
+int moss_densify_joint_table(const float* joint_F_sum /* (23,3,3) */, const float* denom, float* table /* (24,12) */, void* stream);
+
+typedef struct moss_densify_select_args {
+    int32_t mode;                            /* MOSS_DENSIFY_* */
+    int32_t P, n_grads;                      /* n_grads <= P rows carry a gradient */
+    const float* xyz_gradient_accum;         /* (n_grads) */
+    const float* denom;                      /* (n_grads) */
+    const float* xyz;                        /* (P,3) */
+    const float* rotation;                   /* (P,4) raw */
+    const float* scaling;                    /* (P,3) raw (logarithms) */
+    const float* opacity;                    /* (P) raw (logits); PRUNE */
+    const long long* ids;                    /* (P,2): the k = 2 self query; CLONE / SPLIT / MERGE */
+    const uint8_t* surface_mask;             /* (P) or NULL; CLONE */
+    const float* max_radii2D;                /* (P); PRUNE with use_screen_size */
+    const float* vertex_dist;                /* (P); PRUNE */
+    float max_grad, scale_limit, kl_threshold;
+    float min_opacity, max_screen_size, world_scale_limit, vertex_dist_limit;
+    int32_t use_screen_size;
+    uint8_t* mask;                           /* (P) */
+    int32_t* index;                          /* (>= count) or NULL */
+    int32_t* count;                          /* device */
+    int32_t* count_host;                     /* pinned host, or NULL */
+    float* kl_out;                           /* (P) or NULL */
+    char* workspace;
+    size_t workspace_bytes;
+} moss_densify_select_args;
+size_t moss_densify_select_workspace_bytes(int P);
+int moss_densify_select(const moss_densify_select_args* args, void* stream);   /* scene/gaussian_model.py:499-509, :540-549, :579-602, :650-662 */
+
+typedef struct moss_densify_emit_args {
+    int32_t mode;                            /* MOSS_DENSIFY_CLONE / _SPLIT / _MERGE */
+    int32_t P, n_sel, n_new;
+    int32_t rest_floats;                     /* floats of a features_rest row (45) */
+    int32_t dc_stride, rest_stride;          /* floats between rows of features_dc / features_rest */
+    const int32_t* index;                    /* (n_sel) */
+    const long long* ids;                    /* (P,2); MERGE */
+    const float* xyz; const float* features_dc; const float* features_rest; const float* opacity; const float* scaling;
+    const float* rotation;
+    const float* lbs_weights;                /* (P,24) accumulated sum; CLONE */
+    const float* denom;                      /* denom[0] is read; CLONE */
+    const float* table;                      /* (24,12); CLONE */
+    const float* noise;                      /* (n_new,3); CLONE / SPLIT */
+    float* new_xyz; float* new_features_dc; float* new_features_rest; float* new_opacity; float* new_scaling; float* new_rotation;
+    uint8_t* prune_mask;                     /* (P); MERGE */
+} moss_densify_emit_args;
+int moss_densify_emit(const moss_densify_emit_args* args, void* stream);       /* scene/gaussian_model.py:511-524, :551-566, :606-616 */
+
+/*
  * The rasterizer with every extension (ABI 7): one argument block per direction.  The fields are those of moss_raster_forward /
  * moss_raster_backward plus the extensions below; NULL or 0 in an extension field means "not used".  moss_raster_forward /
  * moss_raster_backward fill these blocks with no extension and `capacity` = -1.

@@ -67,6 +67,14 @@ def _declare(lib):
     lib.moss_densify_stats.argtypes = [_i, _p, _p, _i, _p, _p, _p, _p]
     lib.moss_neighbour_kl.restype = _i
     lib.moss_neighbour_kl.argtypes = [_i, _i, _p, _p, _p, _p, _p, _p]
+    lib.moss_densify_joint_table.restype = _i
+    lib.moss_densify_joint_table.argtypes = [_p, _p, _p, _p]
+    lib.moss_densify_select_workspace_bytes.restype = C.c_size_t
+    lib.moss_densify_select_workspace_bytes.argtypes = [_i]
+    lib.moss_densify_select.restype = _i
+    lib.moss_densify_select.argtypes = [_p, _p]
+    lib.moss_densify_emit.restype = _i
+    lib.moss_densify_emit.argtypes = [_p, _p]
     lib.moss_loss_workspace_bytes.restype = C.c_size_t
     lib.moss_loss_workspace_bytes.argtypes = [_i, _i, _i]
     lib.moss_photometric_loss.restype = _i
@@ -251,6 +259,30 @@ class LpipsVggBackwardArgs(C.Structure):
     _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("frame_H", C.c_int32), ("frame_W", C.c_int32), ("rect", C.c_void_p),
                 ("weights_bwd", C.c_void_p * 13), ("scale", C.c_void_p), ("saved", C.c_void_p), ("g_out", C.c_void_p),
                 ("dL_dx", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+DENSIFY_MODES = {"clone": 0, "split": 1, "merge": 2, "prune": 3}                    # MOSS_DENSIFY_*
+
+
+class DensifySelectArgs(C.Structure):
+    """``moss_densify_select_args`` of include/moss_raster.h (``moss_densify_select``: one phase's mask, index list and count)."""
+    _fields_ = [("mode", C.c_int32), ("P", C.c_int32), ("n_grads", C.c_int32), ("xyz_gradient_accum", C.c_void_p), ("denom", C.c_void_p),
+                ("xyz", C.c_void_p), ("rotation", C.c_void_p), ("scaling", C.c_void_p), ("opacity", C.c_void_p), ("ids", C.c_void_p),
+                ("surface_mask", C.c_void_p), ("max_radii2D", C.c_void_p), ("vertex_dist", C.c_void_p), ("max_grad", C.c_float),
+                ("scale_limit", C.c_float), ("kl_threshold", C.c_float), ("min_opacity", C.c_float), ("max_screen_size", C.c_float),
+                ("world_scale_limit", C.c_float), ("vertex_dist_limit", C.c_float), ("use_screen_size", C.c_int32), ("mask", C.c_void_p),
+                ("index", C.c_void_p), ("count", C.c_void_p), ("count_host", C.c_void_p), ("kl_out", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+class DensifyEmitArgs(C.Structure):
+    """``moss_densify_emit_args`` of include/moss_raster.h (``moss_densify_emit``: one phase's new rows)."""
+    _fields_ = [("mode", C.c_int32), ("P", C.c_int32), ("n_sel", C.c_int32), ("n_new", C.c_int32), ("rest_floats", C.c_int32),
+                ("dc_stride", C.c_int32), ("rest_stride", C.c_int32), ("index", C.c_void_p), ("ids", C.c_void_p), ("xyz", C.c_void_p), ("features_dc", C.c_void_p),
+                ("features_rest", C.c_void_p), ("opacity", C.c_void_p), ("scaling", C.c_void_p), ("rotation", C.c_void_p),
+                ("lbs_weights", C.c_void_p), ("denom", C.c_void_p), ("table", C.c_void_p), ("noise", C.c_void_p), ("new_xyz", C.c_void_p),
+                ("new_features_dc", C.c_void_p), ("new_features_rest", C.c_void_p), ("new_opacity", C.c_void_p), ("new_scaling", C.c_void_p),
+                ("new_rotation", C.c_void_p), ("prune_mask", C.c_void_p)]
 
 
 OPT_BITS = {"means3D": 1, "sh": 2, "opacity": 4, "scales": 8, "rotations": 16}      # MOSS_OPT_*; position = index in the struct's arrays

@@ -47,6 +47,7 @@ SOURCES = {
     "optim.hip": [],
     "activations.hip": [],
     "densify.hip": [],
+    "densify_decision.hip": [],
     "raster_api.hip": [],
 }
 

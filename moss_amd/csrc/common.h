@@ -399,6 +399,9 @@ int set_last_error(int code, const char* msg);
 MOSS_INTERNAL int invalid_arg(const char* entry_point, const char* condition);
 // the status of the launches `entry_point` has just made: 0, or MOSS_ERR_HIP with "<entry point>: <HIP's text for the error>"
 MOSS_INTERNAL int launch_status(const char* entry_point);
+// neighbour_kl_kernel (densify.hip) on `s`: P >= 1 pairs, every pointer valid -- for the entry points that need ITS bits (densify_decision.hip)
+MOSS_INTERNAL int launch_neighbour_kl(int P, int Nsrc, const float* xyz, const float* rotation, const float* scaling, const long long* pair_idx,
+                                      float* kl_out, hipStream_t s);
 // compute units of the current device (read once; 256 where it cannot be read)
 MOSS_INTERNAL int device_cus();
 

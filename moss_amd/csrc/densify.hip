@@ -11,8 +11,10 @@
 //    trace in a PYTHON loop over P (:803-804); per Gaussian this is ~150 flops on 2 x 40 B of input.
 //        KL = 0.5 (tr(S1^-1 S0) + d^T S1^-1 d + ln prod((s1/s0)^2) - 3),  S = R diag(s^2) R^T,  R = build_rotation(q / |q|)
 //    computed as  tr = sum_ij (M_ij s0_j / s1_i)^2  with  M = R1^T R0,  and  d^T S1^-1 d = sum_i ((R1^T d)_i / s1_i)^2,
-//    which needs no 3x3 products beyond M and never forms a covariance.
+//    which needs no 3x3 products beyond M and never forms a covariance.  (rotation_of: kl_math.h, shared with densify_decision.hip,
+//    whose selection takes its KL from THIS kernel through launch_neighbour_kl: one body, one machine code, the same bits.)
 #include "common.h"
+#include "kl_math.h"
 
 namespace moss {
 namespace {
@@ -29,16 +31,6 @@ densify_stats_kernel(int P, const int* __restrict__ radii, const float* __restri
     grad_accum[i] += sqrtf(gx * gx + gy * gy);
     denom[i] += 1.0f;
     if (max_radii) max_radii[i] = fmaxf(max_radii[i], (float)r);
-}
-
-__device__ __forceinline__ void rotation_of(const float* __restrict__ q4, float R[3][3])     // utils/general_utils.py:79-100
-{
-    const float a = q4[0], b = q4[1], c = q4[2], d = q4[3];
-    const float inv = 1.0f / sqrtf(a * a + b * b + c * c + d * d);
-    const float r = a * inv, x = b * inv, y = c * inv, z = d * inv;
-    R[0][0] = 1.f - 2.f * (y * y + z * z); R[0][1] = 2.f * (x * y - r * z);       R[0][2] = 2.f * (x * z + r * y);
-    R[1][0] = 2.f * (x * y + r * z);       R[1][1] = 1.f - 2.f * (x * x + z * z); R[1][2] = 2.f * (y * z - r * x);
-    R[2][0] = 2.f * (x * z - r * y);       R[2][1] = 2.f * (y * z + r * x);       R[2][2] = 1.f - 2.f * (x * x + y * y);
 }
 
 __global__ void __launch_bounds__(256)
@@ -93,6 +85,13 @@ extern "C" int moss_densify_stats(int P, const int* radii, const float* viewspac
     hipLaunchKernelGGL(moss::densify_stats_kernel, dim3((P + 255) / 256), dim3(256), 0, (hipStream_t)stream, P, radii, viewspace_grad,
                        grad_stride, xyz_gradient_accum, denom, max_radii2D);
     return hipGetLastError() == hipSuccess ? 0 : MOSS_ERR_HIP;
+}
+
+int moss::launch_neighbour_kl(int P, int Nsrc, const float* xyz, const float* rotation, const float* scaling, const long long* pair_idx,
+                              float* kl_out, hipStream_t s)
+{
+    hipLaunchKernelGGL(moss::neighbour_kl_kernel, dim3((P + 255) / 256), dim3(256), 0, s, P, Nsrc, xyz, rotation, scaling, pair_idx, kl_out);
+    return launch_status("moss_neighbour_kl");
 }
 
 extern "C" int moss_neighbour_kl(int P, int Nsrc, const float* xyz, const float* rotation, const float* scaling,

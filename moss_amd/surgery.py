@@ -3,8 +3,9 @@
 MOSS adds and removes Gaussians every 100 iterations between iterations 400 and 2000 and resets the opacities
 (``train_ZJU.py:171-186``): ``densify_and_prune`` -> ``densification_postfix`` (``cat_tensors_to_optimizer``) / ``prune_points``
 (``_prune_optimizer``), ``reset_opacity`` (``replace_tensor_to_optimizer``) -- ``scene/gaussian_model.py:314-317, 362-454``.  Which
-Gaussians it clones, splits or drops is MOSS's decision logic (``:456-620``) and stays there; THIS module carries out the decision on
-the objects of the fast step, in the order MOSS does, with one call per event and outside graph capture:
+Gaussians it clones, splits, merges or drops is decided by ``moss_amd.densify.densify_and_prune_fused`` (MOSS's rule, ``:495-666``, as
+fused ops) or by the caller; THIS module carries out a decision on the objects of the fast step, in the order MOSS does, with one call
+per event and outside graph capture -- or, with ``rows_changed=True``, finishes an event whose appends and prunes were already made:
 
     parameters + both AdamW moments   ``FlatAdamW.append_rows`` / ``prune_rows`` / ``reset_rows`` (new rows: zero moments; reset: zero moments)
     gradient bucket                   ``GradBucket.relayout`` (new offsets, the loss block moves with the tail)
@@ -36,14 +37,16 @@ def reserve_workspace(nbytes, device):
 
 
 def densification_event(pc, optimizer, *, append=None, prune=None, reset_opacity=False, stats=None, context=None, graphed=None,
-                        probe=None, per_gaussian=None, after_surgery=None):
+                        probe=None, per_gaussian=None, after_surgery=None, rows_changed=False):
     """Carry out one event.  ``append``: dict with the six tensors of ``densification_postfix`` (``new_xyz, new_features_dc,
     new_features_rest, new_opacities, new_scaling, new_rotation``) or a list of such dicts (MOSS appends twice per event: clones, then
     splits) -- applied first, in order; ``prune``: bool mask over the Gaussians AFTER the appends, True = remove (``prune_points``);
     ``reset_opacity``: last.  ``per_gaussian``: optional dict name -> (P, ...) tensor the CALLER keeps per Gaussian (an LBS transform
     table, cached neighbours): appended rows are taken from ``append[i]["source"]`` (index of the Gaussian each new row derives from)
     and pruned with the mask; the re-indexed dict is returned in the report and -- BEFORE the probe and the re-capture, whose step
-    function reads those tables -- handed to ``after_surgery(per_gaussian)``.
+    function reads those tables -- handed to ``after_surgery(per_gaussian)``.  ``rows_changed=True``: the rows of ``pc`` were appended and
+    pruned BEFORE this call (``densify.densify_and_prune_fused``): the tail of an event -- capacity re-learning, probe, re-capture --
+    runs although this call itself changes no row.
 
     Returns a report: rows before / after, what was re-captured, and the host-side cost of the event in milliseconds (it
     synchronises the device: the event is outside the step's asynchronous flow by nature)."""
@@ -62,7 +65,7 @@ def densification_event(pc, optimizer, *, append=None, prune=None, reset_opacity
     rows_before = int(pc._xyz.shape[0])
     per_gaussian = dict(per_gaussian or {})
     appends = [] if append is None else ([append] if isinstance(append, dict) else list(append))
-    shape_changed = False
+    shape_changed = bool(rows_changed)
     for a in appends:
         n_new = int(a["new_xyz"].shape[0])
         if n_new == 0:
