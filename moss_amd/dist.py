@@ -29,7 +29,20 @@ def init_from_env(backend: str | None = None):
         if backend == "nccl":
             torch.cuda.set_device(local_rank)
         dist.init_process_group(backend=backend, rank=rank, world_size=world)
+        if backend == "gloo":
+            # A gloo group that is still alive when the interpreter exits is torn down by static destructors, in no particular order
+            # against its own worker threads: now and then (a few per cent of the runs on a loaded host) one of them is destroyed
+            # while joinable -- "terminate called without an active exception", SIGABRT after the result was already printed, and
+            # the launcher reports a failed job.  Destroy the group while the interpreter is whole.  (No collective is involved, so
+            # a rank that leaves on an error does not wait for its peers here.)
+            import atexit
+            atexit.register(_destroy_group_at_exit)
     return rank, world, local_rank
+
+
+def _destroy_group_at_exit():
+    if dist.is_initialized():
+        dist.destroy_process_group()
 
 
 _AVG_OK = {}          # backend -> does the collective library average inside the collective (ncclAvg)?  Decided ONCE per process.

@@ -27,7 +27,11 @@ def _forward(d, gpu, debug):
                                       ("config3", "scale_rot"), ("config3", "precomp"), ("config5", "scale_rot")])
 def test_forward_only_outputs_equal_the_training_forward_bit_for_bit(gpu, hip_lib, cfg, mode):
     scene = getattr(scenes, cfg)()
-    d = hp.inputs_of(scene, mode)
+    forward_only_equals_the_training_forward(hp.inputs_of(scene, mode), gpu, hip_lib)
+
+
+def forward_only_equals_the_training_forward(d, gpu, hip_lib):
+    """(also called by tests/test_gpu_raster_arguments.py with a scale_modifier other than 1)"""
     t0, e0 = _forward(d, gpu, 0)
     t1, e1 = _forward(d, gpu, FORWARD_ONLY)
     assert t0.R == t1.R > 0

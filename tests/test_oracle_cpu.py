@@ -244,8 +244,32 @@ def test_dist2_known_answers():
 def test_explicit_backward_matches_independent_autograd(mode):
     """The C oracle's explicit backward (restated backward.cu) against autograd of an independent float64 forward.
     Tolerance 2e-3 of each gradient's max: fp32 vs fp64 plus semantic (vii) above."""
+    _explicit_backward_against_autograd(mode, 1.0, 16, 3)
+
+
+# (scale_modifier, M = SH coefficients per Gaussian, active SH degree): the two arguments of the call that nothing else moves off 1.0 / 16.
+# With a precomputed covariance the modifier does not enter: that mode runs where mod == 1 only.
+RASTER_ARGUMENTS = [(1.7, 16, 3), (0.6, 16, 3), (1.7, 4, 1), (1.0, 9, 2), (1.3, 1, 0)]
+
+
+@pytest.mark.parametrize("mode,mod,M,degree", [(mode, *a) for a in RASTER_ARGUMENTS for mode in ("scale_rot", "precomp", "lbs")
+                                               if mode != "precomp" or a[0] == 1.0])
+def test_explicit_backward_matches_independent_autograd_over_scale_modifier_and_sh_size(mode, mod, M, degree):
+    """The same comparison at the same bar over `scale_modifier` and SH arrays of M = 1 / 4 / 9 / 16 coefficients (a model allocated at
+    degree 0 / 1 / 2 / 3): the referee of tests/test_gpu_raster_arguments.py is pinned here first.
+
+    The covariance is built from mod * s, and the reference reports dL_dscales WITH RESPECT TO mod * s: its chain rule stops one factor
+    short (backward.cu:322-325 multiply dL/dM by the rotation's rows and never by `mod`).  The expected scale gradient is therefore
+    autograd's DIVIDED by mod -- the reference's behaviour and so the contract.  Against plain autograd the
+    tensor is off by |1 / mod - 1| of its largest element: 0.41 at mod 1.7, 0.67 at 0.6, 0.23 at 1.3."""
+    _explicit_backward_against_autograd(mode, mod, M, degree)
+
+
+def _explicit_backward_against_autograd(mode, mod, M, degree):
     s = scenes.config1(P=96, W=64, H=64, seed=7)
-    d = hp.inputs_of(s, mode)
+    d = hp.inputs_of(s, mode, degree=degree)
+    d.shs = d.shs[:, :M].contiguous()
+    d.scale_modifier = mod
     fw = hp.oracle_forward(d)
     dc, dd, da = hp.image_grads(d.H, d.W, seed=9)
     ref = hp.oracle_backward(d, fw, dc, dd, da)
@@ -265,24 +289,25 @@ def test_explicit_backward_matches_independent_autograd(mode):
         R = torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y),
                          2 * (x * y + r * z), 1 - 2 * (x * x + z * z), 2 * (y * z - r * x),
                          2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)], dim=1).reshape(-1, 3, 3)
-        Lm = tfm @ (R * scales[:, None, :])
+        Lm = tfm @ (R * (mod * scales)[:, None, :])
         full = Lm @ Lm.transpose(1, 2)
         cov = torch.stack([full[:, 0, 0], full[:, 0, 1], full[:, 0, 2], full[:, 1, 1], full[:, 1, 2], full[:, 2, 2]], dim=1)
     ndc = torch.zeros(d.P, 2, dtype=torch.float64, requires_grad=True)
     col, dep, alp = ag.render(fw, means, opa, f64(c.viewmatrix), f64(c.projmatrix), f64(c.campos), c.tanfovx, c.tanfovy,
                               f64(d.bg), d.degree, shs=shs, scales=None if mode == "lbs" else scales,
-                              rotations=None if mode == "lbs" else rots, cov3D_precomp=cov, ndc_offset=ndc)
+                              rotations=None if mode == "lbs" else rots, scale_modifier=mod, cov3D_precomp=cov, ndc_offset=ndc)
     # forward agreement first (fp32 oracle vs fp64 autograd forward)
     assert hp.rel_err(fw.color, col.detach().numpy()) < 5e-5
     assert hp.rel_err(fw.alpha, alp.detach().numpy()) < 5e-5
     assert hp.rel_err(fw.depth, dep.detach().numpy()) < 5e-5
     loss = (col * dc.double()).sum() + (dep * dd.double()).sum() + (alp * da.double()).sum()
     loss.backward()
+    assert ref.dL_dsh.shape == (d.P, M, 3)
     checks = [("dL_dmeans3D", means.grad), ("dL_dopacity", opa.grad), ("dL_dsh", shs.grad), ("dL_dmeans2D", ndc.grad)]
     if mode == "scale_rot":
-        checks += [("dL_dscales", scales.grad), ("dL_drotations", rots.grad)]
+        checks += [("dL_dscales", scales.grad / mod), ("dL_drotations", rots.grad)]
     elif mode == "lbs":
-        checks += [("dL_dscales", scales.grad), ("dL_drotations", rots.grad), ("dL_dtransforms", tfm.grad)]
+        checks += [("dL_dscales", scales.grad / mod), ("dL_drotations", rots.grad), ("dL_dtransforms", tfm.grad)]
     else:
         checks += [("dL_dcov3D", cov.grad)]
     for name, gref in checks:
