@@ -15,6 +15,7 @@
 // d.x*d.x + d.y*d.y + d.z*d.z (:134-135), and the three smallest values of a multiset do not depend on visiting order,
 // so the result is bit-identical to the brute-force CPU oracle.
 #include "common.h"
+#include "wave.h"
 #include <cfloat>
 
 namespace moss {
@@ -22,9 +23,6 @@ namespace moss {
 namespace {
 
 constexpr int BOX = 1024;      // simple_knn.cu:12
-
-__device__ __forceinline__ uint32_t f2ord(float f) { uint32_t u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
-__device__ __forceinline__ float ord2f(uint32_t u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); }
 
 __global__ void __launch_bounds__(256)
 bounds_kernel(int P, const float* __restrict__ pts, uint32_t* __restrict__ mm /* [0..2]=min, [3..5]=max, ordered ints */)
@@ -36,8 +34,7 @@ bounds_kernel(int P, const float* __restrict__ pts, uint32_t* __restrict__ mm /*
         for (int k = 0; k < 3; k++) { const float v = pts[3 * (size_t)i + k]; mn[k] = fminf(mn[k], v); mx[k] = fmaxf(mx[k], v); }
 #pragma unroll
     for (int k = 0; k < 3; k++) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) { mn[k] = fminf(mn[k], __shfl_xor(mn[k], d)); mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], d)); }
+        mn[k] = wave_min(mn[k]); mx[k] = wave_max(mx[k]);
         if ((threadIdx.x & 63) == 0) { s_mn[threadIdx.x >> 6][k] = mn[k]; s_mx[threadIdx.x >> 6][k] = mx[k]; }
     }
     __syncthreads();
@@ -176,8 +173,7 @@ box_kernel(int P, const float4* __restrict__ sorted, Box* __restrict__ boxes)   
     }
 #pragma unroll
     for (int k = 0; k < 3; k++) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) { mn[k] = fminf(mn[k], __shfl_xor(mn[k], d)); mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], d)); }
+        mn[k] = wave_min(mn[k]); mx[k] = wave_max(mx[k]);
         if ((threadIdx.x & 63) == 0) { s_mn[threadIdx.x >> 6][k] = mn[k]; s_mx[threadIdx.x >> 6][k] = mx[k]; }
     }
     __syncthreads();

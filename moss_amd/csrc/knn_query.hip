@@ -9,6 +9,7 @@
 // closer to displace a kept one).  Distances are Euclidean (sqrt of the fp32 sum of squares), ascending.
 // Cost: Nq x Nr pairs at ~10 lane-instructions each: 100k x 6 890 = 0.2 ms; 100k x 100k = ~3 ms (densification only).
 #include "common.h"
+#include "wave.h"
 
 namespace moss {
 namespace {
@@ -80,9 +81,6 @@ knn_query_kernel(int Nr, int Nq, const float* __restrict__ ref, const float* __r
 constexpr int GRID_HDR = 32;                // words: [0..2] min, [3..5] max (ordered uints); [6] Nr; [8..10] Gx,Gy,Gz; floats [12..14] lo, [15..17] h, [18..20] 1/h, [21] slack
 constexpr int SCAN_BLOCK = 1024;            // cells per block of the first scan level
 
-__device__ __forceinline__ uint32_t f2ord(float f) { uint32_t u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
-__device__ __forceinline__ float ord2f(uint32_t u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); }
-
 struct GridView {
     uint32_t* hdr; uint32_t* start; uint32_t* bsum; uint32_t* cell; uint32_t* rank; float4* sorted;
     int ncells_max, nblocks;
@@ -122,8 +120,7 @@ grid_bounds_kernel(int Nr, const float* __restrict__ pts, uint32_t* __restrict__
         for (int k = 0; k < 3; k++) { const float v = pts[3 * (size_t)i + k]; mn[k] = fminf(mn[k], v); mx[k] = fmaxf(mx[k], v); }
 #pragma unroll
     for (int k = 0; k < 3; k++) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) { mn[k] = fminf(mn[k], __shfl_xor(mn[k], d)); mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], d)); }
+        mn[k] = wave_min(mn[k]); mx[k] = wave_max(mx[k]);
         if ((threadIdx.x & 63) == 0) { s_mn[threadIdx.x >> 6][k] = mn[k]; s_mx[threadIdx.x >> 6][k] = mx[k]; }
     }
     __syncthreads();
@@ -210,9 +207,7 @@ grid_scan_blocks_kernel(uint32_t* __restrict__ start, uint32_t* __restrict__ bsu
     uint4* row = reinterpret_cast<uint4*>(start + (size_t)blockIdx.x * SCAN_BLOCK);
     const uint4 v = row[threadIdx.x];
     const uint32_t mine = v.x + v.y + v.z + v.w;
-    uint32_t inc = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t t = __shfl_up(inc, d); if ((int)(threadIdx.x & 63) >= d) inc += t; }
+    const uint32_t inc = wave_inclusive_scan(mine);
     if ((threadIdx.x & 63) == 63) s_wave[threadIdx.x >> 6] = inc;
     __syncthreads();
     uint32_t base = 0;
@@ -230,9 +225,7 @@ grid_scan_sums_kernel(uint32_t* __restrict__ bsum, int nblocks)
     uint32_t v[4], mine = 0;
 #pragma unroll
     for (int k = 0; k < 4; k++) { const int i = 4 * (int)threadIdx.x + k; v[k] = i < nblocks ? bsum[i] : 0u; mine += v[k]; }
-    uint32_t inc = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t t = __shfl_up(inc, d); if ((int)(threadIdx.x & 63) >= d) inc += t; }
+    const uint32_t inc = wave_inclusive_scan(mine);
     if ((threadIdx.x & 63) == 63) s_wave[threadIdx.x >> 6] = inc;
     __syncthreads();
     uint32_t base = 0;

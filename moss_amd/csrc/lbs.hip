@@ -11,6 +11,7 @@
 // Instantiations: J = 24 (SMPL) with 16-byte loads and stores of the W / L / w rows, and J rounded up to a multiple of 8 (8 .. 64)
 // with per-element guards for every other J.  Nothing is allocated, nothing synchronises, nothing is cleared with a memset.
 #include "common.h"
+#include "wave.h"
 
 namespace moss {
 
@@ -348,8 +349,7 @@ lbs_fold_kernel(int J, int nblocks, const float* __restrict__ partials, float* _
         const size_t stride = (size_t)J * 12, off = (size_t)j * 12 + r * 4 + c;
         for (int b = lane; b < nblocks; b += 64) acc += (double)partials[(size_t)b * stride + off];
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
+    acc = wave_sum(acc);
     if (lane == 0) gA[o] = (float)acc;
 }
 

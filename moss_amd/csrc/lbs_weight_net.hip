@@ -27,12 +27,11 @@
 //        forms the gradients of key.*, value.* and Rs from them.
 // Every sum has a fixed order and there is no atomic: results are bitwise reproducible.  Every output element is written.
 #include "common.h"
+#include "mfma_f32.h"
 
 namespace moss {
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int NPAR = MOSS_LBS_WEIGHT_NET_PARAMS;
 constexpr int T = 32;                      // points per workgroup
@@ -55,22 +54,6 @@ constexpr int SPLITS = MOSS_LBS_WEIGHT_NET_SPLITS;
 // LDS row strides (floats): = 4 mod 64, so that the 32 lanes of a half wave read their float4 from 32 different bank groups
 constexpr int H_LD = 132, EH_LD = 196, Q_LD = 36;
 
-__device__ __forceinline__ int acc_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }   // C/D: col = lane & 31
-
-__device__ __forceinline__ f32x16 splat(float v)
-{
-    f32x16 r;
-#pragma unroll
-    for (int i = 0; i < 16; i++) r[i] = v;
-    return r;
-}
-
-#define MOSS_MFMA4(acc, av, bv)                                                  \
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv[0], acc, 0, 0, 0);       \
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv[1], acc, 0, 0, 0);       \
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv[2], acc, 0, 0, 0);       \
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv[3], acc, 0, 0, 0)
-
 // acc[pt][n] += sum_{k in [kbase, kbase + K)} A[pt][k] W[n][k]: A in LDS (a_row = this lane's point), W (out, LD) row-major in
 // global memory.  SKIP: A is [e (63), 0, h2 (128)] and W is W3 (LD = 191): column 63 of A has no weight.
 template <int K, int LD, bool SKIP>
@@ -90,7 +73,7 @@ __device__ __forceinline__ f32x16 gemm_wt(const float* __restrict__ W, int n, bo
             const int kw = SKIP ? (k < NE ? k : k - 1) : k;
             bv[s] = ok ? w[kw] : 0.0f;
         }
-        MOSS_MFMA4(acc, av, bv);
+        mfma4(acc, av, bv);
     }
     return acc;
 }
@@ -108,7 +91,7 @@ __device__ __forceinline__ f32x16 gemm_w(const float* __restrict__ W, int ld, in
         float bv[4];
 #pragma unroll
         for (int s = 0; s < 4; s++) bv[s] = (col_ok && kk + s < kvalid) ? w[(size_t)(kk + s) * ld] : 0.0f;
-        MOSS_MFMA4(acc, av, bv);
+        mfma4(acc, av, bv);
     }
     return acc;
 }

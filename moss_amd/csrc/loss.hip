@@ -27,14 +27,7 @@ namespace moss {
 
 namespace {
 
-constexpr int LT = 32;              // tile edge: 32 x 32 outputs per 256-thread workgroup
-constexpr int HALO = 5;             // window 11
-constexpr int LP = LT + 2 * HALO;   // 42
-constexpr int SEG = 8;              // outputs per thread in the horizontal pass (a run of 8 in one row: 18 inputs)
-constexpr int VR = 4;               // outputs per thread in the vertical pass (4 consecutive rows of one column: 14 inputs)
-static_assert(LT % SEG == 0 && (LT / SEG) * LP <= 256 && LT * (LT / VR) == 256, "work split of a 256-thread workgroup");
-
-typedef float v2f __attribute__((ext_vector_type(2)));
+// (the tile constants LT, HALO, LP, SEG, VR and v2f: ssim_tiles.h)
 
 // Both passes are separable 11-tap filters through LDS with SLIDING WINDOWS in registers (round 2: one output per thread and pass,
 // 11 LDS reads per output and moment, products recomputed per tap -- 7.8 wave-instructions per pixel-channel, 30 % of the wave
@@ -175,20 +168,10 @@ ssim_pass1_kernel(int C, int H, int W, const float* __restrict__ img, const floa
         const int ly = ly0 + j, py = y0 + ly;
         if (ROI ? in_crop(crop, px, py) : (px < W && py < H)) {
             const float mu1 = m01[j].x, mu2 = m01[j].y, ess = m23[j].x /* E[x^2 + y^2] */, exy = m23[j].y;
-            const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
-            const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
-            const float s12 = exy - mu12;
-            // sigma1^2 + sigma2^2 = E[x^2 + y^2] - mu1^2 - mu2^2 (utils/loss_utils.py:73-75 forms the two variances and adds them)
-            const float a1 = 2.f * mu12 + C1, a2 = 2.f * s12 + C2, b1 = mu1_sq + mu2_sq + C1, b2 = (ess - mu1_sq - mu2_sq) + C2;
-            // (hardware reciprocals, ~1 ulp: this file is compiled with correctly rounded division, ten instructions apiece, and the
-            // four quotients per pixel-channel were an eighth of this kernel's vector instructions; b1 >= C1, b2 ~ C2 + variances)
-            const float rb1 = __builtin_amdgcn_rcpf(b1), rb2 = __builtin_amdgcn_rcpf(b2), inv = rb1 * rb2;
-            const float S = a1 * a2 * inv;
-            // partial derivatives of S w.r.t. (mu1 | sigma1^2 | sigma12), then total derivatives w.r.t. the three filtered
-            // moments E[x], E[x^2], E[xy] (sigma1^2 = E[x^2] - mu1^2, sigma12 = E[xy] - mu1 mu2)
-            const float dS_ds1 = -S * rb2;
-            const float dS_ds12 = 2.f * a1 * inv;
-            const float dS_dmu1 = 2.f * mu2 * a2 * inv - S * 2.f * mu1 * rb1 + dS_ds1 * (-2.f * mu1) + dS_ds12 * (-mu2);
+            // (the results are copied into locals on purpose: reading p.S etc. below schedules one instantiation differently, and this
+            // kernel's assembly is pinned -- profiles/shared_device_code_notes.md)
+            const SsimPoint p = ssim_point(mu1, mu2, ess, exy);
+            const float S = p.S, dS_ds1 = p.dS_ds1, dS_ds12 = p.dS_ds12, dS_dmu1 = p.dS_dmu1;
             const size_t o = ((size_t)c * H + py) * W + px, plane3 = (size_t)C * H * W;
             dmap[o] = dS_dmu1; dmap[plane3 + o] = dS_ds1; dmap[2 * plane3 + o] = dS_ds12;
             ssim_v += S;
@@ -215,9 +198,9 @@ ssim_pass1_kernel(int C, int H, int W, const float* __restrict__ img, const floa
     LSTAMP(5);
     if (tid == 0) {
         const size_t b = ((size_t)tile.c * gridDim.y + tile.by) * gridDim.x + tile.bx;
-        partials[2 * b] = (s_red[0][0] + s_red[0][1]) + (s_red[0][2] + s_red[0][3]);
-        partials[2 * b + 1] = (s_red[1][0] + s_red[1][1]) + (s_red[1][2] + s_red[1][3]);
-        if (c == 0 && alpha != nullptr) mask_partials[tile.by * gridDim.x + tile.bx] = (s_red[2][0] + s_red[2][1]) + (s_red[2][2] + s_red[2][3]);
+        partials[2 * b] = block_sum3(s_red, 0);
+        partials[2 * b + 1] = block_sum3(s_red, 1);
+        if (c == 0 && alpha != nullptr) mask_partials[tile.by * gridDim.x + tile.bx] = block_sum3(s_red, 2);
     }
 }
 
@@ -366,9 +349,9 @@ ssim_pass2_kernel(int C, int H, int W, const float* __restrict__ img, const floa
         if ((tid & 63) == 0) { s_red[0][tid >> 6] = m; s_red[1][tid >> 6] = a; s_red[2][tid >> 6] = b; }
         __syncthreads();
         if (tid == 0) {
-            const float ssim_mean = ((s_red[1][0] + s_red[1][1]) + (s_red[1][2] + s_red[1][3])) / N;
-            const float l1_mean = ((s_red[2][0] + s_red[2][1]) + (s_red[2][2] + s_red[2][3])) / N1;
-            const float mask_mean = ((s_red[0][0] + s_red[0][1]) + (s_red[0][2] + s_red[0][3])) / (ROI ? crop.n_bound : (float)H * (float)W);
+            const float ssim_mean = block_sum3(s_red, 1) / N;
+            const float l1_mean = block_sum3(s_red, 2) / N1;
+            const float mask_mean = block_sum3(s_red, 0) / (ROI ? crop.n_bound : (float)H * (float)W);
             const float lm = alpha != nullptr ? lambda_mask : 0.0f;
             loss_out[1] = l1_mean; loss_out[2] = ssim_mean; loss_out[3] = mask_mean;
             loss_out[0] = lambda_l1 * l1_mean + lm * mask_mean + lambda_dssim * (1.0f - ssim_mean);

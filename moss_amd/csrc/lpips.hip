@@ -24,12 +24,13 @@
 //   pool_kernel, tap_kernel, unpool_tap_kernel, reduce_kernel -- see each.
 // Every sum has a fixed order and there is no atomic: results are bitwise reproducible.  Every element of dL_dx is written.
 #include "common.h"
+#include "mfma_f32.h"
+#include "wave.h"
 
 namespace moss {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int NCONV = MOSS_LPIPS_VGG_CONVS, NTAP = MOSS_LPIPS_VGG_TAPS;
@@ -41,22 +42,6 @@ constexpr int WG = 256;
 constexpr int KC = 64, LD = KC + 4, BN = 64;             // K slice, LDS row stride (floats), output channels per workgroup
 constexpr float NORM_EPS = 1e-10f;
 enum { MODE_FWD, MODE_BWD_MASK, MODE_BWD_PLAIN };
-
-__device__ __forceinline__ int acc_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }   // C/D: col = lane & 31
-
-__device__ __forceinline__ f32x16 splat(float v)
-{
-    f32x16 r;
-#pragma unroll
-    for (int i = 0; i < 16; i++) r[i] = v;
-    return r;
-}
-
-#define MOSS_MFMA4(acc, av, bv)                                                 \
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, acc, 0, 0, 0);       \
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.y, acc, 0, 0, 0);       \
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv.z, acc, 0, 0, 0);       \
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, acc, 0, 0, 0)
 
 // where the crop starts in the frame: the rectangle's corner, moved so that the crop fits
 __device__ __forceinline__ int2 crop_origin(const int* __restrict__ rect, int H, int W, int FH, int FW)
@@ -250,8 +235,8 @@ conv3x3_mfma_kernel(const ConvArgs a)
             const f32x4 av = *reinterpret_cast<const f32x4*>(a_row + 8 * step);
             const f32x4 b0 = *reinterpret_cast<const f32x4*>(b_row + 8 * step);
             const f32x4 b1 = *reinterpret_cast<const f32x4*>(b_row + 32 * LD + 8 * step);
-            MOSS_MFMA4(acc0, av, b0);
-            MOSS_MFMA4(acc1, av, b1);
+            mfma4(acc0, av, b0);
+            mfma4(acc1, av, b1);
         }
         __syncthreads();
         if (kc + 1 < nchunks) {
@@ -338,13 +323,6 @@ pool_kernel(const float* __restrict__ in, float* __restrict__ out, uint32_t* __r
         *reinterpret_cast<float4*>(dst + 4 * quad) = make_float4(best[0], best[1], best[2], best[3]);
     }
     if (win && img == 0) win[(size_t)pp * G + g] = word;
-}
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);       // (a butterfly: every lane ends with the same bits)
-    return v;
 }
 
 // ---- a tap: one wave per pixel ---------------------------------------------------------------------------------------------------------

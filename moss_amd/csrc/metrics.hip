@@ -17,22 +17,15 @@
 //          by the first.
 // Traffic per view and channel: 2 x 4 B read per pixel (+ the halo re-reads, mostly from L2) + 1 B of the mask, + 4 B written with out_image.
 #include "common.h"
+#include "ssim_tiles.h"
 
 namespace moss {
 
 namespace {
 
-constexpr int MT = 32;              // tile edge: 32 x 32 outputs per 256-thread workgroup (as loss.hip)
-constexpr int MHALO = 5;            // window 11
-constexpr int MP = MT + 2 * MHALO;  // 42
-constexpr int MSEG = 8;             // outputs per thread in the horizontal pass
-constexpr int MVR = 4;              // outputs per thread in the vertical pass
 constexpr int MAX_VIEWS = 8;
 constexpr int MAX_CH = 4;
-static_assert(MT % MSEG == 0 && (MT / MSEG) * MP <= 256 && MT * (MT / MVR) == 256, "work split of a 256-thread workgroup");
 
-struct MWin { float g[11]; };
-typedef float v2f __attribute__((ext_vector_type(2)));
 
 struct Views {
     const float* image[MAX_VIEWS];
@@ -45,19 +38,16 @@ struct Views {
 __device__ __forceinline__ float clamp01(float v) { return v < 0.f ? 0.f : (v > 1.f ? 1.f : v); }
 
 __global__ void __launch_bounds__(256)
-eval_tiles_kernel(Views V, int C, int H, int W, int gx, int gy, float fill, MWin win, float* __restrict__ partials /* [views][C][gy][gx][3] */)
+eval_tiles_kernel(Views V, int C, int H, int W, int gx, int gy, float fill, Win win, float* __restrict__ partials /* [views][C][gy][gx][3] */)
 {
-    __shared__ float s_x[MP][MP + 1];
-    __shared__ float s_y[MP][MP + 1];
-    __shared__ float s_h[4][MP][MT + 1];               // (36.7 KB of LDS in all: four workgroups per CU)
+    __shared__ float s_x[LP][LP + 1];
+    __shared__ float s_y[LP][LP + 1];
+    __shared__ float s_h[4][LP][LT + 1];               // (36.7 KB of LDS in all: four workgroups per CU)
     __shared__ float s_red[3][4];
 
-    // XCD-aware order (loss.hip xcd_tile): workgroups are dealt round-robin to the 8 XCDs; XCD k takes the k-th contiguous eighth of
-    // the (view, channel, row, column) sequence, so the tiles that re-read each other's halo share an L2
-    const int total = (int)gridDim.x;
-    const int lin = (int)blockIdx.x;
-    const int q8 = total / 8, r8 = total % 8, xcd = lin % 8, j8 = lin / 8;
-    const int t = xcd * q8 + min(xcd, r8) + j8;
+    // XCD-aware order (ssim_tiles.h xcd_order) over the (view, channel, row, column) sequence: the tiles that re-read each other's halo
+    // share an L2
+    const int t = xcd_order((int)blockIdx.x, (int)gridDim.x);
     const int per_view = C * gy * gx;
     const int view = t / per_view, rem = t % per_view;
     const int c = rem / (gy * gx), by = (rem / gx) % gy, bx = rem % gx;
@@ -71,26 +61,26 @@ eval_tiles_kernel(Views V, int C, int H, int W, int gx, int gy, float fill, MWin
     const size_t plane = (size_t)H * W;
     const float* xc = xi + (size_t)c * plane;
     const float* yc = yi + (size_t)c * plane;
-    const int x0 = bx * MT, y0 = by * MT;
+    const int x0 = bx * LT, y0 = by * LT;
     const int tid = threadIdx.x;
     {
         // tile + halo: all loads first (clamped addresses, in flight together), then clamp / fill / zero padding into LDS
-        constexpr int NLD = (MP * MP + 255) / 256;
+        constexpr int NLD = (LP * LP + 255) / 256;
         float vx[NLD], vy[NLD];
         unsigned char vb[NLD];
 #pragma unroll
         for (int k = 0; k < NLD; k++) {
-            const int i = tid + 256 * k, r = i / MP, q = i % MP;
-            const size_t o = (size_t)min(max(y0 + r - MHALO, 0), H - 1) * W + min(max(x0 + q - MHALO, 0), W - 1);
+            const int i = tid + 256 * k, r = i / LP, q = i % LP;
+            const size_t o = (size_t)min(max(y0 + r - HALO, 0), H - 1) * W + min(max(x0 + q - HALO, 0), W - 1);
             vx[k] = xc[o]; vy[k] = yc[o];
             vb[k] = bd != nullptr ? bd[o] : (unsigned char)1;
         }
 #pragma unroll
         for (int k = 0; k < NLD; k++) {
-            const int i = tid + 256 * k, r = i / MP, q = i % MP;
-            const int gx_ = x0 + q - MHALO, gy_ = y0 + r - MHALO;
+            const int i = tid + 256 * k, r = i / LP, q = i % LP;
+            const int gx_ = x0 + q - HALO, gy_ = y0 + r - HALO;
             const bool in = gx_ >= 0 && gx_ < W && gy_ >= 0 && gy_ < H;
-            if (i < MP * MP) {
+            if (i < LP * LP) {
                 const float a = vb[k] ? clamp01(vx[k]) : fill;          // the fill goes onto the render only, after its clamp
                 s_x[r][q] = in ? a : 0.0f;
                 s_y[r][q] = in ? clamp01(vy[k]) : 0.0f;
@@ -98,18 +88,18 @@ eval_tiles_kernel(Views V, int C, int H, int W, int gx, int gy, float fill, MWin
         }
     }
     __syncthreads();
-    if (tid < (MT / MSEG) * MP) {                        // horizontal 11-tap of the four moments (loss.hip pass 1)
-        const int r = tid % MP, q0 = (tid / MP) * MSEG;
-        v2f a01[MSEG], a23[MSEG];
+    if (tid < (LT / SEG) * LP) {                        // horizontal 11-tap of the four moments (ssim_tiles.h ssim_filter_h)
+        const int r = tid % LP, q0 = (tid / LP) * SEG;
+        v2f a01[SEG], a23[SEG];
 #pragma unroll
-        for (int j = 0; j < MSEG; j++) { a01[j] = v2f{0.f, 0.f}; a23[j] = v2f{0.f, 0.f}; }
+        for (int j = 0; j < SEG; j++) { a01[j] = v2f{0.f, 0.f}; a23[j] = v2f{0.f, 0.f}; }
 #pragma unroll
-        for (int i = 0; i < MSEG + 10; i++) {
+        for (int i = 0; i < SEG + 10; i++) {
             const float a = s_x[r][q0 + i], b = s_y[r][q0 + i];
             const v2f ab = v2f{a, b}, sq = ab * ab;
             const v2f sx = v2f{sq.x + sq.y, a * b};                                // (x^2 + y^2, x y)
 #pragma unroll
-            for (int j = 0; j < MSEG; j++) {
+            for (int j = 0; j < SEG; j++) {
                 if (i - j >= 0 && i - j <= 10) {
                     const float w = win.g[i - j];
                     const v2f w2 = v2f{w, w};
@@ -118,20 +108,20 @@ eval_tiles_kernel(Views V, int C, int H, int W, int gx, int gy, float fill, MWin
             }
         }
 #pragma unroll
-        for (int j = 0; j < MSEG; j++) {
+        for (int j = 0; j < SEG; j++) {
             s_h[0][r][q0 + j] = a01[j].x; s_h[1][r][q0 + j] = a01[j].y; s_h[2][r][q0 + j] = a23[j].x; s_h[3][r][q0 + j] = a23[j].y;
         }
     }
     __syncthreads();
-    const int lx = tid % MT, ly0 = (tid / MT) * MVR;     // vertical: column lx, rows ly0 .. ly0 + MVR - 1
-    v2f m01[MVR], m23[MVR];
+    const int lx = tid % LT, ly0 = (tid / LT) * VR;     // vertical: column lx, rows ly0 .. ly0 + VR - 1
+    v2f m01[VR], m23[VR];
 #pragma unroll
-    for (int j = 0; j < MVR; j++) { m01[j] = v2f{0.f, 0.f}; m23[j] = v2f{0.f, 0.f}; }
+    for (int j = 0; j < VR; j++) { m01[j] = v2f{0.f, 0.f}; m23[j] = v2f{0.f, 0.f}; }
 #pragma unroll
-    for (int i = 0; i < MVR + 10; i++) {
+    for (int i = 0; i < VR + 10; i++) {
         const v2f v01 = v2f{s_h[0][ly0 + i][lx], s_h[1][ly0 + i][lx]}, v23 = v2f{s_h[2][ly0 + i][lx], s_h[3][ly0 + i][lx]};
 #pragma unroll
-        for (int j = 0; j < MVR; j++) {
+        for (int j = 0; j < VR; j++) {
             if (i - j >= 0 && i - j <= 10) {
                 const float w = win.g[i - j];
                 const v2f w2 = v2f{w, w};
@@ -142,18 +132,18 @@ eval_tiles_kernel(Views V, int C, int H, int W, int gx, int gy, float fill, MWin
     float ssim_v = 0.f, l1_v = 0.f, sq_v = 0.f;
     const int px = x0 + lx;
 #pragma unroll
-    for (int j = 0; j < MVR; j++) {
+    for (int j = 0; j < VR; j++) {
         const int ly = ly0 + j, py = y0 + ly;
         if (px < W && py < H) {
             const float mu1 = m01[j].x, mu2 = m01[j].y, ess = m23[j].x /* E[x^2 + y^2] */, exy = m23[j].y;
             const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
             const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu1_mu2 = mu1 * mu2;
             const float sigma12 = exy - mu1_mu2;
-            // sigma1^2 + sigma2^2 = E[x^2 + y^2] - mu1^2 - mu2^2 (as loss.hip); utils/loss_utils.py:84 with a true division (forward only:
+            // sigma1^2 + sigma2^2 = E[x^2 + y^2] - mu1^2 - mu2^2 (as ssim_tiles.h ssim_point); utils/loss_utils.py:84 with a true division (forward only:
             // no derivatives share the reciprocals here)
             const float S = ((2.f * mu1_mu2 + C1) * (2.f * sigma12 + C2)) / ((mu1_sq + mu2_sq + C1) * ((ess - mu1_sq - mu2_sq) + C2));
             ssim_v += S;
-            const float x = s_x[ly + MHALO][lx + MHALO], d = x - s_y[ly + MHALO][lx + MHALO];
+            const float x = s_x[ly + HALO][lx + HALO], d = x - s_y[ly + HALO][lx + HALO];
             l1_v += fabsf(d);
             sq_v += d * d;
             if (out != nullptr) out[(size_t)c * plane + (size_t)py * W + px] = x;
@@ -166,7 +156,7 @@ eval_tiles_kernel(Views V, int C, int H, int W, int gx, int gy, float fill, MWin
     if (tid == 0) {
         float* p = partials + (size_t)t * 3;             // (t: the logical tile id -- view, channel, row, column)
 #pragma unroll
-        for (int k = 0; k < 3; k++) p[k] = (s_red[k][0] + s_red[k][1]) + (s_red[k][2] + s_red[k][3]);
+        for (int k = 0; k < 3; k++) p[k] = block_sum3(s_red, k);
     }
 }
 
@@ -224,15 +214,6 @@ eval_fold_kernel(int B, int C, int H, int W, int tiles /* gx * gy */, const floa
     }
 }
 
-MWin make_metrics_window()
-{
-    // utils/loss_utils.py:47-49: gauss = Tensor([exp(-(x-5)^2 / (2*1.5^2))]) / sum, in fp32 like torch.Tensor (= loss.hip's window)
-    MWin w; float sum = 0.f;
-    for (int i = 0; i < 11; i++) { w.g[i] = (float)exp(-(double)((i - 5) * (i - 5)) / (2.0 * 1.5 * 1.5)); sum += w.g[i]; }
-    for (int i = 0; i < 11; i++) w.g[i] /= sum;
-    return w;
-}
-
 }  // anonymous namespace
 }  // namespace moss
 
@@ -241,7 +222,7 @@ using namespace moss;
 extern "C" size_t moss_metrics_workspace_bytes(int B, int C, int H, int W)
 {
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return 0;
-    const size_t gx = (W + MT - 1) / MT, gy = (H + MT - 1) / MT;
+    const size_t gx = (W + LT - 1) / LT, gy = (H + LT - 1) / LT;
     return align_up((size_t)B * C * gx * gy * 3 * 4);
 }
 
@@ -254,7 +235,7 @@ extern "C" int moss_eval_metrics(const moss_eval_metrics_args* a, void* stream)
     if (C < 1 || C > MAX_CH || H <= 0 || W <= 0 || !a->state || !a->workspace) return MOSS_ERR_INVALID_ARG;
     if (a->per_view_capacity < 0 || (a->per_view_capacity > 0 && !a->per_view)) return MOSS_ERR_INVALID_ARG;
     if (a->workspace_bytes < moss_metrics_workspace_bytes(B, C, H, W)) return MOSS_ERR_INVALID_ARG;
-    const int gx = (W + MT - 1) / MT, gy = (H + MT - 1) / MT;
+    const int gx = (W + LT - 1) / LT, gy = (H + LT - 1) / LT;
     if ((long long)B * C * gx * gy > 0x7fffffffLL) return MOSS_ERR_INVALID_ARG;
     Views V;
     for (int v = 0; v < MAX_VIEWS; v++) {
@@ -263,7 +244,7 @@ extern "C" int moss_eval_metrics(const moss_eval_metrics_args* a, void* stream)
         V.bound[v] = on ? a->bound[v] : nullptr; V.out[v] = on ? a->out_image[v] : nullptr;
         if (on && (!V.image[v] || !V.gt[v])) return MOSS_ERR_INVALID_ARG;
     }
-    static const MWin win = make_metrics_window();
+    static const Win win = make_window();
     hipStream_t s = (hipStream_t)stream;
     float* partials = reinterpret_cast<float*>(a->workspace);
     hipLaunchKernelGGL(eval_tiles_kernel, dim3(B * C * gx * gy), dim3(256), 0, s, V, C, H, W, gx, gy, a->fill, win, partials);

@@ -16,6 +16,7 @@
 // Every sum has a fixed order and there is no atomic: results are bitwise reproducible.  moss_matrix_fisher_nll runs the same SVD
 // and quadrature on n general matrices, 16 per workgroup (one thread per SVD, one wave per quadrature).
 #include "common.h"
+#include "wave.h"
 #include "pose_math.h"
 
 namespace moss {
@@ -33,13 +34,6 @@ constexpr int WG = 256;
 constexpr int SV_H1 = 0, SV_H2 = 128, SV_JF = 256, SV_R = 328, SV_U = 400, SV_V = 608, SV_DET = 816, SV_CBAR = 840, SV_END = 864;
 static_assert(SV_END <= MOSS_POSE_HEAD_SAVED_FLOATS, "saved block");
 constexpr int NLL_PER_WG = 16;             // moss_matrix_fisher_nll: matrices per workgroup
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
 
 // one wave: 0.5 * trapezoid of the integrand (times u with `with_u`); every lane returns the same bits
 __device__ __forceinline__ float wave_integral(float si, float sj, float sk, bool with_u, int lane)

@@ -32,8 +32,6 @@ constexpr int P2_T = 32;               // pass 2: 32 x 32 tiles
 constexpr int P2_VR = 4;               // pass 2: rows per thread
 static_assert(P1_TH * P1_NQ == 256 && P2_T * (P2_T / P2_VR) == 256, "work split of a 256-thread workgroup");
 
-typedef float v2f __attribute__((ext_vector_type(2)));
-
 // h[r][k + 5]: weight of source column s + k in the horizontal window of widened column R s + r (zero outside |k| <= KH)
 struct PhaseTaps { float h[S3_MAX_R][11]; };
 
@@ -136,17 +134,9 @@ s3im_pass1_kernel(int C, int H, int W, int R, const float* __restrict__ img, con
                 const float w = taps.h[r][k - KH + 5];
                 m01 = __builtin_elementwise_fma(v2f{w, w}, v01[k], m01); m23 = __builtin_elementwise_fma(v2f{w, w}, v23[k], m23);
             }
-            // (loss.hip's per-pixel epilogue: the two variances enter only as their sum)
-            const float mu1 = m01.x, mu2 = m01.y, ess = m23.x, exy = m23.y;
-            const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
-            const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
-            const float s12 = exy - mu12;
-            const float a1 = 2.f * mu12 + C1, a2 = 2.f * s12 + C2, b1 = mu1_sq + mu2_sq + C1, b2 = (ess - mu1_sq - mu2_sq) + C2;
-            const float rb1 = __builtin_amdgcn_rcpf(b1), rb2 = __builtin_amdgcn_rcpf(b2), inv = rb1 * rb2;
-            const float S = a1 * a2 * inv;
-            const float dS_ds1 = -S * rb2;
-            const float dS_ds12 = 2.f * a1 * inv;
-            const float dS_dmu1 = 2.f * mu2 * a2 * inv - S * 2.f * mu1 * rb1 + dS_ds1 * (-2.f * mu1) + dS_ds12 * (-mu2);
+            // (the two variances enter only as their sum; the copies into locals keep the instruction order, as in loss.hip)
+            const SsimPoint p = ssim_point(m01.x, m01.y, m23.x, m23.y);
+            const float S = p.S, dS_ds1 = p.dS_ds1, dS_ds12 = p.dS_ds12, dS_dmu1 = p.dS_dmu1;
             if (own) ssim_v += S;
 #pragma unroll
             for (int k = 0; k < NK; k++) {
@@ -159,7 +149,7 @@ s3im_pass1_kernel(int C, int H, int W, int R, const float* __restrict__ img, con
 #pragma unroll
     for (int k = 0; k < NK; k++) { s_q[k][0][lr][q] = acc[k][0]; s_q[k][1][lr][q] = acc[k][1]; s_q[k][2][lr][q] = acc[k][2]; }
 #pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) ssim_v += __shfl_xor(ssim_v, d);
+    for (int d = 32; d >= 1; d >>= 1) ssim_v += __shfl_xor(ssim_v, d);       // (wave.h's wave_sum here changes the kernel's SGPR count)
     if ((tid & 63) == 0) s_red[tid >> 6] = ssim_v;
     __syncthreads();
     // the folded maps of the tile's own columns: G(s) = sum_k Q_k(s + k), k = -KH .. KH in that order
@@ -243,7 +233,7 @@ s3im_pass2_kernel(int C, int H, int W, int R, const float* __restrict__ img, con
         float a = 0.f;
         for (int i = tid; i < nblocks; i += 256) a += partials[i];
 #pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) a += __shfl_xor(a, d);
+        for (int d = 32; d >= 1; d >>= 1) a += __shfl_xor(a, d);       // (not wave.h's wave_sum: it moves an instruction, and one timing row was not explained)
         if ((tid & 63) == 0) s_red[tid >> 6] = a;
         __syncthreads();
         if (tid == 0) {

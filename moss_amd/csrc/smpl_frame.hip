@@ -14,12 +14,13 @@
 //   reduce         a grid over ranges of SF_GPW Gaussians, threads over the 9 (J - 1) pose features: the workgroup walks its Gaussians in
 //                  index order and accumulates sum_c posedirs[ids[i], c, k] g_d[i, c]; one partial vector per workgroup.  Traffic is
 //                  P rows of 12 (J - 1) 9 bytes from a table that lives in the caches; ids that coincide cost nothing extra.
-//   fold           one wave per feature adds the partials in workgroup order (as lbs_fold_kernel).
+//   fold           one wave per feature adds the partials in workgroup order (as lbs.hip's lbs_fold_kernel; wave.h's butterfly).
 //   chain adjoint  one workgroup: g_A_obs through the chain as a reverse walk of the tree, + the folded features, then
 //                  g_correct_Rs = rot_raw[1:]^T g_rot[1:].
 // Every sum is formed in float64 in a fixed order, nothing is atomic, every output element is written: bitwise reproducible.
 // Nothing is allocated, nothing synchronises, nothing is cleared with a memset.
 #include "common.h"
+#include "wave.h"
 
 namespace moss {
 
@@ -84,13 +85,6 @@ __device__ __forceinline__ void sf_stage_rotations(const SfIn& a, float* s_big, 
     __syncthreads();
 }
 
-__device__ __forceinline__ double sf_wave_sum(double v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
 // D rows and regressor shares of vertices [SF_VPB b, SF_VPB (b + 1)); partials [workgroup][J][2 shapes][3]
 __global__ void __launch_bounds__(SF_BLOCK)
 smpl_frame_offsets_kernel(SfIn a, float* __restrict__ D, double* __restrict__ partials)
@@ -136,7 +130,7 @@ smpl_frame_offsets_kernel(SfIn a, float* __restrict__ D, double* __restrict__ pa
             a0 = fma((double)p0[k], f, a0); a1 = fma((double)p1[k], f, a1);
             a2 = fma((double)p2[k], f, a2); a3 = fma((double)p3[k], f, a3);
         }
-        a0 = sf_wave_sum(a0); a1 = sf_wave_sum(a1); a2 = sf_wave_sum(a2); a3 = sf_wave_sum(a3);
+        a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2); a3 = wave_sum(a3);
         if (lane < 4 && r0 + lane < nrows) {
             const double acc = lane == 0 ? a0 : lane == 1 ? a1 : lane == 2 ? a2 : a3;
             D[(size_t)v0 * 3 + r0 + lane] = (float)(s_so[r0 + lane] + acc);
@@ -278,7 +272,7 @@ smpl_frame_fold_kernel(int F, int nblocks, const double* __restrict__ partials, 
     if (k >= F) return;
     double acc = 0.0;
     for (int b = lane; b < nblocks; b += 64) acc += partials[(size_t)b * F + k];
-    acc = sf_wave_sum(acc);
+    acc = wave_sum(acc);
     if (lane == 0) g_feat[k] = acc;
 }
 
