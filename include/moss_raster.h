@@ -886,6 +886,56 @@ typedef struct moss_densify_emit_args {
 int moss_densify_emit(const moss_densify_emit_args* args, void* stream);       /* scene/gaussian_model.py:511-524, :551-566, :606-616 */
 
 /*
+ * Carrying a densification decision OUT: the row changes of one event as ONE gather pass over the flat optimizer buffers, additive in
+ * ABI 7.  MOSS rebuilds every parameter tensor and both AdamW moments of each, one torch indexing / cat call at a time, in
+ * _prune_optimizer (scene/gaussian_model.py:377-394), prune_points (:396-411), cat_tensors_to_optimizer (:413-434) and
+ * densification_postfix (:436-454).  Here a ROW MAP says where each row of the new set comes from and one launch moves everything.
+ * Both entry points enqueue on `stream`, allocate nothing and read nothing back on the host; a refused call launches nothing.
+ *
+ * moss_rows_keep_map (the `[mask]` of :384-388 and the `torch.cat` of :422-426 as an index list): map_out receives the ASCENDING
+ *   indices i < rows_old with remove_mask[i] == 0 (bytes; a NULL mask keeps every row), then rows_old, rows_old + 1, ...,
+ *   rows_old + rows_app - 1; *count_out (one DEVICE int32) is the map's length.  map_out holds rows_old + rows_app entries; those
+ *   beyond the count stay untouched.  Stable compaction in two launches with no order-dependent atomic, as moss_densify_select's:
+ *   per-workgroup totals (wave ballots, an LDS sum), then every workgroup sums the totals before it and ranks its rows with a
+ *   ballot.  workspace: moss_rows_map_workspace_bytes(rows_old) bytes.  Bad arguments: MOSS_ERR_INVALID_ARG.
+ *
+ * moss_rows_relayout: for every tensor descriptor t and destination row r < rows_new, s = map[r]:
+ *     s <  rows_old:  dst[r] = src[s], dst_m[r] = src_m[s], dst_v[r] = src_v[s]                       (:384-388: the kept rows)
+ *     s >= rows_old:  dst[r] = app[s - rows_old], dst_m[r] = dst_v[r] = 0     (:422-423: torch.zeros_like(extension_tensor))
+ *   and the `pad_after` floats behind the tensor's last row are written as ZEROS in dst, dst_m and dst_v (the flat layout promises
+ *   zeros in its alignment gaps), so the destinations may be uninitialised memory.  A descriptor with use_map == 0 is not per-row:
+ *   its `width` floats (and moments) are copied as they are.  src_m / src_v / dst_m / dst_v may be NULL TOGETHER: a tensor without
+ *   optimizer state (:408-411, the statistics).  A map entry outside [0, rows_old + rows_app) writes a row of zeros and reads nothing.
+ *   ONE launch for all tensors: the lanes run along the destination's flat elements (a wave stores 256 contiguous bytes), the
+ *   source row of element e is map[e / width].
+ *   Refused, with the offending field named in moss_last_error(): a NULL block or a NULL required pointer, a negative size, width
+ *   < 1, pad_after outside 0..3, a destination range that overlaps a source range, the map or another destination
+ *   (MOSS_ERR_INVALID_ARG); num_tensors > MOSS_ROWS_MAX_TENSORS, rows * width >= 2^31 (MOSS_ERR_UNSUPPORTED).
+ */
+#define MOSS_ROWS_MAX_TENSORS 12
+typedef struct moss_rows_tensor {
+    const float* src;                        /* (rows_old, width); (width) with use_map == 0 */
+    const float* src_m; const float* src_v;  /* its two moments, or both NULL */
+    const float* app;                        /* (rows_app, width); NULL when rows_app == 0 or use_map == 0 */
+    float* dst;                              /* (rows_new, width) + pad_after floats */
+    float* dst_m; float* dst_v;              /* NULL exactly when src_m / src_v are */
+    int32_t width;                           /* floats per row */
+    int32_t pad_after;                       /* 0..3 floats of alignment gap behind the tensor */
+    int32_t use_map;                         /* 0: not per-row */
+    int32_t reserved;
+} moss_rows_tensor;
+typedef struct moss_rows_relayout_args {
+    int32_t rows_old, rows_app, rows_new;
+    int32_t num_tensors;                     /* <= MOSS_ROWS_MAX_TENSORS */
+    const int32_t* map;                      /* (rows_new), entries in [0, rows_old + rows_app) */
+    moss_rows_tensor tensors[MOSS_ROWS_MAX_TENSORS];
+} moss_rows_relayout_args;
+size_t moss_rows_map_workspace_bytes(int rows_old);
+int moss_rows_keep_map(int rows_old, const uint8_t* remove_mask, int rows_app, int* map_out, int* count_out, char* workspace,
+                       size_t workspace_bytes, void* stream);                  /* scene/gaussian_model.py:384-388, :396-411, :422-426 */
+int moss_rows_relayout(const moss_rows_relayout_args* args, void* stream);     /* scene/gaussian_model.py:377-394, :396-411, :413-434, :436-454 */
+
+/*
  * The rasterizer with every extension (ABI 7): one argument block per direction.  The fields are those of moss_raster_forward /
  * moss_raster_backward plus the extensions below; NULL or 0 in an extension field means "not used".  moss_raster_forward /
  * moss_raster_backward fill these blocks with no extension and `capacity` = -1.

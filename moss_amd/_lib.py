@@ -75,6 +75,12 @@ def _declare(lib):
     lib.moss_densify_select.argtypes = [_p, _p]
     lib.moss_densify_emit.restype = _i
     lib.moss_densify_emit.argtypes = [_p, _p]
+    lib.moss_rows_map_workspace_bytes.restype = C.c_size_t
+    lib.moss_rows_map_workspace_bytes.argtypes = [_i]
+    lib.moss_rows_keep_map.restype = _i
+    lib.moss_rows_keep_map.argtypes = [_i, _p, _i, _p, _p, _p, C.c_size_t, _p]
+    lib.moss_rows_relayout.restype = _i
+    lib.moss_rows_relayout.argtypes = [_p, _p]
     lib.moss_loss_workspace_bytes.restype = C.c_size_t
     lib.moss_loss_workspace_bytes.argtypes = [_i, _i, _i]
     lib.moss_photometric_loss.restype = _i
@@ -283,6 +289,22 @@ class DensifyEmitArgs(C.Structure):
                 ("lbs_weights", C.c_void_p), ("denom", C.c_void_p), ("table", C.c_void_p), ("noise", C.c_void_p), ("new_xyz", C.c_void_p),
                 ("new_features_dc", C.c_void_p), ("new_features_rest", C.c_void_p), ("new_opacity", C.c_void_p), ("new_scaling", C.c_void_p),
                 ("new_rotation", C.c_void_p), ("prune_mask", C.c_void_p)]
+
+
+ROWS_MAX_TENSORS = 12                                                               # MOSS_ROWS_MAX_TENSORS
+
+
+class RowsTensor(C.Structure):
+    """``moss_rows_tensor`` of include/moss_raster.h: one tensor of a ``moss_rows_relayout`` call."""
+    _fields_ = [("src", C.c_void_p), ("src_m", C.c_void_p), ("src_v", C.c_void_p), ("app", C.c_void_p), ("dst", C.c_void_p),
+                ("dst_m", C.c_void_p), ("dst_v", C.c_void_p), ("width", C.c_int32), ("pad_after", C.c_int32), ("use_map", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class RowsRelayoutArgs(C.Structure):
+    """``moss_rows_relayout_args`` of include/moss_raster.h (``moss_rows_relayout``: an event's row changes in one gather pass)."""
+    _fields_ = [("rows_old", C.c_int32), ("rows_app", C.c_int32), ("rows_new", C.c_int32), ("num_tensors", C.c_int32), ("map", C.c_void_p),
+                ("tensors", RowsTensor * ROWS_MAX_TENSORS)]
 
 
 OPT_BITS = {"means3D": 1, "sh": 2, "opacity": 4, "scales": 8, "rotations": 16}      # MOSS_OPT_*; position = index in the struct's arrays

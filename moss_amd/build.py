@@ -48,6 +48,7 @@ SOURCES = {
     "activations.hip": [],
     "densify.hip": [],
     "densify_decision.hip": [],
+    "rows.hip": [],
     "raster_api.hip": [],
 }
 

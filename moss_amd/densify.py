@@ -370,7 +370,7 @@ def merge_rows(index, ids, mask, xyz, features_dc, features_rest, opacity, scali
 
 
 def densify_and_prune_fused(pc, optimizer, stats, joint_F, lbs_weights, max_grad, min_opacity, extent, max_screen_size, t_vertices,
-                            kl_threshold=0.4, surface_mask=None, generator=None, percent_dense=0.01):
+                            kl_threshold=0.4, surface_mask=None, generator=None, percent_dense=0.01, one_pass=False):
     """``GaussianModel.densify_and_prune`` (:621-666) on a ``GaussianSet`` + ``FlatAdamW`` + ``DensifyStats``, in MOSS's order:
     clone-append; split-append and its prune; merge-append and its prune; the final prune -- every selection and every new row from
     the fused ops, every append / prune through ``pc.densification_postfix`` / ``pc.prune_points``.
@@ -382,6 +382,12 @@ def densify_and_prune_fused(pc, optimizer, stats, joint_F, lbs_weights, max_grad
     skipped.  ``joint_F`` (23,3,3) and ``lbs_weights`` (P,24) or (1,P,24) are the accumulated sums; ``t_vertices`` (V,3) or (1,V,3);
     ``surface_mask`` (P,) bool or None: the clone's surface-change test (:503-507), computed by the caller.  ``generator``: a
     ``torch.Generator`` of the device for the noise, or a callable ``n -> (n,3)`` standard normal draws.
+
+    ``one_pass=True``: every append and the prune that follows it are carried out by ONE gather pass over the optimizer's flat
+    buffers (``GaussianSet.relayout_points``, C ABI ``moss_rows_relayout``) instead of a torch pass per tensor and step -- the clone
+    is one re-layout, the split-append with its prune one, the merge-append with its prune one, the final prune one; same bits.  The
+    report then carries ``relayouts`` (at most 4), and ``host_reads`` includes the read of a row map's length where the phase's
+    count does not already give it (the merge, whose mask ``merge_rows`` extends on the device).
 
     Follow it with ``surgery.densification_event(pc, optimizer, rows_changed=True, context=..., graphed=..., probe=...)``.
     Returns a report: rows per phase and ``host_reads``, the reads of the decision ops themselves (one count per phase and the
@@ -396,6 +402,8 @@ def densify_and_prune_fused(pc, optimizer, stats, joint_F, lbs_weights, max_grad
         table = joint_tables(joint_F, denom)
         lbs_w = lbs_weights.detach().reshape(-1, JOINTS)
         report = {"rows_before": int(pc._xyz.shape[0]), "cloned": 0, "split": 0, "merged": 0, "pruned": 0}
+        if one_pass:
+            report["relayouts"] = 0
 
         def draw(n):
             if callable(generator):
@@ -409,6 +417,10 @@ def densify_and_prune_fused(pc, optimizer, stats, joint_F, lbs_weights, max_grad
         def neighbours(xyz):
             return knn(xyz[None], xyz[None], 2)[1][0]
 
+        def relayout(rows, remove, rows_new=None):
+            pc.relayout_points(optimizer, remove_mask=remove, new_rows=rows, stats=stats, rows_new=rows_new)
+            report["relayouts"] += 1
+
         def append(rows):
             pc.densification_postfix(rows["new_xyz"], rows["new_features_dc"], rows["new_features_rest"], rows["new_opacities"],
                                      rows["new_scaling"], rows["new_rotation"], optimizer, stats=stats)
@@ -420,7 +432,9 @@ def densify_and_prune_fused(pc, optimizer, stats, joint_F, lbs_weights, max_grad
         if int(pc._xyz.shape[0]) <= MAX_POINTS:
             xyz, fdc, frest, opa, scl, rot = gaussians()
             mask, index, n = select_clone(xyz, rot, scl, neighbours(xyz), accum, denom, kl_threshold=kl_threshold, surface_mask=surface_mask, **args)
-            if n:
+            if n and one_pass:
+                relayout(clone_rows(index, draw(n), xyz, fdc, frest, opa, scl, rot, lbs_w, denom, table), None)
+            elif n:
                 append(clone_rows(index, draw(n), xyz, fdc, frest, opa, scl, rot, lbs_w, denom, table))
             elif stats is not None:
                 stats.reset()                                 # (densification_postfix re-zeroes the statistics for zero new rows too, :452-454)
@@ -429,7 +443,9 @@ def densify_and_prune_fused(pc, optimizer, stats, joint_F, lbs_weights, max_grad
         if int(pc._xyz.shape[0]) <= MAX_POINTS:
             xyz, fdc, frest, opa, scl, rot = gaussians()
             mask, index, n = select_split(xyz, rot, scl, neighbours(xyz), accum, denom, kl_threshold=kl_threshold, **args)
-            if n:
+            if n and one_pass:                                # (the mask has exactly n rows set: the new row count needs no read)
+                relayout(split_rows(index, draw(2 * n), xyz, fdc, frest, opa, scl, rot), mask, int(xyz.shape[0]) + n)
+            elif n:
                 append(split_rows(index, draw(2 * n), xyz, fdc, frest, opa, scl, rot))
                 pc.prune_points(torch.cat((mask, tail(2 * n))), optimizer, stats=stats)
             elif stats is not None:
@@ -443,8 +459,11 @@ def densify_and_prune_fused(pc, optimizer, stats, joint_F, lbs_weights, max_grad
             if n >= 1:
                 mask = mask.clone()
                 rows = merge_rows(index, ids, mask, xyz, fdc, frest, opa, scl, rot)
-                append(rows)
-                pc.prune_points(torch.cat((mask, tail(n))), optimizer, stats=stats)
+                if one_pass:                                 # (merge_rows added the pairs' second members to the mask: its count is read)
+                    relayout(rows, mask)
+                else:
+                    append(rows)
+                    pc.prune_points(torch.cat((mask, tail(n))), optimizer, stats=stats)
             report["merged"] = n
         # ---- the final prune (:650-664)
         xyz, _, _, opa, scl, _ = gaussians()
@@ -452,7 +471,9 @@ def densify_and_prune_fused(pc, optimizer, stats, joint_F, lbs_weights, max_grad
         dist = knn(tv, xyz[None], 1)[0].reshape(-1)
         max_radii = stats.max_radii2D if stats is not None else torch.zeros((xyz.shape[0],), device=dev)
         mask, _, n, _ = _prune_select(opa, scl, max_radii, dist, min_opacity, extent, max_screen_size, True)
-        if n:
+        if n and one_pass:
+            relayout(None, mask, int(xyz.shape[0]) - n)
+        elif n:
             pc.prune_points(mask, optimizer, stats=stats)
         report["pruned"] = n
     report["rows_after"] = int(pc._xyz.shape[0])

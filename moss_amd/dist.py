@@ -83,6 +83,18 @@ def shard_views(num_views: int, rank: int, world: int):
     return list(range(rank, num_views, world))
 
 
+def flat_offsets(sizes):
+    """``GradBucket``'s layout rule for tensors of ``sizes`` floats: every tensor starts at a multiple of 4 floats.  Returns (offsets,
+    length of the region: the end of the last tensor, inner padding included).  Also used AHEAD of a re-layout, to place the rows of
+    the new shapes before any buffer exists (``FlatAdamW.relayout_rows``)."""
+    offsets, off = [], 0
+    for n in sizes:
+        off = (off + 3) // 4 * 4
+        offsets.append(off)
+        off += int(n)
+    return offsets, off
+
+
 class GradBucket:
     """One flat fp32 buffer for all parameter gradients (+4 slots for the loss and its three terms); a single all-reduce
     averages it.  Layout: [gradients, in parameter order, EVERY tensor starting at a multiple of 4 floats (16-byte aligned: the
@@ -107,12 +119,7 @@ class GradBucket:
     def _layout(self):
         """Offsets, the flat buffer and its views from the CURRENT shapes of ``self.params`` (constructor and ``relayout``)."""
         self.sizes = [p.numel() for p in self.params]
-        self.offsets, off = [], 0
-        for n in self.sizes:
-            off = (off + 3) // 4 * 4
-            self.offsets.append(off)
-            off += n
-        self.n_params = off                                # length of the parameter region (inner padding included)
+        self.offsets, self.n_params = flat_offsets(self.sizes)   # n_params: length of the parameter region (inner padding included)
         self.tail = (self.n_params + 3) // 4 * 4           # offset of the loss block
         self.n_exchange = self.tail + 4                    # what has to travel: gradients + loss block
         self.shard_len, padded = shard_layout(self.n_exchange, self.world)

@@ -120,6 +120,58 @@ class GaussianSet(nn.Module):
         if stats is not None:
             stats.reset(self._xyz.shape[0])
 
+    def relayout_points(self, optimizer, remove_mask=None, new_rows=None, stats=None, order=None, rows_new=None):
+        """``densification_postfix(new_rows...)`` followed by ``prune_points(remove_mask)`` (scene/gaussian_model.py:436-454, :396-411)
+        as ONE pass over the optimizer's flat buffers (``FlatAdamW.relayout_rows``): same parameters, moments and statistics, bit for
+        bit.  ``new_rows``: a dict with the six tensors of ``densification_postfix`` (``new_xyz`` ...), or None; ``remove_mask``: bool,
+        True = remove, over the set AFTER the append (a mask over the OLD rows alone is accepted too when rows are appended: the new
+        rows then all stay).  Statistics as MOSS: an append re-creates all three as zeros at the new size, a prune alone keeps the
+        surviving rows (they ride the same launch).  ``order``: a callable ``xyz_new -> permutation`` (``densify.spatial_order``) whose
+        result is composed with the map -- the rows come out in that order at no extra pass.  ``rows_new``: the number of surviving rows
+        if the caller knows it (saves the host read of the map's length).  Returns the row map (int32): entry r is the row of
+        ``cat(old rows, new rows)`` that became row r."""
+        from .surgery import rows_map
+        opt = self._flat(optimizer)
+        if not hasattr(opt, "relayout_rows"):
+            raise TypeError("relayout_points drives a moss_amd.optim.FlatAdamW")
+        dev = self._xyz.device
+        rows_old = int(self._xyz.shape[0])
+        rows_app = 0 if new_rows is None else int(new_rows["new_xyz"].shape[0])
+        appended = None
+        if rows_app:
+            if self.unified_features:
+                appended = {id(self._features): torch.cat((new_rows["new_features_dc"], new_rows["new_features_rest"]), dim=1)}
+            else:
+                appended = {id(self._features_dc): new_rows["new_features_dc"], id(self._features_rest): new_rows["new_features_rest"]}
+            appended.update({id(self._xyz): new_rows["new_xyz"], id(self._opacity): new_rows["new_opacities"],
+                             id(self._scaling): new_rows["new_scaling"], id(self._rotation): new_rows["new_rotation"]})
+            index = {id(p): i for i, p in enumerate(opt.bucket.params)}
+            appended = {index[k]: v for k, v in appended.items()}
+        if remove_mask is None:
+            row_map = torch.arange(rows_old + rows_app, dtype=torch.int32, device=dev)
+        else:
+            mask = remove_mask.to(dev).bool().reshape(-1)
+            if int(mask.numel()) == rows_old + rows_app:
+                row_map, _ = rows_map(mask, 0, count=rows_new)
+            elif int(mask.numel()) == rows_old:
+                row_map, _ = rows_map(mask, rows_app, count=rows_new)
+            else:
+                raise ValueError(f"remove mask of {int(mask.numel())} entries for {rows_old} + {rows_app} Gaussians")
+        if not rows_app and int(row_map.numel()) == rows_old:
+            return row_map                                   # (no row removed, none new: nothing moves -- as prune_points' caller skips it)
+        if order is not None:
+            with torch.no_grad():
+                xyz_all = self._xyz.detach() if not rows_app else torch.cat((self._xyz.detach(), new_rows["new_xyz"].detach().to(dev).float()), dim=0)
+                row_map = row_map[order(xyz_all[row_map.long()]).to(dev)].contiguous()
+        ride = stats is not None and not rows_app
+        extra = [stats.xyz_gradient_accum, stats.denom, stats.max_radii2D] if ride else None
+        out = opt.relayout_rows(row_map, appended, check=False, rows_old=rows_old, extra=extra)
+        if ride:
+            stats.xyz_gradient_accum, stats.denom, stats.max_radii2D = out
+        elif stats is not None:
+            stats.reset(int(row_map.numel()))
+        return row_map
+
     def reset_opacity(self, optimizer):
         """``reset_opacity`` (scene/gaussian_model.py:314-317): opacity = min(opacity, 0.01) in logits, both moments of it zeroed."""
         with torch.no_grad():

@@ -66,7 +66,8 @@ class FlatAdamW:
     def _adopt_layout(self, values, exp_avg, exp_avg_sq):
         """(Re)build the flat buffers for the bucket's CURRENT layout: ``values[i]`` becomes parameter i (re-homed as a view of
         ``flat_params``), ``exp_avg[i]`` / ``exp_avg_sq[i]`` its moments (None: zeros -- a fresh optimizer).  The constructor and the
-        row surgery (``prune_rows`` / ``append_rows``) end here; learning rates that ``set_learning_rates`` changed are kept."""
+        row surgery (``prune_rows`` / ``append_rows``) end here; learning rates that ``set_learning_rates`` changed are kept.
+        Allocate + copy; the bookkeeping is ``_adopt_segments`` (shared with ``relayout_rows``, whose kernel has filled the buffers)."""
         bucket = self.bucket
         params = bucket.params
         total = bucket.n_params                              # (every tensor starts 16-byte aligned: GradBucket.offsets)
@@ -74,11 +75,26 @@ class FlatAdamW:
         # (sharded: the parameter buffer mirrors the bucket's padded layout -- parameters, loss block, padding -- so that the
         # all-gather of the updated shards is in place)
         self.flat_params = torch.zeros(bucket.flat.numel() if self.shard is not None else total, dtype=torch.float32, device=dev)
-        old_lr = {i: (float(self.seg_lr[i]), float(self.seg_lr2[i])) for i in range(getattr(self, "nseg", 0))}
-        ends, lrs, periods, splits, lr2s = [], [], [], [], []
         for i, (p, n, off) in enumerate(zip(params, bucket.sizes, bucket.offsets)):
             self.flat_params[off:off + n].copy_(values[i].reshape(-1))
             p.data = self.flat_params[off:off + n].view(values[i].shape)      # the parameter now lives in the flat buffer
+        self._adopt_segments()
+        self.exp_avg = torch.zeros(max(self.count, 1), dtype=torch.float32, device=dev)
+        self.exp_avg_sq = torch.zeros(max(self.count, 1), dtype=torch.float32, device=dev)
+        if exp_avg is not None:                              # (row surgery: unsharded by construction)
+            for m, v, n, off in zip(exp_avg, exp_avg_sq, bucket.sizes, bucket.offsets):
+                self.exp_avg[off:off + n].copy_(m.reshape(-1)); self.exp_avg_sq[off:off + n].copy_(v.reshape(-1))
+
+    def _adopt_segments(self):
+        """The bookkeeping of a (re-)layout, from the bucket's CURRENT offsets: the learning-rate segments (rates a schedule changed
+        survive), the element count, the shard range and its gradient buffer.  No parameter or moment is touched."""
+        bucket = self.bucket
+        params = bucket.params
+        total = bucket.n_params
+        dev = params[0].device
+        old_lr = {i: (float(self.seg_lr[i]), float(self.seg_lr2[i])) for i in range(getattr(self, "nseg", 0))}
+        ends, lrs, periods, splits, lr2s = [], [], [], [], []
+        for i, p in enumerate(params):
             # a segment runs to the (aligned) start of the next tensor: the <= 3 floats of padding behind a tensor are zeros with zero
             # gradients, which the update leaves zero
             ends.append(bucket.offsets[i + 1] if i + 1 < len(params) else total); lrs.append(self._lr_of[id(p)])
@@ -103,11 +119,6 @@ class FlatAdamW:
             self.first, self.count = first, min(first + per, total) - first          # (the loss block and the padding are no parameters)
             # the reduce-scattered gradients of this rank's shard land here (equal-sized on every rank: the collective needs that)
             self.grad_shard = torch.zeros(per, dtype=torch.float32, device=dev)
-        self.exp_avg = torch.zeros(max(self.count, 1), dtype=torch.float32, device=dev)
-        self.exp_avg_sq = torch.zeros(max(self.count, 1), dtype=torch.float32, device=dev)
-        if exp_avg is not None:                              # (row surgery: unsharded by construction)
-            for m, v, n, off in zip(exp_avg, exp_avg_sq, bucket.sizes, bucket.offsets):
-                self.exp_avg[off:off + n].copy_(m.reshape(-1)); self.exp_avg_sq[off:off + n].copy_(v.reshape(-1))
 
     # ---- the update applied by the rasterizer's backward kernel itself -----------------------------------------------------------
     def fuse_into_backward(self, context, means3D=None, sh=None, opacity=None, scales=None, rotations=None, local_only=False):
@@ -393,6 +404,140 @@ class FlatAdamW:
             else:
                 vals.append(p.data.clone()); ms.append(m.clone()); vs.append(v.clone())
         self._relayout(vals, ms, vs)
+
+    @torch.no_grad()
+    def relayout_rows(self, row_map: torch.Tensor, appended=None, check=True, rows_old=None, extra=None):
+        """``append_rows(appended)`` followed by a gather of the rows ``row_map`` on every row-parameter and both its moments
+        (``_prune_optimizer`` :377-394 after ``cat_tensors_to_optimizer`` :413-434) -- in ONE pass over memory: the new offsets are
+        computed from the new shapes first, the three new flat buffers are allocated once (uninitialised), and one launch (C ABI
+        ``moss_rows_relayout``) gathers from the old flat buffers straight into them, zero moments for appended rows and zeros in the
+        alignment gaps included.  Same bits as the two calls; parameters that are not per-row keep values and moments, the shared
+        step count stays, the Parameter objects stay, the fused step is re-armed.
+
+        ``row_map``: integer tensor, one entry per row of the result: ``s < rows_old`` takes old row ``s``, ``s >= rows_old`` takes row
+        ``s - rows_old`` of ``appended`` (``surgery.rows_map`` builds the map of a prune mask).  ``appended``: as ``append_rows``; every
+        row-parameter must be named, with the same number of rows.  ``rows_old``: the row count that marks a row-parameter (default:
+        that of the parameters named in ``appended``, else of the bucket's first parameter).  ``check=True`` validates the map's range
+        with one host read (an entry out of range would otherwise give a row of zeros).  ``extra``: float32 tensors of ``rows_old``
+        rows WITHOUT optimizer state (the densification statistics) gathered by the same launch -- only when nothing is appended;
+        their gathered copies are returned as a list (else None).  CPU tensors take the torch restatement."""
+        if self.shard is not None:
+            raise RuntimeError("row surgery on a SHARDED FlatAdamW: a parameter row's moments live on several ranks; use the all-reduce "
+                               "exchange while the set densifies (or gather, rebuild and re-shard)")
+        from ._lib import ROWS_MAX_TENSORS, RowsRelayoutArgs
+        from .dist import flat_offsets
+        bucket = self.bucket
+        params = bucket.params
+        dev = self.flat_params.device
+        index = {id(p): i for i, p in enumerate(params)}
+        ext = {}
+        for key, t in (appended or {}).items():
+            i = key if isinstance(key, int) else index[id(key)]
+            e = t.detach().to(device=dev, dtype=torch.float32).contiguous()
+            if tuple(e.shape[1:]) != tuple(params[i].shape[1:]):
+                raise ValueError(f"relayout_rows: rows of shape {tuple(e.shape)} do not extend a parameter of shape {tuple(params[i].shape)}")
+            ext[i] = e
+        rows_app = {int(e.shape[0]) for e in ext.values()}
+        olds = {int(params[i].shape[0]) for i in ext}
+        if len(rows_app) > 1 or len(olds) > 1:
+            raise ValueError("relayout_rows: the appended tensors must extend parameters of ONE row count by ONE number of rows")
+        rows_app = rows_app.pop() if rows_app else 0
+        if rows_old is None:
+            rows_old = olds.pop() if olds else next(int(p.shape[0]) for p in params if p.dim() >= 1)
+        rows_old = int(rows_old)
+        if rows_app == 0:
+            ext = {}
+        is_row = self._row_params(rows_old)
+        if rows_app and [i for i, r in enumerate(is_row) if r] != sorted(ext):
+            raise ValueError("relayout_rows: `appended` must name every parameter of rows_old rows (and no other)")
+        extra = list(extra or [])
+        if extra and rows_app:
+            raise ValueError("relayout_rows: `extra` tensors ride along only when nothing is appended")
+        for t in extra:
+            if t.dtype != torch.float32 or t.device != dev or t.dim() < 1 or int(t.shape[0]) != rows_old:
+                raise ValueError("relayout_rows: an `extra` tensor must be float32, on the optimizer's device, with rows_old rows")
+        row_map = row_map.to(dev)
+        if row_map.dim() != 1 or row_map.dtype not in (torch.int32, torch.int64):
+            raise ValueError("relayout_rows: row_map must be a 1-D int32 / int64 tensor")
+        rows_new = int(row_map.numel())
+        if check and rows_new and (int(row_map.min()) < 0 or int(row_map.max()) >= rows_old + rows_app):
+            raise ValueError(f"relayout_rows: row_map has entries outside [0, {rows_old + rows_app})")
+        if dev.type != "cuda":
+            return self._relayout_rows_torch(row_map, ext, is_row, extra)
+        if len(params) + len(extra) > ROWS_MAX_TENSORS:
+            raise ValueError(f"relayout_rows: more than {ROWS_MAX_TENSORS} tensors in one launch")
+        row_map = row_map.to(torch.int32).contiguous()
+        fused = getattr(self, "_fused_args", None) if self.fused is not None else None
+        cx = getattr(self, "_fused_context", None)
+        # the new layout, before anything is written
+        shapes = [((rows_new,) + tuple(p.shape[1:])) if r else tuple(p.shape) for p, r in zip(params, is_row)]
+        sizes = [int(torch.Size(s).numel()) for s in shapes]
+        offsets, total = flat_offsets(sizes)
+        old = (self.flat_params, self.exp_avg, self.exp_avg_sq)
+        new = tuple(torch.empty(max(total, 1), dtype=torch.float32, device=dev) for _ in range(3))
+        if total == 0:
+            for t in new:
+                t.zero_()
+        a = RowsRelayoutArgs()
+        a.rows_old, a.rows_app, a.rows_new, a.map = rows_old, rows_app, rows_new, row_map.data_ptr()
+        k = 0
+        for i, (p, r, n, off) in enumerate(zip(params, is_row, sizes, offsets)):
+            pad = (offsets[i + 1] if i + 1 < len(params) else total) - (off + n)
+            if n + pad == 0:
+                continue                                     # (no row left and no gap behind: nothing to write)
+            d = a.tensors[k]
+            k += 1
+            off_old = bucket.offsets[i]
+            d.src, d.src_m, d.src_v = (t.data_ptr() + 4 * off_old for t in old)
+            d.dst, d.dst_m, d.dst_v = (t.data_ptr() + 4 * off for t in new)
+            d.app = ext[i].data_ptr() if i in ext else None
+            d.use_map, d.pad_after = int(r), pad
+            d.width = max(int(torch.Size(p.shape[1:]).numel()), 1) if r else n
+        gathered = []
+        for t in extra:
+            t = t.contiguous()
+            g = torch.empty((rows_new,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev)
+            gathered.append((t, g))
+            if g.numel() == 0:
+                continue
+            d = a.tensors[k]
+            k += 1
+            d.src, d.dst, d.use_map, d.pad_after = t.data_ptr(), g.data_ptr(), 1, 0
+            d.width = int(torch.Size(t.shape[1:]).numel())
+        a.num_tensors = k
+        call("moss_rows_relayout", dev, C.addressof(a))
+        # adopt the buffers the kernel has filled: no second copy
+        self.flat_params, self.exp_avg, self.exp_avg_sq = new
+        for p, n, off, shape in zip(params, sizes, offsets, shapes):
+            p.data = self.flat_params[off:off + n].view(shape)
+        bucket.relayout()
+        if list(bucket.offsets) != list(offsets) or bucket.n_params != total:
+            raise RuntimeError("relayout_rows: the bucket laid itself out differently from the offsets the rows were written at")
+        self._adopt_segments()
+        if self.sh_active_degree < 3:
+            self._verify_sh_inactive()                       # (appended rows may carry non-zero coefficients above the active degree)
+        if fused is not None:
+            self.fuse_into_backward(cx, local_only=fused[1], **fused[0])
+        return [g for _, g in gathered] if extra else None
+
+    def _relayout_rows_torch(self, row_map, ext, is_row, extra=()):
+        """``relayout_rows`` restated with torch indexing (what it does on CPU tensors, and what the tests compare the kernel with):
+        ``cat`` the appended rows with zero moments, index with the map, then the two-copy ``_relayout``."""
+        idx = row_map.long()
+        vals, ms, vs = [], [], []
+        for i, (p, r) in enumerate(zip(self.bucket.params, is_row)):
+            m, v = self._moments_of(i)
+            if r:
+                e = ext.get(i)
+                x = p.data if e is None else torch.cat((p.data, e), dim=0)
+                if e is not None:
+                    m, v = torch.cat((m, torch.zeros_like(e)), dim=0), torch.cat((v, torch.zeros_like(e)), dim=0)
+                vals.append(x[idx].clone()); ms.append(m[idx].clone()); vs.append(v[idx].clone())
+            else:
+                vals.append(p.data.clone()); ms.append(m.clone()); vs.append(v.clone())
+        gathered = [t[idx.to(t.device)].contiguous() for t in extra]
+        self._relayout(vals, ms, vs)
+        return gathered if extra else None
 
     @torch.no_grad()
     def reset_rows(self, param, values: torch.Tensor):

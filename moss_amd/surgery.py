@@ -23,7 +23,7 @@ import time
 
 import torch
 
-__all__ = ["densification_event"]
+__all__ = ["densification_event", "rows_map", "rows_map_torch", "relayout_rows_torch"]
 
 
 def reserve_workspace(nbytes, device):
@@ -36,8 +36,67 @@ def reserve_workspace(nbytes, device):
     del t
 
 
+def rows_map(remove_mask, rows_app=0, rows_old=None, count=None):
+    """The row map of "drop the rows where ``remove_mask`` is True, then keep ``rows_app`` appended rows" (C ABI
+    ``moss_rows_keep_map``): the ascending indices of the surviving old rows followed by ``rows_old .. rows_old + rows_app - 1`` -- what
+    ``FlatAdamW.relayout_rows`` takes.  ``remove_mask``: (rows_old,) bool / uint8 on the GPU, or None (every row stays; give
+    ``rows_old``).  Returns ``(map int32 (count,), count)``.  The count is read from the device (one host read, counted by
+    ``densify.host_reads()``) unless the caller knows it and passes ``count``.  CPU tensors: :func:`rows_map_torch`."""
+    import ctypes as C
+    from . import _lib, densify
+    if remove_mask is None:
+        if rows_old is None:
+            raise ValueError("rows_map: rows_old is needed when there is no mask")
+        return torch.arange(int(rows_old) + int(rows_app), dtype=torch.int32), int(rows_old) + int(rows_app)
+    if not remove_mask.is_cuda:
+        return rows_map_torch(remove_mask, rows_app)
+    dev = remove_mask.device
+    mask = remove_mask.reshape(-1)
+    mask = (mask if mask.dtype in (torch.bool, torch.uint8) else mask != 0).contiguous()
+    rows_old, rows_app = int(mask.numel()), int(rows_app)
+    out = torch.empty((max(rows_old + rows_app, 1),), dtype=torch.int32, device=dev)
+    n_dev = torch.empty((1,), dtype=torch.int32, device=dev)
+    nbytes = int(_lib.lib().moss_rows_map_workspace_bytes(rows_old))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    _lib.call("moss_rows_keep_map", dev, rows_old, mask.data_ptr(), rows_app, out.data_ptr(), n_dev.data_ptr(), ws.data_ptr(), C.c_size_t(nbytes))
+    if count is None:
+        count = int(n_dev.item())                            # THE host read of the map: its length
+        densify._host_reads += 1
+    return out[:int(count)], int(count)
+
+
+def rows_map_torch(remove_mask, rows_app=0):
+    """:func:`rows_map` restated in torch (``nonzero`` of the kept rows, then the appended rows' indices)."""
+    mask = remove_mask.reshape(-1) != 0
+    rows_old = int(mask.numel())
+    kept = torch.nonzero(~mask).reshape(-1).to(torch.int32)
+    m = torch.cat((kept, torch.arange(rows_old, rows_old + int(rows_app), dtype=torch.int32, device=mask.device)))
+    return m, int(m.numel())
+
+
+def relayout_rows_torch(optimizer, row_map, appended=None, rows_old=None):
+    """``FlatAdamW.relayout_rows`` restated with plain torch indexing on the optimizer's own tensors (any device): ``cat`` the appended
+    rows (zero moments), index parameters and moments with the map, rebuild the flat buffers by copy.  What the tests compare the
+    one-pass kernel with."""
+    index = {id(p): i for i, p in enumerate(optimizer.bucket.params)}
+    dev = optimizer.flat_params.device
+    ext = {(k if isinstance(k, int) else index[id(k)]): t.detach().to(device=dev, dtype=torch.float32) for k, t in (appended or {}).items()}
+    if rows_old is None:
+        rows_old = next(int(optimizer.bucket.params[i].shape[0]) for i in ext) if ext else next(int(p.shape[0]) for p in optimizer.bucket.params if p.dim() >= 1)
+    with torch.no_grad():
+        return optimizer._relayout_rows_torch(row_map.to(dev), ext, optimizer._row_params(int(rows_old)))
+
+
+def _concat_appends(appends):
+    """Several ``densification_postfix`` dicts as one (applied in order, the rows end up in the same places)."""
+    keys = ("new_xyz", "new_features_dc", "new_features_rest", "new_opacities", "new_scaling", "new_rotation")
+    if len(appends) == 1:
+        return {k: appends[0][k] for k in keys}
+    return {k: torch.cat([a[k] for a in appends], dim=0) for k in keys}
+
+
 def densification_event(pc, optimizer, *, append=None, prune=None, reset_opacity=False, stats=None, context=None, graphed=None,
-                        probe=None, per_gaussian=None, after_surgery=None, rows_changed=False):
+                        probe=None, per_gaussian=None, after_surgery=None, rows_changed=False, one_pass=False, keep_spatial_order=False):
     """Carry out one event.  ``append``: dict with the six tensors of ``densification_postfix`` (``new_xyz, new_features_dc,
     new_features_rest, new_opacities, new_scaling, new_rotation``) or a list of such dicts (MOSS appends twice per event: clones, then
     splits) -- applied first, in order; ``prune``: bool mask over the Gaussians AFTER the appends, True = remove (``prune_points``);
@@ -46,7 +105,11 @@ def densification_event(pc, optimizer, *, append=None, prune=None, reset_opacity
     and pruned with the mask; the re-indexed dict is returned in the report and -- BEFORE the probe and the re-capture, whose step
     function reads those tables -- handed to ``after_surgery(per_gaussian)``.  ``rows_changed=True``: the rows of ``pc`` were appended and
     pruned BEFORE this call (``densify.densify_and_prune_fused``): the tail of an event -- capacity re-learning, probe, re-capture --
-    runs although this call itself changes no row.
+    runs although this call itself changes no row.  ``one_pass=True``: all appends, in order, and the prune are folded into ONE
+    re-layout (``GaussianSet.relayout_points``: one gather kernel over the flat buffers instead of a torch pass per tensor and step)
+    -- same bits; ``keep_spatial_order=True`` (needs ``one_pass``; used only when ``pc.spatially_ordered`` is set): the rows come out
+    along the Morton curve of the NEW positions (``densify.spatial_order``), as if ``pc.reorder_spatially(optimizer)`` had followed,
+    ``pc.spatially_ordered`` stays set, and statistics and ``per_gaussian`` tables follow the same order.
 
     Returns a report: rows before / after, what was re-captured, and the host-side cost of the event in milliseconds (it
     synchronises the device: the event is outside the step's asynchronous flow by nature)."""
@@ -66,6 +129,31 @@ def densification_event(pc, optimizer, *, append=None, prune=None, reset_opacity
     per_gaussian = dict(per_gaussian or {})
     appends = [] if append is None else ([append] if isinstance(append, dict) else list(append))
     shape_changed = bool(rows_changed)
+    if keep_spatial_order and not one_pass:
+        raise ValueError("keep_spatial_order needs one_pass=True: the order is composed into the one-pass row map")
+    kept_order = False
+    if one_pass:
+        appends = [a for a in appends if int(a["new_xyz"].shape[0]) > 0]
+        rows_app = sum(int(a["new_xyz"].shape[0]) for a in appends)
+        if prune is not None and int(prune.numel()) != rows_before + rows_app:
+            raise ValueError(f"prune mask of {int(prune.numel())} entries for {rows_before + rows_app} Gaussians (it indexes the set AFTER the appends)")
+        if per_gaussian and any("source" not in a for a in appends):
+            raise ValueError("per_gaussian tensors need append['source']: the Gaussian each new row derives from")
+        if rows_app or prune is not None:
+            order = None
+            if keep_spatial_order and getattr(pc, "spatially_ordered", False):
+                from .densify import spatial_order
+                order = spatial_order
+            # (one host read inside, when there is a mask: the number of rows that stay; no row removed and none new: nothing is done)
+            row_map = pc.relayout_points(optimizer, remove_mask=prune, new_rows=_concat_appends(appends) if appends else None, stats=stats,
+                                         order=order)
+            if rows_app or int(row_map.numel()) != rows_before:
+                for k, t in list(per_gaussian.items()):
+                    for a in appends:
+                        t = torch.cat((t, t[a["source"].to(t.device)]), dim=0)
+                    per_gaussian[k] = t[row_map.to(t.device).long()].contiguous()
+                shape_changed, kept_order = True, order is not None
+        appends, prune = [], None
     for a in appends:
         n_new = int(a["new_xyz"].shape[0])
         if n_new == 0:
@@ -98,7 +186,7 @@ def densification_event(pc, optimizer, *, append=None, prune=None, reset_opacity
     t1 = t2 = t3 = lap()
     m1 = m2 = counters()[0]
     if shape_changed:
-        if getattr(pc, "spatially_ordered", False):
+        if getattr(pc, "spatially_ordered", False) and not kept_order:
             pc.spatially_ordered = False                     # (appended rows sit at the end: index neighbours are no longer spatial neighbours)
         if context is not None:
             context.relearn_capacity()
