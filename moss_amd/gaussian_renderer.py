@@ -116,10 +116,15 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
             # ``pipe.lbs_weights_in_op`` (an addition, default off) is set: then it runs as the fused HIP op of moss_amd/lbs_weights.py
             # on the module's parameters (a module of another layout than MOSS's CrossAttention_lbs raises: there is no fallback)
             from .pose import pose_head_fused
-            pose_out = pose_head_fused(pc.auto_regression, viewpoint_camera.smpl_param['poses'], viewpoint_camera.smpl_param['pose_rotmats'])
+            # ``pipe.net_grad_sink`` (an addition, default none): ``param -> tensor or None`` -- where the two network ops' backward
+            # kernels write their weight gradients (``GradBucket.sink_for`` of the networks' optimizer: moss_amd/train.py)
+            net_sink = getattr(pipe, "net_grad_sink", None)
+            sink_kw = {} if net_sink is None else {"grad_sink": net_sink}      # (without a sink the two calls are what they always were)
+            pose_out = pose_head_fused(pc.auto_regression, viewpoint_camera.smpl_param['poses'], viewpoint_camera.smpl_param['pose_rotmats'],
+                                       **sink_kw)
             if getattr(pipe, "lbs_weights_in_op", False):
                 from .lbs_weights import cross_attention_lbs_fused
-                lbs_weights = cross_attention_lbs_fused(pc.cross_attention_lbs, means3D[None], pose_out["Rs"])
+                lbs_weights = cross_attention_lbs_fused(pc.cross_attention_lbs, means3D[None], pose_out["Rs"], **sink_kw)
             else:
                 lbs_weights = pc.cross_attention_lbs(means3D[None], pose_out["Rs"])
             correct_Rs = pose_out["Rs"].reshape(1, 23, 3, 3)

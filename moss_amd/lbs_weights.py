@@ -112,7 +112,7 @@ def net_parameters(net):
 
 class _LbsWeightNet(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, Rs, *params):
+    def forward(ctx, x, Rs, sink, *params):
         from ._lib import LbsWeightNetArgs, call, lib
         dev, P = x.device, int(x.shape[0])
         out = torch.empty((1, P, FEATURE_DIM), dtype=torch.float32, device=dev)
@@ -125,6 +125,7 @@ class _LbsWeightNet(torch.autograd.Function):
                 a.params[i] = p.data_ptr()
             call("moss_lbs_weight_net_forward", dev, ctypes.byref(a))
         ctx.save_for_backward(x, Rs, saved, *params)
+        ctx.sink = sink
         return out
 
     @staticmethod
@@ -138,6 +139,15 @@ class _LbsWeightNet(torch.autograd.Function):
         else:
             flat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)             # every element is written by the kernels
         g_x, g_Rs, *grads = flat.split(sizes)
+        grads = [g.view(p.shape) for g, p in zip(grads, params)]
+        if ctx.sink is not None:                                                         # (a sink replaces the parameter's scratch slice)
+            from .pose import _sunk
+            sunk = [ctx.sink(i) for i in range(len(params))]
+            grads = [_sunk(t, g) for t, g in zip(sunk, grads)]
+            if P == 0:                                                                   # (no kernel runs: the sinks are zeroed here)
+                for t in sunk:
+                    if t is not None:
+                        t.zero_()
         if P > 0:
             g_out = g_out.reshape(P, FEATURE_DIM).float().contiguous()
             nbytes = lib().moss_lbs_weight_net_workspace_bytes(P)
@@ -148,15 +158,22 @@ class _LbsWeightNet(torch.autograd.Function):
             for i, (p, g) in enumerate(zip(params, grads)):
                 a.params[i], a.grads[i] = p.data_ptr(), g.data_ptr()
             call("moss_lbs_weight_net_backward", dev, ctypes.byref(a))
-        return (g_x.view(P, 3), g_Rs.view(23, 3, 3), *[g.view(p.shape) for g, p in zip(grads, params)])
+        return (g_x.view(P, 3), g_Rs.view(23, 3, 3), None, *grads)
 
 
-def cross_attention_lbs_fused(net, xyz, Rs):
+def cross_attention_lbs_fused(net, xyz, Rs, grad_sink=None):
     """MOSS's ``pc.cross_attention_lbs(xyz, Rs)`` as the fused HIP op: one launch forward, three backward.
 
     ``net``: MOSS's ``CrossAttention_lbs`` instance or anything with the same parameter names and shapes (float32, contiguous, on the
     GPU); ``xyz`` (1,P,3) or (P,3); ``Rs`` (23,3,3) or (1,23,3,3).  Returns (1,P,24).  Gradients flow to ``xyz``, ``Rs`` and the 16
-    parameters the forward reads (``out_layer`` / ``gate_proj`` are not read: their ``.grad`` stays ``None``, as with MOSS)."""
+    parameters the forward reads (``out_layer`` / ``gate_proj`` are not read: their ``.grad`` stays ``None``, as with MOSS).
+
+    ``grad_sink``: a callable ``param -> tensor or None`` (the contract of ``GradBucket.sink_for``), asked once per parameter in the
+    backward.  Where it returns a tensor (contiguous float32, the parameter's shape) the backward kernels write that parameter's
+    gradient THERE and autograd receives that tensor; where it returns None the gradient stays a slice of the op's scratch tensor.  The
+    kernels write every element of every weight gradient, so a sink is OVERWRITTEN, not accumulated into (with no Gaussian at all no
+    kernel runs and the sinks are zeroed): a sink must hand out each destination at most once per backward pass
+    (``GradBucket.sink_for`` does).  The gradients of ``xyz`` and ``Rs`` are not sunk."""
     params = net_parameters(net)
     for name, t in (("xyz", xyz), ("Rs", Rs), *zip(PARAM_NAMES, params)):
         if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
@@ -174,7 +191,8 @@ def cross_attention_lbs_fused(net, xyz, Rs):
         if tuple(p.shape[:2]) != shape or p.numel() != _numel(shape) or p.dtype != torch.float32 or p.device != dev or not p.is_contiguous():
             raise ValueError(f"cross_attention_lbs_fused: {name} must be a contiguous float32 tensor of shape {shape} (a Conv1d weight: "
                              f"{shape + (1,)}) on {dev}, got {tuple(p.shape)} {p.dtype} on {p.device}")
-    return _LbsWeightNet.apply(xyz.reshape(-1, 3).contiguous(), Rs.reshape(23, 3, 3).contiguous(), *params)
+    sink = None if grad_sink is None else (lambda i: grad_sink(params[i]))
+    return _LbsWeightNet.apply(xyz.reshape(-1, 3).contiguous(), Rs.reshape(23, 3, 3).contiguous(), sink, *params)
 
 
 def _numel(shape):

@@ -34,19 +34,28 @@ class FlatAdamW:
         """capturable=True keeps the step counter on the device (``moss_adamw_flat_ex`` with a ``step_state``) so that a hipGraph capture of
         the training step replays with the right bias correction (the analogue of torch.optim.AdamW(capturable=True)).
 
+        The kernel reads one learning rate per SEGMENT of the flat buffer, at most 8.  A segment is a run of consecutive bucket
+        tensors of one entry of ``param_groups`` (a tensor with an ``lr_pattern`` is a segment of its own), so the number of TENSORS
+        is not limited: MOSS's ``auto_regression`` (52 tensors) and ``cross_attention_lbs`` (16 that receive gradients) are two
+        groups, two segments and one launch.  ``seg_of[i]`` is the segment of bucket parameter i.
+
         ``shard=(rank, world)``: this rank updates only its 1/world of the flat parameter buffer (the bucket's ``shard_layout``: the
         bucket must have been made with the same ``world``) and keeps moments for that shard alone (moments memory and update time
         / world); the caller reduce-scatters the gradient bucket into ``grad_shard`` before ``step()`` and all-gathers ``flat_params``
         after it -- ``moss_amd.dist.ShardedStep`` does both."""
         self.bucket = bucket
-        self._lr_of, self._pat_of = {}, {}
+        self._lr_of, self._pat_of, self._group_of = {}, {}, {}
         for gidx, grp in enumerate(param_groups):
             for p in grp["params"]:
                 self._lr_of[id(p)] = float(grp["lr"])
                 # optional periodic pattern (period, split, lr_rest): first `split` of every `period` elements use lr, the rest lr_rest
                 self._pat_of[id(p)] = grp.get("lr_pattern")
-        if len(bucket.params) > 8:
-            raise ValueError("FlatAdamW supports at most 8 learning-rate segments")
+                self._group_of[id(p)] = gidx
+        # ONE segment per run of consecutive bucket tensors of one parameter group (they share the group's rate; a tensor with an
+        # lr_pattern is a segment of its own): MOSS's two network groups are 52 and 16 tensors and two segments
+        if len(self._segment_runs(bucket.params)) > 8:
+            raise ValueError("FlatAdamW supports at most 8 learning-rate segments (one per run of consecutive bucket tensors of one "
+                             "parameter group; a tensor with an lr_pattern is a segment of its own)")
         self.shard = None if shard is None else (int(shard[0]), int(shard[1]))
         if self.shard is not None and self.shard[1] != bucket.world:
             raise ValueError(f"shard=(rank, {self.shard[1]}) but the bucket was laid out for {bucket.world} shards")
@@ -85,19 +94,36 @@ class FlatAdamW:
             for m, v, n, off in zip(exp_avg, exp_avg_sq, bucket.sizes, bucket.offsets):
                 self.exp_avg[off:off + n].copy_(m.reshape(-1)); self.exp_avg_sq[off:off + n].copy_(v.reshape(-1))
 
+    def _segment_runs(self, params):
+        """Index of the first tensor of every learning-rate segment: consecutive bucket tensors form one segment when they belong to
+        the same entry of ``param_groups`` and carry no ``lr_pattern`` (the pattern's period counts from the segment's start)."""
+        firsts = []
+        for i, p in enumerate(params):
+            prev = params[i - 1] if i else None
+            if (prev is None or self._group_of[id(p)] != self._group_of[id(prev)] or self._pat_of[id(p)] or self._pat_of[id(prev)]):
+                firsts.append(i)
+        return firsts
+
     def _adopt_segments(self):
         """The bookkeeping of a (re-)layout, from the bucket's CURRENT offsets: the learning-rate segments (rates a schedule changed
-        survive), the element count, the shard range and its gradient buffer.  No parameter or moment is touched."""
+        survive), the parameter -> segment map ``seg_of`` (by index in the bucket), the element count, the shard range and its
+        gradient buffer.  No parameter or moment is touched."""
         bucket = self.bucket
         params = bucket.params
         total = bucket.n_params
         dev = params[0].device
         old_lr = {i: (float(self.seg_lr[i]), float(self.seg_lr2[i])) for i in range(getattr(self, "nseg", 0))}
         ends, lrs, periods, splits, lr2s = [], [], [], [], []
-        for i, p in enumerate(params):
-            # a segment runs to the (aligned) start of the next tensor: the <= 3 floats of padding behind a tensor are zeros with zero
-            # gradients, which the update leaves zero
-            ends.append(bucket.offsets[i + 1] if i + 1 < len(params) else total); lrs.append(self._lr_of[id(p)])
+        firsts = self._segment_runs(params)
+        self.seg_of = [0] * len(params)
+        for s, i in enumerate(firsts):
+            p = params[i]
+            nxt = firsts[s + 1] if s + 1 < len(firsts) else len(params)
+            for k in range(i, nxt):
+                self.seg_of[k] = s
+            # a segment runs to the (aligned) start of the first tensor behind its run: the <= 3 floats of padding behind a tensor --
+            # between the tensors of a run too -- are zeros with zero gradients, which the update leaves zero
+            ends.append(bucket.offsets[nxt] if nxt < len(params) else total); lrs.append(self._lr_of[id(p)])
             pat = self._pat_of[id(p)]
             periods.append(int(pat[0]) if pat else 0); splits.append(int(pat[1]) if pat else 0); lr2s.append(float(pat[2]) if pat else 0.0)
         for i, (lr, lr2) in old_lr.items():                  # (a schedule's current rates survive a re-layout)
@@ -159,7 +185,7 @@ class FlatAdamW:
         st = FusedAdamWStruct()
         for i in range(5):
             st.lr_segment[i] = -1
-        offs = {id(p): (off, i) for i, (p, off) in enumerate(zip(self.bucket.params, self.bucket.offsets))}
+        offs = {id(p): (off, self.seg_of[i]) for i, (p, off) in enumerate(zip(self.bucket.params, self.bucket.offsets))}
         ptrs = {}
         for name, p in given.items():
             slot = OPT_BITS[name].bit_length() - 1
@@ -267,7 +293,7 @@ class FlatAdamW:
     def _seg_active(self):
         act = (C.c_int * self.nseg)(*([0] * self.nseg))
         if self.sh_index is not None and self.sh_active_degree < 3:
-            act[self.sh_index] = 3 * (self.sh_active_degree + 1) ** 2
+            act[self.seg_of[self.sh_index]] = 3 * (self.sh_active_degree + 1) ** 2     # (its lr_pattern makes the SH tensor a segment of its own)
         return act
 
     def set_learning_rates(self, rates):
@@ -278,14 +304,23 @@ class FlatAdamW:
         With ``capturable=True`` the rates also go into the optimizer's device-side state block (one small asynchronous copy on the
         current stream) and every update kernel -- the flat ones and the rasterizer backward that takes the step itself -- reads them
         from there: call this BETWEEN replays of a captured step; no re-capture (the launch arguments baked into the graph are then
-        ignored)."""
+        ignored).
+
+        The tensors of one parameter group that lie side by side in the bucket share ONE segment and one rate: naming any of them sets
+        the rate of the whole run; two of them given different rates raise ``ValueError`` (nothing is changed then)."""
         index = {id(p): i for i, p in enumerate(self.bucket.params)}
+        new = {}
         for key, val in rates.items():
-            i = key if isinstance(key, int) else index[id(key)]
+            seg = self.seg_of[key if isinstance(key, int) else index[id(key)]]
             lr, lr2 = (val if isinstance(val, (tuple, list)) else (val, None))
-            self.seg_lr[i] = float(lr)
+            want = (float(lr), None if lr2 is None else float(lr2))
+            if new.setdefault(seg, want) != want:
+                raise ValueError(f"set_learning_rates: two parameters of one learning-rate segment (one parameter group) were given "
+                                 f"different rates, {new[seg]} and {want}")
+        for seg, (lr, lr2) in new.items():
+            self.seg_lr[seg] = lr
             if lr2 is not None:
-                self.seg_lr2[i] = float(lr2)
+                self.seg_lr2[seg] = lr2
         if self.fused is not None:
             st = self.fused.struct
             for slot in range(5):
@@ -635,7 +670,9 @@ class AdamW(torch.optim.Optimizer):
 
     # A group of MANY tensors (MOSS's two network groups, scene/gaussian_model.py:222-223: the parameters of `auto_regression` and
     # `cross_attention_lbs`) is stepped with torch's multi-tensor primitives -- nine launches for the whole group, where one kernel per
-    # tensor would be dozens; the single-tensor Gaussian groups are where one kernel replaces nine.
+    # tensor would be dozens; the single-tensor Gaussian groups are where one kernel replaces nine.  (THIS class keeps torch's
+    # per-tensor state.  `FlatAdamW` takes such groups too -- one learning-rate segment per group, however many tensors, one launch for
+    # both networks, capturable: `moss_amd.train.MossStep`.)
     FOREACH_ABOVE = 4
 
     def _foreach_group(self, group) -> bool:

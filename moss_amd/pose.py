@@ -189,7 +189,7 @@ def _param_shapes(anc):
 
 class _PoseHead(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, poses, target_R, overreg, parents, *params):
+    def forward(ctx, poses, target_R, overreg, parents, sink, *params):
         from ._lib import POSE_HEAD_SAVED_FLOATS, PoseHeadArgs, call
         dev = poses.device
         nj = NUM_JOINTS
@@ -201,7 +201,7 @@ class _PoseHead(torch.autograd.Function):
         call("moss_pose_head_forward", dev, ctypes.byref(a))
         ctx.mark_non_differentiable(S)
         ctx.save_for_backward(poses, target_R, buf, *params)
-        ctx.overreg, ctx.parents = overreg, parents
+        ctx.overreg, ctx.parents, ctx.sink = overreg, parents, sink
         return Rs, S, nll
 
     @staticmethod
@@ -213,6 +213,8 @@ class _PoseHead(torch.autograd.Function):
         sizes = [p.numel() for p in params]
         flat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)                 # every element is written by the kernel
         grads = [g.view(p.shape) for g, p in zip(flat.split(sizes), params)]
+        if ctx.sink is not None:                                                         # (a sink replaces the parameter's scratch slice)
+            grads = [_sunk(ctx.sink(i), g) for i, g in enumerate(grads)]
         g_Rs = None if g_Rs is None else g_Rs.float().contiguous()
         g_nll = None if g_nll is None else g_nll.float().contiguous()
         a = PoseHeadBackwardArgs()
@@ -222,7 +224,17 @@ class _PoseHead(torch.autograd.Function):
         for i, g in enumerate(grads):
             a.grads[i] = g.data_ptr()
         call("moss_pose_head_backward", dev, ctypes.byref(a))
-        return (None, None, None, None, *grads)
+        return (None, None, None, None, None, *grads)
+
+
+def _sunk(t, like):
+    """A gradient sink's tensor in place of the scratch slice ``like`` (None: the slice stays)."""
+    if t is None:
+        return like
+    if t.shape != like.shape or t.dtype != torch.float32 or t.device != like.device or not t.is_contiguous():
+        raise ValueError(f"grad_sink returned a {t.dtype} tensor of shape {tuple(t.shape)} on {t.device} for a weight gradient of "
+                         f"shape {tuple(like.shape)}: it must be contiguous float32 of the parameter's shape on its device")
+    return t
 
 
 def _fill_head(a, poses, target_R, overreg, parents, params):
@@ -242,14 +254,20 @@ def _need_gpu(name, *tensors):
                                "(autoregression_torch / matrix_fisher_nll are the torch form)")
 
 
-def pose_head_fused(net, poses, target_R, overreg=1.005, parents=SMPL_PARENTS):
+def pose_head_fused(net, poses, target_R, overreg=1.005, parents=SMPL_PARENTS, grad_sink=None):
     """MOSS's ``pc.auto_regression(poses)`` followed by ``matrix_fisher_nll(...)``, one HIP kernel forward and one backward.
 
     ``net``: MOSS's ``Autoregression`` instance or anything with the same ``block_mlps`` / ``fc_pose`` parameters (float32, on the
     GPU); ``poses`` (1,72) or (72,); ``target_R`` (23,3,3) (any leading 1).  Returns ``{"Rs" (23,3,3), "pose_S" (23,3) the PROPER
     singular values, "nll" (23,), "target_R"}``.  Gradients flow from ``Rs`` and ``nll`` to the 52 parameters (``poses`` and
     ``target_R`` are data of the frame: no gradient is formed for them; ``pose_S`` carries none).  ``U`` and ``V`` are not returned:
-    Rs is within 1e-5 of a rotation, so they are not unique, and only the loss reads them."""
+    Rs is within 1e-5 of a rotation, so they are not unique, and only the loss reads them.
+
+    ``grad_sink``: a callable ``param -> tensor or None`` (the contract of ``GradBucket.sink_for``), asked once per parameter in the
+    backward.  Where it returns a tensor (contiguous float32, the parameter's shape) the backward kernel writes that parameter's
+    gradient THERE and autograd receives that tensor; where it returns None the gradient stays a slice of the op's scratch tensor.  The
+    kernel writes every element of every weight gradient, so a sink is OVERWRITTEN, not accumulated into: a sink must hand out each
+    destination at most once per backward pass (``GradBucket.sink_for`` does)."""
     params = head_parameters(net)
     _need_gpu("pose_head_fused", poses, target_R, *params)
     dev = poses.device
@@ -266,7 +284,8 @@ def pose_head_fused(net, poses, target_R, overreg=1.005, parents=SMPL_PARENTS):
         raise ValueError("pose_head_fused: poses and target_R are data of the frame (no gradient is formed for them); detach them")
     poses = poses.reshape(72).float().contiguous()
     tr = target_R.reshape(NUM_JOINTS, 3, 3).float().contiguous()
-    Rs, S, nll = _PoseHead.apply(poses, tr, float(overreg), parents, *params)
+    sink = None if grad_sink is None else (lambda i: grad_sink(params[i]))
+    Rs, S, nll = _PoseHead.apply(poses, tr, float(overreg), parents, sink, *params)
     return {"Rs": Rs, "pose_S": S, "nll": nll, "target_R": target_R}
 
 

@@ -1,0 +1,243 @@
+"""MOSS's whole training iteration (``train_ZJU.py:100-131,171-174,189``) as ONE step of this repository's ops, capturable in a hipGraph.
+
+:class:`MossStep` is a composition and a capture; it has no kernel and no mathematics of its own:
+
+    render()            pose head + matrix-Fisher NLL, LBS-weight network, SMPL frame, LBS deformation, rasterizer with the raw
+                        parameters and the pose inside the op (moss_amd/pose.py, lbs_weights.py, lbs.py, gaussian_renderer.py)
+    loss                ``train_ZJU.py:131``: ROI photometric loss, LPIPS, NLL, S3IM (moss_amd/loss.py, lpips.py)
+    three optimizers    (A) features / opacity / scaling / rotation inside the rasterizer's backward kernel, (B) the position,
+                        (C) MOSS's two networks -- 52 + 16 tensors, two learning-rate segments, one launch (moss_amd/optim.py)
+    statistics          what ``densify_and_prune_fused`` reads (moss_amd/densify.py)
+
+Nothing in the step reads the host.  Everything here imports without a GPU.
+"""
+from __future__ import annotations
+
+from types import SimpleNamespace
+
+import torch
+
+__all__ = ["MossStep", "TERM_NAMES", "LOSS_WEIGHTS", "RENDER_FLAGS"]
+
+# ``terms``, in this order.  ``ssim`` is the SSIM value itself (the loss takes 1 - ssim); ``total`` is train_ZJU.py:131
+TERM_NAMES = ("l1", "ssim", "mask_l2", "lpips", "nll", "s3im", "total")
+# train_ZJU.py:131: Ll1 + 0.5 * mask_loss + 0.2 * (1 - ssim_loss) + 0.5 * lpips_loss + 0.06 * nll_loss + 0.3 * s3im_loss
+LOSS_WEIGHTS = {"mask_l2": 0.5, "ssim": 0.2, "lpips": 0.5, "nll": 0.06, "s3im": 0.3}
+RENDER_FLAGS = ("lbs_in_op", "pose_head_in_op", "lbs_weights_in_op", "smpl_frame_in_op", "transforms_in_op", "pose_in_op",
+                "raw_parameters_in_op")
+
+
+def network_parameters(pc):
+    """(the 52 tensors of ``pc.auto_regression``, the 16 of ``pc.cross_attention_lbs`` that its forward reads), in the order they
+    cross the C ABI.  ``out_layer`` / ``gate_proj`` are not among them: their ``.grad`` is None in MOSS and ``torch.optim.AdamW`` never
+    touches such a tensor, not even with its weight decay."""
+    from .lbs_weights import net_parameters
+    from .pose import head_parameters
+    return list(head_parameters(pc.auto_regression)), list(net_parameters(pc.cross_attention_lbs))
+
+
+class MossStep:
+    """``step = MossStep(pc, view, gt_image, bkgd_mask, region, bg, lpips_net, lrs)``; ``step.compute()`` is one eager iteration,
+    ``step.capture()`` captures it and ``step()`` replays it.
+
+    ``pc``: a ``GaussianSet(unified_features=True)`` that carries what MOSS's ``GaussianModel`` gives the pose branch:
+    ``auto_regression``, ``cross_attention_lbs``, ``SMPL_NEUTRAL``, ``knn``, ``coarse_deform_c2source`` and
+    ``motion_offset_flag=True``.  ``view``: a camera with ``smpl_param`` (``pose_rotmats`` included), ``big_pose_smpl_param`` and
+    ``big_pose_world_vertex``.  ``gt_image`` (3,H,W), ``bkgd_mask`` (1,H,W), ``region`` (a ``loss.ViewRegion``), ``bg`` (3,);
+    ``lpips_net``: an ``lpips.LpipsVGG``.  ALL of them are static inputs: the caller changes frame between steps by ``copy_`` into
+    these tensors and ``region.copy_`` (among views of one crop size: LPIPS bakes the crop's size into its launches).
+
+    ``lrs``: ``{"auto_regression": lr, "cross_attention_lbs": lr}`` (MOSS: 2.5e-4 and 1e-4), optionally with rates for the Gaussian
+    groups by their ``param_groups()`` names (``xyz``, ``features`` -- a number or ``(lr_dc, lr_rest)`` --, ``opacity``, ``scaling``,
+    ``rotation``; default: the reference's).
+
+    Three ``FlatAdamW(capturable=True, eps=1e-15, weight_decay=0.01)``:
+
+    * ``opt_gaussians`` (A): ``_features``, ``_opacity``, ``_scaling``, ``_rotation``, taken inside the rasterizer's backward kernel
+      (``fuse_into_backward``) -- the rasterizer is the only producer of their gradients;
+    * ``opt_xyz`` (B): ``_xyz`` alone.  The rasterizer, the LBS deformation and the LBS-weight network all add to its gradient, so it
+      is summed by autograd and ``collect()``-ed into the bucket;
+    * ``opt_networks`` (C): the 52 + 16 network tensors, one learning-rate segment per network.  Both networks' backward kernels
+      write their weight gradients straight into its bucket (``pipe.net_grad_sink``).
+
+    (B) and (C) step with the frame's status word as ``skip_word`` and (A)'s kernel reads it itself: a frame that overflowed the
+    binning capacity (it rendered nothing) is a no-op for all three -- parameters, moments and step counters stay bit for bit.
+
+    ``stats`` (a ``densify.DensifyStats``): the step also keeps what ``densify_and_prune_fused`` reads -- ``stats.add(radii,
+    viewspace.grad)``, ``joint_F_sum += Rs`` and ``lbs_weights_sum += lbs_weights`` (``train_ZJU.py:102-105,127,171-174``; a dropped
+    frame adds to none of them).  The densification EVENT is not part of this class: the Gaussians sit in two optimizers here, and
+    ``surgery.densification_event`` takes one.
+
+    ``terms`` (7 floats on the device, :data:`TERM_NAMES`): the six loss terms and the total of the last step."""
+
+    def __init__(self, pc, view, gt_image, bkgd_mask, region, bg, lpips_net, lrs, context=None, stats=None):
+        from .diff_gaussian_rasterization import RasterContext
+        from .dist import GradBucket
+        from .optim import FlatAdamW
+        if not getattr(pc, "unified_features", False):
+            raise ValueError("MossStep needs GaussianSet(unified_features=True): the update inside the backward kernel takes the SH "
+                             "coefficients as one tensor")
+        missing = [a for a in ("auto_regression", "cross_attention_lbs", "SMPL_NEUTRAL", "knn", "coarse_deform_c2source") if not hasattr(pc, a)]
+        if missing or not getattr(pc, "motion_offset_flag", False):
+            raise ValueError(f"MossStep: the model lacks {missing or 'motion_offset_flag=True'} (MOSS trains with --motion_offset_flag)")
+        if "pose_rotmats" not in view.smpl_param:
+            raise ValueError("MossStep: view.smpl_param has no 'pose_rotmats' (the target rotations of the matrix-Fisher term)")
+        for k in ("auto_regression", "cross_attention_lbs"):
+            if k not in lrs:
+                raise ValueError(f"MossStep: lrs has no rate for '{k}'")
+        self.pc, self.view, self.gt_image, self.bkgd_mask, self.region, self.bg, self.lpips_net = pc, view, gt_image, bkgd_mask, region, bg, lpips_net
+        self.stats = stats
+        dev = pc._xyz.device
+        self.context = cx = context if context is not None else RasterContext()
+        if not cx.enabled:
+            cx.set_async(True)                               # (the first forward is synchronous and sizes the binning capacity)
+        kw = dict(capturable=True, eps=1e-15, weight_decay=0.01)
+        groups = {}
+        for g in pc.param_groups():
+            g = dict(g)
+            rate = lrs.get(g["name"])
+            if isinstance(rate, (tuple, list)):
+                g["lr"], g["lr_pattern"] = float(rate[0]), tuple(g["lr_pattern"][:2]) + (float(rate[1]),)
+            elif rate is not None:
+                g["lr"] = float(rate)
+            groups[g["name"]] = g
+        # (A) inside the rasterizer's backward
+        names_a = ("features", "opacity", "scaling", "rotation")
+        self.bucket_gaussians = GradBucket([p for n in names_a for p in groups[n]["params"]])
+        self.opt_gaussians = FlatAdamW([groups[n] for n in names_a], self.bucket_gaussians, **kw)
+        self.opt_gaussians.set_active_sh_degree(pc.active_sh_degree)
+        self.opt_gaussians.fuse_into_backward(cx, sh=pc._features, opacity=pc._opacity, scales=pc._scaling, rotations=pc._rotation)
+        # (B) the position
+        self.bucket_xyz = GradBucket([pc._xyz])
+        self.opt_xyz = FlatAdamW([groups["xyz"]], self.bucket_xyz, **kw)
+        # (C) both networks: two groups, two segments, one launch
+        head, net = network_parameters(pc)
+        self.network_params = {"auto_regression": head, "cross_attention_lbs": net}
+        self.bucket_networks = GradBucket(head + net)
+        self.opt_networks = FlatAdamW([{"params": head, "lr": float(lrs["auto_regression"]), "name": "auto_regression"},
+                                       {"params": net, "lr": float(lrs["cross_attention_lbs"]), "name": "cross_attention_lbs"}],
+                                      self.bucket_networks, **kw)
+        self.optimizers = (self.opt_gaussians, self.opt_xyz, self.opt_networks)
+        self.pipe = SimpleNamespace(convert_SHs_python=False, compute_cov3D_python=False, debug=False, raster_context=cx,
+                                    net_grad_sink=self.bucket_networks.sink_for, **dict.fromkeys(RENDER_FLAGS, True))
+        # [photometric loss | l1, ssim, mask_l2 | lpips, nll, s3im, total]: the photometric kernels write the first four themselves
+        self._terms = torch.zeros(8, dtype=torch.float32, device=dev)
+        self.terms = self._terms[1:]
+        self.joint_F_sum = torch.zeros(23, 3, 3, dtype=torch.float32, device=dev)
+        self.lbs_weights_sum = None                          # (made by the first step: the deformation says its shape)
+        self.graphed = None
+
+    # ---- the step ------------------------------------------------------------------------------------------------------------------
+    def compute(self):
+        """One iteration, eagerly: render, the loss of ``train_ZJU.py:131``, backward, the three updates, the statistics.  Returns
+        ``{"render", "terms"}`` (detached; under replay the static outputs of the capture)."""
+        from .diff_gaussian_rasterization._C import frame_status_word
+        from .gaussian_renderer import render
+        from .loss import backward_from_loss, s3im_loss_roi_fused, training_loss_moss_fused
+        from .lpips import lpips_vgg_roi_fused
+        w = LOSS_WEIGHTS
+        for b in (self.bucket_gaussians, self.bucket_xyz, self.bucket_networks):
+            b.detach_grads()
+        out = render(self.view, self.pc, self.pipe, self.bg)
+        image, gt = out["render"], self.gt_image
+        photometric = training_loss_moss_fused(image, out["render_alpha"], gt, self.bkgd_mask, self.region, w["ssim"], w["mask_l2"],
+                                               terms_out=self._terms[:4])
+        lpips = lpips_vgg_roi_fused(self.lpips_net, image, gt, self.region).reshape(())
+        nll = out["pose_out"]["nll"].mean()
+        s3im = s3im_loss_roi_fused(image, gt, self.region)
+        loss = photometric + w["lpips"] * lpips + w["nll"] * nll + w["s3im"] * s3im
+        backward_from_loss(loss)                             # (A) steps in here
+        self.bucket_xyz.collect()
+        self.bucket_networks.collect()                       # (costs nothing: every network gradient was written through its sink)
+        img_buffer = self.context.last_img_buffer            # (None after the synchronous first forward of a context: it cannot overflow)
+        word = None if img_buffer is None else frame_status_word(img_buffer)
+        self.opt_xyz.step(skip_word=word)
+        self.opt_networks.step(skip_word=word)
+        with torch.no_grad():
+            torch.stack((lpips.detach(), nll.detach(), s3im.detach(), loss.detach()), out=self._terms[4:])
+            if self.stats is not None:
+                radii, Rs, lbs_w = out["radii"], out["pose_out"]["Rs"].detach(), out["lbs_weights"].detach()
+                if self.lbs_weights_sum is None:
+                    self.lbs_weights_sum = torch.zeros_like(lbs_w)
+                if word is None:
+                    self.joint_F_sum.add_(Rs)
+                    self.lbs_weights_sum.add_(lbs_w)
+                else:
+                    # a dropped frame contributes to no statistic either: its radii are set to zero (the preprocess computed them before
+                    # the frame overflowed, so ``add`` would count the frame in ``denom``) and the two sums add zero times the frame
+                    kept = 1 - ((word >> 1) & 1)                                 # int32 (1,): 0 for a dropped frame
+                    radii = radii * kept
+                    self.joint_F_sum.addcmul_(Rs, kept.to(torch.float32))
+                    self.lbs_weights_sum.addcmul_(lbs_w, kept.to(torch.float32))
+                self.stats.add(radii, out["viewspace_points"].grad)
+        return {"render": image.detach(), "terms": self.terms}
+
+    # ---- capture and replay -------------------------------------------------------------------------------------------------------
+    def _state(self):
+        s = [o.snapshot() for o in self.optimizers] + [self._terms.clone(), self.joint_F_sum.clone(),
+                                                       None if self.lbs_weights_sum is None else self.lbs_weights_sum.clone()]
+        if self.stats is not None:
+            s += [self.stats.xyz_gradient_accum.clone(), self.stats.denom.clone(), self.stats.max_radii2D.clone()]
+        return s
+
+    def _restore(self, s):
+        for o, snap in zip(self.optimizers, s[:3]):
+            o.restore(snap)
+        self._terms.copy_(s[3]); self.joint_F_sum.copy_(s[4])
+        if self.lbs_weights_sum is not None:
+            self.lbs_weights_sum.zero_() if s[5] is None else self.lbs_weights_sum.copy_(s[5])
+        if self.stats is not None:
+            self.stats.xyz_gradient_accum.copy_(s[6]); self.stats.denom.copy_(s[7]); self.stats.max_radii2D.copy_(s[8])
+
+    def capture(self, warmup=3):
+        """Capture ``compute`` in a hipGraph (``GraphedStep(self.compute, context=...)``).  The ``warmup`` eager runs a capture needs --
+        the first of a fresh context is synchronous and sizes the binning capacity for the frame loaded NOW -- are training steps;
+        they are undone here (parameters, moments, step counters, statistics: snapshot before, restore after), so a capture leaves the
+        model where it found it.  Returns ``self``."""
+        from .graphs import GraphedStep
+        state = self._state()
+        self.graphed = GraphedStep(self.compute, warmup=warmup, device=self.pc._xyz.device, context=self.context)
+        self._restore(state)
+        return self
+
+    def __call__(self):
+        if self.graphed is None:
+            raise RuntimeError("MossStep: capture() first (or call compute() for the eager step)")
+        return self.graphed()
+
+    def check(self) -> bool:
+        """``GraphedStep.check()``: verifies the last replayed frame, counts the dropped ones (``dropped_frames``) and re-captures
+        when the binning capacity has grown.  Synchronises; call it every few hundred steps.  True if it re-captured."""
+        if self.graphed is None:
+            raise RuntimeError("MossStep.check(): nothing is captured")
+        return self.graphed.check()
+
+    @property
+    def dropped_frames(self) -> int:
+        return 0 if self.graphed is None else self.graphed.dropped_frames
+
+    def step_counts(self):
+        """The three device-side step counters (A, B, C); synchronises."""
+        return tuple(o.step_count() for o in self.optimizers)
+
+    def set_learning_rates(self, rates):
+        """A schedule, between replays, no re-capture (``FlatAdamW.set_learning_rates``).  ``rates``: ``{key: lr}`` with ``key`` a
+        parameter, or ``"auto_regression"`` / ``"cross_attention_lbs"`` / a Gaussian group's name (``xyz``, ``features``: ``(lr_dc,
+        lr_rest)``, ``opacity``, ``scaling``, ``rotation``).  Each entry goes to the optimizer that holds the parameter."""
+        pc = self.pc
+        named = {"xyz": pc._xyz, "features": pc._features, "opacity": pc._opacity, "scaling": pc._scaling, "rotation": pc._rotation,
+                 "auto_regression": self.network_params["auto_regression"][0], "cross_attention_lbs": self.network_params["cross_attention_lbs"][0]}
+        per = [{} for _ in self.optimizers]
+        for key, val in rates.items():
+            if isinstance(key, str) and key not in named:
+                raise KeyError(f"MossStep.set_learning_rates: no parameter group '{key}'")
+            p = named[key] if isinstance(key, str) else key
+            for o, d in zip(self.optimizers, per):
+                if id(p) in o.bucket._offset:
+                    d[p] = val
+                    break
+            else:
+                raise KeyError("MossStep.set_learning_rates: a parameter that none of the three optimizers holds")
+        for o, d in zip(self.optimizers, per):
+            if d:
+                o.set_learning_rates(d)

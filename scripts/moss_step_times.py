@@ -1,0 +1,229 @@
+#!/usr/bin/env python3
+"""Times MOSS's whole training iteration -- all six loss terms, all eight parameter groups -- at P = 6 890 and 45 695 Gaussians, 512 x 512,
+SH degree 3, synthetic LPIPS weights, a 192 x 256 region:
+
+    captured   ``moss_amd.train.MossStep`` replayed from its hipGraph (three FlatAdamW, the Gaussians' inside the backward kernel, both
+               networks in one launch)
+    baseline   the same composition -- ``render()`` with the same ``*_in_op`` flags, the same four fused loss calls -- run eagerly with
+               ``moss_amd.optim.AdamW`` over MOSS's eight parameter groups (its two network groups take torch's ``_foreach`` launches).
+               It uses nothing newer than the drop-in optimizer, so it also runs on a checkout from before ``MossStep`` existed:
+               ``--only baseline --package-root <that checkout>``
+    profile    ``rocprofv3 --kernel-trace --stats`` over the captured step at the larger size; the per-kernel table is printed
+
+    python scripts/moss_step_times.py [--replays 300] [--sizes 6890,45695] [--only captured,baseline,profile] [--out DIR]
+
+Every measurement is a process of its own under ``timeout -k 10``; the script stops at the first one that does not exit with 0.  A time
+is the wall clock around ``replays`` back-to-back steps between two device synchronisations, after a warm-up.  Needs a GPU.
+"""
+import argparse
+import csv
+import glob
+import json
+import os
+import subprocess
+import sys
+import time
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+STEP_TIMEOUT = 240
+FLAGS = ("lbs_in_op", "pose_head_in_op", "lbs_weights_in_op", "smpl_frame_in_op", "transforms_in_op", "pose_in_op", "raw_parameters_in_op")
+LR_HEAD, LR_NET = 2.5e-4, 1e-4
+V = 6890
+
+
+def _frame(k, dev):
+    """A frame that keeps the body in view: small joint rotations, a small global rotation and translation, and target rotations
+    near the frame's own."""
+    import torch
+    from moss_amd import lbs as mlbs
+    g = torch.Generator().manual_seed(500 + k)
+    axis = torch.randn(1, 3, generator=g)
+    f = {"poses": 0.15 * torch.randn(1, 72, generator=g), "shapes": 0.3 * torch.randn(1, 10, generator=g),
+         "R": mlbs.batch_rodrigues(0.3 * axis / axis.norm())[0], "Th": 0.05 * torch.randn(1, 3, generator=g)}
+    f["pose_rotmats"] = mlbs.batch_rodrigues(f["poses"].reshape(24, 3)[1:] + 0.05 * torch.randn(23, 3, generator=g))
+    return {k_: v.to(dev) for k_, v in f.items()}
+
+
+def _world(P, dev, unified):
+    """Model, camera and targets: MOSS's initialisation at 6 890 Gaussians, post-densification statistics above."""
+    import torch
+    from moss_amd import lbs as mlbs
+    from moss_amd import lbs_weights as mlw
+    from moss_amd import lpips as mlp
+    from moss_amd import pose as mpose
+    from moss_amd import scenes
+    from moss_amd.gaussian_model import GaussianSet
+    from moss_amd.gaussian_renderer import camera_view
+    from moss_amd.knn_cuda import KNN
+    from moss_amd.loss import ViewRegion
+
+    class DeformableSet(GaussianSet):
+        def coarse_deform_c2source(self, *a, **k):           # (render() only asks whether the model has one: lbs_in_op runs the fused op)
+            raise NotImplementedError
+
+    torch.manual_seed(1)
+    s = scenes.body_scene(P, 512, 512, 540.0, init_like=P <= 6890, name="moss_step")
+    pc = DeformableSet(s, sh_degree=3, device=dev, unified_features=unified)
+    body = mlbs.synthetic_body_model(V, 24, seed=21, device=dev)
+    pc.SMPL_NEUTRAL, pc.knn = body, KNN(k=1, transpose_mode=True)
+    pc.auto_regression = mpose.head_module().to(dev)
+    pc.cross_attention_lbs = mlw.lbs_weight_module().to(dev)
+    pc.motion_offset_flag = True
+    cam = camera_view(s.camera, dev)
+    cam.big_pose_smpl_param = {k: v.to(dev) for k, v in mlbs.synthetic_frame(0, 24, big_pose=True).items()}
+    cam.big_pose_world_vertex = body["v_template"].clone()
+    cam.smpl_param = _frame(0, dev)
+    H, W = s.camera.H, s.camera.W
+    g = torch.Generator().manual_seed(77)
+    bound = torch.zeros(1, H, W)
+    bound[:, 128:384, 160:352] = 1
+    lp = mlp.cast_params(mlp.synthetic_weights(), device=dev)
+    net = mlp.LpipsVGG.from_tensors(lp["conv_weights"], lp["conv_biases"], lp["lin_weights"], lp["shift"], lp["scale"])
+    return dict(pc=pc, cam=cam, gt=torch.rand(3, H, W, generator=g).to(dev), bkgd=(torch.rand(1, H, W, generator=g) > 0.5).float().to(dev),
+                region=ViewRegion(bound.to(dev)), bg=torch.zeros(3, device=dev), lpips=net)
+
+
+def _timed(fn, replays, dev, load):
+    import torch
+    for i in range(20):
+        load(i)
+        fn()
+    torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    for i in range(replays):
+        load(i)
+        fn()
+    torch.cuda.synchronize(dev)
+    return (time.perf_counter() - t0) / replays
+
+
+def measure_captured(P, replays):
+    import torch
+    from moss_amd.train import MossStep
+    dev = torch.device("cuda:0")
+    w = _world(P, dev, unified=True)
+    step = MossStep(w["pc"], w["cam"], w["gt"], w["bkgd"], w["region"], w["bg"], w["lpips"], {"auto_regression": LR_HEAD, "cross_attention_lbs": LR_NET})
+    step.capture(warmup=3)
+    frames = [_frame(k, dev) for k in range(3)]
+
+    def load(i):                                             # a new frame per replay: five small copies into the static inputs
+        for key, v in frames[i % 3].items():
+            w["cam"].smpl_param[key].copy_(v)
+
+    dt = _timed(step, replays, dev, load)
+    step.check()
+    out = step()
+    torch.cuda.synchronize(dev)
+    assert step.dropped_frames == 0 and float(out["render"].abs().max()) > 0 and bool(torch.isfinite(out["terms"]).all())
+    return {"form": "captured", "P": P, "replays": replays, "us_per_step": round(dt * 1e6, 1), "it_per_s": round(1.0 / dt, 1),
+            "steps": list(step.step_counts()), "total_loss": float(out["terms"][-1])}
+
+
+def measure_baseline(P, replays):
+    import torch
+    from types import SimpleNamespace
+    from moss_amd import lbs_weights as mlw
+    from moss_amd import pose as mpose
+    from moss_amd.diff_gaussian_rasterization import RasterContext
+    from moss_amd.gaussian_renderer import render
+    from moss_amd.loss import s3im_loss_roi_fused, training_loss_moss_fused
+    from moss_amd.lpips import lpips_vgg_roi_fused
+    from moss_amd.optim import AdamW
+    dev = torch.device("cuda:0")
+    w = _world(P, dev, unified=False)
+    pc, cam = w["pc"], w["cam"]
+    cx = RasterContext()
+    cx.set_async(True)
+    pipe = SimpleNamespace(convert_SHs_python=False, compute_cov3D_python=False, debug=False, raster_context=cx, **dict.fromkeys(FLAGS, True))
+    # MOSS's eight groups (scene/gaussian_model.py:215-226); the networks' with every tensor of the module, as MOSS passes them
+    groups = pc.param_groups() + [{"params": list(pc.auto_regression.parameters()), "lr": LR_HEAD, "name": "auto_regression"},
+                                  {"params": list(pc.cross_attention_lbs.parameters()), "lr": LR_NET, "name": "cross_attention_lbs"}]
+    assert len(groups) == 8
+    opt = AdamW(groups, lr=0.0, eps=1e-15)
+    frames = [_frame(k, dev) for k in range(3)]
+    last = {}
+
+    def load(i):
+        for key, v in frames[i % 3].items():
+            cam.smpl_param[key].copy_(v)
+
+    def fn():
+        opt.zero_grad(set_to_none=True)
+        out = render(cam, pc, pipe, w["bg"])
+        image = out["render"]
+        loss = (training_loss_moss_fused(image, out["render_alpha"], w["gt"], w["bkgd"], w["region"], 0.2, 0.5)
+                + 0.5 * lpips_vgg_roi_fused(w["lpips"], image, w["gt"], w["region"]).reshape(())
+                + 0.06 * out["pose_out"]["nll"].mean() + 0.3 * s3im_loss_roi_fused(image, w["gt"], w["region"]))
+        loss.backward()
+        opt.step()
+        last["loss"], last["image"] = loss.detach(), image.detach()
+
+    dt = _timed(fn, replays, dev, load)
+    cx.check_status()
+    assert float(last["image"].abs().max()) > 0 and bool(torch.isfinite(last["loss"]))
+    assert all(p.grad is not None for p in mpose.head_parameters(pc.auto_regression) + mlw.net_parameters(pc.cross_attention_lbs))
+    return {"form": "baseline_eager_dropin_adamw", "P": P, "replays": replays, "us_per_step": round(dt * 1e6, 1), "it_per_s": round(1.0 / dt, 1),
+            "total_loss": float(last["loss"])}
+
+
+def kernel_table(directory, top=25):
+    """The per-kernel rows of rocprofv3's ``*kernel_stats.csv`` under ``directory``: (name, calls, total us, mean us, percent)."""
+    rows = []
+    for path in glob.glob(os.path.join(directory, "**", "*kernel_stats.csv"), recursive=True):
+        with open(path, newline="") as f:
+            for r in csv.DictReader(f):
+                rows.append((r["Name"], int(r["Calls"]), float(r["TotalDurationNs"]) / 1e3, float(r["AverageNs"]) / 1e3, float(r["Percentage"])))
+    rows.sort(key=lambda r: -r[2])
+    return rows[:top]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--replays", type=int, default=300)
+    ap.add_argument("--sizes", default="6890,45695")
+    ap.add_argument("--only", default="captured,baseline,profile")
+    ap.add_argument("--out", default="moss_step_times_out")
+    ap.add_argument("--package-root", default=os.path.dirname(HERE), help="the checkout whose moss_amd is measured")
+    ap.add_argument("--worker", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--P", type=int, default=0, help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(a.package_root))
+    if a.worker:
+        if a.replays < 200:
+            raise SystemExit("at least 200 replays per measurement")
+        print("RESULT " + json.dumps({"captured": measure_captured, "baseline": measure_baseline}[a.worker](a.P, a.replays)), flush=True)
+        return
+    os.makedirs(a.out, exist_ok=True)
+    sizes = [int(x) for x in a.sizes.split(",")]
+    only = a.only.split(",")
+    me = [sys.executable, os.path.abspath(__file__), "--package-root", os.path.abspath(a.package_root), "--replays", str(a.replays)]
+    jobs = [(f"{form}_{P}", ["timeout", "-k", "10", str(STEP_TIMEOUT)] + me + ["--worker", form, "--P", str(P)])
+            for form in ("captured", "baseline") if form in only for P in sizes]
+    if "profile" in only:
+        prof = os.path.join(os.path.abspath(a.out), "rocprof")
+        jobs.append(("profile", ["timeout", "-k", "10", str(STEP_TIMEOUT), "rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv",
+                                 "-d", prof, "-o", "moss_step", "--"] + me + ["--worker", "captured", "--P", str(max(sizes))]))
+    results = []
+    for name, cmd in jobs:
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, cwd=os.path.abspath(a.package_root))
+        with open(os.path.join(a.out, name + ".log"), "w") as f:
+            f.write(r.stdout)
+        line = next((ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")), None)
+        if r.returncode != 0 or line is None:
+            print(f"{name}: exit {r.returncode}; stopping (log: {os.path.join(a.out, name + '.log')})\n" + r.stdout[-3000:], flush=True)
+            raise SystemExit(1)
+        res = dict(json.loads(line[7:]), job=name)
+        results.append(res)
+        print(json.dumps(res), flush=True)
+        if name == "profile":
+            # (one process: capture warm-up, 20 + replays + 1 replayed steps; the eager warm-up steps' kernels are in the totals too)
+            n = a.replays + 21
+            print(f"| kernel | calls | total us | mean us | % | us / replayed step (calls / {n}) |\n|---|---|---|---|---|---|")
+            for nm, calls, tot, mean, pct in kernel_table(prof):
+                print(f"| `{nm[:90]}` | {calls} | {tot:.0f} | {mean:.1f} | {pct:.1f} | {tot / n:.1f} |")
+    with open(os.path.join(a.out, "results.json"), "w") as f:
+        json.dump(results, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
