@@ -701,6 +701,22 @@ size_t moss_lbs_weight_net_saved_bytes(int P);      /* what its forward keeps fo
  * capturable; a captured step changes view by rewriting `rect`.  Every sum has a fixed order and there is no atomic: bitwise
  * reproducible.  Bad arguments (a NULL required pointer, a size outside the range, a short workspace) return MOSS_ERR_INVALID_ARG
  * with moss_last_error() set.
+ *
+ * A crop whose SIZE changes under a captured step (additive in ABI 7): cap_H, cap_W, the last two fields of both blocks.  0, 0 is the
+ * static call above.  With a capacity set -- the largest crop the call will ever see, 16 <= cap, cap_H * cap_W <= 2^22, no larger
+ * than the frame -- rect is required and H, W are ignored: every kernel reads w = rect[2], h = rect[3] on the device (clamped into
+ * [16, capacity] per axis for memory safety; the caller validates on the host where it can see the rectangle) and derives each level's
+ * sizes, the row counts, the pool and tap extents and the 1 / (H_l W_l) of the means from them.  The launches, `workspace` and `saved`
+ * are sized for the capacity: workspace_bytes >= moss_lpips_vgg_workspace_bytes(cap_H, cap_W), saved holds
+ * moss_lpips_vgg_saved_bytes(cap_H, cap_W), and the backward is given the capacity the forward had.  Zero padding is at the actual
+ * crop's edge, the frame outside the crop is never read, dL_dx is zero off the actual crop, and nothing depends on what `workspace`
+ * or `saved` held before.  The arithmetic is the static call's.  The wide convolution has two kernel shapes which sum K in different
+ * orders, picked on the host from the row count -- with a capacity from the capacity's -- so a call with a capacity is BIT-IDENTICAL
+ * to the static call at the same h x w exactly when every layer gets the same shape in both: always when the crop equals the
+ * capacity, and for any capacity up to 64 x 64 on a device with more than 64 CUs (both then take the narrow shape everywhere).
+ * Otherwise the two agree to float32 summation order, and each is as close to float64 as the other.  Refused with
+ * MOSS_ERR_INVALID_ARG: a capacity with rect NULL, one outside the range, one larger than the frame, only one of cap_H / cap_W set,
+ * a workspace shorter than the capacity's.
  */
 #define MOSS_LPIPS_VGG_CONVS 13
 #define MOSS_LPIPS_VGG_TAPS 5
@@ -717,9 +733,10 @@ typedef struct moss_lpips_vgg_args {
     const float* scale;
     float* out;
     float* terms;                            /* 5 floats, or NULL */
-    char* saved;                             /* moss_lpips_vgg_saved_bytes(H, W), or NULL */
+    char* saved;                             /* moss_lpips_vgg_saved_bytes(H, W) (of cap_H, cap_W with a capacity), or NULL */
     char* workspace;
     size_t workspace_bytes;
+    int32_t cap_H, cap_W;                    /* 0, 0 = the static call; else the crop's size is rect[3] x rect[2], at most this */
 } moss_lpips_vgg_args;
 int moss_lpips_vgg_forward(const moss_lpips_vgg_args* args, void* stream);   /* lpipsPyTorch/modules/lpips.py:31-37 */
 
@@ -734,6 +751,7 @@ typedef struct moss_lpips_vgg_backward_args {
     float* dL_dx;                            /* (3,frame_H,frame_W) */
     char* workspace;
     size_t workspace_bytes;
+    int32_t cap_H, cap_W;                    /* the forward's */
 } moss_lpips_vgg_backward_args;
 int moss_lpips_vgg_backward(const moss_lpips_vgg_backward_args* args, void* stream);   /* the adjoint of lpipsPyTorch/modules/lpips.py:31-37 w.r.t. x */
 size_t moss_lpips_vgg_workspace_bytes(int H, int W);  /* scratch of either call; 0 for a size outside the range */

@@ -257,14 +257,15 @@ class LpipsVggArgs(C.Structure):
     _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32), ("frame_H", C.c_int32), ("frame_W", C.c_int32),
                 ("rect", C.c_void_p), ("weights", C.c_void_p * 13), ("biases", C.c_void_p * 13), ("lin", C.c_void_p * 5),
                 ("shift", C.c_void_p), ("scale", C.c_void_p), ("out", C.c_void_p), ("terms", C.c_void_p), ("saved", C.c_void_p),
-                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("cap_H", C.c_int32), ("cap_W", C.c_int32)]
 
 
 class LpipsVggBackwardArgs(C.Structure):
     """``moss_lpips_vgg_backward_args`` of include/moss_raster.h (``moss_lpips_vgg_backward``)."""
     _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("frame_H", C.c_int32), ("frame_W", C.c_int32), ("rect", C.c_void_p),
                 ("weights_bwd", C.c_void_p * 13), ("scale", C.c_void_p), ("saved", C.c_void_p), ("g_out", C.c_void_p),
-                ("dL_dx", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+                ("dL_dx", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("cap_H", C.c_int32),
+                ("cap_W", C.c_int32)]
 
 
 DENSIFY_MODES = {"clone": 0, "split": 1, "merge": 2, "prune": 3}                    # MOSS_DENSIFY_*

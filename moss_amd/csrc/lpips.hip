@@ -23,6 +23,14 @@
 //     crop offset read from the device and the planar (3,H,W) layout of the public tensors.
 //   pool_kernel, tap_kernel, unpool_tap_kernel, reduce_kernel -- see each.
 // Every sum has a fixed order and there is no atomic: results are bitwise reproducible.  Every element of dL_dx is written.
+//
+// With a CAPACITY (moss_lpips_vgg_args.cap_H, cap_W) the crop's size is not a launch argument: every kernel reads {w, h} from the
+// device rectangle itself (struct Dyn, actual_size) and derives its level's H_l = h >> l, W_l = w >> l, M and HW from them.  The host
+// sizes the grids and the regions of `saved` and `workspace` for the capacity; inside a region the rows are compact at the ACTUAL
+// size (img * H_l * W_l + y * W_l + x), exactly the layout of the static call at h x w, and a workgroup whose rows all lie beyond
+// the actual M returns before its first barrier.  The arithmetic is the static call's; launch_conv picks the kernel shape from the
+// capacity's M, so the result equals the static call's bit for bit when every layer gets the same shape in both, and to float32
+// summation order otherwise (include/moss_raster.h).
 #include "common.h"
 #include "mfma_f32.h"
 #include "wave.h"
@@ -42,6 +50,21 @@ constexpr int WG = 256;
 constexpr int KC = 64, LD = KC + 4, BN = 64;             // K slice, LDS row stride (floats), output channels per workgroup
 constexpr float NORM_EPS = 1e-10f;
 enum { MODE_FWD, MODE_BWD_MASK, MODE_BWD_PLAIN };
+
+// The crop's size on the device.  cap_H == 0: the static call, the sizes are the launch's.  Otherwise rect[2], rect[3] = {w, h}, clamped
+// into [16, capacity] -- for memory safety only, the host validates what it can see -- and halved `level` times.
+struct Dyn {
+    const int* rect;
+    int cap_H, cap_W, level;
+};
+
+__device__ __forceinline__ void actual_size(const Dyn& d, int& H, int& W)
+{
+    if (d.cap_H > 0) {
+        H = min(max(d.rect[3], 16), d.cap_H) >> d.level;
+        W = min(max(d.rect[2], 16), d.cap_W) >> d.level;
+    }
+}
 
 // where the crop starts in the frame: the rectangle's corner, moved so that the crop fits
 __device__ __forceinline__ int2 crop_origin(const int* __restrict__ rect, int H, int W, int FH, int FW)
@@ -68,13 +91,19 @@ pack_weights_kernel(int cin, int cout, const float* __restrict__ w, float* __res
 }
 
 // ---- conv 1_1 --------------------------------------------------------------------------------------------------------------------------
-// Two threads per output row, 32 channels each.  x, y: (3,FH,FW) planes; the crop (H,W) starts at crop_origin.
+// Two threads per output row, 32 channels each.  x, y: (3,FH,FW) planes; the crop (H,W) starts at crop_origin.  (DYN a template
+// parameter for the same reason as conv3x3_mfma_kernel's.)
+template <bool DYN>
 __global__ void __launch_bounds__(WG)
 conv_first_kernel(const float* __restrict__ x, const float* __restrict__ y, const int* __restrict__ rect, int FH, int FW, int H, int W,
                   const float* __restrict__ wf, const float* __restrict__ bias, const float* __restrict__ shift,
-                  const float* __restrict__ scale, float* __restrict__ out, uint32_t* __restrict__ mask)
+                  const float* __restrict__ scale, float* __restrict__ out, uint32_t* __restrict__ mask, const Dyn dyn)
 {
     __shared__ __attribute__((aligned(16))) float s_w[27 * 64];          // [k = tap * 3 + c][channel]
+    if (DYN) {
+        actual_size(dyn, H, W);
+        if ((int)blockIdx.x * (WG / 2) >= 2 * H * W) return;             // (the whole workgroup, before its first barrier)
+    }
     for (int i = threadIdx.x; i < 27 * 64; i += WG) s_w[(i % 27) * 64 + i / 27] = wf[i];
     __syncthreads();
     const int HW = H * W;
@@ -123,11 +152,12 @@ conv_first_kernel(const float* __restrict__ x, const float* __restrict__ y, cons
 __global__ void __launch_bounds__(WG)
 conv_first_backward_kernel(const float* __restrict__ dz, const int* __restrict__ rect, int FH, int FW, int H, int W,
                            const float* __restrict__ wb, const float* __restrict__ scale, const float* __restrict__ g_out,
-                           float* __restrict__ dx)
+                           float* __restrict__ dx, const Dyn dyn)
 {
     __shared__ __attribute__((aligned(16))) float s_w[3 * 9 * 64];
     for (int i = threadIdx.x; i < 3 * 9 * 64; i += WG) s_w[i] = wb[i];
     __syncthreads();
+    actual_size(dyn, H, W);
     const int t = blockIdx.x * WG + threadIdx.x;
     if (t >= FH * FW) return;
     const int Y = t / FW, X = t - Y * FW;
@@ -168,10 +198,13 @@ struct ConvArgs {
     const uint32_t* mask_in;   // MODE_BWD_MASK: the sign bits of the layer this gradient arrives at, (M, Cout / 32) words
     uint32_t* mask_out;        // MODE_FWD: where this layer's sign bits go (rows < mask_rows), or null
     int M, mask_rows, H, W, Cin, Cout;
+    Dyn dyn;                   // DYN: H, W are read on the device, M = nimg H W, mask_rows = H W (the fields above hold the capacity's)
+    int nimg;
 };
 
-// WM waves along the rows, WK waves along K (WM * WK = 4)
-template <int WM, int WK, int MODE>
+// WM waves along the rows, WK waves along K (WM * WK = 4).  DYN is a template parameter so that the static instantiation stays the
+// code it was.
+template <int WM, int WK, int MODE, bool DYN>
 __global__ void __launch_bounds__(WG)
 conv3x3_mfma_kernel(const ConvArgs a)
 {
@@ -181,8 +214,15 @@ conv3x3_mfma_kernel(const ConvArgs a)
     static_assert(BN * LD >= 4 * 32 * 32, "s_B doubles as the buffer of the four partial blocks");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, half = lane >> 5;
     const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
-    const int H = a.H, W = a.W, HW = H * W, Cin = a.Cin, Cout = a.Cout, M = a.M;
-    const int K9 = 9 * Cin, nchunks = K9 / KC, mask_rows = a.mask_rows;
+    int H = a.H, W = a.W, M = a.M, mask_rows = a.mask_rows;
+    if (DYN) {
+        actual_size(a.dyn, H, W);
+        mask_rows = H * W;
+        M = a.nimg * mask_rows;
+        if (m0 >= M) return;                                             // (the whole workgroup, before its first barrier)
+    }
+    const int HW = H * W, Cin = a.Cin, Cout = a.Cout;
+    const int K9 = 9 * Cin, nchunks = K9 / KC;
     const float* __restrict__ in = a.in;                                 // (locals: the lambdas below must not take the address of `a`)
     const float* __restrict__ bias = a.bias;
     float* __restrict__ out = a.out;
@@ -292,8 +332,10 @@ conv3x3_mfma_kernel(const ConvArgs a)
 // One thread per pooled row and 16 channels.  The winner (first maximum in the order (0,0) (0,1) (1,0) (1,1)), two bits per channel,
 // is kept for the first image when `win` is given: (pooled row, C / 16) words.
 __global__ void __launch_bounds__(WG)
-pool_kernel(const float* __restrict__ in, float* __restrict__ out, uint32_t* __restrict__ win, int nimg, int H, int W, int C)
+pool_kernel(const float* __restrict__ in, float* __restrict__ out, uint32_t* __restrict__ win, int nimg, int H, int W, int C,
+            const Dyn dyn)
 {
+    actual_size(dyn, H, W);
     const int Hp = H >> 1, Wp = W >> 1, G = C >> 4;
     const long long t = (long long)blockIdx.x * WG + threadIdx.x;
     if (t >= (long long)nimg * Hp * Wp * G) return;
@@ -329,8 +371,14 @@ pool_kernel(const float* __restrict__ in, float* __restrict__ out, uint32_t* __r
 // f: the tapped activations of both images ((2, HW, C): y's follow x's).  partial[p] = sum_c lin[c] (nx - ny)^2; with G also
 // G[p][c] = d term / d fx[p][c] for term = mean_p partial[p]:  a = 2 lin (nx - ny) / HW,  G = a / (s + eps) - fx (a . fx) / (s (s + eps)^2).
 __global__ void __launch_bounds__(WG)
-tap_kernel(const float* __restrict__ f, int HW, int C, const float* __restrict__ lin, float* __restrict__ partial, float* __restrict__ G)
+tap_kernel(const float* __restrict__ f, int HW, int C, const float* __restrict__ lin, float* __restrict__ partial, float* __restrict__ G,
+           const Dyn dyn)
 {
+    if (dyn.cap_H > 0) {
+        int H = 0, W = 0;
+        actual_size(dyn, H, W);
+        HW = H * W;
+    }
     const int lane = threadIdx.x & 63, p = blockIdx.x * (WG / 64) + (threadIdx.x >> 6);
     if (p >= HW) return;
     const int n = C >> 6;
@@ -369,7 +417,10 @@ tap_kernel(const float* __restrict__ f, int HW, int C, const float* __restrict__
     }
 }
 
-struct ReduceArgs { int off[NTAP], cnt[NTAP]; };
+struct ReduceArgs {
+    int off[NTAP], cnt[NTAP];
+    Dyn dyn;                   // with a capacity cnt[l] is (h >> l) * (w >> l) of the device rectangle
+};
 
 // the five spatial means and their sum: one workgroup, float64 sums in a fixed order
 __global__ void __launch_bounds__(1024)
@@ -379,15 +430,21 @@ reduce_kernel(const float* __restrict__ partial, const ReduceArgs r, float* __re
     const int tid = threadIdx.x;
     double total = 0.0;
     for (int l = 0; l < NTAP; l++) {
+        int cnt = r.cnt[l];
+        if (r.dyn.cap_H > 0) {
+            int H = 0, W = 0;
+            actual_size(r.dyn, H, W);
+            cnt = (H >> l) * (W >> l);
+        }
         double v = 0.0;
-        for (int p = tid; p < r.cnt[l]; p += 1024) v += (double)partial[r.off[l] + p];
+        for (int p = tid; p < cnt; p += 1024) v += (double)partial[r.off[l] + p];
         s[tid] = v;
         __syncthreads();
         for (int st = 512; st > 0; st >>= 1) {
             if (tid < st) s[tid] += s[tid + st];
             __syncthreads();
         }
-        const double term = s[0] / (double)r.cnt[l];
+        const double term = s[0] / (double)cnt;
         if (tid == 0 && terms) terms[l] = (float)term;
         total += term;
         __syncthreads();
@@ -400,8 +457,9 @@ reduce_kernel(const float* __restrict__ partial, const ReduceArgs r, float* __re
 // dpool null: the last tap, nothing comes from above.
 __global__ void __launch_bounds__(WG)
 unpool_tap_kernel(const float* __restrict__ G, const float* __restrict__ dpool, const uint32_t* __restrict__ win,
-                  const uint32_t* __restrict__ mask, float* __restrict__ out, int H, int W, int C)
+                  const uint32_t* __restrict__ mask, float* __restrict__ out, int H, int W, int C, const Dyn dyn)
 {
+    actual_size(dyn, H, W);
     const int Q = C >> 2;
     const long long t = (long long)blockIdx.x * WG + threadIdx.x;
     if (t >= (long long)H * W * Q) return;
@@ -461,14 +519,21 @@ Geo geometry(int H, int W)
 
 bool size_ok(int H, int W) { return H >= 16 && W >= 16 && (long long)H * W <= (1ll << 22); }   // (32-bit element indices: 2 H W 64 < 2^31)
 
-template <int MODE>
-void launch_conv(const ConvArgs& a, hipStream_t s)
+// a.M: the rows the grid covers and the shape is picked by -- with a capacity the capacity's, whatever the crop turns out to be
+template <int MODE, bool DYN>
+void launch_conv_as(const ConvArgs& a, hipStream_t s)
 {
     const int big = (a.M + 127) / 128 * (a.Cout / BN);
     if (big >= device_cus())
-        hipLaunchKernelGGL((conv3x3_mfma_kernel<4, 1, MODE>), dim3((a.M + 127) / 128, a.Cout / BN), dim3(WG), 0, s, a);
+        hipLaunchKernelGGL((conv3x3_mfma_kernel<4, 1, MODE, DYN>), dim3((a.M + 127) / 128, a.Cout / BN), dim3(WG), 0, s, a);
     else
-        hipLaunchKernelGGL((conv3x3_mfma_kernel<1, 4, MODE>), dim3((a.M + 31) / 32, a.Cout / BN), dim3(WG), 0, s, a);
+        hipLaunchKernelGGL((conv3x3_mfma_kernel<1, 4, MODE, DYN>), dim3((a.M + 31) / 32, a.Cout / BN), dim3(WG), 0, s, a);
+}
+
+template <int MODE>
+void launch_conv(const ConvArgs& a, hipStream_t s)
+{
+    if (a.dyn.cap_H > 0) launch_conv_as<MODE, true>(a, s); else launch_conv_as<MODE, false>(a, s);
 }
 
 int grid_for(long long threads) { return (int)((threads + WG - 1) / WG); }
@@ -490,13 +555,25 @@ extern "C" int moss_lpips_vgg_pack_weights(int cin, int cout, const float* w, fl
     return launch_status("moss_lpips_vgg_pack_weights");
 }
 
-static const char* check_frame(int H, int W, int& FH, int& FW)
+// H, W: on return the size the launches and the regions of `saved` and `workspace` are made for -- the crop's, or the capacity's
+static const char* check_frame(int& H, int& W, int cap_H, int cap_W, const int* rect, int& FH, int& FW)
 {
+    if (cap_H || cap_W) {
+        if (cap_H <= 0 || cap_W <= 0) return "cap_H and cap_W must both be set (or both 0: the static call)";
+        if (!rect) return "a capacity needs rect: the crop's size is read from it on the device";
+        if (!size_ok(cap_H, cap_W)) return "the capacity must be >= 16 per axis (four 2x2 pools) and cap_H * cap_W <= 2^22";
+        if (FH == 0 && FW == 0) { FH = cap_H; FW = cap_W; }
+        if (FH < cap_H || FW < cap_W) return "the capacity is larger than the frame";
+        H = cap_H; W = cap_W;
+        return nullptr;
+    }
     if (!size_ok(H, W)) return "H and W must be >= 16 (four 2x2 pools) and H * W <= 2^22";
     if (FH == 0 && FW == 0) { FH = H; FW = W; }
     if (FH < H || FW < W) return "the frame is smaller than the crop";
     return nullptr;
 }
+
+static const char* SHORT_WORKSPACE = "the workspace is null or smaller than moss_lpips_vgg_workspace_bytes(H, W) (of cap_H, cap_W with a capacity)";
 
 // LPIPS.forward, lpipsPyTorch/modules/lpips.py:31-37 (net_type='vgg')
 extern "C" int moss_lpips_vgg_forward(const moss_lpips_vgg_args* a, void* stream)
@@ -504,15 +581,16 @@ extern "C" int moss_lpips_vgg_forward(const moss_lpips_vgg_args* a, void* stream
     const char* me = "moss_lpips_vgg_forward";
     if (!a) return invalid_arg(me, "null argument block");
     int FH = a->frame_H, FW = a->frame_W;
-    if (const char* why = check_frame(a->H, a->W, FH, FW)) return invalid_arg(me, why);
+    int H = a->H, W = a->W;
+    if (const char* why = check_frame(H, W, a->cap_H, a->cap_W, a->rect, FH, FW)) return invalid_arg(me, why);
     if (!a->x || !a->y || !a->out || !a->shift || !a->scale) return invalid_arg(me, "null x, y, out, shift or scale");
     for (int i = 0; i < NCONV; i++)
         if (!a->weights[i] || !a->biases[i]) return invalid_arg(me, "null weight or bias (13 of each, packed by moss_lpips_vgg_pack_weights)");
     for (int l = 0; l < NTAP; l++)
         if (!a->lin[l]) return invalid_arg(me, "null lin weight (5)");
-    const Geo g = geometry(a->H, a->W);
-    if (!a->workspace || a->workspace_bytes < g.workspace_bytes)
-        return invalid_arg(me, "the workspace is null or smaller than moss_lpips_vgg_workspace_bytes(H, W)");
+    const Geo g = geometry(H, W);
+    if (!a->workspace || a->workspace_bytes < g.workspace_bytes) return invalid_arg(me, SHORT_WORKSPACE);
+    auto dyn_at = [&](int level) { return Dyn{a->rect, a->cap_H, a->cap_W, level}; };     // (cap_H == 0: the kernels take the sizes below)
     hipStream_t s = (hipStream_t)stream;
     float* cur = reinterpret_cast<float*>(a->workspace);
     float* nxt = reinterpret_cast<float*>(a->workspace + g.buf_bytes);
@@ -520,27 +598,33 @@ extern "C" int moss_lpips_vgg_forward(const moss_lpips_vgg_args* a, void* stream
     char* sv = a->saved;
     auto mask_at = [&](int i) { return sv ? reinterpret_cast<uint32_t*>(sv + g.mask_off[i]) : nullptr; };
 
-    const int HW0 = a->H * a->W;
-    hipLaunchKernelGGL(conv_first_kernel, dim3(grid_for(4ll * HW0)), dim3(WG), 0, s, a->x, a->y, a->rect, FH, FW, a->H, a->W,
-                       a->weights[0], a->biases[0], a->shift, a->scale, cur, mask_at(0));
+    const int HW0 = H * W;
+    if (a->cap_H > 0)
+        hipLaunchKernelGGL(conv_first_kernel<true>, dim3(grid_for(4ll * HW0)), dim3(WG), 0, s, a->x, a->y, a->rect, FH, FW, H, W,
+                           a->weights[0], a->biases[0], a->shift, a->scale, cur, mask_at(0), dyn_at(0));
+    else
+        hipLaunchKernelGGL(conv_first_kernel<false>, dim3(grid_for(4ll * HW0)), dim3(WG), 0, s, a->x, a->y, a->rect, FH, FW, H, W,
+                           a->weights[0], a->biases[0], a->shift, a->scale, cur, mask_at(0), dyn_at(0));
     int tap = 0;
     ReduceArgs red{};
+    red.dyn = dyn_at(0);
     for (int i = 1; i < NCONV; i++) {
         const int l = CONV_LEVEL[i], HW = g.H[l] * g.W[l];
         ConvArgs c{};
         c.in = cur; c.w = a->weights[i]; c.bias = a->biases[i]; c.out = nxt; c.mask_out = mask_at(i);
         c.M = 2 * HW; c.mask_rows = HW; c.H = g.H[l]; c.W = g.W[l]; c.Cin = CONV_COUT[i - 1]; c.Cout = CONV_COUT[i];
+        c.dyn = dyn_at(l); c.nimg = 2;
         launch_conv<MODE_FWD>(c, s);
         std::swap(cur, nxt);
         if (i != TAP_CONV[tap]) continue;
         const int C = TAP_C[tap];
         hipLaunchKernelGGL(tap_kernel, dim3((HW + 3) / 4), dim3(WG), 0, s, (const float*)cur, HW, C, a->lin[tap],
-                           partial + g.partial_off[tap], sv ? reinterpret_cast<float*>(sv + g.g_off[tap]) : nullptr);
+                           partial + g.partial_off[tap], sv ? reinterpret_cast<float*>(sv + g.g_off[tap]) : nullptr, dyn_at(l));
         red.off[tap] = (int)g.partial_off[tap];
         red.cnt[tap] = HW;
         if (tap + 1 < NTAP) {
             hipLaunchKernelGGL(pool_kernel, dim3(grid_for(2ll * g.H[l + 1] * g.W[l + 1] * (C / 16))), dim3(WG), 0, s, (const float*)cur, nxt,
-                               sv ? reinterpret_cast<uint32_t*>(sv + g.win_off[tap]) : nullptr, 2, g.H[l], g.W[l], C);
+                               sv ? reinterpret_cast<uint32_t*>(sv + g.win_off[tap]) : nullptr, 2, g.H[l], g.W[l], C, dyn_at(l));
             std::swap(cur, nxt);
         }
         tap++;
@@ -555,13 +639,14 @@ extern "C" int moss_lpips_vgg_backward(const moss_lpips_vgg_backward_args* a, vo
     const char* me = "moss_lpips_vgg_backward";
     if (!a) return invalid_arg(me, "null argument block");
     int FH = a->frame_H, FW = a->frame_W;
-    if (const char* why = check_frame(a->H, a->W, FH, FW)) return invalid_arg(me, why);
+    int H = a->H, W = a->W;
+    if (const char* why = check_frame(H, W, a->cap_H, a->cap_W, a->rect, FH, FW)) return invalid_arg(me, why);
     if (!a->saved || !a->g_out || !a->dL_dx || !a->scale) return invalid_arg(me, "null saved (the forward's), g_out, dL_dx or scale");
     for (int i = 0; i < NCONV; i++)
         if (!a->weights_bwd[i]) return invalid_arg(me, "null backward weight (13, packed by moss_lpips_vgg_pack_weights)");
-    const Geo g = geometry(a->H, a->W);
-    if (!a->workspace || a->workspace_bytes < g.workspace_bytes)
-        return invalid_arg(me, "the workspace is null or smaller than moss_lpips_vgg_workspace_bytes(H, W)");
+    const Geo g = geometry(H, W);
+    if (!a->workspace || a->workspace_bytes < g.workspace_bytes) return invalid_arg(me, SHORT_WORKSPACE);
+    auto dyn_at = [&](int level) { return Dyn{a->rect, a->cap_H, a->cap_W, level}; };     // (cap_H == 0: the kernels take the sizes below)
     hipStream_t s = (hipStream_t)stream;
     float* cur = reinterpret_cast<float*>(a->workspace);
     float* nxt = reinterpret_cast<float*>(a->workspace + g.buf_bytes);
@@ -576,18 +661,19 @@ extern "C" int moss_lpips_vgg_backward(const moss_lpips_vgg_backward_args* a, vo
             hipLaunchKernelGGL(unpool_tap_kernel, dim3(grid_for((long long)g.H[l] * g.W[l] * (TAP_C[l] / 4))), dim3(WG), 0, s,
                                reinterpret_cast<const float*>(sv + g.g_off[l]), from_above,
                                from_above ? reinterpret_cast<const uint32_t*>(sv + g.win_off[l]) : nullptr, mask_at(i), nxt, g.H[l], g.W[l],
-                               TAP_C[l]);
+                               TAP_C[l], dyn_at(l));
             std::swap(cur, nxt);
         }
         const bool pooled_below = CONV_LEVEL[i - 1] != l;                // the input of convolution i is a pool's output
         ConvArgs c{};
         c.in = cur; c.w = a->weights_bwd[i]; c.out = nxt; c.mask_in = pooled_below ? nullptr : mask_at(i - 1);
         c.M = g.H[l] * g.W[l]; c.H = g.H[l]; c.W = g.W[l]; c.Cin = CONV_COUT[i]; c.Cout = CONV_COUT[i - 1];
+        c.dyn = dyn_at(l); c.nimg = 1;
         if (pooled_below) launch_conv<MODE_BWD_PLAIN>(c, s); else launch_conv<MODE_BWD_MASK>(c, s);
         std::swap(cur, nxt);
         from_above = pooled_below ? cur : nullptr;
     }
     hipLaunchKernelGGL(conv_first_backward_kernel, dim3(grid_for((long long)FH * FW)), dim3(WG), 0, s, (const float*)cur, a->rect, FH, FW,
-                       a->H, a->W, a->weights_bwd[0], a->scale, a->g_out, a->dL_dx);
+                       H, W, a->weights_bwd[0], a->scale, a->g_out, a->dL_dx, dyn_at(0));
     return launch_status(me);
 }

@@ -12,7 +12,8 @@ through a non-trainable 1x1 convolution to one channel and a spatial mean; the f
   backward reads sign masks, pool winners and the tap gradients the forward left, never a layer input.  No host read, no atomics,
   bitwise reproducible, capturable.
 * :func:`lpips_vgg_roi_fused` -- the same on the ``ViewRegion`` rectangle of two full frames (no crop copies; the offset is read on the
-  device).
+  device, and with ``capacity=`` the crop's size too: one capture serves views whose crops differ in size).
+  :func:`crop_capacity` -- the capacity of a dataset's views.
 * :func:`lpips_vgg_torch` -- the same mathematics in plain torch (any dtype or device): the yardstick of the tests and of
   scripts/lpips_times.py.  Not a fallback: the fused op has no CPU path.
 * :func:`synthetic_weights` -- VGG16-shaped weights from a seed (a frozen ``numpy.random.RandomState`` stream), for tests, the timing
@@ -27,7 +28,7 @@ import hashlib
 
 import torch
 
-__all__ = ["LpipsVGG", "lpips_vgg_fused", "lpips_vgg_roi_fused", "lpips_vgg_torch", "synthetic_weights", "weights_sha256",
+__all__ = ["LpipsVGG", "lpips_vgg_fused", "lpips_vgg_roi_fused", "crop_capacity", "lpips_vgg_torch", "synthetic_weights", "weights_sha256",
            "CONV_SHAPES", "TAP_CHANNELS", "TAP_AFTER_CONV", "POOL_AFTER_CONV", "SHIFT", "SCALE", "MIN_SIZE"]
 
 _WIDTHS = (64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512)
@@ -202,15 +203,16 @@ class LpipsVGG:
 
 # ---- the fused op -----------------------------------------------------------------------------------------------------------------
 
-def _fill_common(a, net, h, w, frame, rect):
+def _fill_common(a, net, h, w, frame, rect, capacity):
     a.H, a.W = h, w
     a.frame_H, a.frame_W = frame
     a.rect = None if rect is None else rect.data_ptr()
+    a.cap_H, a.cap_W = (0, 0) if capacity is None else capacity
 
 
 class _LpipsVGG(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, y, net, crop, rect):
+    def forward(ctx, x, y, net, crop, rect, capacity):
         from ._lib import LpipsVggArgs, call, lib
         dev = x.device
         FH, FW = int(x.shape[-2]), int(x.shape[-1])
@@ -221,10 +223,10 @@ class _LpipsVGG(torch.autograd.Function):
         terms = torch.empty(5, dtype=torch.float32, device=dev)
         nbytes = int(L.moss_lpips_vgg_workspace_bytes(FH, FW))                        # (sized for the frame: any crop of it fits)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        saved = torch.empty(int(L.moss_lpips_vgg_saved_bytes(h, w)) if keep else 0, dtype=torch.uint8, device=dev)
+        saved = torch.empty(int(L.moss_lpips_vgg_saved_bytes(*(capacity or (h, w)))) if keep else 0, dtype=torch.uint8, device=dev)
         a = LpipsVggArgs()
         a.x, a.y = x.data_ptr(), y.data_ptr()
-        _fill_common(a, net, h, w, (FH, FW), rect)
+        _fill_common(a, net, h, w, (FH, FW), rect, capacity)
         for i in range(13):
             a.weights[i], a.biases[i] = net.w_fwd[i].data_ptr(), net.biases[i].data_ptr()
         for i in range(5):
@@ -234,7 +236,7 @@ class _LpipsVGG(torch.autograd.Function):
         a.saved = saved.data_ptr() if keep else None
         a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
         call("moss_lpips_vgg_forward", dev, ctypes.byref(a))
-        ctx.net, ctx.crop, ctx.frame = net, (h, w), (FH, FW)
+        ctx.net, ctx.crop, ctx.frame, ctx.capacity = net, (h, w), (FH, FW), capacity
         ctx.save_for_backward(saved, rect if rect is not None else torch.empty(0, dtype=torch.int32, device=dev))
         ctx.mark_non_differentiable(terms)
         return out, terms
@@ -250,13 +252,13 @@ class _LpipsVGG(torch.autograd.Function):
         nbytes = int(lib().moss_lpips_vgg_workspace_bytes(FH, FW))
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         a = LpipsVggBackwardArgs()
-        _fill_common(a, net, h, w, (FH, FW), rect if rect.numel() else None)
+        _fill_common(a, net, h, w, (FH, FW), rect if rect.numel() else None, ctx.capacity)
         for i in range(13):
             a.weights_bwd[i] = net.w_bwd[i].data_ptr()
         a.scale, a.saved, a.g_out, a.dL_dx = net.scale.data_ptr(), saved.data_ptr(), g.data_ptr(), d_x.data_ptr()
         a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
         call("moss_lpips_vgg_backward", dev, ctypes.byref(a))
-        return d_x, None, None, None, None
+        return d_x, None, None, None, None, None
 
 
 def _check_images(what, net, x, y):
@@ -278,11 +280,11 @@ def _check_images(what, net, x, y):
         raise RuntimeError(f"{what}: y is the ground truth and gets no gradient; detach it")
 
 
-def _apply(net, x, y, crop, rect, return_terms):
+def _apply(net, x, y, crop, rect, return_terms, capacity=None):
     shape = x.shape
     x3 = x.reshape(3, shape[-2], shape[-1]).contiguous()
     y3 = y.detach().reshape(3, shape[-2], shape[-1]).contiguous()
-    value, terms = _LpipsVGG.apply(x3, y3, net, crop, rect)
+    value, terms = _LpipsVGG.apply(x3, y3, net, crop, rect, capacity)
     return (value, terms) if return_terms else value
 
 
@@ -297,11 +299,53 @@ def lpips_vgg_fused(net, x, y, return_terms=False):
     return _apply(net, x, y, None, None, return_terms)
 
 
-def lpips_vgg_roi_fused(net, image, gt_image, region, return_terms=False):
+def crop_capacity(regions):
+    """The per-axis maximum ``(h, w)`` over an iterable of ``ViewRegion``: the ``capacity`` of :func:`lpips_vgg_roi_fused` that fits
+    every one of them.  Host arithmetic on ``region.xywh``; compute it once, when the dataset is loaded."""
+    cap_h = cap_w = 0
+    for r in regions:
+        _, _, w, h = r.xywh
+        cap_h, cap_w = max(cap_h, int(h)), max(cap_w, int(w))
+    if cap_h == 0:
+        raise ValueError("crop_capacity: no regions")
+    return cap_h, cap_w
+
+
+def resolve_capacity(what, capacity, H, W):
+    """``capacity`` as ``(cap_h, cap_w)`` ints for an H x W frame: a pair, or ``"frame"``; raises if it is not a size the kernels take."""
+    if isinstance(capacity, str):
+        if capacity != "frame":
+            raise ValueError(f"{what}: capacity must be (cap_h, cap_w) or 'frame', got {capacity!r}")
+        return int(H), int(W)
+    cap_h, cap_w = (int(v) for v in capacity)
+    if min(cap_h, cap_w) < MIN_SIZE or cap_h > H or cap_w > W:
+        raise ValueError(f"{what}: the capacity must be at least {MIN_SIZE}x{MIN_SIZE} and fit the {H}x{W} frame, got {cap_h}x{cap_w}")
+    return cap_h, cap_w
+
+
+def lpips_vgg_roi_fused(net, image, gt_image, region, return_terms=False, capacity=None):
     """``loss_fn_vgg(image[:, y:y+h, x:x+w], gt_image[...])`` for ``(x, y, w, h) = region.xywh`` (train_ZJU.py:115-121) on the FULL
-    frames: the crop's size is the region's, its offset is read from ``region.rect`` on the device -- no host read, no crop copies --
-    and the gradient is written for the whole ``image`` (zero off the crop).  Capturable; a replay changes view by ``region.copy_``
-    among views of one crop size."""
+    frames: the gradient is written for the whole ``image`` (zero off the crop), there is no host read and there are no crop copies.
+    Capturable.
+
+    ``capacity=None``: the crop's size is the region's NOW and goes into the launches; its offset is read from ``region.rect`` on the
+    device.  A replay changes view by ``region.copy_`` among views of that one crop size only.
+
+    ``capacity=(cap_h, cap_w)`` or ``"frame"``: the crop's size is read from ``region.rect`` on the device as well, and the launches and
+    buffers are sized for the capacity -- the largest crop the call will see (:func:`crop_capacity` of the dataset's views).  A replay
+    changes view by ``region.copy_`` among views of ANY size from ``MIN_SIZE`` up to the capacity; MOSS's bounding rectangles change
+    with the pose (scene/dataset_readers.py:432-439, train_ZJU.py:115).  A region that does not fit the capacity raises here; under
+    replay nothing on the host sees it, so a caller checks there (``MossStep.check``).  The arithmetic is that of the static call.
+    The wide convolution has two kernel shapes which sum K in different orders, picked by the row count -- here the capacity's -- so
+    the result is bit-identical to the static call at the same crop exactly when every layer gets the same shape in both: always when
+    the crop equals the capacity, and for any capacity up to 64x64 on a device with more than 64 CUs.  Otherwise the two agree to
+    float32 summation order and meet the same bar against float64."""
+    cap = None
+    if capacity is not None:                                 # (host arithmetic on the region alone, before anything touches a device)
+        cap = resolve_capacity("lpips_vgg_roi_fused", capacity, *region.bound.shape)
+        _, _, w, h = region.xywh
+        if h > cap[0] or w > cap[1]:
+            raise ValueError(f"lpips_vgg_roi_fused: the region's crop {h}x{w} exceeds the capacity {cap[0]}x{cap[1]}")
     _check_images("lpips_vgg_roi_fused", net, image, gt_image)
     H, W = image.shape[-2:]
     if tuple(region.bound.shape) != (H, W) or region.rect.device != image.device:
@@ -309,4 +353,4 @@ def lpips_vgg_roi_fused(net, image, gt_image, region, return_terms=False):
     _, _, w, h = region.xywh
     if min(h, w) < MIN_SIZE or h > H or w > W:
         raise ValueError(f"lpips_vgg_roi_fused: the crop must be at least {MIN_SIZE}x{MIN_SIZE} and fit the frame, got {h}x{w}")
-    return _apply(net, image, gt_image, (int(h), int(w)), region.rect, return_terms)
+    return _apply(net, image, gt_image, (int(h), int(w)), region.rect, return_terms, cap)

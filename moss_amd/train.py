@@ -45,7 +45,13 @@ class MossStep:
     ``motion_offset_flag=True``.  ``view``: a camera with ``smpl_param`` (``pose_rotmats`` included), ``big_pose_smpl_param`` and
     ``big_pose_world_vertex``.  ``gt_image`` (3,H,W), ``bkgd_mask`` (1,H,W), ``region`` (a ``loss.ViewRegion``), ``bg`` (3,);
     ``lpips_net``: an ``lpips.LpipsVGG``.  ALL of them are static inputs: the caller changes frame between steps by ``copy_`` into
-    these tensors and ``region.copy_`` (among views of one crop size: LPIPS bakes the crop's size into its launches).
+    these tensors and ``region.copy_``.
+
+    ``lpips_capacity``: ``(cap_h, cap_w)`` -- ``lpips.crop_capacity`` of the dataset's regions -- or ``"frame"``; it goes to
+    ``lpips_vgg_roi_fused(capacity=)``, which then reads the crop's size from the device like the other loss terms, so the frames a
+    capture is replayed on may have crops of any size up to the capacity (MOSS's do: the rectangle follows the pose).  Without it
+    LPIPS has the size of the region at capture in its launches and every replayed frame must have exactly that crop size.  Under
+    replay nothing on the host sees the region; :meth:`check` does, and raises on a region the capture cannot serve.
 
     ``lrs``: ``{"auto_regression": lr, "cross_attention_lbs": lr}`` (MOSS: 2.5e-4 and 1e-4), optionally with rates for the Gaussian
     groups by their ``param_groups()`` names (``xyz``, ``features`` -- a number or ``(lr_dc, lr_rest)`` --, ``opacity``, ``scaling``,
@@ -70,7 +76,7 @@ class MossStep:
 
     ``terms`` (7 floats on the device, :data:`TERM_NAMES`): the six loss terms and the total of the last step."""
 
-    def __init__(self, pc, view, gt_image, bkgd_mask, region, bg, lpips_net, lrs, context=None, stats=None):
+    def __init__(self, pc, view, gt_image, bkgd_mask, region, bg, lpips_net, lrs, context=None, stats=None, lpips_capacity=None):
         from .diff_gaussian_rasterization import RasterContext
         from .dist import GradBucket
         from .optim import FlatAdamW
@@ -87,6 +93,11 @@ class MossStep:
                 raise ValueError(f"MossStep: lrs has no rate for '{k}'")
         self.pc, self.view, self.gt_image, self.bkgd_mask, self.region, self.bg, self.lpips_net = pc, view, gt_image, bkgd_mask, region, bg, lpips_net
         self.stats = stats
+        if lpips_capacity is not None:
+            from .lpips import resolve_capacity
+            lpips_capacity = resolve_capacity("MossStep", lpips_capacity, *region.bound.shape)
+        self.lpips_capacity = lpips_capacity
+        self._captured_crop = None                           # (h, w) of the region at capture: what LPIPS launched for without a capacity
         dev = pc._xyz.device
         self.context = cx = context if context is not None else RasterContext()
         if not cx.enabled:
@@ -142,7 +153,7 @@ class MossStep:
         image, gt = out["render"], self.gt_image
         photometric = training_loss_moss_fused(image, out["render_alpha"], gt, self.bkgd_mask, self.region, w["ssim"], w["mask_l2"],
                                                terms_out=self._terms[:4])
-        lpips = lpips_vgg_roi_fused(self.lpips_net, image, gt, self.region).reshape(())
+        lpips = lpips_vgg_roi_fused(self.lpips_net, image, gt, self.region, capacity=self.lpips_capacity).reshape(())
         nll = out["pose_out"]["nll"].mean()
         s3im = s3im_loss_roi_fused(image, gt, self.region)
         loss = photometric + w["lpips"] * lpips + w["nll"] * nll + w["s3im"] * s3im
@@ -196,6 +207,7 @@ class MossStep:
         model where it found it.  Returns ``self``."""
         from .graphs import GraphedStep
         state = self._state()
+        self._captured_crop = (int(self.region.xywh[3]), int(self.region.xywh[2]))
         self.graphed = GraphedStep(self.compute, warmup=warmup, device=self.pc._xyz.device, context=self.context)
         self._restore(state)
         return self
@@ -207,9 +219,20 @@ class MossStep:
 
     def check(self) -> bool:
         """``GraphedStep.check()``: verifies the last replayed frame, counts the dropped ones (``dropped_frames``) and re-captures
-        when the binning capacity has grown.  Synchronises; call it every few hundred steps.  True if it re-captured."""
+        when the binning capacity has grown.  Synchronises; call it every few hundred steps.  True if it re-captured.  Raises if the
+        region loaded now is one the captured LPIPS does not serve: a crop beyond ``lpips_capacity``, or, without a capacity, a crop
+        of another size than the one captured (its LPIPS term was taken on a crop of the captured size)."""
         if self.graphed is None:
             raise RuntimeError("MossStep.check(): nothing is captured")
+        h, w = int(self.region.xywh[3]), int(self.region.xywh[2])
+        if self.lpips_capacity is not None:
+            if h > self.lpips_capacity[0] or w > self.lpips_capacity[1]:
+                raise RuntimeError(f"MossStep.check(): the region's crop {h}x{w} exceeds lpips_capacity {self.lpips_capacity[0]}x"
+                                   f"{self.lpips_capacity[1]}: the LPIPS term of the last replay was taken on a clamped crop")
+        elif (h, w) != self._captured_crop:
+            raise RuntimeError(f"MossStep.check(): the region's crop is {h}x{w} but LPIPS was captured at {self._captured_crop[0]}x"
+                               f"{self._captured_crop[1]}, so the LPIPS term of the last replay was taken on the wrong crop; build the "
+                               "step with lpips_capacity= (lpips.crop_capacity of the dataset's regions) to replay frames whose crops differ")
         return self.graphed.check()
 
     @property
