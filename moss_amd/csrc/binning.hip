@@ -21,6 +21,7 @@
 //   Sorting 8-byte keys once in LDS replaces 6 global passes over 12-byte pairs: algorithmic HBM traffic of the
 //   sort falls from >= 24 B/instance/pass to 8 B write + 8 B read + 4 B write per instance in total.
 #include "common.h"
+#include "sort_deal.h"
 
 namespace moss {
 
@@ -36,6 +37,7 @@ namespace {
 // 2048 entries, and each part of a two-chunk tile still loads the whole sibling (profiles/r05_notes.md).  Not adopted.
 constexpr int SORT_THREADS = 1024, KPT = 1;
 constexpr int CHUNK = SORT_THREADS * KPT;
+static_assert(sort_deal::CHUNK == CHUNK && sort_deal::MIN_PAD == 64 * KPT, "sort_deal.h: the chunk and the smallest padded size");
 
 // The scan's outputs for one block of `NT` threads (NT a multiple of 64, <= 1024): see scan_kernel.  Shared by scan_kernel (its own
 // launch: synchronous mode, where the host sizes the binning buffer from R before anything else can run) and by the LAST block of
@@ -370,10 +372,35 @@ __device__ __forceinline__ uint32_t lane_xor(uint32_t v, uint32_t lane)
 }
 #undef MOSS_DPP
 
+// Which lanes of a wave keep the SMALLER key of a compare-exchange with partner distance J in a bitonic phase K (element i: "the
+// lower partner of an ascending run", ((i & J) == 0) == ((i & K) == 0)), as a 64-bit lane mask in SCALAR registers.  TJ, TK: the two
+// distances in threads.  A bit of the thread index below 64 is a lane pattern known at compile time, one at or above 64 is the same
+// for the whole wave (`wave`: the wave's index in the workgroup, in a scalar register), so the mask is a literal -- XOR a wave-uniform
+// all-or-nothing word for the steps of the phases K >= 64 threads.  (Left to the compiler -- a per-lane bool from `tid` -- the 44
+// masks of the phases above 64 were computed once per workgroup with v_cmp, parked in the lanes of two spill VGPRs under the 80-SGPR
+// cap and fetched back with two v_readlane per step: 82 v_writelane + 88 v_readlane in the vector issue slots of every sorting wave.)
+template <int B>
+__device__ __forceinline__ uint64_t bit_clear_mask(uint32_t wave)
+{
+    if constexpr (B < 64) {
+        uint64_t m = 0ull;
+        for (int l = 0; l < 64; l++) if ((l & B) == 0) m |= 1ull << l;
+        return m;
+    } else return (wave & (uint32_t)(B / 64)) == 0u ? ~0ull : 0ull;
+}
+template <int TK, int TJ>
+__device__ __forceinline__ uint64_t take_min_mask(uint32_t wave) { return ~(bit_clear_mask<TJ>(wave) ^ bit_clear_mask<TK>(wave)); }
+// key = (key < other) == take_min ? key : other, the comparison's lane mask combined with the step's on the scalar unit
+__device__ __forceinline__ uint64_t exchange(uint64_t key, uint64_t other, uint64_t take_min)
+{
+    const uint64_t take_other = __builtin_amdgcn_ballot_w64(key < other) ^ take_min;      // (lt != take_min ... of the lanes alive)
+    return __builtin_amdgcn_inverse_ballot_w64(~take_other) ? key : other;
+}
+
 // Element i of a chunk lives in thread i / KPT, register i % KPT: steps with partner distance J < KPT are compare-exchanges between a
 // thread's own registers; J / KPT < 64: the partner thread is in the same wave (lane_xor); larger: through LDS.
 template <int K, int J>
-__device__ __forceinline__ void network_steps(uint64_t (&key)[KPT], uint32_t tid, uint64_t (*s_buf)[CHUNK], int& p)
+__device__ __forceinline__ void network_steps(uint64_t (&key)[KPT], uint32_t tid, uint32_t wave, uint64_t (*s_buf)[CHUNK], int& p)
 {
     if constexpr (J < KPT) {
 #pragma unroll
@@ -392,30 +419,23 @@ __device__ __forceinline__ void network_steps(uint64_t (&key)[KPT], uint32_t tid
 #pragma unroll
         for (int e = 0; e < KPT; e++) {
             const uint32_t i = tid * (uint32_t)KPT + (uint32_t)e;
-            const uint64_t other = s_buf[p][i ^ (uint32_t)J];
-            const bool take_min = ((i & (uint32_t)J) == 0u) == ((i & (uint32_t)K) == 0u);     // lower partner of an ascending run
-            const bool lt = key[e] < other;
-            key[e] = (lt == take_min) ? key[e] : other;
+            key[e] = exchange(key[e], s_buf[p][i ^ (uint32_t)J], take_min_mask<K / KPT, J / KPT>(wave));
         }
         p ^= 1;                                            // the next cross-wave step writes the other buffer: no second barrier
     } else {
 #pragma unroll
         for (int e = 0; e < KPT; e++) {
             const uint32_t lo = lane_xor<J / KPT>((uint32_t)key[e], tid), hi = lane_xor<J / KPT>((uint32_t)(key[e] >> 32), tid);
-            const uint64_t other = ((uint64_t)hi << 32) | lo;
-            const uint32_t i = tid * (uint32_t)KPT + (uint32_t)e;
-            const bool take_min = ((i & (uint32_t)J) == 0u) == ((i & (uint32_t)K) == 0u);
-            const bool lt = key[e] < other;
-            key[e] = (lt == take_min) ? key[e] : other;
+            key[e] = exchange(key[e], ((uint64_t)hi << 32) | lo, take_min_mask<K / KPT, J / KPT>(wave));
         }
     }
-    if constexpr (J > 1) network_steps<K, J / 2>(key, tid, s_buf, p);
+    if constexpr (J > 1) network_steps<K, J / 2>(key, tid, wave, s_buf, p);
 }
 template <int K>
-__device__ __forceinline__ void network_phases(uint64_t (&key)[KPT], uint32_t tid, uint32_t npad, uint64_t (*s_buf)[CHUNK], int& p)
+__device__ __forceinline__ void network_phases(uint64_t (&key)[KPT], uint32_t tid, uint32_t wave, uint32_t npad, uint64_t (*s_buf)[CHUNK], int& p)
 {
-    if constexpr (K > 2) network_phases<K / 2>(key, tid, npad, s_buf, p);
-    if ((uint32_t)K <= npad) network_steps<K, K / 2>(key, tid, s_buf, p);          // (wave-uniform)
+    if constexpr (K > 2) network_phases<K / 2>(key, tid, wave, npad, s_buf, p);
+    if ((uint32_t)K <= npad) network_steps<K, K / 2>(key, tid, wave, s_buf, p);    // (wave-uniform)
 }
 
 // Stage A of the sort: one workgroup per CHUNK of a tile's bucket (a tile of n entries has ceil(n/CHUNK) chunks), sorted and
@@ -433,6 +453,12 @@ __device__ __forceinline__ void network_phases(uint64_t (&key)[KPT], uint32_t ti
 // turn of the workgroup -- and ONE EXTRA BLOCK at the end of the grid writes what the later kernels need (ranges, chunk bases, tile
 // order, work table, header, group bases: scan_outputs), so the scan costs no launch of its own.  A frame that overflowed (more
 // instances than the capacity, or a tile that outgrew its bucket) is seen by every workgroup alike: nothing is sorted.
+// THE DEAL (self-scan): turn r of the kernel -- workgroup wg takes the turns wg, wg + grid, ... -- is not chunk r but the r-th chunk by
+// padded size class, largest class first (sort_deal.h).  The bench frame's 340 chunks run on 512 resident workgroups: the 256 that are
+// dispatched first, one per CU, take the full chunks, and the ones that have to share a CU take the frame's shortest, whose networks are
+// a third as long and whose idle waves leave at once.  In tile order, which chunks shared a CU was an accident of tile position and the
+// kernel lasted as long as its late sharing workgroups (profiles/sort_deal_notes.md: 13.4 -> 12.5 us; -> 10.0 us with the step masks
+// as scalar literals, take_min_mask above).  merge_gather_kernel keeps its XCD-aware order: it needs the L2 locality, the sort does not.
 // SORT_PER: tiles per thread of the self-scan, at most -- 1 (T <= 1024: a 512 x 512 frame; the instantiation that must keep its two
 // workgroups per CU: 64 VGPRs) or MAX_LDS_TILES / SORT_THREADS = 8
 template <int SORT_PER>
@@ -450,7 +476,10 @@ chunk_sort_kernel(int T, uint2* __restrict__ ranges, uint32_t* __restrict__ chun
     __shared__ uint32_t s_wave[16];
     __shared__ uint32_t s_max;
     __shared__ uint32_t s_bucket[34];
+    __shared__ uint32_t s_deal[sort_deal::TOP * 16];         // self-scan: [class k < TOP][wave] tiles of the wave whose last chunk is of class k
+    static_assert(sort_deal::TOP * 16 == 64 && SORT_THREADS == 1024, "the deal's table is one word per lane: TOP classes x 16 waves");
     const uint32_t tid = threadIdx.x;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));      // (in a scalar register: the step masks, the deal)
     const bool self_scan = key_stride != 0u;
     uint32_t grid = gridDim.x, wg = blockIdx.x;              // workgroups that sort, and this one's index among them
     if (self_scan) {
@@ -474,7 +503,7 @@ chunk_sort_kernel(int T, uint2* __restrict__ ranges, uint32_t* __restrict__ chun
 #define RSTAMP(i) if (stamps && tid == 0) stamps[(size_t)blockIdx.x * 8 + (i)] = __builtin_amdgcn_s_memrealtime()   /* 100 MHz, device-wide */
     KSTAMP(0); RSTAMP(5);
     // self-scan: this thread's tiles, their counts and chunk bases
-    uint32_t my_cnt[SORT_PER], my_cb[SORT_PER], n_chunks_dev = 0u;
+    uint32_t my_cnt[SORT_PER], my_cb[SORT_PER], my_lc = 0u, n_chunks_dev = 0u;
     const int per = (T + SORT_THREADS - 1) / SORT_THREADS;
     if (self_scan) {
         // (a count above the bucket size means the preprocess kernel dropped keys: the scan block flags the frame and empties every
@@ -488,23 +517,84 @@ chunk_sort_kernel(int T, uint2* __restrict__ ranges, uint32_t* __restrict__ chun
             my_cnt[u] = (u < per && t < T) ? min(tile_count[t], key_stride) : 0u;
             nch += (my_cnt[u] + CHUNK - 1) / CHUNK;
         }
+        // the deal (sort_deal.h: turn r sorts the r-th chunk by size class, largest first): how many of this wave's tiles end in a chunk
+        // of each class below the top one -- ballots, summed on the scalar unit; the block scan's barriers publish the table
+        // (my_lc: the class of the last chunk of each of the thread's tiles, a nibble per tile -- 0xf: an empty tile)
+#pragma unroll
+        for (int u = 0; u < SORT_PER; u++) my_lc |= (SORT_PER == 1 || u < per ? sort_deal::last_class(my_cnt[u]) & 0xfu : 0xfu) << (4 * u);
+        {
+            uint32_t mine = 0u;
+#pragma unroll
+            for (uint32_t k = 0; k < sort_deal::TOP; k++) {
+                uint32_t n_k = 0u;
+#pragma unroll
+                for (int u = 0; u < SORT_PER; u++)
+                    if (SORT_PER == 1 || u < per) n_k += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(((my_lc >> (4 * u)) & 0xfu) == k));
+                mine = (tid & 63u) == k ? n_k : mine;
+            }
+            if ((tid & 63u) < sort_deal::TOP) s_deal[(tid & 63u) * 16u + wave] = mine;
+        }
         uint32_t cb = block_scan<1024>(nch, s_wave, n_chunks_dev);
+        n_chunks_dev = (uint32_t)__builtin_amdgcn_readfirstlane((int)n_chunks_dev);     // (the same in every lane: the deal's arithmetic stays scalar)
         if (n_chunks_dev == 0u) return;                      // nothing rendered
 #pragma unroll
         for (int u = 0; u < SORT_PER; u++) { my_cb[u] = cb; cb += (my_cnt[u] + CHUNK - 1) / CHUNK; }
     }
-    for (uint32_t c = wg;; c += grid) {
+    for (uint32_t c = wg;; c += grid) {                      // turns of this workgroup
         if (self_scan) {
             if (c >= n_chunks_dev) return;
+            // Turn c -> (class k, index q inside the class): every wave reads the table, one word per lane, and scans its rows of 16
+            // (DPP); the classes' totals and the counts of the waves in front of this one come out of it by lane reads.  Then every
+            // thread asks whether the q-th chunk of class k belongs to one of its tiles: the tiles in front of it that count are
+            // those of the waves in front + of the lanes below (ballot, mbcnt) + its own earlier ones.
+            // (opaque per turn: otherwise everything below that depends on the tiles alone -- eight tiles' nibbles, chunk counts,
+            // comparisons -- is computed in front of the turn loop and held across the network: 81 VGPRs for SORT_PER = 8)
+            uint32_t lcs = my_lc;
+            asm volatile("" : "+v"(lcs));
+            const uint32_t tab = s_deal[tid & 63u];
+            uint32_t inc = tab;
+            inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x111, 0xf, 0xf, true);     // row_shr:1
+            inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x112, 0xf, 0xf, true);     // row_shr:2
+            inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x114, 0xf, 0xf, true);     // row_shr:4
+            inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x118, 0xf, 0xf, true);     // row_shr:8
+            uint32_t small_total[sort_deal::TOP];
+#pragma unroll
+            for (uint32_t k = 0; k < sort_deal::TOP; k++) small_total[k] = (uint32_t)__builtin_amdgcn_readlane((int)inc, (int)(16u * k + 15u));
+            uint32_t k, q;
+            sort_deal::turn_class(c, n_chunks_dev, small_total, k, q);
+            const uint32_t exc = inc - tab;
+            uint32_t before = 0u;                            // (wave-uniform so far)
+            if (k < sort_deal::TOP) before = (uint32_t)__builtin_amdgcn_readlane((int)exc, (int)(16u * k + wave));
+            else {
+#pragma unroll
+                for (uint32_t i = 0; i < sort_deal::TOP; i++) before += (uint32_t)__builtin_amdgcn_readlane((int)exc, (int)(16u * i + wave));
+            }
+            uint32_t counts = 0u;                            // bit u: tile u of the thread is one of those
 #pragma unroll
             for (int u = 0; u < SORT_PER; u++) {
-                const uint32_t nch = (my_cnt[u] + CHUNK - 1) / CHUNK;
-                if (my_cb[u] <= c && c < my_cb[u] + nch) {
-                    const int t = (int)tid * per + u;
-                    s_own.tile = t; s_own.start = (uint32_t)t * key_stride; s_own.end = s_own.start + my_cnt[u]; s_own.cbase = my_cb[u];
+                if (SORT_PER == 1 || u < per) {              // (wave-uniform: the tiles the threads really have)
+                    const uint32_t lc = (lcs >> (4 * u)) & 0xfu;
+                    const bool cnts = k < sort_deal::TOP ? lc == k : lc < sort_deal::TOP;
+                    counts |= cnts ? 1u << u : 0u;
+                    const uint64_t b = __builtin_amdgcn_ballot_w64(cnts);
+                    before += __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
                 }
             }
-            if (tid == 0) { s_own.n_chunks = n_chunks_dev; s_own.c = c; }
+            uint32_t chunk = sort_deal::NONE, own_u = 0u, own_cnt = 0u, own_cb = 0u;
+#pragma unroll
+            for (int u = 0; u < SORT_PER; u++) {
+                if (SORT_PER != 1 && u >= per) break;
+                const uint32_t lc = (lcs >> (4 * u)) & 0xfu;
+                const uint32_t ch = sort_deal::claim(k, q, my_cnt[u], lc == 0xfu ? sort_deal::NONE : lc, my_cb[u], before);
+                if (ch != sort_deal::NONE) { chunk = ch; own_u = (uint32_t)u; own_cnt = my_cnt[u]; own_cb = my_cb[u]; }
+                before += (counts >> u) & 1u;
+            }
+            if (chunk != sort_deal::NONE) {                  // (one thread of the workgroup)
+                const int t = (int)tid * per + (int)own_u;
+                s_own.tile = t; s_own.start = (uint32_t)t * key_stride; s_own.end = s_own.start + own_cnt; s_own.cbase = own_cb;
+                s_own.c = chunk;
+            }
+            if (tid == 0) s_own.n_chunks = n_chunks_dev;
             __syncthreads();
         } else {
             find_chunk_tile(T, [&](uint32_t) { return c; }, ranges, chunk_base, header, &s_own);
@@ -512,7 +602,7 @@ chunk_sort_kernel(int T, uint2* __restrict__ ranges, uint32_t* __restrict__ chun
         const uint32_t n_chunks = s_own.n_chunks;
         if (c >= n_chunks) return;
         KSTAMP(1);
-        const uint32_t first = s_own.start + (c - s_own.cbase) * CHUNK;
+        const uint32_t first = s_own.start + (s_own.c - s_own.cbase) * CHUNK;      // (s_own.c: the chunk of this turn -- self-scan: by the deal)
         const uint32_t n = min((uint32_t)CHUNK, s_own.end - first);
         uint64_t* gk = keys + first;
         uint32_t npad = 64 * KPT;                          // at least one wave's worth: the intra-wave steps need no branches
@@ -531,9 +621,20 @@ chunk_sort_kernel(int T, uint2* __restrict__ ranges, uint32_t* __restrict__ chun
         uint64_t key[KPT];                                 // (a thread's keys are neighbours in memory: one 16-byte load)
 #pragma unroll
         for (int e = 0; e < KPT; e++) key[e] = tid * KPT + e < n ? gk[tid * KPT + e] : ~0ull;
-        if (stamps && tid == 0) { stamps[(size_t)blockIdx.x * 8 + 2] = key[0] ? __builtin_amdgcn_s_memtime() : 1ull; stamps[(size_t)blockIdx.x * 8 + 6] = n; }
+        if (stamps && tid == 0) {
+            // (word 6: the chunk's keys, and above them WHERE the workgroup runs -- HW_ID's {cu_id, sh_id, se_id} and the XCD -- so
+            // that scripts/sort_stamps.py can tell the workgroups that share their CU with another sorting workgroup from the lone ones)
+            uint32_t hw, xcc;
+            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+            stamps[(size_t)blockIdx.x * 8 + 2] = key[0] ? __builtin_amdgcn_s_memtime() : 1ull;
+            stamps[(size_t)blockIdx.x * 8 + 6] = n | (((hw >> 8) & 0xffu) << 16) | ((xcc & 0xfu) << 24);
+        }
         int p = 0;
-        network_phases<CHUNK>(key, tid, npad, s_keys, p);
+        uint32_t wv = wave;
+        asm volatile("" : "+s"(wv));                       // (opaque per turn: the masks of the phases K >= 64 are made where they are used --
+                                                           // as loop invariants they were all made in front of the loop and spilled to lanes again)
+        network_phases<CHUNK>(key, tid, wv, npad, s_keys, p);
         KSTAMP(3);
 #pragma unroll
         for (int e = 0; e < KPT; e++) if (tid * KPT + e < n) gk[tid * KPT + e] = key[e];

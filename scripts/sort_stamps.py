@@ -31,6 +31,25 @@ for name, off in (("chunk_sort [lookup, key load, network, store]", 0), ("merge_
         np.median(w[:, 5] - t0) / 100, (w[:, 5].max() - t0) / 100, np.median(w[:, 7] - t0) / 100, np.percentile(w[:, 7] - t0, 90) / 100, (w[:, 7].max() - t0) / 100))
     if scan_row is not None:
         print("   the scan block (workgroup 0): start %.2f end %.2f" % ((scan_row[5] - t0) / 100, (scan_row[7] - t0) / 100))
+    if off == 0:
+        # word 6 of a sort workgroup: keys | {cu_id, sh_id, se_id} << 16 | XCD << 24 -- which workgroups share their CU with another
+        # workgroup that sorted a chunk, and how much later those end
+        place = w[:, 6].astype(np.int64) >> 16
+        w[:, 6] = w[:, 6].astype(np.int64) & 0xffff
+        cus, per_cu = np.unique(place, return_counts=True)
+        shares = per_cu[np.searchsorted(cus, place)] > 1
+        print("   placement: %d CUs hold a sorting workgroup, %d hold two or more" % (len(cus), int((per_cu > 1).sum())))
+        for lab, m in (("lone", ~shares), ("sharing", shares)):
+            if m.any():
+                print("   %-8s %4d workgroups, mean keys %5d | us from the first start: start median %.2f | lookup done median %.2f | network done median %.2f p90 %.2f last %.2f | network cycles mean %d" % (
+                    lab, int(m.sum()), int(w[m, 6].mean()), np.median(w[m, 5] - t0) / 100,
+                    np.median(w[m, 5] - t0 + (w[m, 7] - w[m, 5]) * (w[m, 1] - w[m, 0]) / (w[m, 4] - w[m, 0])) / 100,
+                    np.median(w[m, 7] - t0) / 100, np.percentile(w[m, 7] - t0, 90) / 100, (w[m, 7].max() - t0) / 100, int((w[m, 3] - w[m, 2]).mean())))
+        full = w[:, 6] >= 1024
+        for lab, m in (("lone, full chunk", ~shares & full), ("sharing, full chunk", shares & full)):
+            if m.any():
+                print("   %-20s %4d workgroups: end median %.2f last %.2f | network cycles mean %d max %d" % (
+                    lab, int(m.sum()), np.median(w[m, 7] - t0) / 100, (w[m, 7].max() - t0) / 100, int((w[m, 3] - w[m, 2]).mean()), int((w[m, 3] - w[m, 2]).max())))
     big = w[:, 6] >= (1024 if off == 0 else 3)
     if big.any():
         print("   full chunks / tiles of >= 3 chunks:", int(big.sum()), "mean phases", np.diff(w[big, :5], axis=1).mean(0).astype(int))
