@@ -371,7 +371,8 @@ def merge_rows(index, ids, mask, xyz, features_dc, features_rest, opacity, scali
 
 def densify_and_prune_fused(pc, optimizer, stats, joint_F, lbs_weights, max_grad, min_opacity, extent, max_screen_size, t_vertices,
                             kl_threshold=0.4, surface_mask=None, generator=None, percent_dense=0.01, one_pass=False):
-    """``GaussianModel.densify_and_prune`` (:621-666) on a ``GaussianSet`` + ``FlatAdamW`` + ``DensifyStats``, in MOSS's order:
+    """``GaussianModel.densify_and_prune`` (:621-666) on a ``GaussianSet`` + ``FlatAdamW`` (or an ``optim.FlatAdamWRows`` over several:
+    ``MossStep.rows``) + ``DensifyStats``, in MOSS's order:
     clone-append; split-append and its prune; merge-append and its prune; the final prune -- every selection and every new row from
     the fused ops, every append / prune through ``pc.densification_postfix`` / ``pc.prune_points``.
 

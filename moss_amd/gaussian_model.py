@@ -90,7 +90,7 @@ class GaussianSet(nn.Module):
         return perm
 
     # ---- the three moments MOSS rebuilds its tensors AND its optimizer state (scene/gaussian_model.py:314-317, :396-411, :436-454), on a
-    # FlatAdamW: the Parameter objects stay, their storage and the moments are re-laid-out by the optimizer.  WHICH Gaussians to clone /
+    # FlatAdamW (or an optim.FlatAdamWRows over several): the Parameter objects stay, their storage and the moments are re-laid-out by the optimizer.  WHICH Gaussians to clone /
     # split / merge / prune (:456-666) is decided elsewhere: moss_amd.densify.densify_and_prune_fused (MOSS's KL rule), or the caller.
     def _flat(self, optimizer):
         if not (hasattr(optimizer, "prune_rows") and hasattr(optimizer, "append_rows") and hasattr(optimizer, "reset_rows")):

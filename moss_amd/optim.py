@@ -388,8 +388,7 @@ class FlatAdamW:
         buffers, the fused step re-armed on the new moment addresses.  Everything that holds device addresses of the old buffers -- a
         captured hipGraph above all -- is stale afterwards: ``GraphedStep.recapture()``."""
         if self.shard is not None:
-            raise RuntimeError("row surgery on a SHARDED FlatAdamW: a parameter row's moments live on several ranks; use the all-reduce "
-                               "exchange while the set densifies (or gather, rebuild and re-shard)")
+            raise RuntimeError(_SHARDED_ROWS)
         fused = getattr(self, "_fused_args", None) if self.fused is not None else None
         cx = getattr(self, "_fused_context", None)
         for p, v in zip(self.bucket.params, values):
@@ -456,55 +455,18 @@ class FlatAdamW:
         with one host read (an entry out of range would otherwise give a row of zeros).  ``extra``: float32 tensors of ``rows_old``
         rows WITHOUT optimizer state (the densification statistics) gathered by the same launch -- only when nothing is appended;
         their gathered copies are returned as a list (else None).  CPU tensors take the torch restatement."""
-        if self.shard is not None:
-            raise RuntimeError("row surgery on a SHARDED FlatAdamW: a parameter row's moments live on several ranks; use the all-reduce "
-                               "exchange while the set densifies (or gather, rebuild and re-shard)")
-        from ._lib import ROWS_MAX_TENSORS, RowsRelayoutArgs
+        index = {id(p): i for i, p in enumerate(self.bucket.params)}
+        ext = {(key if isinstance(key, int) else index[id(key)]): t for key, t in (appended or {}).items()}
+        return _relayout_rows_of([self], row_map, [ext], check, rows_old, extra)
+
+    def _rows_describe(self, args, k, is_row, ext, rows_new):
+        """The first third of a GPU re-layout: the new layout from the new shapes (before anything is written), the three new flat
+        buffers (uninitialised), and this optimizer's descriptors -- absolute addresses -- in ``args.tensors[k:]``.  Returns (the next
+        free descriptor, the plan ``_rows_adopt`` takes).  Nothing of the optimizer has changed yet."""
         from .dist import flat_offsets
         bucket = self.bucket
         params = bucket.params
         dev = self.flat_params.device
-        index = {id(p): i for i, p in enumerate(params)}
-        ext = {}
-        for key, t in (appended or {}).items():
-            i = key if isinstance(key, int) else index[id(key)]
-            e = t.detach().to(device=dev, dtype=torch.float32).contiguous()
-            if tuple(e.shape[1:]) != tuple(params[i].shape[1:]):
-                raise ValueError(f"relayout_rows: rows of shape {tuple(e.shape)} do not extend a parameter of shape {tuple(params[i].shape)}")
-            ext[i] = e
-        rows_app = {int(e.shape[0]) for e in ext.values()}
-        olds = {int(params[i].shape[0]) for i in ext}
-        if len(rows_app) > 1 or len(olds) > 1:
-            raise ValueError("relayout_rows: the appended tensors must extend parameters of ONE row count by ONE number of rows")
-        rows_app = rows_app.pop() if rows_app else 0
-        if rows_old is None:
-            rows_old = olds.pop() if olds else next(int(p.shape[0]) for p in params if p.dim() >= 1)
-        rows_old = int(rows_old)
-        if rows_app == 0:
-            ext = {}
-        is_row = self._row_params(rows_old)
-        if rows_app and [i for i, r in enumerate(is_row) if r] != sorted(ext):
-            raise ValueError("relayout_rows: `appended` must name every parameter of rows_old rows (and no other)")
-        extra = list(extra or [])
-        if extra and rows_app:
-            raise ValueError("relayout_rows: `extra` tensors ride along only when nothing is appended")
-        for t in extra:
-            if t.dtype != torch.float32 or t.device != dev or t.dim() < 1 or int(t.shape[0]) != rows_old:
-                raise ValueError("relayout_rows: an `extra` tensor must be float32, on the optimizer's device, with rows_old rows")
-        row_map = row_map.to(dev)
-        if row_map.dim() != 1 or row_map.dtype not in (torch.int32, torch.int64):
-            raise ValueError("relayout_rows: row_map must be a 1-D int32 / int64 tensor")
-        rows_new = int(row_map.numel())
-        if check and rows_new and (int(row_map.min()) < 0 or int(row_map.max()) >= rows_old + rows_app):
-            raise ValueError(f"relayout_rows: row_map has entries outside [0, {rows_old + rows_app})")
-        if dev.type != "cuda":
-            return self._relayout_rows_torch(row_map, ext, is_row, extra)
-        if len(params) + len(extra) > ROWS_MAX_TENSORS:
-            raise ValueError(f"relayout_rows: more than {ROWS_MAX_TENSORS} tensors in one launch")
-        row_map = row_map.to(torch.int32).contiguous()
-        fused = getattr(self, "_fused_args", None) if self.fused is not None else None
-        cx = getattr(self, "_fused_context", None)
-        # the new layout, before anything is written
         shapes = [((rows_new,) + tuple(p.shape[1:])) if r else tuple(p.shape) for p, r in zip(params, is_row)]
         sizes = [int(torch.Size(s).numel()) for s in shapes]
         offsets, total = flat_offsets(sizes)
@@ -513,14 +475,11 @@ class FlatAdamW:
         if total == 0:
             for t in new:
                 t.zero_()
-        a = RowsRelayoutArgs()
-        a.rows_old, a.rows_app, a.rows_new, a.map = rows_old, rows_app, rows_new, row_map.data_ptr()
-        k = 0
         for i, (p, r, n, off) in enumerate(zip(params, is_row, sizes, offsets)):
             pad = (offsets[i + 1] if i + 1 < len(params) else total) - (off + n)
             if n + pad == 0:
                 continue                                     # (no row left and no gap behind: nothing to write)
-            d = a.tensors[k]
+            d = args.tensors[k]
             k += 1
             off_old = bucket.offsets[i]
             d.src, d.src_m, d.src_v = (t.data_ptr() + 4 * off_old for t in old)
@@ -528,22 +487,17 @@ class FlatAdamW:
             d.app = ext[i].data_ptr() if i in ext else None
             d.use_map, d.pad_after = int(r), pad
             d.width = max(int(torch.Size(p.shape[1:]).numel()), 1) if r else n
-        gathered = []
-        for t in extra:
-            t = t.contiguous()
-            g = torch.empty((rows_new,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev)
-            gathered.append((t, g))
-            if g.numel() == 0:
-                continue
-            d = a.tensors[k]
-            k += 1
-            d.src, d.dst, d.use_map, d.pad_after = t.data_ptr(), g.data_ptr(), 1, 0
-            d.width = int(torch.Size(t.shape[1:]).numel())
-        a.num_tensors = k
-        call("moss_rows_relayout", dev, C.addressof(a))
-        # adopt the buffers the kernel has filled: no second copy
+        return k, (new, shapes, sizes, offsets, total)
+
+    def _rows_adopt(self, plan):
+        """The last third: adopt the buffers the kernel has filled (no second copy) -- parameters re-homed, the bucket re-laid out,
+        the segments re-adopted, the fused step re-armed on the new moment addresses."""
+        new, shapes, sizes, offsets, total = plan
+        bucket = self.bucket
+        fused = getattr(self, "_fused_args", None) if self.fused is not None else None
+        cx = getattr(self, "_fused_context", None)
         self.flat_params, self.exp_avg, self.exp_avg_sq = new
-        for p, n, off, shape in zip(params, sizes, offsets, shapes):
+        for p, n, off, shape in zip(bucket.params, sizes, offsets, shapes):
             p.data = self.flat_params[off:off + n].view(shape)
         bucket.relayout()
         if list(bucket.offsets) != list(offsets) or bucket.n_params != total:
@@ -553,7 +507,6 @@ class FlatAdamW:
             self._verify_sh_inactive()                       # (appended rows may carry non-zero coefficients above the active degree)
         if fused is not None:
             self.fuse_into_backward(cx, local_only=fused[1], **fused[0])
-        return [g for _, g in gathered] if extra else None
 
     def _relayout_rows_torch(self, row_map, ext, is_row, extra=()):
         """``relayout_rows`` restated with torch indexing (what it does on CPU tensors, and what the tests compare the kernel with):
@@ -646,6 +599,180 @@ class FlatAdamW:
                 raise ValueError("an extra gradient buffer must be a contiguous float32 tensor laid out like the bucket")
             a.grads_extra[i] = e[first:].data_ptr() if self.shard is None else e.data_ptr()
         call("moss_adamw_flat_ex", dev, C.addressof(a))
+
+
+_SHARDED_ROWS = ("row surgery on a SHARDED FlatAdamW: a parameter row's moments live on several ranks; use the all-reduce "
+                 "exchange while the set densifies (or gather, rebuild and re-shard)")
+
+
+def _relayout_rows_of(members, row_map, exts, check, rows_old, extra):
+    """``FlatAdamW.relayout_rows`` for one optimizer or several (``FlatAdamWRows``): ``exts[k]`` maps an index in member k's bucket to
+    the rows appended to that parameter.  Validate everything first, then describe (every member: new layout, new buffers,
+    descriptors), launch ONCE, adopt (every member)."""
+    from ._lib import ROWS_MAX_TENSORS, RowsRelayoutArgs
+    if any(o.shard is not None for o in members):
+        raise RuntimeError(_SHARDED_ROWS)
+    dev = members[0].flat_params.device
+    norm = []
+    for o, ext in zip(members, exts):
+        params, d = o.bucket.params, {}
+        for i, t in ext.items():
+            e = t.detach().to(device=dev, dtype=torch.float32).contiguous()
+            if tuple(e.shape[1:]) != tuple(params[i].shape[1:]):
+                raise ValueError(f"relayout_rows: rows of shape {tuple(e.shape)} do not extend a parameter of shape {tuple(params[i].shape)}")
+            d[i] = e
+        norm.append(d)
+    rows_app = {int(e.shape[0]) for d in norm for e in d.values()}
+    olds = {int(o.bucket.params[i].shape[0]) for o, d in zip(members, norm) for i in d}
+    if len(rows_app) > 1 or len(olds) > 1:
+        raise ValueError("relayout_rows: the appended tensors must extend parameters of ONE row count by ONE number of rows")
+    rows_app = rows_app.pop() if rows_app else 0
+    if rows_old is None:
+        rows_old = olds.pop() if olds else next(int(p.shape[0]) for o in members for p in o.bucket.params if p.dim() >= 1)
+    rows_old = int(rows_old)
+    if rows_app == 0:
+        norm = [{} for _ in members]
+    is_rows = [o._row_params(rows_old) for o in members]
+    if len(members) > 1:
+        _same_row_count(members, rows_old)
+    if rows_app and any([i for i, r in enumerate(is_row) if r] != sorted(d) for is_row, d in zip(is_rows, norm)):
+        raise ValueError("relayout_rows: `appended` must name every parameter of rows_old rows (and no other)"
+                         + (" of every member" if len(members) > 1 else ""))
+    extra = list(extra or [])
+    if extra and rows_app:
+        raise ValueError("relayout_rows: `extra` tensors ride along only when nothing is appended")
+    for t in extra:
+        if t.dtype != torch.float32 or t.device != dev or t.dim() < 1 or int(t.shape[0]) != rows_old:
+            raise ValueError("relayout_rows: an `extra` tensor must be float32, on the optimizer's device, with rows_old rows")
+    row_map = row_map.to(dev)
+    if row_map.dim() != 1 or row_map.dtype not in (torch.int32, torch.int64):
+        raise ValueError("relayout_rows: row_map must be a 1-D int32 / int64 tensor")
+    rows_new = int(row_map.numel())
+    if check and rows_new and (int(row_map.min()) < 0 or int(row_map.max()) >= rows_old + rows_app):
+        raise ValueError(f"relayout_rows: row_map has entries outside [0, {rows_old + rows_app})")
+    # (the limit of one launch; a group holds to it on CPU tensors too, so that what passes there passes on the GPU)
+    if (dev.type == "cuda" or len(members) > 1) and sum(len(o.bucket.params) for o in members) + len(extra) > ROWS_MAX_TENSORS:
+        raise ValueError(f"relayout_rows: more than {ROWS_MAX_TENSORS} tensors in one launch")
+    if dev.type != "cuda":
+        gathered = [o._relayout_rows_torch(row_map, d, is_row, extra if k == 0 else ())
+                    for k, (o, d, is_row) in enumerate(zip(members, norm, is_rows))]
+        return gathered[0]
+    row_map = row_map.to(torch.int32).contiguous()
+    a = RowsRelayoutArgs()
+    a.rows_old, a.rows_app, a.rows_new, a.map = rows_old, rows_app, rows_new, row_map.data_ptr()
+    k, plans = 0, []
+    for o, d, is_row in zip(members, norm, is_rows):
+        k, plan = o._rows_describe(a, k, is_row, d, rows_new)
+        plans.append(plan)
+    gathered = []
+    for t in extra:
+        t = t.contiguous()
+        g = torch.empty((rows_new,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev)
+        gathered.append((t, g))
+        if g.numel() == 0:
+            continue
+        d = a.tensors[k]
+        k += 1
+        d.src, d.dst, d.use_map, d.pad_after = t.data_ptr(), g.data_ptr(), 1, 0
+        d.width = int(torch.Size(t.shape[1:]).numel())
+    a.num_tensors = k
+    call("moss_rows_relayout", dev, C.addressof(a))
+    for o, plan in zip(members, plans):
+        o._rows_adopt(plan)
+    return [g for _, g in gathered] if extra else None
+
+
+def _same_row_count(members, rows):
+    for k, o in enumerate(members):
+        if not any(o._row_params(rows)):
+            lead = sorted({int(p.shape[0]) for p in o.bucket.params if p.dim() >= 1})
+            raise ValueError(f"FlatAdamWRows: member {k} holds no parameter of {rows} rows (leading dimensions of its parameters: {lead}): "
+                             "the members' row-parameters have different row counts")
+
+
+class FlatAdamWRows:
+    """Several ``FlatAdamW`` whose row-parameters have ONE row count, presented as one optimizer for row surgery:
+    ``rows = FlatAdamWRows([opt_a, opt_b])``.  ``GaussianSet.densification_postfix / prune_points / relayout_points / reset_opacity /
+    reorder_spatially``, ``densify.densify_and_prune_fused`` and ``surgery.densification_event`` take it where they take a
+    ``FlatAdamW`` (``MossStep`` keeps the Gaussians in two: features / opacity / scaling / rotation, updated inside the rasterizer's
+    backward kernel, and the position).  It steps nothing and owns nothing: every member keeps its step counter, its learning-rate
+    state block and its parameters that are not per-row, bit for bit.
+
+    ``bucket.params`` lists all members' parameters in member order; a parameter is named by the object or by its index in that list.
+    ``relayout_rows`` on GPU tensors is ONE ``moss_rows_relayout`` launch for all members (absolute addresses in the descriptors, at
+    most ``MOSS_ROWS_MAX_TENSORS`` of them, the ``extra`` tensors included); the other calls go to each member in turn.
+
+    Refused: a sharded member, a parameter that two members hold, members whose row-parameters differ in row count (the row count is
+    that of the first member's first parameter)."""
+
+    def __init__(self, members):
+        from types import SimpleNamespace
+        self.members = list(members)
+        if not self.members:
+            raise ValueError("FlatAdamWRows: no member")
+        if any(o.shard is not None for o in self.members):
+            raise RuntimeError(_SHARDED_ROWS)
+        params, self._where = [], {}
+        for k, o in enumerate(self.members):
+            for i, p in enumerate(o.bucket.params):
+                if id(p) in self._where:
+                    raise ValueError(f"FlatAdamWRows: members {self._where[id(p)][0]} and {k} both hold one parameter (of shape "
+                                     f"{tuple(p.shape)}): its moments would be moved twice")
+                self._where[id(p)] = (k, i)
+                params.append(p)
+        self.bucket = SimpleNamespace(params=params)         # (the Parameter objects survive every surgery: the list stays true)
+        self.relayouts = 0                                   # relayout_rows calls carried out so far (on GPU tensors: launches)
+        _same_row_count(self.members, self.rows)
+
+    @property
+    def rows(self) -> int:
+        """The row count that marks a row-parameter now."""
+        return next(int(p.shape[0]) for p in self.bucket.params if p.dim() >= 1)
+
+    def _split(self, named):
+        """``{parameter or index in bucket.params: value}`` -> one ``{index in the member's bucket: value}`` per member."""
+        per = [{} for _ in self.members]
+        for key, val in (named or {}).items():
+            k, i = self._where[id(self.bucket.params[key] if isinstance(key, int) else key)]
+            per[k][i] = val
+        return per
+
+    def append_rows(self, new_rows):
+        per = self._split(new_rows)
+        named = {int(o.bucket.params[i].shape[0]) for o, d in zip(self.members, per) for i in d}
+        for k, (o, d) in enumerate(zip(self.members, per)):
+            if any(r and i not in d for n in named for i, r in enumerate(o._row_params(n))):
+                raise ValueError(f"FlatAdamWRows.append_rows: `new_rows` must name every row-parameter of every member (member {k} has "
+                                 "one that is not named): the members would end with different row counts")
+        for o, d in zip(self.members, per):
+            if d:
+                o.append_rows(d)
+
+    def prune_rows(self, keep_mask):
+        _same_row_count(self.members, int(keep_mask.numel()))
+        for o in self.members:
+            o.prune_rows(keep_mask)
+
+    def permute_rows(self, perm):
+        _same_row_count(self.members, int(perm.numel()))
+        for o in self.members:
+            o.permute_rows(perm)
+
+    def reset_rows(self, param, values):
+        k, i = self._where[id(self.bucket.params[param] if isinstance(param, int) else param)]
+        self.members[k].reset_rows(i, values)
+
+    def set_active_sh_degree(self, degree: int):
+        """To every member (one without an SH parameter answers 3); returns the lowest degree in force."""
+        return min(o.set_active_sh_degree(degree) for o in self.members)
+
+    @torch.no_grad()
+    def relayout_rows(self, row_map, appended=None, check=True, rows_old=None, extra=None):
+        """``FlatAdamW.relayout_rows`` over all members: one launch on GPU tensors, the members' torch restatement on CPU tensors.
+        ``appended`` must name every row-parameter of every member."""
+        out = _relayout_rows_of(self.members, row_map, self._split(appended), check, rows_old, extra)
+        self.relayouts += 1
+        return out
 
 
 class AdamW(torch.optim.Optimizer):

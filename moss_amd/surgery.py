@@ -112,8 +112,20 @@ def densification_event(pc, optimizer, *, append=None, prune=None, reset_opacity
     ``pc.spatially_ordered`` stays set, and statistics and ``per_gaussian`` tables follow the same order.
 
     Returns a report: rows before / after, what was re-captured, and the host-side cost of the event in milliseconds (it
-    synchronises the device: the event is outside the step's asynchronous flow by nature)."""
+    synchronises the device: the event is outside the step's asynchronous flow by nature).
+
+    ``optimizer``: a ``FlatAdamW``, or an ``optim.FlatAdamWRows`` over several (``MossStep.rows``).  A shape change with ``context`` and
+    ``graphed`` but no ``probe`` raises ``ValueError`` before anything is touched."""
     dev = pc._xyz.device
+    if context is not None and graphed is not None and probe is None:
+        # re-learning the capacity makes the next forward of the context the synchronous one, and without a probe that forward would
+        # be the one inside the re-capture: refused before anything is touched
+        will_move = bool(rows_changed) or (prune is not None and bool(prune.any())) or any(
+            int(a["new_xyz"].shape[0]) > 0 for a in ([] if append is None else [append] if isinstance(append, dict) else append))
+        if will_move:
+            raise ValueError("densification_event: a shape change with `context` and `graphed` needs `probe` (a forward-only render of the "
+                             "new set under torch.no_grad()): the binning capacity is re-learned by the next forward, which must not be "
+                             "the one the re-capture records")
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
     t0 = time.perf_counter()

@@ -8,8 +8,12 @@
     three optimizers    (A) features / opacity / scaling / rotation inside the rasterizer's backward kernel, (B) the position,
                         (C) MOSS's two networks -- 52 + 16 tensors, two learning-rate segments, one launch (moss_amd/optim.py)
     statistics          what ``densify_and_prune_fused`` reads (moss_amd/densify.py)
+    events              between steps: ``densify_and_prune`` / ``densification_event`` / ``oneup_sh_degree`` carry MOSS's densification
+                        (``train_ZJU.py:176-186``) and its SH-degree raise (``:85-86``) out on both Gaussian optimizers at once
+                        (``optim.FlatAdamWRows``, moss_amd/surgery.py) and capture the step again
+    run_schedule        MOSS's loop order around the step (``train_ZJU.py:82-95,171-186``)
 
-Nothing in the step reads the host.  Everything here imports without a GPU.
+Nothing in the step reads the host (the events do: they sit between steps).  Everything here imports without a GPU.
 """
 from __future__ import annotations
 
@@ -17,7 +21,7 @@ from types import SimpleNamespace
 
 import torch
 
-__all__ = ["MossStep", "TERM_NAMES", "LOSS_WEIGHTS", "RENDER_FLAGS"]
+__all__ = ["MossStep", "run_schedule", "frame_order", "TERM_NAMES", "LOSS_WEIGHTS", "RENDER_FLAGS"]
 
 # ``terms``, in this order.  ``ssim`` is the SSIM value itself (the loss takes 1 - ssim); ``total`` is train_ZJU.py:131
 TERM_NAMES = ("l1", "ssim", "mask_l2", "lpips", "nll", "s3im", "total")
@@ -71,8 +75,21 @@ class MossStep:
 
     ``stats`` (a ``densify.DensifyStats``): the step also keeps what ``densify_and_prune_fused`` reads -- ``stats.add(radii,
     viewspace.grad)``, ``joint_F_sum += Rs`` and ``lbs_weights_sum += lbs_weights`` (``train_ZJU.py:102-105,127,171-174``; a dropped
-    frame adds to none of them).  The densification EVENT is not part of this class: the Gaussians sit in two optimizers here, and
-    ``surgery.densification_event`` takes one.
+    frame adds to none of them).
+
+    Between steps -- ``rows`` is ``optim.FlatAdamWRows([opt_gaussians, opt_xyz])``, the two Gaussian optimizers as one for row surgery:
+
+    * :meth:`densify_and_prune`: ``train_ZJU.py:176-183`` in one call -- MOSS's decision on the step's own statistics, the rows moved
+      in both optimizers by one gather launch per phase, the sums reset, the binning capacity re-learned, the step captured again;
+    * :meth:`densification_event`: the same tail for a decision the caller made; ``reset_opacity`` alone is applied in place and the
+      captured graph stays;
+    * :meth:`oneup_sh_degree`: ``oneupSHdegree`` -- the model, optimizer (A) and the capture learn the new degree together, so the
+      new coefficients cannot stay frozen behind a stale degree.
+
+    A re-capture runs no training step; ``check()`` and ``dropped_frames`` carry on across events.  ORDER: MOSS densifies between
+    ``backward()`` and ``optimizer.step()`` (``train_ZJU.py:176-189``), and the tensors it rebuilds there have lost their ``.grad``,
+    so that iteration's update skips the Gaussians.  Here an event runs between two steps: the iteration's update HAS been taken
+    when the decision reads the parameters (as INTEGRATION states for the step fused into the backward).
 
     ``terms`` (7 floats on the device, :data:`TERM_NAMES`): the six loss terms and the total of the last step."""
 
@@ -129,6 +146,8 @@ class MossStep:
                                        {"params": net, "lr": float(lrs["cross_attention_lbs"]), "name": "cross_attention_lbs"}],
                                       self.bucket_networks, **kw)
         self.optimizers = (self.opt_gaussians, self.opt_xyz, self.opt_networks)
+        from .optim import FlatAdamWRows
+        self.rows = FlatAdamWRows([self.opt_gaussians, self.opt_xyz])     # (A) and (B) as one optimizer for row surgery
         self.pipe = SimpleNamespace(convert_SHs_python=False, compute_cov3D_python=False, debug=False, raster_context=cx,
                                     net_grad_sink=self.bucket_networks.sink_for, **dict.fromkeys(RENDER_FLAGS, True))
         # [photometric loss | l1, ssim, mask_l2 | lpips, nll, s3im, total]: the photometric kernels write the first four themselves
@@ -212,6 +231,105 @@ class MossStep:
         self._restore(state)
         return self
 
+    # ---- between steps: densification and the SH degree -----------------------------------------------------------------------------
+    def _probe(self):
+        """Forward only, no side effect: the loaded frame rendered with the step's flags; after ``relearn_capacity()`` it is the
+        synchronous forward that sizes the binning capacity for the new set."""
+        from .gaussian_renderer import render
+        with torch.no_grad():
+            render(self.view, self.pc, self.pipe, self.bg)
+
+    def _recapture(self):
+        self._captured_crop = (int(self.region.xywh[3]), int(self.region.xywh[2]))
+        self.graphed.recapture()                             # (no warm-up run: no training step is taken, the model stays where it is)
+
+    def _reset_sums(self):
+        """``joint_F = zeros``, ``lbs_weights = None`` (``train_ZJU.py:180-181``) -- the second as zeros at the CURRENT number of
+        Gaussians: its address is baked into the capture, so it has to exist before the capture."""
+        self.joint_F_sum.zero_()
+        w, P = self.lbs_weights_sum, int(self.pc._xyz.shape[0])
+        if w is not None:
+            if int(w.shape[-2]) == P:
+                w.zero_()
+            else:
+                self.lbs_weights_sum = torch.zeros(tuple(w.shape[:-2]) + (P, int(w.shape[-1])), dtype=w.dtype, device=w.device)
+
+    def _event(self, t0, reads0, relayouts0, decision=None, **event):
+        """The tail every event shares (``surgery.densification_event`` on ``rows``: capacity, probe, re-capture) and the report."""
+        import time
+        from . import densify
+        from .surgery import densification_event
+        moves = decision is not None or event.get("append") is not None or event.get("prune") is not None
+        tail = densification_event(self.pc, self.rows, stats=self.stats, context=self.context, graphed=self.graphed, probe=self._probe,
+                                   after_surgery=(lambda _: self._reset_sums()) if moves else None, **event)
+        tail.pop("per_gaussian", None)
+        if tail["recaptured"]:
+            self._captured_crop = (int(self.region.xywh[3]), int(self.region.xywh[2]))
+        report = dict(tail, **(decision or {}))
+        report["relayouts"] = self.rows.relayouts - relayouts0
+        report["host_reads"] = densify.host_reads() - reads0
+        # (the decision and the row moves it made are the event's surgery; the clock started before them)
+        report["event_ms"] = round(1e3 * (time.perf_counter() - t0), 3)
+        report["surgery_ms"] = round(report["event_ms"] - tail["probe_ms"] - tail["capture_ms"], 3)
+        return report
+
+    def _begin_event(self):
+        import time
+        from . import densify
+        if self.graphed is not None:
+            self.check()                                     # (the frames dropped since the last check are counted before the capture goes)
+        elif self.pc._xyz.is_cuda:
+            torch.cuda.synchronize(self.pc._xyz.device)
+        return time.perf_counter(), densify.host_reads(), self.rows.relayouts
+
+    def densify_and_prune(self, max_grad, min_opacity, extent, max_screen_size, kl_threshold=0.4, surface_mask=None, generator=None,
+                          one_pass=True):
+        """``gaussians.densify_and_prune(...)`` and the two resets behind it (``train_ZJU.py:176-183``).  The decision is
+        ``densify.densify_and_prune_fused`` on ``rows`` with the step's own ``stats``, ``joint_F_sum``, ``lbs_weights_sum`` and
+        ``view.big_pose_world_vertex`` (``surface_mask``, ``generator``, ``one_pass``: as there).  Then ``joint_F_sum`` is zeroed,
+        ``lbs_weights_sum`` becomes zeros at the new size, the binning capacity is re-learned on the loaded frame and a captured step
+        is captured again (``warmup=0``: no training step).  Returns the merged reports: ``cloned / split / merged / pruned``,
+        ``rows_before / rows_after``, ``relayouts``, ``host_reads``, ``event_ms`` = ``surgery_ms`` (decision and row moves) +
+        ``probe_ms`` + ``capture_ms``, ``recaptured``."""
+        from .densify import densify_and_prune_fused
+        if self.stats is None:
+            raise RuntimeError("MossStep.densify_and_prune: the step was built without stats= (a densify.DensifyStats): there is nothing "
+                               "to decide on")
+        if self.lbs_weights_sum is None:
+            raise RuntimeError("MossStep.densify_and_prune: no step has been taken yet (the statistics are empty)")
+        t0, reads0, relayouts0 = self._begin_event()
+        decision = densify_and_prune_fused(self.pc, self.rows, self.stats, self.joint_F_sum, self.lbs_weights_sum, max_grad, min_opacity,
+                                           extent, max_screen_size, self.view.big_pose_world_vertex, kl_threshold=kl_threshold,
+                                           surface_mask=surface_mask, generator=generator, one_pass=one_pass)
+        moved = any(decision[k] for k in ("cloned", "split", "merged", "pruned"))
+        return self._event(t0, reads0, relayouts0, decision=decision, rows_changed=moved)
+
+    def densification_event(self, append=None, prune=None, reset_opacity=False, one_pass=True, keep_spatial_order=False):
+        """The tail of :meth:`densify_and_prune` for a decision the caller made (``surgery.densification_event``: ``append``, a dict of
+        the six ``densification_postfix`` tensors or a list of such; ``prune``, a mask over the set AFTER the appends, True = remove;
+        ``reset_opacity`` last).  ``one_pass=True``: all of it is one gather launch over both optimizers.  With ``append`` or ``prune``
+        the two sums are reset as after MOSS's own event.  ``reset_opacity`` alone changes no address: it is applied in place and a
+        captured graph stays valid -- no re-capture.  Returns the report (``relayouts``, ``host_reads``, ``event_ms`` and its parts,
+        ``recaptured``)."""
+        t0, reads0, relayouts0 = self._begin_event()
+        return self._event(t0, reads0, relayouts0, append=append, prune=prune, reset_opacity=reset_opacity, one_pass=one_pass,
+                           keep_spatial_order=keep_spatial_order)
+
+    def oneup_sh_degree(self) -> int:
+        """``gaussians.oneupSHdegree()`` (``train_ZJU.py:85-86``): ``pc.active_sh_degree`` goes up by one (at most 3), optimizer (A)
+        is told (``set_active_sh_degree``: the degree-aware update would otherwise never read the new coefficients' gradients), and a
+        captured step is captured again -- the degree is a launch argument of the rasterizer and of the update.  Returns the degree."""
+        pc = self.pc
+        if pc.active_sh_degree >= pc.max_sh_degree:
+            return int(pc.active_sh_degree)
+        if self.graphed is not None:
+            self.check()
+        pc.active_sh_degree += 1
+        self.rows.set_active_sh_degree(pc.active_sh_degree)
+        if self.graphed is not None:
+            self._recapture()
+        return int(pc.active_sh_degree)
+
     def __call__(self):
         if self.graphed is None:
             raise RuntimeError("MossStep: capture() first (or call compute() for the eager step)")
@@ -239,6 +357,10 @@ class MossStep:
     def dropped_frames(self) -> int:
         return 0 if self.graphed is None else self.graphed.dropped_frames
 
+    @property
+    def recaptures(self) -> int:
+        return 0 if self.graphed is None else self.graphed.recaptures
+
     def step_counts(self):
         """The three device-side step counters (A, B, C); synchronises."""
         return tuple(o.step_count() for o in self.optimizers)
@@ -264,3 +386,94 @@ class MossStep:
         for o, d in zip(self.optimizers, per):
             if d:
                 o.set_learning_rates(d)
+
+
+# ---- MOSS's loop around the step ----------------------------------------------------------------------------------------------------
+def frame_order(frames: int, iterations: int, seed: int = 0):
+    """The frame of every iteration, drawn as ``train_ZJU.py:91-93`` draws its camera: without replacement from a stack that is
+    refilled when it is empty.  ``frames``: how many there are; returns ``iterations`` indices."""
+    import random
+    rng, stack, order = random.Random(seed), [], []
+    for _ in range(int(iterations)):
+        if not stack:
+            stack = list(range(int(frames)))
+        order.append(stack.pop(rng.randint(0, len(stack) - 1)))
+    return order
+
+
+def run_schedule(step, frames, iterations, densify_from=400, densify_until=2000, interval=100, sh_every=1000, opacity_reset_interval=4000,
+                 check_every=100, lr_schedule=None, on_event=None, load_frame=None, densify=None, seed=0):
+    """MOSS's training loop (``train_ZJU.py:82-95,171-186``) around a :class:`MossStep`; no mathematics of its own.  Per iteration
+    ``i = 1 .. iterations``, in MOSS's order:
+
+    1. ``step.set_learning_rates(lr_schedule(i))`` if there is a schedule (``update_learning_rate``, ``:82``);
+    2. ``step.oneup_sh_degree()`` when ``i % sh_every == 0`` (``:85-86``);
+    3. ``load_frame(k)``: the caller's ``copy_`` of frame ``k`` into the step's static inputs and ``region.copy_``; ``k`` follows
+       :func:`frame_order` over ``frames`` (a count, or a sequence whose elements are handed to ``load_frame``);
+    4. the step: a replay if ``step`` is captured, else ``step.compute()`` -- the same schedule run eagerly;
+    5. while ``i < densify_until``: the densification event when ``i > densify_from and i % interval == 0`` (``:176-183``) --
+       ``on_event(step, i)``, which carries the event out and returns its report, or by default ``step.densify_and_prune(**densify,
+       max_screen_size=20 if i > opacity_reset_interval else None)`` (``densify``: ``max_grad``, ``min_opacity``, ``extent`` and
+       whatever else that call takes) -- and ``step.densification_event(reset_opacity=True)`` when ``i % opacity_reset_interval == 0``
+       (``:184-185``).
+
+    A captured step is ``check()``-ed every ``check_every`` iterations.  The device is synchronised where a phase ends (and by every
+    event), nowhere else.  Returns ``seconds``; ``phases`` (``before`` / ``during`` / ``after`` densification: ``iterations``,
+    ``seconds``, ``it_per_s``; the events' time is in ``during``); ``events`` (each report with its ``iteration``); ``sh_raises``;
+    ``opacity_resets``; ``dropped_frames``; ``recaptures``; ``rows``, the final number of Gaussians."""
+    import time
+    ids = list(range(frames)) if isinstance(frames, int) else list(frames)
+    if load_frame is None and len(ids) > 1:
+        raise ValueError("run_schedule: several frames need load_frame (the copies into the step's static inputs)")
+    due = [i for i in range(1, int(iterations) + 1) if densify_from < i < densify_until and i % interval == 0]
+    if due and on_event is None and densify is None:
+        raise ValueError("run_schedule: densification events are due; give densify= (the arguments of step.densify_and_prune: max_grad, "
+                         "min_opacity, extent) or on_event=")
+    order = frame_order(len(ids), iterations, seed)
+    captured = step.graphed is not None
+    dev = step.pc._xyz.device
+    phases = {name: {"iterations": 0, "seconds": 0.0} for name in ("before", "during", "after")}
+    events, sh_raises, resets = [], 0, 0
+
+    def sync():
+        if dev.type == "cuda":
+            torch.cuda.synchronize(dev)
+        return time.perf_counter()
+    start = mark = sync()
+    phase = "before"
+    for i in range(1, int(iterations) + 1):
+        now = "before" if i <= densify_from else "during" if i < densify_until else "after"
+        if now != phase:
+            t = sync()
+            phases[phase]["seconds"] += t - mark
+            phase, mark = now, t
+        if lr_schedule is not None:
+            step.set_learning_rates(lr_schedule(i))
+        if i % sh_every == 0:
+            before = int(step.pc.active_sh_degree)
+            sh_raises += int(step.oneup_sh_degree() != before)
+        if load_frame is not None:
+            load_frame(ids[order[i - 1]])
+        step() if captured else step.compute()
+        phases[phase]["iterations"] += 1
+        if i < densify_until:
+            if i > densify_from and i % interval == 0:
+                if on_event is not None:
+                    report = on_event(step, i)
+                else:
+                    report = step.densify_and_prune(**dict(densify, max_screen_size=20 if i > opacity_reset_interval else None))
+                events.append(dict(report or {}, iteration=i))
+            if i % opacity_reset_interval == 0:
+                step.densification_event(reset_opacity=True)
+                resets += 1
+        if captured and i % check_every == 0:
+            step.check()
+    end = sync()
+    phases[phase]["seconds"] += end - mark
+    if captured:
+        step.check()
+    for p in phases.values():
+        p["it_per_s"] = round(p["iterations"] / p["seconds"], 2) if p["iterations"] and p["seconds"] > 0 else None
+        p["seconds"] = round(p["seconds"], 4)
+    return {"seconds": round(end - start, 4), "iterations": int(iterations), "phases": phases, "events": events, "sh_raises": sh_raises,
+            "opacity_resets": resets, "dropped_frames": step.dropped_frames, "recaptures": step.recaptures, "rows": int(step.pc._xyz.shape[0])}
