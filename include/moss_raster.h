@@ -726,7 +726,7 @@ typedef struct moss_lpips_vgg_args {
     int32_t H, W;                            /* the crop */
     int32_t frame_H, frame_W;                /* 0, 0 = H, W */
     const int* rect;                         /* device ints {x, y, ...} or NULL */
-    const float* weights[MOSS_LPIPS_VGG_CONVS];
+    const float* weights[MOSS_LPIPS_VGG_CONVS]; /* moss_lpips_vgg_forward_bf16: [1..12] are the uint16_t `fwd` arrays of ..._pack_weights_bf16 */
     const float* biases[MOSS_LPIPS_VGG_CONVS];
     const float* lin[MOSS_LPIPS_VGG_TAPS];
     const float* shift;
@@ -744,7 +744,7 @@ typedef struct moss_lpips_vgg_backward_args {
     int32_t H, W;
     int32_t frame_H, frame_W;
     const int* rect;
-    const float* weights_bwd[MOSS_LPIPS_VGG_CONVS];
+    const float* weights_bwd[MOSS_LPIPS_VGG_CONVS]; /* moss_lpips_vgg_backward_bf16: [1..12] are the uint16_t `bwd` arrays of ..._pack_weights_bf16 */
     const float* scale;
     const char* saved;                       /* as the forward wrote it */
     const float* g_out;                      /* 1 device float */
@@ -758,6 +758,27 @@ size_t moss_lpips_vgg_workspace_bytes(int H, int W);  /* scratch of either call;
 size_t moss_lpips_vgg_saved_bytes(int H, int W);      /* what the forward keeps for the backward; 0 for a size outside the range */
 /* w (cout,cin,3,3) fp32 -> fwd [cout][tap][cin] and bwd [cin][8 - tap][cout] (cout * cin * 9 floats each): once, the weights are frozen */
 int moss_lpips_vgg_pack_weights(int cin, int cout, const float* w, float* fwd, float* bwd, void* stream);
+
+/*
+ * The same term with bf16 OPERANDS in the twelve wide convolutions (additive in ABI 7): a mixed-precision form of the TRAINING term.
+ * The float32 calls above stay the default, keep their results bit for bit, and are the only form an evaluation metric may use.
+ * The arithmetic, exactly: in convolutions 2..13 (conv 1_2 .. 5_3), forward and data gradient alike, both operands of every product
+ * are rounded to bf16 with round-to-nearest-even -- the weights once, by moss_lpips_vgg_pack_weights_bf16; the activations (forward)
+ * and the incoming gradients (backward) each time a slice of them is staged for the matrix cores, while in memory they stay float32.
+ * A product of two bf16 values is exact in float32, and every sum is accumulated in float32 (v_mfma_f32_32x32x16_bf16), in a fixed
+ * order.  Nothing else is rounded: conv 1_1 and its adjoint, the bias, ReLU, the pools, the taps and the means are the float32 call's.
+ * It is lpips_vgg_torch(..., operand_dtype=torch.bfloat16) of moss_amd/lpips.py up to float32 summation order.
+ *
+ * Both calls take the argument blocks of the float32 pair, REINTERPRETED in one place: weights[1..12] / weights_bwd[1..12] point at the
+ * uint16_t arrays of moss_lpips_vgg_pack_weights_bf16 (`fwd` / `bwd`: the two layouts of the float32 packer, cout * cin * 9 16-bit
+ * values each); weights[0] / weights_bwd[0] (conv 1_1) are the float32 packing.  Everything else -- sizes, rect, the capacity and its
+ * bit-identity rule (the shapes are picked the same way), `saved`, `workspace` and their sizes, capturability, bitwise
+ * reproducibility, every element of dL_dx written, the refusals and the texts of moss_last_error() -- is the float32 pair's; a `saved`
+ * block goes to the backward of the precision that wrote it.
+ */
+int moss_lpips_vgg_forward_bf16(const moss_lpips_vgg_args* args, void* stream);
+int moss_lpips_vgg_backward_bf16(const moss_lpips_vgg_backward_args* args, void* stream);
+int moss_lpips_vgg_pack_weights_bf16(int cin, int cout, const float* w, uint16_t* fwd, uint16_t* bwd, void* stream);
 
 /*
  * k nearest reference points of every query point, 3-D, exact, k = 1..4: replaces the third-party

@@ -19,6 +19,8 @@
 //     way from L2 into registers; a wave owns a 32 x 64 block (two accumulators share every A read).  Two shapes: 128 rows x 64
 //     channels per workgroup (a wave per 32 rows), and, for the deep layers whose few rows would leave most CUs idle, 32 rows x 64
 //     channels with the four waves splitting every K slice, their partial blocks summed in wave order through LDS.
+//   conv3x3_bf16_kernel -- the same convolution with both operands rounded to bf16 and float32 sums (v_mfma_f32_32x32x16_bf16), behind
+//     moss_lpips_vgg_forward_bf16 / _backward_bf16: an opt-in form of the TRAINING term.  Same shapes, modes and epilogue; see there.
 //   conv_first_kernel / conv_first_backward_kernel -- conv 1_1 (Cin = 3, K = 27) and its adjoint on the VALU, with the z-score, the
 //     crop offset read from the device and the planar (3,H,W) layout of the public tensors.
 //   pool_kernel, tap_kernel, unpool_tap_kernel, reduce_kernel -- see each.
@@ -32,6 +34,7 @@
 // capacity's M, so the result equals the static call's bit for bit when every layer gets the same shape in both, and to float32
 // summation order otherwise (include/moss_raster.h).
 #include "common.h"
+#include "mfma_bf16.h"
 #include "mfma_f32.h"
 #include "wave.h"
 
@@ -79,13 +82,15 @@ __device__ __forceinline__ int2 crop_origin(const int* __restrict__ rect, int H,
 
 // ---- the weights, once ---------------------------------------------------------------------------------------------------------------
 // w (Cout,Cin,3,3) -> fwd [Cout][tap][Cin] and bwd [Cin][flipped tap][Cout]: d in[q][ci] = sum d out[q + (ky' - 1, kx' - 1)][co] bwd[ci][ky' kx'][co]
+// T float, or __bf16: rounded to nearest even, once
+template <typename T>
 __global__ void __launch_bounds__(WG)
-pack_weights_kernel(int cin, int cout, const float* __restrict__ w, float* __restrict__ fwd, float* __restrict__ bwd)
+pack_weights_kernel(int cin, int cout, const float* __restrict__ w, T* __restrict__ fwd, T* __restrict__ bwd)
 {
     const int idx = blockIdx.x * WG + threadIdx.x;
     if (idx >= cout * cin * 9) return;
     const int tap = idx % 9, i = (idx / 9) % cin, o = idx / (9 * cin);
-    const float v = w[idx];
+    const T v = (T)w[idx];
     fwd[((size_t)o * 9 + tap) * cin + i] = v;
     bwd[((size_t)i * 9 + (8 - tap)) * cout + o] = v;
 }
@@ -328,6 +333,152 @@ conv3x3_mfma_kernel(const ConvArgs a)
     }
 }
 
+// ---- the wide convolutions, bf16 operands ------------------------------------------------------------------------------------------
+// What follows the K loop: conv3x3_mfma_kernel's epilogue, statement for statement (the C/D layout of the 32 x 32 tile does not depend
+// on the operand type) -- bias and ReLU with the sign bits by one ballot per accumulator register, or the ReLU bits of the layer
+// below, or nothing; with WK == 4 the four waves' partial blocks go through `s_part` (4096 floats of LDS every wave is done reading)
+// and are summed in wave order.  A copy, because the f32 kernel is left untouched: calling this from it moved its register
+// allocation (62 -> 64 / 66 SGPRs in <4,1,FWD>), and its instantiations are to stay the code they were.
+template <int WK, int MODE>
+__device__ __forceinline__ void conv_epilogue(const f32x16& acc0, const f32x16& acc1, float* s_part, int tid, int wave, int j, int half,
+                                              int m0, int n0, int M, int mask_rows, int Cout, const float* __restrict__ bias,
+                                              float* __restrict__ out, const uint32_t* __restrict__ mask_in,
+                                              uint32_t* __restrict__ mask_out)
+{
+    // one output element per lane and call; every lane of the wave calls it (the ballot): row m, channel n = 32-aligned base + j
+    auto emit = [&](float v, int m, int n) __attribute__((always_inline)) {
+        const bool valid = m < M;
+        if (MODE == MODE_FWD) {
+            v += bias[n];
+            const bool pos = v > 0.0f;
+            if (valid) out[(size_t)m * Cout + n] = pos ? v : 0.0f;
+            if (mask_out) {
+                const unsigned long long b = __ballot(pos);
+                if (j == 0 && m < mask_rows) mask_out[(size_t)m * (Cout >> 5) + (n >> 5)] = (uint32_t)(half ? b >> 32 : b);
+            }
+        } else if (MODE == MODE_BWD_MASK) {
+            if (valid) {
+                const uint32_t word = mask_in[(size_t)m * (Cout >> 5) + (n >> 5)];
+                out[(size_t)m * Cout + n] = (word >> j) & 1u ? v : 0.0f;
+            }
+        } else {
+            if (valid) out[(size_t)m * Cout + n] = v;
+        }
+    };
+    if (WK == 1) {
+#pragma unroll
+        for (int r = 0; r < 16; r++) emit(acc0[r], m0 + 32 * wave + acc_row(r, half), n0 + j);
+#pragma unroll
+        for (int r = 0; r < 16; r++) emit(acc1[r], m0 + 32 * wave + acc_row(r, half), n0 + 32 + j);
+    } else {
+        // the four partial 32 x 32 blocks through LDS (s_part: every wave is past its last read), summed in wave order
+#pragma unroll
+        for (int b = 0; b < 2; b++) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) s_part[wave * 1024 + acc_row(r, half) * 32 + j] = b ? acc1[r] : acc0[r];
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const int row = (tid >> 5) + 8 * i;                      // (tid >> 5) & 1 == half, tid & 31 == j
+                const float* q = s_part + row * 32 + j;
+                emit(((q[0] + q[1024]) + q[2048]) + q[3072], m0 + row, n0 + 32 * b + j);
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// The same implicit GEMM with both operands rounded to bf16 (nearest even) and the sums in float32, on v_mfma_f32_32x32x16_bf16: sixteen
+// k per instruction at sixteen times the f32 tile's rate, so the kernel is bound by staging and is shaped for that.  The activations
+// stay float32 in memory and are rounded on their way into LDS; a.w is the bf16 packing (pack_weights_kernel<__bf16>: rounded once).
+// A slice is KCB channels of one tap: 128 where Cin allows (a row of 272 bytes with its padding, the f32 kernel's), 64 for the Cin =
+// 64 layers and the 128-row shape (144 bytes); both strides are an odd number of 16-byte slots, so the 16-byte fragment reads of
+// consecutive rows fall on different bank groups.  LDS holds TWO slices: the next one is written while this one is read, which
+// leaves one barrier per slice where the f32 kernel has two.  Shapes, modes, DYN and the epilogue are the f32 kernel's.
+template <int WM, int WK, int KCB, int MODE, bool DYN>
+__global__ void __launch_bounds__(WG)
+conv3x3_bf16_kernel(const ConvArgs a)
+{
+    static_assert(WM * WK == 4 && (WK == 1 || WM == 1), "four waves");
+    static_assert(KCB == 64 || KCB == 128, "a slice is 64 or 128 channels");
+    constexpr int BM = 32 * WM, LDB = KCB + 8, SLICE = (BM + BN) * LDB;                 // LDS row stride and one slice, in bf16
+    constexpr int A_CPR = KCB / 4, A_RPP = WG / A_CPR, A_F4 = BM / A_RPP;               // A: float4 columns per row, rows per pass, passes
+    constexpr int B_CPR = KCB / 8, B_RPP = WG / B_CPR, B_V8 = BN / B_RPP;               // B: the same in 8-vectors of bf16
+    static_assert(KCB / 16 >= WK, "every wave has a k step in every slice");
+    __shared__ __attribute__((aligned(16))) __bf16 s_ab[2 * SLICE];
+    static_assert(2 * SLICE * sizeof(__bf16) >= 4 * 32 * 32 * sizeof(float), "s_ab doubles as the buffer of the four partial blocks");
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, half = lane >> 5;
+    const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
+    int H = a.H, W = a.W, M = a.M, mask_rows = a.mask_rows;
+    if (DYN) {
+        actual_size(a.dyn, H, W);
+        mask_rows = H * W;
+        M = a.nimg * mask_rows;
+        if (m0 >= M) return;                                             // (the whole workgroup, before its first barrier)
+    }
+    const int HW = H * W, Cin = a.Cin, Cout = a.Cout;
+    const int K9 = 9 * Cin, nchunks = K9 / KCB;
+    const float* __restrict__ in = a.in;
+
+    // what this thread stages: of A the rows ar + A_RPP i at float4 column ac, of B the rows br + B_RPP i at 8-vector column bc
+    const int ac = tid % A_CPR, ar = tid / A_CPR, bc = tid % B_CPR, br = tid / B_CPR;
+    int rpix[A_F4], ryx[A_F4];
+#pragma unroll
+    for (int i = 0; i < A_F4; i++) {
+        const int m = m0 + ar + A_RPP * i;
+        rpix[i] = -1; ryx[i] = 0;
+        if (m < M) {
+            const int p = m % HW, y = p / W;
+            rpix[i] = m; ryx[i] = (y << 16) | (p - y * W);
+        }
+    }
+    const __bf16* wbase = reinterpret_cast<const __bf16*>(a.w) + (size_t)(n0 + br) * K9 + 8 * bc;
+    f32x4 ra[A_F4];
+    bf16x8 rb[B_V8];
+    auto gload = [&](int kc) __attribute__((always_inline)) {
+        const int k0 = kc * KCB, tap = k0 / Cin, ci0 = k0 - tap * Cin, dy = tap / 3 - 1, dx = tap % 3 - 1;
+#pragma unroll
+        for (int i = 0; i < A_F4; i++) {
+            const int yy = (ryx[i] >> 16) + dy, xx = (ryx[i] & 0xffff) + dx;
+            const bool ok = rpix[i] >= 0 && yy >= 0 && yy < H && xx >= 0 && xx < W;
+            ra[i] = ok ? *reinterpret_cast<const f32x4*>(in + (size_t)(rpix[i] + dy * W + dx) * Cin + ci0 + 4 * ac)
+                       : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        }
+#pragma unroll
+        for (int i = 0; i < B_V8; i++) rb[i] = *reinterpret_cast<const bf16x8*>(wbase + (size_t)(B_RPP * i) * K9 + k0);
+    };
+    auto sstore = [&](int buf) __attribute__((always_inline)) {
+        __bf16* s_A = s_ab + buf * SLICE;
+        __bf16* s_B = s_A + BM * LDB;
+#pragma unroll
+        for (int i = 0; i < A_F4; i++) *reinterpret_cast<bf16x4*>(s_A + (ar + A_RPP * i) * LDB + 4 * ac) = to_bf16x4(ra[i]);
+#pragma unroll
+        for (int i = 0; i < B_V8; i++) *reinterpret_cast<bf16x8*>(s_B + (br + B_RPP * i) * LDB + 8 * bc) = rb[i];
+    };
+
+    f32x16 acc0 = splat(0.0f), acc1 = splat(0.0f);
+    const int a_off = ((WK == 1 ? 32 * wave : 0) + j) * LDB + 8 * half, b_off = (BM + j) * LDB + 8 * half;
+    gload(0);
+    sstore(0);
+    __syncthreads();
+    for (int kc = 0; kc < nchunks; kc++) {
+        const bool more = kc + 1 < nchunks;
+        if (more) gload(kc + 1);                                         // in flight during the MFMAs of this slice
+        const __bf16* s = s_ab + (kc & 1) * SLICE;
+#pragma unroll
+        for (int step = (WK == 1 ? 0 : wave); step < KCB / 16; step += WK) {
+            const bf16x8 av = *reinterpret_cast<const bf16x8*>(s + a_off + 16 * step);
+            const bf16x8 b0 = *reinterpret_cast<const bf16x8*>(s + b_off + 16 * step);
+            const bf16x8 b1 = *reinterpret_cast<const bf16x8*>(s + b_off + 32 * LDB + 16 * step);
+            mfma16(acc0, av, b0);
+            mfma16(acc1, av, b1);
+        }
+        if (more) sstore((kc + 1) & 1);                                  // (the other slice: every wave left it at the last barrier)
+        __syncthreads();
+    }
+    conv_epilogue<WK, MODE>(acc0, acc1, reinterpret_cast<float*>(s_ab), tid, wave, j, half, m0, n0, M, mask_rows, Cout, a.bias, a.out, a.mask_in, a.mask_out);
+}
+
 // ---- 2x2 max-pool, stride 2, floor ---------------------------------------------------------------------------------------------------
 // One thread per pooled row and 16 channels.  The winner (first maximum in the order (0,0) (0,1) (1,0) (1,1)), two bits per channel,
 // is kept for the first image when `win` is given: (pooled row, C / 16) words.
@@ -530,10 +681,28 @@ void launch_conv_as(const ConvArgs& a, hipStream_t s)
         hipLaunchKernelGGL((conv3x3_mfma_kernel<1, 4, MODE, DYN>), dim3((a.M + 31) / 32, a.Cout / BN), dim3(WG), 0, s, a);
 }
 
-template <int MODE>
-void launch_conv(const ConvArgs& a, hipStream_t s)
+// the same choice of shape for the bf16 kernel; a slice of 128 channels where Cin has them and the shape has the LDS for two
+template <int MODE, bool DYN>
+void launch_conv_bf16_as(const ConvArgs& a, hipStream_t s)
 {
-    if (a.dyn.cap_H > 0) launch_conv_as<MODE, true>(a, s); else launch_conv_as<MODE, false>(a, s);
+    const int big = (a.M + 127) / 128 * (a.Cout / BN);
+    if (big >= device_cus())
+        hipLaunchKernelGGL((conv3x3_bf16_kernel<4, 1, 64, MODE, DYN>), dim3((a.M + 127) / 128, a.Cout / BN), dim3(WG), 0, s, a);
+    else if (a.Cin % 128 == 0)
+        hipLaunchKernelGGL((conv3x3_bf16_kernel<1, 4, 128, MODE, DYN>), dim3((a.M + 31) / 32, a.Cout / BN), dim3(WG), 0, s, a);
+    else
+        hipLaunchKernelGGL((conv3x3_bf16_kernel<1, 4, 64, MODE, DYN>), dim3((a.M + 31) / 32, a.Cout / BN), dim3(WG), 0, s, a);
+}
+
+// bf16: a.w is the bf16 packing and the operands are rounded (conv3x3_bf16_kernel)
+template <int MODE>
+void launch_conv(const ConvArgs& a, bool bf16, hipStream_t s)
+{
+    if (bf16) {
+        if (a.dyn.cap_H > 0) launch_conv_bf16_as<MODE, true>(a, s); else launch_conv_bf16_as<MODE, false>(a, s);
+    } else {
+        if (a.dyn.cap_H > 0) launch_conv_as<MODE, true>(a, s); else launch_conv_as<MODE, false>(a, s);
+    }
 }
 
 int grid_for(long long threads) { return (int)((threads + WG - 1) / WG); }
@@ -551,8 +720,17 @@ extern "C" size_t moss_lpips_vgg_saved_bytes(int H, int W) { return size_ok(H, W
 extern "C" int moss_lpips_vgg_pack_weights(int cin, int cout, const float* w, float* fwd, float* bwd, void* stream)
 {
     if (cin <= 0 || cout <= 0 || !w || !fwd || !bwd) return invalid_arg("moss_lpips_vgg_pack_weights", "sizes <= 0 or a null pointer");
-    hipLaunchKernelGGL(pack_weights_kernel, dim3(grid_for((long long)cin * cout * 9)), dim3(WG), 0, (hipStream_t)stream, cin, cout, w, fwd, bwd);
+    hipLaunchKernelGGL(pack_weights_kernel<float>, dim3(grid_for((long long)cin * cout * 9)), dim3(WG), 0, (hipStream_t)stream, cin, cout, w, fwd, bwd);
     return launch_status("moss_lpips_vgg_pack_weights");
+}
+
+extern "C" int moss_lpips_vgg_pack_weights_bf16(int cin, int cout, const float* w, uint16_t* fwd, uint16_t* bwd, void* stream)
+{
+    const char* me = "moss_lpips_vgg_pack_weights_bf16";
+    if (cin <= 0 || cout <= 0 || !w || !fwd || !bwd) return invalid_arg(me, "sizes <= 0 or a null pointer");
+    hipLaunchKernelGGL(pack_weights_kernel<__bf16>, dim3(grid_for((long long)cin * cout * 9)), dim3(WG), 0, (hipStream_t)stream, cin, cout, w,
+                       reinterpret_cast<__bf16*>(fwd), reinterpret_cast<__bf16*>(bwd));
+    return launch_status(me);
 }
 
 // H, W: on return the size the launches and the regions of `saved` and `workspace` are made for -- the crop's, or the capacity's
@@ -575,10 +753,9 @@ static const char* check_frame(int& H, int& W, int cap_H, int cap_W, const int* 
 
 static const char* SHORT_WORKSPACE = "the workspace is null or smaller than moss_lpips_vgg_workspace_bytes(H, W) (of cap_H, cap_W with a capacity)";
 
-// LPIPS.forward, lpipsPyTorch/modules/lpips.py:31-37 (net_type='vgg')
-extern "C" int moss_lpips_vgg_forward(const moss_lpips_vgg_args* a, void* stream)
+// LPIPS.forward, lpipsPyTorch/modules/lpips.py:31-37 (net_type='vgg').  bf16: weights[1..12] are the bf16 packing
+static int lpips_forward(const char* me, const moss_lpips_vgg_args* a, bool bf16, void* stream)
 {
-    const char* me = "moss_lpips_vgg_forward";
     if (!a) return invalid_arg(me, "null argument block");
     int FH = a->frame_H, FW = a->frame_W;
     int H = a->H, W = a->W;
@@ -614,7 +791,7 @@ extern "C" int moss_lpips_vgg_forward(const moss_lpips_vgg_args* a, void* stream
         c.in = cur; c.w = a->weights[i]; c.bias = a->biases[i]; c.out = nxt; c.mask_out = mask_at(i);
         c.M = 2 * HW; c.mask_rows = HW; c.H = g.H[l]; c.W = g.W[l]; c.Cin = CONV_COUT[i - 1]; c.Cout = CONV_COUT[i];
         c.dyn = dyn_at(l); c.nimg = 2;
-        launch_conv<MODE_FWD>(c, s);
+        launch_conv<MODE_FWD>(c, bf16, s);
         std::swap(cur, nxt);
         if (i != TAP_CONV[tap]) continue;
         const int C = TAP_C[tap];
@@ -633,10 +810,19 @@ extern "C" int moss_lpips_vgg_forward(const moss_lpips_vgg_args* a, void* stream
     return launch_status(me);
 }
 
-// the adjoint of LPIPS.forward (lpipsPyTorch/modules/lpips.py:31-37) w.r.t. x
-extern "C" int moss_lpips_vgg_backward(const moss_lpips_vgg_backward_args* a, void* stream)
+extern "C" int moss_lpips_vgg_forward(const moss_lpips_vgg_args* a, void* stream)
 {
-    const char* me = "moss_lpips_vgg_backward";
+    return lpips_forward("moss_lpips_vgg_forward", a, false, stream);
+}
+
+extern "C" int moss_lpips_vgg_forward_bf16(const moss_lpips_vgg_args* a, void* stream)
+{
+    return lpips_forward("moss_lpips_vgg_forward_bf16", a, true, stream);
+}
+
+// the adjoint of LPIPS.forward (lpipsPyTorch/modules/lpips.py:31-37) w.r.t. x.  bf16: weights_bwd[1..12] are the bf16 packing
+static int lpips_backward(const char* me, const moss_lpips_vgg_backward_args* a, bool bf16, void* stream)
+{
     if (!a) return invalid_arg(me, "null argument block");
     int FH = a->frame_H, FW = a->frame_W;
     int H = a->H, W = a->W;
@@ -669,11 +855,21 @@ extern "C" int moss_lpips_vgg_backward(const moss_lpips_vgg_backward_args* a, vo
         c.in = cur; c.w = a->weights_bwd[i]; c.out = nxt; c.mask_in = pooled_below ? nullptr : mask_at(i - 1);
         c.M = g.H[l] * g.W[l]; c.H = g.H[l]; c.W = g.W[l]; c.Cin = CONV_COUT[i]; c.Cout = CONV_COUT[i - 1];
         c.dyn = dyn_at(l); c.nimg = 1;
-        if (pooled_below) launch_conv<MODE_BWD_PLAIN>(c, s); else launch_conv<MODE_BWD_MASK>(c, s);
+        if (pooled_below) launch_conv<MODE_BWD_PLAIN>(c, bf16, s); else launch_conv<MODE_BWD_MASK>(c, bf16, s);
         std::swap(cur, nxt);
         from_above = pooled_below ? cur : nullptr;
     }
     hipLaunchKernelGGL(conv_first_backward_kernel, dim3(grid_for((long long)FH * FW)), dim3(WG), 0, s, (const float*)cur, a->rect, FH, FW,
                        H, W, a->weights_bwd[0], a->scale, a->g_out, a->dL_dx, dyn_at(0));
     return launch_status(me);
+}
+
+extern "C" int moss_lpips_vgg_backward(const moss_lpips_vgg_backward_args* a, void* stream)
+{
+    return lpips_backward("moss_lpips_vgg_backward", a, false, stream);
+}
+
+extern "C" int moss_lpips_vgg_backward_bf16(const moss_lpips_vgg_backward_args* a, void* stream)
+{
+    return lpips_backward("moss_lpips_vgg_backward_bf16", a, true, stream);
 }

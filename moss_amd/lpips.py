@@ -11,6 +11,8 @@ through a non-trainable 1x1 convolution to one channel and a spatial mean; the f
   images as one batch of two, every wide convolution on the f32-input matrix cores in exact float32, gradient to ``x`` only.  The
   backward reads sign masks, pool winners and the tap gradients the forward left, never a layer input.  No host read, no atomics,
   bitwise reproducible, capturable.
+  ``LpipsVGG(..., precision="bf16")`` is the opt-in mixed-precision form of the TRAINING term (``moss_lpips_vgg_forward_bf16`` /
+  ``_backward_bf16``): see :class:`LpipsVGG`.  The net carries the choice; the ops take no argument for it.
 * :func:`lpips_vgg_roi_fused` -- the same on the ``ViewRegion`` rectangle of two full frames (no crop copies; the offset is read on the
   device, and with ``capacity=`` the crop's size too: one capture serves views whose crops differ in size).
   :func:`crop_capacity` -- the capacity of a dataset's views.
@@ -29,7 +31,7 @@ import hashlib
 import torch
 
 __all__ = ["LpipsVGG", "lpips_vgg_fused", "lpips_vgg_roi_fused", "crop_capacity", "lpips_vgg_torch", "synthetic_weights", "weights_sha256",
-           "CONV_SHAPES", "TAP_CHANNELS", "TAP_AFTER_CONV", "POOL_AFTER_CONV", "SHIFT", "SCALE", "MIN_SIZE"]
+           "PRECISIONS", "CONV_SHAPES", "TAP_CHANNELS", "TAP_AFTER_CONV", "POOL_AFTER_CONV", "SHIFT", "SCALE", "MIN_SIZE"]
 
 _WIDTHS = (64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512)
 CONV_SHAPES = tuple((co, ci, 3, 3) for ci, co in zip((3,) + _WIDTHS[:-1], _WIDTHS))
@@ -40,15 +42,43 @@ SHIFT = (-0.030, -0.088, -0.188)                          # BaseNet.mean (lpipsP
 SCALE = (0.458, 0.448, 0.450)                             # BaseNet.std
 MIN_SIZE = 16                                             # four pools: the last tap is at least 1x1
 EPS = 1e-10                                               # normalize_activation (lpipsPyTorch/modules/utils.py:5-7)
+PRECISIONS = ("f32", "bf16")                              # LpipsVGG(precision=): the operands of the twelve wide convolutions
+_SUFFIX = {"f32": "", "bf16": "_bf16"}                    # of the C entry points
 
 
 # ---- the torch form ---------------------------------------------------------------------------------------------------------------
 
-def lpips_vgg_torch(params, x, y, return_terms=False):
+class _RoundedOperandConv(torch.autograd.Function):
+    """``conv2d(h, w, b, padding=1)`` with both operands of every product rounded to ``dtype`` and back (round-to-nearest-even), in
+    the forward AND in the data gradient: the backward rounds the incoming gradient and convolves it with the rounded weight.  A plain
+    ``.to(dtype)`` would not do: its backward is the identity, and the gradient convolution would see unrounded operands.  The sums
+    are in the tensors' own dtype; the weight and the bias get no gradient (they are frozen)."""
+
+    @staticmethod
+    def forward(ctx, h, w, b, dtype):
+        import torch.nn.functional as F
+        rounded = lambda t: t.to(dtype).to(t.dtype)                                  # noqa: E731
+        wr = rounded(w)
+        ctx.save_for_backward(wr)
+        ctx.dtype, ctx.shape = dtype, h.shape
+        return F.conv2d(rounded(h), wr, b, padding=1)
+
+    @staticmethod
+    def backward(ctx, g):
+        (wr,) = ctx.saved_tensors
+        return torch.nn.grad.conv2d_input(ctx.shape, wr, g.to(ctx.dtype).to(g.dtype), padding=1), None, None, None
+
+
+def lpips_vgg_torch(params, x, y, return_terms=False, operand_dtype=None):
     """``LPIPS.forward(x, y)`` for ``net_type='vgg'`` in plain torch.  ``params``: a mapping with ``conv_weights`` (13 tensors
     (Cout,Cin,3,3)), ``conv_biases`` (13), ``lin_weights`` (5 tensors of C, any shape), ``shift`` and ``scale`` (3 each), all of the
     images' dtype and device; ``x``, ``y`` (3,H,W) or (1,3,H,W).  Returns (1,1,1,1); with ``return_terms`` also the five per-tap
-    terms as a (5,) tensor."""
+    terms as a (5,) tensor.
+
+    ``operand_dtype=torch.bfloat16``: the arithmetic of ``LpipsVGG(precision="bf16")`` -- in convolutions 2..13 the input, the weight
+    and (in the backward) the incoming gradient are rounded to bf16 before they are multiplied; the sums, conv 1_1 and everything else
+    stay in the tensors' dtype.  In float64 this is the exact statement of what the bf16 kernels compute.  ``None``: nothing is
+    rounded."""
     import torch.nn.functional as F
     shift = params["shift"].reshape(1, 3, 1, 1)
     scale = params["scale"].reshape(1, 3, 1, 1)
@@ -57,7 +87,10 @@ def lpips_vgg_torch(params, x, y, return_terms=False):
         h = (img.reshape(1, 3, img.shape[-2], img.shape[-1]) - shift) / scale
         taps = []
         for i, (w, b) in enumerate(zip(params["conv_weights"], params["conv_biases"])):
-            h = torch.relu(F.conv2d(h, w, b, padding=1))
+            if operand_dtype is None or i == 0:
+                h = torch.relu(F.conv2d(h, w, b, padding=1))
+            else:
+                h = torch.relu(_RoundedOperandConv.apply(h, w, b, operand_dtype))
             if i in TAP_AFTER_CONV:
                 taps.append(h / (torch.sqrt(torch.sum(h ** 2, dim=1, keepdim=True)) + EPS))
             if i in POOL_AFTER_CONV:
@@ -113,9 +146,25 @@ def _is_conv(m, k):
 class LpipsVGG:
     """The frozen LPIPS-VGG16 weights on a GPU, packed once into the two layouts of moss_amd/csrc/lpips.hip: per convolution
     ``[Cout][tap][Cin]`` for the forward and ``[Cin][flipped tap][Cout]`` for the data gradient.  The packed copies are this object's
-    own; the tensors or the module they came from are only read (:meth:`refresh` reads them again)."""
+    own; the tensors or the module they came from are only read (:meth:`refresh` reads them again).
 
-    def __init__(self, conv_weights, conv_biases, lin_weights, shift, scale):
+    ``precision="f32"`` (the default): every product and sum in float32 -- the only form an evaluation metric may use
+    (``metrics.evaluate_views`` refuses any other).  ``precision="bf16"``: in convolutions 2..13, forward and data gradient, both
+    operands of every product are rounded to bf16 (nearest even: the weights once, here; the activations and incoming gradients as
+    the kernel stages them -- in memory they stay float32) and the sums are float32; conv 1_1 and everything outside the convolutions
+    are unchanged (``w_fwd[1:]`` / ``w_bwd[1:]`` are ``torch.bfloat16``, ``[0]`` float32).  It is
+    ``lpips_vgg_torch(..., operand_dtype=torch.bfloat16)`` to float32 summation order, bitwise reproducible, and 2.1-2.4x faster
+    (256x176: 1.02 against 2.14 ms forward + backward).  What it costs, measured on the CPU with an emulation in torch against exact
+    float64, SYNTHETIC weights (``synthetic_weights(0)``; pretrained weights were not measured) -- value relative / gradient relative
+    L2 / gradient cosine, and plain float32's gradient relative L2 beside it: uniform noise 37x53 3.8e-4 / 0.058 / 0.9983 (float32:
+    1e-6); a person-like crop 101x77 1.1e-2 / 0.23 / 0.974 (0.056); 256x176 1.1e-2 / 0.27 / 0.964 (0.090).  On a person-shaped crop
+    float32 itself is 6-9 % from float64 in the gradient (ReLU and pool decisions on the near-black ground flip); bf16 is about three
+    times that.  Use it for the training term (weighted 0.5 in MOSS's loss), not for a reported number."""
+
+    def __init__(self, conv_weights, conv_biases, lin_weights, shift, scale, precision="f32"):
+        if precision not in PRECISIONS:
+            raise ValueError(f"LpipsVGG: precision must be one of {PRECISIONS}, got {precision!r}")
+        self.precision = precision
         self._src = (list(conv_weights), list(conv_biases), list(lin_weights), shift, scale)
         cw, cb, lw = self._src[:3]
         if len(cw) != 13 or len(cb) != 13 or len(lw) != 5:
@@ -139,15 +188,15 @@ class LpipsVGG:
         self.refresh()
 
     @classmethod
-    def from_tensors(cls, conv_weights, conv_biases, lin_weights, shift, scale):
+    def from_tensors(cls, conv_weights, conv_biases, lin_weights, shift, scale, precision="f32"):
         """13 weights (Cout,Cin,3,3), 13 biases, 5 lin weights ((1,C,1,1) or (C,)), shift and scale (3 values each), on one GPU."""
-        return cls(conv_weights, conv_biases, lin_weights, shift, scale)
+        return cls(conv_weights, conv_biases, lin_weights, shift, scale, precision)
 
     @classmethod
-    def from_module(cls, module):
+    def from_module(cls, module, precision="f32"):
         """An :class:`LpipsVGG` of the weights :meth:`find_tensors` finds in the caller's module.  The module stays the caller's: it is
         only read, its ``state_dict`` and checkpoints are untouched."""
-        return cls(*cls.find_tensors(module))
+        return cls(*cls.find_tensors(module), precision=precision)
 
     @staticmethod
     def find_tensors(module):
@@ -177,7 +226,7 @@ class LpipsVGG:
         return [m.weight for m in convs], [m.bias for m in convs], [m.weight for m in lins], shift, scale
 
     def refresh(self):
-        """Pack the source tensors again (a caller who reloaded its weights)."""
+        """Pack the source tensors again (a caller who reloaded its weights), in this net's precision."""
         from ._lib import call
         cw, cb, lw, shift, scale = self._src
         f32 = lambda t: t.detach().to(torch.float32).contiguous()
@@ -188,9 +237,11 @@ class LpipsVGG:
         for i, w in enumerate(cw):
             w = f32(w)
             co, ci = int(w.shape[0]), int(w.shape[1])
-            fwd = torch.empty(w.numel(), dtype=torch.float32, device=self.device)
-            bwd = torch.empty(w.numel(), dtype=torch.float32, device=self.device)
-            call("moss_lpips_vgg_pack_weights", self.device, ci, co, w.data_ptr(), fwd.data_ptr(), bwd.data_ptr())
+            bf16 = self.precision == "bf16" and i > 0                                # (conv 1_1 stays float32 on the VALU)
+            fwd = torch.empty(w.numel(), dtype=torch.bfloat16 if bf16 else torch.float32, device=self.device)
+            bwd = torch.empty_like(fwd)
+            call("moss_lpips_vgg_pack_weights_bf16" if bf16 else "moss_lpips_vgg_pack_weights", self.device, ci, co, w.data_ptr(),
+                 fwd.data_ptr(), bwd.data_ptr())
             self.w_fwd.append(fwd)
             self.w_bwd.append(bwd)
         return self
@@ -235,7 +286,7 @@ class _LpipsVGG(torch.autograd.Function):
         a.out, a.terms = out.data_ptr(), terms.data_ptr()
         a.saved = saved.data_ptr() if keep else None
         a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
-        call("moss_lpips_vgg_forward", dev, ctypes.byref(a))
+        call("moss_lpips_vgg_forward" + _SUFFIX[net.precision], dev, ctypes.byref(a))
         ctx.net, ctx.crop, ctx.frame, ctx.capacity = net, (h, w), (FH, FW), capacity
         ctx.save_for_backward(saved, rect if rect is not None else torch.empty(0, dtype=torch.int32, device=dev))
         ctx.mark_non_differentiable(terms)
@@ -257,7 +308,7 @@ class _LpipsVGG(torch.autograd.Function):
             a.weights_bwd[i] = net.w_bwd[i].data_ptr()
         a.scale, a.saved, a.g_out, a.dL_dx = net.scale.data_ptr(), saved.data_ptr(), g.data_ptr(), d_x.data_ptr()
         a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
-        call("moss_lpips_vgg_backward", dev, ctypes.byref(a))
+        call("moss_lpips_vgg_backward" + _SUFFIX[net.precision], dev, ctypes.byref(a))
         return d_x, None, None, None, None, None
 
 

@@ -150,8 +150,13 @@ def evaluate_views(pc, cameras, gts, regions, bg, transforms=None, translation=N
     on the device.  ``gts``: (3,H,W) float32 images; ``regions``: a :class:`moss_amd.loss.ViewRegion` per view or None (no fill);
     ``transforms`` / ``translation``: one LBS table for all views or a list.  No host read inside the loop; one at the end.
     ``lpips``: a :class:`moss_amd.lpips.LpipsVGG` instead of ``lpips_fn`` -- the term from the fused HIP op
-    (:func:`moss_amd.lpips.lpips_vgg_fused`, its forward that keeps nothing), summed in float64 in view order like the others.
+    (:func:`moss_amd.lpips.lpips_vgg_fused`, its forward that keeps nothing), summed in float64 in view order like the others.  The net
+    must be a float32 one: reported LPIPS is the float32 term, and a ``precision="bf16"`` net (the training term's mixed-precision
+    mode) raises ``ValueError`` before anything is rendered.
     Returns ``{"l1", "psnr", "ssim", "lpips", "n"}``: the reference's four set means (``lpips`` None without ``lpips_fn`` / ``lpips``)."""
+    if lpips is not None and getattr(lpips, "precision", "f32") != "f32":
+        raise ValueError(f"evaluate_views: reported LPIPS is the float32 term; the net given has precision={lpips.precision!r} "
+                         "(build a second LpipsVGG with precision='f32' for evaluation)")
     from types import SimpleNamespace
 
     from .diff_gaussian_rasterization import RasterContext

@@ -48,7 +48,10 @@ class MossStep:
     ``auto_regression``, ``cross_attention_lbs``, ``SMPL_NEUTRAL``, ``knn``, ``coarse_deform_c2source`` and
     ``motion_offset_flag=True``.  ``view``: a camera with ``smpl_param`` (``pose_rotmats`` included), ``big_pose_smpl_param`` and
     ``big_pose_world_vertex``.  ``gt_image`` (3,H,W), ``bkgd_mask`` (1,H,W), ``region`` (a ``loss.ViewRegion``), ``bg`` (3,);
-    ``lpips_net``: an ``lpips.LpipsVGG``.  ALL of them are static inputs: the caller changes frame between steps by ``copy_`` into
+    ``lpips_net``: an ``lpips.LpipsVGG``; the net carries the precision of the term -- ``LpipsVGG(..., precision="bf16")`` runs the
+    twelve wide convolutions with bf16 operands and float32 sums (the step at P = 45 695: 3.55 against 4.68 ms; the term moves by about
+    1 % and its gradient by about 0.2 relative L2 on a person-like crop with synthetic weights, three times what float32 itself is from
+    float64 there -- a training term, never the reported metric: ``lpips.py``, profiles/lpips_notes.md).  ALL of them are static inputs: the caller changes frame between steps by ``copy_`` into
     these tensors and ``region.copy_``.
 
     ``lpips_capacity``: ``(cap_h, cap_w)`` -- ``lpips.crop_capacity`` of the dataset's regions -- or ``"frame"``; it goes to

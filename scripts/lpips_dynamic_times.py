@@ -93,9 +93,13 @@ class Variant:
 
 
 def load_other(path):
-    from moss_amd._lib import _declare
+    """Another build's library with the prototypes of the float32 LPIPS calls alone (it may lack entry points newer than those)."""
     lib = ctypes.CDLL(os.path.abspath(path))
-    _declare(lib)
+    for name in ("moss_lpips_vgg_forward", "moss_lpips_vgg_backward"):
+        getattr(lib, name).restype, getattr(lib, name).argtypes = ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]
+    for name in ("moss_lpips_vgg_workspace_bytes", "moss_lpips_vgg_saved_bytes"):
+        getattr(lib, name).restype, getattr(lib, name).argtypes = ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]
+    lib.moss_last_error.restype = ctypes.c_char_p
     return lib
 
 

@@ -5,12 +5,13 @@ convolutions and the small kernels around them) replayed from a graph and eagerl
 search.  Forward alone (the evaluation call, under no_grad) and forward + backward to x (the training call); the peak device memory
 of one training call of each form on top of what is allocated before it (torch.cuda.max_memory_allocated).
 
-    python scripts/lpips_times.py [--iters 20] [--sizes 256x176,512x352,512x512:fwd,1024x1024:fwd] [--json PATH]
+    python scripts/lpips_times.py [--iters 20] [--sizes 256x176,512x352,512x512:fwd,1024x1024:fwd] [--precision f32|bf16] [--json PATH]
 
 A size with ``:fwd`` is timed forward only.  Every (implementation, size) is a process of its own under ``timeout``; the script stops
 at the first one that does not exit with 0.  A time is the wall clock around ``iters`` back-to-back calls between two device
 synchronisations, per call, after a warm-up.  The weights are synthetic (moss_amd.lpips.synthetic_weights): the arithmetic does not
-depend on their values.  Needs a GPU; there is no CPU timing.
+depend on their values.  ``--precision bf16`` times the fused op's bf16-operand mode (``LpipsVGG(precision="bf16")``; the torch form
+is float32 either way, and the share printed stays that of the f32 matrix peak).  Needs a GPU; there is no CPU timing.
 """
 import argparse
 import json
@@ -38,7 +39,7 @@ def flop_per_pass(H, W):
     return total
 
 
-def measure(impl, H, W, fwd_only, iters):
+def measure(impl, H, W, fwd_only, iters, precision="f32"):
     import torch
     from moss_amd import lpips as mlp
     from moss_amd.graphs import capturing
@@ -50,7 +51,8 @@ def measure(impl, H, W, fwd_only, iters):
     if impl == "torch":
         term = lambda: mlp.lpips_vgg_torch(params, x, y)                            # noqa: E731
     else:
-        net = mlp.LpipsVGG.from_tensors(params["conv_weights"], params["conv_biases"], params["lin_weights"], params["shift"], params["scale"])
+        net = mlp.LpipsVGG.from_tensors(params["conv_weights"], params["conv_biases"], params["lin_weights"], params["shift"], params["scale"],
+                                        precision=precision)
         term = lambda: mlp.lpips_vgg_fused(net, x, y)                               # noqa: E731
 
     def fwd():
@@ -101,13 +103,14 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--sizes", default="256x176,512x352,512x512:fwd,1024x1024:fwd")
     ap.add_argument("--impls", default=",".join(IMPLS))
+    ap.add_argument("--precision", default="f32", choices=("f32", "bf16"), help="the fused op's operand precision")
     ap.add_argument("--json", default=None)
     ap.add_argument("--step", default=None, help="(internal) IMPL:HxW[:fwd] -- run that measurement in this process and print its JSON line")
     args = ap.parse_args()
     if args.step:
         impl, size, *rest = args.step.split(":")
         H, W = (int(v) for v in size.split("x"))
-        print(json.dumps({"impl": impl, "size": size, "us_per_call": measure(impl, H, W, bool(rest), args.iters), "iters": args.iters}))
+        print(json.dumps({"impl": impl, "size": size, "us_per_call": measure(impl, H, W, bool(rest), args.iters, args.precision), "iters": args.iters}))
         return 0
     res = {}
     for spec in args.sizes.split(","):
@@ -115,7 +118,7 @@ def main():
         H, W = (int(v) for v in size.split("x"))
         for impl in args.impls.split(","):
             p = subprocess.run(["timeout", "-k", "10", str(STEP_TIMEOUT), sys.executable, os.path.abspath(__file__), "--step",
-                                f"{impl}:{spec}", "--iters", str(args.iters)], stdout=subprocess.PIPE, text=True)
+                                f"{impl}:{spec}", "--iters", str(args.iters), "--precision", args.precision], stdout=subprocess.PIPE, text=True)
             if p.returncode != 0:
                 print(f"{impl} {size}: exit status {p.returncode}; stopping here", flush=True)
                 return p.returncode
@@ -130,7 +133,7 @@ def main():
                               f"{flop / (r[mode] * 1e-6) / F32_MFMA_PEAK * 100:.1f} % of the f32 matrix peak", flush=True)
     if args.json:
         with open(args.json, "w") as fh:
-            json.dump({"iters": args.iters, "results": res}, fh, indent=1)
+            json.dump({"iters": args.iters, "precision": args.precision, "results": res}, fh, indent=1)
     return 0
 
 

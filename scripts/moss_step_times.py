@@ -11,6 +11,7 @@ SH degree 3, synthetic LPIPS weights, a 192 x 256 region:
     profile    ``rocprofv3 --kernel-trace --stats`` over the captured step at the larger size; the per-kernel table is printed
 
     python scripts/moss_step_times.py [--replays 300] [--sizes 6890,45695] [--only captured,baseline,profile] [--out DIR]
+                                      [--lpips-precision f32|bf16]
 
 Every measurement is a process of its own under ``timeout -k 10``; the script stops at the first one that does not exit with 0.  A time
 is the wall clock around ``replays`` back-to-back steps between two device synchronisations, after a warm-up.  Needs a GPU.
@@ -44,7 +45,7 @@ def _frame(k, dev):
     return {k_: v.to(dev) for k_, v in f.items()}
 
 
-def _world(P, dev, unified):
+def _world(P, dev, unified, lpips_precision="f32"):
     """Model, camera and targets: MOSS's initialisation at 6 890 Gaussians, post-densification statistics above."""
     import torch
     from moss_amd import lbs as mlbs
@@ -78,7 +79,8 @@ def _world(P, dev, unified):
     bound = torch.zeros(1, H, W)
     bound[:, 128:384, 160:352] = 1
     lp = mlp.cast_params(mlp.synthetic_weights(), device=dev)
-    net = mlp.LpipsVGG.from_tensors(lp["conv_weights"], lp["conv_biases"], lp["lin_weights"], lp["shift"], lp["scale"])
+    net = mlp.LpipsVGG.from_tensors(lp["conv_weights"], lp["conv_biases"], lp["lin_weights"], lp["shift"], lp["scale"],
+                                    precision=lpips_precision)
     return dict(pc=pc, cam=cam, gt=torch.rand(3, H, W, generator=g).to(dev), bkgd=(torch.rand(1, H, W, generator=g) > 0.5).float().to(dev),
                 region=ViewRegion(bound.to(dev)), bg=torch.zeros(3, device=dev), lpips=net)
 
@@ -97,11 +99,11 @@ def _timed(fn, replays, dev, load):
     return (time.perf_counter() - t0) / replays
 
 
-def measure_captured(P, replays):
+def measure_captured(P, replays, lpips_precision="f32"):
     import torch
     from moss_amd.train import MossStep
     dev = torch.device("cuda:0")
-    w = _world(P, dev, unified=True)
+    w = _world(P, dev, unified=True, lpips_precision=lpips_precision)
     step = MossStep(w["pc"], w["cam"], w["gt"], w["bkgd"], w["region"], w["bg"], w["lpips"], {"auto_regression": LR_HEAD, "cross_attention_lbs": LR_NET})
     step.capture(warmup=3)
     frames = [_frame(k, dev) for k in range(3)]
@@ -115,11 +117,11 @@ def measure_captured(P, replays):
     out = step()
     torch.cuda.synchronize(dev)
     assert step.dropped_frames == 0 and float(out["render"].abs().max()) > 0 and bool(torch.isfinite(out["terms"]).all())
-    return {"form": "captured", "P": P, "replays": replays, "us_per_step": round(dt * 1e6, 1), "it_per_s": round(1.0 / dt, 1),
+    return {"form": "captured", "P": P, "lpips_precision": lpips_precision, "replays": replays, "us_per_step": round(dt * 1e6, 1), "it_per_s": round(1.0 / dt, 1),
             "steps": list(step.step_counts()), "total_loss": float(out["terms"][-1])}
 
 
-def measure_baseline(P, replays):
+def measure_baseline(P, replays, lpips_precision="f32"):
     import torch
     from types import SimpleNamespace
     from moss_amd import lbs_weights as mlw
@@ -130,7 +132,7 @@ def measure_baseline(P, replays):
     from moss_amd.lpips import lpips_vgg_roi_fused
     from moss_amd.optim import AdamW
     dev = torch.device("cuda:0")
-    w = _world(P, dev, unified=False)
+    w = _world(P, dev, unified=False, lpips_precision=lpips_precision)
     pc, cam = w["pc"], w["cam"]
     cx = RasterContext()
     cx.set_async(True)
@@ -162,7 +164,7 @@ def measure_baseline(P, replays):
     cx.check_status()
     assert float(last["image"].abs().max()) > 0 and bool(torch.isfinite(last["loss"]))
     assert all(p.grad is not None for p in mpose.head_parameters(pc.auto_regression) + mlw.net_parameters(pc.cross_attention_lbs))
-    return {"form": "baseline_eager_dropin_adamw", "P": P, "replays": replays, "us_per_step": round(dt * 1e6, 1), "it_per_s": round(1.0 / dt, 1),
+    return {"form": "baseline_eager_dropin_adamw", "P": P, "lpips_precision": lpips_precision, "replays": replays, "us_per_step": round(dt * 1e6, 1), "it_per_s": round(1.0 / dt, 1),
             "total_loss": float(last["loss"])}
 
 
@@ -183,6 +185,7 @@ def main():
     ap.add_argument("--sizes", default="6890,45695")
     ap.add_argument("--only", default="captured,baseline,profile")
     ap.add_argument("--out", default="moss_step_times_out")
+    ap.add_argument("--lpips-precision", default="f32", choices=("f32", "bf16"), help="the LPIPS net's operand precision (LpipsVGG(precision=))")
     ap.add_argument("--package-root", default=os.path.dirname(HERE), help="the checkout whose moss_amd is measured")
     ap.add_argument("--worker", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--P", type=int, default=0, help=argparse.SUPPRESS)
@@ -191,12 +194,13 @@ def main():
     if a.worker:
         if a.replays < 200:
             raise SystemExit("at least 200 replays per measurement")
-        print("RESULT " + json.dumps({"captured": measure_captured, "baseline": measure_baseline}[a.worker](a.P, a.replays)), flush=True)
+        print("RESULT " + json.dumps({"captured": measure_captured, "baseline": measure_baseline}[a.worker](a.P, a.replays, a.lpips_precision)), flush=True)
         return
     os.makedirs(a.out, exist_ok=True)
     sizes = [int(x) for x in a.sizes.split(",")]
     only = a.only.split(",")
-    me = [sys.executable, os.path.abspath(__file__), "--package-root", os.path.abspath(a.package_root), "--replays", str(a.replays)]
+    me = [sys.executable, os.path.abspath(__file__), "--package-root", os.path.abspath(a.package_root), "--replays", str(a.replays),
+          "--lpips-precision", a.lpips_precision]
     jobs = [(f"{form}_{P}", ["timeout", "-k", "10", str(STEP_TIMEOUT)] + me + ["--worker", form, "--P", str(P)])
             for form in ("captured", "baseline") if form in only for P in sizes]
     if "profile" in only:
