@@ -688,7 +688,8 @@ size_t moss_lbs_weight_net_saved_bytes(int P);      /* what its forward keeps fo
  * Both images run as one batch of two; the weights are frozen and y gets no gradient, so the backward is the data gradient w.r.t. x.
  *   x, y: (3,frame_H,frame_W) fp32 planes; the term is taken on the crop of H x W pixels whose corner is rect[0] (x), rect[1] (y) --
  *     DEVICE ints as moss_photometric_loss_roi's, moved so that the crop fits the frame -- or (0,0) with rect NULL; frame_H = frame_W
- *     = 0 means the frame is the crop.  H, W >= 16, H * W <= 2^22; neither needs to be a multiple of anything.
+ *     = 0 means the frame is the crop.  H, W >= 16, H * W <= 2^22, and H <= 32768, W <= 65536 (the convolution kernels keep a
+ *     pixel's y and x in the two halves of one signed 32-bit word); neither needs to be a multiple of anything.
  *   weights / biases: per convolution, packed by moss_lpips_vgg_pack_weights (`fwd`); lin: 5 arrays of 64, 128, 256, 512, 512 floats;
  *     shift, scale: 3 device floats each.  weights_bwd: the `bwd` arrays of the same packing.
  *   out: 1 device float; terms: 5 device floats or NULL; saved: moss_lpips_vgg_saved_bytes(H, W) bytes the forward writes for the
@@ -703,7 +704,7 @@ size_t moss_lbs_weight_net_saved_bytes(int P);      /* what its forward keeps fo
  * with moss_last_error() set.
  *
  * A crop whose SIZE changes under a captured step (additive in ABI 7): cap_H, cap_W, the last two fields of both blocks.  0, 0 is the
- * static call above.  With a capacity set -- the largest crop the call will ever see, 16 <= cap, cap_H * cap_W <= 2^22, no larger
+ * static call above.  With a capacity set -- the largest crop the call will ever see, within the range of H, W above, no larger
  * than the frame -- rect is required and H, W are ignored: every kernel reads w = rect[2], h = rect[3] on the device (clamped into
  * [16, capacity] per axis for memory safety; the caller validates on the host where it can see the rectangle) and derives each level's
  * sizes, the row counts, the pool and tap extents and the 1 / (H_l W_l) of the means from them.  The launches, `workspace` and `saved`
@@ -779,6 +780,46 @@ int moss_lpips_vgg_pack_weights(int cin, int cout, const float* w, float* fwd, f
 int moss_lpips_vgg_forward_bf16(const moss_lpips_vgg_args* args, void* stream);
 int moss_lpips_vgg_backward_bf16(const moss_lpips_vgg_backward_args* args, void* stream);
 int moss_lpips_vgg_pack_weights_bf16(int cin, int cout, const float* w, uint16_t* fwd, uint16_t* bwd, void* stream);
+
+/*
+ * ONE of the wide convolutions of the term above, on its own (additive in ABI 7): the 3x3, padding-1 convolution of conv 1_2 .. 5_3,
+ * forward or data gradient, through the launcher the two full calls use and so on the very kernels they run -- with the kernel SHAPE
+ * named by the caller, which the full calls pick from the row count and the device's compute units.  It exists so that a layer can be
+ * checked per element, in either shape, at sizes of a few rows; the full calls are the product's path.
+ *   in: (nimg * H * W, cin) fp32 channels-last, row m = img * H * W + y * W + x; out: (nimg * H * W, cout).  cin, cout: multiples of 64.
+ *   weights: the `fwd` (mode 0) or `bwd` (modes 1, 2) array of moss_lpips_vgg_pack_weights -- of ..._pack_weights_bf16 with bf16 = 1 --
+ *     packed with the (cin, cout) of the FORWARD layer; for a data gradient this call's cin is that layer's cout and the other way round.
+ *   mode 0, forward: out = relu(conv(in) + bias); mask_out, if given, gets the sign words of the rows of the FIRST image (H * W rows).
+ *   mode 1, data gradient below a ReLU: out = conv(in) with the flipped, transposed weights where the bit of mask_in is set, +0 elsewhere.
+ *   mode 2, data gradient below a pool: the same, unmasked.
+ *   MASK WORDS: row-major, cout / 32 uint32_t per row; bit j of word k of row m is channel 32 k + j of that row (set: the activation
+ *     was > 0).  mask_in has a row for every row of `out`.
+ *   shape: 0 the launcher's own choice, 1 the 128-row shape, 2 the 32-row split-K shape (bf16: its slice is 128 channels where cin is a
+ *     multiple of 128, else 64, as in the full calls).  The two shapes sum K in different orders.
+ *   rect, cap_H, cap_W, level: the dynamic form of the full calls.  With a capacity (both > 0; 16 <= cap, within the range below) rect is
+ *     required, H and W are ignored, the grid is sized for (cap_H >> level) x (cap_W >> level), level 0..4, and the kernel reads
+ *     h = rect[3], w = rect[2] on the device, clamps them into [16, capacity] and halves them `level` times.  The rows are compact at that
+ *     size; rows beyond it are not written.
+ * Static sizes: H, W >= 1 (the levels a 16-pixel crop reaches are 1 x 1), H <= 32768, W <= 65536, H * W <= 2^22.  No host
+ * synchronisation, no allocation.  Refused with MOSS_ERR_INVALID_ARG and a text: a NULL block, in, weights or out, bias (mode 0) or
+ * mask_in (mode 1); cin or cout not a positive multiple of 64; a mode, shape, bf16 or level out of range; nimg outside 1..2; a size
+ * < 1 or beyond the range; a capacity without rect, outside the range, or with only one of cap_H / cap_W set.
+ */
+typedef struct moss_lpips_conv3x3_args {
+    const float* in;
+    const void* weights;                     /* float (bf16 = 0) or uint16_t (bf16 = 1) */
+    const float* bias;                       /* mode 0: cout floats */
+    float* out;
+    const uint32_t* mask_in;                 /* mode 1 */
+    uint32_t* mask_out;                      /* mode 0, or NULL */
+    int32_t nimg, H, W, cin, cout;
+    int32_t mode;                            /* 0 forward, 1 data gradient masked by ReLU bits, 2 data gradient plain */
+    int32_t shape;                           /* 0 the launcher's choice, 1 128 rows, 2 32 rows with split K */
+    int32_t bf16;                            /* 0 or 1 */
+    const int* rect;                         /* device ints {x, y, w, h}; required with a capacity */
+    int32_t cap_H, cap_W, level;             /* 0, 0 = the static call */
+} moss_lpips_conv3x3_args;
+int moss_lpips_vgg_conv3x3(const moss_lpips_conv3x3_args* args, void* stream);
 
 /*
  * k nearest reference points of every query point, 3-D, exact, k = 1..4: replaces the third-party

@@ -141,6 +141,8 @@ def _declare(lib):
     lib.moss_lpips_vgg_backward_bf16.argtypes = [_p, _p]
     lib.moss_lpips_vgg_pack_weights_bf16.restype = _i
     lib.moss_lpips_vgg_pack_weights_bf16.argtypes = [_i, _i, _p, _p, _p, _p]
+    lib.moss_lpips_vgg_conv3x3.restype = _i
+    lib.moss_lpips_vgg_conv3x3.argtypes = [_p, _p]
     lib.moss_photometric_loss_roi.restype = _i
     lib.moss_photometric_loss_roi.argtypes = [_i, _i, _i, _p, _p, _p, _p, _p, _p, _f, _f, _f, _p, _p, _p, _p, C.c_size_t, _p]
     lib.moss_adamw_flat_ex.restype = _i
@@ -272,6 +274,19 @@ class LpipsVggBackwardArgs(C.Structure):
                 ("weights_bwd", C.c_void_p * 13), ("scale", C.c_void_p), ("saved", C.c_void_p), ("g_out", C.c_void_p),
                 ("dL_dx", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("cap_H", C.c_int32),
                 ("cap_W", C.c_int32)]
+
+
+class LpipsConv3x3Args(C.Structure):
+    """``moss_lpips_conv3x3_args`` of include/moss_raster.h (``moss_lpips_vgg_conv3x3``: one wide convolution of the LPIPS term, the
+    kernel shape named by the caller)."""
+    _fields_ = [("in_", C.c_void_p), ("weights", C.c_void_p), ("bias", C.c_void_p), ("out", C.c_void_p), ("mask_in", C.c_void_p),
+                ("mask_out", C.c_void_p), ("nimg", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("cin", C.c_int32),
+                ("cout", C.c_int32), ("mode", C.c_int32), ("shape", C.c_int32), ("bf16", C.c_int32), ("rect", C.c_void_p),
+                ("cap_H", C.c_int32), ("cap_W", C.c_int32), ("level", C.c_int32)]
+
+
+LPIPS_CONV_MODES = {"fwd": 0, "bwd_mask": 1, "bwd_plain": 2}                        # moss_lpips_conv3x3_args.mode
+LPIPS_CONV_SHAPES = {"auto": 0, "rows128": 1, "rows32": 2}                          # moss_lpips_conv3x3_args.shape
 
 
 DENSIFY_MODES = {"clone": 0, "split": 1, "merge": 2, "prune": 3}                    # MOSS_DENSIFY_*

@@ -668,14 +668,28 @@ Geo geometry(int H, int W)
     return g;
 }
 
-bool size_ok(int H, int W) { return H >= 16 && W >= 16 && (long long)H * W <= (1ll << 22); }   // (32-bit element indices: 2 H W 64 < 2^31)
+// The conv kernels pack a row's pixel as (y << 16) | x in an int and take x = packed & 0xffff, y = packed >> 16: x <= 65535 and
+// y <= 32767 (one more and the shift reaches the sign bit), that is W <= 65536 and H <= 32768.
+constexpr int MAX_H = 1 << 15, MAX_W = 1 << 16;
+bool packing_ok(int H, int W) { return H <= MAX_H && W <= MAX_W; }
+
+// (32-bit element indices: 2 H W 64 < 2^31)
+bool size_ok(int H, int W) { return H >= 16 && W >= 16 && (long long)H * W <= (1ll << 22) && packing_ok(H, W); }
+
+// which of the two kernel shapes a wide convolution takes: the launcher's own choice, or the caller's (moss_lpips_vgg_conv3x3)
+enum { SHAPE_AUTO, SHAPE_ROWS128, SHAPE_ROWS32 };
+
+// the 128-row shape where its grid fills the device, the 32-row split-K shape for the deep layers' few rows
+inline bool rows128(const ConvArgs& a, int shape)
+{
+    return shape == SHAPE_AUTO ? (a.M + 127) / 128 * (a.Cout / BN) >= device_cus() : shape == SHAPE_ROWS128;
+}
 
 // a.M: the rows the grid covers and the shape is picked by -- with a capacity the capacity's, whatever the crop turns out to be
 template <int MODE, bool DYN>
-void launch_conv_as(const ConvArgs& a, hipStream_t s)
+void launch_conv_as(const ConvArgs& a, int shape, hipStream_t s)
 {
-    const int big = (a.M + 127) / 128 * (a.Cout / BN);
-    if (big >= device_cus())
+    if (rows128(a, shape))
         hipLaunchKernelGGL((conv3x3_mfma_kernel<4, 1, MODE, DYN>), dim3((a.M + 127) / 128, a.Cout / BN), dim3(WG), 0, s, a);
     else
         hipLaunchKernelGGL((conv3x3_mfma_kernel<1, 4, MODE, DYN>), dim3((a.M + 31) / 32, a.Cout / BN), dim3(WG), 0, s, a);
@@ -683,10 +697,9 @@ void launch_conv_as(const ConvArgs& a, hipStream_t s)
 
 // the same choice of shape for the bf16 kernel; a slice of 128 channels where Cin has them and the shape has the LDS for two
 template <int MODE, bool DYN>
-void launch_conv_bf16_as(const ConvArgs& a, hipStream_t s)
+void launch_conv_bf16_as(const ConvArgs& a, int shape, hipStream_t s)
 {
-    const int big = (a.M + 127) / 128 * (a.Cout / BN);
-    if (big >= device_cus())
+    if (rows128(a, shape))
         hipLaunchKernelGGL((conv3x3_bf16_kernel<4, 1, 64, MODE, DYN>), dim3((a.M + 127) / 128, a.Cout / BN), dim3(WG), 0, s, a);
     else if (a.Cin % 128 == 0)
         hipLaunchKernelGGL((conv3x3_bf16_kernel<1, 4, 128, MODE, DYN>), dim3((a.M + 31) / 32, a.Cout / BN), dim3(WG), 0, s, a);
@@ -696,12 +709,12 @@ void launch_conv_bf16_as(const ConvArgs& a, hipStream_t s)
 
 // bf16: a.w is the bf16 packing and the operands are rounded (conv3x3_bf16_kernel)
 template <int MODE>
-void launch_conv(const ConvArgs& a, bool bf16, hipStream_t s)
+void launch_conv(const ConvArgs& a, bool bf16, hipStream_t s, int shape = SHAPE_AUTO)
 {
     if (bf16) {
-        if (a.dyn.cap_H > 0) launch_conv_bf16_as<MODE, true>(a, s); else launch_conv_bf16_as<MODE, false>(a, s);
+        if (a.dyn.cap_H > 0) launch_conv_bf16_as<MODE, true>(a, shape, s); else launch_conv_bf16_as<MODE, false>(a, shape, s);
     } else {
-        if (a.dyn.cap_H > 0) launch_conv_as<MODE, true>(a, s); else launch_conv_as<MODE, false>(a, s);
+        if (a.dyn.cap_H > 0) launch_conv_as<MODE, true>(a, shape, s); else launch_conv_as<MODE, false>(a, shape, s);
     }
 }
 
@@ -739,13 +752,13 @@ static const char* check_frame(int& H, int& W, int cap_H, int cap_W, const int* 
     if (cap_H || cap_W) {
         if (cap_H <= 0 || cap_W <= 0) return "cap_H and cap_W must both be set (or both 0: the static call)";
         if (!rect) return "a capacity needs rect: the crop's size is read from it on the device";
-        if (!size_ok(cap_H, cap_W)) return "the capacity must be >= 16 per axis (four 2x2 pools) and cap_H * cap_W <= 2^22";
+        if (!size_ok(cap_H, cap_W)) return "the capacity must be >= 16 per axis (four 2x2 pools), cap_H <= 32768, cap_W <= 65536 and cap_H * cap_W <= 2^22";
         if (FH == 0 && FW == 0) { FH = cap_H; FW = cap_W; }
         if (FH < cap_H || FW < cap_W) return "the capacity is larger than the frame";
         H = cap_H; W = cap_W;
         return nullptr;
     }
-    if (!size_ok(H, W)) return "H and W must be >= 16 (four 2x2 pools) and H * W <= 2^22";
+    if (!size_ok(H, W)) return "H and W must be >= 16 (four 2x2 pools), H <= 32768, W <= 65536 and H * W <= 2^22";
     if (FH == 0 && FW == 0) { FH = H; FW = W; }
     if (FH < H || FW < W) return "the frame is smaller than the crop";
     return nullptr;
@@ -872,4 +885,43 @@ extern "C" int moss_lpips_vgg_backward(const moss_lpips_vgg_backward_args* a, vo
 extern "C" int moss_lpips_vgg_backward_bf16(const moss_lpips_vgg_backward_args* a, void* stream)
 {
     return lpips_backward("moss_lpips_vgg_backward_bf16", a, true, stream);
+}
+
+// ONE wide convolution, through launch_conv with the kernel shape the caller names: the product's own instantiations, a layer at a time
+extern "C" int moss_lpips_vgg_conv3x3(const moss_lpips_conv3x3_args* a, void* stream)
+{
+    const char* me = "moss_lpips_vgg_conv3x3";
+    if (!a) return invalid_arg(me, "null argument block");
+    if (a->mode < MODE_FWD || a->mode > MODE_BWD_PLAIN) return invalid_arg(me, "mode must be 0 (forward), 1 (data gradient, masked) or 2 (data gradient, plain)");
+    if (a->shape < SHAPE_AUTO || a->shape > SHAPE_ROWS32) return invalid_arg(me, "shape must be 0 (the launcher's choice), 1 (128 rows) or 2 (32 rows, split K)");
+    if (a->bf16 != 0 && a->bf16 != 1) return invalid_arg(me, "bf16 must be 0 or 1");
+    if (a->nimg < 1 || a->nimg > 2) return invalid_arg(me, "nimg must be 1 or 2");
+    if (a->cin < 64 || a->cout < 64 || a->cin % 64 || a->cout % 64) return invalid_arg(me, "cin and cout must be positive multiples of 64");
+    if (!a->in || !a->weights || !a->out) return invalid_arg(me, "null in, weights or out");
+    if (a->mode == MODE_FWD && !a->bias) return invalid_arg(me, "the forward needs bias");
+    if (a->mode == MODE_BWD_MASK && !a->mask_in) return invalid_arg(me, "the masked data gradient needs mask_in");
+    int H = a->H, W = a->W, level = 0;
+    if (a->cap_H || a->cap_W) {
+        if (a->cap_H <= 0 || a->cap_W <= 0) return invalid_arg(me, "cap_H and cap_W must both be set (or both 0: the static call)");
+        if (!a->rect) return invalid_arg(me, "a capacity needs rect: the size is read from it on the device");
+        if (!size_ok(a->cap_H, a->cap_W)) return invalid_arg(me, "the capacity must be >= 16 per axis, cap_H <= 32768, cap_W <= 65536 and cap_H * cap_W <= 2^22");
+        if (a->level < 0 || a->level > 4) return invalid_arg(me, "level must be 0..4");
+        level = a->level;
+        H = a->cap_H >> level; W = a->cap_W >> level;
+    } else {
+        if (H < 1 || W < 1) return invalid_arg(me, "H and W must be >= 1");
+        if (!packing_ok(H, W) || (long long)H * W > (1ll << 22)) return invalid_arg(me, "H <= 32768, W <= 65536 and H * W <= 2^22");
+    }
+    ConvArgs c{};
+    c.in = a->in; c.w = static_cast<const float*>(a->weights); c.out = a->out;
+    c.bias = a->mode == MODE_FWD ? a->bias : nullptr;
+    c.mask_in = a->mode == MODE_BWD_MASK ? a->mask_in : nullptr;
+    c.mask_out = a->mode == MODE_FWD ? a->mask_out : nullptr;
+    c.M = a->nimg * H * W; c.mask_rows = H * W; c.H = H; c.W = W; c.Cin = a->cin; c.Cout = a->cout;
+    c.dyn = Dyn{a->rect, a->cap_H, a->cap_W, level}; c.nimg = a->nimg;
+    hipStream_t s = (hipStream_t)stream;
+    if (a->mode == MODE_FWD) launch_conv<MODE_FWD>(c, a->bf16 != 0, s, a->shape);
+    else if (a->mode == MODE_BWD_MASK) launch_conv<MODE_BWD_MASK>(c, a->bf16 != 0, s, a->shape);
+    else launch_conv<MODE_BWD_PLAIN>(c, a->bf16 != 0, s, a->shape);
+    return launch_status(me);
 }
