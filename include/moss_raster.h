@@ -822,6 +822,41 @@ typedef struct moss_lpips_conv3x3_args {
 int moss_lpips_vgg_conv3x3(const moss_lpips_conv3x3_args* args, void* stream);
 
 /*
+ * The same term with SPLIT-bf16 operands in the twelve wide convolutions (additive in ABI 7): three bf16 products per float32 product,
+ * about 16 bits of every operand -- between the float32 calls and the bf16 ones in cost and in accuracy.  A form of the TRAINING term;
+ * the float32 calls stay the default, keep their bits, and are the only form an evaluation metric may use.
+ * The arithmetic, exactly: for a float32 value a let hi(a) = bf16_rne(a) and lo(a) = bf16_rne(a - hi(a)) (the subtraction is exact in
+ * float32).  In convolutions 2..13 (conv 1_2 .. 5_3), forward and data gradient alike, every product a b is replaced by
+ *     hi(a) hi(b) + hi(a) lo(b) + lo(a) hi(b)
+ * -- each bf16 x bf16 product exact in float32, every sum float32 in a fixed order (on v_mfma_f32_32x32x16_bf16; the hi hi products in
+ * one accumulator, the two small terms in another -- per sixteen k lo hi, then hi lo -- the two added per element after the last k),
+ * the lo lo term dropped.  The weights are split once, by moss_lpips_vgg_pack_weights_bf16x3; the
+ * activations (forward) and the incoming gradients (backward) each time a slice of them is staged, while in memory they stay float32.
+ * Nothing else changes: conv 1_1 and its adjoint, the bias, ReLU and its sign words, the pools, the taps, unpool and the means are the
+ * float32 call's kernels.  Per element the split sum is held to 2^-16 x mass of the unsplit product sum, mass = conv(|in|, |w|) +
+ * |bias| (measured: 0.04-0.12 of it).  One product alone: |lo| <= 2^-8 |a|, |a - hi - lo| <= 2^-17 |a| for either operand and the dropped
+ * product is at most 2^-16 |a b|, so it is off by at most 2^-15 |a b|; a sum's roundings are not all at their worst at once.
+ * A lo below bf16's normal range (|lo| < 2^-126) may be flushed to zero by the matrix core; that is not part of the contract.
+ * The split convolution equals one plain convolution over 3 cin channels, inputs [lo, hi, hi] against weights [hi, lo, hi]; it is
+ * lpips_vgg_torch(..., operand_dtype=torch.bfloat16, operand_split=True) of moss_amd/lpips.py up to float32 summation order.
+ *
+ * moss_lpips_vgg_pack_weights_bf16x3: `fwd` and `bwd` hold 2 * cout * cin * 9 16-bit values each, two planes in the layouts of the
+ * float32 packer: [0, n) the hi plane -- bit for bit what moss_lpips_vgg_pack_weights_bf16 writes -- and [n, 2n) the lo plane.
+ * moss_lpips_vgg_forward_bf16x3 / _backward_bf16x3 take the argument blocks of the float32 pair, REINTERPRETED in one place:
+ * weights[1..12] / weights_bwd[1..12] point at those arrays; [0] (conv 1_1) is the float32 packing.  Everything else -- sizes, rect, the
+ * capacity and its bit-identity rule, `saved`, `workspace` and their sizes, capturability, bitwise reproducibility, every element of
+ * dL_dx written, the refusals and the texts of moss_last_error() -- is the float32 pair's; a `saved` block goes to the backward of the
+ * precision that wrote it.
+ * moss_lpips_vgg_conv3x3_bf16x3: ONE layer on the split kernels, the block and the rules of moss_lpips_vgg_conv3x3 with `weights` the
+ * split packing (uint16_t) and the bf16 field required to be 0; the slices are the bf16 call's (64 channels, 128 in the 32-row shape
+ *   where cin is a multiple of 128).
+ */
+int moss_lpips_vgg_forward_bf16x3(const moss_lpips_vgg_args* args, void* stream);
+int moss_lpips_vgg_backward_bf16x3(const moss_lpips_vgg_backward_args* args, void* stream);
+int moss_lpips_vgg_pack_weights_bf16x3(int cin, int cout, const float* w, uint16_t* fwd, uint16_t* bwd, void* stream);
+int moss_lpips_vgg_conv3x3_bf16x3(const moss_lpips_conv3x3_args* args, void* stream);
+
+/*
  * k nearest reference points of every query point, 3-D, exact, k = 1..4: replaces the third-party
  * `knn_cuda.KNN(k, transpose_mode=True)(ref, query)` MOSS calls at scene/gaussian_model.py:85-86,586,657,759,827 (a CUDA-only
  * binary wheel, not in the repository; parity unpinned by the reference).

@@ -143,6 +143,14 @@ def _declare(lib):
     lib.moss_lpips_vgg_pack_weights_bf16.argtypes = [_i, _i, _p, _p, _p, _p]
     lib.moss_lpips_vgg_conv3x3.restype = _i
     lib.moss_lpips_vgg_conv3x3.argtypes = [_p, _p]
+    lib.moss_lpips_vgg_forward_bf16x3.restype = _i
+    lib.moss_lpips_vgg_forward_bf16x3.argtypes = [_p, _p]
+    lib.moss_lpips_vgg_backward_bf16x3.restype = _i
+    lib.moss_lpips_vgg_backward_bf16x3.argtypes = [_p, _p]
+    lib.moss_lpips_vgg_pack_weights_bf16x3.restype = _i
+    lib.moss_lpips_vgg_pack_weights_bf16x3.argtypes = [_i, _i, _p, _p, _p, _p]
+    lib.moss_lpips_vgg_conv3x3_bf16x3.restype = _i
+    lib.moss_lpips_vgg_conv3x3_bf16x3.argtypes = [_p, _p]
     lib.moss_photometric_loss_roi.restype = _i
     lib.moss_photometric_loss_roi.argtypes = [_i, _i, _i, _p, _p, _p, _p, _p, _p, _f, _f, _f, _p, _p, _p, _p, C.c_size_t, _p]
     lib.moss_adamw_flat_ex.restype = _i

@@ -21,6 +21,8 @@
 //     channels with the four waves splitting every K slice, their partial blocks summed in wave order through LDS.
 //   conv3x3_bf16_kernel -- the same convolution with both operands rounded to bf16 and float32 sums (v_mfma_f32_32x32x16_bf16), behind
 //     moss_lpips_vgg_forward_bf16 / _backward_bf16: an opt-in form of the TRAINING term.  Same shapes, modes and epilogue; see there.
+//   conv3x3_bf16x3_kernel -- the same convolution with each operand split into two bf16 and three products per product (about 16 bits
+//     of every operand), behind moss_lpips_vgg_forward_bf16x3 / _backward_bf16x3: between the two in cost and in accuracy; see there.
 //   conv_first_kernel / conv_first_backward_kernel -- conv 1_1 (Cin = 3, K = 27) and its adjoint on the VALU, with the z-score, the
 //     crop offset read from the device and the planar (3,H,W) layout of the public tensors.
 //   pool_kernel, tap_kernel, unpool_tap_kernel, reduce_kernel -- see each.
@@ -93,6 +95,21 @@ pack_weights_kernel(int cin, int cout, const float* __restrict__ w, T* __restric
     const T v = (T)w[idx];
     fwd[((size_t)o * 9 + tap) * cin + i] = v;
     bwd[((size_t)i * 9 + (8 - tap)) * cout + o] = v;
+}
+
+// the split packing: each array two planes of n = cout cin 9 values in the layouts above -- [0, n) hi = rne(w), what
+// pack_weights_kernel<__bf16> writes, and [n, 2n) lo = rne(w - hi)
+__global__ void __launch_bounds__(WG)
+pack_weights_split_kernel(int cin, int cout, const float* __restrict__ w, __bf16* __restrict__ fwd, __bf16* __restrict__ bwd)
+{
+    const int idx = blockIdx.x * WG + threadIdx.x, n = cout * cin * 9;
+    if (idx >= n) return;
+    const int tap = idx % 9, i = (idx / 9) % cin, o = idx / (9 * cin);
+    __bf16 hi, lo;
+    split_bf16(w[idx], hi, lo);
+    const size_t f = ((size_t)o * 9 + tap) * cin + i, b = ((size_t)i * 9 + (8 - tap)) * cout + o;
+    fwd[f] = hi; fwd[n + f] = lo;
+    bwd[b] = hi; bwd[n + b] = lo;
 }
 
 // ---- conv 1_1 --------------------------------------------------------------------------------------------------------------------------
@@ -479,6 +496,134 @@ conv3x3_bf16_kernel(const ConvArgs a)
     conv_epilogue<WK, MODE>(acc0, acc1, reinterpret_cast<float*>(s_ab), tid, wave, j, half, m0, n0, M, mask_rows, Cout, a.bias, a.out, a.mask_in, a.mask_out);
 }
 
+// ---- the wide convolutions, split-bf16 operands (three products) ---------------------------------------------------------------------
+// The same implicit GEMM with every float32 operand a carried as two bf16, hi(a) = rne(a) and lo(a) = rne(a - hi(a)) (split_bf16,
+// mfma_bf16.h), and every product a b replaced by
+//     lo(a) hi(b) + hi(a) lo(b) + hi(a) hi(b)
+// on v_mfma_f32_32x32x16_bf16: three exact bf16 x bf16 products summed in float32, lo(a) lo(b) dropped.  A single product is off by at
+// most 2^-15 |a b| (|a - hi - lo| <= 2^-17 |a| for either operand, the dropped product at most 2^-16 |a b|); the sums are held to
+// 2^-16 of mass = conv(|in|, |w|) + |bias| per element by the tests and measure 0.04-0.12 of it.  A lo below bf16's normal range
+// (|lo| < 2^-126) may be flushed by the matrix core: not part of the contract.  It equals ONE plain convolution over 3 Cin channels,
+// inputs [lo, hi, hi] against weights [hi, lo, hi].
+//   The activations (forward) and incoming gradients (backward) stay float32 in memory and are split by the staging thread on their
+// way into LDS; a.w is the split packing (pack_weights_split_kernel: a hi plane, which is the bf16 packing, and a lo plane of the same
+// layout Cout * 9 Cin values further on).  A slice is KCB channels of one tap in FOUR planes (A hi, A lo, B hi, B lo), rows of KCB + 8
+// bf16 as in conv3x3_bf16_kernel: the float32 kernel's bytes.  LDS holds ONE slice, with the f32 kernel's two barriers around its
+// refill: 55 296 bytes in the 128-row shape (two workgroups per CU), 52 224 / 27 648 in the 32-row shape with 128 / 64 channels.  A
+// second slice (one barrier) was measured in every shape and lost or changed nothing: it costs workgroups per CU, which hide more.
+//   The order, per k step of sixteen: small += lo(a) hi(b); acc += hi(a) hi(b); small += hi(a) lo(b) -- the two small terms in an
+// accumulator pair of their own, added to the large one element by element once, after the last slice.  Four independent chains
+// instead of two: the same MFMAs into ONE pair were 20 % slower at 256 x 176 (each waits for the one before it); the 32 registers
+// more cost no occupancy.  The 32-row shape asks for three waves per SIMD (it is launched when the grid is small, and its 180
+// registers would otherwise leave two).  Shapes, modes, DYN and the epilogue are conv3x3_bf16_kernel's.  profiles/lpips_notes.md.
+template <int WM, int WK, int KCB, int MODE, bool DYN>
+__global__ void __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(WK == 4 ? 3 : 2)))
+conv3x3_bf16x3_kernel(const ConvArgs a)
+{
+    static_assert(WM * WK == 4 && (WK == 1 || WM == 1), "four waves");
+    static_assert(KCB == 64 || KCB == 128, "a slice is 64 or 128 channels");
+    constexpr int BM = 32 * WM, LDB = KCB + 8;                                          // LDS row stride, in bf16
+    constexpr int A_LO = BM * LDB, B_HI = 2 * BM * LDB, B_LO = B_HI + BN * LDB, SLICE = 2 * (BM + BN) * LDB;   // the planes of a slice
+    constexpr int A_CPR = KCB / 4, A_RPP = WG / A_CPR, A_F4 = BM / A_RPP;               // A: float4 columns per row, rows per pass, passes
+    constexpr int B_CPR = KCB / 8, B_RPP = WG / B_CPR, B_V8 = BN / B_RPP;               // B: the same in 8-vectors of bf16, per plane
+    static_assert(KCB / 16 >= WK, "every wave has a k step in every slice");
+    __shared__ __attribute__((aligned(16))) __bf16 s_ab[SLICE];
+    static_assert(SLICE * sizeof(__bf16) >= 4 * 32 * 32 * sizeof(float), "s_ab doubles as the buffer of the four partial blocks");
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, half = lane >> 5;
+    const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
+    int H = a.H, W = a.W, M = a.M, mask_rows = a.mask_rows;
+    if (DYN) {
+        actual_size(a.dyn, H, W);
+        mask_rows = H * W;
+        M = a.nimg * mask_rows;
+        if (m0 >= M) return;                                             // (the whole workgroup, before its first barrier)
+    }
+    const int HW = H * W, Cin = a.Cin, Cout = a.Cout;
+    const int K9 = 9 * Cin, nchunks = K9 / KCB;
+    const float* __restrict__ in = a.in;
+
+    // what this thread stages: of A the rows ar + A_RPP i at float4 column ac, of B (both planes) the rows br + B_RPP i at 8-vector column bc
+    const int ac = tid % A_CPR, ar = tid / A_CPR, bc = tid % B_CPR, br = tid / B_CPR;
+    int rpix[A_F4], ryx[A_F4];
+#pragma unroll
+    for (int i = 0; i < A_F4; i++) {
+        const int m = m0 + ar + A_RPP * i;
+        rpix[i] = -1; ryx[i] = 0;
+        if (m < M) {
+            const int p = m % HW, y = p / W;
+            rpix[i] = m; ryx[i] = (y << 16) | (p - y * W);
+        }
+    }
+    const __bf16* whi = reinterpret_cast<const __bf16*>(a.w) + (size_t)(n0 + br) * K9 + 8 * bc;
+    const __bf16* wlo = whi + (size_t)Cout * K9;
+    f32x4 ra[A_F4];
+    bf16x8 rbh[B_V8], rbl[B_V8];
+    auto gload = [&](int kc) __attribute__((always_inline)) {
+        const int k0 = kc * KCB, tap = k0 / Cin, ci0 = k0 - tap * Cin, dy = tap / 3 - 1, dx = tap % 3 - 1;
+#pragma unroll
+        for (int i = 0; i < A_F4; i++) {
+            const int yy = (ryx[i] >> 16) + dy, xx = (ryx[i] & 0xffff) + dx;
+            const bool ok = rpix[i] >= 0 && yy >= 0 && yy < H && xx >= 0 && xx < W;
+            ra[i] = ok ? *reinterpret_cast<const f32x4*>(in + (size_t)(rpix[i] + dy * W + dx) * Cin + ci0 + 4 * ac)
+                       : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        }
+#pragma unroll
+        for (int i = 0; i < B_V8; i++) {
+            rbh[i] = *reinterpret_cast<const bf16x8*>(whi + (size_t)(B_RPP * i) * K9 + k0);
+            rbl[i] = *reinterpret_cast<const bf16x8*>(wlo + (size_t)(B_RPP * i) * K9 + k0);
+        }
+    };
+    auto sstore = [&]() __attribute__((always_inline)) {
+        __bf16* s = s_ab;
+#pragma unroll
+        for (int i = 0; i < A_F4; i++) {
+            bf16x4 hi, lo;
+            split_bf16x4(ra[i], hi, lo);
+            *reinterpret_cast<bf16x4*>(s + (ar + A_RPP * i) * LDB + 4 * ac) = hi;
+            *reinterpret_cast<bf16x4*>(s + A_LO + (ar + A_RPP * i) * LDB + 4 * ac) = lo;
+        }
+#pragma unroll
+        for (int i = 0; i < B_V8; i++) {
+            *reinterpret_cast<bf16x8*>(s + B_HI + (br + B_RPP * i) * LDB + 8 * bc) = rbh[i];
+            *reinterpret_cast<bf16x8*>(s + B_LO + (br + B_RPP * i) * LDB + 8 * bc) = rbl[i];
+        }
+    };
+
+    f32x16 acc0 = splat(0.0f), acc1 = splat(0.0f), small0 = splat(0.0f), small1 = splat(0.0f);
+    const int a_off = ((WK == 1 ? 32 * wave : 0) + j) * LDB + 8 * half, b_off = j * LDB + 8 * half;
+    gload(0);
+    sstore();
+    __syncthreads();
+    const __bf16* s = s_ab;
+    for (int kc = 0; kc < nchunks; kc++) {
+        const bool more = kc + 1 < nchunks;
+        if (more) gload(kc + 1);                                         // in flight during the MFMAs of this slice
+#pragma unroll
+        for (int step = (WK == 1 ? 0 : wave); step < KCB / 16; step += WK) {
+            const bf16x8 ah = *reinterpret_cast<const bf16x8*>(s + a_off + 16 * step);
+            const bf16x8 al = *reinterpret_cast<const bf16x8*>(s + A_LO + a_off + 16 * step);
+            const bf16x8 bh0 = *reinterpret_cast<const bf16x8*>(s + B_HI + b_off + 16 * step);
+            const bf16x8 bh1 = *reinterpret_cast<const bf16x8*>(s + B_HI + b_off + 32 * LDB + 16 * step);
+            const bf16x8 bl0 = *reinterpret_cast<const bf16x8*>(s + B_LO + b_off + 16 * step);
+            const bf16x8 bl1 = *reinterpret_cast<const bf16x8*>(s + B_LO + b_off + 32 * LDB + 16 * step);
+            mfma16(small0, al, bh0);
+            mfma16(small1, al, bh1);
+            mfma16(acc0, ah, bh0);
+            mfma16(acc1, ah, bh1);
+            mfma16(small0, ah, bl0);
+            mfma16(small1, ah, bl1);
+        }
+        __syncthreads();
+        if (more) {
+            sstore();
+            __syncthreads();
+        }
+    }
+    acc0 += small0;                                                      // (element by element: the small terms join the large one once)
+    acc1 += small1;
+    conv_epilogue<WK, MODE>(acc0, acc1, reinterpret_cast<float*>(s_ab), tid, wave, j, half, m0, n0, M, mask_rows, Cout, a.bias, a.out, a.mask_in, a.mask_out);
+}
+
 // ---- 2x2 max-pool, stride 2, floor ---------------------------------------------------------------------------------------------------
 // One thread per pooled row and 16 channels.  The winner (first maximum in the order (0,0) (0,1) (1,0) (1,1)), two bits per channel,
 // is kept for the first image when `win` is given: (pooled row, C / 16) words.
@@ -707,11 +852,29 @@ void launch_conv_bf16_as(const ConvArgs& a, int shape, hipStream_t s)
         hipLaunchKernelGGL((conv3x3_bf16_kernel<1, 4, 64, MODE, DYN>), dim3((a.M + 31) / 32, a.Cout / BN), dim3(WG), 0, s, a);
 }
 
-// bf16: a.w is the bf16 packing and the operands are rounded (conv3x3_bf16_kernel)
-template <int MODE>
-void launch_conv(const ConvArgs& a, bool bf16, hipStream_t s, int shape = SHAPE_AUTO)
+// the same choice of shape for the split-bf16 kernel, and the bf16 kernel's choice of slice: 64 channels in the 128-row shape, 128 in
+// the 32-row shape where Cin has them (two k steps per wave and barrier pair instead of one: 17 % faster at 256 x 176)
+template <int MODE, bool DYN>
+void launch_conv_bf16x3_as(const ConvArgs& a, int shape, hipStream_t s)
 {
-    if (bf16) {
+    if (rows128(a, shape))
+        hipLaunchKernelGGL((conv3x3_bf16x3_kernel<4, 1, 64, MODE, DYN>), dim3((a.M + 127) / 128, a.Cout / BN), dim3(WG), 0, s, a);
+    else if (a.Cin % 128 == 0)
+        hipLaunchKernelGGL((conv3x3_bf16x3_kernel<1, 4, 128, MODE, DYN>), dim3((a.M + 31) / 32, a.Cout / BN), dim3(WG), 0, s, a);
+    else
+        hipLaunchKernelGGL((conv3x3_bf16x3_kernel<1, 4, 64, MODE, DYN>), dim3((a.M + 31) / 32, a.Cout / BN), dim3(WG), 0, s, a);
+}
+
+// the operands of the wide convolutions.  PREC_BF16: a.w is the bf16 packing and the operands are rounded (conv3x3_bf16_kernel);
+// PREC_BF16X3: a.w is the split packing and every product is three (conv3x3_bf16x3_kernel)
+enum Precision { PREC_F32, PREC_BF16, PREC_BF16X3 };
+
+template <int MODE>
+void launch_conv(const ConvArgs& a, Precision prec, hipStream_t s, int shape = SHAPE_AUTO)
+{
+    if (prec == PREC_BF16X3) {
+        if (a.dyn.cap_H > 0) launch_conv_bf16x3_as<MODE, true>(a, shape, s); else launch_conv_bf16x3_as<MODE, false>(a, shape, s);
+    } else if (prec == PREC_BF16) {
         if (a.dyn.cap_H > 0) launch_conv_bf16_as<MODE, true>(a, shape, s); else launch_conv_bf16_as<MODE, false>(a, shape, s);
     } else {
         if (a.dyn.cap_H > 0) launch_conv_as<MODE, true>(a, shape, s); else launch_conv_as<MODE, false>(a, shape, s);
@@ -746,6 +909,15 @@ extern "C" int moss_lpips_vgg_pack_weights_bf16(int cin, int cout, const float* 
     return launch_status(me);
 }
 
+extern "C" int moss_lpips_vgg_pack_weights_bf16x3(int cin, int cout, const float* w, uint16_t* fwd, uint16_t* bwd, void* stream)
+{
+    const char* me = "moss_lpips_vgg_pack_weights_bf16x3";
+    if (cin <= 0 || cout <= 0 || !w || !fwd || !bwd) return invalid_arg(me, "sizes <= 0 or a null pointer");
+    hipLaunchKernelGGL(pack_weights_split_kernel, dim3(grid_for((long long)cin * cout * 9)), dim3(WG), 0, (hipStream_t)stream, cin, cout, w,
+                       reinterpret_cast<__bf16*>(fwd), reinterpret_cast<__bf16*>(bwd));
+    return launch_status(me);
+}
+
 // H, W: on return the size the launches and the regions of `saved` and `workspace` are made for -- the crop's, or the capacity's
 static const char* check_frame(int& H, int& W, int cap_H, int cap_W, const int* rect, int& FH, int& FW)
 {
@@ -766,8 +938,8 @@ static const char* check_frame(int& H, int& W, int cap_H, int cap_W, const int* 
 
 static const char* SHORT_WORKSPACE = "the workspace is null or smaller than moss_lpips_vgg_workspace_bytes(H, W) (of cap_H, cap_W with a capacity)";
 
-// LPIPS.forward, lpipsPyTorch/modules/lpips.py:31-37 (net_type='vgg').  bf16: weights[1..12] are the bf16 packing
-static int lpips_forward(const char* me, const moss_lpips_vgg_args* a, bool bf16, void* stream)
+// LPIPS.forward, lpipsPyTorch/modules/lpips.py:31-37 (net_type='vgg').  prec: weights[1..12] are that precision's packing
+static int lpips_forward(const char* me, const moss_lpips_vgg_args* a, Precision prec, void* stream)
 {
     if (!a) return invalid_arg(me, "null argument block");
     int FH = a->frame_H, FW = a->frame_W;
@@ -804,7 +976,7 @@ static int lpips_forward(const char* me, const moss_lpips_vgg_args* a, bool bf16
         c.in = cur; c.w = a->weights[i]; c.bias = a->biases[i]; c.out = nxt; c.mask_out = mask_at(i);
         c.M = 2 * HW; c.mask_rows = HW; c.H = g.H[l]; c.W = g.W[l]; c.Cin = CONV_COUT[i - 1]; c.Cout = CONV_COUT[i];
         c.dyn = dyn_at(l); c.nimg = 2;
-        launch_conv<MODE_FWD>(c, bf16, s);
+        launch_conv<MODE_FWD>(c, prec, s);
         std::swap(cur, nxt);
         if (i != TAP_CONV[tap]) continue;
         const int C = TAP_C[tap];
@@ -825,16 +997,21 @@ static int lpips_forward(const char* me, const moss_lpips_vgg_args* a, bool bf16
 
 extern "C" int moss_lpips_vgg_forward(const moss_lpips_vgg_args* a, void* stream)
 {
-    return lpips_forward("moss_lpips_vgg_forward", a, false, stream);
+    return lpips_forward("moss_lpips_vgg_forward", a, PREC_F32, stream);
 }
 
 extern "C" int moss_lpips_vgg_forward_bf16(const moss_lpips_vgg_args* a, void* stream)
 {
-    return lpips_forward("moss_lpips_vgg_forward_bf16", a, true, stream);
+    return lpips_forward("moss_lpips_vgg_forward_bf16", a, PREC_BF16, stream);
 }
 
-// the adjoint of LPIPS.forward (lpipsPyTorch/modules/lpips.py:31-37) w.r.t. x.  bf16: weights_bwd[1..12] are the bf16 packing
-static int lpips_backward(const char* me, const moss_lpips_vgg_backward_args* a, bool bf16, void* stream)
+extern "C" int moss_lpips_vgg_forward_bf16x3(const moss_lpips_vgg_args* a, void* stream)
+{
+    return lpips_forward("moss_lpips_vgg_forward_bf16x3", a, PREC_BF16X3, stream);
+}
+
+// the adjoint of LPIPS.forward (lpipsPyTorch/modules/lpips.py:31-37) w.r.t. x.  prec: weights_bwd[1..12] are that precision's packing
+static int lpips_backward(const char* me, const moss_lpips_vgg_backward_args* a, Precision prec, void* stream)
 {
     if (!a) return invalid_arg(me, "null argument block");
     int FH = a->frame_H, FW = a->frame_W;
@@ -868,7 +1045,7 @@ static int lpips_backward(const char* me, const moss_lpips_vgg_backward_args* a,
         c.in = cur; c.w = a->weights_bwd[i]; c.out = nxt; c.mask_in = pooled_below ? nullptr : mask_at(i - 1);
         c.M = g.H[l] * g.W[l]; c.H = g.H[l]; c.W = g.W[l]; c.Cin = CONV_COUT[i]; c.Cout = CONV_COUT[i - 1];
         c.dyn = dyn_at(l); c.nimg = 1;
-        if (pooled_below) launch_conv<MODE_BWD_PLAIN>(c, bf16, s); else launch_conv<MODE_BWD_MASK>(c, bf16, s);
+        if (pooled_below) launch_conv<MODE_BWD_PLAIN>(c, prec, s); else launch_conv<MODE_BWD_MASK>(c, prec, s);
         std::swap(cur, nxt);
         from_above = pooled_below ? cur : nullptr;
     }
@@ -879,22 +1056,31 @@ static int lpips_backward(const char* me, const moss_lpips_vgg_backward_args* a,
 
 extern "C" int moss_lpips_vgg_backward(const moss_lpips_vgg_backward_args* a, void* stream)
 {
-    return lpips_backward("moss_lpips_vgg_backward", a, false, stream);
+    return lpips_backward("moss_lpips_vgg_backward", a, PREC_F32, stream);
 }
 
 extern "C" int moss_lpips_vgg_backward_bf16(const moss_lpips_vgg_backward_args* a, void* stream)
 {
-    return lpips_backward("moss_lpips_vgg_backward_bf16", a, true, stream);
+    return lpips_backward("moss_lpips_vgg_backward_bf16", a, PREC_BF16, stream);
+}
+
+extern "C" int moss_lpips_vgg_backward_bf16x3(const moss_lpips_vgg_backward_args* a, void* stream)
+{
+    return lpips_backward("moss_lpips_vgg_backward_bf16x3", a, PREC_BF16X3, stream);
 }
 
 // ONE wide convolution, through launch_conv with the kernel shape the caller names: the product's own instantiations, a layer at a time
-extern "C" int moss_lpips_vgg_conv3x3(const moss_lpips_conv3x3_args* a, void* stream)
+// split: the call of moss_lpips_vgg_conv3x3_bf16x3 (weights are the split packing, the bf16 field must be 0)
+static int conv3x3_layer(const char* me, const moss_lpips_conv3x3_args* a, bool split, void* stream)
 {
-    const char* me = "moss_lpips_vgg_conv3x3";
     if (!a) return invalid_arg(me, "null argument block");
     if (a->mode < MODE_FWD || a->mode > MODE_BWD_PLAIN) return invalid_arg(me, "mode must be 0 (forward), 1 (data gradient, masked) or 2 (data gradient, plain)");
     if (a->shape < SHAPE_AUTO || a->shape > SHAPE_ROWS32) return invalid_arg(me, "shape must be 0 (the launcher's choice), 1 (128 rows) or 2 (32 rows, split K)");
-    if (a->bf16 != 0 && a->bf16 != 1) return invalid_arg(me, "bf16 must be 0 or 1");
+    if (split) {
+        if (a->bf16 != 0) return invalid_arg(me, "bf16 must be 0: the split-bf16 convolution has an entry point of its own");
+    } else if (a->bf16 != 0 && a->bf16 != 1) {
+        return invalid_arg(me, "bf16 must be 0 or 1");
+    }
     if (a->nimg < 1 || a->nimg > 2) return invalid_arg(me, "nimg must be 1 or 2");
     if (a->cin < 64 || a->cout < 64 || a->cin % 64 || a->cout % 64) return invalid_arg(me, "cin and cout must be positive multiples of 64");
     if (!a->in || !a->weights || !a->out) return invalid_arg(me, "null in, weights or out");
@@ -920,8 +1106,19 @@ extern "C" int moss_lpips_vgg_conv3x3(const moss_lpips_conv3x3_args* a, void* st
     c.M = a->nimg * H * W; c.mask_rows = H * W; c.H = H; c.W = W; c.Cin = a->cin; c.Cout = a->cout;
     c.dyn = Dyn{a->rect, a->cap_H, a->cap_W, level}; c.nimg = a->nimg;
     hipStream_t s = (hipStream_t)stream;
-    if (a->mode == MODE_FWD) launch_conv<MODE_FWD>(c, a->bf16 != 0, s, a->shape);
-    else if (a->mode == MODE_BWD_MASK) launch_conv<MODE_BWD_MASK>(c, a->bf16 != 0, s, a->shape);
-    else launch_conv<MODE_BWD_PLAIN>(c, a->bf16 != 0, s, a->shape);
+    const Precision prec = split ? PREC_BF16X3 : a->bf16 ? PREC_BF16 : PREC_F32;
+    if (a->mode == MODE_FWD) launch_conv<MODE_FWD>(c, prec, s, a->shape);
+    else if (a->mode == MODE_BWD_MASK) launch_conv<MODE_BWD_MASK>(c, prec, s, a->shape);
+    else launch_conv<MODE_BWD_PLAIN>(c, prec, s, a->shape);
     return launch_status(me);
+}
+
+extern "C" int moss_lpips_vgg_conv3x3(const moss_lpips_conv3x3_args* a, void* stream)
+{
+    return conv3x3_layer("moss_lpips_vgg_conv3x3", a, false, stream);
+}
+
+extern "C" int moss_lpips_vgg_conv3x3_bf16x3(const moss_lpips_conv3x3_args* a, void* stream)
+{
+    return conv3x3_layer("moss_lpips_vgg_conv3x3_bf16x3", a, true, stream);
 }

@@ -17,6 +17,22 @@ __device__ __forceinline__ bf16x4 to_bf16x4(const V& v)
     return bf16x4{(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w};
 }
 
+// a float32 as two bf16: hi = rne(a), lo = rne(a - hi).  The subtraction is exact in float32 (hi is a's leading 8 bits), so hi + lo
+// carries about 16 bits of a: |lo| <= 2^-8 |a| and |a - hi - lo| <= 2^-17 |a|.  (A lo below bf16's normal range may be flushed by the
+// matrix core.)
+__device__ __forceinline__ void split_bf16(float a, __bf16& hi, __bf16& lo)
+{
+    hi = (__bf16)a;
+    lo = (__bf16)(a - (float)hi);
+}
+
+template <typename V>
+__device__ __forceinline__ void split_bf16x4(const V& v, bf16x4& hi, bf16x4& lo)
+{
+    hi = to_bf16x4(v);
+    lo = bf16x4{(__bf16)(v.x - (float)hi.x), (__bf16)(v.y - (float)hi.y), (__bf16)(v.z - (float)hi.z), (__bf16)(v.w - (float)hi.w)};
+}
+
 // acc += A B over the wave's sixteen k of this step
 __device__ __forceinline__ void mfma16(f32x16& acc, const bf16x8& av, const bf16x8& bv)
 {

@@ -12,7 +12,8 @@ through a non-trainable 1x1 convolution to one channel and a spatial mean; the f
   backward reads sign masks, pool winners and the tap gradients the forward left, never a layer input.  No host read, no atomics,
   bitwise reproducible, capturable.
   ``LpipsVGG(..., precision="bf16")`` is the opt-in mixed-precision form of the TRAINING term (``moss_lpips_vgg_forward_bf16`` /
-  ``_backward_bf16``): see :class:`LpipsVGG`.  The net carries the choice; the ops take no argument for it.
+  ``_backward_bf16``), ``precision="bf16x3"`` the split-bf16 (three-product) form between the two (``..._bf16x3``): see
+  :class:`LpipsVGG`.  The net carries the choice; the ops take no argument for it.
 * :func:`lpips_vgg_roi_fused` -- the same on the ``ViewRegion`` rectangle of two full frames (no crop copies; the offset is read on the
   device, and with ``capacity=`` the crop's size too: one capture serves views whose crops differ in size).
   :func:`crop_capacity` -- the capacity of a dataset's views.
@@ -31,7 +32,7 @@ import hashlib
 import torch
 
 __all__ = ["LpipsVGG", "lpips_vgg_fused", "lpips_vgg_roi_fused", "crop_capacity", "lpips_vgg_torch", "synthetic_weights", "weights_sha256",
-           "PRECISIONS", "CONV_SHAPES", "TAP_CHANNELS", "TAP_AFTER_CONV", "POOL_AFTER_CONV", "SHIFT", "SCALE", "MIN_SIZE"]
+           "PRECISIONS", "ALL_PRECISIONS", "CONV_SHAPES", "TAP_CHANNELS", "TAP_AFTER_CONV", "POOL_AFTER_CONV", "SHIFT", "SCALE", "MIN_SIZE"]
 
 _WIDTHS = (64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512)
 CONV_SHAPES = tuple((co, ci, 3, 3) for ci, co in zip((3,) + _WIDTHS[:-1], _WIDTHS))
@@ -42,8 +43,9 @@ SHIFT = (-0.030, -0.088, -0.188)                          # BaseNet.mean (lpipsP
 SCALE = (0.458, 0.448, 0.450)                             # BaseNet.std
 MIN_SIZE = 16                                             # four pools: the last tap is at least 1x1
 EPS = 1e-10                                               # normalize_activation (lpipsPyTorch/modules/utils.py:5-7)
-PRECISIONS = ("f32", "bf16")                              # LpipsVGG(precision=): the operands of the twelve wide convolutions
-_SUFFIX = {"f32": "", "bf16": "_bf16"}                    # of the C entry points
+PRECISIONS = ("f32", "bf16")                              # LpipsVGG(precision=): the operands of the twelve wide convolutions ...
+ALL_PRECISIONS = PRECISIONS + ("bf16x3",)                 # ... and the split-bf16 (three-product) form
+_SUFFIX = {"f32": "", "bf16": "_bf16", "bf16x3": "_bf16x3"}                          # of the C entry points
 
 
 # ---- the torch form ---------------------------------------------------------------------------------------------------------------
@@ -69,7 +71,37 @@ class _RoundedOperandConv(torch.autograd.Function):
         return torch.nn.grad.conv2d_input(ctx.shape, wr, g.to(ctx.dtype).to(g.dtype), padding=1), None, None, None
 
 
-def lpips_vgg_torch(params, x, y, return_terms=False, operand_dtype=None):
+def split_operand(t, dtype):
+    """``(hi, lo)`` of ``t`` in ``t``'s own dtype: ``hi = round(t)`` to ``dtype`` and ``lo = round(t - hi)``.  For float32 ``t`` the
+    subtraction is exact; ``hi + lo`` carries about twice ``dtype``'s bits of ``t``."""
+    hi = t.to(dtype).to(t.dtype)
+    return hi, (t - hi).to(dtype).to(t.dtype)
+
+
+class _SplitOperandConv(torch.autograd.Function):
+    """``conv2d(h, w, b, padding=1)`` with every product ``a b`` replaced by ``lo(a) hi(b) + hi(a) lo(b) + hi(a) hi(b)``
+    (:func:`split_operand`; ``lo(a) lo(b)`` is dropped), in the forward AND in the data gradient: the backward splits the incoming
+    gradient and convolves its parts with the split weight.  Three convolutions each way, summed small terms first; the sums are in the
+    tensors' own dtype; the weight and the bias get no gradient (they are frozen)."""
+
+    @staticmethod
+    def forward(ctx, h, w, b, dtype):
+        import torch.nn.functional as F
+        wh, wl = split_operand(w, dtype)
+        hh, hl = split_operand(h, dtype)
+        ctx.save_for_backward(wh, wl)
+        ctx.dtype, ctx.shape = dtype, h.shape
+        return (F.conv2d(hl, wh, None, padding=1) + F.conv2d(hh, wl, None, padding=1)) + F.conv2d(hh, wh, b, padding=1)
+
+    @staticmethod
+    def backward(ctx, g):
+        wh, wl = ctx.saved_tensors
+        gh, gl = split_operand(g, ctx.dtype)
+        gin = torch.nn.grad.conv2d_input
+        return (gin(ctx.shape, wh, gl, padding=1) + gin(ctx.shape, wl, gh, padding=1)) + gin(ctx.shape, wh, gh, padding=1), None, None, None
+
+
+def lpips_vgg_torch(params, x, y, return_terms=False, operand_dtype=None, operand_split=False):
     """``LPIPS.forward(x, y)`` for ``net_type='vgg'`` in plain torch.  ``params``: a mapping with ``conv_weights`` (13 tensors
     (Cout,Cin,3,3)), ``conv_biases`` (13), ``lin_weights`` (5 tensors of C, any shape), ``shift`` and ``scale`` (3 each), all of the
     images' dtype and device; ``x``, ``y`` (3,H,W) or (1,3,H,W).  Returns (1,1,1,1); with ``return_terms`` also the five per-tap
@@ -78,8 +110,16 @@ def lpips_vgg_torch(params, x, y, return_terms=False, operand_dtype=None):
     ``operand_dtype=torch.bfloat16``: the arithmetic of ``LpipsVGG(precision="bf16")`` -- in convolutions 2..13 the input, the weight
     and (in the backward) the incoming gradient are rounded to bf16 before they are multiplied; the sums, conv 1_1 and everything else
     stay in the tensors' dtype.  In float64 this is the exact statement of what the bf16 kernels compute.  ``None``: nothing is
-    rounded."""
+    rounded.
+
+    ``operand_split=True`` (with ``operand_dtype=torch.bfloat16``): the arithmetic of ``LpipsVGG(precision="bf16x3")`` -- those operands
+    are not rounded but SPLIT, ``hi = bf16(a)``, ``lo = bf16(a - hi)``, and every product is ``lo(a) hi(b) + hi(a) lo(b) + hi(a) hi(b)``
+    (``_SplitOperandConv``).  In float64 the exact statement of what the split kernels compute.  ``False`` (the default): the function
+    is what it was."""
     import torch.nn.functional as F
+    if operand_split and operand_dtype is None:
+        raise ValueError("lpips_vgg_torch: operand_split needs operand_dtype (the dtype of the two halves)")
+    conv_op = _SplitOperandConv if operand_split else _RoundedOperandConv
     shift = params["shift"].reshape(1, 3, 1, 1)
     scale = params["scale"].reshape(1, 3, 1, 1)
 
@@ -90,7 +130,7 @@ def lpips_vgg_torch(params, x, y, return_terms=False, operand_dtype=None):
             if operand_dtype is None or i == 0:
                 h = torch.relu(F.conv2d(h, w, b, padding=1))
             else:
-                h = torch.relu(_RoundedOperandConv.apply(h, w, b, operand_dtype))
+                h = torch.relu(conv_op.apply(h, w, b, operand_dtype))
             if i in TAP_AFTER_CONV:
                 taps.append(h / (torch.sqrt(torch.sum(h ** 2, dim=1, keepdim=True)) + EPS))
             if i in POOL_AFTER_CONV:
@@ -159,11 +199,23 @@ class LpipsVGG:
     L2 / gradient cosine, and plain float32's gradient relative L2 beside it: uniform noise 37x53 3.8e-4 / 0.058 / 0.9983 (float32:
     1e-6); a person-like crop 101x77 1.1e-2 / 0.23 / 0.974 (0.056); 256x176 1.1e-2 / 0.27 / 0.964 (0.090).  On a person-shaped crop
     float32 itself is 6-9 % from float64 in the gradient (ReLU and pool decisions on the near-black ground flip); bf16 is about three
-    times that.  Use it for the training term (weighted 0.5 in MOSS's loss), not for a reported number."""
+    times that.  Use it for the training term (weighted 0.5 in MOSS's loss), not for a reported number.
+
+    ``precision="bf16x3"``: the middle -- in the same convolutions every float32 operand ``a`` is SPLIT into two bf16, ``hi = bf16(a)`` and
+    ``lo = bf16(a - hi)`` (about 16 bits of ``a``), and every product is ``lo(a) hi(b) + hi(a) lo(b) + hi(a) hi(b)``: three exact
+    bf16 products summed in float32, ``lo lo`` dropped (the weights are split once, here: ``w_fwd[1:]`` / ``w_bwd[1:]`` are
+    ``torch.bfloat16`` of TWICE the elements, a hi plane -- the bf16 net's array bit for bit -- then a lo plane; the activations and
+    incoming gradients are split as the kernel stages them).  It is ``lpips_vgg_torch(..., operand_dtype=torch.bfloat16,
+    operand_split=True)`` to float32 summation order, bitwise reproducible, and 1.7-1.8x faster than float32 (256x176: 1.20 against
+    2.13 ms forward + backward, bf16 1.02; 512x352: 2.64 against 4.66, bf16 2.08).  The same CPU emulation against exact float64, SYNTHETIC
+    weights (``synthetic_weights(0)``) -- value relative / gradient relative L2 / gradient cosine, float32's gradient relative L2
+    beside it: uniform noise 37x53 6.4e-7 / 3.7e-5 / 1.000000 (float32: 2e-6); a person-like crop 101x77 9.3e-6 / 0.074 / 0.9973
+    (0.057); 256x176 3.2e-6 / 0.107 / 0.9942 (0.090).  The value error is a thousand times smaller than bf16's, and on person crops
+    the gradient is 1.2-1.3 times float32's own distance from float64 where bf16 is three to four times it.  Still a training term: ``evaluate_views`` takes float32 only."""
 
     def __init__(self, conv_weights, conv_biases, lin_weights, shift, scale, precision="f32"):
-        if precision not in PRECISIONS:
-            raise ValueError(f"LpipsVGG: precision must be one of {PRECISIONS}, got {precision!r}")
+        if precision not in ALL_PRECISIONS:
+            raise ValueError(f"LpipsVGG: precision must be one of {ALL_PRECISIONS}, got {precision!r}")
         self.precision = precision
         self._src = (list(conv_weights), list(conv_biases), list(lin_weights), shift, scale)
         cw, cb, lw = self._src[:3]
@@ -237,11 +289,11 @@ class LpipsVGG:
         for i, w in enumerate(cw):
             w = f32(w)
             co, ci = int(w.shape[0]), int(w.shape[1])
-            bf16 = self.precision == "bf16" and i > 0                                # (conv 1_1 stays float32 on the VALU)
-            fwd = torch.empty(w.numel(), dtype=torch.bfloat16 if bf16 else torch.float32, device=self.device)
+            prec = self.precision if i > 0 else "f32"                                # (conv 1_1 stays float32 on the VALU)
+            planes = 2 if prec == "bf16x3" else 1                                    # (split: a hi plane, then a lo plane)
+            fwd = torch.empty(planes * w.numel(), dtype=torch.float32 if prec == "f32" else torch.bfloat16, device=self.device)
             bwd = torch.empty_like(fwd)
-            call("moss_lpips_vgg_pack_weights_bf16" if bf16 else "moss_lpips_vgg_pack_weights", self.device, ci, co, w.data_ptr(),
-                 fwd.data_ptr(), bwd.data_ptr())
+            call("moss_lpips_vgg_pack_weights" + _SUFFIX[prec], self.device, ci, co, w.data_ptr(), fwd.data_ptr(), bwd.data_ptr())
             self.w_fwd.append(fwd)
             self.w_bwd.append(bwd)
         return self

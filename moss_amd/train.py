@@ -51,7 +51,8 @@ class MossStep:
     ``lpips_net``: an ``lpips.LpipsVGG``; the net carries the precision of the term -- ``LpipsVGG(..., precision="bf16")`` runs the
     twelve wide convolutions with bf16 operands and float32 sums (the step at P = 45 695: 3.55 against 4.68 ms; the term moves by about
     1 % and its gradient by about 0.2 relative L2 on a person-like crop with synthetic weights, three times what float32 itself is from
-    float64 there -- a training term, never the reported metric: ``lpips.py``, profiles/lpips_notes.md).  ALL of them are static inputs: the caller changes frame between steps by ``copy_`` into
+    float64 there -- a training term, never the reported metric: ``lpips.py``, profiles/lpips_notes.md; ``precision="bf16x3"``, the
+    split-bf16 form, sits between the two: 3.73 ms, the term within 1e-5 of float64's).  ALL of them are static inputs: the caller changes frame between steps by ``copy_`` into
     these tensors and ``region.copy_``.
 
     ``lpips_capacity``: ``(cap_h, cap_w)`` -- ``lpips.crop_capacity`` of the dataset's regions -- or ``"frame"``; it goes to

@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
-"""Times the LPIPS term's bf16-operand mode (``LpipsVGG(precision="bf16")``; ``moss_lpips_vgg_forward_bf16`` / ``_backward_bf16``) against
-the float32 call, by the interleaved-graphs method of scripts/lpips_dynamic_times.py: per size and per call (forward alone, keeping
-nothing; forward + backward), every variant is the pair of C entry points captured in a hipGraph of its own,
+"""Times the LPIPS term's bf16-operand mode (``LpipsVGG(precision="bf16")``; ``moss_lpips_vgg_forward_bf16`` / ``_backward_bf16``) and its
+split-bf16 mode (``precision="bf16x3"``; ``moss_lpips_vgg_forward_bf16x3`` / ``_backward_bf16x3``) against the float32 call, by the
+interleaved-graphs method of scripts/lpips_dynamic_times.py: per size and per call (forward alone, keeping nothing; forward +
+backward), every variant is the pair of C entry points captured in a hipGraph of its own,
 
     f32             the float32 call of this build
     f32 again       the same once more, a second graph with buffers of its own: the control -- what two captures of ONE code differ by
     f32 other       ``--other-lib``: the float32 call of ANOTHER build of libmoss_raster.so (the parent commit's: has the float32 path moved?)
     bf16            the bf16-operand call
+    bf16x3          the split-bf16 (three-product) call
 
 all in one process: a round replays every variant's graph ``--inner`` times between two device events, in an order that rotates from
 round to round; the first three rounds are discarded.  Reported per variant: the median, the minimum and the 10th / 90th percentile of
@@ -36,7 +38,8 @@ class PrecisionVariant(Variant):
 
     def __init__(self, name, lib, net, image, gt, rect, size, backward):
         super().__init__(name, lib, net, image, gt, rect, size, size, None)
-        suffix = "_bf16" if net.precision == "bf16" else ""
+        from moss_amd.lpips import _SUFFIX
+        suffix = _SUFFIX[net.precision]
         self.calls = [(getattr(lib, "moss_lpips_vgg_forward" + suffix), self.a)]
         if backward:
             self.calls.append((getattr(lib, "moss_lpips_vgg_backward" + suffix), self.b))
@@ -95,7 +98,7 @@ def main():
     dev = torch.device("cuda:0")
     params = mlp.cast_params(mlp.synthetic_weights(1), device=dev)
     nets = {p: mlp.LpipsVGG.from_tensors(params["conv_weights"], params["conv_biases"], params["lin_weights"], params["shift"], params["scale"],
-                                         precision=p) for p in mlp.PRECISIONS}
+                                         precision=p) for p in mlp.ALL_PRECISIONS}
     other = load_other(args.other_lib) if args.other_lib else None
     out = {}
     for size in (pair(s) for s in args.sizes.split(",")):
@@ -109,28 +112,29 @@ def main():
             variants = [PrecisionVariant(n, lib(), nets["f32"], image, gt, rect, size, backward) for n in ("f32", "f32 again")]
             if other is not None:
                 variants.append(PrecisionVariant("f32 other", other, nets["f32"], image, gt, rect, size, backward))
-            variants.append(PrecisionVariant("bf16", lib(), nets["bf16"], image, gt, rect, size, backward))
+            reduced = [PrecisionVariant(p, lib(), nets[p], image, gt, rect, size, backward) for p in mlp.ALL_PRECISIONS[1:]]
+            variants += reduced
             for v in variants:
                 v.capture()
                 for _ in range(3):
                     v.graph.replay()
             torch.cuda.synchronize(dev)
             base = variants[0]
-            for v in variants[1:-1]:
+            for v in variants[1:-len(reduced)]:
                 same = torch.equal(v.out, base.out) and (not backward or torch.equal(v.d_x, base.d_x))
                 print(f"{h}x{w} {what}: {v.name} is {'bit-identical to' if same else 'DIFFERENT from'} f32", flush=True)
-            b = variants[-1]
-            rel = abs(float(b.out[0]) - float(base.out[0])) / float(base.out[0])
-            grel = float((b.d_x - base.d_x).norm() / base.d_x.norm()) if backward else float("nan")
-            print(f"{h}x{w} {what}: bf16 value {float(b.out[0]):.8g} against f32 {float(base.out[0]):.8g} (relative {rel:.3g}), gradient relative L2 "
-                  f"difference {grel:.3g}", flush=True)
+            for b in reduced:
+                rel = abs(float(b.out[0]) - float(base.out[0])) / float(base.out[0])
+                grel = float((b.d_x - base.d_x).norm() / base.d_x.norm()) if backward else float("nan")
+                print(f"{h}x{w} {what}: {b.name} value {float(b.out[0]):.8g} against f32 {float(base.out[0]):.8g} (relative {rel:.3g}), gradient "
+                      f"relative L2 difference {grel:.3g}", flush=True)
             res = out[f"{h}x{w} {what}"] = measure(variants, args.rounds, args.inner)
             print(f"{h}x{w} {what} from a graph, {args.rounds} rounds x {args.inner} replays, us per call")
             for v in variants:
                 s = res[v.name]
                 print(f"  {v.name:10s} median {s['median_us']:9.1f}  min {s['min_us']:9.1f}  p10..p90 {s['p10_us']:9.1f} .. {s['p90_us']:9.1f}   "
                       f"/ f32 {s['ratio_median']:.4f} ({s['ratio_p10']:.4f} .. {s['ratio_p90']:.4f})", flush=True)
-            del variants, base, b
+            del variants, reduced, base, b
     if args.json:
         with open(args.json, "w") as fh:
             json.dump({"rounds": args.rounds, "inner": args.inner, "results": out}, fh, indent=1)

@@ -11,7 +11,7 @@ SH degree 3, synthetic LPIPS weights, a 192 x 256 region:
     profile    ``rocprofv3 --kernel-trace --stats`` over the captured step at the larger size; the per-kernel table is printed
 
     python scripts/moss_step_times.py [--replays 300] [--sizes 6890,45695] [--only captured,baseline,profile] [--out DIR]
-                                      [--lpips-precision f32|bf16]
+                                      [--lpips-precision f32|bf16|bf16x3]
 
 Every measurement is a process of its own under ``timeout -k 10``; the script stops at the first one that does not exit with 0.  A time
 is the wall clock around ``replays`` back-to-back steps between two device synchronisations, after a warm-up.  Needs a GPU.
@@ -185,7 +185,7 @@ def main():
     ap.add_argument("--sizes", default="6890,45695")
     ap.add_argument("--only", default="captured,baseline,profile")
     ap.add_argument("--out", default="moss_step_times_out")
-    ap.add_argument("--lpips-precision", default="f32", choices=("f32", "bf16"), help="the LPIPS net's operand precision (LpipsVGG(precision=))")
+    ap.add_argument("--lpips-precision", default="f32", choices=("f32", "bf16", "bf16x3"), help="the LPIPS net's operand precision (LpipsVGG(precision=))")
     ap.add_argument("--package-root", default=os.path.dirname(HERE), help="the checkout whose moss_amd is measured")
     ap.add_argument("--worker", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--P", type=int, default=0, help=argparse.SUPPRESS)
