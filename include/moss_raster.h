@@ -857,6 +857,77 @@ int moss_lpips_vgg_pack_weights_bf16x3(int cin, int cout, const float* w, uint16
 int moss_lpips_vgg_conv3x3_bf16x3(const moss_lpips_conv3x3_args* args, void* stream);
 
 /*
+ * The ground truth's half of the term, computed ONCE (additive in ABI 7).  y is fixed per camera -- viewpoint_cam.original_image
+ * cropped to its bound_mask's rectangle, train_ZJU.py:108-121 -- yet both calls above run VGG16 on it every time.  A REFERENCE is what
+ * y contributes, kept by the caller and accepted in y's place:
+ *   moss_lpips_vgg_reference{,_bf16,_bf16x3}: the forward on y ALONE (one image, M = H W rows) -- feat_y = self.net(y),
+ *     lpipsPyTorch/modules/lpips.py:32, second half -- with no sign masks, pool winners or tap gradients.  It leaves the tapped
+ *     activations in `reference`.
+ *   moss_lpips_vgg_forward_ref{,_bf16,_bf16x3}: lpipsPyTorch/modules/lpips.py:31-37 on x ALONE with feat_y read from `reference`; out,
+ *     terms and `saved` are those of moss_lpips_vgg_forward, in its layout, and moss_lpips_vgg_backward{,_bf16,_bf16x3} of the same
+ *     precision takes that `saved` unchanged.
+ * THE BLOCK: moss_lpips_vgg_reference_bytes(H, W) bytes (0 for a size the calls refuse), five regions in tap order -- the RAW
+ * activations after ReLU 1_2, 2_2, 3_3, 4_3, 5_3 (the normalisation of lpips.py:34 is done by the tap, by the float32 operations
+ * the two-image call uses) -- region l at the sum of the sizes before it, each (H >> l) * (W >> l) * C_l * 4 bytes rounded up to 256,
+ * C = 64, 128, 256, 512, 512; inside a region row y * W_l + x, C_l floats, channels-last.  That is 122 floats per crop pixel: 22 MB at
+ * 256 x 176.  With a capacity the regions are laid out for cap_H x cap_W and the rows are compact at the ACTUAL size, as in `saved`; a
+ * block may be copied (all its bytes) into another of the same capacity.  A block is valid for ONE (weights, precision, crop size or
+ * capacity): in the bf16 modes y's activations are what that mode's kernels compute for y.
+ *   y / x: (3,frame_H,frame_W); H, W, frame_H, frame_W, rect, cap_H, cap_W, weights, biases, lin, shift, scale, out, terms, saved,
+ *   workspace: as in moss_lpips_vgg_args (the crop of y starts where the two-image call's does: rect's corner, moved so that the crop
+ *   fits).  workspace: moss_lpips_vgg_workspace_bytes, the two-image call's.
+ * THE SAME RESULT: per row the convolution does not know how many images the batch holds; what can differ is the kernel shape, picked
+ * from the row count, which is H W here and 2 H W in the two-image call.  out, terms, `saved` and so the gradient are BIT-IDENTICAL to
+ * the two-image call of the same inputs and capacity whenever every wide layer gets the same shape at M = H W as at M = 2 H W: on a
+ * device with more than 122 CUs, for every crop or capacity up to 101 x 77 (all layers take the 32-row shape either way).  Otherwise
+ * the two agree to float32 summation order and are as close to float64 as each other.
+ * No host synchronisation, no allocation: capturable; bitwise reproducible.  Refused with MOSS_ERR_INVALID_ARG before any launch, the
+ * field named in moss_last_error(): a NULL block, y / x, out, shift, scale, weight, bias or lin; a `reference` that is NULL or shorter
+ * than moss_lpips_vgg_reference_bytes; a short workspace; a capacity without rect; every size the two-image call refuses.
+ */
+typedef struct moss_lpips_vgg_reference_args {
+    const float* y;                          /* (3,frame_H,frame_W): the ground truth */
+    int32_t H, W;
+    int32_t frame_H, frame_W;
+    const int* rect;
+    const float* weights[MOSS_LPIPS_VGG_CONVS]; /* the precision's `fwd` packing, as in moss_lpips_vgg_args */
+    const float* biases[MOSS_LPIPS_VGG_CONVS];
+    const float* shift;
+    const float* scale;
+    char* reference;                         /* written: moss_lpips_vgg_reference_bytes(H, W) (of cap_H, cap_W with a capacity) */
+    size_t reference_bytes;
+    char* workspace;
+    size_t workspace_bytes;
+    int32_t cap_H, cap_W;
+} moss_lpips_vgg_reference_args;
+typedef struct moss_lpips_vgg_forward_ref_args {
+    const float* x;                          /* (3,frame_H,frame_W) */
+    const char* reference;                   /* as moss_lpips_vgg_reference of this precision, weights and size / capacity wrote it */
+    size_t reference_bytes;
+    int32_t H, W;
+    int32_t frame_H, frame_W;
+    const int* rect;
+    const float* weights[MOSS_LPIPS_VGG_CONVS];
+    const float* biases[MOSS_LPIPS_VGG_CONVS];
+    const float* lin[MOSS_LPIPS_VGG_TAPS];
+    const float* shift;
+    const float* scale;
+    float* out;
+    float* terms;                            /* 5 floats, or NULL */
+    char* saved;                             /* moss_lpips_vgg_saved_bytes, or NULL */
+    char* workspace;
+    size_t workspace_bytes;
+    int32_t cap_H, cap_W;
+} moss_lpips_vgg_forward_ref_args;
+size_t moss_lpips_vgg_reference_bytes(int H, int W);
+int moss_lpips_vgg_reference(const moss_lpips_vgg_reference_args* args, void* stream);          /* lpipsPyTorch/modules/lpips.py:32, y's half */
+int moss_lpips_vgg_reference_bf16(const moss_lpips_vgg_reference_args* args, void* stream);
+int moss_lpips_vgg_reference_bf16x3(const moss_lpips_vgg_reference_args* args, void* stream);
+int moss_lpips_vgg_forward_ref(const moss_lpips_vgg_forward_ref_args* args, void* stream);      /* lpipsPyTorch/modules/lpips.py:31-37 */
+int moss_lpips_vgg_forward_ref_bf16(const moss_lpips_vgg_forward_ref_args* args, void* stream);
+int moss_lpips_vgg_forward_ref_bf16x3(const moss_lpips_vgg_forward_ref_args* args, void* stream);
+
+/*
  * k nearest reference points of every query point, 3-D, exact, k = 1..4: replaces the third-party
  * `knn_cuda.KNN(k, transpose_mode=True)(ref, query)` MOSS calls at scene/gaussian_model.py:85-86,586,657,759,827 (a CUDA-only
  * binary wheel, not in the repository; parity unpinned by the reference).

@@ -151,6 +151,13 @@ def _declare(lib):
     lib.moss_lpips_vgg_pack_weights_bf16x3.argtypes = [_i, _i, _p, _p, _p, _p]
     lib.moss_lpips_vgg_conv3x3_bf16x3.restype = _i
     lib.moss_lpips_vgg_conv3x3_bf16x3.argtypes = [_p, _p]
+    lib.moss_lpips_vgg_reference_bytes.restype = C.c_size_t
+    lib.moss_lpips_vgg_reference_bytes.argtypes = [_i, _i]
+    for suffix in ("", "_bf16", "_bf16x3"):
+        for name in ("moss_lpips_vgg_reference", "moss_lpips_vgg_forward_ref"):
+            fn = getattr(lib, name + suffix)
+            fn.restype = _i
+            fn.argtypes = [_p, _p]
     lib.moss_photometric_loss_roi.restype = _i
     lib.moss_photometric_loss_roi.argtypes = [_i, _i, _i, _p, _p, _p, _p, _p, _p, _f, _f, _f, _p, _p, _p, _p, C.c_size_t, _p]
     lib.moss_adamw_flat_ex.restype = _i
@@ -282,6 +289,25 @@ class LpipsVggBackwardArgs(C.Structure):
                 ("weights_bwd", C.c_void_p * 13), ("scale", C.c_void_p), ("saved", C.c_void_p), ("g_out", C.c_void_p),
                 ("dL_dx", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("cap_H", C.c_int32),
                 ("cap_W", C.c_int32)]
+
+
+class LpipsVggReferenceArgs(C.Structure):
+    """``moss_lpips_vgg_reference_args`` of include/moss_raster.h (``moss_lpips_vgg_reference``: the ground truth's tapped activations,
+    once)."""
+    _fields_ = [("y", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32), ("frame_H", C.c_int32), ("frame_W", C.c_int32),
+                ("rect", C.c_void_p), ("weights", C.c_void_p * 13), ("biases", C.c_void_p * 13), ("shift", C.c_void_p),
+                ("scale", C.c_void_p), ("reference", C.c_void_p), ("reference_bytes", C.c_size_t), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_size_t), ("cap_H", C.c_int32), ("cap_W", C.c_int32)]
+
+
+class LpipsVggForwardRefArgs(C.Structure):
+    """``moss_lpips_vgg_forward_ref_args`` of include/moss_raster.h (``moss_lpips_vgg_forward_ref``: the forward on x alone against a
+    reference)."""
+    _fields_ = [("x", C.c_void_p), ("reference", C.c_void_p), ("reference_bytes", C.c_size_t), ("H", C.c_int32), ("W", C.c_int32),
+                ("frame_H", C.c_int32), ("frame_W", C.c_int32), ("rect", C.c_void_p), ("weights", C.c_void_p * 13),
+                ("biases", C.c_void_p * 13), ("lin", C.c_void_p * 5), ("shift", C.c_void_p), ("scale", C.c_void_p), ("out", C.c_void_p),
+                ("terms", C.c_void_p), ("saved", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("cap_H", C.c_int32), ("cap_W", C.c_int32)]
 
 
 class LpipsConv3x3Args(C.Structure):

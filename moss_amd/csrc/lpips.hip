@@ -26,6 +26,9 @@
 //   conv_first_kernel / conv_first_backward_kernel -- conv 1_1 (Cin = 3, K = 27) and its adjoint on the VALU, with the z-score, the
 //     crop offset read from the device and the planar (3,H,W) layout of the public tensors.
 //   pool_kernel, tap_kernel, unpool_tap_kernel, reduce_kernel -- see each.
+//   conv_first_one_kernel, tap_ref_kernel -- the one-image forms behind moss_lpips_vgg_reference (the ground truth's tapped activations,
+//     once, into a caller's block) and moss_lpips_vgg_forward_ref (the forward on x alone, y's activations read from that block): the
+//     wide convolutions, the pool and the reduction are the kernels above at nimg = 1, the backward is untouched (forward_launches).
 // Every sum has a fixed order and there is no atomic: results are bitwise reproducible.  Every element of dL_dx is written.
 //
 // With a CAPACITY (moss_lpips_vgg_args.cap_H, cap_W) the crop's size is not a launch argument: every kernel reads {w, h} from the
@@ -168,6 +171,63 @@ conv_first_kernel(const float* __restrict__ x, const float* __restrict__ y, cons
         *reinterpret_cast<float4*>(dst + i) = v;
     }
     if (mask && img == 0) mask[(size_t)m * 2 + g] = bits;
+}
+
+// The one-image form: H W rows of x alone (the forward against a reference, and -- on the ground truth, without a mask -- the reference
+// pass).  A copy with the second image taken out: sharing the body moved conv_first_kernel's register allocation (92 -> 96 and 100 ->
+// 120 VGPRs), and the instantiations of the two-image path are to stay the code they were.
+template <bool DYN>
+__global__ void __launch_bounds__(WG)
+conv_first_one_kernel(const float* __restrict__ x, const int* __restrict__ rect, int FH, int FW, int H, int W,
+                      const float* __restrict__ wf, const float* __restrict__ bias, const float* __restrict__ shift,
+                      const float* __restrict__ scale, float* __restrict__ out, uint32_t* __restrict__ mask, const Dyn dyn)
+{
+    __shared__ __attribute__((aligned(16))) float s_w[27 * 64];          // [k = tap * 3 + c][channel]
+    if (DYN) {
+        actual_size(dyn, H, W);
+        if ((int)blockIdx.x * (WG / 2) >= H * W) return;                 // (the whole workgroup, before its first barrier)
+    }
+    for (int i = threadIdx.x; i < 27 * 64; i += WG) s_w[(i % 27) * 64 + i / 27] = wf[i];
+    __syncthreads();
+    const int HW = H * W;
+    const int t = blockIdx.x * WG + threadIdx.x, m = t >> 1, g = t & 1;
+    if (m >= HW) return;
+    const int p = m, py = p / W, px = p - py * W;
+    const int2 o = crop_origin(rect, H, W, FH, FW);
+    float in[27];
+#pragma unroll
+    for (int tap = 0; tap < 9; tap++) {
+        const int yy = py + tap / 3 - 1, xx = px + tap % 3 - 1;
+        const bool ok = yy >= 0 && yy < H && xx >= 0 && xx < W;
+#pragma unroll
+        for (int c = 0; c < 3; c++)
+            in[tap * 3 + c] = ok ? (x[((size_t)c * FH + o.y + yy) * FW + o.x + xx] - shift[c]) / scale[c] : 0.0f;
+    }
+    float acc[32];
+#pragma unroll
+    for (int i = 0; i < 32; i++) acc[i] = bias[32 * g + i];
+#pragma unroll
+    for (int k = 0; k < 27; k++) {
+#pragma unroll
+        for (int i = 0; i < 32; i += 4) {
+            const float4 wv = *reinterpret_cast<const float4*>(s_w + k * 64 + 32 * g + i);
+            acc[i] = __fmaf_rn(in[k], wv.x, acc[i]);
+            acc[i + 1] = __fmaf_rn(in[k], wv.y, acc[i + 1]);
+            acc[i + 2] = __fmaf_rn(in[k], wv.z, acc[i + 2]);
+            acc[i + 3] = __fmaf_rn(in[k], wv.w, acc[i + 3]);
+        }
+    }
+    uint32_t bits = 0;
+    float* dst = out + (size_t)m * 64 + 32 * g;
+#pragma unroll
+    for (int i = 0; i < 32; i += 4) {
+        float4 v;
+        v.x = fmaxf(acc[i], 0.0f); v.y = fmaxf(acc[i + 1], 0.0f); v.z = fmaxf(acc[i + 2], 0.0f); v.w = fmaxf(acc[i + 3], 0.0f);
+        bits |= (uint32_t)(acc[i] > 0.0f) << i | (uint32_t)(acc[i + 1] > 0.0f) << (i + 1) | (uint32_t)(acc[i + 2] > 0.0f) << (i + 2) |
+                (uint32_t)(acc[i + 3] > 0.0f) << (i + 3);
+        *reinterpret_cast<float4*>(dst + i) = v;
+    }
+    if (mask) mask[(size_t)m * 2 + g] = bits;
 }
 
 // d x[c][Y][X] = g / scale[c] * sum_{tap', co} d z[q + tap'][co] wb[c][tap'][co] inside the crop, 0 outside: one thread per FRAME pixel
@@ -713,6 +773,56 @@ tap_kernel(const float* __restrict__ f, int HW, int C, const float* __restrict__
     }
 }
 
+// The tap of the forward against a reference: f holds x's activations alone and y's row comes from `fyref`, a region of a reference
+// block (HW rows of C, the same layout) -- the same float32 operations on the same values.  A copy with that one line changed:
+// sharing the body moved tap_kernel's scalar prologue, and the kernels of the two-image path are to stay the code they were.
+__global__ void __launch_bounds__(WG)
+tap_ref_kernel(const float* __restrict__ f, const float* __restrict__ fyref, int HW, int C, const float* __restrict__ lin,
+               float* __restrict__ partial, float* __restrict__ G, const Dyn dyn)
+{
+    if (dyn.cap_H > 0) {
+        int H = 0, W = 0;
+        actual_size(dyn, H, W);
+        HW = H * W;
+    }
+    const int lane = threadIdx.x & 63, p = blockIdx.x * (WG / 64) + (threadIdx.x >> 6);
+    if (p >= HW) return;
+    const int n = C >> 6;
+    const float* rx = f + (size_t)p * C + lane;
+    const float* ry = fyref + (size_t)p * C + lane;
+    float fx[8], fy[8], w[8], sx2 = 0.0f, sy2 = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        fx[i] = fy[i] = w[i] = 0.0f;
+        if (i < n) {
+            fx[i] = rx[64 * i]; fy[i] = ry[64 * i]; w[i] = lin[lane + 64 * i];
+            sx2 = __fmaf_rn(fx[i], fx[i], sx2);
+            sy2 = __fmaf_rn(fy[i], fy[i], sy2);
+        }
+    }
+    const float sx = sqrtf(wave_sum(sx2)), sy = sqrtf(wave_sum(sy2)), ex = sx + NORM_EPS, ey = sy + NORM_EPS;
+    float av[8], t = 0.0f, dot = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        av[i] = 0.0f;
+        if (i < n) {
+            const float d = fx[i] / ex - fy[i] / ey;
+            t = __fmaf_rn(w[i] * d, d, t);
+            av[i] = 2.0f * w[i] * d / (float)HW;
+            dot = __fmaf_rn(av[i], fx[i], dot);
+        }
+    }
+    t = wave_sum(t);
+    if (lane == 0) partial[p] = t;
+    if (G) {
+        dot = wave_sum(dot);
+        const float k = sx > 0.0f ? dot / (sx * ex * ex) : 0.0f;
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+            if (i < n) G[(size_t)p * C + lane + 64 * i] = av[i] / ex - fx[i] * k;
+    }
+}
+
 struct ReduceArgs {
     int off[NTAP], cnt[NTAP];
     Dyn dyn;                   // with a capacity cnt[l] is (h >> l) * (w >> l) of the device rectangle
@@ -785,6 +895,7 @@ struct Geo {
     int H[NTAP], W[NTAP];
     size_t mask_off[NCONV], win_off[NTAP - 1], g_off[NTAP], saved_bytes;          // byte offsets into `saved`
     size_t buf_bytes, partial_off[NTAP], workspace_bytes;                           // partial_off: floats into the partial array
+    size_t ref_off[NTAP], reference_bytes;                                          // byte offsets into a reference block
 };
 
 Geo geometry(int H, int W)
@@ -810,6 +921,12 @@ Geo geometry(int H, int W)
     size_t n = 0;
     for (int l = 0; l < NTAP; l++) { g.partial_off[l] = n; n += (size_t)g.H[l] * g.W[l]; }
     g.workspace_bytes = 2 * g.buf_bytes + align_up(n * sizeof(float));
+    off = 0;
+    for (int l = 0; l < NTAP; l++) {                                               // the tapped activations of ONE image
+        g.ref_off[l] = off;
+        off += align_up((size_t)g.H[l] * g.W[l] * TAP_C[l] * sizeof(float));
+    }
+    g.reference_bytes = off;
     return g;
 }
 
@@ -938,6 +1055,99 @@ static const char* check_frame(int& H, int& W, int cap_H, int cap_W, const int* 
 
 static const char* SHORT_WORKSPACE = "the workspace is null or smaller than moss_lpips_vgg_workspace_bytes(H, W) (of cap_H, cap_W with a capacity)";
 
+// What the three forwards share.  The two-image call: x and y, the batch of two.  The forward against a reference: x alone (nimg = 1,
+// M = H W), the taps read y's activations from ref_in.  The reference pass: `x` is the ground truth, alone; the tapped layers write
+// straight into their regions of ref_out, the pools read them there, and there is no tap, no mean and no `saved`.
+struct FwdCall {
+    const float* x;
+    const float* y;                          // the two-image call, else null
+    const char* ref_in;                      // the forward against a reference, else null
+    char* ref_out;                           // the reference pass, else null
+    const int* rect;
+    int cap_H, cap_W;
+    const float* const* weights;
+    const float* const* biases;
+    const float* const* lin;
+    const float* shift;
+    const float* scale;
+    float* out;
+    float* terms;
+    char* saved;
+    char* workspace;
+};
+
+// H, W: the crop's size or the capacity's (check_frame).  launch_conv picks each layer's shape from the rows THIS call has.
+static void forward_launches(const FwdCall& f, const Geo& g, int H, int W, int FH, int FW, Precision prec, hipStream_t s)
+{
+    const int nimg = f.y ? 2 : 1;
+    auto dyn_at = [&](int level) { return Dyn{f.rect, f.cap_H, f.cap_W, level}; };        // (cap_H == 0: the kernels take the sizes below)
+    float* const ws[2] = {reinterpret_cast<float*>(f.workspace), reinterpret_cast<float*>(f.workspace + g.buf_bytes)};
+    float* partial = reinterpret_cast<float*>(f.workspace + 2 * g.buf_bytes);
+    char* sv = f.saved;
+    auto mask_at = [&](int i) { return sv ? reinterpret_cast<uint32_t*>(sv + g.mask_off[i]) : nullptr; };
+    auto other = [&](const float* in) { return in == ws[0] ? ws[1] : ws[0]; };             // a workspace buffer `in` is not
+
+    const int HW0 = H * W;
+    float* cur = ws[0];
+    if (nimg == 2) {
+        if (f.cap_H > 0)
+            hipLaunchKernelGGL(conv_first_kernel<true>, dim3(grid_for(4ll * HW0)), dim3(WG), 0, s, f.x, f.y, f.rect, FH, FW, H, W,
+                               f.weights[0], f.biases[0], f.shift, f.scale, cur, mask_at(0), dyn_at(0));
+        else
+            hipLaunchKernelGGL(conv_first_kernel<false>, dim3(grid_for(4ll * HW0)), dim3(WG), 0, s, f.x, f.y, f.rect, FH, FW, H, W,
+                               f.weights[0], f.biases[0], f.shift, f.scale, cur, mask_at(0), dyn_at(0));
+    } else {
+        if (f.cap_H > 0)
+            hipLaunchKernelGGL(conv_first_one_kernel<true>, dim3(grid_for(2ll * HW0)), dim3(WG), 0, s, f.x, f.rect, FH, FW, H, W,
+                               f.weights[0], f.biases[0], f.shift, f.scale, cur, mask_at(0), dyn_at(0));
+        else
+            hipLaunchKernelGGL(conv_first_one_kernel<false>, dim3(grid_for(2ll * HW0)), dim3(WG), 0, s, f.x, f.rect, FH, FW, H, W,
+                               f.weights[0], f.biases[0], f.shift, f.scale, cur, mask_at(0), dyn_at(0));
+    }
+    int tap = 0;
+    ReduceArgs red{};
+    red.dyn = dyn_at(0);
+    for (int i = 1; i < NCONV; i++) {
+        const int l = CONV_LEVEL[i], HW = g.H[l] * g.W[l];
+        const bool tapped = i == TAP_CONV[tap];
+        float* out = tapped && f.ref_out ? reinterpret_cast<float*>(f.ref_out + g.ref_off[tap]) : other(cur);
+        ConvArgs c{};
+        c.in = cur; c.w = f.weights[i]; c.bias = f.biases[i]; c.out = out; c.mask_out = mask_at(i);
+        c.M = nimg * HW; c.mask_rows = HW; c.H = g.H[l]; c.W = g.W[l]; c.Cin = CONV_COUT[i - 1]; c.Cout = CONV_COUT[i];
+        c.dyn = dyn_at(l); c.nimg = nimg;
+        launch_conv<MODE_FWD>(c, prec, s);
+        cur = out;
+        if (!tapped) continue;
+        const int C = TAP_C[tap];
+        float* G = sv ? reinterpret_cast<float*>(sv + g.g_off[tap]) : nullptr;
+        if (f.y)
+            hipLaunchKernelGGL(tap_kernel, dim3((HW + 3) / 4), dim3(WG), 0, s, (const float*)cur, HW, C, f.lin[tap],
+                               partial + g.partial_off[tap], G, dyn_at(l));
+        else if (f.ref_in)
+            hipLaunchKernelGGL(tap_ref_kernel, dim3((HW + 3) / 4), dim3(WG), 0, s, (const float*)cur,
+                               reinterpret_cast<const float*>(f.ref_in + g.ref_off[tap]), HW, C, f.lin[tap], partial + g.partial_off[tap],
+                               G, dyn_at(l));
+        red.off[tap] = (int)g.partial_off[tap];
+        red.cnt[tap] = HW;
+        if (tap + 1 < NTAP) {
+            out = other(cur);
+            hipLaunchKernelGGL(pool_kernel, dim3(grid_for((long long)nimg * g.H[l + 1] * g.W[l + 1] * (C / 16))), dim3(WG), 0, s,
+                               (const float*)cur, out, sv ? reinterpret_cast<uint32_t*>(sv + g.win_off[tap]) : nullptr, nimg, g.H[l], g.W[l],
+                               C, dyn_at(l));
+            cur = out;
+        }
+        tap++;
+    }
+    if (!f.ref_out) hipLaunchKernelGGL(reduce_kernel, dim3(1), dim3(1024), 0, s, (const float*)partial, red, f.out, f.terms);
+}
+
+static const char* null_weights(const float* const* weights, const float* const* biases)
+{
+    for (int i = 0; i < NCONV; i++)
+        if (!weights[i] || !biases[i]) return "null weight or bias (13 of each, packed by moss_lpips_vgg_pack_weights)";
+    return nullptr;
+}
+
 // LPIPS.forward, lpipsPyTorch/modules/lpips.py:31-37 (net_type='vgg').  prec: weights[1..12] are that precision's packing
 static int lpips_forward(const char* me, const moss_lpips_vgg_args* a, Precision prec, void* stream)
 {
@@ -946,52 +1156,57 @@ static int lpips_forward(const char* me, const moss_lpips_vgg_args* a, Precision
     int H = a->H, W = a->W;
     if (const char* why = check_frame(H, W, a->cap_H, a->cap_W, a->rect, FH, FW)) return invalid_arg(me, why);
     if (!a->x || !a->y || !a->out || !a->shift || !a->scale) return invalid_arg(me, "null x, y, out, shift or scale");
-    for (int i = 0; i < NCONV; i++)
-        if (!a->weights[i] || !a->biases[i]) return invalid_arg(me, "null weight or bias (13 of each, packed by moss_lpips_vgg_pack_weights)");
+    if (const char* why = null_weights(a->weights, a->biases)) return invalid_arg(me, why);
     for (int l = 0; l < NTAP; l++)
         if (!a->lin[l]) return invalid_arg(me, "null lin weight (5)");
     const Geo g = geometry(H, W);
     if (!a->workspace || a->workspace_bytes < g.workspace_bytes) return invalid_arg(me, SHORT_WORKSPACE);
-    auto dyn_at = [&](int level) { return Dyn{a->rect, a->cap_H, a->cap_W, level}; };     // (cap_H == 0: the kernels take the sizes below)
-    hipStream_t s = (hipStream_t)stream;
-    float* cur = reinterpret_cast<float*>(a->workspace);
-    float* nxt = reinterpret_cast<float*>(a->workspace + g.buf_bytes);
-    float* partial = reinterpret_cast<float*>(a->workspace + 2 * g.buf_bytes);
-    char* sv = a->saved;
-    auto mask_at = [&](int i) { return sv ? reinterpret_cast<uint32_t*>(sv + g.mask_off[i]) : nullptr; };
+    const FwdCall f{a->x, a->y, nullptr, nullptr, a->rect, a->cap_H, a->cap_W, a->weights, a->biases, a->lin, a->shift, a->scale,
+                    a->out, a->terms, a->saved, a->workspace};
+    forward_launches(f, g, H, W, FH, FW, prec, (hipStream_t)stream);
+    return launch_status(me);
+}
 
-    const int HW0 = H * W;
-    if (a->cap_H > 0)
-        hipLaunchKernelGGL(conv_first_kernel<true>, dim3(grid_for(4ll * HW0)), dim3(WG), 0, s, a->x, a->y, a->rect, FH, FW, H, W,
-                           a->weights[0], a->biases[0], a->shift, a->scale, cur, mask_at(0), dyn_at(0));
-    else
-        hipLaunchKernelGGL(conv_first_kernel<false>, dim3(grid_for(4ll * HW0)), dim3(WG), 0, s, a->x, a->y, a->rect, FH, FW, H, W,
-                           a->weights[0], a->biases[0], a->shift, a->scale, cur, mask_at(0), dyn_at(0));
-    int tap = 0;
-    ReduceArgs red{};
-    red.dyn = dyn_at(0);
-    for (int i = 1; i < NCONV; i++) {
-        const int l = CONV_LEVEL[i], HW = g.H[l] * g.W[l];
-        ConvArgs c{};
-        c.in = cur; c.w = a->weights[i]; c.bias = a->biases[i]; c.out = nxt; c.mask_out = mask_at(i);
-        c.M = 2 * HW; c.mask_rows = HW; c.H = g.H[l]; c.W = g.W[l]; c.Cin = CONV_COUT[i - 1]; c.Cout = CONV_COUT[i];
-        c.dyn = dyn_at(l); c.nimg = 2;
-        launch_conv<MODE_FWD>(c, prec, s);
-        std::swap(cur, nxt);
-        if (i != TAP_CONV[tap]) continue;
-        const int C = TAP_C[tap];
-        hipLaunchKernelGGL(tap_kernel, dim3((HW + 3) / 4), dim3(WG), 0, s, (const float*)cur, HW, C, a->lin[tap],
-                           partial + g.partial_off[tap], sv ? reinterpret_cast<float*>(sv + g.g_off[tap]) : nullptr, dyn_at(l));
-        red.off[tap] = (int)g.partial_off[tap];
-        red.cnt[tap] = HW;
-        if (tap + 1 < NTAP) {
-            hipLaunchKernelGGL(pool_kernel, dim3(grid_for(2ll * g.H[l + 1] * g.W[l + 1] * (C / 16))), dim3(WG), 0, s, (const float*)cur, nxt,
-                               sv ? reinterpret_cast<uint32_t*>(sv + g.win_off[tap]) : nullptr, 2, g.H[l], g.W[l], C, dyn_at(l));
-            std::swap(cur, nxt);
-        }
-        tap++;
-    }
-    hipLaunchKernelGGL(reduce_kernel, dim3(1), dim3(1024), 0, s, (const float*)partial, red, a->out, a->terms);
+static const char* SHORT_REFERENCE = "reference is null or reference_bytes is smaller than moss_lpips_vgg_reference_bytes(H, W) (of cap_H, cap_W with a capacity)";
+
+// lpipsPyTorch/modules/lpips.py:32 for the SECOND image alone: feat_y = self.net(y), kept raw (line 34's normalisation is the tap's)
+static int lpips_reference(const char* me, const moss_lpips_vgg_reference_args* a, Precision prec, void* stream)
+{
+    if (!a) return invalid_arg(me, "null argument block");
+    int FH = a->frame_H, FW = a->frame_W;
+    int H = a->H, W = a->W;
+    if (const char* why = check_frame(H, W, a->cap_H, a->cap_W, a->rect, FH, FW)) return invalid_arg(me, why);
+    if (!a->y) return invalid_arg(me, "null y");
+    if (!a->shift || !a->scale) return invalid_arg(me, "null shift or scale");
+    if (const char* why = null_weights(a->weights, a->biases)) return invalid_arg(me, why);
+    const Geo g = geometry(H, W);
+    if (!a->reference || a->reference_bytes < g.reference_bytes) return invalid_arg(me, SHORT_REFERENCE);
+    if (!a->workspace || a->workspace_bytes < g.workspace_bytes) return invalid_arg(me, SHORT_WORKSPACE);
+    const FwdCall f{a->y, nullptr, nullptr, a->reference, a->rect, a->cap_H, a->cap_W, a->weights, a->biases, nullptr, a->shift,
+                    a->scale, nullptr, nullptr, nullptr, a->workspace};
+    forward_launches(f, g, H, W, FH, FW, prec, (hipStream_t)stream);
+    return launch_status(me);
+}
+
+// lpipsPyTorch/modules/lpips.py:31-37 with feat_y (line 32) read from a reference block instead of computed
+static int lpips_forward_ref(const char* me, const moss_lpips_vgg_forward_ref_args* a, Precision prec, void* stream)
+{
+    if (!a) return invalid_arg(me, "null argument block");
+    int FH = a->frame_H, FW = a->frame_W;
+    int H = a->H, W = a->W;
+    if (const char* why = check_frame(H, W, a->cap_H, a->cap_W, a->rect, FH, FW)) return invalid_arg(me, why);
+    if (!a->x) return invalid_arg(me, "null x");
+    if (!a->out) return invalid_arg(me, "null out");
+    if (!a->shift || !a->scale) return invalid_arg(me, "null shift or scale");
+    if (const char* why = null_weights(a->weights, a->biases)) return invalid_arg(me, why);
+    for (int l = 0; l < NTAP; l++)
+        if (!a->lin[l]) return invalid_arg(me, "null lin weight (5)");
+    const Geo g = geometry(H, W);
+    if (!a->reference || a->reference_bytes < g.reference_bytes) return invalid_arg(me, SHORT_REFERENCE);
+    if (!a->workspace || a->workspace_bytes < g.workspace_bytes) return invalid_arg(me, SHORT_WORKSPACE);
+    const FwdCall f{a->x, nullptr, a->reference, nullptr, a->rect, a->cap_H, a->cap_W, a->weights, a->biases, a->lin, a->shift,
+                    a->scale, a->out, a->terms, a->saved, a->workspace};
+    forward_launches(f, g, H, W, FH, FW, prec, (hipStream_t)stream);
     return launch_status(me);
 }
 
@@ -1008,6 +1223,38 @@ extern "C" int moss_lpips_vgg_forward_bf16(const moss_lpips_vgg_args* a, void* s
 extern "C" int moss_lpips_vgg_forward_bf16x3(const moss_lpips_vgg_args* a, void* stream)
 {
     return lpips_forward("moss_lpips_vgg_forward_bf16x3", a, PREC_BF16X3, stream);
+}
+
+extern "C" size_t moss_lpips_vgg_reference_bytes(int H, int W) { return size_ok(H, W) ? geometry(H, W).reference_bytes : 0; }
+
+extern "C" int moss_lpips_vgg_reference(const moss_lpips_vgg_reference_args* a, void* stream)
+{
+    return lpips_reference("moss_lpips_vgg_reference", a, PREC_F32, stream);
+}
+
+extern "C" int moss_lpips_vgg_reference_bf16(const moss_lpips_vgg_reference_args* a, void* stream)
+{
+    return lpips_reference("moss_lpips_vgg_reference_bf16", a, PREC_BF16, stream);
+}
+
+extern "C" int moss_lpips_vgg_reference_bf16x3(const moss_lpips_vgg_reference_args* a, void* stream)
+{
+    return lpips_reference("moss_lpips_vgg_reference_bf16x3", a, PREC_BF16X3, stream);
+}
+
+extern "C" int moss_lpips_vgg_forward_ref(const moss_lpips_vgg_forward_ref_args* a, void* stream)
+{
+    return lpips_forward_ref("moss_lpips_vgg_forward_ref", a, PREC_F32, stream);
+}
+
+extern "C" int moss_lpips_vgg_forward_ref_bf16(const moss_lpips_vgg_forward_ref_args* a, void* stream)
+{
+    return lpips_forward_ref("moss_lpips_vgg_forward_ref_bf16", a, PREC_BF16, stream);
+}
+
+extern "C" int moss_lpips_vgg_forward_ref_bf16x3(const moss_lpips_vgg_forward_ref_args* a, void* stream)
+{
+    return lpips_forward_ref("moss_lpips_vgg_forward_ref_bf16x3", a, PREC_BF16X3, stream);
 }
 
 // the adjoint of LPIPS.forward (lpipsPyTorch/modules/lpips.py:31-37) w.r.t. x.  prec: weights_bwd[1..12] are that precision's packing

@@ -17,6 +17,9 @@ through a non-trainable 1x1 convolution to one channel and a spatial mean; the f
 * :func:`lpips_vgg_roi_fused` -- the same on the ``ViewRegion`` rectangle of two full frames (no crop copies; the offset is read on the
   device, and with ``capacity=`` the crop's size too: one capture serves views whose crops differ in size).
   :func:`crop_capacity` -- the capacity of a dataset's views.
+* :class:`LpipsReference`, :func:`lpips_vgg_reference`, :func:`lpips_vgg_roi_reference`, :func:`reference_cache` -- the ground truth's
+  tapped activations computed once per camera (``moss_lpips_vgg_reference``) and given to the two ops above in the ground truth's
+  place (``moss_lpips_vgg_forward_ref``): the forward then runs VGG16 on one image, not two, and the result is the same.
 * :func:`lpips_vgg_torch` -- the same mathematics in plain torch (any dtype or device): the yardstick of the tests and of
   scripts/lpips_times.py.  Not a fallback: the fused op has no CPU path.
 * :func:`synthetic_weights` -- VGG16-shaped weights from a seed (a frozen ``numpy.random.RandomState`` stream), for tests, the timing
@@ -28,10 +31,12 @@ from __future__ import annotations
 
 import ctypes
 import hashlib
+import itertools
 
 import torch
 
-__all__ = ["LpipsVGG", "lpips_vgg_fused", "lpips_vgg_roi_fused", "crop_capacity", "lpips_vgg_torch", "synthetic_weights", "weights_sha256",
+__all__ = ["LpipsVGG", "LpipsReference", "lpips_vgg_fused", "lpips_vgg_roi_fused", "lpips_vgg_reference", "lpips_vgg_roi_reference",
+           "reference_bytes", "reference_cache", "crop_capacity", "lpips_vgg_torch", "synthetic_weights", "weights_sha256",
            "PRECISIONS", "ALL_PRECISIONS", "CONV_SHAPES", "TAP_CHANNELS", "TAP_AFTER_CONV", "POOL_AFTER_CONV", "SHIFT", "SCALE", "MIN_SIZE"]
 
 _WIDTHS = (64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512)
@@ -46,6 +51,7 @@ EPS = 1e-10                                               # normalize_activation
 PRECISIONS = ("f32", "bf16")                              # LpipsVGG(precision=): the operands of the twelve wide convolutions ...
 ALL_PRECISIONS = PRECISIONS + ("bf16x3",)                 # ... and the split-bf16 (three-product) form
 _SUFFIX = {"f32": "", "bf16": "_bf16", "bf16x3": "_bf16x3"}                          # of the C entry points
+_GENERATIONS = itertools.count(1)                         # LpipsVGG.generation: one number per (net, refresh)
 
 
 # ---- the torch form ---------------------------------------------------------------------------------------------------------------
@@ -278,8 +284,11 @@ class LpipsVGG:
         return [m.weight for m in convs], [m.bias for m in convs], [m.weight for m in lins], shift, scale
 
     def refresh(self):
-        """Pack the source tensors again (a caller who reloaded its weights), in this net's precision."""
+        """Pack the source tensors again (a caller who reloaded its weights), in this net's precision.  Advances ``generation`` (a
+        number no other net or refresh has had): an :class:`LpipsReference` made before holds the old weights' activations and is
+        refused from here on."""
         from ._lib import call
+        self.generation = next(_GENERATIONS)
         cw, cb, lw, shift, scale = self._src
         f32 = lambda t: t.detach().to(torch.float32).contiguous()
         self.biases = [f32(b).clone() for b in cb]
@@ -313,10 +322,109 @@ def _fill_common(a, net, h, w, frame, rect, capacity):
     a.cap_H, a.cap_W = (0, 0) if capacity is None else capacity
 
 
+def reference_bytes(h, w):
+    """The bytes of an :class:`LpipsReference` block for an ``h`` x ``w`` crop, or for a capacity: the five tapped activation maps of
+    one image, 122 floats per crop pixel (22 MB at 256x176).  0 for a size the kernels refuse."""
+    from ._lib import lib
+    return int(lib().moss_lpips_vgg_reference_bytes(int(h), int(w)))
+
+
+class LpipsReference:
+    """What the ground truth contributes to the term, computed ONCE (:func:`lpips_vgg_reference`, :func:`lpips_vgg_roi_reference`) and
+    accepted by :func:`lpips_vgg_fused` / :func:`lpips_vgg_roi_fused` wherever they take the ground-truth tensor: its raw activations
+    after ReLU 1_2, 2_2, 3_3, 4_3 and 5_3 (``moss_lpips_vgg_reference`` of include/moss_raster.h states the layout).
+
+    ``block``: one uint8 tensor of :func:`reference_bytes`; ``crop``: the ``(h, w)`` the block holds now (None: nothing loaded yet);
+    ``capacity``: the ``(cap_h, cap_w)`` the block is laid out for, or None (laid out for ``crop``); ``precision`` and ``generation``:
+    those of the net that made it.  A reference is valid for ONE (weights, precision, crop size or capacity): ``LpipsVGG.refresh()``
+    advances the net's generation, and the ops refuse a reference of another precision, generation, device, size or capacity.
+
+    THE SAME RESULT.  Against a reference the term runs on ``x`` alone.  Per row the convolution does not know how many images the
+    batch holds; what can differ is the kernel shape, which the launcher picks from the row count -- H W here, 2 H W with two images
+    -- and the two shapes sum K in different orders.  So the value, the five terms and the gradient are BIT-IDENTICAL to the two-image
+    call of the same net, inputs and capacity whenever every wide layer gets the same shape at M = H W as at M = 2 H W: on a device
+    with more than 122 CUs for every crop (or capacity) up to 101x77, where all layers take the 32-row shape either way.  Otherwise
+    the two agree to float32 summation order and meet the same bar against float64.  In the bf16 modes the ground truth's
+    activations are what that mode's kernels compute for it, as in the two-image call."""
+
+    def __init__(self, block, crop, capacity, precision, generation):
+        self.block, self.crop, self.capacity, self.precision, self.generation = block, crop, capacity, precision, generation
+
+    @classmethod
+    def empty(cls, net, size, static=False):
+        """An unloaded reference on ``net``'s device -- the static buffer of a capture, filled by :meth:`copy_`.  ``size``: the capacity
+        ``(cap_h, cap_w)`` (``MossStep(lpips_capacity=)``); with ``static=True`` the one crop size of a call without a capacity."""
+        h, w = (int(v) for v in size)
+        nbytes = reference_bytes(h, w)
+        if nbytes == 0:
+            raise ValueError(f"LpipsReference.empty: {h}x{w} is not a size the kernels take (at least {MIN_SIZE}x{MIN_SIZE})")
+        block = torch.empty(nbytes, dtype=torch.uint8, device=net.device)
+        return cls(block, (h, w) if static else None, None if static else (h, w), net.precision, net.generation)
+
+    @property
+    def nbytes(self):
+        return self.block.numel()
+
+    @property
+    def device(self):
+        return self.block.device
+
+    def _layout(self):
+        return self.capacity if self.capacity is not None else self.crop
+
+    def copy_(self, other):
+        """Load ``other`` into this reference: the block (one device copy, capturable as any ``copy_``) and the host fields.  Both must
+        be laid out alike -- one capacity, or without one the same crop size.  This is how a captured step changes frame."""
+        if not isinstance(other, LpipsReference):
+            raise TypeError(f"LpipsReference.copy_: expected an LpipsReference, got {type(other).__name__}")
+        if other.crop is None:
+            raise ValueError("LpipsReference.copy_: the source holds nothing yet")
+        if self.capacity != other.capacity or self._layout() != other._layout():
+            raise ValueError(f"LpipsReference.copy_: the two are laid out differently: capacity {self.capacity} crop {self.crop}, and "
+                             f"capacity {other.capacity} crop {other.crop}")
+        self.block.copy_(other.block)
+        self.crop, self.precision, self.generation = other.crop, other.precision, other.generation
+        return self
+
+    def __repr__(self):
+        return (f"LpipsReference(crop={self.crop}, capacity={self.capacity}, precision={self.precision!r}, "
+                f"generation={self.generation}, nbytes={self.nbytes})")
+
+
+def _fill_net(a, net, lin=True):
+    for i in range(13):
+        a.weights[i], a.biases[i] = net.w_fwd[i].data_ptr(), net.biases[i].data_ptr()
+    if lin:
+        for i in range(5):
+            a.lin[i] = net.lin[i].data_ptr()
+    a.shift, a.scale = net.shift.data_ptr(), net.scale.data_ptr()
+
+
+def _make_reference(net, y3, crop, rect, capacity):
+    """The reference pass on the (3,FH,FW) ground truth: allocates the block and the workspace, nothing else."""
+    from ._lib import LpipsVggReferenceArgs, call, lib
+    dev = y3.device
+    FH, FW = int(y3.shape[-2]), int(y3.shape[-1])
+    h, w = (FH, FW) if crop is None else crop
+    L = lib()
+    ref = LpipsReference(torch.empty(reference_bytes(*(capacity or (h, w))), dtype=torch.uint8, device=dev), (h, w), capacity,
+                         net.precision, net.generation)
+    nbytes = int(L.moss_lpips_vgg_workspace_bytes(FH, FW))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    a = LpipsVggReferenceArgs()
+    a.y = y3.data_ptr()
+    _fill_common(a, net, h, w, (FH, FW), rect, capacity)
+    _fill_net(a, net, lin=False)
+    a.reference, a.reference_bytes = ref.block.data_ptr(), ref.nbytes
+    a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+    call("moss_lpips_vgg_reference" + _SUFFIX[net.precision], dev, ctypes.byref(a))
+    return ref
+
+
 class _LpipsVGG(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, y, net, crop, rect, capacity):
-        from ._lib import LpipsVggArgs, call, lib
+        from ._lib import LpipsVggArgs, LpipsVggForwardRefArgs, call, lib
         dev = x.device
         FH, FW = int(x.shape[-2]), int(x.shape[-1])
         h, w = (FH, FW) if crop is None else crop
@@ -327,18 +435,18 @@ class _LpipsVGG(torch.autograd.Function):
         nbytes = int(L.moss_lpips_vgg_workspace_bytes(FH, FW))                        # (sized for the frame: any crop of it fits)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         saved = torch.empty(int(L.moss_lpips_vgg_saved_bytes(*(capacity or (h, w)))) if keep else 0, dtype=torch.uint8, device=dev)
-        a = LpipsVggArgs()
-        a.x, a.y = x.data_ptr(), y.data_ptr()
+        if isinstance(y, LpipsReference):                    # x alone; `saved` is the two-image call's, and so is the backward
+            a, entry = LpipsVggForwardRefArgs(), "moss_lpips_vgg_forward_ref"
+            a.x, a.reference, a.reference_bytes = x.data_ptr(), y.block.data_ptr(), y.nbytes
+        else:
+            a, entry = LpipsVggArgs(), "moss_lpips_vgg_forward"
+            a.x, a.y = x.data_ptr(), y.data_ptr()
         _fill_common(a, net, h, w, (FH, FW), rect, capacity)
-        for i in range(13):
-            a.weights[i], a.biases[i] = net.w_fwd[i].data_ptr(), net.biases[i].data_ptr()
-        for i in range(5):
-            a.lin[i] = net.lin[i].data_ptr()
-        a.shift, a.scale = net.shift.data_ptr(), net.scale.data_ptr()
+        _fill_net(a, net)
         a.out, a.terms = out.data_ptr(), terms.data_ptr()
         a.saved = saved.data_ptr() if keep else None
         a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
-        call("moss_lpips_vgg_forward" + _SUFFIX[net.precision], dev, ctypes.byref(a))
+        call(entry + _SUFFIX[net.precision], dev, ctypes.byref(a))
         ctx.net, ctx.crop, ctx.frame, ctx.capacity = net, (h, w), (FH, FW), capacity
         ctx.save_for_backward(saved, rect if rect is not None else torch.empty(0, dtype=torch.int32, device=dev))
         ctx.mark_non_differentiable(terms)
@@ -368,6 +476,8 @@ def _check_images(what, net, x, y):
     if not isinstance(net, LpipsVGG):
         raise TypeError(f"{what}: net must be an LpipsVGG (LpipsVGG.from_tensors / from_module), got {type(net).__name__}")
     for name, t in (("x", x), ("y", y)):
+        if isinstance(t, LpipsReference):                    # (the ground truth as a reference: _check_reference)
+            continue
         if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
             raise RuntimeError(f"{what} runs the HIP kernels of the LPIPS term: {name} must be a tensor on a GPU (lpips_vgg_torch is "
                                "the torch form)")
@@ -377,16 +487,35 @@ def _check_images(what, net, x, y):
             raise ValueError(f"{what}: the batch must be 1, got {tuple(t.shape)}")
         if t.dim() not in (3, 4) or t.shape[-3] != 3:
             raise ValueError(f"{what}: {name} must be (3,H,W) or (1,3,H,W), got {tuple(t.shape)}")
+    if isinstance(y, LpipsReference):
+        return
     if x.shape[-2:] != y.shape[-2:]:
         raise ValueError(f"{what}: the two images differ in size: {tuple(x.shape)} and {tuple(y.shape)}")
     if y.requires_grad and torch.is_grad_enabled():
         raise RuntimeError(f"{what}: y is the ground truth and gets no gradient; detach it")
 
 
+def _check_reference(what, net, ref, crop, capacity):
+    """Host checks of a reference against the call that is about to read it: ``crop`` the call's (h, w), ``capacity`` the call's."""
+    if ref.precision != net.precision:
+        raise ValueError(f"{what}: the reference was made by a precision={ref.precision!r} net and this net has "
+                         f"precision={net.precision!r}; a reference belongs to the precision that made it")
+    if ref.generation != net.generation:
+        raise ValueError(f"{what}: the reference was made before net.refresh() (or by another net): its generation is "
+                         f"{ref.generation}, the net's {net.generation}; make it again")
+    if ref.device != net.device:
+        raise ValueError(f"{what}: the reference is on {ref.device}, the net on {net.device}")
+    if ref.capacity != capacity:
+        raise ValueError(f"{what}: the reference is laid out for capacity {ref.capacity} and the call has capacity {capacity}")
+    if ref.crop != tuple(crop):
+        raise ValueError(f"{what}: the reference holds a {ref.crop[0]}x{ref.crop[1]} crop and the call's is {crop[0]}x{crop[1]}"
+                         if ref.crop else f"{what}: the reference holds nothing yet (LpipsReference.empty: copy_ one into it)")
+
+
 def _apply(net, x, y, crop, rect, return_terms, capacity=None):
     shape = x.shape
     x3 = x.reshape(3, shape[-2], shape[-1]).contiguous()
-    y3 = y.detach().reshape(3, shape[-2], shape[-1]).contiguous()
+    y3 = y if isinstance(y, LpipsReference) else y.detach().reshape(3, shape[-2], shape[-1]).contiguous()
     value, terms = _LpipsVGG.apply(x3, y3, net, crop, rect, capacity)
     return (value, terms) if return_terms else value
 
@@ -395,11 +524,54 @@ def lpips_vgg_fused(net, x, y, return_terms=False):
     """MOSS's ``loss_fn_vgg(x, y)`` as the fused HIP op.  ``net``: an :class:`LpipsVGG`; ``x``, ``y``: (3,H,W) or (1,3,H,W) float32 on
     the GPU, H, W >= 16.  Returns (1,1,1,1) float32 (with ``return_terms`` also the five per-tap terms, no gradient).  The gradient
     goes to ``x`` only; a ``y`` that requires grad raises.  Under ``torch.no_grad()``, or when ``x`` needs no gradient, the forward
-    keeps nothing."""
+    keeps nothing.
+
+    ``y`` may be an :class:`LpipsReference` of ``x``'s size made by :func:`lpips_vgg_reference` with this net: half of the forward's
+    convolutions are then not run.  The result is the two-image call's, bit for bit where
+    the kernel shapes agree (:class:`LpipsReference` states the rule).  A reference of another precision, from before ``net.refresh()``, on
+    another device, with a capacity, or of another size than ``x`` raises before anything touches the device."""
     _check_images("lpips_vgg_fused", net, x, y)
     if min(x.shape[-2:]) < MIN_SIZE:
         raise ValueError(f"lpips_vgg_fused: H and W must be >= {MIN_SIZE} (four 2x2 pools), got {tuple(x.shape[-2:])}")
+    if isinstance(y, LpipsReference):
+        _check_reference("lpips_vgg_fused", net, y, tuple(int(v) for v in x.shape[-2:]), None)
     return _apply(net, x, y, None, None, return_terms)
+
+
+def _check_truth(what, net, y):
+    _check_images(what, net, y, y)
+    if min(y.shape[-2:]) < MIN_SIZE:
+        raise ValueError(f"{what}: H and W must be >= {MIN_SIZE} (four 2x2 pools), got {tuple(y.shape[-2:])}")
+    return y.detach().reshape(3, y.shape[-2], y.shape[-1]).contiguous()
+
+
+def lpips_vgg_reference(net, y):
+    """The :class:`LpipsReference` of the ground truth ``y`` ((3,H,W) or (1,3,H,W) float32 on the GPU) for ``lpips_vgg_fused(net, x,
+    ref)``: VGG16 on ``y`` alone (``moss_lpips_vgg_reference``), in the net's precision, keeping the five tapped activation maps and
+    nothing else.  No gradient is recorded whatever the mode; it allocates the block and a workspace, reads nothing on the host, and
+    is capturable.  What "the same result" means: :class:`LpipsReference`."""
+    with torch.no_grad():
+        return _make_reference(net, _check_truth("lpips_vgg_reference", net, y), None, None, None)
+
+
+def lpips_vgg_roi_reference(net, gt_image, region, capacity=None):
+    """The :class:`LpipsReference` of the full-frame ground truth on ``region``'s rectangle, for ``lpips_vgg_roi_fused(net, image, ref,
+    region, capacity=capacity)``: the crop starts where the two-image call's does (the rectangle's corner, moved so that the crop
+    fits the frame).  With ``capacity`` the block is laid out for the capacity and the size is read from ``region.rect`` on the
+    device; a reference serves the calls of that one capacity (or, without one, of that one crop size).  What "the same result" means:
+    :class:`LpipsReference`."""
+    with torch.no_grad():                                    # (as lpips_vgg_reference: nothing is recorded, whatever gt_image requires)
+        cap, (h, w) = _roi_sizes("lpips_vgg_roi_reference", net, gt_image, gt_image, region, capacity)
+        y3 = gt_image.detach().reshape(3, gt_image.shape[-2], gt_image.shape[-1]).contiguous()
+        return _make_reference(net, y3, (h, w), region.rect, cap)
+
+
+def reference_cache(net, gt_images, regions, capacity=None):
+    """``(refs, nbytes)``: one :class:`LpipsReference` per (ground truth, region) -- :func:`lpips_vgg_roi_reference` with ``capacity``
+    -- and the bytes they hold together (122 floats per pixel of the capacity, or of each crop: the caller decides how many views to
+    keep).  A captured step changes frame by ``step.lpips_reference.copy_(refs[k])``."""
+    refs = [lpips_vgg_roi_reference(net, gt, region, capacity) for gt, region in zip(gt_images, regions)]
+    return refs, sum(r.nbytes for r in refs)
 
 
 def crop_capacity(regions):
@@ -426,6 +598,24 @@ def resolve_capacity(what, capacity, H, W):
     return cap_h, cap_w
 
 
+def _roi_sizes(what, net, image, gt_image, region, capacity):
+    """The host checks of a call on a region: the resolved capacity (or None) and the crop's (h, w)."""
+    cap = None
+    if capacity is not None:                                 # (host arithmetic on the region alone, before anything touches a device)
+        cap = resolve_capacity(what, capacity, *region.bound.shape)
+        _, _, w, h = region.xywh
+        if h > cap[0] or w > cap[1]:
+            raise ValueError(f"{what}: the region's crop {h}x{w} exceeds the capacity {cap[0]}x{cap[1]}")
+    _check_images(what, net, image, gt_image)
+    H, W = image.shape[-2:]
+    if tuple(region.bound.shape) != (H, W) or region.rect.device != image.device:
+        raise RuntimeError(f"{what}: the view's region does not belong to this image")
+    _, _, w, h = region.xywh
+    if min(h, w) < MIN_SIZE or h > H or w > W:
+        raise ValueError(f"{what}: the crop must be at least {MIN_SIZE}x{MIN_SIZE} and fit the frame, got {h}x{w}")
+    return cap, (int(h), int(w))
+
+
 def lpips_vgg_roi_fused(net, image, gt_image, region, return_terms=False, capacity=None):
     """``loss_fn_vgg(image[:, y:y+h, x:x+w], gt_image[...])`` for ``(x, y, w, h) = region.xywh`` (train_ZJU.py:115-121) on the FULL
     frames: the gradient is written for the whole ``image`` (zero off the crop), there is no host read and there are no crop copies.
@@ -443,17 +633,7 @@ def lpips_vgg_roi_fused(net, image, gt_image, region, return_terms=False, capaci
     the result is bit-identical to the static call at the same crop exactly when every layer gets the same shape in both: always when
     the crop equals the capacity, and for any capacity up to 64x64 on a device with more than 64 CUs.  Otherwise the two agree to
     float32 summation order and meet the same bar against float64."""
-    cap = None
-    if capacity is not None:                                 # (host arithmetic on the region alone, before anything touches a device)
-        cap = resolve_capacity("lpips_vgg_roi_fused", capacity, *region.bound.shape)
-        _, _, w, h = region.xywh
-        if h > cap[0] or w > cap[1]:
-            raise ValueError(f"lpips_vgg_roi_fused: the region's crop {h}x{w} exceeds the capacity {cap[0]}x{cap[1]}")
-    _check_images("lpips_vgg_roi_fused", net, image, gt_image)
-    H, W = image.shape[-2:]
-    if tuple(region.bound.shape) != (H, W) or region.rect.device != image.device:
-        raise RuntimeError("lpips_vgg_roi_fused: the view's region does not belong to this image")
-    _, _, w, h = region.xywh
-    if min(h, w) < MIN_SIZE or h > H or w > W:
-        raise ValueError(f"lpips_vgg_roi_fused: the crop must be at least {MIN_SIZE}x{MIN_SIZE} and fit the frame, got {h}x{w}")
-    return _apply(net, image, gt_image, (int(h), int(w)), region.rect, return_terms, cap)
+    cap, (h, w) = _roi_sizes("lpips_vgg_roi_fused", net, image, gt_image, region, capacity)
+    if isinstance(gt_image, LpipsReference):
+        _check_reference("lpips_vgg_roi_fused", net, gt_image, (h, w), cap)
+    return _apply(net, image, gt_image, (h, w), region.rect, return_terms, cap)

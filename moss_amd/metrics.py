@@ -143,7 +143,8 @@ class QualityReport:
         return self._per_view[:min(n, self.per_view_capacity)].cpu()
 
 
-def evaluate_views(pc, cameras, gts, regions, bg, transforms=None, translation=None, lpips_fn=None, lpips=None):
+def evaluate_views(pc, cameras, gts, regions, bg, transforms=None, translation=None, lpips_fn=None, lpips=None,
+                   lpips_references=None):
     """MOSS's ``training_report`` over one split (train_ZJU.py:238-262), the metric part on the device: every view rendered with
     ``render()`` under ``torch.no_grad()`` (the forward-only path), its L1 / PSNR / SSIM added to a :class:`QualityReport`, and -- with
     ``lpips_fn`` -- ``lpips_fn(image, gt_image)`` on the clamped and filled render and the clamped ground truth, accumulated in float64
@@ -153,10 +154,22 @@ def evaluate_views(pc, cameras, gts, regions, bg, transforms=None, translation=N
     (:func:`moss_amd.lpips.lpips_vgg_fused`, its forward that keeps nothing), summed in float64 in view order like the others.  The net
     must be a float32 one: reported LPIPS is the float32 term, and a ``precision="bf16"`` net (the training term's mixed-precision
     mode) raises ``ValueError`` before anything is rendered.
+    ``lpips_references`` (with ``lpips``): one :class:`moss_amd.lpips.LpipsReference` per view, made by
+    ``lpips_vgg_reference(lpips, torch.clamp(gts[i], 0, 1))`` and used instead of the clamped ground truth: evaluation is forward-only,
+    so half of every LPIPS call is otherwise VGG16 on an image that never changes.  The same means (``lpips.LpipsReference`` states
+    when bit for bit); references of a net that is not float32 raise like the net itself.
     Returns ``{"l1", "psnr", "ssim", "lpips", "n"}``: the reference's four set means (``lpips`` None without ``lpips_fn`` / ``lpips``)."""
     if lpips is not None and getattr(lpips, "precision", "f32") != "f32":
         raise ValueError(f"evaluate_views: reported LPIPS is the float32 term; the net given has precision={lpips.precision!r} "
                          "(build a second LpipsVGG with precision='f32' for evaluation)")
+    if lpips_references is not None:
+        lpips_references = list(lpips_references)
+        if lpips is None:
+            raise ValueError("evaluate_views: lpips_references needs lpips= (the LpipsVGG that made them)")
+        for r in lpips_references:
+            if getattr(r, "precision", None) != "f32":
+                raise ValueError(f"evaluate_views: reported LPIPS is the float32 term; a reference given has precision="
+                                 f"{getattr(r, 'precision', None)!r}")
     from types import SimpleNamespace
 
     from .diff_gaussian_rasterization import RasterContext
@@ -172,6 +185,8 @@ def evaluate_views(pc, cameras, gts, regions, bg, transforms=None, translation=N
     regions = list(regions) if regions is not None else [None] * n
     if len(gts) != n or len(regions) != n or n == 0:
         raise ValueError("evaluate_views: one ground truth and one region (or None) per camera")
+    if lpips_references is not None and len(lpips_references) != n:
+        raise ValueError("evaluate_views: one LPIPS reference per camera")
     per = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * n
     transforms, translation = per(transforms), per(translation)
     dev = pc._xyz.device
@@ -194,7 +209,8 @@ def evaluate_views(pc, cameras, gts, regions, bg, transforms=None, translation=N
                     image = render(cameras[i], pc, pipe, bg, transforms=transforms[i], translation=translation[i])["render"]
                     report.add(image, gts[i], regions[i], out_image)
                     if lpips_fn is not None:
-                        report.extra += lpips_fn(out_image, torch.clamp(gts[i], 0.0, 1.0)).mean().double()
+                        truth = torch.clamp(gts[i], 0.0, 1.0) if lpips_references is None else lpips_references[i]
+                        report.extra += lpips_fn(out_image, truth).mean().double()
             s = report.sums()
             cx.check_status()
             if cx.read_dropped_frames() == 0:

@@ -61,6 +61,14 @@ class MossStep:
     LPIPS has the size of the region at capture in its launches and every replayed frame must have exactly that crop size.  Under
     replay nothing on the host sees the region; :meth:`check` does, and raises on a region the capture cannot serve.
 
+    ``lpips_reference``: a static ``lpips.LpipsReference`` -- ``LpipsReference.empty(lpips_net, lpips_capacity)``, or one of the crop's
+    size without a capacity -- that ``compute()`` hands to ``lpips_vgg_roi_fused`` in ``gt_image``'s place: LPIPS then runs VGG16 on
+    the render alone.  Build the per-camera references once (``refs, nbytes = lpips.reference_cache(lpips_net, gt_images, regions,
+    lpips_capacity)``, 122 floats per pixel of the capacity each) and change frame by ``step.lpips_reference.copy_(refs[k])`` beside
+    the input copies and ``region.copy_``.  The step's result is the same (bit for bit where the kernel shapes agree:
+    ``lpips.LpipsReference``); :meth:`check` raises when the loaded reference's crop is not the region's.  None (the default): the
+    step is what it was.
+
     ``lrs``: ``{"auto_regression": lr, "cross_attention_lbs": lr}`` (MOSS: 2.5e-4 and 1e-4), optionally with rates for the Gaussian
     groups by their ``param_groups()`` names (``xyz``, ``features`` -- a number or ``(lr_dc, lr_rest)`` --, ``opacity``, ``scaling``,
     ``rotation``; default: the reference's).
@@ -97,7 +105,8 @@ class MossStep:
 
     ``terms`` (7 floats on the device, :data:`TERM_NAMES`): the six loss terms and the total of the last step."""
 
-    def __init__(self, pc, view, gt_image, bkgd_mask, region, bg, lpips_net, lrs, context=None, stats=None, lpips_capacity=None):
+    def __init__(self, pc, view, gt_image, bkgd_mask, region, bg, lpips_net, lrs, context=None, stats=None, lpips_capacity=None,
+                 lpips_reference=None):
         from .diff_gaussian_rasterization import RasterContext
         from .dist import GradBucket
         from .optim import FlatAdamW
@@ -118,6 +127,14 @@ class MossStep:
             from .lpips import resolve_capacity
             lpips_capacity = resolve_capacity("MossStep", lpips_capacity, *region.bound.shape)
         self.lpips_capacity = lpips_capacity
+        if lpips_reference is not None:
+            from .lpips import LpipsReference
+            if not isinstance(lpips_reference, LpipsReference):
+                raise TypeError(f"MossStep: lpips_reference must be an lpips.LpipsReference, got {type(lpips_reference).__name__}")
+            if lpips_reference.capacity != lpips_capacity:
+                raise ValueError(f"MossStep: lpips_reference is laid out for capacity {lpips_reference.capacity} and lpips_capacity is "
+                                 f"{lpips_capacity} (LpipsReference.empty(lpips_net, lpips_capacity))")
+        self.lpips_reference = lpips_reference
         self._captured_crop = None                           # (h, w) of the region at capture: what LPIPS launched for without a capacity
         dev = pc._xyz.device
         self.context = cx = context if context is not None else RasterContext()
@@ -176,7 +193,8 @@ class MossStep:
         image, gt = out["render"], self.gt_image
         photometric = training_loss_moss_fused(image, out["render_alpha"], gt, self.bkgd_mask, self.region, w["ssim"], w["mask_l2"],
                                                terms_out=self._terms[:4])
-        lpips = lpips_vgg_roi_fused(self.lpips_net, image, gt, self.region, capacity=self.lpips_capacity).reshape(())
+        truth = gt if self.lpips_reference is None else self.lpips_reference         # (the ground truth's half, computed once)
+        lpips = lpips_vgg_roi_fused(self.lpips_net, image, truth, self.region, capacity=self.lpips_capacity).reshape(())
         nll = out["pose_out"]["nll"].mean()
         s3im = s3im_loss_roi_fused(image, gt, self.region)
         loss = photometric + w["lpips"] * lpips + w["nll"] * nll + w["s3im"] * s3im
@@ -343,10 +361,15 @@ class MossStep:
         """``GraphedStep.check()``: verifies the last replayed frame, counts the dropped ones (``dropped_frames``) and re-captures
         when the binning capacity has grown.  Synchronises; call it every few hundred steps.  True if it re-captured.  Raises if the
         region loaded now is one the captured LPIPS does not serve: a crop beyond ``lpips_capacity``, or, without a capacity, a crop
-        of another size than the one captured (its LPIPS term was taken on a crop of the captured size)."""
+        of another size than the one captured (its LPIPS term was taken on a crop of the captured size); or, with
+        ``lpips_reference``, a reference loaded now whose crop is not the region's (its rows were read at the region's size)."""
         if self.graphed is None:
             raise RuntimeError("MossStep.check(): nothing is captured")
         h, w = int(self.region.xywh[3]), int(self.region.xywh[2])
+        if self.lpips_reference is not None and self.lpips_reference.crop != (h, w):
+            raise RuntimeError(f"MossStep.check(): lpips_reference holds a crop of {self.lpips_reference.crop} and the region's is "
+                               f"{h}x{w}: the LPIPS term of the last replay compared the render with another view's ground truth "
+                               "(step.lpips_reference.copy_(refs[k]) goes with region.copy_)")
         if self.lpips_capacity is not None:
             if h > self.lpips_capacity[0] or w > self.lpips_capacity[1]:
                 raise RuntimeError(f"MossStep.check(): the region's crop {h}x{w} exceeds lpips_capacity {self.lpips_capacity[0]}x"

@@ -12,6 +12,12 @@ SH degree 3, synthetic LPIPS weights, a 192 x 256 region:
 
     python scripts/moss_step_times.py [--replays 300] [--sizes 6890,45695] [--only captured,baseline,profile] [--out DIR]
                                       [--lpips-precision f32|bf16|bf16x3]
+    python scripts/moss_step_times.py --lpips-reference [--replays 300]
+
+``--lpips-reference``: the captured step at P = 45 695 over its three frames WITH ``MossStep(lpips_reference=)`` -- one
+``lpips.LpipsReference`` per frame built before the clock starts, ``step.lpips_reference.copy_(refs[k])`` per replay INSIDE the timed
+window beside the five input copies -- and without, LPIPS precisions f32 and bf16, the four runs alternated and the whole sequence
+twice (eight processes); the table gives each pair's ratio and the spread of the control between the two repetitions.
 
 Every measurement is a process of its own under ``timeout -k 10``; the script stops at the first one that does not exit with 0.  A time
 is the wall clock around ``replays`` back-to-back steps between two device synchronisations, after a warm-up.  Needs a GPU.
@@ -99,25 +105,34 @@ def _timed(fn, replays, dev, load):
     return (time.perf_counter() - t0) / replays
 
 
-def measure_captured(P, replays, lpips_precision="f32"):
+def measure_captured(P, replays, lpips_precision="f32", lpips_reference=False):
     import torch
     from moss_amd.train import MossStep
     dev = torch.device("cuda:0")
     w = _world(P, dev, unified=True, lpips_precision=lpips_precision)
-    step = MossStep(w["pc"], w["cam"], w["gt"], w["bkgd"], w["region"], w["bg"], w["lpips"], {"auto_regression": LR_HEAD, "cross_attention_lbs": LR_NET})
+    kw, refs = {}, None
+    if lpips_reference:                                      # one reference per frame (here of one ground truth: what is timed is the copy)
+        from moss_amd import lpips as mlp
+        refs, nbytes = mlp.reference_cache(w["lpips"], [w["gt"]] * 3, [w["region"]] * 3)
+        kw["lpips_reference"] = mlp.LpipsReference.empty(w["lpips"], refs[0].crop, static=True).copy_(refs[0])
+    step = MossStep(w["pc"], w["cam"], w["gt"], w["bkgd"], w["region"], w["bg"], w["lpips"], {"auto_regression": LR_HEAD, "cross_attention_lbs": LR_NET},
+                    **kw)
     step.capture(warmup=3)
     frames = [_frame(k, dev) for k in range(3)]
 
     def load(i):                                             # a new frame per replay: five small copies into the static inputs
         for key, v in frames[i % 3].items():
             w["cam"].smpl_param[key].copy_(v)
+        if refs is not None:                                 # ... and the frame's reference: 122 floats per crop pixel
+            step.lpips_reference.copy_(refs[i % 3])
 
     dt = _timed(step, replays, dev, load)
     step.check()
     out = step()
     torch.cuda.synchronize(dev)
     assert step.dropped_frames == 0 and float(out["render"].abs().max()) > 0 and bool(torch.isfinite(out["terms"]).all())
-    return {"form": "captured", "P": P, "lpips_precision": lpips_precision, "replays": replays, "us_per_step": round(dt * 1e6, 1), "it_per_s": round(1.0 / dt, 1),
+    return {"form": "captured", "P": P, "lpips_precision": lpips_precision, "lpips_reference": bool(lpips_reference),
+            "reference_bytes_per_camera": refs[0].nbytes if refs else 0, "replays": replays, "us_per_step": round(dt * 1e6, 1), "it_per_s": round(1.0 / dt, 1),
             "steps": list(step.step_counts()), "total_loss": float(out["terms"][-1])}
 
 
@@ -179,6 +194,38 @@ def kernel_table(directory, top=25):
     return rows[:top]
 
 
+def reference_comparison(a, P=45695):
+    """With and without references, f32 and bf16, each run a process of its own, the sequence twice."""
+    os.makedirs(a.out, exist_ok=True)
+    me = [sys.executable, os.path.abspath(__file__), "--package-root", os.path.abspath(a.package_root), "--replays", str(a.replays)]
+    results = []
+    for rep in (1, 2):
+        for prec in ("f32", "bf16"):
+            for ref in (False, True):
+                name = f"captured_{P}_{prec}_{'reference' if ref else 'two_image'}_{rep}"
+                cmd = (["timeout", "-k", "10", str(STEP_TIMEOUT)] + me + ["--lpips-precision", prec, "--worker", "captured", "--P", str(P)]
+                       + (["--with-reference"] if ref else []))
+                r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, cwd=os.path.abspath(a.package_root))
+                with open(os.path.join(a.out, name + ".log"), "w") as f:
+                    f.write(r.stdout)
+                line = next((ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")), None)
+                if r.returncode != 0 or line is None:
+                    print(f"{name}: exit {r.returncode}; stopping (log: {os.path.join(a.out, name + '.log')})\n" + r.stdout[-3000:], flush=True)
+                    raise SystemExit(1)
+                res = dict(json.loads(line[7:]), job=name, repetition=rep)
+                results.append(res)
+                print(json.dumps(res), flush=True)
+    print("| LPIPS precision | two-image us (1, 2) | spread | reference us (1, 2) | reference / two-image (1, 2) | bytes per camera |\n|---|---|---|---|---|---|")
+    for prec in ("f32", "bf16"):
+        t = {ref: [r["us_per_step"] for r in results if r["lpips_precision"] == prec and r["lpips_reference"] == ref] for ref in (False, True)}
+        spread = abs(t[False][0] - t[False][1]) / (0.5 * sum(t[False]))
+        nbytes = next(r["reference_bytes_per_camera"] for r in results if r["lpips_reference"])
+        print(f"| {prec} | {t[False][0]:.1f}, {t[False][1]:.1f} | {100 * spread:.2f} % | {t[True][0]:.1f}, {t[True][1]:.1f} | "
+              f"{t[True][0] / t[False][0]:.4f}, {t[True][1] / t[False][1]:.4f} | {nbytes} |")
+    with open(os.path.join(a.out, "reference_results.json"), "w") as f:
+        json.dump(results, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--replays", type=int, default=300)
@@ -186,6 +233,9 @@ def main():
     ap.add_argument("--only", default="captured,baseline,profile")
     ap.add_argument("--out", default="moss_step_times_out")
     ap.add_argument("--lpips-precision", default="f32", choices=("f32", "bf16", "bf16x3"), help="the LPIPS net's operand precision (LpipsVGG(precision=))")
+    ap.add_argument("--lpips-reference", action="store_true",
+                    help="the captured step at P = 45 695 with and without MossStep(lpips_reference=), f32 and bf16, alternated twice")
+    ap.add_argument("--with-reference", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--package-root", default=os.path.dirname(HERE), help="the checkout whose moss_amd is measured")
     ap.add_argument("--worker", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--P", type=int, default=0, help=argparse.SUPPRESS)
@@ -194,8 +244,11 @@ def main():
     if a.worker:
         if a.replays < 200:
             raise SystemExit("at least 200 replays per measurement")
-        print("RESULT " + json.dumps({"captured": measure_captured, "baseline": measure_baseline}[a.worker](a.P, a.replays, a.lpips_precision)), flush=True)
+        extra = (True,) if a.with_reference else ()
+        print("RESULT " + json.dumps({"captured": measure_captured, "baseline": measure_baseline}[a.worker](a.P, a.replays, a.lpips_precision, *extra)), flush=True)
         return
+    if a.lpips_reference:
+        return reference_comparison(a)
     os.makedirs(a.out, exist_ok=True)
     sizes = [int(x) for x in a.sizes.split(",")]
     only = a.only.split(",")
