@@ -950,6 +950,24 @@ int moss_knn_grid_query(int Nr, int Nq, int k, const char* workspace, size_t wor
                         float* dist_out, long long* idx_out, void* stream);
 
 /*
+ * The nearest reference of every query, k = 1, against a vertex set that never changes, through an index built ONCE: replaces MOSS's
+ * per-step knn(t_vertices, query_pts) (scene/gaussian_model.py:827; the vertices are view.big_pose_world_vertex, the same every
+ * step) and the vertex distance of the final prune (:657).  Exact: ids and distances equal moss_knn_query(k = 1) bit for bit, ties
+ * to the lower vertex index; a query with a non-finite coordinate gets id -1 and distance +inf, as there.  (csrc/nearest_vertex.hip)
+ *   moss_nearest_vertex_index_bytes(V): device bytes of the index, 1 <= V <= 65536 (0 outside that range).
+ *   moss_nearest_vertex_build: vertices (V,3) fp32 -> index (caller-owned; a snapshot of the vertices: Morton-ordered blocks of 64
+ *     with their boxes).  Three launches on `stream`, no host read.
+ *   moss_nearest_vertex_query: points (P,3) fp32 -> ids_out (P) int64, dist_out (P) fp32 Euclidean distances or NULL.  ONE launch on
+ *     `stream`, no host read, no allocation: capturable.  The index is read-only.  P = 0 is a no-op.
+ * Bad arguments (V outside 1..65536, P < 0, a NULL pointer, index_bytes below moss_nearest_vertex_index_bytes(V)) return
+ * MOSS_ERR_INVALID_ARG with moss_last_error() set and launch nothing.
+ */
+size_t moss_nearest_vertex_index_bytes(int V);
+int moss_nearest_vertex_build(int V, const float* vertices, char* index, size_t index_bytes, void* stream);
+int moss_nearest_vertex_query(int V, int P, const char* index, size_t index_bytes, const float* points,
+                              long long* ids_out, float* dist_out /* may be NULL */, void* stream);
+
+/*
  * Densification bookkeeping, one launch, no host synchronisation.  Replaces, for vis = radii > 0,
  *   gaussians.max_radii2D[vis] = max(max_radii2D[vis], radii[vis])                          (train_ZJU.py:173)
  *   xyz_gradient_accum[vis] += norm(viewspace_points.grad[vis,:2], dim=-1); denom[vis] += 1  (scene/gaussian_model.py:815-817)

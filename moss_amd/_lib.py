@@ -63,6 +63,12 @@ def _declare(lib):
     lib.moss_knn_grid_build.argtypes = [_i, _p, _p, C.c_size_t, _p]
     lib.moss_knn_grid_query.restype = _i
     lib.moss_knn_grid_query.argtypes = [_i, _i, _i, _p, C.c_size_t, _p, _p, _p, _p]
+    lib.moss_nearest_vertex_index_bytes.restype = C.c_size_t
+    lib.moss_nearest_vertex_index_bytes.argtypes = [_i]
+    lib.moss_nearest_vertex_build.restype = _i
+    lib.moss_nearest_vertex_build.argtypes = [_i, _p, _p, C.c_size_t, _p]
+    lib.moss_nearest_vertex_query.restype = _i
+    lib.moss_nearest_vertex_query.argtypes = [_i, _i, _p, C.c_size_t, _p, _p, _p, _p]
     lib.moss_densify_stats.restype = _i
     lib.moss_densify_stats.argtypes = [_i, _p, _p, _i, _p, _p, _p, _p]
     lib.moss_neighbour_kl.restype = _i

@@ -34,6 +34,7 @@ SOURCES = {
     "preprocess.hip": ["-ffp-contract=off"],
     "knn.hip": ["-ffp-contract=off"],
     "knn_query.hip": ["-ffp-contract=off"],
+    "nearest_vertex.hip": ["-ffp-contract=off"],
     "binning.hip": [],
     "blend.hip": [],
     "loss.hip": [],

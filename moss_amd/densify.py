@@ -370,7 +370,8 @@ def merge_rows(index, ids, mask, xyz, features_dc, features_rest, opacity, scali
 
 
 def densify_and_prune_fused(pc, optimizer, stats, joint_F, lbs_weights, max_grad, min_opacity, extent, max_screen_size, t_vertices,
-                            kl_threshold=0.4, surface_mask=None, generator=None, percent_dense=0.01, one_pass=False):
+                            kl_threshold=0.4, surface_mask=None, generator=None, percent_dense=0.01, one_pass=False,
+                            template_index=None):
     """``GaussianModel.densify_and_prune`` (:621-666) on a ``GaussianSet`` + ``FlatAdamW`` (or an ``optim.FlatAdamWRows`` over several:
     ``MossStep.rows``) + ``DensifyStats``, in MOSS's order:
     clone-append; split-append and its prune; merge-append and its prune; the final prune -- every selection and every new row from
@@ -389,6 +390,9 @@ def densify_and_prune_fused(pc, optimizer, stats, joint_F, lbs_weights, max_grad
     is one re-layout, the split-append with its prune one, the merge-append with its prune one, the final prune one; same bits.  The
     report then carries ``relayouts`` (at most 4), and ``host_reads`` includes the read of a row map's length where the phase's
     count does not already give it (the merge, whose mask ``merge_rows`` extends on the device).
+
+    ``template_index``: a ``knn_cuda.TemplateIndex`` over ``t_vertices``; the final prune's vertex distance (:657) then comes from it
+    (the same distances, no grid build).
 
     Follow it with ``surgery.densification_event(pc, optimizer, rows_changed=True, context=..., graphed=..., probe=...)``.
     Returns a report: rows per phase and ``host_reads``, the reads of the decision ops themselves (one count per phase and the
@@ -468,8 +472,11 @@ def densify_and_prune_fused(pc, optimizer, stats, joint_F, lbs_weights, max_grad
             report["merged"] = n
         # ---- the final prune (:650-664)
         xyz, _, _, opa, scl, _ = gaussians()
-        tv = t_vertices.detach().reshape(1, -1, 3).to(dev).float()
-        dist = knn(tv, xyz[None], 1)[0].reshape(-1)
+        if template_index is not None:
+            dist = template_index.query(xyz, want_dist=True)[1]
+        else:
+            tv = t_vertices.detach().reshape(1, -1, 3).to(dev).float()
+            dist = knn(tv, xyz[None], 1)[0].reshape(-1)
         max_radii = stats.max_radii2D if stats is not None else torch.zeros((xyz.shape[0],), device=dev)
         mask, _, n, _ = _prune_select(opa, scl, max_radii, dist, min_opacity, extent, max_screen_size, True)
         if n and one_pass:

@@ -9,6 +9,14 @@ cell grid over the references (``moss_knn_grid_build`` / ``moss_knn_grid_query``
 return identical results, ties included.  ``KnnGrid`` keeps a built grid for reference sets that do not change between calls
 (MOSS's template vertices, scene/gaussian_model.py:827).  The original wheel is a binary that is not part of the reference
 repository, so this replacement is "parity unpinned": its tests compare with an exhaustive search.
+
+``TemplateIndex`` (opt-in; nothing above uses it) is the op for the k = 1 query against those template vertices alone
+(csrc/nearest_vertex.hip, C ABI ``moss_nearest_vertex_build`` / ``moss_nearest_vertex_query``): the vertices sorted along a Morton
+curve and cut into blocks of 64 with their boxes, built once per subject; a query is ONE launch in which a wave works on a point,
+prunes the blocks by their boxes and evaluates the few that are left, 64 vertices in 64 lanes.  Ids and distances are those of
+``knn(ref, query, 1)`` bit for bit, ties included.  ``lbs.coarse_deform_c2source`` uses ``model.template_index`` when the model has
+one, ``densify.densify_and_prune_fused(template_index=)`` takes it for the prune's vertex distance, and
+``train.MossStep(template_index=True)`` builds and hands it to both.
 """
 from __future__ import annotations
 
@@ -19,7 +27,7 @@ import torch.nn as nn
 
 from .._lib import call, check, lib, stream
 
-__all__ = ["KNN", "KnnGrid", "knn"]
+__all__ = ["KNN", "KnnGrid", "TemplateIndex", "knn"]
 
 GRID_MIN_REF = 2048        # below this the brute-force kernel (one launch) is as fast as building a grid (8 launches)
 
@@ -64,6 +72,44 @@ class KnnGrid:
             idx = torch.empty((Nq, k), dtype=torch.int64, device=self.device)
         call("moss_knn_grid_query", self.device, self.Nr, Nq, k, self._ws.data_ptr(), self._bytes, pts.data_ptr(), dist.data_ptr(), idx.data_ptr())
         return dist, idx
+
+
+class TemplateIndex:
+    """The nearest vertex of ``vertices`` ((V, 3) or (1, V, 3), 1 <= V <= 65 536) for any number of ``query(points)`` calls: built
+    once (a snapshot: later changes of ``vertices`` are not seen), one launch per query, no host read, no allocation inside the
+    launch -- a query with preallocated outputs can be captured.  Exactly ``knn(vertices, points, 1)``, ties to the lower index."""
+
+    def __init__(self, vertices: torch.Tensor):
+        if vertices.dim() == 3 and vertices.shape[0] == 1:
+            vertices = vertices[0]
+        if vertices.dim() != 2 or vertices.shape[1] != 3 or not 1 <= vertices.shape[0] <= 65536:
+            raise RuntimeError("TemplateIndex: expected vertices (V, 3) or (1, V, 3) with 1 <= V <= 65536")
+        if not vertices.is_cuda:
+            raise RuntimeError("knn needs GPU tensors; this op has no CPU path")
+        self.V = int(vertices.shape[0])
+        self.device = vertices.device
+        v_c = vertices.detach().float().contiguous()
+        self._bytes = int(lib().moss_nearest_vertex_index_bytes(self.V))
+        self._index = torch.empty(self._bytes, dtype=torch.uint8, device=self.device)
+        call("moss_nearest_vertex_build", self.device, self.V, v_c.data_ptr(), self._index.data_ptr(), self._bytes)
+
+    def query(self, points: torch.Tensor, want_dist: bool = False, ids: torch.Tensor = None, dist: torch.Tensor = None):
+        """``points (P, 3)`` -> ``ids (P,)`` int64, and with ``want_dist`` also ``dist (P,)`` float32 Euclidean distances.  A point
+        with a non-finite coordinate gets id -1 and distance +inf.  ``ids`` / ``dist``: outputs to write into (contiguous)."""
+        if points.dim() != 2 or points.shape[1] != 3 or points.device != self.device:
+            raise RuntimeError("TemplateIndex.query: expected points (P, 3) on the index's device")
+        P = int(points.shape[0])
+        pts = points.detach().float().contiguous()
+        if ids is None:
+            ids = torch.empty((P,), dtype=torch.int64, device=self.device)
+        if want_dist and dist is None:
+            dist = torch.empty((P,), dtype=torch.float32, device=self.device)
+        for name, t, dt in (("ids", ids, torch.int64), ("dist", dist if want_dist else None, torch.float32)):
+            if t is not None and (t.shape != (P,) or t.dtype != dt or t.device != self.device or not t.is_contiguous()):
+                raise RuntimeError(f"TemplateIndex.query: {name} must be a contiguous ({P},) {dt} tensor on the index's device")
+        call("moss_nearest_vertex_query", self.device, self.V, P, self._index.data_ptr(), self._bytes, pts.data_ptr(), ids.data_ptr(),
+             dist.data_ptr() if want_dist else None)
+        return (ids, dist) if want_dist else ids
 
 
 def knn(ref: torch.Tensor, query: torch.Tensor, k: int, impl: str = None):

@@ -396,7 +396,8 @@ def coarse_deform_c2source(model, query_pts, params, t_params, t_vertices, lbs_w
     """Drop-in for ``GaussianModel.coarse_deform_c2source`` (scene/gaussian_model.py:820-923): same arguments, same
     ``(smpl_src_pts, world_src_pts, bweights, transforms, translation)`` of shapes (1,P,3), (1,P,3), (1,P,J), (1,P,3,3), (1,P,3) --
     ``translation`` only with ``return_transl``, else None.  ``model`` supplies ``SMPL_NEUTRAL`` (the body model, on the GPU) and
-    ``knn`` (``moss_amd.knn_cuda.KNN(k=1, transpose_mode=True)``), as MOSS's ``GaussianModel`` does.  The per-Gaussian work is
+    ``knn`` (``moss_amd.knn_cuda.KNN(k=1, transpose_mode=True)``), as MOSS's ``GaussianModel`` does; a model with a ``template_index``
+    (a ``knn_cuda.TemplateIndex`` over ``t_vertices``, an addition) is asked through it instead: the same ids.  The per-Gaussian work is
     :func:`lbs_deform`; the kinematic chain and the blend shapes are torch, or with ``fused_frame`` (an addition, default off) the
     fused op :func:`smpl_frame_fused`.  ``bweights`` carries no gradient (MOSS only accumulates it for densification).  Batch size 1,
     as MOSS renders."""
@@ -406,8 +407,15 @@ def coarse_deform_c2source(model, query_pts, params, t_params, t_vertices, lbs_w
     W = body["weights"]
     J = W.shape[-1]
     P = query_pts.shape[1]
-    _, vert_ids = model.knn(t_vertices.float(), query_pts.float())
-    ids = vert_ids.reshape(P)
+    index = getattr(model, "template_index", None)
+    if index is not None:
+        # (an addition, opt-in: a knn_cuda.TemplateIndex built once over t_vertices -- the same ids, one launch, no grid build per call)
+        if index.V != t_vertices.shape[-2]:
+            raise ValueError(f"coarse_deform_c2source: model.template_index holds {index.V} vertices, t_vertices has {t_vertices.shape[-2]}")
+        ids = index.query(query_pts[0])
+    else:
+        _, vert_ids = model.knn(t_vertices.float(), query_pts.float())
+        ids = vert_ids.reshape(P)
     if fused_frame:
         c32 = lambda t: t.float().contiguous()                                        # noqa: E731
         A_big, A_obs, d, _ = smpl_frame_fused(

@@ -69,6 +69,11 @@ class MossStep:
     ``lpips.LpipsReference``); :meth:`check` raises when the loaded reference's crop is not the region's.  None (the default): the
     step is what it was.
 
+    ``template_index=True``: the nearest-vertex query of the LBS deformation (``knn(t_vertices, xyz)``: a cell grid built and walked on
+    every step) goes through a ``knn_cuda.TemplateIndex`` built HERE, once, from ``view.big_pose_world_vertex`` -- one launch per step,
+    the same ids bit for bit; it is set as ``pc.template_index`` and also serves :meth:`densify_and_prune`'s vertex distance.  The
+    vertices are snapshotted: a step whose template changes needs a new step.  False (the default): the step is what it was.
+
     ``lrs``: ``{"auto_regression": lr, "cross_attention_lbs": lr}`` (MOSS: 2.5e-4 and 1e-4), optionally with rates for the Gaussian
     groups by their ``param_groups()`` names (``xyz``, ``features`` -- a number or ``(lr_dc, lr_rest)`` --, ``opacity``, ``scaling``,
     ``rotation``; default: the reference's).
@@ -106,7 +111,7 @@ class MossStep:
     ``terms`` (7 floats on the device, :data:`TERM_NAMES`): the six loss terms and the total of the last step."""
 
     def __init__(self, pc, view, gt_image, bkgd_mask, region, bg, lpips_net, lrs, context=None, stats=None, lpips_capacity=None,
-                 lpips_reference=None):
+                 lpips_reference=None, template_index=False):
         from .diff_gaussian_rasterization import RasterContext
         from .dist import GradBucket
         from .optim import FlatAdamW
@@ -135,6 +140,11 @@ class MossStep:
                 raise ValueError(f"MossStep: lpips_reference is laid out for capacity {lpips_reference.capacity} and lpips_capacity is "
                                  f"{lpips_capacity} (LpipsReference.empty(lpips_net, lpips_capacity))")
         self.lpips_reference = lpips_reference
+        self.template_index = None
+        if template_index:
+            from .knn_cuda import TemplateIndex
+            # (does not depend on P: densification events and re-captures keep it)
+            self.template_index = pc.template_index = TemplateIndex(view.big_pose_world_vertex)
         self._captured_crop = None                           # (h, w) of the region at capture: what LPIPS launched for without a capacity
         dev = pc._xyz.device
         self.context = cx = context if context is not None else RasterContext()
@@ -322,7 +332,8 @@ class MossStep:
         t0, reads0, relayouts0 = self._begin_event()
         decision = densify_and_prune_fused(self.pc, self.rows, self.stats, self.joint_F_sum, self.lbs_weights_sum, max_grad, min_opacity,
                                            extent, max_screen_size, self.view.big_pose_world_vertex, kl_threshold=kl_threshold,
-                                           surface_mask=surface_mask, generator=generator, one_pass=one_pass)
+                                           surface_mask=surface_mask, generator=generator, one_pass=one_pass,
+                                           template_index=self.template_index)
         moved = any(decision[k] for k in ("cloned", "split", "merged", "pruned"))
         return self._event(t0, reads0, relayouts0, decision=decision, rows_changed=moved)
 

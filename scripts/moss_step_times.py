@@ -13,11 +13,16 @@ SH degree 3, synthetic LPIPS weights, a 192 x 256 region:
     python scripts/moss_step_times.py [--replays 300] [--sizes 6890,45695] [--only captured,baseline,profile] [--out DIR]
                                       [--lpips-precision f32|bf16|bf16x3]
     python scripts/moss_step_times.py --lpips-reference [--replays 300]
+    python scripts/moss_step_times.py --template-index [--replays 300] [--only profile]
 
 ``--lpips-reference``: the captured step at P = 45 695 over its three frames WITH ``MossStep(lpips_reference=)`` -- one
 ``lpips.LpipsReference`` per frame built before the clock starts, ``step.lpips_reference.copy_(refs[k])`` per replay INSIDE the timed
 window beside the five input copies -- and without, LPIPS precisions f32 and bf16, the four runs alternated and the whole sequence
 twice (eight processes); the table gives each pair's ratio and the spread of the control between the two repetitions.
+
+``--template-index``: the captured step at P = 45 695 WITH ``MossStep(template_index=True)`` -- the nearest-vertex query through a
+``knn_cuda.TemplateIndex`` built once -- and without, in the same eight-process scheme; with ``--only profile`` instead ONE
+``rocprofv3 --kernel-trace --stats`` run of the step with the index.
 
 Every measurement is a process of its own under ``timeout -k 10``; the script stops at the first one that does not exit with 0.  A time
 is the wall clock around ``replays`` back-to-back steps between two device synchronisations, after a warm-up.  Needs a GPU.
@@ -105,7 +110,7 @@ def _timed(fn, replays, dev, load):
     return (time.perf_counter() - t0) / replays
 
 
-def measure_captured(P, replays, lpips_precision="f32", lpips_reference=False):
+def measure_captured(P, replays, lpips_precision="f32", lpips_reference=False, template_index=False):
     import torch
     from moss_amd.train import MossStep
     dev = torch.device("cuda:0")
@@ -115,6 +120,8 @@ def measure_captured(P, replays, lpips_precision="f32", lpips_reference=False):
         from moss_amd import lpips as mlp
         refs, nbytes = mlp.reference_cache(w["lpips"], [w["gt"]] * 3, [w["region"]] * 3)
         kw["lpips_reference"] = mlp.LpipsReference.empty(w["lpips"], refs[0].crop, static=True).copy_(refs[0])
+    if template_index:
+        kw["template_index"] = True
     step = MossStep(w["pc"], w["cam"], w["gt"], w["bkgd"], w["region"], w["bg"], w["lpips"], {"auto_regression": LR_HEAD, "cross_attention_lbs": LR_NET},
                     **kw)
     step.capture(warmup=3)
@@ -132,7 +139,7 @@ def measure_captured(P, replays, lpips_precision="f32", lpips_reference=False):
     torch.cuda.synchronize(dev)
     assert step.dropped_frames == 0 and float(out["render"].abs().max()) > 0 and bool(torch.isfinite(out["terms"]).all())
     return {"form": "captured", "P": P, "lpips_precision": lpips_precision, "lpips_reference": bool(lpips_reference),
-            "reference_bytes_per_camera": refs[0].nbytes if refs else 0, "replays": replays, "us_per_step": round(dt * 1e6, 1), "it_per_s": round(1.0 / dt, 1),
+            "template_index": bool(template_index), "reference_bytes_per_camera": refs[0].nbytes if refs else 0, "replays": replays, "us_per_step": round(dt * 1e6, 1), "it_per_s": round(1.0 / dt, 1),
             "steps": list(step.step_counts()), "total_loss": float(out["terms"][-1])}
 
 
@@ -194,17 +201,18 @@ def kernel_table(directory, top=25):
     return rows[:top]
 
 
-def reference_comparison(a, P=45695):
-    """With and without references, f32 and bf16, each run a process of its own, the sequence twice."""
+def ab_comparison(a, key, worker_flag, names, P=45695):
+    """The captured step with and without the option ``key`` of ``measure_captured`` (``worker_flag`` switches it on in the worker),
+    LPIPS precisions f32 and bf16, each run a process of its own, the sequence twice.  ``names``: (without, with) for the table."""
     os.makedirs(a.out, exist_ok=True)
     me = [sys.executable, os.path.abspath(__file__), "--package-root", os.path.abspath(a.package_root), "--replays", str(a.replays)]
     results = []
     for rep in (1, 2):
         for prec in ("f32", "bf16"):
-            for ref in (False, True):
-                name = f"captured_{P}_{prec}_{'reference' if ref else 'two_image'}_{rep}"
+            for on in (False, True):
+                name = f"captured_{P}_{prec}_{names[on].replace('-', '_').replace(' ', '_')}_{rep}"
                 cmd = (["timeout", "-k", "10", str(STEP_TIMEOUT)] + me + ["--lpips-precision", prec, "--worker", "captured", "--P", str(P)]
-                       + (["--with-reference"] if ref else []))
+                       + ([worker_flag] if on else []))
                 r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, cwd=os.path.abspath(a.package_root))
                 with open(os.path.join(a.out, name + ".log"), "w") as f:
                     f.write(r.stdout)
@@ -215,14 +223,15 @@ def reference_comparison(a, P=45695):
                 res = dict(json.loads(line[7:]), job=name, repetition=rep)
                 results.append(res)
                 print(json.dumps(res), flush=True)
-    print("| LPIPS precision | two-image us (1, 2) | spread | reference us (1, 2) | reference / two-image (1, 2) | bytes per camera |\n|---|---|---|---|---|---|")
+    nbytes = max(r["reference_bytes_per_camera"] for r in results)
+    print(f"| LPIPS precision | {names[0]} us (1, 2) | spread | {names[1]} us (1, 2) | spread | {names[1]} / {names[0]} (1, 2) |"
+          + (" bytes per camera |" if nbytes else "") + "\n|---|---|---|---|---|---|" + ("---|" if nbytes else ""))
     for prec in ("f32", "bf16"):
-        t = {ref: [r["us_per_step"] for r in results if r["lpips_precision"] == prec and r["lpips_reference"] == ref] for ref in (False, True)}
-        spread = abs(t[False][0] - t[False][1]) / (0.5 * sum(t[False]))
-        nbytes = next(r["reference_bytes_per_camera"] for r in results if r["lpips_reference"])
-        print(f"| {prec} | {t[False][0]:.1f}, {t[False][1]:.1f} | {100 * spread:.2f} % | {t[True][0]:.1f}, {t[True][1]:.1f} | "
-              f"{t[True][0] / t[False][0]:.4f}, {t[True][1] / t[False][1]:.4f} | {nbytes} |")
-    with open(os.path.join(a.out, "reference_results.json"), "w") as f:
+        t = {on: [r["us_per_step"] for r in results if r["lpips_precision"] == prec and r[key] == on] for on in (False, True)}
+        spread = {on: abs(t[on][0] - t[on][1]) / (0.5 * sum(t[on])) for on in (False, True)}
+        print(f"| {prec} | {t[False][0]:.1f}, {t[False][1]:.1f} | {100 * spread[False]:.2f} % | {t[True][0]:.1f}, {t[True][1]:.1f} | "
+              f"{100 * spread[True]:.2f} % | {t[True][0] / t[False][0]:.4f}, {t[True][1] / t[False][1]:.4f} |" + (f" {nbytes} |" if nbytes else ""))
+    with open(os.path.join(a.out, key + "_results.json"), "w") as f:
         json.dump(results, f, indent=1)
 
 
@@ -236,6 +245,10 @@ def main():
     ap.add_argument("--lpips-reference", action="store_true",
                     help="the captured step at P = 45 695 with and without MossStep(lpips_reference=), f32 and bf16, alternated twice")
     ap.add_argument("--with-reference", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--template-index", action="store_true",
+                    help="the captured step at P = 45 695 with and without MossStep(template_index=True), f32 and bf16, alternated twice; "
+                         "with --only profile: one rocprofv3 run of the step with the index")
+    ap.add_argument("--with-template-index", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--package-root", default=os.path.dirname(HERE), help="the checkout whose moss_amd is measured")
     ap.add_argument("--worker", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--P", type=int, default=0, help=argparse.SUPPRESS)
@@ -244,11 +257,13 @@ def main():
     if a.worker:
         if a.replays < 200:
             raise SystemExit("at least 200 replays per measurement")
-        extra = (True,) if a.with_reference else ()
+        extra = (a.with_reference, a.with_template_index) if a.worker == "captured" else ()
         print("RESULT " + json.dumps({"captured": measure_captured, "baseline": measure_baseline}[a.worker](a.P, a.replays, a.lpips_precision, *extra)), flush=True)
         return
     if a.lpips_reference:
-        return reference_comparison(a)
+        return ab_comparison(a, "lpips_reference", "--with-reference", ("two-image", "reference"))
+    if a.template_index and a.only != "profile":
+        return ab_comparison(a, "template_index", "--with-template-index", ("grid", "template index"))
     os.makedirs(a.out, exist_ok=True)
     sizes = [int(x) for x in a.sizes.split(",")]
     only = a.only.split(",")
@@ -259,7 +274,8 @@ def main():
     if "profile" in only:
         prof = os.path.join(os.path.abspath(a.out), "rocprof")
         jobs.append(("profile", ["timeout", "-k", "10", str(STEP_TIMEOUT), "rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv",
-                                 "-d", prof, "-o", "moss_step", "--"] + me + ["--worker", "captured", "--P", str(max(sizes))]))
+                                 "-d", prof, "-o", "moss_step", "--"] + me + ["--worker", "captured", "--P", str(max(sizes))]
+                     + (["--with-template-index"] if a.template_index else [])))
     results = []
     for name, cmd in jobs:
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, cwd=os.path.abspath(a.package_root))
