@@ -201,12 +201,61 @@ __constant__ const float SH_C2[5] = { 1.0925484305920792f, -1.0925484305920792f,
 __constant__ const float SH_C3[7] = { -0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f, 0.3731763325901154f,
                                       -0.4570457994644658f, 1.445305721320277f, -0.5900435899266435f };
 
+// SH -> RGB of one Gaussian (forward.cu:20-71), the expressions in the reference's order; `sh` = its M x 3 record (global memory or a
+// staged LDS row), `p` = the (posed) mean.  Sets bit c of `clamp_bits` where channel c was clamped at zero.
+__device__ __forceinline__ float3 sh_to_rgb(const float* sh, int D, float3 p, float3 campos, uint8_t& clamp_bits)
+{
+    float3 dir = make_float3(p.x - campos.x, p.y - campos.y, p.z - campos.z);
+    const float len = sqrtf(dir.x * dir.x + dir.y * dir.y + dir.z * dir.z);
+    dir.x = dir.x / len; dir.y = dir.y / len; dir.z = dir.z / len;
+    const float x = dir.x, y = dir.y, z = dir.z;
+    float res[3];
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+#define SH(k) sh[3 * (k) + c]
+        float result = SH_C0 * SH(0);
+        if (D > 0) {
+            result = result - SH_C1 * y * SH(1) + SH_C1 * z * SH(2) - SH_C1 * x * SH(3);
+            if (D > 1) {
+                const float xx = x * x, yy = y * y, zz = z * z;
+                const float xy = x * y, yz = y * z, xz = x * z;
+                result = result +
+                    SH_C2[0] * xy * SH(4) +
+                    SH_C2[1] * yz * SH(5) +
+                    SH_C2[2] * (2.0f * zz - xx - yy) * SH(6) +
+                    SH_C2[3] * xz * SH(7) +
+                    SH_C2[4] * (xx - yy) * SH(8);
+                if (D > 2) {
+                    result = result +
+                        SH_C3[0] * y * (3.0f * xx - yy) * SH(9) +
+                        SH_C3[1] * xy * z * SH(10) +
+                        SH_C3[2] * y * (4.0f * zz - xx - yy) * SH(11) +
+                        SH_C3[3] * z * (2.0f * zz - 3.0f * xx - 3.0f * yy) * SH(12) +
+                        SH_C3[4] * x * (4.0f * zz - xx - yy) * SH(13) +
+                        SH_C3[5] * z * (xx - yy) * SH(14) +
+                        SH_C3[6] * x * (xx - 3.0f * yy) * SH(15);
+                }
+            }
+        }
+#undef SH
+        result += 0.5f;
+        if (result < 0) clamp_bits |= (uint8_t)(1u << c);
+        res[c] = fmaxf(result, 0.0f);
+    }
+    return make_float3(res[0], res[1], res[2]);
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // K1: forward preprocess, one thread per Gaussian (grid-stride).  Also counts instances per tile: lanes add into
 // an LDS-private histogram and the block flushes its non-zero bins with one global atomic each.
 // ---------------------------------------------------------------------------------------------------------
 constexpr int SH_ROW_F = 49;           // LDS row stride (floats) of a staged 48-float SH record
-__global__ void __launch_bounds__(256)
+// (three waves per SIMD -- three blocks per CU -- is the register budget: the 48 SH registers are live across part A)
+// SCATTER = scatter mode (below), an instantiation of its own: with the mode a run-time branch, the wait for the SH record -- the
+// oldest loads in flight -- could not tell how many younger requests (the reservations' atomics) are outstanding behind it on every
+// path, and waited for all of them.
+template <bool SCATTER>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3)))
 preprocess_forward_kernel(int P, int D, int M, int W, int H, int gx, int gy,
                           float tan_fovx, float tan_fovy, float focal_x, float focal_y, float scale_modifier, int prefiltered,
                           const float* __restrict__ means3D, const float* __restrict__ shs, const float* __restrict__ colors_precomp,
@@ -214,7 +263,7 @@ preprocess_forward_kernel(int P, int D, int M, int W, int H, int gx, int gy,
                           const float* __restrict__ cov3D_precomp, const float* __restrict__ viewmatrix,
                           const float* __restrict__ projmatrix, const float* __restrict__ cam_pos,
                           GeomView g, uint32_t* __restrict__ tile_count, uint32_t* __restrict__ header /* the error-flag word */,
-                          int* __restrict__ radii_out, int lds_hist, int stage_sh, const float* __restrict__ transforms, int raw,
+                          int* __restrict__ radii_out, int lds_hist_arg, int stage_sh, const float* __restrict__ transforms, int raw,
                           unsigned long long* __restrict__ stamps /* diagnostics: 8 words per block, else NULL */,
                           const float* __restrict__ translation /* RAW_POSE only, may be NULL */,
                           uint64_t* __restrict__ keys /* scatter mode (below): the tiles' key buckets, else NULL */, uint32_t key_stride)
@@ -234,7 +283,8 @@ preprocess_forward_kernel(int P, int D, int M, int W, int H, int gx, int gy,
     // writes its keys there at once.  Nothing needs the scan before the sort, whose workgroups turn the counts into their own chunk
     // tables (binning.hip, chunk_sort_kernel).  A tile that outgrows its bucket drops the frame like a capacity overflow (flagged by
     // the scan block, `needed` scaled so that the caller's next capacity fits it).
-    const bool scatter = keys != nullptr;
+    constexpr bool scatter = SCATTER;
+    const bool lds_hist = SCATTER || lds_hist_arg;           // (scatter mode works on the LDS histogram: no global atomic in its tile loops)
     if (lds_hist) {
         for (int i = threadIdx.x; i < T; i += blockDim.x) s_hist[i] = 0;
         __syncthreads();
@@ -247,69 +297,107 @@ preprocess_forward_kernel(int P, int D, int M, int W, int H, int gx, int gy,
     // every thread runs the same number of iterations (the slot reservation below uses block barriers)
     const int iters = (P + gridDim.x * blockDim.x - 1) / (gridDim.x * blockDim.x);
     // SH staging (M == 16 only): per thread a record is 48 floats at a 192-byte stride, i.e. each of the 48 scalar loads of a wave
-    // touches 64 cache lines.  The block's 256 records of this iteration are instead read with coalesced 16-byte loads into LDS
-    // (row stride 49 words: conflict-free) and evaluated from there -- same values, same arithmetic, so still bit-exact.
+    // touches 64 cache lines.  The records of this iteration are instead read with coalesced 16-byte loads, every wave its own 64, held
+    // in registers across part A and written to LDS in front of part B (row stride 49 words: conflict-free), which evaluates them
+    // from there -- same values, same arithmetic, so still bit-exact.
     float* const s_shf = reinterpret_cast<float*>(s_hist + (lds_hist ? ((T + 3) & ~3) : 0));
+    typedef float v4f __attribute__((ext_vector_type(4)));
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     for (int it = 0; it < iters; it++) {
         const int idx = (it * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x;
-        if (stage_sh) {
-            const size_t base4 = (size_t)(it * gridDim.x + blockIdx.x) * blockDim.x * 12, total4 = (size_t)P * 12;
-            // DEGREE-AWARE: only the float4 parts of a record that hold a coefficient of the ACTIVE degree are fetched -- 1 / 3 / 7 / 12 of
-            // 12 at degree 0 / 1 / 2 / 3 (MOSS trains below degree 3 for iterations 1-2999, train_ZJU.py:85-86); the others are never read
-            // by the evaluation below.  Buffer loads: an out-of-range offset returns 0 WITHOUT a memory request, and no branch surrounds
-            // the loads (the twelve stay in flight together).  (the launcher stages only while the tensor is < 4 GB: 32-bit offsets)
-            const int na = (3 * (D + 1) * (D + 1) + 3) >> 2;
-            const __amdgpu_buffer_rsrc_t rs_sh = __builtin_amdgcn_make_buffer_rsrc((void*)shs, 0, 0xffffff00u, 0x00020000u);
-            typedef float v4f __attribute__((ext_vector_type(4)));
-            v4f v[12];
+        // (the camera matrices stay in SGPRs: redefined per iteration as far as the compiler can tell, their vector copies cannot be
+        // hoisted out of this loop, where some twenty of them stood in VGPRs across part A, beside the 48 SH registers)
+#pragma unroll
+        for (int i = 0; i < 16; i++) { asm volatile("" : "+s"(view[i])); asm volatile("" : "+s"(proj[i])); }
+        asm volatile("" : "+s"(tan_fovx)); asm volatile("" : "+s"(tan_fovy)); asm volatile("" : "+s"(focal_x)); asm volatile("" : "+s"(focal_y));
+        asm volatile("" : "+s"(scale_modifier)); asm volatile("" : "+s"(W)); asm volatile("" : "+s"(H));   // (W, H: their double copies)
+        // (the SH requests' offsets, worked out -- and pinned -- in front of the first request, so that nothing but requests stands between
+        // the geometry loads and the SH loads below; 32-bit: a staged tensor is < 4 GB)
+        uint32_t sh_off[12];
+        {
+            const uint32_t base4 = ((uint32_t)(it * gridDim.x + blockIdx.x) * blockDim.x + (uint32_t)wv * 64u) * 12u, total4 = (uint32_t)P * 12u;
+            const int na = stage_sh ? (3 * (D + 1) * (D + 1) + 3) >> 2 : 0;
 #pragma unroll
             for (int j = 0; j < 12; j++) {
-                const int f = threadIdx.x + j * blockDim.x;  // (base4 is a multiple of 12: f % 12 is the float4's part of its record)
-                const size_t a = min(base4 + (size_t)f, total4 - 1);
-                v[j] = __builtin_amdgcn_raw_buffer_load_b128(rs_sh, (f % 12) < na ? (uint32_t)a * 16u : 0xffffffffu, 0, 0);
+                const int f = lane + j * 64;                 // (base4 is a multiple of 12: f % 12 is the float4's part of its record)
+                sh_off[j] = (f % 12) < na ? min(base4 + (uint32_t)f, total4 - 1u) * 16u : 0xffffffffu;
+                asm volatile("" : "+v"(sh_off[j]));
             }
-            __syncthreads();                                 // the previous iteration's readers are done
-#pragma unroll
-            for (int j = 0; j < 12; j++) {
-                const int f = threadIdx.x + j * blockDim.x;
-                float* d = &s_shf[(f / 12) * SH_ROW_F + (f % 12) * 4];
-                d[0] = v[j].x; d[1] = v[j].y; d[2] = v[j].z; d[3] = v[j].w;
-            }
-            __syncthreads();
         }
-        // Every per-Gaussian input is requested HERE, unconditionally (clamped index), before anything is waited for: read where
-        // they are used -- means, then (behind the frustum test) scales / rotations, then (behind the covariance and colour math) the
-        // opacity -- each was a memory round trip of its own on this kernel's critical path (~2 us each at 1.5 waves per SIMD).
+        const __amdgpu_buffer_rsrc_t rs_sh = __builtin_amdgcn_make_buffer_rsrc((void*)shs, 0, 0xffffff00u, 0x00020000u);
+        // ONE ROUND TRIP: every per-Gaussian input is requested HERE, unconditionally (clamped index), and nothing is waited for
+        // before the SH loads below are out as well.  First the inputs of the geometry (part A: means, opacity, scales, rotations, the
+        // 3x3 transform, the translation), then the SH record: loads return in order, so what the rectangle needs arrives first, and
+        // the 19 MB of SH stream in behind it while part A, the histogram and the bucket reservations run.  (Read where they are used
+        // -- means, then scales / rotations behind the frustum test, then the opacity -- each was a round trip of its own, ~2 us at
+        // 1.5 waves per SIMD; staged and waited for IN FRONT of these requests, as until round 6, the SH burst was another.)
         const size_t ic = (size_t)min(idx, P - 1);
-        const float3 p_ld = make_float3(means3D[3 * ic], means3D[3 * ic + 1], means3D[3 * ic + 2]);
-        const float opa_ld = opacities[ic];
-        float cov_ld[6] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f }, sc_ld[3] = { 0.f, 0.f, 0.f }, q_ld[4] = { 0.f, 0.f, 0.f, 0.f };
-        float tm_ld[9] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
-        if (cov3D_precomp != nullptr) {                      // (kernel-uniform branches)
+        float3 p_ld = make_float3(means3D[3 * ic], means3D[3 * ic + 1], means3D[3 * ic + 2]);
+        float opa_ld = opacities[ic];
+        // (no branch surrounds these loads either -- a uniform branch around a load ends in a copy of its result, i.e. in a wait, in front
+        // of the requests that follow: an input the call does not have is read from the view matrix instead, 16 floats every call has,
+        // and never used)
+        const bool has_cov = cov3D_precomp != nullptr, has_tm = !has_cov && transforms != nullptr;
+        const bool has_tr = (raw & RAW_POSE) && translation != nullptr;
+        const float* const cov_p = has_cov ? cov3D_precomp + 6 * ic : viewmatrix;
+        const float* const sc_p = has_cov ? viewmatrix : scales + 3 * ic;
+        const float* const q_p = has_cov ? viewmatrix : rotations + 4 * ic;
+        const float* const tm_p = has_tm ? transforms + 9 * ic : viewmatrix;
+        const float* const col_p = colors_precomp != nullptr ? colors_precomp + 3 * ic : viewmatrix;
+        const float* const tr_p = has_tr ? translation + 3 * ic : viewmatrix;
+        float cov_ld[6], sc_ld[3], q_ld[4], tm_ld[9];
 #pragma unroll
-            for (int i = 0; i < 6; i++) cov_ld[i] = cov3D_precomp[6 * ic + i];
-        } else {
+        for (int i = 0; i < 6; i++) cov_ld[i] = cov_p[i];
 #pragma unroll
-            for (int i = 0; i < 3; i++) sc_ld[i] = scales[3 * ic + i];
+        for (int i = 0; i < 3; i++) sc_ld[i] = sc_p[i];
 #pragma unroll
-            for (int i = 0; i < 4; i++) q_ld[i] = rotations[4 * ic + i];
-            if (transforms != nullptr) {
+        for (int i = 0; i < 4; i++) q_ld[i] = q_p[i];
 #pragma unroll
-                for (int i = 0; i < 9; i++) tm_ld[i] = transforms[9 * ic + i];
-            }
+        for (int i = 0; i < 9; i++) tm_ld[i] = tm_p[i];
+        float3 col_ld = make_float3(col_p[0], col_p[1], col_p[2]);
+        float3 tr_ld = make_float3(tr_p[0], tr_p[1], tr_p[2]);
+        // SH staging (M == 16 only), the requests: the twelve coalesced 16-byte loads per lane that bring in the 64 records of THIS
+        // WAVE's lanes (each wave stages the rows it reads itself: no block barrier around the staging, a wave never waits for the
+        // slowest SH load of its block).  They are held in registers until part B.
+        // DEGREE-AWARE: only the float4 parts of a record that hold a coefficient of the ACTIVE degree are fetched -- 1 / 3 / 7 / 12 of
+        // 12 at degree 0 / 1 / 2 / 3 (MOSS trains below degree 3 for iterations 1-2999, train_ZJU.py:85-86); the others are never read
+        // by the evaluation below.  Buffer loads: an out-of-range offset returns 0 WITHOUT a memory request, and no branch surrounds
+        // the loads (the twelve stay in flight together).  (the launcher stages only while the tensor is < 4 GB: 32-bit offsets)
+        // Not staged (M != 16, given colours): every offset is out of range, nothing is requested -- a branch around the loads would end
+        // in a merge behind which the wait for the geometry inputs above could no longer tell the SH loads from them.
+        v4f shv[12];
+#pragma unroll
+        for (int j = 0; j < 12; j++) shv[j] = __builtin_amdgcn_raw_buffer_load_b128(rs_sh, sh_off[j], 0, 0);
+        // (pinned: the geometry inputs must be in registers HERE, or the compiler sinks their loads down to their uses -- behind the
+        // SH requests is where the wave waits for them alone, the younger SH loads still in flight)
+        asm volatile("" : "+v"(p_ld.x)); asm volatile("" : "+v"(p_ld.y)); asm volatile("" : "+v"(p_ld.z));
+        asm volatile("" : "+v"(tr_ld.x)); asm volatile("" : "+v"(tr_ld.y)); asm volatile("" : "+v"(tr_ld.z));
+        asm volatile("" : "+v"(col_ld.x)); asm volatile("" : "+v"(col_ld.y)); asm volatile("" : "+v"(col_ld.z));
+        asm volatile("" : "+v"(opa_ld));
+#pragma unroll
+        for (int i = 0; i < 6; i++) asm volatile("" : "+v"(cov_ld[i]));
+#pragma unroll
+        for (int i = 0; i < 3; i++) asm volatile("" : "+v"(sc_ld[i]));
+#pragma unroll
+        for (int i = 0; i < 4; i++) asm volatile("" : "+v"(q_ld[i]));
+#pragma unroll
+        for (int i = 0; i < 9; i++) asm volatile("" : "+v"(tm_ld[i]));
+        if (!has_tm) {                                       // (what the call does not have is zero, as ever)
+#pragma unroll
+            for (int i = 0; i < 9; i++) tm_ld[i] = 0.f;
         }
-        float3 col_ld = make_float3(0.f, 0.f, 0.f);
-        if (colors_precomp != nullptr) col_ld = make_float3(colors_precomp[3 * ic], colors_precomp[3 * ic + 1], colors_precomp[3 * ic + 2]);
-        float3 tr_ld = make_float3(0.f, 0.f, 0.f);
-        if ((raw & RAW_POSE) && translation != nullptr) tr_ld = make_float3(translation[3 * ic], translation[3 * ic + 1], translation[3 * ic + 2]);
+        if (!has_tr) tr_ld = make_float3(0.f, 0.f, 0.f);
         FSTAMP(1);
+        // ---- PART A: everything that needs no colour -- pose, view and projection transforms, cov3D, cov2D, conic, radius, pixel,
+        // rectangle, depth, opacity, cull extents, cell count.  The histogram, the bucket reservations and the keys hang on this alone.
         int out_radius = 0; uint32_t out_tiles = 0; uint2 out_rect = make_uint2(0u, 0u);
         float out_depth = 0.0f;
         uint32_t out_cells = 0u;                             // gradient-record cells of this Gaussian (common.h: box_cells)
+        float3 p_orig = make_float3(0.f, 0.f, 0.f);
         if (idx < P) do {
             // RAW_POSE: the canonical position is posed here, p = T x + t (the reference's caller does it with torch ops,
             // gaussian_renderer/__init__.py:74-77); rows of T times x summed left to right, then the translation
-            const float3 p_orig = (raw & RAW_POSE) ? pose_point(tm_ld, p_ld, tr_ld) : p_ld;
+            p_orig = (raw & RAW_POSE) ? pose_point(tm_ld, p_ld, tr_ld) : p_ld;
             const float3 p_view = xform4x3(p_orig, view);
             if (p_view.z <= 0.2f) {                                   // in_frustum, auxiliary.h:154
                 if (prefiltered) atomicOr(header, ERRFLAG_PREFILTERED);
@@ -363,52 +451,6 @@ preprocess_forward_kernel(int P, int D, int M, int W, int H, int gx, int gy,
             const int y1 = min(gy, max(0, sat_int((pix.y + rad + TILE - 1) / TILE)));
             if ((uint32_t)(x1 - x0) * (uint32_t)(y1 - y0) == 0u) break;
 
-            float3 rgb;
-            uint8_t clamp_bits = 0;
-            if (colors_precomp == nullptr) {
-                const float* sh = stage_sh ? &s_shf[threadIdx.x * SH_ROW_F] : shs + (size_t)idx * M * 3;
-                float3 dir = make_float3(p_orig.x - campos.x, p_orig.y - campos.y, p_orig.z - campos.z);
-                const float len = sqrtf(dir.x * dir.x + dir.y * dir.y + dir.z * dir.z);
-                dir.x = dir.x / len; dir.y = dir.y / len; dir.z = dir.z / len;
-                const float x = dir.x, y = dir.y, z = dir.z;
-                float res[3];
-#pragma unroll
-                for (int c = 0; c < 3; c++) {
-#define SH(k) sh[3 * (k) + c]
-                    float result = SH_C0 * SH(0);
-                    if (D > 0) {
-                        result = result - SH_C1 * y * SH(1) + SH_C1 * z * SH(2) - SH_C1 * x * SH(3);
-                        if (D > 1) {
-                            const float xx = x * x, yy = y * y, zz = z * z;
-                            const float xy = x * y, yz = y * z, xz = x * z;
-                            result = result +
-                                SH_C2[0] * xy * SH(4) +
-                                SH_C2[1] * yz * SH(5) +
-                                SH_C2[2] * (2.0f * zz - xx - yy) * SH(6) +
-                                SH_C2[3] * xz * SH(7) +
-                                SH_C2[4] * (xx - yy) * SH(8);
-                            if (D > 2) {
-                                result = result +
-                                    SH_C3[0] * y * (3.0f * xx - yy) * SH(9) +
-                                    SH_C3[1] * xy * z * SH(10) +
-                                    SH_C3[2] * y * (4.0f * zz - xx - yy) * SH(11) +
-                                    SH_C3[3] * z * (2.0f * zz - 3.0f * xx - 3.0f * yy) * SH(12) +
-                                    SH_C3[4] * x * (4.0f * zz - xx - yy) * SH(13) +
-                                    SH_C3[5] * z * (xx - yy) * SH(14) +
-                                    SH_C3[6] * x * (xx - 3.0f * yy) * SH(15);
-                            }
-                        }
-                    }
-#undef SH
-                    result += 0.5f;
-                    if (result < 0) clamp_bits |= (uint8_t)(1u << c);
-                    res[c] = fmaxf(result, 0.0f);
-                }
-                rgb = make_float3(res[0], res[1], res[2]);
-            } else {
-                rgb = col_ld;
-            }
-
             // Conservative extent of the region where this Gaussian can reach alpha >= 1/255 (power >= -tau,
             // tau = ln(255*opacity)): half-widths sqrt(2*tau*cov_xx), sqrt(2*tau*cov_yy) of the ellipse's bounding box,
             // widened by 1e-4 relative + 0.01 px against rounding.  Since round 5 the box does more than let the blend kernels SKIP
@@ -434,8 +476,6 @@ preprocess_forward_kernel(int P, int D, int M, int W, int H, int gx, int gy,
 
             g.geo[4 * (size_t)idx + 0] = make_float4(pix.x, pix.y, hx, hy);  // position + cull extents (the cull record)
             g.geo[4 * (size_t)idx + 1] = make_float4(conic.x, conic.y, conic.z, opa);
-            g.geo[4 * (size_t)idx + 2] = make_float4(rgb.x, rgb.y, rgb.z, p_view.z);
-            g.clamped[idx] = clamp_bits;
             out_radius = rad;
             out_depth = p_view.z;
             out_tiles = (uint32_t)(y1 - y0) * (uint32_t)(x1 - x0);
@@ -449,55 +489,21 @@ preprocess_forward_kernel(int P, int D, int M, int W, int H, int gx, int gy,
             if (lds_hist) atomicAdd(&s_hist[t], 1u);
             else atomicAdd(&tile_count[t], 1u);
         });
-        // ---- scatter mode, first half: one returning atomic per (block, non-empty tile) reserves the block's run in the tile's bucket and
-        // adds to the tile's count.  Four tiles per thread at a time, as BUFFER atomics whose offset is out of range for an empty tile
-        // (dropped without a memory request): no branch around the atomic, so the four are in flight together (a device-scope
-        // returning atomic is ~2 us; see scatter_kernel, which this replaces on the asynchronous path).  The LAST batch's answers --
-        // for up to 1024 tiles the only one -- are waited for BEHIND the slot-run prefix sum and its stores below, not here.
-        uint32_t pend_c[4] = { 0u, 0u, 0u, 0u }, pend_old[4] = { 0u, 0u, 0u, 0u };
-        int pend_b0 = 0;
-        if (scatter) {
-            __syncthreads();                                 // this iteration's counts are complete
-            const __amdgpu_buffer_rsrc_t rs_cnt = __builtin_amdgcn_make_buffer_rsrc((void*)tile_count, 0, 0xffffff00u, 0x00020000u);
-            for (int b0 = 0; b0 < T; b0 += 4 * (int)blockDim.x) {
-                uint32_t c[4], old[4];
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    const int i = b0 + u * (int)blockDim.x + (int)threadIdx.x;
-                    c[u] = i < T ? s_hist[i] : 0u;
-                }
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    const int i = b0 + u * (int)blockDim.x + (int)threadIdx.x;
-                    old[u] = (uint32_t)__builtin_amdgcn_raw_ptr_buffer_atomic_add_i32((int)c[u], rs_cnt, c[u] ? (uint32_t)i * 4u : 0xfffffffcu /* out of range AND dword-aligned */, 0, 0);
-                }
-                if (b0 + 4 * (int)blockDim.x < T) {          // (kernel-uniform) not the last batch: its answers are needed now
-#pragma unroll
-                    for (int u = 0; u < 4; u++) {
-                        const int i = b0 + u * (int)blockDim.x + (int)threadIdx.x;
-                        if (c[u]) s_hist[i] = old[u];        // (the count word becomes the CURSOR of the pass below: it starts at the run's start)
-                    }
-                } else {
-#pragma unroll
-                    for (int u = 0; u < 4; u++) { pend_c[u] = c[u]; pend_old[u] = old[u]; }
-                    pend_b0 = b0;
-                }
-            }
-        }
         // rec_offsets: each Gaussian needs a private run of `out_cells` records in the record pool (the reference's counterpart: the
         // device-wide inclusive scan of tiles_touched, rasterizer_impl.cu:279).  Here: the run's start RELATIVE to the block's group of 256
         // Gaussians (a block prefix sum) and the group's total; the scan block that rides along with the sort kernel turns the totals
         // into group bases.  (Round 1-2 reserved the group's run with ONE returning atomic per block on a header word: 391 atomics on
         // one address, 11 ns each -- the last block got its answer 4.5 us after the first: the tail of this kernel, scripts/sort_stamps.py.)
+        // It stands HERE, in front of the reservations and of part B: it needs part A alone, its barrier is the one the reservations need
+        // anyway, and its stores are older than the reservations' atomics -- the SH wait of part B leaves exactly those in flight.
         uint32_t rincl = out_cells;
-        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {
             const uint32_t ry = __shfl_up(rincl, d);
             if (lane >= d) rincl += ry;
         }
         if (lane == 63) s_wsum[wv] = rincl;
-        __syncthreads();
+        __syncthreads();                                     // ONE barrier: this iteration's tile counts are complete, and the waves' cell sums
         if (threadIdx.x == 0 && (it * gridDim.x + blockIdx.x) * blockDim.x < (unsigned)P)
             g.group_rtot[it * gridDim.x + blockIdx.x] = s_wsum[0] + s_wsum[1] + s_wsum[2] + s_wsum[3];
         uint32_t rwbase = 0u;
@@ -511,7 +517,80 @@ preprocess_forward_kernel(int P, int D, int M, int W, int H, int gx, int gy,
                                                      __uint_as_float(rwbase + rincl - out_cells), __uint_as_float(out_cells));
             if (radii_out) radii_out[idx] = out_radius;
         }
-        __syncthreads();
+        // ---- scatter mode, first half: one returning atomic per (block, non-empty tile) reserves the block's run in the tile's bucket and
+        // adds to the tile's count.  Four tiles per thread at a time, as BUFFER atomics whose offset is out of range for an empty tile
+        // (dropped without a memory request): no branch around the atomic, so the four are in flight together (a device-scope
+        // returning atomic is ~2 us; see scatter_kernel, which this replaces on the asynchronous path).  The LAST batch's answers --
+        // for up to 1024 tiles the only one -- are waited for BEHIND part B (the SH wait, its staging, the colours), not here: they are in flight
+        // while the SH record arrives.
+        uint32_t pend_c[4] = { 0u, 0u, 0u, 0u }, pend_old[4] = { 0u, 0u, 0u, 0u };
+        int pend_b0 = 0;
+        if (scatter) {
+            const __amdgpu_buffer_rsrc_t rs_cnt = __builtin_amdgcn_make_buffer_rsrc((void*)tile_count, 0, 0xffffff00u, 0x00020000u);
+            // (the last batch stands outside the loop, in straight-line code: no loop header between the SH requests and their wait)
+            int b0 = 0;
+            for (; b0 + 4 * (int)blockDim.x < T; b0 += 4 * (int)blockDim.x) {   // not the last batch: its answers are needed now
+                uint32_t c[4], old[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const int i = b0 + u * (int)blockDim.x + (int)threadIdx.x;
+                    c[u] = s_hist[i];
+                }
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const int i = b0 + u * (int)blockDim.x + (int)threadIdx.x;
+                    old[u] = (uint32_t)__builtin_amdgcn_raw_ptr_buffer_atomic_add_i32((int)c[u], rs_cnt, c[u] ? (uint32_t)i * 4u : 0xfffffffcu /* out of range AND dword-aligned */, 0, 0);
+                }
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const int i = b0 + u * (int)blockDim.x + (int)threadIdx.x;
+                    asm volatile("" :: "v"(old[u]));         // (every lane has its answer: none is pending behind this loop, where a
+                                                             // pending one would make the last batch's requests wait for all loads, SH included)
+                    if (c[u]) s_hist[i] = old[u];            // (the count word becomes the CURSOR of the pass below: it starts at the run's start)
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const int i = b0 + u * (int)blockDim.x + (int)threadIdx.x;
+                pend_c[u] = i < T ? s_hist[i] : 0u;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const int i = b0 + u * (int)blockDim.x + (int)threadIdx.x;
+                pend_old[u] = (uint32_t)__builtin_amdgcn_raw_ptr_buffer_atomic_add_i32((int)pend_c[u], rs_cnt, pend_c[u] ? (uint32_t)i * 4u : 0xfffffffcu, 0, 0);
+            }
+            pend_b0 = b0;
+        }
+        FSTAMP(3);
+        // ---- PART B: the colour.  Only here is the SH record waited for -- the oldest loads in flight: neither part A's stores nor the
+        // reservations' answers are waited for with them -- and staged: every wave writes the 64 rows its own lanes read (row stride 49
+        // words: conflict-free), so a wave barrier is all the staging needs, also against the previous iteration's reads.
+        if (stage_sh) {
+#pragma unroll
+            for (int j = 0; j < 12; j++) {
+                const int f = wv * 768 + lane + j * 64;      // (768 = 64 rows x 12 float4: f / 12 is the row in the block, f % 12 the part)
+                float* d = &s_shf[(f / 12) * SH_ROW_F + (f % 12) * 4];
+                d[0] = shv[j].x; d[1] = shv[j].y; d[2] = shv[j].z; d[3] = shv[j].w;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
+        if (out_tiles) {                                     // (part A ran to its end: idx < P, a rectangle of at least one tile)
+            float3 rgb;
+            uint8_t clamp_bits = 0;
+            // (two calls: one pointer that is either would be a FLAT one, whose loads count as vector-memory loads -- waiting for a row's
+            // word would wait for the reservations' answers as well)
+            if (stage_sh)
+                rgb = sh_to_rgb(&s_shf[threadIdx.x * SH_ROW_F], D, p_orig, campos, clamp_bits);
+            else if (colors_precomp == nullptr)
+                rgb = sh_to_rgb(shs + (size_t)idx * M * 3, D, p_orig, campos, clamp_bits);
+            else
+                rgb = col_ld;
+            g.geo[4 * (size_t)idx + 2] = make_float4(rgb.x, rgb.y, rgb.z, out_depth);
+            g.clamped[idx] = clamp_bits;
+        }
+        FSTAMP(7);
         if (scatter) {
             // ---- scatter mode, second half: the reserved runs' starts, then the keys -- (depth bits << 32 | Gaussian id) -- into them (slot
             // order inside a bucket is arbitrary: the sort orders by the whole key)
@@ -520,6 +599,7 @@ preprocess_forward_kernel(int P, int D, int M, int W, int H, int gx, int gy,
                 const int i = pend_b0 + u * (int)blockDim.x + (int)threadIdx.x;
                 if (pend_c[u]) s_hist[i] = pend_old[u];       // (the count word becomes the cursor of the pass below)
             }
+            FSTAMP(6);
             __syncthreads();
             const uint64_t key = out_tiles ? (((uint64_t)__float_as_uint(out_depth) << 32) | (uint32_t)idx) : 0ull;
             wave_for_each_tile(out_rect, gx, key, [&](int t, uint64_t k) {
@@ -531,6 +611,8 @@ preprocess_forward_kernel(int P, int D, int M, int W, int H, int gx, int gy,
                 for (int i = threadIdx.x; i < T; i += blockDim.x) s_hist[i] = 0;
                 __syncthreads();
             }
+        } else if (it + 1 < iters) {
+            __syncthreads();                                 // (the waves' cell sums are rewritten by the next iteration)
         }
         FSTAMP(4);
     }
@@ -1553,17 +1635,21 @@ void launch_preprocess_forward(const FrameParams& fp, const float* means3D, cons
     // (dynamic LDS beyond the default 64 KB of a launch -- 1024 x 1024: 16 KB of histogram + 49 KB of SH rows -- is asked for once; two
     // such blocks still fit a CU's 160 KB.  Round 5's first scatter mode kept a second array of run starts beside the histogram: 82 KB
     // there, no SH staging and ONE block per CU)
-    static const bool big_lds = hipFuncSetAttribute(reinterpret_cast<const void*>(preprocess_forward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess;
+    static const bool big_lds =
+        hipFuncSetAttribute(reinterpret_cast<const void*>(preprocess_forward_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(preprocess_forward_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess;
     const int stage_sh = (fp.M == 16 && shs != nullptr && colors_precomp == nullptr && (reinterpret_cast<uintptr_t>(shs) & 15u) == 0 &&
                           (size_t)fp.P * 192u < 0xffffff00u /* the staging loads address the tensor with 32-bit byte offsets */ &&
                           lds_h + lds_s <= (big_lds ? 80u * 1024u : 65536u) && knob("MOSS_PREFWD_STAGE", 1)) ? 1 : 0;
     const size_t lds = lds_h + (stage_sh ? lds_s : 0);
-    MOSS_LAUNCH_TIMED(preprocess_forward_kernel, dim3(blocks), dim3(256), lds, s,
-                       fp.P, fp.D, fp.M, fp.W, fp.H, fp.gx, fp.gy, fp.tan_fovx, fp.tan_fovy, fp.focal_x, fp.focal_y,
-                       fp.scale_modifier, fp.prefiltered, means3D, shs, colors_precomp, opacities, scales, rotations,
-                       cov3D_precomp, fp.view_dev, fp.proj_dev, fp.campos_dev, g, im.tile_count, im.flags_acc, radii_out, lds_hist, stage_sh,
-                       transforms, fp.raw,
-                       (g_stamps && knob("MOSS_SORT_STAMPS", 0)) ? g_stamps + 131072 + 32768 : nullptr, translation, scatter_keys, key_stride);
+#define PREFWD_ARGS fp.P, fp.D, fp.M, fp.W, fp.H, fp.gx, fp.gy, fp.tan_fovx, fp.tan_fovy, fp.focal_x, fp.focal_y,                          \
+                    fp.scale_modifier, fp.prefiltered, means3D, shs, colors_precomp, opacities, scales, rotations,                        \
+                    cov3D_precomp, fp.view_dev, fp.proj_dev, fp.campos_dev, g, im.tile_count, im.flags_acc, radii_out, lds_hist, stage_sh, \
+                    transforms, fp.raw,                                                                                                  \
+                    (g_stamps && knob("MOSS_SORT_STAMPS", 0)) ? g_stamps + 131072 + 32768 : nullptr, translation, scatter_keys, key_stride
+    if (scatter_keys != nullptr) MOSS_LAUNCH_TIMED((preprocess_forward_kernel<true>), dim3(blocks), dim3(256), lds, s, PREFWD_ARGS);
+    else MOSS_LAUNCH_TIMED((preprocess_forward_kernel<false>), dim3(blocks), dim3(256), lds, s, PREFWD_ARGS);
+#undef PREFWD_ARGS
 }
 
 // resident blocks per CU of the per-Gaussian backward (the fused instantiation: the larger one)

@@ -58,8 +58,11 @@ w = s[32768: 32768 + 8 * 4096].reshape(-1, 8).astype(np.float64)
 w = w[w[:, 0] > 0]
 t0 = w[:, 0].min()
 print("preprocess_forward blocks", len(w), "(realtime us, relative to the first block's start)")
-for i, name in ((0, "start"), (1, "loads issued + SH staged"), (2, "geometry done + stored"), (4, "histogram + slot runs"), (5, "flushed, end")):
-    print("   %-28s median %6.2f  p90 %6.2f  max %6.2f" % (name, np.median(w[:, i] - t0) / 100, np.percentile(w[:, i] - t0, 90) / 100, (w[:, i].max() - t0) / 100))
+for i, name in ((0, "start"), (1, "geometry inputs arrived"), (2, "rectangles known (part A)"), (3, "reservations issued"), (7, "SH staged, colours stored"),
+                (6, "answers consumed"), (4, "keys stored"), (5, "flushed, end")):
+    c = w[:, i][w[:, i] > 0]                                  # (words 3 and 6 are stamped in scatter mode only: --async)
+    if len(c):
+        print("   %-28s median %6.2f  p90 %6.2f  max %6.2f" % (name, np.median(c - t0) / 100, np.percentile(c - t0, 90) / 100, (c.max() - t0) / 100))
 
 w = s[16384: 16384 + 8 * 512].reshape(-1, 8).astype(np.float64)
 w = w[w[:, 0] > 0]
