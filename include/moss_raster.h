@@ -675,6 +675,18 @@ typedef struct moss_lbs_weight_net_backward_args {
 int moss_lbs_weight_net_backward(const moss_lbs_weight_net_backward_args* args, void* stream);   /* the adjoint of nets/mlp_delta_weight_lbs.py:31-54 */
 size_t moss_lbs_weight_net_workspace_bytes(int P);  /* scratch of the backward of nets/mlp_delta_weight_lbs.py:31-54; 0 for P <= 0 */
 size_t moss_lbs_weight_net_saved_bytes(int P);      /* what its forward keeps for the backward; 0 for P <= 0 */
+/*
+ * The same pair in the split-bf16 (three-product) mode (additive in ABI 7).  In the five wide products (layers 0-3 and bw_fc) --
+ * forward (activation x weight), data gradient (d pre-activation x weight) and weight gradient (d pre-activation x layer input, summed
+ * over the points) -- both operands are split, hi = bf16(a) (round to nearest even), lo = bf16(a - hi), and a b is taken as
+ * lo(a) hi(b) + hi(a) lo(b) + hi(a) hi(b) on the bf16-input matrix cores; all sums are float32.  The embedding, the biases and their
+ * gradients, the ReLU masks, query / key / value, the scores, the softmax, the output and g_x from d e are float32 as above.  Same
+ * argument blocks, same launches, same refusals, same determinism; `saved` and
+ * the workspace have the SAME layouts and sizes (moss_lbs_weight_net_saved_bytes / _workspace_bytes).  A forward's `saved` belongs to
+ * the backward of the same mode.
+ */
+int moss_lbs_weight_net_forward_bf16x3(const moss_lbs_weight_net_args* args, void* stream);   /* nets/mlp_delta_weight_lbs.py:31-54, split-bf16 products */
+int moss_lbs_weight_net_backward_bf16x3(const moss_lbs_weight_net_backward_args* args, void* stream);   /* the adjoint of nets/mlp_delta_weight_lbs.py:31-54, split-bf16 products */
 
 /*
  * MOSS's LPIPS term (additive in ABI 7): loss_fn_vgg(img_pred, img_gt), train_ZJU.py:121 (weighted 0.5 at :131) and :256 ->

@@ -127,6 +127,10 @@ def _declare(lib):
     lib.moss_lbs_weight_net_forward.argtypes = [_p, _p]
     lib.moss_lbs_weight_net_backward.restype = _i
     lib.moss_lbs_weight_net_backward.argtypes = [_p, _p]
+    lib.moss_lbs_weight_net_forward_bf16x3.restype = _i
+    lib.moss_lbs_weight_net_forward_bf16x3.argtypes = [_p, _p]
+    lib.moss_lbs_weight_net_backward_bf16x3.restype = _i
+    lib.moss_lbs_weight_net_backward_bf16x3.argtypes = [_p, _p]
     lib.moss_lbs_weight_net_workspace_bytes.restype = C.c_size_t
     lib.moss_lbs_weight_net_workspace_bytes.argtypes = [_i]
     lib.moss_lbs_weight_net_saved_bytes.restype = C.c_size_t

@@ -26,8 +26,13 @@
 //     3. fold: the partial blocks are summed in split order into the 12 gradient tensors; one more workgroup folds d K, d V and
 //        forms the gradients of key.*, value.* and Rs from them.
 // Every sum has a fixed order and there is no atomic: results are bitwise reproducible.  Every output element is written.
+//
+// A second, opt-in set of kernels (moss_lbs_weight_net_forward_bf16x3 / _backward_bf16x3; "the split-bf16 mode" below) runs the five
+// wide products -- forward, data gradient and weight gradient -- on v_mfma_f32_32x32x16_bf16 with both operands split in two bf16
+// halves and three products per product; same launches, same layouts of `saved` and the workspace, same order rules.  The f32 kernels
+// are not touched by it.
 #include "common.h"
-#include "mfma_f32.h"
+#include "mfma_bf16.h"
 
 namespace moss {
 
@@ -398,6 +403,404 @@ lbs_weight_net_backward_weights_kernel(int P, int chunk, const float* __restrict
     if (it.bias_off >= 0 && half == 0 && a_ok) out[it.bias_off + j] = bsum;
 }
 
+// ---- the split-bf16 (three-product) mode: moss_lbs_weight_net_forward_bf16x3 / _backward_bf16x3 ---------------------------------------
+// The five wide products (layers 0-3 and bw_fc) forward, in the data gradient and in the weight gradient, on
+// v_mfma_f32_32x32x16_bf16 (mfma_bf16.h): both operands split, hi = bf16(a), lo = bf16(a - hi), and a b taken as
+// lo(a) hi(b) + hi(a) lo(b) + hi(a) hi(b), accumulated in float32.  A lane supplies eight consecutive k per operand; K = 63 pads to 64
+// and 191 to 192 through the same [e, 0, h2] row.  The weights change every step, so there is no pack-once: a weight is split in
+// registers as it is read.  An activation (or a d pre-activation) is split ONCE, when its tile row is stored to LDS as two bf16 planes
+// (the same bytes as the float32 tile).  `saved` and the workspace keep the float32 layouts of the f32 mode (the ReLU masks, the biases'
+// column sums, query / key / value and the head read them as float32), so the two size queries serve both modes; the weight-gradient
+// kernel splits its operands as it reads them, sixteen points per step, and runs the float32 items of the head (query.*, d K, d V)
+// on the f32 loop in the same launch.  Everything else is the f32 mode's code and order.
+constexpr int HB_LD = 136, EHB_LD = 200, QB_LD = 40;     // LDS row strides of the bf16 planes: an odd multiple of 16 bytes mod 256
+constexpr int B_FLOATS = 4 * 1024 > T * HB_LD ? 4 * 1024 : T * HB_LD;   // a pair of planes, or four 32 x 32 float blocks / a float tile
+static_assert(B_FLOATS >= T * H_LD && 2 * T * HB_LD * 2 <= B_FLOATS * 4, "aliased LDS tile");
+
+typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));   // four floats at a float's alignment (a weight row starts anywhere)
+
+// gemm_wt with both operands split: A as two bf16 planes in LDS (this lane's row), W split as it is read
+template <int K, int LD, bool SKIP>
+__device__ __forceinline__ f32x16 gemm_wt3(const float* __restrict__ W, int n, bool n_ok, const __bf16* a_hi, const __bf16* a_lo, int half,
+                                           f32x16 acc, int kbase = 0)
+{
+    const float* w = W + (size_t)(n_ok ? n : 0) * LD;
+#pragma unroll 2
+    for (int k0 = kbase; k0 < kbase + K; k0 += 16) {
+        const int kk = k0 + 8 * half;
+        const bf16x8 ah = *reinterpret_cast<const bf16x8*>(a_hi + kk), al = *reinterpret_cast<const bf16x8*>(a_lo + kk);
+        // this lane's eight weights: W[n][kk ...] (SKIP: the row without its column 63), as two 16-byte reads where all eight exist
+        const int first = SKIP && kk > NE ? kk - 1 : kk, valid = SKIP ? (kk + 8 == NE + 1 ? 7 : 8) : min(8, LD - kk);
+        float bv[8];
+        if (n_ok && valid == 8) {
+            const f32x4u lo4 = *reinterpret_cast<const f32x4u*>(w + first), hi4 = *reinterpret_cast<const f32x4u*>(w + first + 4);
+#pragma unroll
+            for (int s = 0; s < 4; s++) { bv[s] = lo4[s]; bv[4 + s] = hi4[s]; }
+        } else {
+#pragma unroll
+            for (int s = 0; s < 8; s++) bv[s] = n_ok && s < valid ? w[first + s] : 0.0f;
+        }
+        bf16x8 bh, bl;
+        split_bf16x8(bv, bh, bl);
+        mfma16x3(acc, ah, al, bh, bl);
+    }
+    return acc;
+}
+
+// gemm_w with both operands split
+template <int K>
+__device__ __forceinline__ f32x16 gemm_w3(const float* __restrict__ W, int ld, int kvalid, int col, bool col_ok, const __bf16* a_hi,
+                                          const __bf16* a_lo, int half)
+{
+    f32x16 acc = splat(0.0f);
+    const float* w = W + (col_ok ? col : 0);
+#pragma unroll 2
+    for (int k0 = 0; k0 < K; k0 += 16) {
+        const int kk = k0 + 8 * half;
+        const bf16x8 ah = *reinterpret_cast<const bf16x8*>(a_hi + kk), al = *reinterpret_cast<const bf16x8*>(a_lo + kk);
+        float bv[8];
+#pragma unroll
+        for (int s = 0; s < 8; s++) bv[s] = (col_ok && kk + s < kvalid) ? w[(size_t)(kk + s) * ld] : 0.0f;
+        bf16x8 bh, bl;
+        split_bf16x8(bv, bh, bl);
+        mfma16x3(acc, ah, al, bh, bl);
+    }
+    return acc;
+}
+
+__device__ __forceinline__ void store_split(__bf16* hi, __bf16* lo, int idx, float v)
+{
+    __bf16 h, l;
+    split_bf16(v, h, l);
+    hi[idx] = h;
+    lo[idx] = l;
+}
+
+// relu(acc) -> the two LDS planes [row][col] and, with `saved`, the float32 rows of the points that exist
+__device__ __forceinline__ void store_act3(const f32x16& acc, __bf16* hi, __bf16* lo, int ld, int col, int half, float* saved, int sv_col,
+                                           int p0, int P)
+{
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int row = acc_row(r, half);
+        const float v = fmaxf(acc[r], 0.0f);
+        store_split(hi, lo, row * ld + col, v);
+        if (saved && p0 + row < P) saved[(size_t)(p0 + row) * SV_ROW + sv_col] = v;
+    }
+}
+
+__global__ void __launch_bounds__(WG)
+lbs_weight_net_forward_bf16x3_kernel(const moss_lbs_weight_net_args a)
+{
+    __shared__ __attribute__((aligned(16))) __bf16 s_eh_hi[T * EHB_LD], s_eh_lo[T * EHB_LD];   // [e (63), 0, h2 (128)]
+    __shared__ __attribute__((aligned(16))) __bf16 s_a_hi[T * HB_LD], s_a_lo[T * HB_LD];
+    __shared__ __attribute__((aligned(16))) float s_b[B_FLOATS];       // two planes; then bw_fc's four partial blocks (float)
+    __shared__ float s_K[NR * NC], s_V[NR * NC], s_Wq[NF * NF], s_q0[T][NF], s_Q[T][NF], s_s[T][12];
+    __bf16* const s_b_hi = reinterpret_cast<__bf16*>(s_b);
+    __bf16* const s_b_lo = s_b_hi + T * HB_LD;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, half = lane >> 5;
+    const int p0 = blockIdx.x * T, P = a.P;
+    const float* const* par = a.params;
+    float* saved = a.saved;
+
+    head_constants(a.Rs, par, s_K, s_V, s_Wq, tid);
+    for (int i = tid; i < T * 3 * NFREQ; i += WG) {
+        const int pt = i / (3 * NFREQ), r = i % (3 * NFREQ), f = r / 3, d = r % 3;
+        const float xv = p0 + pt < P ? a.x[(size_t)(p0 + pt) * 3 + d] : 0.0f;
+        float sn, cs;
+        sincosf(xv * (float)(1 << f), &sn, &cs);
+        float* sv = saved && p0 + pt < P ? saved + (size_t)(p0 + pt) * SV_ROW + SV_E : nullptr;
+        auto put = [&](int k, float v) {
+            store_split(s_eh_hi, s_eh_lo, pt * EHB_LD + k, v);
+            if (sv) sv[k] = v;
+        };
+        put(3 + 6 * f + d, sn);
+        put(6 + 6 * f + d, cs);
+        if (f == 0) put(d, xv);
+        if (r == 0) put(NE, 0.0f);
+    }
+    __syncthreads();
+
+    const int n = 32 * wave + j;                                        // this lane's output channel in the 128-wide layers
+    const int ea = j * EHB_LD, ha = j * HB_LD;
+    f32x16 acc = gemm_wt3<64, NE, false>(par[P_W0], n, true, s_eh_hi + ea, s_eh_lo + ea, half, splat(par[P_B0][n]));
+    store_act3(acc, s_a_hi, s_a_lo, HB_LD, n, half, saved, SV_H0 + n, p0, P);
+    __syncthreads();
+    acc = gemm_wt3<NH, NH, false>(par[P_W1], n, true, s_a_hi + ha, s_a_lo + ha, half, splat(par[P_B1][n]));
+    store_act3(acc, s_b_hi, s_b_lo, HB_LD, n, half, saved, SV_H1 + n, p0, P);
+    __syncthreads();
+    acc = gemm_wt3<NH, NH, false>(par[P_W2], n, true, s_b_hi + ha, s_b_lo + ha, half, splat(par[P_B2][n]));
+    store_act3(acc, s_eh_hi, s_eh_lo, EHB_LD, 64 + n, half, saved, SV_H2 + n, p0, P);
+    __syncthreads();                                                    // (the planes in s_b were last read before this barrier)
+    acc = gemm_wt3<64 + NH, W3_LD, true>(par[P_W3], n, true, s_eh_hi + ea, s_eh_lo + ea, half, splat(par[P_B3][n]));
+    store_act3(acc, s_a_hi, s_a_lo, HB_LD, n, half, saved, SV_H3 + n, p0, P);
+    __syncthreads();
+    // bw_fc: one 32 x 32 block (24 channels), the k range split over the waves; the four partial blocks go to s_b
+    acc = gemm_wt3<NH / 4, NH, false>(par[P_WFC], j, j < NF, s_a_hi + ha, s_a_lo + ha, half, splat(0.0f), (NH / 4) * wave);
+#pragma unroll
+    for (int r = 0; r < 16; r++) s_b[wave * 1024 + acc_row(r, half) * 32 + j] = acc[r];
+    __syncthreads();
+
+    // the head, float32 as in the f32 kernel: eight threads per point
+    const int pt = tid >> 3, sub = tid & 7;
+    const bool live = p0 + pt < P;
+    float* sv = saved && live ? saved + (size_t)(p0 + pt) * SV_ROW : nullptr;
+#pragma unroll
+    for (int k = sub; k < NF; k += 8) {
+        const float* q = s_b + pt * 32 + k;
+        const float v = (((q[0] + q[1024]) + q[2048]) + q[3072]) + par[P_BFC][k];
+        s_q0[pt][k] = v;
+        if (sv) sv[SV_Q0 + k] = v;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = sub; i < NF; i += 8) {
+        float v = par[P_BQ][i];
+#pragma unroll
+        for (int k = 0; k < NF; k++) v = __fmaf_rn(s_Wq[i * NF + k], s_q0[pt][k], v);
+        s_Q[pt][i] = v;
+        if (sv) sv[SV_Q + i] = v;
+    }
+    __syncthreads();
+    for (int c = sub; c < NC; c += 8) {
+        float v = 0.0f;
+#pragma unroll
+        for (int i = 0; i < NF; i++) v = __fmaf_rn(s_Q[pt][i], s_K[i * NC + c], v);
+        s_s[pt][c] = v / sqrtf((float)NF);
+    }
+    __syncthreads();
+    float att[NC], m = s_s[pt][0], sum = 0.0f;
+#pragma unroll
+    for (int c = 1; c < NC; c++) m = fmaxf(m, s_s[pt][c]);
+#pragma unroll
+    for (int c = 0; c < NC; c++) { att[c] = expf(s_s[pt][c] - m); sum += att[c]; }
+#pragma unroll
+    for (int c = 0; c < NC; c++) att[c] /= sum;
+    if (sv) {
+        if (sub == 0) {
+#pragma unroll
+            for (int c = 0; c < NC; c++) sv[SV_A + c] = att[c];
+        } else if (sub == 1) {
+#pragma unroll
+            for (int c = NC; c < SV_ROW - SV_A; c++) sv[SV_A + c] = 0.0f;      // (the row's padding: defined, never read)
+        }
+    }
+    if (live) {
+#pragma unroll
+        for (int o = sub; o < NR; o += 8) {
+            float v = 0.0f;
+#pragma unroll
+            for (int c = 0; c < NC; c++) v = __fmaf_rn(att[c], s_V[o * NC + c], v);
+            a.out[(size_t)(p0 + pt) * NR + o] = v;
+        }
+    }
+}
+
+// backward 1, split-bf16: the data gradients of a tile of points
+__global__ void __launch_bounds__(WG)
+lbs_weight_net_backward_data_bf16x3_kernel(const moss_lbs_weight_net_backward_args a, float* __restrict__ ws)
+{
+    __shared__ __attribute__((aligned(16))) __bf16 s_x_hi[T * HB_LD], s_x_lo[T * HB_LD], s_y_hi[T * HB_LD], s_y_lo[T * HB_LD];
+    __shared__ __attribute__((aligned(16))) __bf16 s_dq0_hi[T * QB_LD], s_dq0_lo[T * QB_LD];
+    __shared__ __attribute__((aligned(16))) float s_z[B_FLOATS];        // two planes (d z1); then d e as a float tile
+    __shared__ float s_K[NR * NC], s_V[NR * NC], s_Wq[NF * NF], s_g[T][NR], s_att[T][12], s_da[T][12], s_ds[T][12], s_dQ[T][NF];
+    __bf16* const s_z_hi = reinterpret_cast<__bf16*>(s_z);
+    __bf16* const s_z_lo = s_z_hi + T * HB_LD;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, half = lane >> 5;
+    const int p0 = blockIdx.x * T, P = a.P;
+    const float* const* par = a.params;
+    const float* saved = a.saved;
+
+    head_constants(a.Rs, par, s_K, s_V, s_Wq, tid);
+    for (int i = tid; i < T * NR; i += WG) {
+        const int pt = i / NR;
+        s_g[pt][i % NR] = p0 + pt < P ? a.g_out[(size_t)p0 * NR + i] : 0.0f;
+    }
+    for (int i = tid; i < T * NC; i += WG) {
+        const int pt = i / NC, c = i % NC;
+        s_att[pt][c] = p0 + pt < P ? saved[(size_t)(p0 + pt) * SV_ROW + SV_A + c] : 0.0f;
+    }
+    for (int i = tid; i < T * (QB_LD - NF); i += WG) {
+        const int idx = (i / (QB_LD - NF)) * QB_LD + NF + i % (QB_LD - NF);
+        s_dq0_hi[idx] = (__bf16)0.0f;
+        s_dq0_lo[idx] = (__bf16)0.0f;
+    }
+    __syncthreads();
+
+    const int pt = tid >> 3, sub = tid & 7;
+    const bool live = p0 + pt < P;
+    float* wrow = live ? ws + (size_t)(p0 + pt) * WS_ROW : nullptr;
+    for (int c = sub; c < NC; c += 8) {
+        float v = 0.0f;
+#pragma unroll
+        for (int o = 0; o < NR; o++) v = __fmaf_rn(s_g[pt][o], s_V[o * NC + c], v);
+        s_da[pt][c] = v;
+    }
+    __syncthreads();
+    {
+        float dot = 0.0f;
+#pragma unroll
+        for (int c = 0; c < NC; c++) dot = __fmaf_rn(s_att[pt][c], s_da[pt][c], dot);
+        for (int c = sub; c < NC; c += 8) {
+            const float v = s_att[pt][c] * (s_da[pt][c] - dot) / sqrtf((float)NF);
+            s_ds[pt][c] = v;
+            if (wrow) wrow[WS_DS + c] = v;
+        }
+        if (wrow && sub == 7)
+            for (int c = NC; c < WS_ROW - WS_DS; c++) wrow[WS_DS + c] = 0.0f;   // (the row's padding: defined, never read)
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = sub; i < NF; i += 8) {
+        float v = 0.0f;
+#pragma unroll
+        for (int c = 0; c < NC; c++) v = __fmaf_rn(s_ds[pt][c], s_K[i * NC + c], v);
+        s_dQ[pt][i] = v;
+        if (wrow) wrow[WS_DQ + i] = v;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = sub; k < NF; k += 8) {
+        float v = 0.0f;
+#pragma unroll
+        for (int i = 0; i < NF; i++) v = __fmaf_rn(s_Wq[i * NF + k], s_dQ[pt][i], v);
+        store_split(s_dq0_hi, s_dq0_lo, pt * QB_LD + k, v);
+        if (wrow) wrow[WS_DQ0 + k] = v;
+    }
+    __syncthreads();
+
+    const int n = 32 * wave + j;
+    // d z = (h > 0) * acc -> the LDS planes and the workspace (float32)
+    auto store_dz = [&](const f32x16& acc, __bf16* hi, __bf16* lo, int sv_col, int ws_col) {
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const int row = acc_row(r, half);
+            const bool ok = p0 + row < P;
+            const float h = ok ? saved[(size_t)(p0 + row) * SV_ROW + sv_col + n] : 0.0f;
+            const float v = h > 0.0f ? acc[r] : 0.0f;
+            store_split(hi, lo, row * HB_LD + n, v);
+            if (ok) ws[(size_t)(p0 + row) * WS_ROW + ws_col + n] = v;
+        }
+    };
+    const int ha = j * HB_LD;
+    f32x16 acc = gemm_w3<32>(par[P_WFC], NH, NF, n, true, s_dq0_hi + j * QB_LD, s_dq0_lo + j * QB_LD, half);
+    store_dz(acc, s_x_hi, s_x_lo, SV_H3, WS_DZ3);
+    __syncthreads();
+    acc = gemm_w3<NH>(par[P_W3], W3_LD, NH, NE + n, true, s_x_hi + ha, s_x_lo + ha, half);
+    store_dz(acc, s_y_hi, s_y_lo, SV_H2, WS_DZ2);
+    __syncthreads();
+    acc = gemm_w3<NH>(par[P_W2], NH, NH, n, true, s_y_hi + ha, s_y_lo + ha, half);
+    store_dz(acc, s_z_hi, s_z_lo, SV_H1, WS_DZ1);
+    __syncthreads();
+    acc = gemm_w3<NH>(par[P_W1], NH, NH, n, true, s_z_hi + ha, s_z_lo + ha, half);
+    store_dz(acc, s_y_hi, s_y_lo, SV_H0, WS_DZ0);                       // (d z2 in s_y was last read before the barrier above)
+    __syncthreads();
+    // d e = d z3 . W3[:, :63] + d z0 . W0: two blocks of 32 columns each, one product per wave, the two halves into s_z as floats
+    // (its planes, d z1, were last read before the barrier above)
+    {
+        const int col = 32 * (wave & 1) + j;
+        acc = (wave >> 1) == 0 ? gemm_w3<NH>(par[P_W3], W3_LD, NH, col, col < NE, s_x_hi + ha, s_x_lo + ha, half)
+                               : gemm_w3<NH>(par[P_W0], NE, NH, col, col < NE, s_y_hi + ha, s_y_lo + ha, half);
+#pragma unroll
+        for (int r = 0; r < 16; r++) s_z[acc_row(r, half) * H_LD + 64 * (wave >> 1) + col] = acc[r];
+    }
+    __syncthreads();
+    if (tid < T * 3) {
+        const int q = tid / 3, d = tid % 3;
+        if (p0 + q < P) {
+            const float* z = s_z + q * H_LD;
+            const float* e = saved + (size_t)(p0 + q) * SV_ROW + SV_E;
+            float v = z[d] + z[64 + d];
+#pragma unroll
+            for (int f = 0; f < NFREQ; f++) {
+                const int is = 3 + 6 * f + d, ic = is + 3;
+                const float dsn = z[is] + z[64 + is], dcs = z[ic] + z[64 + ic];
+                v += (float)(1 << f) * (e[ic] * dsn - e[is] * dcs);
+            }
+            a.g_x[(size_t)(p0 + q) * 3 + d] = v;
+        }
+    }
+}
+
+// backward 2, split-bf16: one (32 x 64) block of one weight gradient over one range of points, per wave.  The items below `n_split` are
+// the five wide products: STEPS x sixteen points per iteration, a lane reads its column at eight consecutive points per operand and
+// step and splits them; the bias is the float32 column sum.  The other items (query.weight / bias, d K, d V) stay float32: the loop of
+// the f32 kernel, in the same launch, so that their waves run beside the wide ones.
+__global__ void __launch_bounds__(WG)
+lbs_weight_net_backward_weights_bf16x3_kernel(int P, int chunk, const float* __restrict__ saved, const float* __restrict__ ws,
+                                              const float* __restrict__ g_out, float* __restrict__ partial, const WgItems items, int n_split)
+{
+    constexpr int STEPS = 2;
+    const int lane = threadIdx.x & 63, j = lane & 31, half = lane >> 5;
+    const int id = blockIdx.x * (WG / 64) + (threadIdx.x >> 6);
+    if (id >= items.count * SPLITS) return;
+    const int split = id / items.count, item = id % items.count;
+    const WgItem it = items.it[item];
+    const float* src[3] = {saved, ws, g_out};
+    const float* A = src[it.a_src] + it.a_off + j;
+    const float* B = src[it.b_src] + it.b_off + j;
+    const bool a_ok = j < it.a_n, b0_ok = j < it.b_n, b1_ok = j + 32 < it.b_n;
+    const int pbeg = min(P, split * chunk), pend = min(P, pbeg + chunk);
+    f32x16 acc0 = splat(0.0f), acc1 = splat(0.0f);
+    float bsum = 0.0f;
+    const bool wide = it.b_n > 32;                                      // (wave-uniform, as is the choice of the loop)
+    if (item < n_split) {
+        for (int q = pbeg; q < pend; q += 16 * STEPS) {                 // the loads of all steps first
+            float av[STEPS][8], b0[STEPS][8], b1[STEPS][8];
+#pragma unroll
+            for (int t = 0; t < STEPS; t++)
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    const int p = q + 16 * t + 8 * half + u;
+                    const bool ok = p < pend;
+                    av[t][u] = ok && a_ok ? A[(size_t)p * it.a_ld] : 0.0f;
+                    b0[t][u] = ok && b0_ok ? B[(size_t)p * it.b_ld] : 0.0f;
+                    b1[t][u] = ok && b1_ok ? B[(size_t)p * it.b_ld + 32] : 0.0f;
+                }
+#pragma unroll
+            for (int t = 0; t < STEPS; t++) {
+                bf16x8 ah, al, bh, bl;
+                split_bf16x8(av[t], ah, al);
+                split_bf16x8(b0[t], bh, bl);
+                mfma16x3(acc0, ah, al, bh, bl);
+                if (wide) {
+                    split_bf16x8(b1[t], bh, bl);
+                    mfma16x3(acc1, ah, al, bh, bl);
+                }
+#pragma unroll
+                for (int u = 0; u < 8; u++) bsum += av[t][u];
+            }
+        }
+    } else {
+        for (int q = pbeg; q < pend; q += 8) {                          // four MFMA steps of two points; the loads first
+            float av[4], b0[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const int p = q + 2 * u + half;
+                const bool ok = p < pend;
+                av[u] = ok && a_ok ? A[(size_t)p * it.a_ld] : 0.0f;
+                b0[u] = ok && b0_ok ? B[(size_t)p * it.b_ld] : 0.0f;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], b0[u], acc0, 0, 0, 0);
+                bsum += av[u];
+            }
+        }
+    }
+    float* out = partial + (size_t)split * G_ALL;
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int row = acc_row(r, half);
+        if (row < it.a_n) {
+            if (b0_ok) out[it.out_off + row * it.out_ld + j] = acc0[r];
+            if (b1_ok) out[it.out_off + row * it.out_ld + 32 + j] = acc1[r];
+        }
+    }
+    bsum += __shfl_xor(bsum, 32);
+    if (it.bias_off >= 0 && half == 0 && a_ok) out[it.bias_off + j] = bsum;
+}
+
 struct GradPtrs { float* g[NPAR]; };
 
 // backward 3: the partial sums in split order; the last workgroup: d K, d V -> the gradients of key.*, value.* and Rs
@@ -473,10 +876,14 @@ void add_items(WgItems& w, int a_src, int a_off, int a_cols, int b_src, int b_of
         }
 }
 
-const WgItems& weight_items()
+// the item table; the first `wide` items are the five wide products (what the split-bf16 mode runs on the bf16-input matrix cores)
+struct ItemTable { WgItems all; int wide; };
+
+const ItemTable& weight_items()
 {
-    static const WgItems items = [] {
-        WgItems w{};
+    static const ItemTable table = [] {
+        ItemTable t{};
+        WgItems& w = t.all;
         enum { SAVED, WS, GOUT };
         add_items(w, WS, WS_DZ0, NH, SAVED, SV_E, NE, G_W0, NE, G_B0);
         add_items(w, WS, WS_DZ1, NH, SAVED, SV_H0, NH, G_W1, NH, G_B1);
@@ -484,12 +891,13 @@ const WgItems& weight_items()
         add_items(w, WS, WS_DZ3, NH, SAVED, SV_E, NE, G_W3, W3_LD, G_B3);
         add_items(w, WS, WS_DZ3, NH, SAVED, SV_H2, NH, G_W3 + NE, W3_LD, -1);
         add_items(w, WS, WS_DQ0, NF, SAVED, SV_H3, NH, G_WFC, NH, G_BFC);
+        t.wide = w.count;
         add_items(w, WS, WS_DQ, NF, SAVED, SV_Q0, NF, G_WQ, NF, G_BQ);
         add_items(w, SAVED, SV_Q, NF, WS, WS_DS, NC, G_DK, NC, -1);       // d K[i][c] = sum_p Q[i] d s[c] / sqrt(24)
         add_items(w, GOUT, 0, NR, SAVED, SV_A, NC, G_DV, NC, -1);         // d V[j][c] = sum_p g[j] a[c]
-        return w;
+        return t;
     }();
-    return items;
+    return table;
 }
 
 size_t ws_rows_bytes(int P) { return align_up((size_t)P * WS_ROW * sizeof(float)); }
@@ -507,44 +915,77 @@ extern "C" size_t moss_lbs_weight_net_workspace_bytes(int P)
 
 extern "C" size_t moss_lbs_weight_net_saved_bytes(int P) { return P <= 0 ? 0 : (size_t)P * SV_ROW * sizeof(float); }
 
-// CrossAttention_lbs.forward, nets/mlp_delta_weight_lbs.py:31-54
-extern "C" int moss_lbs_weight_net_forward(const moss_lbs_weight_net_args* a, void* stream)
+// CrossAttention_lbs.forward, nets/mlp_delta_weight_lbs.py:31-54; `fn` names the entry point in a refusal
+static int forward_impl(const char* fn, const moss_lbs_weight_net_args* a, void* stream, bool bf16x3)
 {
-    if (!a) return invalid_arg("moss_lbs_weight_net_forward", "null argument block");
-    if (a->P < 0) return invalid_arg("moss_lbs_weight_net_forward", "P must be >= 0");
+    if (!a) return invalid_arg(fn, "null argument block");
+    if (a->P < 0) return invalid_arg(fn, "P must be >= 0");
     if (a->P == 0) return 0;
-    if (!a->x || !a->Rs || !a->out) return invalid_arg("moss_lbs_weight_net_forward", "null x, Rs or out");
+    if (!a->x || !a->Rs || !a->out) return invalid_arg(fn, "null x, Rs or out");
     for (int i = 0; i < NPAR; i++)
-        if (!a->params[i]) return invalid_arg("moss_lbs_weight_net_forward", "null parameter tensor (all 16 are read)");
+        if (!a->params[i]) return invalid_arg(fn, "null parameter tensor (all 16 are read)");
     static_assert(MAX_ITEMS >= 37, "item table");
-    hipLaunchKernelGGL(lbs_weight_net_forward_kernel, dim3((a->P + T - 1) / T), dim3(WG), 0, (hipStream_t)stream, *a);
-    return launch_status("moss_lbs_weight_net_forward");
+    if (bf16x3)
+        hipLaunchKernelGGL(lbs_weight_net_forward_bf16x3_kernel, dim3((a->P + T - 1) / T), dim3(WG), 0, (hipStream_t)stream, *a);
+    else
+        hipLaunchKernelGGL(lbs_weight_net_forward_kernel, dim3((a->P + T - 1) / T), dim3(WG), 0, (hipStream_t)stream, *a);
+    return launch_status(fn);
 }
 
 // the adjoint of CrossAttention_lbs.forward, nets/mlp_delta_weight_lbs.py:31-54
-extern "C" int moss_lbs_weight_net_backward(const moss_lbs_weight_net_backward_args* a, void* stream)
+static int backward_impl(const char* fn, const moss_lbs_weight_net_backward_args* a, void* stream, bool bf16x3)
 {
-    if (!a) return invalid_arg("moss_lbs_weight_net_backward", "null argument block");
-    if (a->P < 0) return invalid_arg("moss_lbs_weight_net_backward", "P must be >= 0");
+    if (!a) return invalid_arg(fn, "null argument block");
+    if (a->P < 0) return invalid_arg(fn, "P must be >= 0");
     if (a->P == 0) return 0;
-    if (!a->Rs || !a->saved || !a->g_out) return invalid_arg("moss_lbs_weight_net_backward", "null Rs, saved (the forward's) or g_out");
-    if (!a->g_x || !a->g_Rs) return invalid_arg("moss_lbs_weight_net_backward", "null g_x or g_Rs (both are written)");
+    if (!a->Rs || !a->saved || !a->g_out) return invalid_arg(fn, "null Rs, saved (the forward's) or g_out");
+    if (!a->g_x || !a->g_Rs) return invalid_arg(fn, "null g_x or g_Rs (both are written)");
     for (int i = 0; i < NPAR; i++)
-        if (!a->params[i] || !a->grads[i]) return invalid_arg("moss_lbs_weight_net_backward", "null parameter or gradient tensor (all 16 are written)");
+        if (!a->params[i] || !a->grads[i]) return invalid_arg(fn, "null parameter or gradient tensor (all 16 are written)");
     if (!a->workspace || a->workspace_bytes < moss_lbs_weight_net_workspace_bytes(a->P))
-        return invalid_arg("moss_lbs_weight_net_backward", "the workspace is null or smaller than moss_lbs_weight_net_workspace_bytes(P)");
+        return invalid_arg(fn, "the workspace is null or smaller than moss_lbs_weight_net_workspace_bytes(P)");
     const int P = a->P;
     hipStream_t s = (hipStream_t)stream;
     float* ws = reinterpret_cast<float*>(a->workspace);
     float* partial = reinterpret_cast<float*>(a->workspace + ws_rows_bytes(P));
-    const WgItems& items = weight_items();
-    const int chunk = ((P + SPLITS - 1) / SPLITS + 1) & ~1;           // points per split, even: an MFMA step takes two
     GradPtrs gp;
     for (int i = 0; i < NPAR; i++) gp.g[i] = a->grads[i];
-    hipLaunchKernelGGL(lbs_weight_net_backward_data_kernel, dim3((P + T - 1) / T), dim3(WG), 0, s, *a, ws);
-    hipLaunchKernelGGL(lbs_weight_net_backward_weights_kernel, dim3((items.count * SPLITS + WG / 64 - 1) / (WG / 64)), dim3(WG), 0, s,
-                       P, chunk, a->saved, (const float*)ws, a->g_out, partial, items);
+    const ItemTable& table = weight_items();
+    const WgItems& items = table.all;
+    const dim3 grid((items.count * SPLITS + WG / 64 - 1) / (WG / 64));
+    if (bf16x3) {
+        const int chunk = ((P + SPLITS - 1) / SPLITS + 15) & ~15;     // points per split, a multiple of 16: an MFMA step takes sixteen
+        hipLaunchKernelGGL(lbs_weight_net_backward_data_bf16x3_kernel, dim3((P + T - 1) / T), dim3(WG), 0, s, *a, ws);
+        hipLaunchKernelGGL(lbs_weight_net_backward_weights_bf16x3_kernel, grid, dim3(WG), 0, s, P, chunk, a->saved, (const float*)ws,
+                           a->g_out, partial, items, table.wide);
+    } else {
+        const int chunk = ((P + SPLITS - 1) / SPLITS + 1) & ~1;       // points per split, even: an MFMA step takes two
+        hipLaunchKernelGGL(lbs_weight_net_backward_data_kernel, dim3((P + T - 1) / T), dim3(WG), 0, s, *a, ws);
+        hipLaunchKernelGGL(lbs_weight_net_backward_weights_kernel, grid, dim3(WG), 0, s, P, chunk, a->saved, (const float*)ws, a->g_out,
+                           partial, items);
+    }
     hipLaunchKernelGGL(lbs_weight_net_backward_fold_kernel, dim3((G_NET + WG - 1) / WG + 1), dim3(WG), 0, s, (const float*)partial,
                        a->Rs, a->params[P_WK], a->params[P_WV], gp, a->g_Rs);
-    return launch_status("moss_lbs_weight_net_backward");
+    return launch_status(fn);
+}
+
+extern "C" int moss_lbs_weight_net_forward(const moss_lbs_weight_net_args* a, void* stream)
+{
+    return forward_impl("moss_lbs_weight_net_forward", a, stream, false);
+}
+
+extern "C" int moss_lbs_weight_net_backward(const moss_lbs_weight_net_backward_args* a, void* stream)
+{
+    return backward_impl("moss_lbs_weight_net_backward", a, stream, false);
+}
+
+// the same pair in the split-bf16 (three-product) mode; `saved` and the workspace have the f32 pair's sizes
+extern "C" int moss_lbs_weight_net_forward_bf16x3(const moss_lbs_weight_net_args* a, void* stream)
+{
+    return forward_impl("moss_lbs_weight_net_forward_bf16x3", a, stream, true);
+}
+
+extern "C" int moss_lbs_weight_net_backward_bf16x3(const moss_lbs_weight_net_backward_args* a, void* stream)
+{
+    return backward_impl("moss_lbs_weight_net_backward_bf16x3", a, stream, true);
 }

@@ -33,10 +33,28 @@ __device__ __forceinline__ void split_bf16x4(const V& v, bf16x4& hi, bf16x4& lo)
     lo = bf16x4{(__bf16)(v.x - (float)hi.x), (__bf16)(v.y - (float)hi.y), (__bf16)(v.z - (float)hi.z), (__bf16)(v.w - (float)hi.w)};
 }
 
+// a lane's eight k of one operand, split
+__device__ __forceinline__ void split_bf16x8(const float (&v)[8], bf16x8& hi, bf16x8& lo)
+{
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        hi[i] = (__bf16)v[i];
+        lo[i] = (__bf16)(v[i] - (float)hi[i]);
+    }
+}
+
 // acc += A B over the wave's sixteen k of this step
 __device__ __forceinline__ void mfma16(f32x16& acc, const bf16x8& av, const bf16x8& bv)
 {
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, acc, 0, 0, 0);
+}
+
+// acc += lo(A) hi(B) + hi(A) lo(B) + hi(A) hi(B): the three-product form of a float32 product (lo lo is dropped), small terms first
+__device__ __forceinline__ void mfma16x3(f32x16& acc, const bf16x8& ah, const bf16x8& al, const bf16x8& bh, const bf16x8& bl)
+{
+    mfma16(acc, al, bh);
+    mfma16(acc, ah, bl);
+    mfma16(acc, ah, bh);
 }
 
 }  // namespace moss

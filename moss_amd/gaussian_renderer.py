@@ -114,7 +114,8 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
             # ``pipe.pose_head_in_op`` (an addition, default off): MOSS's pose branch (reference :65-72) with the refinement head and
             # the matrix-Fisher term as the fused HIP op (moss_amd/pose.py); cross_attention_lbs stays the caller's torch module unless
             # ``pipe.lbs_weights_in_op`` (an addition, default off) is set: then it runs as the fused HIP op of moss_amd/lbs_weights.py
-            # on the module's parameters (a module of another layout than MOSS's CrossAttention_lbs raises: there is no fallback)
+            # on the module's parameters (a module of another layout than MOSS's CrossAttention_lbs raises: there is no fallback), in the
+            # precision ``pipe.lbs_weights_precision`` names ("f32", the default, or "bf16x3": the split-bf16 products)
             from .pose import pose_head_fused
             # ``pipe.net_grad_sink`` (an addition, default none): ``param -> tensor or None`` -- where the two network ops' backward
             # kernels write their weight gradients (``GradBucket.sink_for`` of the networks' optimizer: moss_amd/train.py)
@@ -124,7 +125,8 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
                                        **sink_kw)
             if getattr(pipe, "lbs_weights_in_op", False):
                 from .lbs_weights import cross_attention_lbs_fused
-                lbs_weights = cross_attention_lbs_fused(pc.cross_attention_lbs, means3D[None], pose_out["Rs"], **sink_kw)
+                lbs_weights = cross_attention_lbs_fused(pc.cross_attention_lbs, means3D[None], pose_out["Rs"],
+                                                        precision=getattr(pipe, "lbs_weights_precision", "f32"), **sink_kw)
             else:
                 lbs_weights = pc.cross_attention_lbs(means3D[None], pose_out["Rs"])
             correct_Rs = pose_out["Rs"].reshape(1, 23, 3, 3)

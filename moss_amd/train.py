@@ -74,6 +74,11 @@ class MossStep:
     the same ids bit for bit; it is set as ``pc.template_index`` and also serves :meth:`densify_and_prune`'s vertex distance.  The
     vertices are snapshotted: a step whose template changes needs a new step.  False (the default): the step is what it was.
 
+    ``lbs_weights_precision``: ``"f32"`` (the default: the step is what it was) or ``"bf16x3"`` -- the LBS-weight network's five wide
+    products, forward and in both gradients, on the bf16-input matrix cores with both operands split in two
+    (``lbs_weights.cross_attention_lbs_fused(precision=)``, handed on as ``pipe.lbs_weights_precision``).  The gradient sinks, the
+    capture and the events are the same.
+
     ``lrs``: ``{"auto_regression": lr, "cross_attention_lbs": lr}`` (MOSS: 2.5e-4 and 1e-4), optionally with rates for the Gaussian
     groups by their ``param_groups()`` names (``xyz``, ``features`` -- a number or ``(lr_dc, lr_rest)`` --, ``opacity``, ``scaling``,
     ``rotation``; default: the reference's).
@@ -111,8 +116,9 @@ class MossStep:
     ``terms`` (7 floats on the device, :data:`TERM_NAMES`): the six loss terms and the total of the last step."""
 
     def __init__(self, pc, view, gt_image, bkgd_mask, region, bg, lpips_net, lrs, context=None, stats=None, lpips_capacity=None,
-                 lpips_reference=None, template_index=False):
+                 lpips_reference=None, template_index=False, lbs_weights_precision="f32"):
         from .diff_gaussian_rasterization import RasterContext
+        from .lbs_weights import PRECISIONS
         from .dist import GradBucket
         from .optim import FlatAdamW
         if not getattr(pc, "unified_features", False):
@@ -126,6 +132,8 @@ class MossStep:
         for k in ("auto_regression", "cross_attention_lbs"):
             if k not in lrs:
                 raise ValueError(f"MossStep: lrs has no rate for '{k}'")
+        if lbs_weights_precision not in PRECISIONS:
+            raise ValueError(f"MossStep: lbs_weights_precision must be one of {PRECISIONS}, got {lbs_weights_precision!r}")
         self.pc, self.view, self.gt_image, self.bkgd_mask, self.region, self.bg, self.lpips_net = pc, view, gt_image, bkgd_mask, region, bg, lpips_net
         self.stats = stats
         if lpips_capacity is not None:
@@ -180,7 +188,8 @@ class MossStep:
         from .optim import FlatAdamWRows
         self.rows = FlatAdamWRows([self.opt_gaussians, self.opt_xyz])     # (A) and (B) as one optimizer for row surgery
         self.pipe = SimpleNamespace(convert_SHs_python=False, compute_cov3D_python=False, debug=False, raster_context=cx,
-                                    net_grad_sink=self.bucket_networks.sink_for, **dict.fromkeys(RENDER_FLAGS, True))
+                                    net_grad_sink=self.bucket_networks.sink_for, lbs_weights_precision=lbs_weights_precision,
+                                    **dict.fromkeys(RENDER_FLAGS, True))
         # [photometric loss | l1, ssim, mask_l2 | lpips, nll, s3im, total]: the photometric kernels write the first four themselves
         self._terms = torch.zeros(8, dtype=torch.float32, device=dev)
         self.terms = self._terms[1:]

@@ -14,6 +14,7 @@ SH degree 3, synthetic LPIPS weights, a 192 x 256 region:
                                       [--lpips-precision f32|bf16|bf16x3]
     python scripts/moss_step_times.py --lpips-reference [--replays 300]
     python scripts/moss_step_times.py --template-index [--replays 300] [--only profile]
+    python scripts/moss_step_times.py --lbs-weights-precision bf16x3 [--template-index] [--lpips-precision bf16] [--replays 300]
 
 ``--lpips-reference``: the captured step at P = 45 695 over its three frames WITH ``MossStep(lpips_reference=)`` -- one
 ``lpips.LpipsReference`` per frame built before the clock starts, ``step.lpips_reference.copy_(refs[k])`` per replay INSIDE the timed
@@ -23,6 +24,11 @@ twice (eight processes); the table gives each pair's ratio and the spread of the
 ``--template-index``: the captured step at P = 45 695 WITH ``MossStep(template_index=True)`` -- the nearest-vertex query through a
 ``knn_cuda.TemplateIndex`` built once -- and without, in the same eight-process scheme; with ``--only profile`` instead ONE
 ``rocprofv3 --kernel-trace --stats`` run of the step with the index.
+
+``--lbs-weights-precision bf16x3``: the captured step at P = 45 695 WITH ``MossStep(lbs_weights_precision="bf16x3")`` -- the LBS-weight
+network's split-bf16 mode -- and without (the control), at the given ``--lpips-precision`` and, with ``--template-index``, with the
+index in both; the two runs alternated and the sequence twice (four processes); the table gives the ratio, the control's spread and
+the last step's total loss of both.
 
 Every measurement is a process of its own under ``timeout -k 10``; the script stops at the first one that does not exit with 0.  A time
 is the wall clock around ``replays`` back-to-back steps between two device synchronisations, after a warm-up.  Needs a GPU.
@@ -110,7 +116,7 @@ def _timed(fn, replays, dev, load):
     return (time.perf_counter() - t0) / replays
 
 
-def measure_captured(P, replays, lpips_precision="f32", lpips_reference=False, template_index=False):
+def measure_captured(P, replays, lpips_precision="f32", lpips_reference=False, template_index=False, lbs_weights_precision="f32"):
     import torch
     from moss_amd.train import MossStep
     dev = torch.device("cuda:0")
@@ -122,6 +128,8 @@ def measure_captured(P, replays, lpips_precision="f32", lpips_reference=False, t
         kw["lpips_reference"] = mlp.LpipsReference.empty(w["lpips"], refs[0].crop, static=True).copy_(refs[0])
     if template_index:
         kw["template_index"] = True
+    if lbs_weights_precision != "f32":                       # (left out for the control: a checkout without the argument serves)
+        kw["lbs_weights_precision"] = lbs_weights_precision
     step = MossStep(w["pc"], w["cam"], w["gt"], w["bkgd"], w["region"], w["bg"], w["lpips"], {"auto_regression": LR_HEAD, "cross_attention_lbs": LR_NET},
                     **kw)
     step.capture(warmup=3)
@@ -139,7 +147,7 @@ def measure_captured(P, replays, lpips_precision="f32", lpips_reference=False, t
     torch.cuda.synchronize(dev)
     assert step.dropped_frames == 0 and float(out["render"].abs().max()) > 0 and bool(torch.isfinite(out["terms"]).all())
     return {"form": "captured", "P": P, "lpips_precision": lpips_precision, "lpips_reference": bool(lpips_reference),
-            "template_index": bool(template_index), "reference_bytes_per_camera": refs[0].nbytes if refs else 0, "replays": replays, "us_per_step": round(dt * 1e6, 1), "it_per_s": round(1.0 / dt, 1),
+            "template_index": bool(template_index), "lbs_weights_precision": lbs_weights_precision, "reference_bytes_per_camera": refs[0].nbytes if refs else 0, "replays": replays, "us_per_step": round(dt * 1e6, 1), "it_per_s": round(1.0 / dt, 1),
             "steps": list(step.step_counts()), "total_loss": float(out["terms"][-1])}
 
 
@@ -235,6 +243,39 @@ def ab_comparison(a, key, worker_flag, names, P=45695):
         json.dump(results, f, indent=1)
 
 
+def lbs_weights_comparison(a, P=45695):
+    """The captured step with MossStep(lbs_weights_precision=a.lbs_weights_precision) and without (f32, the control), at
+    a.lpips_precision, with the template index in both if a.template_index; each run a process of its own, the sequence twice."""
+    os.makedirs(a.out, exist_ok=True)
+    me = ([sys.executable, os.path.abspath(__file__), "--package-root", os.path.abspath(a.package_root), "--replays", str(a.replays),
+           "--lpips-precision", a.lpips_precision, "--worker", "captured", "--P", str(P)] + (["--with-template-index"] if a.template_index else []))
+    modes = ("f32", a.lbs_weights_precision)
+    results = []
+    for rep in (1, 2):
+        for mode in modes:
+            name = f"captured_{P}_lbs_weights_{mode}_{rep}"
+            cmd = ["timeout", "-k", "10", str(STEP_TIMEOUT)] + me + ["--lbs-weights-precision", mode]
+            r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, cwd=os.path.abspath(a.package_root))
+            with open(os.path.join(a.out, name + ".log"), "w") as f:
+                f.write(r.stdout)
+            line = next((ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")), None)
+            if r.returncode != 0 or line is None:
+                print(f"{name}: exit {r.returncode}; stopping (log: {os.path.join(a.out, name + '.log')})\n" + r.stdout[-3000:], flush=True)
+                raise SystemExit(1)
+            res = dict(json.loads(line[7:]), job=name, repetition=rep)
+            results.append(res)
+            print(json.dumps(res), flush=True)
+    t = {m: [r["us_per_step"] for r in results if r["lbs_weights_precision"] == m] for m in modes}
+    loss = {m: [r["total_loss"] for r in results if r["lbs_weights_precision"] == m] for m in modes}
+    spread = {m: abs(t[m][0] - t[m][1]) / (0.5 * sum(t[m])) for m in modes}
+    print(f"| LBS-weight network | us per step (1, 2) | spread | / f32 (1, 2) | total loss of the last step |\n|---|---|---|---|---|")
+    for m in modes:
+        print(f"| {m} | {t[m][0]:.1f}, {t[m][1]:.1f} | {100 * spread[m]:.2f} % | {t[m][0] / t['f32'][0]:.4f}, {t[m][1] / t['f32'][1]:.4f} | "
+              f"{loss[m][0]:.6f} |")
+    with open(os.path.join(a.out, "lbs_weights_precision_results.json"), "w") as f:
+        json.dump(results, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--replays", type=int, default=300)
@@ -242,6 +283,8 @@ def main():
     ap.add_argument("--only", default="captured,baseline,profile")
     ap.add_argument("--out", default="moss_step_times_out")
     ap.add_argument("--lpips-precision", default="f32", choices=("f32", "bf16", "bf16x3"), help="the LPIPS net's operand precision (LpipsVGG(precision=))")
+    ap.add_argument("--lbs-weights-precision", default="f32", choices=("f32", "bf16x3"),
+                    help="bf16x3: the captured step at P = 45 695 with and without MossStep(lbs_weights_precision=\"bf16x3\"), alternated twice")
     ap.add_argument("--lpips-reference", action="store_true",
                     help="the captured step at P = 45 695 with and without MossStep(lpips_reference=), f32 and bf16, alternated twice")
     ap.add_argument("--with-reference", action="store_true", help=argparse.SUPPRESS)
@@ -257,9 +300,11 @@ def main():
     if a.worker:
         if a.replays < 200:
             raise SystemExit("at least 200 replays per measurement")
-        extra = (a.with_reference, a.with_template_index) if a.worker == "captured" else ()
+        extra = (a.with_reference, a.with_template_index, a.lbs_weights_precision) if a.worker == "captured" else ()
         print("RESULT " + json.dumps({"captured": measure_captured, "baseline": measure_baseline}[a.worker](a.P, a.replays, a.lpips_precision, *extra)), flush=True)
         return
+    if a.lbs_weights_precision != "f32":
+        return lbs_weights_comparison(a)
     if a.lpips_reference:
         return ab_comparison(a, "lpips_reference", "--with-reference", ("two-image", "reference"))
     if a.template_index and a.only != "profile":
