@@ -27,10 +27,14 @@
 //        forms the gradients of key.*, value.* and Rs from them.
 // Every sum has a fixed order and there is no atomic: results are bitwise reproducible.  Every output element is written.
 //
-// A second, opt-in set of kernels (moss_lbs_weight_net_forward_bf16x3 / _backward_bf16x3; "the split-bf16 mode" below) runs the five
-// wide products -- forward, data gradient and weight gradient -- on v_mfma_f32_32x32x16_bf16 with both operands split in two bf16
-// halves and three products per product; same launches, same layouts of `saved` and the workspace, same order rules.  The f32 kernels
-// are not touched by it.
+// The forward, data-gradient and weight-gradient kernels are templates with two instantiations each: <false> is the f32 mode above,
+// <true> the opt-in split-bf16 mode (moss_lbs_weight_net_forward_bf16x3 / _backward_bf16x3), which runs the five wide products on
+// v_mfma_f32_32x32x16_bf16 with both operands split in two bf16 halves and three products per product.  What a mode contributes is its
+// OPERAND POLICY (TileF32 / TileSplit below: the LDS tile, put() and the two products over it) and its loop in the weight-gradient
+// kernel.  Everything else -- the embedding, the head, the attention adjoint, the ReLU masks, g_x, the layouts of `saved` and the
+// workspace, the launches and the order rules -- is float32, stated once, and the same in both.
+#include <type_traits>
+
 #include "common.h"
 #include "mfma_bf16.h"
 
@@ -56,8 +60,55 @@ constexpr int G_W0 = 0, G_B0 = G_W0 + NH * NE, G_W1 = G_B0 + NH, G_B1 = G_W1 + N
               G_BQ = G_WQ + NF * NF, G_NET = G_BQ + NF, G_DK = G_NET, G_DV = G_DK + NR * NC, G_ALL = G_DV + NR * NC;
 static_assert(G_NET == 69488, "flat gradient layout");
 constexpr int SPLITS = MOSS_LBS_WEIGHT_NET_SPLITS;
-// LDS row strides (floats): = 4 mod 64, so that the 32 lanes of a half wave read their float4 from 32 different bank groups
-constexpr int H_LD = 132, EH_LD = 196, Q_LD = 36;
+
+// ---- the operand policies ------------------------------------------------------------------------------------------------------------
+// A wide product reads its A operand (lane = point) from an LDS tile of T rows and COLS columns, Tile<SPLIT, COLS>: put() stores a
+// float32 value in the tile's format, row() is what a lane hands to gemm_wt (activation x weight^T) and gemm_w (the adjoint products),
+// which are overloaded on it.  A tile occupies FLOATS floats of LDS in either format.
+//   TileF32: floats; a lane reads four consecutive k, the wave takes eight per step on v_mfma_f32_32x32x2_f32.
+//   TileSplit: two bf16 planes, hi = bf16(a) and lo = bf16(a - hi) (mfma_bf16.h), a value split ONCE, when it is put; a lane reads eight
+//     consecutive k of each plane, the wave takes sixteen per step on v_mfma_f32_32x32x16_bf16, and a b is taken as
+//     lo(a) hi(b) + hi(a) lo(b) + hi(a) hi(b), accumulated in float32.  The weights change every step, so there is no pack-once: a
+//     weight is split in registers as it is read.  K = 63 pads to 64 and 191 to 192 through the same [e, 0, h2] row as in f32.
+// `saved` and the workspace are float32 in both modes (the ReLU masks, the biases' column sums, query / key / value and the head read
+// them), so the two size queries serve both.
+template <int COLS>
+struct TileF32 {
+    static constexpr int LD = COLS + 4;      // row stride (floats) = 4 mod 64: the 32 lanes of a half wave read their float4 from 32 different bank groups
+    static constexpr int FLOATS = T * LD;
+    float* p;
+    __device__ __forceinline__ explicit TileF32(float* lds) : p(lds) {}
+    __device__ __forceinline__ void put(int row, int col, float v) const { p[row * LD + col] = v; }
+    __device__ __forceinline__ const float* row(int r) const { return p + r * LD; }
+};
+
+struct RowSplit { const __bf16 *hi, *lo; };
+
+template <int COLS>
+struct TileSplit {
+    static constexpr int LD = COLS + 8;      // row stride (bf16) of a plane: an odd multiple of 16 bytes mod 256
+    static constexpr int FLOATS = T * LD;    // the pair of planes
+    __bf16 *hi, *lo;
+    __device__ __forceinline__ explicit TileSplit(float* lds) : hi(reinterpret_cast<__bf16*>(lds)), lo(hi + T * LD) {}
+    __device__ __forceinline__ void put(int row, int col, float v) const
+    {
+        __bf16 h, l;
+        split_bf16(v, h, l);
+        hi[row * LD + col] = h;
+        lo[row * LD + col] = l;
+    }
+    __device__ __forceinline__ RowSplit row(int r) const { return {hi + r * LD, lo + r * LD}; }
+};
+
+template <bool SPLIT, int COLS>
+using Tile = typename std::conditional<SPLIT, TileSplit<COLS>, TileF32<COLS>>::type;
+
+// A tile of NH columns also serves as plain floats once its last reader has passed a barrier: the four 32 x 32 partial blocks of
+// bw_fc (forward), d e as a float tile of stride H_LD (data gradient)
+constexpr int H_LD = TileF32<NH>::LD;
+static_assert(TileF32<NH>::FLOATS >= 4 * 1024 && TileSplit<NH>::FLOATS >= 4 * 1024 && TileSplit<NH>::FLOATS >= T * H_LD, "aliased LDS tile");
+
+typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));   // four floats at a float's alignment (a weight row starts anywhere)
 
 // acc[pt][n] += sum_{k in [kbase, kbase + K)} A[pt][k] W[n][k]: A in LDS (a_row = this lane's point), W (out, LD) row-major in
 // global memory.  SKIP: A is [e (63), 0, h2 (128)] and W is W3 (LD = 191): column 63 of A has no weight.
@@ -83,352 +134,15 @@ __device__ __forceinline__ f32x16 gemm_wt(const float* __restrict__ W, int n, bo
     return acc;
 }
 
-// acc[pt][col] = sum_{k < K} A[pt][k] W[k][col] (rows k >= kvalid and a column that is not ok count as zero): the adjoint products
-template <int K>
-__device__ __forceinline__ f32x16 gemm_w(const float* __restrict__ W, int ld, int kvalid, int col, bool col_ok, const float* a_row, int half)
-{
-    f32x16 acc = splat(0.0f);
-    const float* w = W + (col_ok ? col : 0);
-#pragma unroll 2
-    for (int k0 = 0; k0 < K; k0 += 8) {
-        const int kk = k0 + 4 * half;
-        const float4 av = *reinterpret_cast<const float4*>(a_row + kk);
-        float bv[4];
-#pragma unroll
-        for (int s = 0; s < 4; s++) bv[s] = (col_ok && kk + s < kvalid) ? w[(size_t)(kk + s) * ld] : 0.0f;
-        mfma4(acc, av, bv);
-    }
-    return acc;
-}
-
-// relu(acc) -> LDS [row][col] and, with `saved`, the rows of the points that exist
-__device__ __forceinline__ void store_act(const f32x16& acc, float* lds, int ld, int col, int half, float* saved, int sv_col, int p0, int P)
-{
-#pragma unroll
-    for (int r = 0; r < 16; r++) {
-        const int row = acc_row(r, half);
-        const float v = fmaxf(acc[r], 0.0f);
-        lds[row * ld + col] = v;
-        if (saved && p0 + row < P) saved[(size_t)(p0 + row) * SV_ROW + sv_col] = v;
-    }
-}
-
-// K = M Wk^T + bk, V = M Wv^T + bv (24 x 9) and a copy of Wq, into LDS (no barrier inside)
-__device__ __forceinline__ void head_constants(const float* __restrict__ Rs, const float* const* par, float* s_K, float* s_V, float* s_Wq, int tid)
-{
-    if (tid < NR * NC) {
-        const int r = tid / NC, c = tid % NC;
-        float k = par[P_BK][c], v = par[P_BV][c];
-#pragma unroll
-        for (int i = 0; i < NC; i++) {
-            const float m = r == 0 ? 1.0f : Rs[(r - 1) * NC + i];
-            k = __fmaf_rn(m, par[P_WK][c * NC + i], k);
-            v = __fmaf_rn(m, par[P_WV][c * NC + i], v);
-        }
-        s_K[tid] = k;
-        s_V[tid] = v;
-    }
-    for (int i = tid; i < NF * NF; i += WG) s_Wq[i] = par[P_WQ][i];
-}
-
-__global__ void __launch_bounds__(WG)
-lbs_weight_net_forward_kernel(const moss_lbs_weight_net_args a)
-{
-    __shared__ __attribute__((aligned(16))) float s_eh[T * EH_LD];      // [e (63), 0, h2 (128)]
-    __shared__ __attribute__((aligned(16))) float s_a[T * H_LD], s_b[T * H_LD];
-    __shared__ float s_K[NR * NC], s_V[NR * NC], s_Wq[NF * NF], s_q0[T][NF], s_Q[T][NF], s_s[T][12];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, half = lane >> 5;
-    const int p0 = blockIdx.x * T, P = a.P;
-    const float* const* par = a.params;
-    float* saved = a.saved;
-
-    head_constants(a.Rs, par, s_K, s_V, s_Wq, tid);
-    for (int i = tid; i < T * 3 * NFREQ; i += WG) {
-        const int pt = i / (3 * NFREQ), r = i % (3 * NFREQ), f = r / 3, d = r % 3;
-        const float xv = p0 + pt < P ? a.x[(size_t)(p0 + pt) * 3 + d] : 0.0f;
-        float sn, cs;
-        sincosf(xv * (float)(1 << f), &sn, &cs);
-        float* e = s_eh + pt * EH_LD;
-        e[3 + 6 * f + d] = sn;
-        e[6 + 6 * f + d] = cs;
-        if (f == 0) e[d] = xv;
-        if (r == 0) e[NE] = 0.0f;
-    }
-    __syncthreads();
-    if (saved)
-        for (int i = tid; i < T * 64; i += WG) {
-            const int pt = i >> 6, k = i & 63;
-            if (p0 + pt < P) saved[(size_t)(p0 + pt) * SV_ROW + SV_E + k] = s_eh[pt * EH_LD + k];
-        }
-
-    const int n = 32 * wave + j;                                        // this lane's output channel in the 128-wide layers
-    f32x16 acc = gemm_wt<64, NE, false>(par[P_W0], n, true, s_eh + j * EH_LD, half, splat(par[P_B0][n]));
-    store_act(acc, s_a, H_LD, n, half, saved, SV_H0 + n, p0, P);
-    __syncthreads();
-    acc = gemm_wt<NH, NH, false>(par[P_W1], n, true, s_a + j * H_LD, half, splat(par[P_B1][n]));
-    store_act(acc, s_b, H_LD, n, half, saved, SV_H1 + n, p0, P);
-    __syncthreads();
-    acc = gemm_wt<NH, NH, false>(par[P_W2], n, true, s_b + j * H_LD, half, splat(par[P_B2][n]));
-    store_act(acc, s_eh, EH_LD, 64 + n, half, saved, SV_H2 + n, p0, P);
-    __syncthreads();
-    acc = gemm_wt<64 + NH, W3_LD, true>(par[P_W3], n, true, s_eh + j * EH_LD, half, splat(par[P_B3][n]));
-    store_act(acc, s_a, H_LD, n, half, saved, SV_H3 + n, p0, P);
-    __syncthreads();
-    // bw_fc: one 32 x 32 block (24 channels), the k range split over the waves; the four partial blocks go to s_b
-    acc = gemm_wt<NH / 4, NH, false>(par[P_WFC], j, j < NF, s_a + j * H_LD, half, splat(0.0f), (NH / 4) * wave);
-#pragma unroll
-    for (int r = 0; r < 16; r++) s_b[wave * 1024 + acc_row(r, half) * 32 + j] = acc[r];
-    __syncthreads();
-
-    // the head: eight threads per point
-    const int pt = tid >> 3, sub = tid & 7;
-    const bool live = p0 + pt < P;
-    float* sv = saved && live ? saved + (size_t)(p0 + pt) * SV_ROW : nullptr;
-#pragma unroll
-    for (int k = sub; k < NF; k += 8) {
-        const float* q = s_b + pt * 32 + k;
-        const float v = (((q[0] + q[1024]) + q[2048]) + q[3072]) + par[P_BFC][k];
-        s_q0[pt][k] = v;
-        if (sv) sv[SV_Q0 + k] = v;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = sub; i < NF; i += 8) {
-        float v = par[P_BQ][i];
-#pragma unroll
-        for (int k = 0; k < NF; k++) v = __fmaf_rn(s_Wq[i * NF + k], s_q0[pt][k], v);
-        s_Q[pt][i] = v;
-        if (sv) sv[SV_Q + i] = v;
-    }
-    __syncthreads();
-    for (int c = sub; c < NC; c += 8) {
-        float v = 0.0f;
-#pragma unroll
-        for (int i = 0; i < NF; i++) v = __fmaf_rn(s_Q[pt][i], s_K[i * NC + c], v);
-        s_s[pt][c] = v / sqrtf((float)NF);
-    }
-    __syncthreads();
-    float att[NC], m = s_s[pt][0], sum = 0.0f;
-#pragma unroll
-    for (int c = 1; c < NC; c++) m = fmaxf(m, s_s[pt][c]);
-#pragma unroll
-    for (int c = 0; c < NC; c++) { att[c] = expf(s_s[pt][c] - m); sum += att[c]; }
-#pragma unroll
-    for (int c = 0; c < NC; c++) att[c] /= sum;
-    if (sv) {
-        if (sub == 0) {
-#pragma unroll
-            for (int c = 0; c < NC; c++) sv[SV_A + c] = att[c];
-        } else if (sub == 1) {
-#pragma unroll
-            for (int c = NC; c < SV_ROW - SV_A; c++) sv[SV_A + c] = 0.0f;      // (the row's padding: defined, never read)
-        }
-    }
-    if (live) {
-#pragma unroll
-        for (int o = sub; o < NR; o += 8) {
-            float v = 0.0f;
-#pragma unroll
-            for (int c = 0; c < NC; c++) v = __fmaf_rn(att[c], s_V[o * NC + c], v);
-            a.out[(size_t)(p0 + pt) * NR + o] = v;
-        }
-    }
-}
-
-// backward 1: the data gradients of a tile of points
-__global__ void __launch_bounds__(WG)
-lbs_weight_net_backward_data_kernel(const moss_lbs_weight_net_backward_args a, float* __restrict__ ws)
-{
-    __shared__ __attribute__((aligned(16))) float s_x[T * H_LD], s_y[T * H_LD], s_z[T * H_LD], s_dq0[T * Q_LD];
-    __shared__ float s_K[NR * NC], s_V[NR * NC], s_Wq[NF * NF], s_g[T][NR], s_att[T][12], s_da[T][12], s_ds[T][12], s_dQ[T][NF];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, half = lane >> 5;
-    const int p0 = blockIdx.x * T, P = a.P;
-    const float* const* par = a.params;
-    const float* saved = a.saved;
-
-    head_constants(a.Rs, par, s_K, s_V, s_Wq, tid);
-    for (int i = tid; i < T * NR; i += WG) {
-        const int pt = i / NR;
-        s_g[pt][i % NR] = p0 + pt < P ? a.g_out[(size_t)p0 * NR + i] : 0.0f;
-    }
-    for (int i = tid; i < T * NC; i += WG) {
-        const int pt = i / NC, c = i % NC;
-        s_att[pt][c] = p0 + pt < P ? saved[(size_t)(p0 + pt) * SV_ROW + SV_A + c] : 0.0f;
-    }
-    for (int i = tid; i < T * (Q_LD - NF); i += WG) s_dq0[(i / (Q_LD - NF)) * Q_LD + NF + i % (Q_LD - NF)] = 0.0f;
-    __syncthreads();
-
-    const int pt = tid >> 3, sub = tid & 7;
-    const bool live = p0 + pt < P;
-    float* wrow = live ? ws + (size_t)(p0 + pt) * WS_ROW : nullptr;
-    for (int c = sub; c < NC; c += 8) {
-        float v = 0.0f;
-#pragma unroll
-        for (int o = 0; o < NR; o++) v = __fmaf_rn(s_g[pt][o], s_V[o * NC + c], v);
-        s_da[pt][c] = v;
-    }
-    __syncthreads();
-    {
-        float dot = 0.0f;
-#pragma unroll
-        for (int c = 0; c < NC; c++) dot = __fmaf_rn(s_att[pt][c], s_da[pt][c], dot);
-        for (int c = sub; c < NC; c += 8) {
-            const float v = s_att[pt][c] * (s_da[pt][c] - dot) / sqrtf((float)NF);
-            s_ds[pt][c] = v;
-            if (wrow) wrow[WS_DS + c] = v;
-        }
-        if (wrow && sub == 7)
-            for (int c = NC; c < WS_ROW - WS_DS; c++) wrow[WS_DS + c] = 0.0f;   // (the row's padding: defined, never read)
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = sub; i < NF; i += 8) {
-        float v = 0.0f;
-#pragma unroll
-        for (int c = 0; c < NC; c++) v = __fmaf_rn(s_ds[pt][c], s_K[i * NC + c], v);
-        s_dQ[pt][i] = v;
-        if (wrow) wrow[WS_DQ + i] = v;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = sub; k < NF; k += 8) {
-        float v = 0.0f;
-#pragma unroll
-        for (int i = 0; i < NF; i++) v = __fmaf_rn(s_Wq[i * NF + k], s_dQ[pt][i], v);
-        s_dq0[pt * Q_LD + k] = v;
-        if (wrow) wrow[WS_DQ0 + k] = v;
-    }
-    __syncthreads();
-
-    const int n = 32 * wave + j;
-    // d z = (h > 0) * acc -> LDS and the workspace
-    auto store_dz = [&](const f32x16& acc, float* lds, int sv_col, int ws_col) {
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-            const int row = acc_row(r, half);
-            const bool ok = p0 + row < P;
-            const float h = ok ? saved[(size_t)(p0 + row) * SV_ROW + sv_col + n] : 0.0f;
-            const float v = h > 0.0f ? acc[r] : 0.0f;
-            lds[row * H_LD + n] = v;
-            if (ok) ws[(size_t)(p0 + row) * WS_ROW + ws_col + n] = v;
-        }
-    };
-    f32x16 acc = gemm_w<32>(par[P_WFC], NH, NF, n, true, s_dq0 + j * Q_LD, half);
-    store_dz(acc, s_x, SV_H3, WS_DZ3);
-    __syncthreads();
-    acc = gemm_w<NH>(par[P_W3], W3_LD, NH, NE + n, true, s_x + j * H_LD, half);
-    store_dz(acc, s_y, SV_H2, WS_DZ2);
-    __syncthreads();
-    acc = gemm_w<NH>(par[P_W2], NH, NH, n, true, s_y + j * H_LD, half);
-    store_dz(acc, s_z, SV_H1, WS_DZ1);
-    __syncthreads();
-    acc = gemm_w<NH>(par[P_W1], NH, NH, n, true, s_z + j * H_LD, half);
-    store_dz(acc, s_y, SV_H0, WS_DZ0);                                  // (d z2 in s_y was last read before the barrier above)
-    __syncthreads();
-    // d e = d z3 . W3[:, :63] + d z0 . W0: two blocks of 32 columns each, one product per wave, the two halves into s_z
-    {
-        const int col = 32 * (wave & 1) + j;
-        acc = (wave >> 1) == 0 ? gemm_w<NH>(par[P_W3], W3_LD, NH, col, col < NE, s_x + j * H_LD, half)
-                               : gemm_w<NH>(par[P_W0], NE, NH, col, col < NE, s_y + j * H_LD, half);
-#pragma unroll
-        for (int r = 0; r < 16; r++) s_z[acc_row(r, half) * H_LD + 64 * (wave >> 1) + col] = acc[r];
-    }
-    __syncthreads();
-    if (tid < T * 3) {
-        const int q = tid / 3, d = tid % 3;
-        if (p0 + q < P) {
-            const float* z = s_z + q * H_LD;
-            const float* e = saved + (size_t)(p0 + q) * SV_ROW + SV_E;
-            float v = z[d] + z[64 + d];
-#pragma unroll
-            for (int f = 0; f < NFREQ; f++) {
-                const int is = 3 + 6 * f + d, ic = is + 3;
-                const float dsn = z[is] + z[64 + is], dcs = z[ic] + z[64 + ic];
-                v += (float)(1 << f) * (e[ic] * dsn - e[is] * dcs);
-            }
-            a.g_x[(size_t)(p0 + q) * 3 + d] = v;
-        }
-    }
-}
-
-// backward 2: one (32 x 64) block of one weight gradient over one range of points, per wave
-struct WgItem { int a_src, a_off, a_ld, a_n, b_src, b_off, b_ld, b_n, out_off, out_ld, bias_off; };
-constexpr int MAX_ITEMS = 40;
-struct WgItems { int count; WgItem it[MAX_ITEMS]; };
-
-__global__ void __launch_bounds__(WG)
-lbs_weight_net_backward_weights_kernel(int P, int chunk, const float* __restrict__ saved, const float* __restrict__ ws,
-                                       const float* __restrict__ g_out, float* __restrict__ partial, const WgItems items)
-{
-    const int lane = threadIdx.x & 63, j = lane & 31, half = lane >> 5;
-    const int id = blockIdx.x * (WG / 64) + (threadIdx.x >> 6);
-    if (id >= items.count * SPLITS) return;
-    const int split = id / items.count;
-    const WgItem it = items.it[id % items.count];
-    const float* src[3] = {saved, ws, g_out};
-    const float* A = src[it.a_src] + it.a_off + j;
-    const float* B = src[it.b_src] + it.b_off + j;
-    const bool a_ok = j < it.a_n, b0_ok = j < it.b_n, b1_ok = j + 32 < it.b_n;
-    const int pbeg = min(P, split * chunk), pend = min(P, pbeg + chunk);
-    f32x16 acc0 = splat(0.0f), acc1 = splat(0.0f);
-    float bsum = 0.0f;
-    const bool wide = it.b_n > 32;                                      // (wave-uniform)
-    for (int q = pbeg; q < pend; q += 8) {                              // four MFMA steps of two points; the loads first
-        float av[4], b0[4], b1[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const int p = q + 2 * u + half;
-            const bool ok = p < pend;
-            av[u] = ok && a_ok ? A[(size_t)p * it.a_ld] : 0.0f;
-            b0[u] = ok && b0_ok ? B[(size_t)p * it.b_ld] : 0.0f;
-            b1[u] = ok && b1_ok ? B[(size_t)p * it.b_ld + 32] : 0.0f;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], b0[u], acc0, 0, 0, 0);
-            if (wide) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], b1[u], acc1, 0, 0, 0);
-            bsum += av[u];
-        }
-    }
-    float* out = partial + (size_t)split * G_ALL;
-#pragma unroll
-    for (int r = 0; r < 16; r++) {
-        const int row = acc_row(r, half);
-        if (row < it.a_n) {
-            if (b0_ok) out[it.out_off + row * it.out_ld + j] = acc0[r];
-            if (b1_ok) out[it.out_off + row * it.out_ld + 32 + j] = acc1[r];
-        }
-    }
-    bsum += __shfl_xor(bsum, 32);
-    if (it.bias_off >= 0 && half == 0 && a_ok) out[it.bias_off + j] = bsum;
-}
-
-// ---- the split-bf16 (three-product) mode: moss_lbs_weight_net_forward_bf16x3 / _backward_bf16x3 ---------------------------------------
-// The five wide products (layers 0-3 and bw_fc) forward, in the data gradient and in the weight gradient, on
-// v_mfma_f32_32x32x16_bf16 (mfma_bf16.h): both operands split, hi = bf16(a), lo = bf16(a - hi), and a b taken as
-// lo(a) hi(b) + hi(a) lo(b) + hi(a) hi(b), accumulated in float32.  A lane supplies eight consecutive k per operand; K = 63 pads to 64
-// and 191 to 192 through the same [e, 0, h2] row.  The weights change every step, so there is no pack-once: a weight is split in
-// registers as it is read.  An activation (or a d pre-activation) is split ONCE, when its tile row is stored to LDS as two bf16 planes
-// (the same bytes as the float32 tile).  `saved` and the workspace keep the float32 layouts of the f32 mode (the ReLU masks, the biases'
-// column sums, query / key / value and the head read them as float32), so the two size queries serve both modes; the weight-gradient
-// kernel splits its operands as it reads them, sixteen points per step, and runs the float32 items of the head (query.*, d K, d V)
-// on the f32 loop in the same launch.  Everything else is the f32 mode's code and order.
-constexpr int HB_LD = 136, EHB_LD = 200, QB_LD = 40;     // LDS row strides of the bf16 planes: an odd multiple of 16 bytes mod 256
-constexpr int B_FLOATS = 4 * 1024 > T * HB_LD ? 4 * 1024 : T * HB_LD;   // a pair of planes, or four 32 x 32 float blocks / a float tile
-static_assert(B_FLOATS >= T * H_LD && 2 * T * HB_LD * 2 <= B_FLOATS * 4, "aliased LDS tile");
-
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));   // four floats at a float's alignment (a weight row starts anywhere)
-
-// gemm_wt with both operands split: A as two bf16 planes in LDS (this lane's row), W split as it is read
 template <int K, int LD, bool SKIP>
-__device__ __forceinline__ f32x16 gemm_wt3(const float* __restrict__ W, int n, bool n_ok, const __bf16* a_hi, const __bf16* a_lo, int half,
-                                           f32x16 acc, int kbase = 0)
+__device__ __forceinline__ f32x16 gemm_wt(const float* __restrict__ W, int n, bool n_ok, const RowSplit a_row, int half, f32x16 acc,
+                                          int kbase = 0)
 {
     const float* w = W + (size_t)(n_ok ? n : 0) * LD;
 #pragma unroll 2
     for (int k0 = kbase; k0 < kbase + K; k0 += 16) {
         const int kk = k0 + 8 * half;
-        const bf16x8 ah = *reinterpret_cast<const bf16x8*>(a_hi + kk), al = *reinterpret_cast<const bf16x8*>(a_lo + kk);
+        const bf16x8 ah = *reinterpret_cast<const bf16x8*>(a_row.hi + kk), al = *reinterpret_cast<const bf16x8*>(a_row.lo + kk);
         // this lane's eight weights: W[n][kk ...] (SKIP: the row without its column 63), as two 16-byte reads where all eight exist
         const int first = SKIP && kk > NE ? kk - 1 : kk, valid = SKIP ? (kk + 8 == NE + 1 ? 7 : 8) : min(8, LD - kk);
         float bv[8];
@@ -447,17 +161,33 @@ __device__ __forceinline__ f32x16 gemm_wt3(const float* __restrict__ W, int n, b
     return acc;
 }
 
-// gemm_w with both operands split
+// acc[pt][col] = sum_{k < K} A[pt][k] W[k][col] (rows k >= kvalid and a column that is not ok count as zero): the adjoint products
 template <int K>
-__device__ __forceinline__ f32x16 gemm_w3(const float* __restrict__ W, int ld, int kvalid, int col, bool col_ok, const __bf16* a_hi,
-                                          const __bf16* a_lo, int half)
+__device__ __forceinline__ f32x16 gemm_w(const float* __restrict__ W, int ld, int kvalid, int col, bool col_ok, const float* a_row, int half)
+{
+    f32x16 acc = splat(0.0f);
+    const float* w = W + (col_ok ? col : 0);
+#pragma unroll 2
+    for (int k0 = 0; k0 < K; k0 += 8) {
+        const int kk = k0 + 4 * half;
+        const float4 av = *reinterpret_cast<const float4*>(a_row + kk);
+        float bv[4];
+#pragma unroll
+        for (int s = 0; s < 4; s++) bv[s] = (col_ok && kk + s < kvalid) ? w[(size_t)(kk + s) * ld] : 0.0f;
+        mfma4(acc, av, bv);
+    }
+    return acc;
+}
+
+template <int K>
+__device__ __forceinline__ f32x16 gemm_w(const float* __restrict__ W, int ld, int kvalid, int col, bool col_ok, const RowSplit a_row, int half)
 {
     f32x16 acc = splat(0.0f);
     const float* w = W + (col_ok ? col : 0);
 #pragma unroll 2
     for (int k0 = 0; k0 < K; k0 += 16) {
         const int kk = k0 + 8 * half;
-        const bf16x8 ah = *reinterpret_cast<const bf16x8*>(a_hi + kk), al = *reinterpret_cast<const bf16x8*>(a_lo + kk);
+        const bf16x8 ah = *reinterpret_cast<const bf16x8*>(a_row.hi + kk), al = *reinterpret_cast<const bf16x8*>(a_row.lo + kk);
         float bv[8];
 #pragma unroll
         for (int s = 0; s < 8; s++) bv[s] = (col_ok && kk + s < kvalid) ? w[(size_t)(kk + s) * ld] : 0.0f;
@@ -468,50 +198,54 @@ __device__ __forceinline__ f32x16 gemm_w3(const float* __restrict__ W, int ld, i
     return acc;
 }
 
-__device__ __forceinline__ void store_split(__bf16* hi, __bf16* lo, int idx, float v)
-{
-    __bf16 h, l;
-    split_bf16(v, h, l);
-    hi[idx] = h;
-    lo[idx] = l;
-}
+// ---- the phases both modes share (float32) -------------------------------------------------------------------------------------------
 
-// relu(acc) -> the two LDS planes [row][col] and, with `saved`, the float32 rows of the points that exist
-__device__ __forceinline__ void store_act3(const f32x16& acc, __bf16* hi, __bf16* lo, int ld, int col, int half, float* saved, int sv_col,
-                                           int p0, int P)
+// relu(acc) -> the tile [row][col] and, with `saved`, the rows of the points that exist
+template <class TileT>
+__device__ __forceinline__ void store_act(const f32x16& acc, const TileT& tile, int col, int half, float* saved, int sv_col, int p0, int P)
 {
 #pragma unroll
     for (int r = 0; r < 16; r++) {
         const int row = acc_row(r, half);
         const float v = fmaxf(acc[r], 0.0f);
-        store_split(hi, lo, row * ld + col, v);
+        tile.put(row, col, v);
         if (saved && p0 + row < P) saved[(size_t)(p0 + row) * SV_ROW + sv_col] = v;
     }
 }
 
-__global__ void __launch_bounds__(WG)
-lbs_weight_net_forward_bf16x3_kernel(const moss_lbs_weight_net_args a)
-{
-    __shared__ __attribute__((aligned(16))) __bf16 s_eh_hi[T * EHB_LD], s_eh_lo[T * EHB_LD];   // [e (63), 0, h2 (128)]
-    __shared__ __attribute__((aligned(16))) __bf16 s_a_hi[T * HB_LD], s_a_lo[T * HB_LD];
-    __shared__ __attribute__((aligned(16))) float s_b[B_FLOATS];       // two planes; then bw_fc's four partial blocks (float)
-    __shared__ float s_K[NR * NC], s_V[NR * NC], s_Wq[NF * NF], s_q0[T][NF], s_Q[T][NF], s_s[T][12];
-    __bf16* const s_b_hi = reinterpret_cast<__bf16*>(s_b);
-    __bf16* const s_b_lo = s_b_hi + T * HB_LD;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, half = lane >> 5;
-    const int p0 = blockIdx.x * T, P = a.P;
-    const float* const* par = a.params;
-    float* saved = a.saved;
+// K = M Wk^T + bk, V = M Wv^T + bv (24 x 9) and a copy of Wq, in LDS
+struct alignas(16) HeadConstants { float K[NR * NC], V[NR * NC], Wq[NF * NF]; };
 
-    head_constants(a.Rs, par, s_K, s_V, s_Wq, tid);
+// (no barrier inside)
+__device__ __forceinline__ void head_constants(const float* __restrict__ Rs, const float* const* par, HeadConstants& hc, int tid)
+{
+    if (tid < NR * NC) {
+        const int r = tid / NC, c = tid % NC;
+        float k = par[P_BK][c], v = par[P_BV][c];
+#pragma unroll
+        for (int i = 0; i < NC; i++) {
+            const float m = r == 0 ? 1.0f : Rs[(r - 1) * NC + i];
+            k = __fmaf_rn(m, par[P_WK][c * NC + i], k);
+            v = __fmaf_rn(m, par[P_WV][c * NC + i], v);
+        }
+        hc.K[tid] = k;
+        hc.V[tid] = v;
+    }
+    for (int i = tid; i < NF * NF; i += WG) hc.Wq[i] = par[P_WQ][i];
+}
+
+// [e (63), 0] of the tile's points -> columns 0 .. 63 of the tile and, with `saved`, of the rows of the points that exist (no barrier inside)
+template <class TileT>
+__device__ __forceinline__ void embed(const float* __restrict__ x, const TileT& eh, float* saved, int p0, int P, int tid)
+{
     for (int i = tid; i < T * 3 * NFREQ; i += WG) {
         const int pt = i / (3 * NFREQ), r = i % (3 * NFREQ), f = r / 3, d = r % 3;
-        const float xv = p0 + pt < P ? a.x[(size_t)(p0 + pt) * 3 + d] : 0.0f;
+        const float xv = p0 + pt < P ? x[(size_t)(p0 + pt) * 3 + d] : 0.0f;
         float sn, cs;
         sincosf(xv * (float)(1 << f), &sn, &cs);
         float* sv = saved && p0 + pt < P ? saved + (size_t)(p0 + pt) * SV_ROW + SV_E : nullptr;
         auto put = [&](int k, float v) {
-            store_split(s_eh_hi, s_eh_lo, pt * EHB_LD + k, v);
+            eh.put(pt, k, v);
             if (sv) sv[k] = v;
         };
         put(3 + 6 * f + d, sn);
@@ -519,37 +253,24 @@ lbs_weight_net_forward_bf16x3_kernel(const moss_lbs_weight_net_args a)
         if (f == 0) put(d, xv);
         if (r == 0) put(NE, 0.0f);
     }
-    __syncthreads();
+}
 
-    const int n = 32 * wave + j;                                        // this lane's output channel in the 128-wide layers
-    const int ea = j * EHB_LD, ha = j * HB_LD;
-    f32x16 acc = gemm_wt3<64, NE, false>(par[P_W0], n, true, s_eh_hi + ea, s_eh_lo + ea, half, splat(par[P_B0][n]));
-    store_act3(acc, s_a_hi, s_a_lo, HB_LD, n, half, saved, SV_H0 + n, p0, P);
-    __syncthreads();
-    acc = gemm_wt3<NH, NH, false>(par[P_W1], n, true, s_a_hi + ha, s_a_lo + ha, half, splat(par[P_B1][n]));
-    store_act3(acc, s_b_hi, s_b_lo, HB_LD, n, half, saved, SV_H1 + n, p0, P);
-    __syncthreads();
-    acc = gemm_wt3<NH, NH, false>(par[P_W2], n, true, s_b_hi + ha, s_b_lo + ha, half, splat(par[P_B2][n]));
-    store_act3(acc, s_eh_hi, s_eh_lo, EHB_LD, 64 + n, half, saved, SV_H2 + n, p0, P);
-    __syncthreads();                                                    // (the planes in s_b were last read before this barrier)
-    acc = gemm_wt3<64 + NH, W3_LD, true>(par[P_W3], n, true, s_eh_hi + ea, s_eh_lo + ea, half, splat(par[P_B3][n]));
-    store_act3(acc, s_a_hi, s_a_lo, HB_LD, n, half, saved, SV_H3 + n, p0, P);
-    __syncthreads();
-    // bw_fc: one 32 x 32 block (24 channels), the k range split over the waves; the four partial blocks go to s_b
-    acc = gemm_wt3<NH / 4, NH, false>(par[P_WFC], j, j < NF, s_a_hi + ha, s_a_lo + ha, half, splat(0.0f), (NH / 4) * wave);
-#pragma unroll
-    for (int r = 0; r < 16; r++) s_b[wave * 1024 + acc_row(r, half) * 32 + j] = acc[r];
-    __syncthreads();
+// the forward's head, eight threads per point: q0 from bw_fc's four partial blocks (`part`: 4 x 32 x 32 floats, summed in wave
+// order), Q, the scores, the softmax, out; with `saved`, q0, Q, a and the row's padding.  The caller's barrier precedes it.
+struct alignas(16) ForwardHeadLds { float q0[T][NF], Q[T][NF], s[T][12]; };
 
-    // the head, float32 as in the f32 kernel: eight threads per point
+__device__ __forceinline__ void forward_head(const moss_lbs_weight_net_args& a, const float* part, const HeadConstants& hc, ForwardHeadLds& s,
+                                             int p0, int tid)
+{
+    const float* const* par = a.params;
     const int pt = tid >> 3, sub = tid & 7;
-    const bool live = p0 + pt < P;
-    float* sv = saved && live ? saved + (size_t)(p0 + pt) * SV_ROW : nullptr;
+    const bool live = p0 + pt < a.P;
+    float* sv = a.saved && live ? a.saved + (size_t)(p0 + pt) * SV_ROW : nullptr;
 #pragma unroll
     for (int k = sub; k < NF; k += 8) {
-        const float* q = s_b + pt * 32 + k;
+        const float* q = part + pt * 32 + k;
         const float v = (((q[0] + q[1024]) + q[2048]) + q[3072]) + par[P_BFC][k];
-        s_q0[pt][k] = v;
+        s.q0[pt][k] = v;
         if (sv) sv[SV_Q0 + k] = v;
     }
     __syncthreads();
@@ -557,23 +278,23 @@ lbs_weight_net_forward_bf16x3_kernel(const moss_lbs_weight_net_args a)
     for (int i = sub; i < NF; i += 8) {
         float v = par[P_BQ][i];
 #pragma unroll
-        for (int k = 0; k < NF; k++) v = __fmaf_rn(s_Wq[i * NF + k], s_q0[pt][k], v);
-        s_Q[pt][i] = v;
+        for (int k = 0; k < NF; k++) v = __fmaf_rn(hc.Wq[i * NF + k], s.q0[pt][k], v);
+        s.Q[pt][i] = v;
         if (sv) sv[SV_Q + i] = v;
     }
     __syncthreads();
     for (int c = sub; c < NC; c += 8) {
         float v = 0.0f;
 #pragma unroll
-        for (int i = 0; i < NF; i++) v = __fmaf_rn(s_Q[pt][i], s_K[i * NC + c], v);
-        s_s[pt][c] = v / sqrtf((float)NF);
+        for (int i = 0; i < NF; i++) v = __fmaf_rn(s.Q[pt][i], hc.K[i * NC + c], v);
+        s.s[pt][c] = v / sqrtf((float)NF);
     }
     __syncthreads();
-    float att[NC], m = s_s[pt][0], sum = 0.0f;
+    float att[NC], m = s.s[pt][0], sum = 0.0f;
 #pragma unroll
-    for (int c = 1; c < NC; c++) m = fmaxf(m, s_s[pt][c]);
+    for (int c = 1; c < NC; c++) m = fmaxf(m, s.s[pt][c]);
 #pragma unroll
-    for (int c = 0; c < NC; c++) { att[c] = expf(s_s[pt][c] - m); sum += att[c]; }
+    for (int c = 0; c < NC; c++) { att[c] = expf(s.s[pt][c] - m); sum += att[c]; }
 #pragma unroll
     for (int c = 0; c < NC; c++) att[c] /= sum;
     if (sv) {
@@ -590,41 +311,31 @@ lbs_weight_net_forward_bf16x3_kernel(const moss_lbs_weight_net_args a)
         for (int o = sub; o < NR; o += 8) {
             float v = 0.0f;
 #pragma unroll
-            for (int c = 0; c < NC; c++) v = __fmaf_rn(att[c], s_V[o * NC + c], v);
+            for (int c = 0; c < NC; c++) v = __fmaf_rn(att[c], hc.V[o * NC + c], v);
             a.out[(size_t)(p0 + pt) * NR + o] = v;
         }
     }
 }
 
-// backward 1, split-bf16: the data gradients of a tile of points
-__global__ void __launch_bounds__(WG)
-lbs_weight_net_backward_data_bf16x3_kernel(const moss_lbs_weight_net_backward_args a, float* __restrict__ ws)
-{
-    __shared__ __attribute__((aligned(16))) __bf16 s_x_hi[T * HB_LD], s_x_lo[T * HB_LD], s_y_hi[T * HB_LD], s_y_lo[T * HB_LD];
-    __shared__ __attribute__((aligned(16))) __bf16 s_dq0_hi[T * QB_LD], s_dq0_lo[T * QB_LD];
-    __shared__ __attribute__((aligned(16))) float s_z[B_FLOATS];        // two planes (d z1); then d e as a float tile
-    __shared__ float s_K[NR * NC], s_V[NR * NC], s_Wq[NF * NF], s_g[T][NR], s_att[T][12], s_da[T][12], s_ds[T][12], s_dQ[T][NF];
-    __bf16* const s_z_hi = reinterpret_cast<__bf16*>(s_z);
-    __bf16* const s_z_lo = s_z_hi + T * HB_LD;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, half = lane >> 5;
-    const int p0 = blockIdx.x * T, P = a.P;
-    const float* const* par = a.params;
-    const float* saved = a.saved;
+// the backward's first phase, eight threads per point: d a, d s / sqrt(24), d Q and d q0 from g_out and the saved softmax; d s, d Q and
+// d q0 go to the workspace (with the row's padding), d q0 also into the tile `dq0`, whose padding columns are zeroed.  Ends in a barrier.
+struct alignas(16) AdjointLds { float g[T][NR], att[T][12], da[T][12], ds[T][12], dQ[T][NF]; };
 
-    head_constants(a.Rs, par, s_K, s_V, s_Wq, tid);
+template <class TileT>
+__device__ __forceinline__ void attention_adjoint(const moss_lbs_weight_net_backward_args& a, float* __restrict__ ws, const HeadConstants& hc,
+                                                  AdjointLds& s, const TileT& dq0, int p0, int tid)
+{
+    constexpr int PAD = TileT::LD - NF;
+    const int P = a.P;
     for (int i = tid; i < T * NR; i += WG) {
         const int pt = i / NR;
-        s_g[pt][i % NR] = p0 + pt < P ? a.g_out[(size_t)p0 * NR + i] : 0.0f;
+        s.g[pt][i % NR] = p0 + pt < P ? a.g_out[(size_t)p0 * NR + i] : 0.0f;
     }
     for (int i = tid; i < T * NC; i += WG) {
         const int pt = i / NC, c = i % NC;
-        s_att[pt][c] = p0 + pt < P ? saved[(size_t)(p0 + pt) * SV_ROW + SV_A + c] : 0.0f;
+        s.att[pt][c] = p0 + pt < P ? a.saved[(size_t)(p0 + pt) * SV_ROW + SV_A + c] : 0.0f;
     }
-    for (int i = tid; i < T * (QB_LD - NF); i += WG) {
-        const int idx = (i / (QB_LD - NF)) * QB_LD + NF + i % (QB_LD - NF);
-        s_dq0_hi[idx] = (__bf16)0.0f;
-        s_dq0_lo[idx] = (__bf16)0.0f;
-    }
+    for (int i = tid; i < T * PAD; i += WG) dq0.put(i / PAD, NF + i % PAD, 0.0f);
     __syncthreads();
 
     const int pt = tid >> 3, sub = tid & 7;
@@ -633,17 +344,17 @@ lbs_weight_net_backward_data_bf16x3_kernel(const moss_lbs_weight_net_backward_ar
     for (int c = sub; c < NC; c += 8) {
         float v = 0.0f;
 #pragma unroll
-        for (int o = 0; o < NR; o++) v = __fmaf_rn(s_g[pt][o], s_V[o * NC + c], v);
-        s_da[pt][c] = v;
+        for (int o = 0; o < NR; o++) v = __fmaf_rn(s.g[pt][o], hc.V[o * NC + c], v);
+        s.da[pt][c] = v;
     }
     __syncthreads();
     {
         float dot = 0.0f;
 #pragma unroll
-        for (int c = 0; c < NC; c++) dot = __fmaf_rn(s_att[pt][c], s_da[pt][c], dot);
+        for (int c = 0; c < NC; c++) dot = __fmaf_rn(s.att[pt][c], s.da[pt][c], dot);
         for (int c = sub; c < NC; c += 8) {
-            const float v = s_att[pt][c] * (s_da[pt][c] - dot) / sqrtf((float)NF);
-            s_ds[pt][c] = v;
+            const float v = s.att[pt][c] * (s.da[pt][c] - dot) / sqrtf((float)NF);
+            s.ds[pt][c] = v;
             if (wrow) wrow[WS_DS + c] = v;
         }
         if (wrow && sub == 7)
@@ -654,8 +365,8 @@ lbs_weight_net_backward_data_bf16x3_kernel(const moss_lbs_weight_net_backward_ar
     for (int i = sub; i < NF; i += 8) {
         float v = 0.0f;
 #pragma unroll
-        for (int c = 0; c < NC; c++) v = __fmaf_rn(s_ds[pt][c], s_K[i * NC + c], v);
-        s_dQ[pt][i] = v;
+        for (int c = 0; c < NC; c++) v = __fmaf_rn(s.ds[pt][c], hc.K[i * NC + c], v);
+        s.dQ[pt][i] = v;
         if (wrow) wrow[WS_DQ + i] = v;
     }
     __syncthreads();
@@ -663,53 +374,21 @@ lbs_weight_net_backward_data_bf16x3_kernel(const moss_lbs_weight_net_backward_ar
     for (int k = sub; k < NF; k += 8) {
         float v = 0.0f;
 #pragma unroll
-        for (int i = 0; i < NF; i++) v = __fmaf_rn(s_Wq[i * NF + k], s_dQ[pt][i], v);
-        store_split(s_dq0_hi, s_dq0_lo, pt * QB_LD + k, v);
+        for (int i = 0; i < NF; i++) v = __fmaf_rn(hc.Wq[i * NF + k], s.dQ[pt][i], v);
+        dq0.put(pt, k, v);
         if (wrow) wrow[WS_DQ0 + k] = v;
     }
     __syncthreads();
+}
 
-    const int n = 32 * wave + j;
-    // d z = (h > 0) * acc -> the LDS planes and the workspace (float32)
-    auto store_dz = [&](const f32x16& acc, __bf16* hi, __bf16* lo, int sv_col, int ws_col) {
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-            const int row = acc_row(r, half);
-            const bool ok = p0 + row < P;
-            const float h = ok ? saved[(size_t)(p0 + row) * SV_ROW + sv_col + n] : 0.0f;
-            const float v = h > 0.0f ? acc[r] : 0.0f;
-            store_split(hi, lo, row * HB_LD + n, v);
-            if (ok) ws[(size_t)(p0 + row) * WS_ROW + ws_col + n] = v;
-        }
-    };
-    const int ha = j * HB_LD;
-    f32x16 acc = gemm_w3<32>(par[P_WFC], NH, NF, n, true, s_dq0_hi + j * QB_LD, s_dq0_lo + j * QB_LD, half);
-    store_dz(acc, s_x_hi, s_x_lo, SV_H3, WS_DZ3);
-    __syncthreads();
-    acc = gemm_w3<NH>(par[P_W3], W3_LD, NH, NE + n, true, s_x_hi + ha, s_x_lo + ha, half);
-    store_dz(acc, s_y_hi, s_y_lo, SV_H2, WS_DZ2);
-    __syncthreads();
-    acc = gemm_w3<NH>(par[P_W2], NH, NH, n, true, s_y_hi + ha, s_y_lo + ha, half);
-    store_dz(acc, s_z_hi, s_z_lo, SV_H1, WS_DZ1);
-    __syncthreads();
-    acc = gemm_w3<NH>(par[P_W1], NH, NH, n, true, s_z_hi + ha, s_z_lo + ha, half);
-    store_dz(acc, s_y_hi, s_y_lo, SV_H0, WS_DZ0);                       // (d z2 in s_y was last read before the barrier above)
-    __syncthreads();
-    // d e = d z3 . W3[:, :63] + d z0 . W0: two blocks of 32 columns each, one product per wave, the two halves into s_z as floats
-    // (its planes, d z1, were last read before the barrier above)
-    {
-        const int col = 32 * (wave & 1) + j;
-        acc = (wave >> 1) == 0 ? gemm_w3<NH>(par[P_W3], W3_LD, NH, col, col < NE, s_x_hi + ha, s_x_lo + ha, half)
-                               : gemm_w3<NH>(par[P_W0], NE, NH, col, col < NE, s_y_hi + ha, s_y_lo + ha, half);
-#pragma unroll
-        for (int r = 0; r < 16; r++) s_z[acc_row(r, half) * H_LD + 64 * (wave >> 1) + col] = acc[r];
-    }
-    __syncthreads();
+// g_x from d e: `de` is a float tile of stride H_LD whose columns 0 .. 62 and 64 .. 126 hold the two halves of d e (W3's and W0's)
+__device__ __forceinline__ void gx_tail(const moss_lbs_weight_net_backward_args& a, const float* de, int p0, int tid)
+{
     if (tid < T * 3) {
         const int q = tid / 3, d = tid % 3;
-        if (p0 + q < P) {
-            const float* z = s_z + q * H_LD;
-            const float* e = saved + (size_t)(p0 + q) * SV_ROW + SV_E;
+        if (p0 + q < a.P) {
+            const float* z = de + q * H_LD;
+            const float* e = a.saved + (size_t)(p0 + q) * SV_ROW + SV_E;
             float v = z[d] + z[64 + d];
 #pragma unroll
             for (int f = 0; f < NFREQ; f++) {
@@ -722,13 +401,119 @@ lbs_weight_net_backward_data_bf16x3_kernel(const moss_lbs_weight_net_backward_ar
     }
 }
 
-// backward 2, split-bf16: one (32 x 64) block of one weight gradient over one range of points, per wave.  The items below `n_split` are
-// the five wide products: STEPS x sixteen points per iteration, a lane reads its column at eight consecutive points per operand and
-// step and splits them; the bias is the float32 column sum.  The other items (query.weight / bias, d K, d V) stay float32: the loop of
-// the f32 kernel, in the same launch, so that their waves run beside the wide ones.
+// ---- the kernels: <false> the f32 mode, <true> the split-bf16 mode -------------------------------------------------------------------------
+
+template <bool SPLIT>
 __global__ void __launch_bounds__(WG)
-lbs_weight_net_backward_weights_bf16x3_kernel(int P, int chunk, const float* __restrict__ saved, const float* __restrict__ ws,
-                                              const float* __restrict__ g_out, float* __restrict__ partial, const WgItems items, int n_split)
+lbs_weight_net_forward_kernel(const moss_lbs_weight_net_args a)
+{
+    typedef Tile<SPLIT, 64 + NH> TileEH;
+    typedef Tile<SPLIT, NH> TileH;
+    __shared__ __attribute__((aligned(16))) float s_eh[TileEH::FLOATS], s_a[TileH::FLOATS], s_b[TileH::FLOATS];
+    __shared__ HeadConstants s_hc;
+    __shared__ ForwardHeadLds s_head;
+    const TileEH t_eh(s_eh);                                            // [e (63), 0, h2 (128)]
+    const TileH t_a(s_a), t_b(s_b);                                     // (s_b: then bw_fc's four partial blocks, as floats)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, half = lane >> 5;
+    const int p0 = blockIdx.x * T, P = a.P;
+    const float* const* par = a.params;
+    float* saved = a.saved;
+
+    head_constants(a.Rs, par, s_hc, tid);
+    embed(a.x, t_eh, saved, p0, P, tid);
+    __syncthreads();
+
+    const int n = 32 * wave + j;                                        // this lane's output channel in the 128-wide layers
+    f32x16 acc = gemm_wt<64, NE, false>(par[P_W0], n, true, t_eh.row(j), half, splat(par[P_B0][n]));
+    store_act(acc, t_a, n, half, saved, SV_H0 + n, p0, P);
+    __syncthreads();
+    acc = gemm_wt<NH, NH, false>(par[P_W1], n, true, t_a.row(j), half, splat(par[P_B1][n]));
+    store_act(acc, t_b, n, half, saved, SV_H1 + n, p0, P);
+    __syncthreads();
+    acc = gemm_wt<NH, NH, false>(par[P_W2], n, true, t_b.row(j), half, splat(par[P_B2][n]));
+    store_act(acc, t_eh, 64 + n, half, saved, SV_H2 + n, p0, P);
+    __syncthreads();                                                    // (h1 in s_b was last read before this barrier)
+    acc = gemm_wt<64 + NH, W3_LD, true>(par[P_W3], n, true, t_eh.row(j), half, splat(par[P_B3][n]));
+    store_act(acc, t_a, n, half, saved, SV_H3 + n, p0, P);
+    __syncthreads();
+    // bw_fc: one 32 x 32 block (24 channels), the k range split over the waves; the four partial blocks go to s_b
+    acc = gemm_wt<NH / 4, NH, false>(par[P_WFC], j, j < NF, t_a.row(j), half, splat(0.0f), (NH / 4) * wave);
+#pragma unroll
+    for (int r = 0; r < 16; r++) s_b[wave * 1024 + acc_row(r, half) * 32 + j] = acc[r];
+    __syncthreads();
+    forward_head(a, s_b, s_hc, s_head, p0, tid);
+}
+
+// backward 1: the data gradients of a tile of points
+template <bool SPLIT>
+__global__ void __launch_bounds__(WG)
+lbs_weight_net_backward_data_kernel(const moss_lbs_weight_net_backward_args a, float* __restrict__ ws)
+{
+    typedef Tile<SPLIT, NH> TileH;
+    typedef Tile<SPLIT, 32> TileQ;
+    __shared__ __attribute__((aligned(16))) float s_x[TileH::FLOATS], s_y[TileH::FLOATS], s_z[TileH::FLOATS], s_dq0[TileQ::FLOATS];
+    __shared__ HeadConstants s_hc;
+    __shared__ AdjointLds s_adj;
+    const TileH t_x(s_x), t_y(s_y), t_z(s_z);                           // (s_z: d z1; then d e as a float tile)
+    const TileQ t_dq0(s_dq0);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, half = lane >> 5;
+    const int p0 = blockIdx.x * T, P = a.P;
+    const float* const* par = a.params;
+    const float* saved = a.saved;
+
+    head_constants(a.Rs, par, s_hc, tid);
+    attention_adjoint(a, ws, s_hc, s_adj, t_dq0, p0, tid);
+
+    const int n = 32 * wave + j;
+    // d z = (h > 0) * acc -> the tile and the workspace
+    auto store_dz = [&](const f32x16& acc, const TileH& tile, int sv_col, int ws_col) {
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const int row = acc_row(r, half);
+            const bool ok = p0 + row < P;
+            const float h = ok ? saved[(size_t)(p0 + row) * SV_ROW + sv_col + n] : 0.0f;
+            const float v = h > 0.0f ? acc[r] : 0.0f;
+            tile.put(row, n, v);
+            if (ok) ws[(size_t)(p0 + row) * WS_ROW + ws_col + n] = v;
+        }
+    };
+    f32x16 acc = gemm_w<32>(par[P_WFC], NH, NF, n, true, t_dq0.row(j), half);
+    store_dz(acc, t_x, SV_H3, WS_DZ3);
+    __syncthreads();
+    acc = gemm_w<NH>(par[P_W3], W3_LD, NH, NE + n, true, t_x.row(j), half);
+    store_dz(acc, t_y, SV_H2, WS_DZ2);
+    __syncthreads();
+    acc = gemm_w<NH>(par[P_W2], NH, NH, n, true, t_y.row(j), half);
+    store_dz(acc, t_z, SV_H1, WS_DZ1);
+    __syncthreads();
+    acc = gemm_w<NH>(par[P_W1], NH, NH, n, true, t_z.row(j), half);
+    store_dz(acc, t_y, SV_H0, WS_DZ0);                                  // (d z2 in s_y was last read before the barrier above)
+    __syncthreads();
+    // d e = d z3 . W3[:, :63] + d z0 . W0: two blocks of 32 columns each, one product per wave, the two halves into s_z as floats
+    // (d z1 in it was last read before the barrier above)
+    {
+        const int col = 32 * (wave & 1) + j;
+        acc = (wave >> 1) == 0 ? gemm_w<NH>(par[P_W3], W3_LD, NH, col, col < NE, t_x.row(j), half)
+                               : gemm_w<NH>(par[P_W0], NE, NH, col, col < NE, t_y.row(j), half);
+#pragma unroll
+        for (int r = 0; r < 16; r++) s_z[acc_row(r, half) * H_LD + 64 * (wave >> 1) + col] = acc[r];
+    }
+    __syncthreads();
+    gx_tail(a, s_z, p0, tid);
+}
+
+// backward 2: one (32 x 64) block of one weight gradient over one range of points, per wave.  In the split-bf16 mode the first
+// `items.wide` items, the five wide products, take STEPS x sixteen points per iteration: a lane reads its column at eight consecutive
+// points per operand and step and splits them; the bias is the float32 column sum.  Its other items (query.weight / bias, d K, d V)
+// stay float32: the f32 mode's loop, in the same launch, so that their waves run beside the wide ones.
+struct WgItem { int a_src, a_off, a_ld, a_n, b_src, b_off, b_ld, b_n, out_off, out_ld, bias_off; };
+constexpr int MAX_ITEMS = 40;
+struct WgItems { int count, wide; WgItem it[MAX_ITEMS]; };
+
+template <bool SPLIT>
+__global__ void __launch_bounds__(WG)
+lbs_weight_net_backward_weights_kernel(int P, int chunk, const float* __restrict__ saved, const float* __restrict__ ws,
+                                       const float* __restrict__ g_out, float* __restrict__ partial, const WgItems items)
 {
     constexpr int STEPS = 2;
     const int lane = threadIdx.x & 63, j = lane & 31, half = lane >> 5;
@@ -744,7 +529,7 @@ lbs_weight_net_backward_weights_bf16x3_kernel(int P, int chunk, const float* __r
     f32x16 acc0 = splat(0.0f), acc1 = splat(0.0f);
     float bsum = 0.0f;
     const bool wide = it.b_n > 32;                                      // (wave-uniform, as is the choice of the loop)
-    if (item < n_split) {
+    if (SPLIT && item < items.wide) {
         for (int q = pbeg; q < pend; q += 16 * STEPS) {                 // the loads of all steps first
             float av[STEPS][8], b0[STEPS][8], b1[STEPS][8];
 #pragma unroll
@@ -773,17 +558,19 @@ lbs_weight_net_backward_weights_bf16x3_kernel(int P, int chunk, const float* __r
         }
     } else {
         for (int q = pbeg; q < pend; q += 8) {                          // four MFMA steps of two points; the loads first
-            float av[4], b0[4];
+            float av[4], b0[4], b1[4];
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 const int p = q + 2 * u + half;
                 const bool ok = p < pend;
                 av[u] = ok && a_ok ? A[(size_t)p * it.a_ld] : 0.0f;
                 b0[u] = ok && b0_ok ? B[(size_t)p * it.b_ld] : 0.0f;
+                b1[u] = ok && b1_ok ? B[(size_t)p * it.b_ld + 32] : 0.0f;
             }
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], b0[u], acc0, 0, 0, 0);
+                if (!SPLIT && wide) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], b1[u], acc1, 0, 0, 0);   // (the split mode's float32 items are narrow)
                 bsum += av[u];
             }
         }
@@ -877,13 +664,10 @@ void add_items(WgItems& w, int a_src, int a_off, int a_cols, int b_src, int b_of
 }
 
 // the item table; the first `wide` items are the five wide products (what the split-bf16 mode runs on the bf16-input matrix cores)
-struct ItemTable { WgItems all; int wide; };
-
-const ItemTable& weight_items()
+const WgItems& weight_items()
 {
-    static const ItemTable table = [] {
-        ItemTable t{};
-        WgItems& w = t.all;
+    static const WgItems table = [] {
+        WgItems w{};
         enum { SAVED, WS, GOUT };
         add_items(w, WS, WS_DZ0, NH, SAVED, SV_E, NE, G_W0, NE, G_B0);
         add_items(w, WS, WS_DZ1, NH, SAVED, SV_H0, NH, G_W1, NH, G_B1);
@@ -891,11 +675,11 @@ const ItemTable& weight_items()
         add_items(w, WS, WS_DZ3, NH, SAVED, SV_E, NE, G_W3, W3_LD, G_B3);
         add_items(w, WS, WS_DZ3, NH, SAVED, SV_H2, NH, G_W3 + NE, W3_LD, -1);
         add_items(w, WS, WS_DQ0, NF, SAVED, SV_H3, NH, G_WFC, NH, G_BFC);
-        t.wide = w.count;
+        w.wide = w.count;
         add_items(w, WS, WS_DQ, NF, SAVED, SV_Q0, NF, G_WQ, NF, G_BQ);
         add_items(w, SAVED, SV_Q, NF, WS, WS_DS, NC, G_DK, NC, -1);       // d K[i][c] = sum_p Q[i] d s[c] / sqrt(24)
         add_items(w, GOUT, 0, NR, SAVED, SV_A, NC, G_DV, NC, -1);         // d V[j][c] = sum_p g[j] a[c]
-        return t;
+        return w;
     }();
     return table;
 }
@@ -925,10 +709,8 @@ static int forward_impl(const char* fn, const moss_lbs_weight_net_args* a, void*
     for (int i = 0; i < NPAR; i++)
         if (!a->params[i]) return invalid_arg(fn, "null parameter tensor (all 16 are read)");
     static_assert(MAX_ITEMS >= 37, "item table");
-    if (bf16x3)
-        hipLaunchKernelGGL(lbs_weight_net_forward_bf16x3_kernel, dim3((a->P + T - 1) / T), dim3(WG), 0, (hipStream_t)stream, *a);
-    else
-        hipLaunchKernelGGL(lbs_weight_net_forward_kernel, dim3((a->P + T - 1) / T), dim3(WG), 0, (hipStream_t)stream, *a);
+    hipLaunchKernelGGL(bf16x3 ? lbs_weight_net_forward_kernel<true> : lbs_weight_net_forward_kernel<false>, dim3((a->P + T - 1) / T),
+                       dim3(WG), 0, (hipStream_t)stream, *a);
     return launch_status(fn);
 }
 
@@ -950,20 +732,14 @@ static int backward_impl(const char* fn, const moss_lbs_weight_net_backward_args
     float* partial = reinterpret_cast<float*>(a->workspace + ws_rows_bytes(P));
     GradPtrs gp;
     for (int i = 0; i < NPAR; i++) gp.g[i] = a->grads[i];
-    const ItemTable& table = weight_items();
-    const WgItems& items = table.all;
+    const WgItems& items = weight_items();
     const dim3 grid((items.count * SPLITS + WG / 64 - 1) / (WG / 64));
-    if (bf16x3) {
-        const int chunk = ((P + SPLITS - 1) / SPLITS + 15) & ~15;     // points per split, a multiple of 16: an MFMA step takes sixteen
-        hipLaunchKernelGGL(lbs_weight_net_backward_data_bf16x3_kernel, dim3((P + T - 1) / T), dim3(WG), 0, s, *a, ws);
-        hipLaunchKernelGGL(lbs_weight_net_backward_weights_bf16x3_kernel, grid, dim3(WG), 0, s, P, chunk, a->saved, (const float*)ws,
-                           a->g_out, partial, items, table.wide);
-    } else {
-        const int chunk = ((P + SPLITS - 1) / SPLITS + 1) & ~1;       // points per split, even: an MFMA step takes two
-        hipLaunchKernelGGL(lbs_weight_net_backward_data_kernel, dim3((P + T - 1) / T), dim3(WG), 0, s, *a, ws);
-        hipLaunchKernelGGL(lbs_weight_net_backward_weights_kernel, grid, dim3(WG), 0, s, P, chunk, a->saved, (const float*)ws, a->g_out,
-                           partial, items);
-    }
+    const int step = bf16x3 ? 16 : 2;                                 // the points an MFMA step takes
+    const int chunk = ((P + SPLITS - 1) / SPLITS + step - 1) & ~(step - 1);   // points per split, a multiple of `step`
+    hipLaunchKernelGGL(bf16x3 ? lbs_weight_net_backward_data_kernel<true> : lbs_weight_net_backward_data_kernel<false>,
+                       dim3((P + T - 1) / T), dim3(WG), 0, s, *a, ws);
+    hipLaunchKernelGGL(bf16x3 ? lbs_weight_net_backward_weights_kernel<true> : lbs_weight_net_backward_weights_kernel<false>, grid,
+                       dim3(WG), 0, s, P, chunk, a->saved, (const float*)ws, a->g_out, partial, items);
     hipLaunchKernelGGL(lbs_weight_net_backward_fold_kernel, dim3((G_NET + WG - 1) / WG + 1), dim3(WG), 0, s, (const float*)partial,
                        a->Rs, a->params[P_WK], a->params[P_WV], gp, a->g_Rs);
     return launch_status(fn);

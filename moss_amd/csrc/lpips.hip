@@ -284,138 +284,54 @@ struct ConvArgs {
     int nimg;
 };
 
-// WM waves along the rows, WK waves along K (WM * WK = 4).  DYN is a template parameter so that the static instantiation stays the
-// code it was.
-template <int WM, int WK, int MODE, bool DYN>
-__global__ void __launch_bounds__(WG)
-conv3x3_mfma_kernel(const ConvArgs a)
+// ---- what the three wide-convolution kernels share: the size, the A tile's gather, the epilogue ----------------------------------------
+// The convolution's size: the launch's, or with DYN what the device holds now.  False: every row of this workgroup lies beyond the
+// actual M, and the whole workgroup returns before its first barrier.
+template <bool DYN>
+__device__ __forceinline__ bool conv_size(const ConvArgs& a, int m0, int& H, int& W, int& M, int& mask_rows)
 {
-    static_assert(WM * WK == 4 && (WK == 1 || WM == 1), "four waves");
-    constexpr int BM = 32 * WM, A_F4 = BM * (KC / 4) / WG, B_F4 = BN * (KC / 4) / WG;
-    __shared__ __attribute__((aligned(16))) float s_A[BM * LD], s_B[BN * LD];
-    static_assert(BN * LD >= 4 * 32 * 32, "s_B doubles as the buffer of the four partial blocks");
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, half = lane >> 5;
-    const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
-    int H = a.H, W = a.W, M = a.M, mask_rows = a.mask_rows;
+    H = a.H; W = a.W; M = a.M; mask_rows = a.mask_rows;
     if (DYN) {
         actual_size(a.dyn, H, W);
         mask_rows = H * W;
         M = a.nimg * mask_rows;
-        if (m0 >= M) return;                                             // (the whole workgroup, before its first barrier)
+        if (m0 >= M) return false;
     }
-    const int HW = H * W, Cin = a.Cin, Cout = a.Cout;
-    const int K9 = 9 * Cin, nchunks = K9 / KC;
-    const float* __restrict__ in = a.in;                                 // (locals: the lambdas below must not take the address of `a`)
-    const float* __restrict__ bias = a.bias;
-    float* __restrict__ out = a.out;
-    const uint32_t* __restrict__ mask_in = a.mask_in;
-    uint32_t* __restrict__ mask_out = a.mask_out;
-
-    // the rows and float4 columns this thread stages: rows r0 + 16 i, column c4
-    const int c4 = tid & 15, r0 = tid >> 4;
-    int rpix[A_F4], ryx[A_F4];
-#pragma unroll
-    for (int i = 0; i < A_F4; i++) {
-        const int m = m0 + r0 + 16 * i;
-        rpix[i] = -1; ryx[i] = 0;
-        if (m < M) {
-            const int p = m % HW, y = p / W;
-            rpix[i] = m; ryx[i] = (y << 16) | (p - y * W);
-        }
-    }
-    const float* wbase = a.w + (size_t)(n0 + r0) * K9 + 4 * c4;
-    f32x4 ra[A_F4], rb[B_F4];
-    auto gload = [&](int kc) __attribute__((always_inline)) {
-        const int k0 = kc * KC, tap = k0 / Cin, ci0 = k0 - tap * Cin, dy = tap / 3 - 1, dx = tap % 3 - 1;
-#pragma unroll
-        for (int i = 0; i < A_F4; i++) {
-            const int yy = (ryx[i] >> 16) + dy, xx = (ryx[i] & 0xffff) + dx;
-            const bool ok = rpix[i] >= 0 && yy >= 0 && yy < H && xx >= 0 && xx < W;
-            ra[i] = ok ? *reinterpret_cast<const f32x4*>(in + (size_t)(rpix[i] + dy * W + dx) * Cin + ci0 + 4 * c4)
-                       : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        }
-#pragma unroll
-        for (int i = 0; i < B_F4; i++) rb[i] = *reinterpret_cast<const f32x4*>(wbase + (size_t)(16 * i) * K9 + k0);
-    };
-    auto sstore = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < A_F4; i++) *reinterpret_cast<f32x4*>(s_A + (r0 + 16 * i) * LD + 4 * c4) = ra[i];
-#pragma unroll
-        for (int i = 0; i < B_F4; i++) *reinterpret_cast<f32x4*>(s_B + (r0 + 16 * i) * LD + 4 * c4) = rb[i];
-    };
-
-    f32x16 acc0 = splat(0.0f), acc1 = splat(0.0f);
-    const float* a_row = s_A + ((WK == 1 ? 32 * wave : 0) + j) * LD + 4 * half;
-    const float* b_row = s_B + j * LD + 4 * half;
-    gload(0);
-    sstore();
-    __syncthreads();
-    for (int kc = 0; kc < nchunks; kc++) {
-        if (kc + 1 < nchunks) gload(kc + 1);                             // in flight during the MFMAs of this slice
-#pragma unroll
-        for (int step = (WK == 1 ? 0 : wave); step < KC / 8; step += WK) {
-            const f32x4 av = *reinterpret_cast<const f32x4*>(a_row + 8 * step);
-            const f32x4 b0 = *reinterpret_cast<const f32x4*>(b_row + 8 * step);
-            const f32x4 b1 = *reinterpret_cast<const f32x4*>(b_row + 32 * LD + 8 * step);
-            mfma4(acc0, av, b0);
-            mfma4(acc1, av, b1);
-        }
-        __syncthreads();
-        if (kc + 1 < nchunks) {
-            sstore();
-            __syncthreads();
-        }
-    }
-
-    // one output element per lane and call; every lane of the wave calls it (the ballot): row m, channel n = 32-aligned base + j
-    auto emit = [&](float v, int m, int n) __attribute__((always_inline)) {
-        const bool valid = m < M;
-        if (MODE == MODE_FWD) {
-            v += bias[n];
-            const bool pos = v > 0.0f;
-            if (valid) out[(size_t)m * Cout + n] = pos ? v : 0.0f;
-            if (mask_out) {
-                const unsigned long long b = __ballot(pos);
-                if (j == 0 && m < mask_rows) mask_out[(size_t)m * (Cout >> 5) + (n >> 5)] = (uint32_t)(half ? b >> 32 : b);
-            }
-        } else if (MODE == MODE_BWD_MASK) {
-            if (valid) {
-                const uint32_t word = mask_in[(size_t)m * (Cout >> 5) + (n >> 5)];
-                out[(size_t)m * Cout + n] = (word >> j) & 1u ? v : 0.0f;
-            }
-        } else {
-            if (valid) out[(size_t)m * Cout + n] = v;
-        }
-    };
-    if (WK == 1) {
-#pragma unroll
-        for (int r = 0; r < 16; r++) emit(acc0[r], m0 + 32 * wave + acc_row(r, half), n0 + j);
-#pragma unroll
-        for (int r = 0; r < 16; r++) emit(acc1[r], m0 + 32 * wave + acc_row(r, half), n0 + 32 + j);
-    } else {
-        // the four partial 32 x 32 blocks through LDS (s_B: every wave is past its last read), summed in wave order
-#pragma unroll
-        for (int b = 0; b < 2; b++) {
-#pragma unroll
-            for (int r = 0; r < 16; r++) s_B[wave * 1024 + acc_row(r, half) * 32 + j] = b ? acc1[r] : acc0[r];
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const int row = (tid >> 5) + 8 * i;                      // (tid >> 5) & 1 == half, tid & 31 == j
-                const float* q = s_B + row * 32 + j;
-                emit(((q[0] + q[1024]) + q[2048]) + q[3072], m0 + row, n0 + 32 * b + j);
-            }
-            __syncthreads();
-        }
-    }
+    return true;
 }
 
-// ---- the wide convolutions, bf16 operands ------------------------------------------------------------------------------------------
-// What follows the K loop: conv3x3_mfma_kernel's epilogue, statement for statement (the C/D layout of the 32 x 32 tile does not depend
-// on the operand type) -- bias and ReLU with the sign bits by one ballot per accumulator register, or the ReLU bits of the layer
-// below, or nothing; with WK == 4 the four waves' partial blocks go through `s_part` (4096 floats of LDS every wave is done reading)
-// and are summed in wave order.  A copy, because the f32 kernel is left untouched: calling this from it moved its register
-// allocation (62 -> 64 / 66 SGPRs in <4,1,FWD>), and its instantiations are to stay the code they were.
+// What one thread stages of the A tile: F4 rows, RPP apart from row `first` on, at one float4 column.  rpix: the row's index in `in`
+// (-1: beyond M), ryx: its pixel as (y << 16) | x.  gather(): the four channels from `ci` on of each row's neighbour at (dy, dx), zero
+// outside the image.
+template <int F4, int RPP>
+struct AStage {
+    int rpix[F4], ryx[F4];
+    __device__ __forceinline__ AStage(int first, int M, int HW, int W)
+    {
+#pragma unroll
+        for (int i = 0; i < F4; i++) {
+            const int m = first + RPP * i;
+            rpix[i] = -1; ryx[i] = 0;
+            if (m < M) {
+                const int p = m % HW, y = p / W;
+                rpix[i] = m; ryx[i] = (y << 16) | (p - y * W);
+            }
+        }
+    }
+    __device__ __forceinline__ void gather(f32x4 (&ra)[F4], const float* __restrict__ in, int H, int W, int Cin, int ci, int dy, int dx) const
+    {
+#pragma unroll
+        for (int i = 0; i < F4; i++) {
+            const int yy = (ryx[i] >> 16) + dy, xx = (ryx[i] & 0xffff) + dx;
+            const bool ok = rpix[i] >= 0 && yy >= 0 && yy < H && xx >= 0 && xx < W;
+            ra[i] = ok ? *reinterpret_cast<const f32x4*>(in + (size_t)(rpix[i] + dy * W + dx) * Cin + ci) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        }
+    }
+};
+
+// What follows the K loop (the C/D layout of the 32 x 32 tile does not depend on the operand type): bias and ReLU with the sign bits by
+// one ballot per accumulator register, or the ReLU bits of the layer below, or nothing; with WK == 4 the four waves' partial blocks go
+// through `s_part` (4096 floats of LDS every wave is done reading) and are summed in wave order.
 template <int WK, int MODE>
 __device__ __forceinline__ void conv_epilogue(const f32x16& acc0, const f32x16& acc1, float* s_part, int tid, int wave, int j, int half,
                                               int m0, int n0, int M, int mask_rows, int Cout, const float* __restrict__ bias,
@@ -465,6 +381,73 @@ __device__ __forceinline__ void conv_epilogue(const f32x16& acc0, const f32x16& 
     }
 }
 
+// WM waves along the rows, WK waves along K (WM * WK = 4).  DYN is a template parameter so that the static instantiation stays the
+// code it was.
+template <int WM, int WK, int MODE, bool DYN>
+__global__ void __launch_bounds__(WG)
+conv3x3_mfma_kernel(const ConvArgs a)
+{
+    static_assert(WM * WK == 4 && (WK == 1 || WM == 1), "four waves");
+    constexpr int BM = 32 * WM, A_F4 = BM * (KC / 4) / WG, B_F4 = BN * (KC / 4) / WG;
+    __shared__ __attribute__((aligned(16))) float s_A[BM * LD], s_B[BN * LD];
+    static_assert(BN * LD >= 4 * 32 * 32, "s_B doubles as the buffer of the four partial blocks");
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, half = lane >> 5;
+    const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
+    int H, W, M, mask_rows;
+    if (!conv_size<DYN>(a, m0, H, W, M, mask_rows)) return;
+    const int HW = H * W, Cin = a.Cin, Cout = a.Cout;
+    const int K9 = 9 * Cin, nchunks = K9 / KC;
+    const float* __restrict__ in = a.in;                                 // (locals: the lambdas below must not take the address of `a`)
+    const float* __restrict__ bias = a.bias;
+    float* __restrict__ out = a.out;
+    const uint32_t* __restrict__ mask_in = a.mask_in;
+    uint32_t* __restrict__ mask_out = a.mask_out;
+
+    // the rows and float4 columns this thread stages: rows r0 + 16 i, column c4
+    const int c4 = tid & 15, r0 = tid >> 4;
+    const AStage<A_F4, 16> stage(m0 + r0, M, HW, W);
+    const float* wbase = a.w + (size_t)(n0 + r0) * K9 + 4 * c4;
+    f32x4 ra[A_F4], rb[B_F4];
+    auto gload = [&](int kc) __attribute__((always_inline)) {
+        const int k0 = kc * KC, tap = k0 / Cin, ci0 = k0 - tap * Cin, dy = tap / 3 - 1, dx = tap % 3 - 1;
+        stage.gather(ra, in, H, W, Cin, ci0 + 4 * c4, dy, dx);
+#pragma unroll
+        for (int i = 0; i < B_F4; i++) rb[i] = *reinterpret_cast<const f32x4*>(wbase + (size_t)(16 * i) * K9 + k0);
+    };
+    auto sstore = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < A_F4; i++) *reinterpret_cast<f32x4*>(s_A + (r0 + 16 * i) * LD + 4 * c4) = ra[i];
+#pragma unroll
+        for (int i = 0; i < B_F4; i++) *reinterpret_cast<f32x4*>(s_B + (r0 + 16 * i) * LD + 4 * c4) = rb[i];
+    };
+
+    f32x16 acc0 = splat(0.0f), acc1 = splat(0.0f);
+    const float* a_row = s_A + ((WK == 1 ? 32 * wave : 0) + j) * LD + 4 * half;
+    const float* b_row = s_B + j * LD + 4 * half;
+    gload(0);
+    sstore();
+    __syncthreads();
+    for (int kc = 0; kc < nchunks; kc++) {
+        if (kc + 1 < nchunks) gload(kc + 1);                             // in flight during the MFMAs of this slice
+#pragma unroll
+        for (int step = (WK == 1 ? 0 : wave); step < KC / 8; step += WK) {
+            const f32x4 av = *reinterpret_cast<const f32x4*>(a_row + 8 * step);
+            const f32x4 b0 = *reinterpret_cast<const f32x4*>(b_row + 8 * step);
+            const f32x4 b1 = *reinterpret_cast<const f32x4*>(b_row + 32 * LD + 8 * step);
+            mfma4(acc0, av, b0);
+            mfma4(acc1, av, b1);
+        }
+        __syncthreads();
+        if (kc + 1 < nchunks) {
+            sstore();
+            __syncthreads();
+        }
+    }
+
+    conv_epilogue<WK, MODE>(acc0, acc1, s_B, tid, wave, j, half, m0, n0, M, mask_rows, Cout, bias, out, mask_in, mask_out);
+}
+
+// ---- the wide convolutions, bf16 operands ------------------------------------------------------------------------------------------
 // The same implicit GEMM with both operands rounded to bf16 (nearest even) and the sums in float32, on v_mfma_f32_32x32x16_bf16: sixteen
 // k per instruction at sixteen times the f32 tile's rate, so the kernel is bound by staging and is shaped for that.  The activations
 // stay float32 in memory and are rounded on their way into LDS; a.w is the bf16 packing (pack_weights_kernel<__bf16>: rounded once).
@@ -486,41 +469,21 @@ conv3x3_bf16_kernel(const ConvArgs a)
     static_assert(2 * SLICE * sizeof(__bf16) >= 4 * 32 * 32 * sizeof(float), "s_ab doubles as the buffer of the four partial blocks");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, half = lane >> 5;
     const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
-    int H = a.H, W = a.W, M = a.M, mask_rows = a.mask_rows;
-    if (DYN) {
-        actual_size(a.dyn, H, W);
-        mask_rows = H * W;
-        M = a.nimg * mask_rows;
-        if (m0 >= M) return;                                             // (the whole workgroup, before its first barrier)
-    }
+    int H, W, M, mask_rows;
+    if (!conv_size<DYN>(a, m0, H, W, M, mask_rows)) return;
     const int HW = H * W, Cin = a.Cin, Cout = a.Cout;
     const int K9 = 9 * Cin, nchunks = K9 / KCB;
     const float* __restrict__ in = a.in;
 
     // what this thread stages: of A the rows ar + A_RPP i at float4 column ac, of B the rows br + B_RPP i at 8-vector column bc
     const int ac = tid % A_CPR, ar = tid / A_CPR, bc = tid % B_CPR, br = tid / B_CPR;
-    int rpix[A_F4], ryx[A_F4];
-#pragma unroll
-    for (int i = 0; i < A_F4; i++) {
-        const int m = m0 + ar + A_RPP * i;
-        rpix[i] = -1; ryx[i] = 0;
-        if (m < M) {
-            const int p = m % HW, y = p / W;
-            rpix[i] = m; ryx[i] = (y << 16) | (p - y * W);
-        }
-    }
+    const AStage<A_F4, A_RPP> stage(m0 + ar, M, HW, W);
     const __bf16* wbase = reinterpret_cast<const __bf16*>(a.w) + (size_t)(n0 + br) * K9 + 8 * bc;
     f32x4 ra[A_F4];
     bf16x8 rb[B_V8];
     auto gload = [&](int kc) __attribute__((always_inline)) {
         const int k0 = kc * KCB, tap = k0 / Cin, ci0 = k0 - tap * Cin, dy = tap / 3 - 1, dx = tap % 3 - 1;
-#pragma unroll
-        for (int i = 0; i < A_F4; i++) {
-            const int yy = (ryx[i] >> 16) + dy, xx = (ryx[i] & 0xffff) + dx;
-            const bool ok = rpix[i] >= 0 && yy >= 0 && yy < H && xx >= 0 && xx < W;
-            ra[i] = ok ? *reinterpret_cast<const f32x4*>(in + (size_t)(rpix[i] + dy * W + dx) * Cin + ci0 + 4 * ac)
-                       : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        }
+        stage.gather(ra, in, H, W, Cin, ci0 + 4 * ac, dy, dx);
 #pragma unroll
         for (int i = 0; i < B_V8; i++) rb[i] = *reinterpret_cast<const bf16x8*>(wbase + (size_t)(B_RPP * i) * K9 + k0);
     };
@@ -591,19 +554,16 @@ conv3x3_bf16x3_kernel(const ConvArgs a)
     static_assert(SLICE * sizeof(__bf16) >= 4 * 32 * 32 * sizeof(float), "s_ab doubles as the buffer of the four partial blocks");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, half = lane >> 5;
     const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
-    int H = a.H, W = a.W, M = a.M, mask_rows = a.mask_rows;
-    if (DYN) {
-        actual_size(a.dyn, H, W);
-        mask_rows = H * W;
-        M = a.nimg * mask_rows;
-        if (m0 >= M) return;                                             // (the whole workgroup, before its first barrier)
-    }
+    int H, W, M, mask_rows;
+    if (!conv_size<DYN>(a, m0, H, W, M, mask_rows)) return;
     const int HW = H * W, Cin = a.Cin, Cout = a.Cout;
     const int K9 = 9 * Cin, nchunks = K9 / KCB;
     const float* __restrict__ in = a.in;
 
     // what this thread stages: of A the rows ar + A_RPP i at float4 column ac, of B (both planes) the rows br + B_RPP i at 8-vector column bc
     const int ac = tid % A_CPR, ar = tid / A_CPR, bc = tid % B_CPR, br = tid / B_CPR;
+    // AStage's table and, in gload, its gather, written out: through AStage the 128-row forward of this kernel alone was slower (512x352
+    // forward 1 648 -> 1 693 us; profiles/lpips_notes.md) where the other two kernels gained, and the cause was not found
     int rpix[A_F4], ryx[A_F4];
 #pragma unroll
     for (int i = 0; i < A_F4; i++) {
