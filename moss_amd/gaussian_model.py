@@ -1,7 +1,8 @@
-"""A minimal Gaussian parameter container exposing the property names the render binding reads from MOSS's
-``GaussianModel`` (scene/gaussian_model.py:134-173).  It is NOT a rebuild of that class (densification, LBS, ply I/O
-are out of scope): it exists so the step harness, the tests and bench.py can drive the
-rasterizer exactly the way ``gaussian_renderer.render`` does.
+"""The Gaussian model of the fast step: the property names the render binding reads from MOSS's ``GaussianModel``
+(scene/gaussian_model.py:134-173), the row surgery of its densification on a ``FlatAdamW`` (:362-454) and its PLY file
+(``save_ply`` / ``load_ply``, :271-360, through moss_amd/checkpoint.py).  It is NOT a rebuild of that class: the densification
+DECISION lives in moss_amd/densify.py, the LBS deformation in moss_amd/lbs.py, the model directory and the training state in
+moss_amd/checkpoint.py.
 """
 from __future__ import annotations
 
@@ -171,6 +172,29 @@ class GaussianSet(nn.Module):
         elif stats is not None:
             stats.reset(int(row_map.numel()))
         return row_map
+
+    # ---- MOSS's point_cloud.ply (scene/gaussian_model.py:271-360), without plyfile: moss_amd/checkpoint.py
+    def save_ply(self, path):
+        """``save_ply(path)`` (:286-303): the raw parameters as MOSS's binary little-endian PLY, byte for byte
+        (``checkpoint.write_ply``); ``save_scene`` writes the whole model directory."""
+        from .checkpoint import write_ply
+        write_ply(path, self)
+
+    def load_ply(self, path, optimizer=None):
+        """``load_ply(path)`` (:319-360; ``checkpoint.read_ply``: ascii or binary little-endian, properties by name): the parameters
+        take the file's values and row count, ``active_sh_degree = max_sh_degree`` (:360), ``spatially_ordered`` is cleared.  An
+        ``f_rest`` count that does not fit ``max_sh_degree``, a missing attribute or an unreadable file raises ``ValueError`` before
+        anything is changed.  ``optimizer``: the ``FlatAdamW`` / ``FlatAdamWRows`` that holds the parameters -- the rows are re-laid
+        through its row surgery (the Parameter objects survive, the bucket follows), both moments of the loaded rows are zero and it
+        is told the degree; a captured step must be captured again.  None: each Parameter's ``.data`` is replaced (only while no
+        optimizer has re-homed them)."""
+        from .checkpoint import assign_rows, gaussians_from_ply, read_ply
+        values = gaussians_from_ply(read_ply(path), self.max_sh_degree)
+        assign_rows(self, values, optimizer)
+        self.active_sh_degree = self.max_sh_degree
+        self.spatially_ordered = False
+        if optimizer is not None and hasattr(optimizer, "set_active_sh_degree"):
+            optimizer.set_active_sh_degree(self.active_sh_degree)
 
     def reset_opacity(self, optimizer):
         """``reset_opacity`` (scene/gaussian_model.py:314-317): opacity = min(opacity, 0.01) in logits, both moments of it zeroed."""

@@ -321,14 +321,7 @@ class FlatAdamW:
             self.seg_lr[seg] = lr
             if lr2 is not None:
                 self.seg_lr2[seg] = lr2
-        if self.fused is not None:
-            st = self.fused.struct
-            for slot in range(5):
-                seg = st.lr_segment[slot]
-                if seg >= 0:
-                    st.lr[slot] = self.seg_lr[seg]
-                    if slot == 1:
-                        st.lr_sh_rest = self.seg_lr2[seg] if int(self.seg_period[seg]) else self.seg_lr[seg]
+        self._fused_rates()
         if self.step_state is not None:
             # a small ring of pinned staging buffers: the copy is asynchronous and the device may be several steps behind the host, so a
             # buffer is rewritten only after the copy that last read it has completed (its event)
@@ -349,6 +342,18 @@ class FlatAdamW:
             slot[1] = torch.cuda.Event()
             slot[1].record(torch.cuda.current_stream(self.step_state.device))
 
+    def _fused_rates(self):
+        """The segments' rates in force, into the host struct of a step fused into the rasterizer's backward."""
+        if self.fused is None:
+            return
+        st = self.fused.struct
+        for slot in range(5):
+            seg = st.lr_segment[slot]
+            if seg >= 0:
+                st.lr[slot] = self.seg_lr[seg]
+                if slot == 1:
+                    st.lr_sh_rest = self.seg_lr2[seg] if int(self.seg_period[seg]) else self.seg_lr[seg]
+
     def step_count(self) -> int:
         """Steps taken so far (reads the device-side counter when there is one: it synchronises)."""
         return int(self.step_state[0].item()) if self.step_state is not None else self.t
@@ -362,6 +367,62 @@ class FlatAdamW:
         self.flat_params.copy_(snap[0]); self.exp_avg.copy_(snap[1]); self.exp_avg_sq.copy_(snap[2]); self.t = snap[3]
         if self.step_state is not None:
             self.step_state.copy_(snap[4])
+
+    # ---- the state as CPU tensors and plain values (moss_amd/checkpoint.py) ---------------------------------------------------------
+    def state_dict(self):
+        """Everything a later ``load_state_dict`` needs to go on bit for bit, as CPU tensors and plain Python values
+        (``torch.load(weights_only=True)`` reads it): ``flat_params``, ``exp_avg``, ``exp_avg_sq``; the whole ``step_state`` block (the
+        device-side step counter and the ``MOSS_ADAMW_LR_*`` words; None without ``capturable``); ``t``; ``seg_lr`` / ``seg_lr2``,
+        the rates in force (a schedule's included); ``sh_active_degree`` / ``sh_inactive_zero``; and ``shapes``, the bucket's
+        parameter shapes, which the load checks.  A sharded optimizer holds a part of the moments only: ``NotImplementedError``."""
+        if self.shard is not None:
+            raise NotImplementedError("FlatAdamW.state_dict on a sharded optimizer: every rank holds the moments of its shard alone")
+
+        def host(t):
+            return t.detach().to("cpu", copy=True)
+        return {"flat_params": host(self.flat_params), "exp_avg": host(self.exp_avg), "exp_avg_sq": host(self.exp_avg_sq),
+                "step_state": None if self.step_state is None else host(self.step_state), "t": int(self.t),
+                "seg_lr": [float(x) for x in self.seg_lr], "seg_lr2": [float(x) for x in self.seg_lr2],
+                "sh_active_degree": int(self.sh_active_degree), "sh_inactive_zero": bool(self.sh_inactive_zero),
+                "shapes": [[int(d) for d in p.shape] for p in self.bucket.params]}
+
+    def check_state_dict(self, sd, who="FlatAdamW.load_state_dict"):
+        """Raise ``ValueError`` naming the field of ``sd`` that does not fit this optimizer's CURRENT layout; changes nothing."""
+        if self.shard is not None:
+            raise NotImplementedError(f"{who} on a sharded optimizer")
+        shapes = [[int(d) for d in p.shape] for p in self.bucket.params]
+        if [list(s) for s in sd["shapes"]] != shapes:
+            diff = next((i for i, (a, b) in enumerate(zip(sd["shapes"], shapes)) if list(a) != b), min(len(shapes), len(sd["shapes"])))
+            raise ValueError(f"{who}: shapes: the state holds {len(sd['shapes'])} tensors and the bucket {len(shapes)}; the first that "
+                             f"differs is number {diff}")
+        for k, mine in (("flat_params", self.flat_params), ("exp_avg", self.exp_avg), ("exp_avg_sq", self.exp_avg_sq)):
+            if tuple(sd[k].shape) != tuple(mine.shape) or sd[k].dtype != torch.float32:
+                raise ValueError(f"{who}: {k}: {tuple(sd[k].shape)} {sd[k].dtype} for a buffer of {tuple(mine.shape)} float32")
+        if len(sd["seg_lr"]) != self.nseg or len(sd["seg_lr2"]) != self.nseg:
+            raise ValueError(f"{who}: seg_lr: {len(sd['seg_lr'])} learning-rate segments for an optimizer of {self.nseg}")
+        if (sd["step_state"] is None) != (self.step_state is None):
+            raise ValueError(f"{who}: step_state: one of the two optimizers is capturable and the other is not")
+        if self.step_state is not None and tuple(sd["step_state"].shape) != tuple(self.step_state.shape):
+            raise ValueError(f"{who}: step_state: a block of {tuple(sd['step_state'].shape)} words for one of {tuple(self.step_state.shape)}")
+
+    @torch.no_grad()
+    def load_state_dict(self, sd):
+        """Take a :meth:`state_dict` of an optimizer with the same layout (checked first: ``ValueError``, nothing changed): buffers and
+        the state block by ``copy_`` -- no address changes, so a fused step stays armed; it is told the rates and the SH degree --, the
+        host-side counter, rates and degree by value.  A step captured in a hipGraph bakes the rates and the degree into its launches:
+        capture it again."""
+        self.check_state_dict(sd)
+        self.flat_params.copy_(sd["flat_params"]); self.exp_avg.copy_(sd["exp_avg"]); self.exp_avg_sq.copy_(sd["exp_avg_sq"])
+        if self.step_state is not None:
+            self.step_state.copy_(sd["step_state"])
+        self.t = int(sd["t"])
+        for s in range(self.nseg):
+            self.seg_lr[s], self.seg_lr2[s] = float(sd["seg_lr"][s]), float(sd["seg_lr2"][s])
+        self._fused_rates()
+        self.sh_active_degree, self.sh_inactive_zero = int(sd["sh_active_degree"]), bool(sd["sh_inactive_zero"])
+        if self.fused is not None:
+            self.fused.struct.sh_active_degree = int(self.sh_active_degree)
+            self.fused.struct.sh_inactive_zero = int(self.sh_inactive_zero)
 
     def permute_rows(self, perm: torch.Tensor):
         """Re-index the Gaussians: row i of every parameter whose leading dimension is len(perm) -- and of its two moments -- becomes

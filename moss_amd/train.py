@@ -196,6 +196,7 @@ class MossStep:
         self.joint_F_sum = torch.zeros(23, 3, 3, dtype=torch.float32, device=dev)
         self.lbs_weights_sum = None                          # (made by the first step: the deformation says its shape)
         self.graphed = None
+        self._dropped_carried = 0
 
     # ---- the step ------------------------------------------------------------------------------------------------------------------
     def compute(self):
@@ -402,7 +403,8 @@ class MossStep:
 
     @property
     def dropped_frames(self) -> int:
-        return 0 if self.graphed is None else self.graphed.dropped_frames
+        # (``_dropped_carried``: what a loaded state had counted before this process, ``load_state_dict``)
+        return self._dropped_carried + (0 if self.graphed is None else self.graphed.dropped_frames)
 
     @property
     def recaptures(self) -> int:
@@ -434,6 +436,141 @@ class MossStep:
             if d:
                 o.set_learning_rates(d)
 
+    # ---- the training state: stop and continue (moss_amd/checkpoint.py) --------------------------------------------------------------
+    STATE_VERSION = 1
+    _OPTIMIZER_KEYS = ("gaussians", "xyz", "networks")
+
+    def _layout(self):
+        """What a state must agree on with the step that takes it: per optimizer (A), (B) the Gaussian groups' names and per-row
+        shapes, per network the names and shapes of the tensors optimizer (C) holds."""
+        pc = self.pc
+        names = {id(pc._xyz): "xyz", id(pc._features): "features", id(pc._opacity): "opacity", id(pc._scaling): "scaling",
+                 id(pc._rotation): "rotation"}
+        gaussians = [[names[id(p)], [int(d) for d in p.shape[1:]]] for o in (self.opt_gaussians, self.opt_xyz) for p in o.bucket.params]
+        networks = {}
+        for key, held in self.network_params.items():
+            named = {id(p): n for n, p in getattr(pc, key).named_parameters()}
+            networks[key] = [[named[id(p)], [int(d) for d in p.shape]] for p in held]
+        return gaussians, networks
+
+    def state_dict(self):
+        """All it takes to continue THIS run bit for bit in another process, as CPU tensors and plain Python values
+        (``torch.load(weights_only=True)`` reads it; ``checkpoint.save_checkpoint`` writes it): a format ``version``; ``rows`` (P),
+        ``max_sh_degree``, ``active_sh_degree`` and ``spatially_ordered`` (the hint changes the float32 summation order inside the
+        op); the Gaussian groups' names and per-row shapes and the network tensors' names and shapes; ``FlatAdamW.state_dict()`` of
+        the three optimizers (parameters, both moments, the step-state block with the counter and the rates, ``t``, the segments'
+        rates, the SH degree in force); the three ``DensifyStats`` accumulators (None without ``stats``); ``joint_F_sum``;
+        ``lbs_weights_sum`` (None before the first step); all of ``_terms``; ``dropped_frames``.  A captured step is ``check()``-ed
+        first, so that the frames dropped since the last check are counted.  Synchronises.
+
+        NOT kept: the binning capacity (re-learned by a probe on load); the captured graph (captured again on load); the caller's
+        frame inputs -- ``view.smpl_param``, ``gt_image``, ``bkgd_mask``, ``region`` -- and ``lpips_reference`` (loaded per frame by
+        the caller anyway); the densification noise generator, which the caller owns (``save_checkpoint(extra=)`` is the place for
+        ``generator.get_state()``); the four ``out_layer`` / ``gate_proj`` tensors that no step changes (``save_scene`` writes them)."""
+        if self.graphed is not None:
+            self.check()
+        pc = self.pc
+
+        def host(t):
+            return None if t is None else t.detach().to("cpu", copy=True)
+        gaussians, networks = self._layout()
+        st = self.stats
+        return {"version": self.STATE_VERSION, "unified_features": True, "rows": int(pc._xyz.shape[0]),
+                "max_sh_degree": int(pc.max_sh_degree), "active_sh_degree": int(pc.active_sh_degree),
+                "spatially_ordered": bool(pc.spatially_ordered), "gaussians": gaussians, "networks": networks,
+                "optimizers": {k: o.state_dict() for k, o in zip(self._OPTIMIZER_KEYS, self.optimizers)},
+                "stats": None if st is None else {"xyz_gradient_accum": host(st.xyz_gradient_accum), "denom": host(st.denom),
+                                                  "max_radii2D": host(st.max_radii2D)},
+                "joint_F_sum": host(self.joint_F_sum), "lbs_weights_sum": host(self.lbs_weights_sum), "terms": host(self._terms),
+                "dropped_frames": int(self.dropped_frames)}
+
+    def _check_state(self, sd):
+        who = "MossStep.load_state_dict"
+        pc = self.pc
+        if sd.get("version") != self.STATE_VERSION:
+            raise ValueError(f"{who}: version: the state is of format version {sd.get('version')!r}, this code reads {self.STATE_VERSION}")
+        if not sd.get("unified_features", False) or not getattr(pc, "unified_features", False):
+            raise ValueError(f"{who}: unified_features: the state and the step's model must both keep the SH coefficients as one tensor")
+        if int(sd["max_sh_degree"]) != int(pc.max_sh_degree):
+            raise ValueError(f"{who}: max_sh_degree: the state has {sd['max_sh_degree']}, the step's model {pc.max_sh_degree}")
+        gaussians, networks = self._layout()
+        if [[n, list(s)] for n, s in sd["gaussians"]] != gaussians:
+            raise ValueError(f"{who}: gaussians: the state's groups and per-row shapes are {sd['gaussians']}, the step's {gaussians}")
+        for key, mine in networks.items():
+            theirs = [[n, list(s)] for n, s in sd["networks"].get(key, [])]
+            if theirs != mine:
+                bad = next((a for a, b in zip(theirs, mine) if a != b), None) or f"{len(theirs)} tensors for {len(mine)}"
+                raise ValueError(f"{who}: networks: {key}: tensor names or shapes differ ({bad})")
+        if (sd["stats"] is None) != (self.stats is None):
+            raise ValueError(f"{who}: stats: the state " + ("has no" if sd["stats"] is None else "has") + " densification statistics and "
+                             "the step was built " + ("without" if self.stats is None else "with") + " stats=")
+        P = int(sd["rows"])
+        if P < 1:
+            raise ValueError(f"{who}: rows: {P}")
+        # (the Gaussian optimizers are checked at THEIR new layout by their own load, after the rows are re-laid: the groups and
+        # per-row shapes agree, so it is the one a step of P rows has; the networks' layout does not depend on P)
+        self.opt_networks.check_state_dict(sd["optimizers"]["networks"], who=f"{who}: optimizers: networks")
+        for key in ("gaussians", "xyz"):
+            shapes = sd["optimizers"][key]["shapes"]
+            if any(int(s[0]) != P for s in shapes):
+                raise ValueError(f"{who}: optimizers: {key}: shapes {shapes} in a state of {P} rows")
+        if sd["stats"] is not None and [tuple(sd["stats"][k].shape) for k in ("xyz_gradient_accum", "denom", "max_radii2D")] != [(P, 1), (P, 1), (P,)]:
+            raise ValueError(f"{who}: stats: the accumulators are not those of {P} rows")
+        if tuple(sd["joint_F_sum"].shape) != tuple(self.joint_F_sum.shape) or tuple(sd["terms"].shape) != tuple(self._terms.shape):
+            raise ValueError(f"{who}: joint_F_sum / terms: shapes {tuple(sd['joint_F_sum'].shape)}, {tuple(sd['terms'].shape)}")
+        w = sd["lbs_weights_sum"]
+        if w is not None and int(w.shape[-2]) != P:
+            raise ValueError(f"{who}: lbs_weights_sum: shape {tuple(w.shape)} in a state of {P} rows")
+
+    def load_state_dict(self, sd):
+        """Take a :meth:`state_dict` -- of this run or of one with ANOTHER number of Gaussians (a run saved at 45 695 rows, loaded into
+        a step built from the 6 890-vertex initialisation).  Refused with a ``ValueError`` that names the field, before anything is
+        modified: another format version, another ``max_sh_degree``, other Gaussian group names or per-row shapes, network tensor
+        names or shapes that differ, statistics on one side only, a non-unified model.
+
+        The rows are re-laid ONCE through ``rows`` (``FlatAdamWRows.relayout_rows``: the Parameter objects stay, the bucket and the
+        update inside the backward follow), then every buffer is overwritten.  The tail is a densification event's: statistics at the
+        new size, ``lbs_weights_sum`` re-created there, the binning capacity re-learned by the forward-only probe on the frame loaded
+        NOW, and a captured step captured again (always: the SH degree and the rates are launch arguments).  No training step is
+        taken: the three step counters afterwards are the saved ones.  What a state does not keep: :meth:`state_dict`."""
+        self._check_state(sd)
+        self._overwrite(sd)
+        dev = self.pc._xyz.device
+        self.context.relearn_capacity()
+        self._probe()
+        if dev.type == "cuda":
+            torch.cuda.synchronize(dev)
+        if self.graphed is not None:
+            self._recapture()                                # (outside no_grad: the capture records a backward)
+        # the count goes on from the saved one: frames the step dropped BEFORE the load belong to the state that was overwritten (the
+        # re-capture has reset the context's sticky counter, so the next check() cannot count them either)
+        self._dropped_carried = int(sd["dropped_frames"]) - (0 if self.graphed is None else self.graphed.dropped_frames)
+
+    @torch.no_grad()
+    def _overwrite(self, sd):
+        """``load_state_dict``'s middle: the rows re-laid once, then every buffer and host-side value taken from the (checked) state."""
+        from .checkpoint import resize_rows
+        pc, dev = self.pc, self.pc._xyz.device
+        P = int(sd["rows"])
+        resize_rows(self.rows, int(pc._xyz.shape[0]), P)
+        for key, o in zip(self._OPTIMIZER_KEYS, self.optimizers):
+            o.load_state_dict(sd["optimizers"][key])
+        pc.active_sh_degree, pc.spatially_ordered = int(sd["active_sh_degree"]), bool(sd["spatially_ordered"])
+        if self.stats is not None:
+            self.stats.reset(P)
+            for k, v in sd["stats"].items():
+                getattr(self.stats, k).copy_(v)
+        self.joint_F_sum.copy_(sd["joint_F_sum"])
+        self._terms.copy_(sd["terms"])
+        w = sd["lbs_weights_sum"]
+        if w is None:
+            self._reset_sums()                               # (zeros at the new size if the step has taken one; else still None)
+            self.joint_F_sum.copy_(sd["joint_F_sum"])
+        elif self.lbs_weights_sum is not None and tuple(self.lbs_weights_sum.shape) == tuple(w.shape):
+            self.lbs_weights_sum.copy_(w)
+        else:
+            self.lbs_weights_sum = w.to(dev)
+
 
 # ---- MOSS's loop around the step ----------------------------------------------------------------------------------------------------
 def frame_order(frames: int, iterations: int, seed: int = 0):
@@ -449,7 +586,8 @@ def frame_order(frames: int, iterations: int, seed: int = 0):
 
 
 def run_schedule(step, frames, iterations, densify_from=400, densify_until=2000, interval=100, sh_every=1000, opacity_reset_interval=4000,
-                 check_every=100, lr_schedule=None, on_event=None, load_frame=None, densify=None, seed=0):
+                 check_every=100, lr_schedule=None, on_event=None, load_frame=None, densify=None, seed=0, start_iteration=1,
+                 saving_iterations=(), save=None):
     """MOSS's training loop (``train_ZJU.py:82-95,171-186``) around a :class:`MossStep`; no mathematics of its own.  Per iteration
     ``i = 1 .. iterations``, in MOSS's order:
 
@@ -464,6 +602,16 @@ def run_schedule(step, frames, iterations, densify_from=400, densify_until=2000,
        whatever else that call takes) -- and ``step.densification_event(reset_opacity=True)`` when ``i % opacity_reset_interval == 0``
        (``:184-185``).
 
+    6. ``save(step, i)`` when ``i`` is one of ``saving_iterations`` -- after everything iteration ``i`` does, its event included
+       (``save``: e.g. ``lambda step, i: (checkpoint.save_scene(model_path, i, step.pc), checkpoint.save_checkpoint(step, path, i))``).
+       ORDER: MOSS calls ``scene.save`` between ``backward()`` and ``optimizer.step()`` (``train_ZJU.py:164-166,189``), so its file holds
+       the parameters BEFORE that iteration's update; here the update has been taken (and the event carried out).
+
+    ``start_iteration=k`` continues a run: iterations ``k .. iterations`` are run.  The frame order is still
+    ``frame_order(len(frames), iterations, seed)`` over the WHOLE run, entered at ``k``; degree raises, events and saves happen only at
+    iterations >= ``k``, and the phase bookkeeping starts in the phase ``k`` lies in (``load_checkpoint`` returns the iteration it was
+    saved after: continue at that plus one).  With the defaults -- 1, no saving iterations -- the loop is what it was.
+
     A captured step is ``check()``-ed every ``check_every`` iterations.  The device is synchronised where a phase ends (and by every
     event), nowhere else.  Returns ``seconds``; ``phases`` (``before`` / ``during`` / ``after`` densification: ``iterations``,
     ``seconds``, ``it_per_s``; the events' time is in ``during``); ``events`` (each report with its ``iteration``); ``sh_raises``;
@@ -472,7 +620,13 @@ def run_schedule(step, frames, iterations, densify_from=400, densify_until=2000,
     ids = list(range(frames)) if isinstance(frames, int) else list(frames)
     if load_frame is None and len(ids) > 1:
         raise ValueError("run_schedule: several frames need load_frame (the copies into the step's static inputs)")
-    due = [i for i in range(1, int(iterations) + 1) if densify_from < i < densify_until and i % interval == 0]
+    first = int(start_iteration)
+    if first < 1:
+        raise ValueError(f"run_schedule: start_iteration = {start_iteration} (iterations count from 1)")
+    saving = {int(i) for i in saving_iterations}
+    if saving and save is None:
+        raise ValueError("run_schedule: saving_iterations without save= (a callable (step, iteration))")
+    due = [i for i in range(first, int(iterations) + 1) if densify_from < i < densify_until and i % interval == 0]
     if due and on_event is None and densify is None:
         raise ValueError("run_schedule: densification events are due; give densify= (the arguments of step.densify_and_prune: max_grad, "
                          "min_opacity, extent) or on_event=")
@@ -487,8 +641,8 @@ def run_schedule(step, frames, iterations, densify_from=400, densify_until=2000,
             torch.cuda.synchronize(dev)
         return time.perf_counter()
     start = mark = sync()
-    phase = "before"
-    for i in range(1, int(iterations) + 1):
+    phase = "before" if first <= densify_from else "during" if first < densify_until else "after"
+    for i in range(first, int(iterations) + 1):
         now = "before" if i <= densify_from else "during" if i < densify_until else "after"
         if now != phase:
             t = sync()
@@ -513,6 +667,8 @@ def run_schedule(step, frames, iterations, densify_from=400, densify_until=2000,
             if i % opacity_reset_interval == 0:
                 step.densification_event(reset_opacity=True)
                 resets += 1
+        if i in saving:
+            save(step, i)
         if captured and i % check_every == 0:
             step.check()
     end = sync()
