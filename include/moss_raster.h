@@ -395,6 +395,31 @@ size_t moss_metrics_state_bytes(void);
 int moss_eval_metrics(const moss_eval_metrics_args* args, void* stream);
 
 /*
+ * Float32 frames to 8-bit pixels (additive in ABI 7; no existing entry point changes): what render_ZJU.py:83-84 does through
+ * torchvision.utils.save_image and train_ZJU.py:75 for the viewer.  Up to eight views of one size per call, planar float32 in,
+ * interleaved bytes out.  Per element, in float32 with each operation rounded on its own:
+ *     rounding 0 (nearest):   trunc(min(max(x * 255 + 0.5, 0), 255))      save_image: mul(255).add_(0.5).clamp_(0, 255).to(uint8)
+ *     rounding 1 (truncate):  trunc(min(max(x, 0), 1) * 255)              (clamp(img, 0, 1) * 255).byte()
+ * NaN gives 0 in both.
+ *   image[v]: (3,H,W) fp32; alpha[v]: (H,W) fp32, required iff channels_out == 4 (the fourth byte of every pixel; quantised by the same
+ *     rule, never filled); bound[v]: (H,W) bytes or NULL -- where != 1 the colour is `fill`, applied before the quantisation (the
+ *     selection of moss_eval_metrics); out[v]: (H,W,channels_out) bytes at ANY byte address, every byte written and none beside them.
+ *   image and alpha must be 4-byte aligned (float arrays); wide loads and packed stores are used per view where its pointers allow.
+ * One launch on `stream`, no workspace, no host synchronisation: capturable in a hipGraph. */
+typedef struct moss_frames_to_u8_args {
+    int32_t num_views;                       /* 1..8 */
+    int32_t H, W;
+    int32_t channels_out;                    /* 3 = RGB, 4 = RGBA (alpha from alpha[b]) */
+    int32_t rounding;                        /* 0 = nearest, 1 = truncate */
+    const float* image[8];
+    const float* alpha[8];
+    const unsigned char* bound[8];
+    float fill;
+    unsigned char* out[8];
+} moss_frames_to_u8_args;
+int moss_frames_to_u8(const moss_frames_to_u8_args* args, void* stream);
+
+/*
  * Per-Gaussian linear blend skinning of MOSS's coarse_deform_c2source (scene/gaussian_model.py:820-923, called from
  * gaussian_renderer/__init__.py:60,72), from the blend weights to the world-space transform, fused into one launch each way.
  * Per Gaussian i with v = vert_ids[i] (its nearest big-pose SMPL vertex):

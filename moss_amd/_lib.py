@@ -101,6 +101,8 @@ def _declare(lib):
     lib.moss_metrics_state_bytes.argtypes = []
     lib.moss_eval_metrics.restype = _i
     lib.moss_eval_metrics.argtypes = [_p, _p]
+    lib.moss_frames_to_u8.restype = _i
+    lib.moss_frames_to_u8.argtypes = [_p, _p]
     lib.moss_lbs_workspace_bytes.restype = C.c_size_t
     lib.moss_lbs_workspace_bytes.argtypes = [_i, _i]
     lib.moss_lbs_deform_forward.restype = _i
@@ -216,6 +218,13 @@ class EvalMetricsArgs(C.Structure):
                 ("gt", C.c_void_p * 8), ("bound", C.c_void_p * 8), ("out_image", C.c_void_p * 8), ("fill", C.c_float),
                 ("state", C.c_void_p), ("per_view", C.c_void_p), ("per_view_capacity", C.c_int32), ("workspace", C.c_void_p),
                 ("workspace_bytes", C.c_size_t)]
+
+
+class FramesToU8Args(C.Structure):
+    """``moss_frames_to_u8_args`` of include/moss_raster.h (``moss_frames_to_u8``: up to eight float32 frames to 8-bit pixels, one launch)."""
+    _fields_ = [("num_views", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("channels_out", C.c_int32), ("rounding", C.c_int32),
+                ("image", C.c_void_p * 8), ("alpha", C.c_void_p * 8), ("bound", C.c_void_p * 8), ("fill", C.c_float),
+                ("out", C.c_void_p * 8)]
 
 
 _LBS_INPUTS = [("P", C.c_int32), ("J", C.c_int32), ("V", C.c_int32), ("vert_ids", C.c_void_p), ("weights", C.c_void_p),

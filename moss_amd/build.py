@@ -40,6 +40,7 @@ SOURCES = {
     "loss.hip": [],
     "s3im.hip": [],
     "metrics.hip": [],
+    "present.hip": [],
     "lbs.hip": [],
     "smpl_frame.hip": [],
     "pose_head.hip": [],

@@ -5,6 +5,7 @@ buffers are contiguous and each crosses to the host whole, once per hundreds of 
                                     ``plyfile``; ``GaussianSet.save_ply / load_ply`` are these on a model
     save_scene / load_scene         MOSS's model directory (``Scene.save``, scene/__init__.py:86-123): what ``render_ZJU.py`` reads
     save_checkpoint / load_checkpoint   ``MossStep.state_dict()`` in a file: stop a run and continue it, bit for bit
+    save_pose_tables / load_pose_tables The per-pose LBS tables of an evaluation (``play.evaluate_split``): MOSS's ``smpl_rot`` folder
 
 Every file that holds tensors is written by ``torch.save`` with tensors on the CPU and plain containers only, so
 ``torch.load(..., weights_only=True)`` reads it.  Everything here imports and runs without a GPU.
@@ -19,7 +20,8 @@ import numpy as np
 import torch
 
 __all__ = ["write_ply", "read_ply", "ply_attributes", "ply_rows", "gaussians_from_ply", "resize_rows", "assign_rows", "save_scene",
-           "load_scene", "latest_iteration", "save_checkpoint", "load_checkpoint", "CHECKPOINT_FORMAT"]
+           "load_scene", "latest_iteration", "save_checkpoint", "load_checkpoint", "CHECKPOINT_FORMAT", "save_pose_tables", "load_pose_tables",
+           "POSE_TABLES_FORMAT"]
 
 CHECKPOINT_FORMAT = "moss_amd.checkpoint"
 
@@ -319,3 +321,81 @@ def load_checkpoint(step, path):
                          f"{payload.get('format') if isinstance(payload, dict) else type(payload).__name__!r})")
     step.load_state_dict(payload["step"])
     return int(payload["iteration"]), payload["extra"]
+
+
+# ---- the pose tables of an evaluation -------------------------------------------------------------------------------------------------
+POSE_TABLES_FORMAT = "moss_amd.pose_tables"
+
+
+def _pose_tables_dir(model_path, iteration):
+    return os.path.join(model_path, "smpl_rot", f"iteration_{int(iteration)}")
+
+
+def _checked_tables(tables_by_split):
+    """``{split: {pose_id: {"transforms" (1,P,3,3), "translation" (1,P,3)}}}`` with exactly these two tensors per pose (MOSS's layout,
+    ``train_ZJU.py:255-259``); raises ``ValueError`` naming the entry otherwise."""
+    out = {}
+    for split, poses in tables_by_split.items():
+        out[split] = {}
+        for pose_id, entry in poses.items():
+            T, t = entry["transforms"], entry["translation"]
+            if T.dim() != 4 or tuple(T.shape[::3]) != (1, 3) or T.shape[2] != 3 or tuple(t.shape) != (1, T.shape[1], 3):
+                raise ValueError(f"save_pose_tables: {split}[{pose_id!r}]: transforms {tuple(T.shape)} / translation {tuple(t.shape)} are "
+                                 "not (1,P,3,3) / (1,P,3)")
+            out[split][pose_id] = {"transforms": T.detach(), "translation": t.detach()}
+    return out
+
+
+def save_pose_tables(model_path, iteration, tables_by_split, moss_pickle=False):
+    """The per-pose LBS tables MOSS's ``training_report`` collects through ``render(..., return_smpl_rot=True)`` and ``render_ZJU.py``
+    renders from (``train_ZJU.py:242-259,283-286``, ``render_ZJU.py:42-58``).  ``tables_by_split``: ``{"train": {pose_id:
+    {"transforms" (1,P,3,3), "translation" (1,P,3)}}, "test": {...}}`` -- ``play.evaluate_split(...)["tables"]`` per split.
+
+    Writes ``smpl_rot/iteration_N/pose_tables.pth``: the same nesting with CPU tensors and plain containers, read by
+    ``torch.load(weights_only=True)`` (:func:`load_pose_tables`).  ``moss_pickle=True`` ALSO writes MOSS's own
+    ``smpl_rot/iteration_N/smpl_rot.pickle`` -- ``pickle.dump(tables, f, protocol=pickle.HIGHEST_PROTOCOL)`` with the tensors on the
+    device they are on: ``render_ZJU.py:77`` multiplies them with CUDA positions, so the file unpickles to what MOSS itself would have
+    written.  Returns the path(s) written, as a tuple ``(pth, pickle or None)``."""
+    tables = _checked_tables(tables_by_split)
+    folder = _pose_tables_dir(model_path, iteration)
+    pth = os.path.join(folder, "pose_tables.pth")
+    payload = {"format": POSE_TABLES_FORMAT, "iteration": int(iteration),
+               "tables": {split: {pid: {k: v.to("cpu", copy=True) for k, v in e.items()} for pid, e in poses.items()}
+                          for split, poses in tables.items()}}
+    _replace(pth, lambda f: torch.save(payload, f))
+    pkl = None
+    if moss_pickle:
+        import pickle
+        pkl = os.path.join(folder, "smpl_rot.pickle")
+        _replace(pkl, lambda f: pickle.dump(tables, f, protocol=pickle.HIGHEST_PROTOCOL))
+    return pth, pkl
+
+
+def load_pose_tables(model_path, iteration=-1, device=None, trust_pickle=False):
+    """Read what :func:`save_pose_tables` wrote: ``{split: {pose_id: {"transforms", "translation"}}}`` with the tensors on ``device``
+    (None: the CPU).  ``model_path``: the model directory (``iteration=-1``: the largest ``iteration_*`` under ``smpl_rot/``) or the
+    path of one file.  A ``.pickle`` -- MOSS's own file -- is refused unless ``trust_pickle=True``: unpickling runs whatever code the
+    file names, so it is only for files you wrote yourself; ``pose_tables.pth`` beside it holds the same tables and is read with
+    ``weights_only=True``."""
+    path = model_path
+    if os.path.isdir(model_path):
+        if int(iteration) == -1:
+            iteration = latest_iteration(os.path.join(model_path, "smpl_rot"))
+        folder = _pose_tables_dir(model_path, iteration)
+        path = os.path.join(folder, "pose_tables.pth")
+        if not os.path.exists(path) and os.path.exists(os.path.join(folder, "smpl_rot.pickle")):
+            path = os.path.join(folder, "smpl_rot.pickle")
+    if str(path).endswith((".pickle", ".pkl")):
+        if not trust_pickle:
+            raise ValueError(f"load_pose_tables: {path} is a pickle, and unpickling executes code the file chooses: it is not read unless "
+                             "trust_pickle=True says the file is your own (pose_tables.pth holds the same tables and is read safely)")
+        import pickle
+        with open(path, "rb") as f:
+            tables = pickle.load(f)
+    else:
+        payload = torch.load(path, map_location="cpu", weights_only=True)
+        if not isinstance(payload, dict) or payload.get("format") != POSE_TABLES_FORMAT:
+            raise ValueError(f"load_pose_tables: {path} is no {POSE_TABLES_FORMAT} file")
+        tables = payload["tables"]
+    dev = torch.device("cpu" if device is None else device)
+    return {split: {pid: {k: v.to(dev) for k, v in e.items()} for pid, e in poses.items()} for split, poses in tables.items()}
