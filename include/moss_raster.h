@@ -563,6 +563,94 @@ int moss_smpl_frame_backward(const moss_smpl_frame_backward_args* args, void* st
 size_t moss_smpl_frame_workspace_bytes(int P, int V, int J);
 
 /*
+ * The posed SMPL vertices of a frame in the world and their padded box (additive in ABI 7): the reference's numpy SMPL.__call__
+ * (smpl/smpl_numpy.py:46-98) followed by `xyz @ R^T + Th` and the min / max of scene/dataset_readers.py:428-436 (the frame, pad 0.1)
+ * and :331-339 (the big pose, pad 0.05), on the device.
+ *     v_shaped = v_template + shapedirs[..., :num_betas] beta                                                (smpl_numpy.py:52)
+ *     joints   = J_regressor v_shaped                                                                        (:53)
+ *     rot      = Rodrigues(poses)      the project's form: angle = |r + 1e-8|, R = I + sin K + (1 - cos) K K (:61; gaussian_model.py:945-963)
+ *     v_posed  = v_shaped + posedirs (rot[1:] - I)                        ONE pass over posedirs             (:68-71)
+ *     G_0 = [rot_0 | joints_0], G_j = G_parent[j] [rot_j | joints_j - joints_parent[j]], A_j = [G_j.R | G_j.t - G_j.R joints_j]   (:73-92)
+ *     T_v = sum_j weights[v, j] A_j,  world_v = R (T_v [v_posed, 1]) + Th                                    (:94-96; dataset_readers.py:429)
+ *     world_bound = fl32(min_v world_v - fl32(pad)), fl32(max_v world_v + fl32(pad))     over the float32 world_v written (:432-436)
+ *     joints_out[j] = G_j.t                  the posed joints SMPL.__call__ returns second (SMPL space: R and Th do not enter)   (:85)
+ * Shapes (fp32, contiguous): the body-model arrays as moss_smpl_frame_args names them, plus weights (V,J); poses (3J), shapes
+ * (num_betas <= shapedirs_stride), R (3,3), Th (3), pad (1) -- all DEVICE pointers, so that a captured graph serves a new pose after
+ * five small copies.  parents: by value, parents[j] in [0, j) for j >= 1; J = 1..MOSS_SMPL_FRAME_MAX_JOINTS, V >= 1.
+ * Outputs: world_vertex (V,3), world_bound (2,3), joints (J,3) or NULL.  workspace: moss_smpl_vertices_workspace_bytes(V, J) device
+ * bytes (v_posed in float64, the regressor shares, one min / max record per workgroup; garbage afterwards).
+ * Three launches on `stream`.  Every sum is formed in float64 in a fixed order and rounded to float32 once; the min / max are folded
+ * from per-workgroup records in workgroup order; no atomics: bitwise reproducible.  No host synchronisation, no allocation, no memset,
+ * every output element written: capturable.  Bad arguments return MOSS_ERR_INVALID_ARG with the field named in moss_last_error().
+ */
+typedef struct moss_smpl_vertices_args {
+    int32_t V, J;
+    int32_t num_betas, shapedirs_stride;
+    int32_t parents[MOSS_SMPL_FRAME_MAX_JOINTS];
+    const float* v_template;
+    const float* shapedirs;
+    const float* posedirs;                   /* may be NULL for J = 1 */
+    const float* J_regressor;
+    const float* weights;
+    const float* poses;
+    const float* shapes;                     /* may be NULL for num_betas = 0 */
+    const float* R;
+    const float* Th;
+    const float* pad;
+    float* world_vertex;
+    float* world_bound;
+    float* joints;                           /* (J,3) or NULL */
+    char* workspace; size_t workspace_bytes;
+} moss_smpl_vertices_args;
+int moss_smpl_vertices(const moss_smpl_vertices_args* args, void* stream);   /* smpl/smpl_numpy.py:46-98, scene/dataset_readers.py:331-339, :428-436 */
+/* device bytes of the call's workspace (host-side arithmetic, monotonic); 0 for V <= 0 or J outside 1..64 */
+size_t moss_smpl_vertices_workspace_bytes(int V, int J);
+
+/*
+ * The 2D bound masks of one world_bound seen by C >= 1 cameras, with their bounding rectangles (additive in ABI 7):
+ * get_bound_2d_mask of scene/dataset_readers.py:1034-1045 with get_bound_corners (:1008-1021) and project (:1023-1032), and
+ * cv2.boundingRect of the mask (train_ZJU.py:115), in one call for all cameras.
+ *   Corners: the eight corners in get_bound_corners' order (corner i takes max x for i & 4, max y for i & 2, max z for i & 1);
+ *     cam = c RT[:, :3]^T + RT[:, 3], uvw = K cam, xy = uvw[:2] / uvw[2], computed in FLOAT64 from the float32 inputs, every operation
+ *     rounded on its own ((c0 RT[r][0] + c1 RT[r][1]) + c2 RT[r][2]) + RT[r][3]; (K[r][0] cam0 + K[r][1] cam1) + K[r][2] cam2), then
+ *     rounded half-to-even as np.round does.
+ *   Flag: flags[c] bit 0 is set when any corner has uvw[2] <= 0 or a rounded coordinate exceeds 2^20 in magnitude (a NaN counts): the
+ *     reference divides through and fills garbage there.  For a flagged camera the mask is the WHOLE frame, rect = (0, 0, W, H, W H).
+ *     corners holds what was computed, clamped to +-2^20 (a NaN: -2^20).
+ *   Mask: pixel (x, y) is 1 when it belongs to at least one of the six faces [0,1,3,2], [4,5,7,6], [0,1,5,4], [2,3,7,6], [0,2,6,4],
+ *     [1,3,7,5] (:1039-1044).  A face has integer vertices q0..q3 in that cyclic order; all arithmetic is int64.  A pixel p belongs to
+ *     a face when
+ *       (a) closed quad: p is inside the face's bounding box and the four cross products (q_{k+1} - q_k) x (p - q_k) are all >= 0 or
+ *           all <= 0; or
+ *       (b) drawn edge: for some k, with (dx, dy) = q_{k+1} - q_k and m = max(|dx|, |dy|), p is inside the edge's bounding box and
+ *           |2 (dx (y - q_k.y) - dy (x - q_k.x))| <= m: the nearest pixel along the major axis, both at an exact tie (fillPoly draws
+ *           every polygon edge as an 8-connected line beside filling the interior).
+ *   Rect: (x, y, w, h) of the mask's non-zero pixels (moss_amd.loss.bounding_rect; 0 0 0 0 when empty) and the number of ones, laid
+ *     out as ViewRegion.rect is.
+ * Not verified against cv2.fillPoly: tie pixels of rule (b) and lines cv2 clips at the image border may differ
+ * by single pixels on the outline.
+ * Inputs (DEVICE pointers): world_bound (2,3), K (C,3,3), RT (C,3,4) float32.  Outputs: bound (C,H,W) uint8 of 0 / 1, rect (C,5) int32,
+ * corners (C,8,2) int32 (x, y), flags (C) int32.  C = 1..65535, H, W >= 1 with H W < 2^31.  workspace:
+ * moss_bound_mask_workspace_bytes(C, H, W) device bytes (one record per 64 x 8 pixel tile and camera; garbage afterwards).
+ * Two launches on `stream` whatever C is.  Integer arithmetic, no atomics, every output element written, no clearing launch:
+ * bitwise reproducible; capturable.  Bad arguments return MOSS_ERR_INVALID_ARG with the field named in moss_last_error().
+ */
+typedef struct moss_bound_mask_args {
+    int32_t C, H, W;
+    const float* world_bound;
+    const float* K;
+    const float* RT;
+    uint8_t* bound;
+    int32_t* rect;
+    int32_t* corners;
+    int32_t* flags;
+    char* workspace; size_t workspace_bytes;
+} moss_bound_mask_args;
+int moss_bound_mask(const moss_bound_mask_args* args, void* stream);   /* scene/dataset_readers.py:1008-1045, train_ZJU.py:115 */
+/* device bytes of the call's workspace (host-side arithmetic, monotonic); 0 for a size <= 0, C > 65535 or H W >= 2^31 */
+size_t moss_bound_mask_workspace_bytes(int C, int H, int W);
+
+/*
  * MOSS's S3IM term and its gradient (additive in ABI 7): s3im_loss = s3im_fun(img_pred, img_gt) (train_ZJU.py:123, weighted 0.3 at
  * :131; utils/loss_utils.py:17-38).  MOSS hands it two (1,C,h,w) crops, so every randperm(1) is [0] and the term is deterministic:
  *     s3im = 1 - ssim(x~, y~),   x~ = the crop with every pixel repeated `repeat` times along a row (width repeat * w)

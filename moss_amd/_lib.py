@@ -115,6 +115,14 @@ def _declare(lib):
     lib.moss_smpl_frame_forward.argtypes = [_p, _p]
     lib.moss_smpl_frame_backward.restype = _i
     lib.moss_smpl_frame_backward.argtypes = [_p, _p]
+    lib.moss_smpl_vertices_workspace_bytes.restype = C.c_size_t
+    lib.moss_smpl_vertices_workspace_bytes.argtypes = [_i, _i]
+    lib.moss_smpl_vertices.restype = _i
+    lib.moss_smpl_vertices.argtypes = [_p, _p]
+    lib.moss_bound_mask_workspace_bytes.restype = C.c_size_t
+    lib.moss_bound_mask_workspace_bytes.argtypes = [_i, _i, _i]
+    lib.moss_bound_mask.restype = _i
+    lib.moss_bound_mask.argtypes = [_p, _p]
     lib.moss_s3im_workspace_bytes.restype = C.c_size_t
     lib.moss_s3im_workspace_bytes.argtypes = [_i, _i, _i]
     lib.moss_s3im_loss.restype = _i
@@ -263,6 +271,23 @@ class SmplFrameBackwardArgs(C.Structure):
     _fields_ = [("P", C.c_int32), ("V", C.c_int32), ("J", C.c_int32), ("parents", C.c_int32 * 64), ("posedirs", C.c_void_p),
                 ("vert_ids", C.c_void_p), ("saved", C.c_void_p), ("g_A_obs", C.c_void_p), ("g_d", C.c_void_p),
                 ("g_correct_Rs", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+class SmplVerticesArgs(C.Structure):
+    """``moss_smpl_vertices_args`` of include/moss_raster.h (``moss_smpl_vertices``: a frame's posed SMPL vertices in the world and
+    their padded box)."""
+    _fields_ = [("V", C.c_int32), ("J", C.c_int32), ("num_betas", C.c_int32), ("shapedirs_stride", C.c_int32),
+                ("parents", C.c_int32 * 64), ("v_template", C.c_void_p), ("shapedirs", C.c_void_p), ("posedirs", C.c_void_p),
+                ("J_regressor", C.c_void_p), ("weights", C.c_void_p), ("poses", C.c_void_p), ("shapes", C.c_void_p), ("R", C.c_void_p),
+                ("Th", C.c_void_p), ("pad", C.c_void_p), ("world_vertex", C.c_void_p), ("world_bound", C.c_void_p),
+                ("joints", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+class BoundMaskArgs(C.Structure):
+    """``moss_bound_mask_args`` of include/moss_raster.h (``moss_bound_mask``: the bound masks and rectangles of one box for C cameras)."""
+    _fields_ = [("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("world_bound", C.c_void_p), ("K", C.c_void_p), ("RT", C.c_void_p),
+                ("bound", C.c_void_p), ("rect", C.c_void_p), ("corners", C.c_void_p), ("flags", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_size_t)]
 
 
 POSE_HEAD_SAVED_FLOATS = 896                             # MOSS_POSE_HEAD_SAVED_FLOATS

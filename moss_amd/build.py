@@ -43,6 +43,7 @@ SOURCES = {
     "present.hip": [],
     "lbs.hip": [],
     "smpl_frame.hip": [],
+    "frame_bounds.hip": [],
     "pose_head.hip": [],
     "lbs_weight_net.hip": [],
     "lpips.hip": [],

@@ -20,6 +20,7 @@
 // Every sum is formed in float64 in a fixed order, nothing is atomic, every output element is written: bitwise reproducible.
 // Nothing is allocated, nothing synchronises, nothing is cleared with a memset.
 #include "common.h"
+#include "smpl_math.h"
 #include "wave.h"
 
 namespace moss {
@@ -50,19 +51,6 @@ struct SfIn {
     const float* cR;
     const int64_t* ids;
 };
-
-// the reference's Rodrigues (gaussian_model.py:945-963): angle = |r + 1e-8|, n = r / angle, R = I + sin K + (1 - cos) K K
-__device__ __forceinline__ void sf_rodrigues(const float* r, float* R)
-{
-    const float x = r[0], y = r[1], z = r[2];
-    const float ex = x + 1e-8f, ey = y + 1e-8f, ez = z + 1e-8f;
-    const float angle = sqrtf(ex * ex + ey * ey + ez * ez);
-    const float nx = x / angle, ny = y / angle, nz = z / angle;
-    const float s = sinf(angle), c = 1.0f - cosf(angle);
-    R[0] = 1.0f - c * (ny * ny + nz * nz); R[1] = c * (nx * ny) - s * nz;          R[2] = c * (nx * nz) + s * ny;
-    R[3] = c * (nx * ny) + s * nz;          R[4] = 1.0f - c * (nx * nx + nz * nz); R[5] = c * (ny * nz) - s * nx;
-    R[6] = c * (nx * nz) - s * ny;          R[7] = c * (ny * nz) + s * nx;          R[8] = 1.0f - c * (nx * nx + ny * ny);
-}
 
 // s_big: the big pose's rotations; s_raw: the frame's; s_rot: the frame's with rot[1:] = raw[1:] correct_Rs (J x 9 floats each)
 __device__ __forceinline__ void sf_stage_rotations(const SfIn& a, float* s_big, float* s_raw, float* s_rot)

@@ -187,11 +187,41 @@ class ViewRegion:
         inside = m[y:y + h, x:x + w]                          # (pixels of the mask outside a caller's rectangle count for nothing)
         self.rect = torch.tensor([x, y, w, h, int(inside.sum())], dtype=torch.int32, device=m.device)
 
+    @classmethod
+    def from_device(cls, bound, rect):
+        """A region over device buffers that something else fills (``moss_amd.bounds``: C ABI ``moss_bound_mask``): ``bound`` (H,W) uint8
+        of 0 / 1 and ``rect`` 5 int32 are wrapped as they are -- no copy, no host read -- so a captured consumer sees what the next launch
+        writes there.  ``xywh`` is None until :meth:`read`."""
+        if bound.dtype != torch.uint8 or bound.dim() != 2 or not bound.is_contiguous():
+            raise ValueError(f"ViewRegion.from_device: bound must be a contiguous (H,W) uint8 tensor, got {bound.dtype} {tuple(bound.shape)}")
+        if rect.dtype != torch.int32 or tuple(rect.shape) != (5,) or not rect.is_contiguous() or rect.device != bound.device:
+            raise ValueError(f"ViewRegion.from_device: rect must be 5 contiguous int32 on {bound.device}, got {rect.dtype} "
+                             f"{tuple(rect.shape)} on {rect.device}")
+        self = cls.__new__(cls)
+        self.bound, self.rect, self.xywh = bound, rect, None
+        return self
+
+    def read(self, rect_host=None):
+        """Set ``xywh`` from ``rect`` as it is NOW on the device: one host read (it synchronises), or none with ``rect_host``, the
+        five values somebody has read already.  Returns ``self``."""
+        x, y, w, h = (int(v) for v in (self.rect.tolist() if rect_host is None else rect_host)[:4])
+        self.xywh = (x, y, w, h)
+        return self
+
     def copy_(self, other):
         self.bound.copy_(other.bound)
         self.rect.copy_(other.rect)
         self.xywh = other.xywh
         return self
+
+
+def region_xywh(region, who):
+    """``region.xywh`` for a consumer that needs the rectangle on the host; a region made by ``ViewRegion.from_device`` has none until
+    ``region.read()``."""
+    if region.xywh is None:
+        raise RuntimeError(f"{who}: the region's rectangle has not been read on the host (it wraps device buffers: "
+                           "ViewRegion.from_device); call region.read() first -- one host read")
+    return region.xywh
 
 
 def training_loss_moss_fused(image, alpha, gt_image, bkgd_mask, region, lambda_dssim=0.2, lambda_mask=0.5, terms_out=None):

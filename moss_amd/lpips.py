@@ -35,6 +35,8 @@ import itertools
 
 import torch
 
+from .loss import region_xywh
+
 __all__ = ["LpipsVGG", "LpipsReference", "lpips_vgg_fused", "lpips_vgg_roi_fused", "lpips_vgg_reference", "lpips_vgg_roi_reference",
            "reference_bytes", "reference_cache", "crop_capacity", "lpips_vgg_torch", "synthetic_weights", "weights_sha256",
            "PRECISIONS", "ALL_PRECISIONS", "CONV_SHAPES", "TAP_CHANNELS", "TAP_AFTER_CONV", "POOL_AFTER_CONV", "SHIFT", "SCALE", "MIN_SIZE"]
@@ -579,7 +581,7 @@ def crop_capacity(regions):
     every one of them.  Host arithmetic on ``region.xywh``; compute it once, when the dataset is loaded."""
     cap_h = cap_w = 0
     for r in regions:
-        _, _, w, h = r.xywh
+        _, _, w, h = region_xywh(r, "crop_capacity")
         cap_h, cap_w = max(cap_h, int(h)), max(cap_w, int(w))
     if cap_h == 0:
         raise ValueError("crop_capacity: no regions")
@@ -603,14 +605,14 @@ def _roi_sizes(what, net, image, gt_image, region, capacity):
     cap = None
     if capacity is not None:                                 # (host arithmetic on the region alone, before anything touches a device)
         cap = resolve_capacity(what, capacity, *region.bound.shape)
-        _, _, w, h = region.xywh
+        _, _, w, h = region_xywh(region, what)
         if h > cap[0] or w > cap[1]:
             raise ValueError(f"{what}: the region's crop {h}x{w} exceeds the capacity {cap[0]}x{cap[1]}")
     _check_images(what, net, image, gt_image)
     H, W = image.shape[-2:]
     if tuple(region.bound.shape) != (H, W) or region.rect.device != image.device:
         raise RuntimeError(f"{what}: the view's region does not belong to this image")
-    _, _, w, h = region.xywh
+    _, _, w, h = region_xywh(region, what)
     if min(h, w) < MIN_SIZE or h > H or w > W:
         raise ValueError(f"{what}: the crop must be at least {MIN_SIZE}x{MIN_SIZE} and fit the frame, got {h}x{w}")
     return cap, (int(h), int(w))

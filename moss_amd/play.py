@@ -240,6 +240,12 @@ class MossPlayer:
     ``view.big_pose_world_vertex`` (as in ``MossStep``; the model is not touched).  ``lbs_weights_precision``: ``"f32"`` or
     ``"bf16x3"``, handed to ``cross_attention_lbs_fused``.  ``max_render_graphs``: the size of the LRU; an evicted graph frees its pool.
 
+    ``bounds``: a list of cameras (MOSS ``Camera`` objects with ``K``, ``R``, ``T``, or ``(K, RT)`` pairs; ``True``: ``view`` alone), all
+    of ``view``'s frame size.  The player then owns a ``moss_amd.bounds.FrameBounds`` over its static ``smpl_param`` whose five launches
+    are part of the pose half: every ``pose()`` also writes the bound masks and rectangles of that pose's RAW ``poses`` for these
+    cameras (``bounds_pad``: the box's padding, MOSS's 0.1 m), ``frame()`` returns ``"region"`` beside the render, :meth:`region_of`
+    gives any camera's, and ``evaluate_split(..., regions="pose")`` uses them.  Default: no bounds, and nothing changes.
+
     Before :meth:`capture` everything runs eagerly, with the same results.  After it the pose is one replay and a render is one
     replay; a camera with intrinsics not seen before is captured on first use.  After the warm-up ``frame()`` reads nothing on the
     host.  Call :meth:`check` now and then (it synchronises) and :meth:`refresh` after the model's row count, SH degree or parameter
@@ -249,7 +255,8 @@ class MossPlayer:
     Counters: ``captures`` (graphs captured: the pose graph and every render graph, evicted ones included), ``recaptures`` (by
     ``check()``), ``poses`` (runs of the pose pipeline), ``pose_replays`` (those that were replays), ``dropped_frames``."""
 
-    def __init__(self, pc, view, bg, template_index=False, lbs_weights_precision="f32", max_render_graphs=32):
+    def __init__(self, pc, view, bg, template_index=False, lbs_weights_precision="f32", max_render_graphs=32, bounds=False,
+                 bounds_pad=0.1):
         from .lbs_weights import PRECISIONS
         if not getattr(pc, "unified_features", False):
             raise ValueError("MossPlayer needs GaussianSet(unified_features=True)")
@@ -282,10 +289,19 @@ class MossPlayer:
             self._camera = {k: torch.empty_like(getattr(view, k)) for k in ("world_view_transform", "full_proj_transform", "camera_center")}
             for k, t in self._camera.items():
                 t.copy_(getattr(view, k))
+            self.bounds, self._bounds_index = None, {}
+            if bounds:
+                from .bounds import FrameBounds, camera_KRT
+                cameras = [view] if bounds is True else list(bounds)
+                pairs = [c if isinstance(c, (tuple, list)) else camera_KRT(c) for c in cameras]
+                self.bounds = FrameBounds(pc.SMPL_NEUTRAL, pairs, int(view.image_height), int(view.image_width), pad=bounds_pad,
+                                          smpl_param=self.smpl_param)
+                self._bounds_index = {self._camera_key(pair): i for i, pair in reversed(list(enumerate(pairs)))}
         self._intrinsics = self._intrinsics_of(view)
         self.captures = self.poses = self.pose_replays = 0
         self._dropped = self._recaptured = 0
         self._captured = False
+        self._last_camera = None
         self._warmup = 2
         self._renders = collections.OrderedDict()                # key -> SimpleNamespace(camera, context, pipe, graphed)
         self._pose_graph = None
@@ -354,6 +370,8 @@ class MossPlayer:
             t["lbs_weights"].copy_(bweights)
             if Rs is not None:
                 t["Rs"].copy_(Rs)
+            if self.bounds is not None:
+                self.bounds.update()                             # (the region of the RAW poses, as the reference's: not of Rs)
         return None
 
     def pose(self, smpl_param=None):
@@ -442,6 +460,7 @@ class MossPlayer:
                 self._tables["translation"].copy_(translation.reshape(self._tables["translation"].shape))
                 self._posed = True
             if camera is not None:
+                self._last_camera = camera
                 for k, t in self._camera.items():
                     src = getattr(camera, k)
                     if src is not t:
@@ -459,9 +478,38 @@ class MossPlayer:
         return e.graphed()
 
     def frame(self, camera=None, smpl_param=None):
-        """``pose(smpl_param)`` then ``render(camera)``; returns the render's dict."""
+        """``pose(smpl_param)`` then ``render(camera)``; returns the render's dict -- with ``bounds``, a copy of it that also holds
+        ``"region"``: :meth:`region_of` the camera."""
         self.pose(smpl_param)
-        return self.render(camera)
+        out = self.render(camera)
+        if self.bounds is None:
+            return out
+        return dict(out, region=self.region_of(camera))
+
+    # ---- the bound masks ---------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _camera_key(pair):
+        K, RT = pair
+        return (torch.as_tensor(K, dtype=torch.float32).cpu().numpy().tobytes(), torch.as_tensor(RT, dtype=torch.float32).cpu().numpy().tobytes())
+
+    def bounds_index(self, camera=None):
+        """Which of the cameras given as ``bounds=`` ``camera`` is (None: the last one rendered): matched by the values of its ``K``,
+        ``R`` and ``T`` -- host arithmetic when those are host arrays, as a MOSS ``Camera``'s are."""
+        if self.bounds is None:
+            raise RuntimeError("MossPlayer: built without bounds= (MossPlayer(..., bounds=True) or bounds=[cameras])")
+        if camera is None:
+            camera = self._last_camera if self._last_camera is not None else self.view
+        from .bounds import camera_KRT
+        i = self._bounds_index.get(self._camera_key(camera if isinstance(camera, (tuple, list)) else camera_KRT(camera)))
+        if i is None:
+            raise ValueError("MossPlayer: this camera is not among the cameras the player's bounds were built for")
+        return i
+
+    def region_of(self, camera=None):
+        """The ``ViewRegion`` of the last pose seen by ``camera``: device buffers of the player's ``FrameBounds``, rewritten by the next
+        ``pose()``; ``xywh`` is None until ``read()``."""
+        i = self.bounds_index(camera)                            # (raises for a player without bounds)
+        return self.bounds.regions[i]
 
     # ---- capture, check ---------------------------------------------------------------------------------------------------------------
     def capture(self, warmup=2):
@@ -512,7 +560,8 @@ def evaluate_split(player, views, gts, regions, lpips=None, lpips_references=Non
     """MOSS's ``training_report`` body for one split (``train_ZJU.py:242-264``) and ``render_ZJU.py``'s ``render_set`` on a
     :class:`MossPlayer`.  ``views``: cameras with ``smpl_param``; those that carry a ``pose_id`` are grouped -- each pose is posed ONCE
     (its tables are kept on the device and copied back in when a pose returns later in the order) -- views without one are posed per
-    view.  Per view, in the given order, exactly what ``metrics.evaluate_views`` runs: ``QualityReport.add(image, gt, region,
+    view.  ``regions``: one ``ViewRegion`` (or None) per view, or ``"pose"``: every view's region comes from the player's bounds
+    (``MossPlayer(..., bounds=cameras)``; a pose's masks are kept on the device like its tables).  Per view, in the given order, exactly what ``metrics.evaluate_views`` runs: ``QualityReport.add(image, gt, region,
     out_image)`` and, with ``lpips`` (a float32 ``LpipsVGG``; others are refused as there), ``lpips_vgg_fused`` on ``out_image``
     against the clamped ground truth or its ``LpipsReference``, summed in float64 on the device.  One host read at the end; when
     ``check()`` finds a dropped view the whole split is run again, at most 3 times, then ``RuntimeError``.
@@ -540,7 +589,14 @@ def evaluate_split(player, views, gts, regions, lpips=None, lpips_references=Non
                                  f"{getattr(r, 'precision', None)!r}")
     views, gts = list(views), list(gts)
     n = len(views)
-    regions = list(regions) if regions is not None else [None] * n
+    from_pose = isinstance(regions, str)
+    if from_pose:
+        if regions != "pose":
+            raise ValueError(f"{who}: regions must be a list, None or 'pose', got {regions!r}")
+        index = [player.bounds_index(v) for v in views]          # (raises for a player without bounds or a camera it does not know)
+        regions = [None] * n
+    else:
+        regions = list(regions) if regions is not None else [None] * n
     if len(gts) != n or len(regions) != n or n == 0:
         raise ValueError(f"{who}: one ground truth and one region (or None) per view")
     if lpips_references is not None and len(lpips_references) != n:
@@ -558,14 +614,22 @@ def evaluate_split(player, views, gts, regions, lpips=None, lpips_references=Non
     keys = [getattr(v, "pose_id", None) for v in views]
     from .diff_gaussian_rasterization._C import CapacityOverflow
 
+    def region_at(i, key, masks):
+        """regions='pose': view i's region over the clones of its pose's masks (a pose's masks are kept like its tables)."""
+        from .loss import ViewRegion
+        bound, rect = masks[("view", i) if key is None else key]
+        return ViewRegion.from_device(bound[index[i]], rect[index[i]])
+
     def one_pass():
-        tables, loaded = {}, object()
+        tables, loaded, masks = {}, object(), {}
         with torch.no_grad():
             for i, view in enumerate(views):
                 key = keys[i]
                 if key is None or key not in tables:
                     t = player.pose(view.smpl_param)
                     loaded = key if key is not None else object()
+                    if from_pose:
+                        masks[("view", i) if key is None else key] = (player.bounds.bound.clone(), player.bounds.rect.clone())
                     if key is not None or keep_tables:
                         tables[("view", i) if key is None else key] = {"transforms": t["transforms"][None].clone(),
                                                                        "translation": t["translation"][None].clone()}
@@ -575,7 +639,7 @@ def evaluate_split(player, views, gts, regions, lpips=None, lpips_references=Non
                 else:                                            # a pose that was posed earlier in the order: its tables come back
                     image = player.render(view, tables[key]["transforms"], tables[key]["translation"])["render"]
                     loaded = key
-                report.add(image, gts[i], regions[i], out_image)
+                report.add(image, gts[i], region_at(i, key, masks) if from_pose else regions[i], out_image)
                 if lpips is not None:
                     truth = torch.clamp(gts[i], 0.0, 1.0) if lpips_references is None else lpips_references[i]
                     report.extra += lpips_vgg_fused(lpips, out_image, truth).mean().double()

@@ -261,6 +261,11 @@ class MossStep:
         if self.stats is not None:
             self.stats.xyz_gradient_accum.copy_(s[6]); self.stats.denom.copy_(s[7]); self.stats.max_radii2D.copy_(s[8])
 
+    def _crop_of_region(self):
+        from .loss import region_xywh
+        _, _, w, h = region_xywh(self.region, "MossStep")
+        return int(h), int(w)
+
     def capture(self, warmup=3):
         """Capture ``compute`` in a hipGraph (``GraphedStep(self.compute, context=...)``).  The ``warmup`` eager runs a capture needs --
         the first of a fresh context is synchronous and sizes the binning capacity for the frame loaded NOW -- are training steps;
@@ -268,7 +273,7 @@ class MossStep:
         model where it found it.  Returns ``self``."""
         from .graphs import GraphedStep
         state = self._state()
-        self._captured_crop = (int(self.region.xywh[3]), int(self.region.xywh[2]))
+        self._captured_crop = self._crop_of_region()
         self.graphed = GraphedStep(self.compute, warmup=warmup, device=self.pc._xyz.device, context=self.context)
         self._restore(state)
         return self
@@ -282,7 +287,7 @@ class MossStep:
             render(self.view, self.pc, self.pipe, self.bg)
 
     def _recapture(self):
-        self._captured_crop = (int(self.region.xywh[3]), int(self.region.xywh[2]))
+        self._captured_crop = self._crop_of_region()
         self.graphed.recapture()                             # (no warm-up run: no training step is taken, the model stays where it is)
 
     def _reset_sums(self):
@@ -306,7 +311,7 @@ class MossStep:
                                    after_surgery=(lambda _: self._reset_sums()) if moves else None, **event)
         tail.pop("per_gaussian", None)
         if tail["recaptured"]:
-            self._captured_crop = (int(self.region.xywh[3]), int(self.region.xywh[2]))
+            self._captured_crop = self._crop_of_region()
         report = dict(tail, **(decision or {}))
         report["relayouts"] = self.rows.relayouts - relayouts0
         report["host_reads"] = densify.host_reads() - reads0
@@ -386,7 +391,7 @@ class MossStep:
         ``lpips_reference``, a reference loaded now whose crop is not the region's (its rows were read at the region's size)."""
         if self.graphed is None:
             raise RuntimeError("MossStep.check(): nothing is captured")
-        h, w = int(self.region.xywh[3]), int(self.region.xywh[2])
+        h, w = self._crop_of_region()
         if self.lpips_reference is not None and self.lpips_reference.crop != (h, w):
             raise RuntimeError(f"MossStep.check(): lpips_reference holds a crop of {self.lpips_reference.crop} and the region's is "
                                f"{h}x{w}: the LPIPS term of the last replay compared the render with another view's ground truth "
