@@ -1596,9 +1596,13 @@ def test_means_posed_inside_the_op_equal_the_torch_posing(gpu, hip_lib):
       * every integer stage (radii, sorted keys, ranges) is BIT-EXACT against the CPU oracle run on means posed with the kernel's
         expression (rows of T times x summed left to right, then t: float32, one rounding per operation);
       * the gradients of x, T and t equal those autograd sends back through the torch posing."""
+    means_posed_inside_the_op_equal_the_torch_posing(scenes.config1(P=500, W=112, H=96), gpu)
+
+
+def means_posed_inside_the_op_equal_the_torch_posing(s, gpu):
+    """The body of the test above for a scene `s` (also called by tests/test_gpu_cameras.py under a general camera)."""
     import moss_amd.diff_gaussian_rasterization as dgr
     from moss_amd.diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer, _C
-    s = scenes.config1(P=500, W=112, H=96)
     c = s.camera
     g = torch.Generator().manual_seed(21)
     T = (torch.eye(3) + 0.1 * torch.randn(s.P, 3, 3, generator=g)).float()
