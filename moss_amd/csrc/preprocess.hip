@@ -1301,7 +1301,9 @@ preprocess_backward_kernel(int P, int D, int M, float tan_fovx, float tan_fovy, 
     PSTAMP(2);
     // the blend kernel's records carry the geometry sums without their constant factors (blend.hip, the backward trip):
     // d pixel / d ndc = W/2, H/2 (backward.cu:472-473, 574-575) and the -1/2 of the exponent (backward.cu:578-580)
-    gmx *= mean2d_sx; gmy *= mean2d_sy; gca *= -0.5f; gcb *= -0.5f; gcc *= -0.5f;
+    // (+ 0.0f: the factors are negative, and a Gaussian nothing contributed to -- culled, or in no pixel's list -- must get the +0 the
+    //  reference's zero-filled dL_dmean2D holds, not 0 * -W/2 = -0; with the multiply it is one fma, and x + 0 = x for every other x)
+    gmx = gmx * mean2d_sx + 0.0f; gmy = gmy * mean2d_sy + 0.0f; gca *= -0.5f; gcb *= -0.5f; gcc *= -0.5f;
     // (the step count, its bias corrections and the learning rates: chains of dependent SCALAR loads, requested HERE -- behind the
     // gather, in front of the arithmetic -- and used after it.  At the top of the kernel they delayed every block's first vector load
     // by three to four scalar round trips (2.3 us of the kernel, measured); between the first requests and the first wait their

@@ -2,6 +2,7 @@
 reference's own terms (GeometryState / BinningState / ImageState fields), so every stage can be compared."""
 from __future__ import annotations
 
+import contextlib
 from types import SimpleNamespace
 
 import numpy as np
@@ -306,3 +307,103 @@ def single_rule_ratio(got, ref64, mass, spread):
     r = np.zeros_like(err); r[pos] = err[pos] / den[pos]
     k = int(np.argmax(r))
     return float(r.reshape(-1)[k]), k
+
+
+# ---- poisoned allocator memory ---------------------------------------------------------------------------------------------------
+# The ops take their outputs and scratch from torch.empty on the promise that the kernels write every element before anything reads
+# it.  Early in a process the caching allocator hands out fresh pages from the driver -- zeros, the one content that hides a missing
+# write.  `poisoned_allocator` makes every block the allocator can hand out hold a chosen byte instead.
+POISON_FILLS = (0x00, 0xFF, 0x3C)      # benign | float NaN, int -1, bool true | float ~0.0115, a large positive int (passes x > 0 guards)
+POISON_CANARIES = (512, 300 << 10, 3 << 20, 40 << 20)
+
+
+class Poison:
+    """What `poisoned_allocator` yields: the seeded address ranges and the allocator's segment count after seeding."""
+
+    def __init__(self, device, byte, ranges, segments):
+        self.device, self.byte, self.segments = device, byte, segments
+        self.ranges = []                  # (neighbours merged: freed blocks coalesce, and a later allocation may straddle two of them)
+        for lo, hi in sorted(ranges):
+            if self.ranges and self.ranges[-1][1] == lo:
+                self.ranges[-1] = (self.ranges[-1][0], hi)
+            else:
+                self.ranges.append((lo, hi))
+
+    def owns(self, t):
+        lo = t.data_ptr(); hi = lo + t.numel() * t.element_size()
+        return any(a <= lo and hi <= b for a, b in self.ranges)
+
+    def assert_owns(self, *tensors):
+        """Every given tensor (None and empty ones excepted) was allocated out of the poisoned blocks."""
+        for i, t in enumerate(tensors):
+            if t is not None and t.numel():
+                assert t.is_cuda and self.owns(t), f"tensor {i} ({tuple(t.shape)}, {t.dtype}) does not lie in poisoned memory"
+
+
+def _free_blocks(device):
+    """(size, is_small_pool) of every cached free block of the default pool on the default stream of `device`."""
+    out = []
+    for seg in torch.cuda.memory_snapshot():
+        if seg["device"] != device.index or seg.get("stream", 0) != 0 or tuple(seg.get("segment_pool_id", (0, 0))) != (0, 0):
+            continue
+        for b in seg["blocks"]:
+            if b["state"] == "inactive":
+                out.append((int(b["size"]), seg["segment_type"] == "small"))
+    return out
+
+
+@contextlib.contextmanager
+def poisoned_allocator(device, byte, large_bytes=256 << 20, small_segments=32):
+    """Inside the block, torch's caching allocator hands out only memory filled with `byte` (on `device`, default stream, eager calls:
+    captured graphs allocate from private pools and are out of scope).  Create the op's inputs BEFORE entering, so they lie outside
+    the poison; move results to the CPU and drop the device tensors before the next use (the cache then holds the last run's data).
+
+    Seeding: synchronise, empty_cache(); one uint8 block of `large_bytes`; 2 x `small_segments` tensors of 1 MiB (the small pool's
+    limit; two fill one of its 2 MiB segments); then a sweep that claims every free block the cache still holds -- empty_cache()
+    returns only wholly free segments to the driver, so the free remainders of the segments that hold live tensors (the op's inputs,
+    other tests' module state) are still there, unpoisoned, and being the smallest blocks that fit they would be handed out FIRST.
+    The sweep reads them from torch.cuda.memory_snapshot() and requests each one's exact size (a small-pool block larger than 1 MiB
+    in pieces of 1 MiB, since a larger request would go to the large pool) until none is left.  Everything held is filled with
+    `byte` and freed without emptying the cache.
+
+    Found on ROCm torch 2.10 / MI355X: the allocator behaves as upstream's (small pool up to 1 MiB in 2 MiB segments, larger requests
+    split off the one large block; no pool limit or split rule got in the way), and all four canaries, the segment count and the
+    pointer check hold with this seeding -- also late in a suite run, when hundreds of earlier tests have left live tensors and
+    fragmented segments behind.  The one surprise: freed neighbours coalesce, so an allocation may straddle two seeded tensors;
+    `Poison` merges adjacent ranges.
+
+    The helper shows that it worked, and fails otherwise:
+      * canaries: torch.empty of 512 B, 300 KiB, 3 MiB and 40 MiB must come back all-`byte`; they are read through a device-to-host
+        copy (a comparison on the device would allocate its result out of the poison and dirty it) and freed unwritten;
+      * on exit memory_stats()["segment.all.allocated"] must equal its value after seeding: no fresh segment from the driver, so
+        everything allocated inside came out of poisoned blocks;
+      * `Poison.assert_owns(*tensors)`: the tensors an op returns lie inside the seeded ranges."""
+    assert torch.cuda.current_stream(device).cuda_stream == 0, "poisoned_allocator seeds the default stream's blocks"
+    torch.cuda.synchronize(device)
+    torch.cuda.empty_cache()
+    held = [torch.empty(large_bytes, dtype=torch.uint8, device=device)]
+    held += [torch.empty(1 << 20, dtype=torch.uint8, device=device) for _ in range(2 * small_segments)]
+    for _ in range(16):
+        free = sorted(_free_blocks(device), reverse=True)
+        if not free:
+            break
+        held += [torch.empty(min(size, 1 << 20) if small else size, dtype=torch.uint8, device=device) for size, small in free]
+    assert not _free_blocks(device), "poisoned_allocator: free blocks are left that the sweep could not claim"
+    for t in held:
+        t.fill_(byte)
+    ranges = [(t.data_ptr(), t.data_ptr() + t.numel()) for t in held]
+    torch.cuda.synchronize(device)
+    del held, t
+    segments = torch.cuda.memory_stats(device)["segment.all.allocated"]
+    poison = Poison(device, byte, ranges, segments)
+    for n in POISON_CANARIES:
+        c = torch.empty(n, dtype=torch.uint8, device=device)
+        assert poison.owns(c), f"poison did not take: a {n}-byte request came from outside the seeded ranges"
+        host = c.cpu().numpy()
+        del c
+        assert host.min() == byte == host.max(), f"poison did not take: a {n}-byte request is not all 0x{byte:02X}"
+    assert torch.cuda.memory_stats(device)["segment.all.allocated"] == segments, "poison did not take: a canary needed a fresh segment"
+    yield poison
+    torch.cuda.synchronize(device)
+    got = torch.cuda.memory_stats(device)["segment.all.allocated"]
+    assert got == segments, f"{got - segments} fresh segment(s) came from the driver inside the poisoned block: not all memory was poisoned"

@@ -1407,6 +1407,63 @@ def test_fused_activations_match_torch_getters(gpu, hip_lib, P, K):
             assert hp.rel_err(a[k].grad.cpu().numpy(), b[k].grad.cpu().numpy()) < 1e-5, k
 
 
+def _ulp32(x):
+    """The float32 unit in the last place at the magnitude of the float64 values ``x``: 2^(floor(log2 |x|) - 23)."""
+    return np.ldexp(1.0, np.frexp(np.abs(x))[1] - 24)
+
+
+@pytest.mark.parametrize("P,K", [(150001, 16), (1000001, 1)])
+def test_fused_activations_match_torch_getters_in_the_second_grid_turn(gpu, hip_lib, P, K):
+    """activations.hip caps its grid at 8192 x 256 threads and walks the remaining float4 cells with a grid stride: at these sizes the
+    loop body runs twice.  (150001, 16): 2 212 516 cells, the turn falls in the quaternion section; (1000001, 1): 3 500 005 cells, it
+    falls inside the scaling section and all of the rotation section runs in the second turn.  Every ELEMENT against the float64 torch
+    getters and float64 autograd on the same float32 inputs (randn), not against a max-normalised error:
+      xyz, features and their gradients   bit-exact
+      sigmoid, exp, normalize             within 4 float32 ulps of the float64 value
+      d opacity                           8 * 2^-24 * |g|                (absolute: 1 - s cancels)
+      d scaling                           4 ulps
+      d rotation                          8 * 2^-24 * |g|_2 / |q|        (absolute: g - y (y.g) cancels)
+    with g the incoming gradient: one expf, sqrtf or reciprocal at <= 1-2 ulp each plus the two to four roundings around it.
+    The bounds are derived, not measured.  Measured on an MI355X, worst error / bound over all elements (the test prints them):
+      (150001, 16)   sigmoid 0.536  exp 0.204  normalize 0.651  d_scaling 0.413  d_opacity 0.162  d_rotation 0.613
+      (1000001, 1)   sigmoid 0.536  exp 0.211  normalize 0.706  d_scaling 0.434  d_opacity 0.164  d_rotation 0.665"""
+    from moss_amd.activations import activate_gaussians
+    a = _raw_params(P, K, gpu)
+    outs = activate_gaussians(a["xyz"], a["dc"], a["rest"], a["opa"], a["scl"], a["rot"])
+    g = torch.Generator().manual_seed(9)
+    ws = [torch.randn(*o.shape, generator=g) for o in outs]
+    sum((o * w.to(gpu)).sum() for o, w in zip(outs, ws)).backward()
+    b = {k: v.detach().cpu().double().requires_grad_(True) for k, v in a.items()}
+    refs = (b["xyz"] * 1.0, torch.cat((b["dc"], b["rest"]), dim=1), torch.sigmoid(b["opa"]), torch.exp(b["scl"]),
+            torch.nn.functional.normalize(b["rot"]))
+    sum((r * w.double()).sum() for r, w in zip(refs, ws)).backward()
+    got = [o.detach().cpu() for o in outs]
+    # copies: bit-exact
+    assert torch.equal(got[0], a["xyz"].detach().cpu()) and torch.equal(got[1], torch.cat((a["dc"], a["rest"]), dim=1).detach().cpu())
+    assert torch.equal(a["xyz"].grad.cpu(), ws[0]) and torch.equal(a["dc"].grad.cpu(), ws[1][:, :1])
+    if K > 1:
+        assert torch.equal(a["rest"].grad.cpu(), ws[1][:, 1:])
+    worst = {}
+
+    def within(name, x, ref, bound):
+        x, ref = x.double().numpy(), ref.detach().numpy()
+        ratio = np.abs(x - ref) / bound
+        k = int(np.argmax(ratio))
+        worst[name] = float(ratio.reshape(-1)[k])
+        return worst[name] <= 1.0, (name, k, worst[name])
+
+    checks = []
+    for name, x, ref in (("sigmoid", got[2], refs[2]), ("exp", got[3], refs[3]), ("normalize", got[4], refs[4]),
+                         ("d_scaling", a["scl"].grad.cpu(), b["scl"].grad)):
+        checks.append(within(name, x, ref, 4.0 * _ulp32(ref.detach().numpy())))
+    checks.append(within("d_opacity", a["opa"].grad.cpu(), b["opa"].grad, 8.0 * hp.U32 * np.abs(ws[2].double().numpy())))
+    row = (ws[4].double().norm(dim=1, keepdim=True) / b["rot"].detach().norm(dim=1, keepdim=True)).numpy()
+    checks.append(within("d_rotation", a["rot"].grad.cpu(), b["rot"].grad, 8.0 * hp.U32 * np.broadcast_to(row, (P, 4))))
+    print(f"\nP={P} K={K}: worst error / bound: " + ", ".join(f"{k} {v:.3f}" for k, v in worst.items()))
+    for ok, what in checks:
+        assert ok, what
+
+
 def test_fused_activations_write_into_the_bucket_without_copies(gpu, hip_lib):
     """With a GradBucket as sink the backward kernel writes the raw-parameter gradients into the flat bucket and autograd adopts
     those views as .grad (same storage, no accumulate kernel); an unused output (NULL incoming gradient) yields zeros even
