@@ -420,6 +420,71 @@ typedef struct moss_frames_to_u8_args {
 int moss_frames_to_u8(const moss_frames_to_u8_args* args, void* stream);
 
 /*
+ * A view's ground truth from its raw image and mask (additive in ABI 7; no existing entry point changes): the image path of MOSS's
+ * dataset readers -- scene/dataset_readers.py:613-654 (ZJU), :361-407 (MonoCap), :830-868 (DNA-Rendering) and, later,
+ * PILtoTorch(...)/255 (utils/general_utils.py:22-28): imread/255, cv2.undistort of image and mask, image[msk == 0] = background,
+ * cv2.resize by an integer factor (INTER_AREA; INTER_NEAREST for the mask), np.array(image*255.0, dtype=np.byte).  Up to eight views of
+ * one size per call: raw bytes in, packed 8-bit ground truth out.  THE CONTRACT is the text below -- the maintainers' reading of
+ * OpenCV 4 (undistort = initUndistortRectifyMap(R = I, newK = K) + remap(INTER_LINEAR, BORDER_CONSTANT 0), source coordinates
+ * quantised to 1/32 pixel, INTER_AREA at an integer factor = a box mean) -- and not OpenCV: the agreement with cv2 is unmeasured
+ * (DESIGN.md lists where the two may differ).  Every operation is rounded on its own (no FMA contraction).
+ *   rgb[b] (H0,W0,3) bytes, interleaved; mask[b] (H0,W0) bytes; K[b] 9 doubles, row-major (K[b][1] must be 0, fx = K[b][0] and
+ *   fy = K[b][4] positive; cx = K[b][2], cy = K[b][5]; row 2 is not read); D[b] = k1, k2, p1, p2, k3 (all zero: no distortion, sampled
+ *   by the same code).  K and D are HOST values of the block.  scale = 1, 2 or 4 must divide H0 and W0: H = H0/scale, W = W0/scale.
+ * Per full-resolution sample (u, v), u the column:
+ *   1. the map, in float64, in this order:  x = (u - cx)/fx, y = (v - cy)/fy;  x2 = x*x, y2 = y*y, r2 = x2 + y2, xy2 = 2*x*y;
+ *      kr = 1 + ((k3*r2 + k2)*r2 + k1)*r2;  xd = x*kr + p1*xy2 + p2*(r2 + 2*x2),  yd = y*kr + p1*(r2 + 2*y2) + p2*xy2  (sums left to
+ *      right);  su = fx*xd + cx, sv = fy*yd + cy;  iu = rint(su*32), iv = rint(sv*32), ties to even.  If either is not finite or has
+ *      magnitude >= 2^30 every tap of the sample is outside; else ix = iu >> 5 (floor), ax = iu & 31, likewise iy, ay.
+ *   2. taps (ix,iy), (ix+1,iy), (ix,iy+1), (ix+1,iy+1); a tap outside the image reads 0.
+ *   3. colour, in float32: per channel p = byte/255.f, weights w00 = (1-ay/32.f)*(1-ax/32.f), w01 = (1-ay/32.f)*(ax/32.f),
+ *      w10 = (ay/32.f)*(1-ax/32.f), w11 = (ay/32.f)*(ax/32.f);  c = ((p00*w00 + p01*w01) + p10*w10) + p11*w11.
+ *   4. mask_mode 0 ("round": ZJU's uint8 msk != 0, whose byte remap rounds), in integers: weights in 1/1024 (32-ax)(32-ay),
+ *      ax(32-ay), (32-ax)ay, ax*ay; a tap is foreground iff its byte != 0; the sample is foreground iff the foreground weights sum to
+ *      >= 512 (half rounds up); m = 0 or 1.
+ *   5. mask_mode 1 ("any": MonoCap / DNA-Rendering's float mask/255), in float32: m = the bilinear value of byte/255.f with the
+ *      weights and the order of 3; foreground iff m != 0.
+ *   6. a background sample's colour is `background` (float32 0 or 1).
+ * Output pixel (i, j) takes the samples (scale*j + dx, scale*i + dy):
+ *   colour: scale 1 the sample; scale 2 ((c00 + c01) + (c10 + c11)) * 0.25f; scale 4 the balanced pairwise tree over the 16 samples in
+ *     row-major order -- neighbours, then pairs (a row's four), then rows 0+1 and 2+3, then the two halves -- times 0.0625f;
+ *   gt_u8[b] planar (3,H,W): trunc(colour * 255.f), in [0, 255];  bkgd_u8[b] (H,W): trunc(m * 255.f) of the sample dx = dy = 0
+ *     (INTER_NEAREST at an integer factor): 0 or 255 in mode 0.
+ * Every output byte is written and none beside them, at any address; wide loads and packed stores are used per view where its
+ * pointers allow.  H0 * W0 * 3 must be < 2^31.  One launch on `stream`, no workspace, no host synchronisation: capturable.
+ */
+typedef struct moss_view_images_prepare_args {
+    int32_t num_views;                       /* 1..8 */
+    int32_t H0, W0;                          /* the raw size; every view of a call has it */
+    int32_t scale;                           /* 1, 2 or 4; divides H0 and W0 */
+    int32_t background;                      /* 0 or 1 */
+    int32_t mask_mode;                       /* 0 = round, 1 = any */
+    const unsigned char* rgb[8];
+    const unsigned char* mask[8];
+    double K[8][9];
+    double D[8][5];
+    unsigned char* gt_u8[8];                 /* (3,H,W) */
+    unsigned char* bkgd_u8[8];               /* (H,W) */
+} moss_view_images_prepare_args;
+int moss_view_images_prepare(const moss_view_images_prepare_args* args, void* stream);
+
+/*
+ * One view's packed ground truth to the float32 static inputs of a step (additive in ABI 7): what PILtoTorch(...)/255
+ * (utils/general_utils.py:22-28) makes of the reader's bytes.  gt_image (3,H,W) = gt_u8/255.f and bkgd_mask (1,H,W) = bkgd_u8/255.f,
+ * a correctly rounded float32 division (not a multiplication by a reciprocal): bit for bit torch.from_numpy(u8)/255.0.  The float
+ * outputs must be 4-byte aligned; the bytes may start anywhere.  One launch on `stream`, no host read: capturable -- what a caller's
+ * load_frame calls per frame change.
+ */
+typedef struct moss_view_images_load_args {
+    int32_t H, W;
+    const unsigned char* gt_u8;              /* (3,H,W) */
+    const unsigned char* bkgd_u8;            /* (H,W) */
+    float* gt_image;                         /* (3,H,W) */
+    float* bkgd_mask;                        /* (1,H,W) */
+} moss_view_images_load_args;
+int moss_view_images_load(const moss_view_images_load_args* args, void* stream);
+
+/*
  * Per-Gaussian linear blend skinning of MOSS's coarse_deform_c2source (scene/gaussian_model.py:820-923, called from
  * gaussian_renderer/__init__.py:60,72), from the blend weights to the world-space transform, fused into one launch each way.
  * Per Gaussian i with v = vert_ids[i] (its nearest big-pose SMPL vertex):

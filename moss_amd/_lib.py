@@ -103,6 +103,10 @@ def _declare(lib):
     lib.moss_eval_metrics.argtypes = [_p, _p]
     lib.moss_frames_to_u8.restype = _i
     lib.moss_frames_to_u8.argtypes = [_p, _p]
+    lib.moss_view_images_prepare.restype = _i
+    lib.moss_view_images_prepare.argtypes = [_p, _p]
+    lib.moss_view_images_load.restype = _i
+    lib.moss_view_images_load.argtypes = [_p, _p]
     lib.moss_lbs_workspace_bytes.restype = C.c_size_t
     lib.moss_lbs_workspace_bytes.argtypes = [_i, _i]
     lib.moss_lbs_deform_forward.restype = _i
@@ -233,6 +237,20 @@ class FramesToU8Args(C.Structure):
     _fields_ = [("num_views", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("channels_out", C.c_int32), ("rounding", C.c_int32),
                 ("image", C.c_void_p * 8), ("alpha", C.c_void_p * 8), ("bound", C.c_void_p * 8), ("fill", C.c_float),
                 ("out", C.c_void_p * 8)]
+
+
+class ViewImagesPrepareArgs(C.Structure):
+    """``moss_view_images_prepare_args`` of include/moss_raster.h (``moss_view_images_prepare``: up to eight views' raw image and mask
+    bytes to their packed 8-bit ground truth, one launch).  ``K[b]`` / ``D[b]`` are host doubles."""
+    _fields_ = [("num_views", C.c_int32), ("H0", C.c_int32), ("W0", C.c_int32), ("scale", C.c_int32), ("background", C.c_int32),
+                ("mask_mode", C.c_int32), ("rgb", C.c_void_p * 8), ("mask", C.c_void_p * 8), ("K", C.c_double * 9 * 8),
+                ("D", C.c_double * 5 * 8), ("gt_u8", C.c_void_p * 8), ("bkgd_u8", C.c_void_p * 8)]
+
+
+class ViewImagesLoadArgs(C.Structure):
+    """``moss_view_images_load_args`` of include/moss_raster.h (``moss_view_images_load``: one view's packed bytes / 255 to float32)."""
+    _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("gt_u8", C.c_void_p), ("bkgd_u8", C.c_void_p), ("gt_image", C.c_void_p),
+                ("bkgd_mask", C.c_void_p)]
 
 
 _LBS_INPUTS = [("P", C.c_int32), ("J", C.c_int32), ("V", C.c_int32), ("vert_ids", C.c_void_p), ("weights", C.c_void_p),

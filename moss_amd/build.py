@@ -41,6 +41,7 @@ SOURCES = {
     "s3im.hip": [],
     "metrics.hip": [],
     "present.hip": [],
+    "view_images.hip": ["-ffp-contract=off"],
     "lbs.hip": [],
     "smpl_frame.hip": [],
     "frame_bounds.hip": [],
