@@ -1,7 +1,8 @@
 """moss_amd: MOSS's hot paths as HIP kernels for the MI355X (gfx950).  The ops live in the submodules (``moss_amd.bounds``,
 ``moss_amd.play``, ...); importing the package loads none of them.  The names below resolve on first use."""
 
-_LAZY = {"prepare_views": "images", "prepare_views_torch": "images"}
+_LAZY = {"prepare_views": "images", "prepare_views_torch": "images",
+         "BakedGaussians": "bake", "render_baked": "bake"}
 
 __all__ = sorted(_LAZY)
 
