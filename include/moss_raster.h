@@ -555,6 +555,47 @@ int moss_lbs_deform_backward(const moss_lbs_backward_args* args, void* stream);
 size_t moss_lbs_workspace_bytes(int P, int J);
 
 /*
+ * moss_lbs_deform_backward with the frame's R and Th as variables too (additive in ABI 7): what fitting a frame's SMPL parameters to
+ * images needs.  Every field of moss_lbs_backward_args with its meaning there, plus g_R (3,3) and g_Th (3), each optional.  With
+ *     gT'_i = g_T_i + g_p_i x_i^T,   gt'_i = g_t_i + g_p_i,   N_i = O3 Q,   n_i = O3 (d_i - Q b) + o      (T = R N, t = R n + Th)
+ *     g_Th = sum_i gt'_i,            g_R = sum_i (gT'_i N_i^T + gt'_i n_i^T)
+ * -- the gradient of the op as defined above (M = R O3), not of the reference's torch.inverse(R) expression (scene/gaussian_model.py:
+ * 915-918); the two agree where R is a rotation.  The twelve values ride the reduction of g_A_obs: per-workgroup sums (float64, in lane
+ * order) in `workspace`, folded in workgroup order in float64 by the same fold launch; no float atomics: bitwise reproducible.  A
+ * Gaussian with an id outside [0, V) adds nothing.  g_L, g_A_obs, g_d and g_x equal moss_lbs_deform_backward's bit for bit.
+ *   workspace: moss_lbs_frame_workspace_bytes(P, J) device bytes (needed with g_A_obs, g_R or g_Th; >= moss_lbs_workspace_bytes).
+ * Three launches on `stream` (moss_lbs_deform_backward's kernel as it is, a kernel of the same shape for the twelve values, the fold);
+ * no host synchronisation, no allocation, no memset: capturable.  Every device loop has a trip count fixed by the arguments.  P = 0
+ * launches nothing that reads a Gaussian: g_R and g_Th are written as zero (g_A_obs is not written).  Bad
+ * arguments return MOSS_ERR_INVALID_ARG with "moss_lbs_deform_backward_frame" in moss_last_error().
+ */
+typedef struct moss_lbs_backward_frame_args {
+    int32_t P, J, V;
+    const int64_t* vert_ids;
+    const float* weights;
+    const float* lbs_offsets;
+    const float* A_big;
+    const float* A_obs;
+    const float* d;
+    const float* R;
+    const float* Th;
+    const float* x;
+    const float* g_T;                        /* (P,3,3) or NULL */
+    const float* g_t;                        /* (P,3) or NULL */
+    const float* g_p;                        /* (P,3) or NULL; needs x */
+    float* g_L;                              /* (P,J) or NULL; needs lbs_offsets */
+    float* g_A_obs;                          /* (J,4,4) or NULL */
+    float* g_d;                              /* (P,3) or NULL */
+    float* g_x;                              /* (P,3) or NULL; needs x */
+    char* workspace; size_t workspace_bytes;
+    float* g_R;                              /* (3,3) or NULL */
+    float* g_Th;                             /* (3) or NULL */
+} moss_lbs_backward_frame_args;
+int moss_lbs_deform_backward_frame(const moss_lbs_backward_frame_args* args, void* stream);
+/* device bytes of moss_lbs_deform_backward_frame's workspace (host-side arithmetic, monotonic); 0 for P <= 0 or J outside 1..64 */
+size_t moss_lbs_frame_workspace_bytes(int P, int J);
+
+/*
  * The per-frame, per-subject part of MOSS's coarse_deform_c2source (additive in ABI 7): what scene/gaussian_model.py:835-901 computes
  * before and between the per-Gaussian steps, with get_transform_params_torch / get_rigid_transformation_torch (:965-1031) and
  * batch_rodrigues_torch (:945-963).  It feeds moss_lbs_deform_forward (A_big, A_obs, d) and takes its gradients back.
@@ -626,6 +667,40 @@ typedef struct moss_smpl_frame_backward_args {
 int moss_smpl_frame_backward(const moss_smpl_frame_backward_args* args, void* stream);   /* the adjoint of scene/gaussian_model.py:885-901, :965-995 */
 /* device bytes of either call's workspace (host-side arithmetic, monotonic); 0 for a size <= 0 or J outside 1..64 (gaussian_model.py:835-901) */
 size_t moss_smpl_frame_workspace_bytes(int P, int V, int J);
+
+/*
+ * Backward of moss_smpl_frame_forward to the frame's pose as well (additive in ABI 7): what fitting a frame's SMPL parameters to
+ * images needs.  Every field of moss_smpl_frame_backward_args with its meaning there (g_correct_Rs becomes optional), plus poses (3J)
+ * and correct_Rs ((J-1,3,3) or NULL: the identity) as the forward read them, and the output g_poses (3J), written, never accumulated
+ * into.  g_feat and the reverse walk of the tree are moss_smpl_frame_backward's; then
+ *     g_rot_0 = gGR_0 after the walk has accumulated into it (G_0.R = rot_0),    g_raw_0 = g_rot_0,
+ *     g_raw_j = (g_rot_j + g_feat[9(j-1) .. 9(j-1)+8]) correct_Rs[j-1]^T         for j >= 1,
+ *     and the adjoint of batch_rodrigues_torch as the reference writes it (scene/gaussian_model.py:945-963), one joint per thread:
+ *     e = r + 1e-8, a = |e|, k = r / a (the shift is in the norm only), raw = I + sin a K + (1 - cos a) K K, G = g_raw_j:
+ *       g_s = <G, K>,  g_c = <G, K K>,  gK = sin a G + (1 - cos a)(G K^T + K^T G),  g_k = (gK_21 - gK_12, gK_02 - gK_20, gK_10 - gK_01),
+ *       g_a = g_s cos a + g_c sin a - <g_k, r> / a^2,   g_poses[3j .. 3j+2] = g_k / a + g_a e / a.
+ * shapes, the body model and the big pose stay data.  saved: as the forward wrote it (MOSS_SMPL_FRAME_SAVED_FLOATS_PER_JOINT per joint).
+ * workspace: moss_smpl_frame_workspace_bytes(P, V, J) device bytes (needed with g_d).  Three launches on `stream` (one without g_d or
+ * with P = 0: g_poses then comes from g_A_obs alone), float64 sums in a fixed order, no atomics: bitwise reproducible.  No host
+ * synchronisation, no allocation, no memset: capturable.  Every device loop has a trip count fixed by the arguments (J, a workgroup's
+ * run of Gaussians, the number of workgroups).  Bad arguments return MOSS_ERR_INVALID_ARG with "moss_smpl_frame_backward_pose" in
+ * moss_last_error().
+ */
+typedef struct moss_smpl_frame_backward_pose_args {
+    int32_t P, V, J;
+    int32_t parents[MOSS_SMPL_FRAME_MAX_JOINTS];
+    const float* posedirs;
+    const int64_t* vert_ids;
+    const float* saved;
+    const float* g_A_obs;                    /* (J,4,4) or NULL; row 3 is not read */
+    const float* g_d;                        /* (P,3) or NULL */
+    float* g_correct_Rs;                     /* (J-1,3,3) or NULL */
+    char* workspace; size_t workspace_bytes;
+    const float* poses;                      /* (3J) */
+    const float* correct_Rs;                 /* (J-1,3,3) or NULL */
+    float* g_poses;                          /* (3J) */
+} moss_smpl_frame_backward_pose_args;
+int moss_smpl_frame_backward_pose(const moss_smpl_frame_backward_pose_args* args, void* stream);   /* the adjoint of scene/gaussian_model.py:885-901, :945-995 */
 
 /*
  * The posed SMPL vertices of a frame in the world and their padded box (additive in ABI 7): the reference's numpy SMPL.__call__

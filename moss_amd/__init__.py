@@ -2,7 +2,8 @@
 ``moss_amd.play``, ...); importing the package loads none of them.  The names below resolve on first use."""
 
 _LAZY = {"prepare_views": "images", "prepare_views_torch": "images",
-         "BakedGaussians": "bake", "render_baked": "bake"}
+         "BakedGaussians": "bake", "render_baked": "bake",
+         "PoseFitter": "posefit", "posed_frame": "posefit"}
 
 __all__ = sorted(_LAZY)
 

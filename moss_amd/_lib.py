@@ -113,6 +113,12 @@ def _declare(lib):
     lib.moss_lbs_deform_forward.argtypes = [_p, _p]
     lib.moss_lbs_deform_backward.restype = _i
     lib.moss_lbs_deform_backward.argtypes = [_p, _p]
+    lib.moss_lbs_frame_workspace_bytes.restype = C.c_size_t
+    lib.moss_lbs_frame_workspace_bytes.argtypes = [_i, _i]
+    lib.moss_lbs_deform_backward_frame.restype = _i
+    lib.moss_lbs_deform_backward_frame.argtypes = [_p, _p]
+    lib.moss_smpl_frame_backward_pose.restype = _i
+    lib.moss_smpl_frame_backward_pose.argtypes = [_p, _p]
     lib.moss_smpl_frame_workspace_bytes.restype = C.c_size_t
     lib.moss_smpl_frame_workspace_bytes.argtypes = [_i, _i, _i]
     lib.moss_smpl_frame_forward.restype = _i
@@ -270,6 +276,11 @@ class LbsBackwardArgs(C.Structure):
                               ("workspace_bytes", C.c_size_t)]
 
 
+class LbsBackwardFrameArgs(C.Structure):
+    """``moss_lbs_backward_frame_args`` of include/moss_raster.h (``moss_lbs_deform_backward_frame``: the backward with ``g_R``, ``g_Th``)."""
+    _fields_ = LbsBackwardArgs._fields_ + [("g_R", C.c_void_p), ("g_Th", C.c_void_p)]
+
+
 SMPL_FRAME_MAX_JOINTS = 64                               # MOSS_SMPL_FRAME_MAX_JOINTS
 SMPL_FRAME_SAVED_FLOATS_PER_JOINT = 33                   # MOSS_SMPL_FRAME_SAVED_FLOATS_PER_JOINT
 
@@ -289,6 +300,11 @@ class SmplFrameBackwardArgs(C.Structure):
     _fields_ = [("P", C.c_int32), ("V", C.c_int32), ("J", C.c_int32), ("parents", C.c_int32 * 64), ("posedirs", C.c_void_p),
                 ("vert_ids", C.c_void_p), ("saved", C.c_void_p), ("g_A_obs", C.c_void_p), ("g_d", C.c_void_p),
                 ("g_correct_Rs", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+class SmplFrameBackwardPoseArgs(C.Structure):
+    """``moss_smpl_frame_backward_pose_args`` of include/moss_raster.h (``moss_smpl_frame_backward_pose``: the backward with ``g_poses``)."""
+    _fields_ = SmplFrameBackwardArgs._fields_ + [("poses", C.c_void_p), ("correct_Rs", C.c_void_p), ("g_poses", C.c_void_p)]
 
 
 class SmplVerticesArgs(C.Structure):

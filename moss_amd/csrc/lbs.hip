@@ -8,6 +8,11 @@
 //           math in torch).  The J x 12 gradient of A_obs is sum_i w_ij gO_i: each workgroup of 128 lanes stages w and gO in LDS and
 //           forms its 128-term sums in a fixed order (one output element per thread), the J x 12 partials of every workgroup go to
 //           the workspace, and a fold launch adds them up in workgroup order in float64.  No atomics: bitwise reproducible.
+// backward_frame (moss_lbs_deform_backward_frame): the backward kernel as it is (so its outputs keep their bits), and beside it a
+//           kernel of the same shape that forms, per Gaussian, the twelve terms of g_R = sum_i (gT'_i N_i^T + gt'_i n_i^T) and
+//           g_Th = sum_i gt'_i (N = O3 Q, n = O3 (d - Q b) + o).  They ride the same reduction: staged in LDS, summed per workgroup
+//           in lane order in float64 (one value per thread), folded in workgroup order by the same fold launch.  Every loop's trip
+//           count is a constant or the number of workgroups.
 // Instantiations: J = 24 (SMPL) with 16-byte loads and stores of the W / L / w rows, and J rounded up to a multiple of 8 (8 .. 64)
 // with per-element guards for every other J.  Nothing is allocated, nothing synchronises, nothing is cleared with a memset.
 #include "common.h"
@@ -353,6 +358,103 @@ lbs_fold_kernel(int J, int nblocks, const float* __restrict__ partials, float* _
     if (lane == 0) gA[o] = (float)acc;
 }
 
+// this workgroup's share of [g_R | g_Th]: one lane per Gaussian (the workgroups of lbs_backward_kernel), the forward recomputed;
+// fpartials [blocks][12] (g_R row-major, then g_Th).  Lanes past P and Gaussians with an id outside [0, V) stage zeros.
+template <int JB, bool VEC>
+__global__ void __launch_bounds__(LBS_BWD_BLOCK)
+lbs_frame_terms_kernel(LbsIn a, const float* __restrict__ g_T, const float* __restrict__ g_t, const float* __restrict__ g_p,
+                       double* __restrict__ fpartials)
+{
+    __shared__ float4 s_Ab[3 * JB], s_Ao[3 * JB];
+    __shared__ float s_RT[12];
+    __shared__ float s_f[LBS_BWD_BLOCK][12];
+    lbs_stage_frame(a, s_Ab, s_Ao, s_RT);
+    __syncthreads();
+    const int lane = threadIdx.x;
+    const int i = blockIdx.x * LBS_BWD_BLOCK + lane;
+    const int64_t v = i < a.P ? a.ids[i] : 0;
+    const bool valid = i < a.P && v >= 0 && v < a.V;
+    float gF[12];
+#pragma unroll
+    for (int k = 0; k < 12; k++) gF[k] = 0.0f;
+    if (valid) {
+        float w[JB];
+        lbs_weights<JB, VEC>(a, i, v, w);
+        LbsState s;
+        lbs_state<JB>(w, a.J, s_Ab, s_Ao, s_RT, a.d + (size_t)i * 3, s);
+        float gT[9], gt[3], gp[3], x[3];
+#pragma unroll
+        for (int k = 0; k < 9; k++) gT[k] = g_T ? g_T[(size_t)i * 9 + k] : 0.0f;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            gt[k] = g_t ? g_t[(size_t)i * 3 + k] : 0.0f;
+            gp[k] = g_p ? g_p[(size_t)i * 3 + k] : 0.0f;
+            x[k] = a.x ? a.x[(size_t)i * 3 + k] : 0.0f;
+        }
+        // p = T x + t:  gT' = gT + gp x^T, gt' = gt + gp
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+#pragma unroll
+            for (int c = 0; c < 3; c++) gT[3 * r + c] = fmaf(gp[r], x[c], gT[3 * r + c]);
+            gt[r] += gp[r];
+        }
+        // T = R N, t = R n + Th with N = O3 Q, n = O3 u + o:  gR = gT' N^T + gt' n^T;  gTh = gt'
+        float N[9], n[3];
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+#pragma unroll
+            for (int c = 0; c < 3; c++)
+                N[3 * r + c] = s.O[4 * r] * s.Q[c] + s.O[4 * r + 1] * s.Q[3 + c] + s.O[4 * r + 2] * s.Q[6 + c];
+            n[r] = (s.O[4 * r] * s.u[0] + s.O[4 * r + 1] * s.u[1] + s.O[4 * r + 2] * s.u[2]) + s.O[4 * r + 3];
+        }
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+#pragma unroll
+            for (int c = 0; c < 3; c++)
+                gF[3 * r + c] = gT[3 * r] * N[3 * c] + gT[3 * r + 1] * N[3 * c + 1] + gT[3 * r + 2] * N[3 * c + 2] + gt[r] * n[c];
+            gF[9 + r] = gt[r];
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 12; k++) s_f[lane][k] = gF[k];
+    __syncthreads();
+    if (lane < 12) {
+        double acc = 0.0;
+#pragma unroll 8
+        for (int q = 0; q < LBS_BWD_BLOCK; q++) acc += (double)s_f[q][lane];
+        fpartials[(size_t)blockIdx.x * 12 + lane] = acc;
+    }
+}
+
+// the fold of moss_lbs_deform_backward_frame: elements [0, 16 J) are gA_obs exactly as lbs_fold_kernel forms them (skipped without gA),
+// elements 16 J + [0, 12) are [g_R | g_Th] from the float64 partials, in workgroup order.  nblocks = 0 (P = 0) writes zeros.
+__global__ void __launch_bounds__(64 * LBS_FOLD_WAVES)
+lbs_fold_frame_kernel(int J, int nblocks, const float* __restrict__ partials, float* __restrict__ gA,
+                      const double* __restrict__ fpartials, float* __restrict__ gR, float* __restrict__ gTh)
+{
+    const int o = blockIdx.x * LBS_FOLD_WAVES + threadIdx.x / 64;
+    const int lane = threadIdx.x % 64;
+    if (o >= J * 16 + 12) return;
+    double acc = 0.0;
+    if (o < J * 16) {
+        if (!gA) return;
+        const int j = o / 16, r = (o % 16) / 4, c = o % 4;
+        if (r < 3) {
+            const size_t stride = (size_t)J * 12, off = (size_t)j * 12 + r * 4 + c;
+            for (int b = lane; b < nblocks; b += 64) acc += (double)partials[(size_t)b * stride + off];
+        }
+        acc = wave_sum(acc);
+        if (lane == 0) gA[o] = (float)acc;
+        return;
+    }
+    const int k = o - J * 16;
+    float* out = k < 9 ? (gR ? gR + k : nullptr) : (gTh ? gTh + (k - 9) : nullptr);
+    if (!out) return;
+    for (int b = lane; b < nblocks; b += 64) acc += fpartials[(size_t)b * 12 + k];
+    acc = wave_sum(acc);
+    if (lane == 0) *out = (float)acc;
+}
+
 // the instantiation for J: 24 with 16-byte row accesses when the rows are 16-byte aligned, else J rounded up to a multiple of 8
 template <template <int, bool> class F, typename... Args>
 void lbs_dispatch(int J, bool vec, Args... args)
@@ -383,6 +485,14 @@ struct LaunchBwd {
     static void run(dim3 grid, hipStream_t s, LbsIn a, LbsGrad g)
     {
         hipLaunchKernelGGL((lbs_backward_kernel<JB, VEC>), grid, dim3(LBS_BWD_BLOCK), 0, s, a, g);
+    }
+};
+
+template <int JB, bool VEC>
+struct LaunchFrameTerms {
+    static void run(dim3 grid, hipStream_t s, LbsIn a, const float* gT, const float* gt, const float* gp, double* fpartials)
+    {
+        hipLaunchKernelGGL((lbs_frame_terms_kernel<JB, VEC>), grid, dim3(LBS_BWD_BLOCK), 0, s, a, gT, gt, gp, fpartials);
     }
 };
 
@@ -449,4 +559,47 @@ extern "C" int moss_lbs_deform_backward(const moss_lbs_backward_args* a, void* s
         hipLaunchKernelGGL(lbs_fold_kernel, dim3((a->J * 16 + LBS_FOLD_WAVES - 1) / LBS_FOLD_WAVES), dim3(64 * LBS_FOLD_WAVES), 0, s,
                            a->J, nblocks, (const float*)partials, a->g_A_obs);
     return launch_status("moss_lbs_deform_backward");
+}
+
+extern "C" size_t moss_lbs_frame_workspace_bytes(int P, int J)
+{
+    if (P <= 0 || J < 1 || J > LBS_MAX_J) return 0;
+    const size_t nb = ((size_t)P + LBS_BWD_BLOCK - 1) / LBS_BWD_BLOCK;
+    return moss_lbs_workspace_bytes(P, J) + align_up(nb * 12 * sizeof(double));
+}
+
+extern "C" int moss_lbs_deform_backward_frame(const moss_lbs_backward_frame_args* a, void* stream)
+{
+    const char* who = "moss_lbs_deform_backward_frame";
+    if (!a) return invalid_arg(who, "null argument block");
+    if (a->P < 0) return invalid_arg(who, "P must be >= 0");
+    if (a->J < 1 || a->J > LBS_MAX_J) return invalid_arg(who, "J must be 1..64");
+    if (a->V < 1) return invalid_arg(who, "V must be >= 1");
+    if (!a->vert_ids || !a->weights || !a->A_big || !a->A_obs || !a->d || !a->R || !a->Th)
+        return invalid_arg(who, "null required input (vert_ids, weights, A_big, A_obs, d, R, Th)");
+    if ((a->g_p || a->g_x) && !a->x) return invalid_arg(who, "g_p and g_x need x");
+    if (a->g_L && !a->lbs_offsets) return invalid_arg(who, "g_L needs lbs_offsets");
+    const bool frame = a->g_R || a->g_Th;
+    if (a->P > 0 && (a->g_A_obs || frame) && (!a->workspace || a->workspace_bytes < moss_lbs_frame_workspace_bytes(a->P, a->J)))
+        return invalid_arg(who, "g_A_obs, g_R and g_Th need moss_lbs_frame_workspace_bytes(P, J) bytes of workspace");
+    hipStream_t s = (hipStream_t)stream;
+    const int nblocks = (a->P + LBS_BWD_BLOCK - 1) / LBS_BWD_BLOCK;
+    float* partials = nullptr;
+    double* fpartials = nullptr;
+    if (a->P > 0) {
+        partials = a->g_A_obs ? reinterpret_cast<float*>(a->workspace) : nullptr;
+        fpartials = frame ? reinterpret_cast<double*>(a->workspace + moss_lbs_workspace_bytes(a->P, a->J)) : nullptr;
+        const bool vec = aligned16(a->weights) && aligned16(a->lbs_offsets) && aligned16(a->g_L);
+        if (a->g_L || a->g_A_obs || a->g_d || a->g_x) {
+            const LbsGrad g{a->g_T, a->g_t, a->g_p, a->g_L, a->g_d, a->g_x, partials};
+            lbs_dispatch<LaunchBwd>(a->J, vec, dim3(nblocks), s, lbs_in(a), g);
+        }
+        if (frame) lbs_dispatch<LaunchFrameTerms>(a->J, vec, dim3(nblocks), s, lbs_in(a), a->g_T, a->g_t, a->g_p, fpartials);
+    }
+    // P = 0: nothing reads a Gaussian; g_R and g_Th are written as zero (g_A_obs is not written, as by moss_lbs_deform_backward)
+    float* gA = a->P > 0 ? a->g_A_obs : nullptr;
+    if (gA || frame)
+        hipLaunchKernelGGL(lbs_fold_frame_kernel, dim3((a->J * 16 + 12 + LBS_FOLD_WAVES - 1) / LBS_FOLD_WAVES), dim3(64 * LBS_FOLD_WAVES), 0,
+                           s, a->J, nblocks, (const float*)partials, gA, (const double*)fpartials, a->g_R, a->g_Th);
+    return launch_status(who);
 }

@@ -17,6 +17,8 @@
 //   fold           one wave per feature adds the partials in workgroup order (as lbs.hip's lbs_fold_kernel; wave.h's butterfly).
 //   chain adjoint  one workgroup: g_A_obs through the chain as a reverse walk of the tree, + the folded features, then
 //                  g_correct_Rs = rot_raw[1:]^T g_rot[1:].
+// backward to the pose (moss_smpl_frame_backward_pose), the same 3 launches: the chain adjoint also keeps the root's g_rot_0 = gGR_0 and
+//                  then, one joint per thread, forms g_raw_j = (g_rot_j + g_feat_j) correct_Rs[j-1]^T and the adjoint of Rodrigues.
 // Every sum is formed in float64 in a fixed order, nothing is atomic, every output element is written: bitwise reproducible.
 // Nothing is allocated, nothing synchronises, nothing is cleared with a memset.
 #include "common.h"
@@ -267,9 +269,17 @@ smpl_frame_fold_kernel(int F, int nblocks, const double* __restrict__ partials, 
 // the adjoint of the frame's chain and of rot[1:] = raw[1:] correct_Rs.  With G_j = G_p local_j (p = parent[j]) and
 // A_j = [GR_j | Gt_j - GR_j joint_j]:  gGR_j = gA_j[:3,:3] - gA_j[:3,3] joint_j^T, gGt_j = gA_j[:3,3]; walking j = J-1 .. 1:
 // g_rot_j = GR_p^T gGR_j, gGR_p += gGR_j rot_j^T + gGt_j rel_j^T, gGt_p += gGt_j.
+//
+// POSE (moss_smpl_frame_backward_pose; the other instantiation never reads poses, cR, g_poses): the root keeps g_rot_0 = gGR_0 (G_0.R = rot_0), and joint j (one per thread) forms
+// g_raw_j = g_rot_j cR_j^T (cR_0 = I; cR = NULL: all I) and the adjoint of r -> raw = I + s K + c K K, e = r + 1e-8, a = |e|, k = r / a,
+// s = sin a, c = 1 - cos a (K K = k k^T - |k|^2 I; the shift is in the norm only):
+//   g_s = <G, K>, g_c = <G, K K>, gK = s G + c (G K^T + K^T G), g_k = (gK_21 - gK_12, gK_02 - gK_20, gK_10 - gK_01),
+//   g_a = g_s cos a + g_c sin a - <g_k, r> / a^2,  g_r = g_k / a + g_a e / a.
+template <bool POSE>
 __global__ void __launch_bounds__(SF_BLOCK)
 smpl_frame_chain_backward_kernel(int J, SfParents par, const float* __restrict__ saved, const float* __restrict__ gA,
-                                 const double* __restrict__ g_feat, float* __restrict__ g_cR)
+                                 const double* __restrict__ g_feat, float* __restrict__ g_cR, const float* __restrict__ poses,
+                                 const float* __restrict__ cR, float* __restrict__ g_poses)
 {
     __shared__ float s_sv[SF_SAVED_PER_J * SF_MAX_J];
     __shared__ double s_gGR[SF_MAX_J * 9], s_gGt[SF_MAX_J * 3], s_gR[SF_MAX_J * 9];
@@ -311,13 +321,59 @@ smpl_frame_chain_backward_kernel(int J, SfParents par, const float* __restrict__
     const int F = 9 * (J - 1);
     if (g_feat)
         for (int k = t; k < F; k += SF_BLOCK) s_gR[9 + k] += g_feat[k];
+    if (POSE && t < 9) s_gR[t] = s_gGR[t];                   // (thread t wrote s_gGR[t] itself in the walk's last steps)
     __syncthreads();
-    for (int k = t; k < F; k += SF_BLOCK) {
-        const int j = 1 + k / 9, r = (k % 9) / 3, c = k % 3;
-        const float* m = raw + 9 * j;
+    if (g_cR)
+        for (int k = t; k < F; k += SF_BLOCK) {
+            const int j = 1 + k / 9, r = (k % 9) / 3, c = k % 3;
+            const float* m = raw + 9 * j;
+            const double* g = s_gR + 9 * j;
+            g_cR[k] = (float)((double)m[r] * g[c] + (double)m[3 + r] * g[3 + c] + (double)m[6 + r] * g[6 + c]);
+        }
+    if (!POSE || t >= J) return;
+    const int j = t;
+    double G[9];
+    {
         const double* g = s_gR + 9 * j;
-        g_cR[k] = (float)((double)m[r] * g[c] + (double)m[3 + r] * g[3 + c] + (double)m[6 + r] * g[6 + c]);
+        if (cR && j >= 1) {
+            const float* m = cR + 9 * (j - 1);
+#pragma unroll
+            for (int r = 0; r < 3; r++)
+#pragma unroll
+                for (int c = 0; c < 3; c++)                          // g_raw = g_rot cR^T
+                    G[3 * r + c] = g[3 * r] * (double)m[3 * c] + g[3 * r + 1] * (double)m[3 * c + 1] + g[3 * r + 2] * (double)m[3 * c + 2];
+        } else {
+#pragma unroll
+            for (int e = 0; e < 9; e++) G[e] = g[e];
+        }
     }
+    const double rx = (double)poses[3 * j], ry = (double)poses[3 * j + 1], rz = (double)poses[3 * j + 2];
+    const double ex = rx + 1e-8, ey = ry + 1e-8, ez = rz + 1e-8;
+    const double a = sqrt(ex * ex + ey * ey + ez * ez);
+    const double kx = rx / a, ky = ry / a, kz = rz / a;
+    const double sh = sin(0.5 * a), sn = sin(a), cs = cos(a);
+    const double cc = 2.0 * sh * sh;                           // 1 - cos a, without the cancellation at small angles
+    const double K[9] = {0.0, -kz, ky, kz, 0.0, -kx, -ky, kx, 0.0};
+    const double kk = kx * kx + ky * ky + kz * kz;
+    const double KK[9] = {kx * kx - kk, kx * ky, kx * kz, kx * ky, ky * ky - kk, ky * kz, kx * kz, ky * kz, kz * kz - kk};
+    double g_s = 0.0, g_c = 0.0;
+#pragma unroll
+    for (int e = 0; e < 9; e++) { g_s = fma(G[e], K[e], g_s); g_c = fma(G[e], KK[e], g_c); }
+    double gK[9];
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            // (G K^T)_rc = sum_q G_rq K_cq;  (K^T G)_rc = sum_q K_qr G_qc
+            const double gkt = G[3 * r] * K[3 * c] + G[3 * r + 1] * K[3 * c + 1] + G[3 * r + 2] * K[3 * c + 2];
+            const double ktg = K[r] * G[c] + K[3 + r] * G[3 + c] + K[6 + r] * G[6 + c];
+            gK[3 * r + c] = sn * G[3 * r + c] + cc * (gkt + ktg);
+        }
+    const double gkx = gK[7] - gK[5], gky = gK[2] - gK[6], gkz = gK[3] - gK[1];
+    const double g_a = g_s * cs + g_c * sn - (gkx * rx + gky * ry + gkz * rz) / (a * a);
+    g_poses[3 * j] = (float)(gkx / a + g_a * ex / a);
+    g_poses[3 * j + 1] = (float)(gky / a + g_a * ey / a);
+    g_poses[3 * j + 2] = (float)(gkz / a + g_a * ez / a);
 }
 
 size_t sf_forward_bytes(int V, int J)
@@ -410,7 +466,40 @@ extern "C" int moss_smpl_frame_backward(const moss_smpl_frame_backward_args* a, 
         hipLaunchKernelGGL(smpl_frame_fold_kernel, dim3((F + SF_FOLD_WAVES - 1) / SF_FOLD_WAVES), dim3(64 * SF_FOLD_WAVES), 0, s, F,
                            nblocks, (const double*)partials, g_feat);
     }
-    hipLaunchKernelGGL(smpl_frame_chain_backward_kernel, dim3(1), dim3(SF_BLOCK), 0, s, a->J, par, a->saved, a->g_A_obs,
-                       (const double*)g_feat, a->g_correct_Rs);
+    hipLaunchKernelGGL(smpl_frame_chain_backward_kernel<false>, dim3(1), dim3(SF_BLOCK), 0, s, a->J, par, a->saved, a->g_A_obs,
+                       (const double*)g_feat, a->g_correct_Rs, (const float*)nullptr, (const float*)nullptr, (float*)nullptr);
+    return launch_status(who);
+}
+
+extern "C" int moss_smpl_frame_backward_pose(const moss_smpl_frame_backward_pose_args* a, void* stream)
+{
+    const char* who = "moss_smpl_frame_backward_pose";
+    if (!a) return invalid_arg(who, "null argument block");
+    if (a->P < 0) return invalid_arg(who, "P must be >= 0");
+    if (a->V < 1) return invalid_arg(who, "V must be >= 1");
+    if (a->J < 1 || a->J > SF_MAX_J) return invalid_arg(who, "J must be 1..64");
+    if (!a->g_poses) return invalid_arg(who, "null g_poses");
+    if (!a->saved || !a->poses) return invalid_arg(who, "null saved or poses");
+    if (int rc = sf_check_parents(who, a->J, a->parents)) return rc;
+    const bool reduce = a->g_d && a->P > 0 && a->J > 1;
+    if (reduce && (!a->vert_ids || !a->posedirs)) return invalid_arg(who, "g_d needs vert_ids and posedirs");
+    if (reduce && (!a->workspace || a->workspace_bytes < sf_backward_bytes(a->P, a->J)))
+        return invalid_arg(who, "g_d needs moss_smpl_frame_workspace_bytes(P, V, J) bytes of workspace");
+    hipStream_t s = (hipStream_t)stream;
+    SfParents par;
+    for (int j = 0; j < SF_MAX_J; j++) par.p[j] = j < a->J ? a->parents[j] : 0;
+    const int F = 9 * (a->J - 1);
+    double* g_feat = nullptr;
+    if (reduce) {
+        const int nblocks = (a->P + SF_GPW - 1) / SF_GPW;
+        double* partials = reinterpret_cast<double*>(a->workspace);
+        g_feat = reinterpret_cast<double*>(a->workspace + align_up((size_t)nblocks * F * sizeof(double)));
+        hipLaunchKernelGGL(smpl_frame_reduce_kernel, dim3(nblocks), dim3(SF_BLOCK), 0, s, a->P, a->V, F, a->vert_ids, a->posedirs, a->g_d,
+                           partials);
+        hipLaunchKernelGGL(smpl_frame_fold_kernel, dim3((F + SF_FOLD_WAVES - 1) / SF_FOLD_WAVES), dim3(64 * SF_FOLD_WAVES), 0, s, F,
+                           nblocks, (const double*)partials, g_feat);
+    }
+    hipLaunchKernelGGL(smpl_frame_chain_backward_kernel<true>, dim3(1), dim3(SF_BLOCK), 0, s, a->J, par, a->saved, a->g_A_obs,
+                       (const double*)g_feat, a->J > 1 ? a->g_correct_Rs : nullptr, a->poses, a->correct_Rs, a->g_poses);
     return launch_status(who);
 }
