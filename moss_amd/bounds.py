@@ -21,7 +21,8 @@ import ctypes
 import numpy as np
 import torch
 
-from .lbs import MAX_JOINTS, _parents, batch_rodrigues
+from ._checks import body_arrays, frame_params, need, need_gpu, no_grad
+from .lbs import batch_rodrigues
 
 __all__ = ["posed_vertices", "posed_vertices_torch", "bound_masks", "bound_mask_numpy", "project_corners_numpy", "camera_KRT",
            "FrameBounds", "dataset_regions", "FACES", "CORNER_LIMIT"]
@@ -128,51 +129,23 @@ def camera_KRT(camera):
 
 
 # ---- the fused ops -------------------------------------------------------------------------------------------------------------------------
-def _need(who, t, name, shape=None, dtype=torch.float32, numel=None):
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"{who}: {name} must be a tensor")
-    if t.dtype != dtype:
-        raise ValueError(f"{who}: {name} must be {dtype}, got {t.dtype}")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{who}: {name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
-    if numel is not None and t.numel() != numel:
-        raise ValueError(f"{who}: {name} must have {numel} elements, got {t.numel()}")
-    if not t.is_contiguous():
-        raise ValueError(f"{who}: {name} must be contiguous")
-    if t.requires_grad:
-        raise ValueError(f"{who}: {name} requires grad, but no gradient is formed for it; detach it")
+_WHY = "no gradient is formed for it"
+
+
+def _data(who, t, name, shape=None, dtype=torch.float32, numel=None, device=None):
+    """``need`` of a tensor that must not require grad."""
+    no_grad(who, ((name, need(who, t, name, shape, dtype, numel, device)),), _WHY)
     return t
 
 
 def _body_arrays(who, body):
-    for key in ("v_template", "shapedirs", "posedirs", "J_regressor", "weights", "kintree_table"):
-        if not isinstance(body.get(key), torch.Tensor):
-            raise ValueError(f"{who}: body['{key}'] must be a tensor")
-    vt, sd, pd, jr, w = (body[k] for k in ("v_template", "shapedirs", "posedirs", "J_regressor", "weights"))
-    J = int(w.shape[-1])
-    if not 1 <= J <= MAX_JOINTS:
-        raise ValueError(f"{who}: J = {J} joints; the kernels take 1..{MAX_JOINTS}")
-    if vt.dim() != 2 or vt.shape[0] < 1:
-        raise ValueError(f"{who}: v_template must be (V, 3) with V >= 1")
-    V = int(vt.shape[0])
-    if sd.dim() != 3:
-        raise ValueError(f"{who}: shapedirs must be (V, 3, B)")
-    _need(who, vt, "v_template", (V, 3))
-    _need(who, sd, "shapedirs", (V, 3, sd.shape[2]))
-    _need(who, pd, "posedirs", (V, 3, 9 * (J - 1)))
-    _need(who, jr, "J_regressor", (J, V))
-    _need(who, w, "weights", (V, J))
-    dev = vt.device
-    if dev.type != "cuda":
-        raise ValueError(f"{who} runs the HIP kernels of csrc/frame_bounds.hip: its tensors must be on a GPU (posed_vertices_torch is "
-                         "the torch form)")
-    for name, t in (("shapedirs", sd), ("posedirs", pd), ("J_regressor", jr), ("weights", w)):
-        if t.device != dev:
-            raise ValueError(f"{who}: {name} must be on {dev}, got {t.device}")
-    par = _parents(body, dev)[0]
-    if len(par) != J or any(not 0 <= par[j] < j for j in range(1, J)):
-        raise ValueError(f"{who}: kintree_table[0] must list J parents with 0 <= parent[j] < j for j >= 1")
-    return V, J, [-1] + list(par[1:]), dev
+    return body_arrays(who, body, _WHY, "kernels of csrc/frame_bounds.hip", "posed_vertices_torch is the torch form", check_weights=True)
+
+
+def _frame_inputs(who, params, J, body, dev):
+    flat = frame_params(who, params, ("poses", "shapes", "R", "Th"), J, int(body["shapedirs"].shape[2]), dev)
+    no_grad(who, [(f"params['{k}']", t) for k, t in flat.items()], _WHY)
+    return flat
 
 
 def _launch_vertices(body, V, J, par, poses, shapes, R, Th, pad, world_vertex, world_bound, joints, ws):
@@ -188,22 +161,6 @@ def _launch_vertices(body, V, J, par, poses, shapes, R, Th, pad, world_vertex, w
     call("moss_smpl_vertices", world_vertex.device, ctypes.byref(a))
 
 
-def _frame_inputs(who, params, J, B, dev):
-    for key in ("poses", "shapes", "R", "Th"):
-        if not isinstance(params.get(key), torch.Tensor):
-            raise ValueError(f"{who}: params['{key}'] must be a tensor")
-    nb = int(params["shapes"].numel())
-    if nb > B:
-        raise ValueError(f"{who}: {nb} shape coefficients, but shapedirs stores {B}")
-    flat = {}
-    for key, n in (("poses", 3 * J), ("shapes", nb), ("R", 9), ("Th", 3)):
-        t = _need(who, params[key], f"params['{key}']", numel=n)
-        if t.device != dev:
-            raise ValueError(f"{who}: params['{key}'] must be on {dev}, got {t.device}")
-        flat[key] = t.reshape(-1)
-    return flat
-
-
 def posed_vertices(body, params, pad=0.1, out=None, joints=False):
     """``(world_vertex (V,3), world_bound (2,3)[, joints (J,3)])`` of one frame on the device (C ABI ``moss_smpl_vertices``, three
     launches): what dataset_readers.py:428-436 computes with numpy SMPL on the CPU; a subject's ``big_pose_world_vertex`` /
@@ -217,11 +174,9 @@ def posed_vertices(body, params, pad=0.1, out=None, joints=False):
     from ._lib import lib
     who = "posed_vertices"
     V, J, par, dev = _body_arrays(who, body)
-    flat = _frame_inputs(who, params, J, int(body["shapedirs"].shape[2]), dev)
+    flat = _frame_inputs(who, params, J, body, dev)
     if isinstance(pad, torch.Tensor):
-        pad_t = _need(who, pad, "pad", numel=1)
-        if pad_t.device != dev:
-            raise ValueError(f"{who}: pad must be on {dev}, got {pad_t.device}")
+        pad_t = _data(who, pad, "pad", numel=1, device=dev)
     else:
         pad_t = torch.full((1,), float(pad), dtype=torch.float32, device=dev)
     f32 = dict(dtype=torch.float32, device=dev)
@@ -233,8 +188,7 @@ def posed_vertices(body, params, pad=0.1, out=None, joints=False):
         if len(out) != len(shapes):
             raise ValueError(f"{who}: out must hold {len(shapes)} tensors")
         for t, s, name in zip(out, shapes, ("world_vertex", "world_bound", "joints")):
-            if _need(who, t, f"out {name}", s).device != dev:
-                raise ValueError(f"{who}: out {name} must be on {dev}, got {t.device}")
+            _data(who, t, f"out {name}", s, device=dev)
     ws = torch.empty(int(lib().moss_smpl_vertices_workspace_bytes(V, J)), dtype=torch.uint8, device=dev)
     _launch_vertices(body, V, J, par, flat["poses"], flat["shapes"], flat["R"], flat["Th"], pad_t, out[0], out[1],
                      out[2] if joints else None, ws)
@@ -270,15 +224,10 @@ def bound_masks(world_bound, K, RT, H, W, out=None):
         raise ValueError(f"{who}: K must be a (C,3,3) tensor")
     C = int(K.shape[0])
     dev = K.device
-    if dev.type != "cuda":
-        raise ValueError(f"{who} runs the HIP kernels of csrc/frame_bounds.hip: its tensors must be on a GPU (project_corners_numpy and "
-                         "bound_mask_numpy are the CPU form)")
-    _need(who, world_bound, "world_bound", (2, 3))
-    _need(who, K, "K", (C, 3, 3))
-    _need(who, RT, "RT", (C, 3, 4))
-    for name, t in (("world_bound", world_bound), ("RT", RT)):
-        if t.device != dev:
-            raise ValueError(f"{who}: {name} must be on {dev}, got {t.device}")
+    need_gpu(who, dev, "kernels of csrc/frame_bounds.hip", "project_corners_numpy and bound_mask_numpy are the CPU form")
+    _data(who, world_bound, "world_bound", (2, 3), device=dev)
+    _data(who, K, "K", (C, 3, 3))
+    _data(who, RT, "RT", (C, 3, 4), device=dev)
     ws = _mask_workspace(C, H, W, dev)
     specs = [((C, int(H), int(W)), torch.uint8), ((C, 5), torch.int32), ((C, 8, 2), torch.int32), ((C,), torch.int32)]
     if out is None:
@@ -288,8 +237,7 @@ def bound_masks(world_bound, K, RT, H, W, out=None):
         if len(out) != 4:
             raise ValueError(f"{who}: out must hold bound, rect, corners, flags")
         for t, (s, d), name in zip(out, specs, ("bound", "rect", "corners", "flags")):
-            if _need(who, t, f"out {name}", s, d).device != dev:
-                raise ValueError(f"{who}: out {name} must be on {dev}, got {t.device}")
+            _data(who, t, f"out {name}", s, d, device=dev)
     _launch_masks(world_bound, K, RT, H, W, *out, ws)
     return tuple(out)
 
@@ -333,7 +281,7 @@ class FrameBounds:
             self.smpl_param = {"poses": torch.zeros(1, 3 * self.J, **f32), "shapes": torch.zeros(1, nb, **f32), "R": torch.eye(3, **f32),
                                "Th": torch.zeros(1, 3, **f32)}
         else:                                                    # (the caller's static tensors are the inputs themselves)
-            _frame_inputs(who, smpl_param, self.J, B, dev)
+            _frame_inputs(who, smpl_param, self.J, body, dev)
             self.smpl_param = {k: smpl_param[k] for k in ("poses", "shapes", "R", "Th")}
         self.pad = torch.full((1,), float(pad), **f32)
         self.K, self.RT = _cameras_KRT(cameras, dev)
@@ -388,14 +336,13 @@ def dataset_regions(body, smpl_params_by_pose, cameras_by_pose, H, W, pad=0.1):
     if len(smpl_params_by_pose) != len(cameras_by_pose) or not len(smpl_params_by_pose):
         raise ValueError(f"{who}: one camera list per pose, at least one pose")
     f32 = dict(dtype=torch.float32, device=dev)
-    B = int(body["shapedirs"].shape[2])
     pad_t = torch.full((1,), float(pad), **f32)
     ws_v = torch.empty(int(lib().moss_smpl_vertices_workspace_bytes(V, J)), dtype=torch.uint8, device=dev)
     ws_m = {}
     regions, vertices, bounds, words = [], [], [], []
     for params, cameras in zip(smpl_params_by_pose, cameras_by_pose):
         frame = {k: torch.as_tensor(params[k]).detach().to(**f32).reshape(-1).contiguous() for k in ("poses", "shapes", "R", "Th")}
-        flat = _frame_inputs(who, frame, J, B, dev)
+        flat = _frame_inputs(who, frame, J, body, dev)
         K, RT = _cameras_KRT(cameras, dev)
         C = int(K.shape[0])
         if C not in ws_m:

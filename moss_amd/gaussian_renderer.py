@@ -210,6 +210,27 @@ class RenderOutput(dict):
         return self[key] if key in self else default
 
 
+def raw_pose_pipe(context):
+    """The ``pipe`` of a render that hands the op the raw parameters and the pose (``transforms`` / ``translation``), on ``context``."""
+    return SimpleNamespace(convert_SHs_python=False, compute_cov3D_python=False, debug=False, fused_activations=False,
+                           transforms_in_op=True, pose_in_op=True, raw_parameters_in_op=True, raster_context=context)
+
+
+def intrinsics_of(camera):
+    return (int(camera.image_height), int(camera.image_width), float(camera.FoVx), float(camera.FoVy))
+
+
+def static_view(intrinsics, tensors):
+    """``(camera, context, pipe)`` of a view that is rendered over and over, captured or not: a static camera of ``intrinsics``
+    (``intrinsics_of``) over the caller's ``world_view_transform`` / ``full_proj_transform`` / ``camera_center`` tensors, an
+    asynchronous ``RasterContext`` of its own (its first forward is synchronous and sizes the binning capacity) and its raw-pose pipe."""
+    from .diff_gaussian_rasterization import RasterContext
+    H, W, fovx, fovy = intrinsics
+    cx = RasterContext()
+    cx.set_async(True)
+    return SimpleNamespace(FoVx=fovx, FoVy=fovy, image_height=H, image_width=W, **tensors), cx, raw_pose_pipe(cx)
+
+
 def camera_view(cam, device):
     """Adapt a ``scenes.make_camera`` namespace to the attribute names render() reads from MOSS's Camera
     (scene/cameras.py:17-72)."""

@@ -27,30 +27,21 @@ import torch
 import torch.nn.functional as F
 from torch.utils.weak import WeakIdKeyDictionary
 
-from ._lib import (LbsBackwardArgs, LbsForwardArgs, SMPL_FRAME_SAVED_FLOATS_PER_JOINT, SmplFrameArgs, SmplFrameBackwardArgs, call, lib,
-                   ptr)
+from ._checks import MAX_JOINTS, body_arrays, frame_params, need, need_gpu, need_ids, no_grad
+from ._lib import (LbsBackwardArgs, LbsBackwardFrameArgs, LbsForwardArgs, SMPL_FRAME_SAVED_FLOATS_PER_JOINT, SmplFrameArgs,
+                   SmplFrameBackwardArgs, SmplFrameBackwardPoseArgs, call, lib, ptr)
 
 __all__ = ["lbs_deform", "smpl_joint_transforms", "vertex_offsets", "smpl_frame_fused", "coarse_deform_c2source", "deform_torch",
            "synthetic_body_model", "batch_rodrigues", "MAX_JOINTS", "SMPL_PARENTS"]
 
-MAX_JOINTS = 64
 SMPL_PARENTS = (-1, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9, 9, 12, 13, 14, 16, 17, 18, 19, 20, 21)
 
 
+def _c32(g):
+    return None if g is None else g.float().contiguous()
+
+
 # ---- the per-Gaussian op -------------------------------------------------------------------------------------------------------
-
-def _need(t, name, shape, dtype, device):
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"lbs_deform: {name} must be a tensor")
-    if t.dtype != dtype:
-        raise ValueError(f"lbs_deform: {name} must be {dtype}, got {t.dtype}")
-    if t.device != device:
-        raise ValueError(f"lbs_deform: {name} must be on {device}, got {t.device}")
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError(f"lbs_deform: {name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
-    if not t.is_contiguous():
-        raise ValueError(f"lbs_deform: {name} must be contiguous")
-
 
 def _fill_inputs(a, ids, W, L, A_big, A_obs, d, R, Th, x):
     a.P, a.J, a.V = int(ids.shape[0]), int(W.shape[1]), int(W.shape[0])
@@ -58,20 +49,53 @@ def _fill_inputs(a, ids, W, L, A_big, A_obs, d, R, Th, x):
     a.A_big, a.A_obs, a.d, a.R, a.Th, a.x = A_big.data_ptr(), A_obs.data_ptr(), d.data_ptr(), R.data_ptr(), Th.data_ptr(), ptr(x)
 
 
+def _launch_lbs_forward(ids, W, L, A_big, A_obs, d, R, Th, x, want_weights):
+    """``moss_lbs_deform_forward`` (no launch at P = 0): ``(T, t, p or None without x, w or None)``."""
+    P, J = int(ids.shape[0]), int(W.shape[1])
+    dev = W.device
+    T = torch.empty((P, 3, 3), dtype=torch.float32, device=dev)
+    t = torch.empty((P, 3), dtype=torch.float32, device=dev)
+    p = torch.empty((P, 3), dtype=torch.float32, device=dev) if x is not None else None
+    w = torch.empty((P, J), dtype=torch.float32, device=dev) if want_weights else None
+    if P > 0:
+        a = LbsForwardArgs()
+        _fill_inputs(a, ids, W, L, A_big, A_obs, d, R, Th, x)
+        a.T, a.t, a.p, a.w = T.data_ptr(), t.data_ptr(), ptr(p), ptr(w)
+        call("moss_lbs_deform_forward", dev, ctypes.byref(a))
+    return T, t, p, w
+
+
+def _launch_lbs_backward(inputs, gT, gt, gp, want):
+    """The gradients named in ``want`` (``g_L``, ``g_A_obs``, ``g_d``, ``g_x``, ``g_R``, ``g_Th``: fields of the args block) of the
+    forward's ``inputs``, as a dict.  With ``g_R`` among them ``moss_lbs_deform_backward_frame`` (the plain block plus ``g_R``,
+    ``g_Th``; launched whatever P is), else ``moss_lbs_deform_backward``: no launch when nothing is wanted or P = 0, and only then is
+    ``g_A_obs`` zeros."""
+    ids, W, x = inputs[0], inputs[1], inputs[8]
+    P, J = int(ids.shape[0]), int(W.shape[1])
+    dev = W.device
+    frame = "g_R" in want
+    launch = frame or (P > 0 and bool(want))
+    shapes = {"g_L": (P, J), "g_A_obs": (J, 4, 4), "g_d": (P, 3), "g_x": (P, 3), "g_R": (3, 3), "g_Th": (3,)}
+    g = {k: (torch.empty if launch or k != "g_A_obs" else torch.zeros)(shapes[k], dtype=torch.float32, device=dev) for k in want}
+    if launch:
+        a = (LbsBackwardFrameArgs if frame else LbsBackwardArgs)()
+        _fill_inputs(a, *inputs)
+        gT, gt, gp = _c32(gT), _c32(gt), (None if x is None else _c32(gp))
+        a.g_T, a.g_t, a.g_p = ptr(gT), ptr(gt), ptr(gp)
+        for k, t in g.items():
+            setattr(a, k, t.data_ptr())
+        if "g_A_obs" in g:
+            nbytes = int((lib().moss_lbs_frame_workspace_bytes if frame else lib().moss_lbs_workspace_bytes)(P, J))
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            a.workspace, a.workspace_bytes = (ws.data_ptr() if nbytes else None), nbytes
+        call("moss_lbs_deform_backward_frame" if frame else "moss_lbs_deform_backward", dev, ctypes.byref(a))
+    return g
+
+
 class _LbsDeform(torch.autograd.Function):
     @staticmethod
     def forward(ctx, ids, W, L, A_big, A_obs, d, R, Th, x, want_weights):
-        P, J = int(ids.shape[0]), int(W.shape[1])
-        dev = W.device
-        T = torch.empty((P, 3, 3), dtype=torch.float32, device=dev)
-        t = torch.empty((P, 3), dtype=torch.float32, device=dev)
-        p = torch.empty((P, 3), dtype=torch.float32, device=dev) if x is not None else None
-        w = torch.empty((P, J), dtype=torch.float32, device=dev) if want_weights else None
-        if P > 0:
-            a = LbsForwardArgs()
-            _fill_inputs(a, ids, W, L, A_big, A_obs, d, R, Th, x)
-            a.T, a.t, a.p, a.w = T.data_ptr(), t.data_ptr(), ptr(p), ptr(w)
-            call("moss_lbs_deform_forward", dev, ctypes.byref(a))
+        T, t, p, w = _launch_lbs_forward(ids, W, L, A_big, A_obs, d, R, Th, x, want_weights)
         if w is not None:
             ctx.mark_non_differentiable(w)
         ctx.save_for_backward(ids, W, L, A_big, A_obs, d, R, Th, x)
@@ -80,32 +104,13 @@ class _LbsDeform(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gT, gt, gp, _gw):
-        ids, W, L, A_big, A_obs, d, R, Th, x = ctx.saved_tensors
-        L = L if ctx.has_L else None
-        x = x if ctx.has_x else None
-        need = ctx.needs_input_grad
-        P, J = int(ids.shape[0]), int(W.shape[1])
-        dev = W.device
-        gL = torch.empty((P, J), dtype=torch.float32, device=dev) if (need[2] and L is not None) else None
-        gA = torch.zeros((J, 4, 4), dtype=torch.float32, device=dev) if (need[4] and P == 0) else (
-            torch.empty((J, 4, 4), dtype=torch.float32, device=dev) if need[4] else None)
-        gd = torch.empty((P, 3), dtype=torch.float32, device=dev) if need[5] else None
-        gx = torch.empty((P, 3), dtype=torch.float32, device=dev) if (need[8] and x is not None) else None
-        if P > 0 and any(g is not None for g in (gL, gA, gd, gx)):
-            a = LbsBackwardArgs()
-            _fill_inputs(a, ids, W, L, A_big, A_obs, d, R, Th, x)
-            gT = None if gT is None else gT.float().contiguous()
-            gt = None if gt is None else gt.float().contiguous()
-            gp = None if (gp is None or x is None) else gp.float().contiguous()
-            a.g_T, a.g_t, a.g_p = ptr(gT), ptr(gt), ptr(gp)
-            a.g_L, a.g_A_obs, a.g_d, a.g_x = ptr(gL), ptr(gA), ptr(gd), ptr(gx)
-            ws = None
-            if gA is not None:
-                nbytes = int(lib().moss_lbs_workspace_bytes(P, J))
-                ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-                a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
-            call("moss_lbs_deform_backward", dev, ctypes.byref(a))
-        return None, None, gL, None, gA, gd, None, None, gx, None
+        inputs = list(ctx.saved_tensors)
+        inputs[2] = inputs[2] if ctx.has_L else None
+        inputs[8] = inputs[8] if ctx.has_x else None
+        wanted = ctx.needs_input_grad
+        g = _launch_lbs_backward(inputs, gT, gt, gp, [k for k, yes in (("g_L", wanted[2] and ctx.has_L), ("g_A_obs", wanted[4]),
+                                                                       ("g_d", wanted[5]), ("g_x", wanted[8] and ctx.has_x)) if yes])
+        return None, None, g.get("g_L"), None, g.get("g_A_obs"), g.get("g_d"), None, None, g.get("g_x"), None
 
 
 def lbs_deform(vert_ids, W, lbs_offsets, A_big, A_obs, d, R, Th, x=None, want_weights=False):
@@ -120,32 +125,19 @@ def lbs_deform(vert_ids, W, lbs_offsets, A_big, A_obs, d, R, Th, x=None, want_we
     if not isinstance(W, torch.Tensor) or W.dim() != 2:
         raise ValueError("lbs_deform: W must be a (V, J) tensor")
     dev = W.device
-    if dev.type != "cuda":
-        raise ValueError("lbs_deform runs the HIP LBS kernels: its tensors must be on a GPU (deform_torch is the torch form)")
+    need_gpu("lbs_deform", dev, "LBS kernels", "deform_torch is the torch form")
     V, J = int(W.shape[0]), int(W.shape[1])
     if not 1 <= J <= MAX_JOINTS:
         raise ValueError(f"lbs_deform: J = {J} joints; the kernels take 1..{MAX_JOINTS}")
     if V < 1:
         raise ValueError("lbs_deform: W has no vertices")
-    if not isinstance(vert_ids, torch.Tensor) or vert_ids.dim() != 1:
-        raise ValueError("lbs_deform: vert_ids must be a (P,) tensor")
-    P = int(vert_ids.shape[0])
-    f32 = torch.float32
-    _need(vert_ids, "vert_ids", (P,), torch.int64, dev)
-    _need(W, "W", (V, J), f32, dev)
-    if lbs_offsets is not None:
-        _need(lbs_offsets, "lbs_offsets", (P, J), f32, dev)
-    _need(A_big, "A_big", (J, 4, 4), f32, dev)
-    _need(A_obs, "A_obs", (J, 4, 4), f32, dev)
-    _need(d, "d", (P, 3), f32, dev)
-    _need(R, "R", (3, 3), f32, dev)
-    _need(Th, "Th", (3,), f32, dev)
-    if x is not None:
-        _need(x, "x", (P, 3), f32, dev)
-    for name, c in (("W", W), ("A_big", A_big), ("R", R), ("Th", Th)):
-        if c.requires_grad:
-            raise ValueError(f"lbs_deform: {name} requires grad, but it is a constant of the deformation (no gradient is formed "
-                             "for it); detach it")
+    P = int(need_ids("lbs_deform", vert_ids, dev).shape[0])
+    for name, t, shape in (("W", W, (V, J)), ("lbs_offsets", lbs_offsets, (P, J)), ("A_big", A_big, (J, 4, 4)), ("A_obs", A_obs, (J, 4, 4)),
+                           ("d", d, (P, 3)), ("R", R, (3, 3)), ("Th", Th, (3,)), ("x", x, (P, 3))):
+        if t is not None or name not in ("lbs_offsets", "x"):
+            need("lbs_deform", t, name, shape, device=dev)
+    no_grad("lbs_deform", (("W", W), ("A_big", A_big), ("R", R), ("Th", Th)),
+            "it is a constant of the deformation (no gradient is formed for it)")
     return _LbsDeform.apply(vert_ids, W, lbs_offsets, A_big, A_obs, d, R, Th, x, bool(want_weights))
 
 
@@ -258,32 +250,65 @@ def vertex_offsets(body, params, t_params, rot_mats):
 
 # ---- the per-frame part as a fused op -------------------------------------------------------------------------------------------
 
+def _launch_smpl_frame_forward(cR, par, vt, sd, pd, jr, poses_big, shapes_big, poses, shapes, ids, want_saved):
+    """``moss_smpl_frame_forward``: ``(A_big, A_obs, d, rot_mats, saved or None)``."""
+    V, J, P = int(vt.shape[0]), int(jr.shape[0]), int(ids.shape[0])
+    dev = vt.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    A_big, A_obs = torch.empty((J, 4, 4), **f32), torch.empty((J, 4, 4), **f32)
+    d, rot = torch.empty((P, 3), **f32), torch.empty((J, 3, 3), **f32)
+    saved = torch.empty(SMPL_FRAME_SAVED_FLOATS_PER_JOINT * J, **f32) if want_saved else None
+    nbytes = int(lib().moss_smpl_frame_workspace_bytes(max(P, 1), V, J))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    a = SmplFrameArgs()
+    a.P, a.V, a.J = P, V, J
+    a.num_betas_big, a.num_betas, a.shapedirs_stride = int(shapes_big.shape[0]), int(shapes.shape[0]), int(sd.shape[2])
+    a.parents[:J] = par
+    a.v_template, a.shapedirs, a.posedirs, a.J_regressor = vt.data_ptr(), sd.data_ptr(), pd.data_ptr(), jr.data_ptr()
+    a.poses_big, a.shapes_big, a.poses, a.shapes = poses_big.data_ptr(), shapes_big.data_ptr(), poses.data_ptr(), shapes.data_ptr()
+    a.correct_Rs, a.vert_ids = ptr(cR), ids.data_ptr()
+    a.A_big, a.A_obs, a.d, a.rot_mats, a.saved = A_big.data_ptr(), A_obs.data_ptr(), d.data_ptr(), rot.data_ptr(), ptr(saved)
+    a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+    call("moss_smpl_frame_forward", dev, ctypes.byref(a))
+    return A_big, A_obs, d, rot, saved
+
+
+def _launch_smpl_frame_backward(par, V, pd, ids, saved, gA_obs, gd, poses=None, cR=None):
+    """Without ``poses`` ``moss_smpl_frame_backward`` (no launch at J = 1): ``g_correct_Rs`` (J-1,3,3).  With ``poses`` (and the
+    forward's ``cR``) ``moss_smpl_frame_backward_pose``, the same block plus ``poses``, ``correct_Rs``, ``g_poses``: ``g_poses`` (3J)."""
+    J, P = len(par), int(ids.shape[0])
+    dev = pd.device
+    pose = poses is not None
+    g = torch.empty(3 * J if pose else (J - 1, 3, 3), dtype=torch.float32, device=dev)
+    if pose or J > 1:
+        a = (SmplFrameBackwardPoseArgs if pose else SmplFrameBackwardArgs)()
+        a.P, a.V, a.J = P, V, J
+        a.parents[:J] = par
+        a.posedirs, a.vert_ids, a.saved = pd.data_ptr(), ids.data_ptr(), saved.data_ptr()
+        gA_obs, gd = _c32(gA_obs), (None if P == 0 else _c32(gd))
+        a.g_A_obs, a.g_d = ptr(gA_obs), ptr(gd)
+        if pose:
+            a.poses, a.correct_Rs, a.g_poses = poses.data_ptr(), ptr(cR), g.data_ptr()
+        else:
+            a.g_correct_Rs = g.data_ptr()
+        if pose or gd is not None:
+            nbytes = int(lib().moss_smpl_frame_workspace_bytes(max(P, 1), V, J))
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+        call("moss_smpl_frame_backward_pose" if pose else "moss_smpl_frame_backward", dev, ctypes.byref(a))
+    return g
+
+
 class _SmplFrame(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cR, par, vt, sd, pd, jr, poses_big, shapes_big, poses, shapes, ids):
-        V, J, P = int(vt.shape[0]), int(jr.shape[0]), int(ids.shape[0])
-        dev = vt.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        A_big, A_obs = torch.empty((J, 4, 4), **f32), torch.empty((J, 4, 4), **f32)
-        d, rot = torch.empty((P, 3), **f32), torch.empty((J, 3, 3), **f32)
-        saved = torch.empty(SMPL_FRAME_SAVED_FLOATS_PER_JOINT * J, **f32) if cR is not None else None
-        nbytes = int(lib().moss_smpl_frame_workspace_bytes(max(P, 1), V, J))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        a = SmplFrameArgs()
-        a.P, a.V, a.J = P, V, J
-        a.num_betas_big, a.num_betas, a.shapedirs_stride = int(shapes_big.shape[0]), int(shapes.shape[0]), int(sd.shape[2])
-        a.parents[:J] = par
-        a.v_template, a.shapedirs, a.posedirs, a.J_regressor = vt.data_ptr(), sd.data_ptr(), pd.data_ptr(), jr.data_ptr()
-        a.poses_big, a.shapes_big, a.poses, a.shapes = poses_big.data_ptr(), shapes_big.data_ptr(), poses.data_ptr(), shapes.data_ptr()
-        a.correct_Rs, a.vert_ids = ptr(cR), ids.data_ptr()
-        a.A_big, a.A_obs, a.d, a.rot_mats, a.saved = A_big.data_ptr(), A_obs.data_ptr(), d.data_ptr(), rot.data_ptr(), ptr(saved)
-        a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
-        call("moss_smpl_frame_forward", dev, ctypes.byref(a))
+        A_big, A_obs, d, rot, saved = _launch_smpl_frame_forward(cR, par, vt, sd, pd, jr, poses_big, shapes_big, poses, shapes, ids,
+                                                                 want_saved=cR is not None)
         ctx.mark_non_differentiable(A_big, rot)
         ctx.set_materialize_grads(False)                        # (no zero-fill launches for the cotangents nobody formed)
         if cR is not None:
             ctx.save_for_backward(pd, ids, saved)
-        ctx.par, ctx.V = par, V
+        ctx.par, ctx.V = par, int(vt.shape[0])
         return A_big, A_obs, d, rot
 
     @staticmethod
@@ -291,34 +316,7 @@ class _SmplFrame(torch.autograd.Function):
         if not ctx.needs_input_grad[0]:
             return (None,) * 11
         pd, ids, saved = ctx.saved_tensors
-        J, P, V = len(ctx.par), int(ids.shape[0]), ctx.V
-        dev = pd.device
-        g = torch.empty((J - 1, 3, 3), dtype=torch.float32, device=dev)
-        if J > 1:
-            a = SmplFrameBackwardArgs()
-            a.P, a.V, a.J = P, V, J
-            a.parents[:J] = ctx.par
-            a.posedirs, a.vert_ids, a.saved = pd.data_ptr(), ids.data_ptr(), saved.data_ptr()
-            gA_obs = None if gA_obs is None else gA_obs.float().contiguous()
-            gd = None if (gd is None or P == 0) else gd.float().contiguous()
-            a.g_A_obs, a.g_d, a.g_correct_Rs = ptr(gA_obs), ptr(gd), g.data_ptr()
-            if gd is not None:
-                nbytes = int(lib().moss_smpl_frame_workspace_bytes(P, V, J))
-                ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-                a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
-            call("moss_smpl_frame_backward", dev, ctypes.byref(a))
-        return (g,) + (None,) * 10
-
-
-def _need_frame(t, name, shape, dtype=torch.float32):
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"smpl_frame_fused: {name} must be a tensor")
-    if t.dtype != dtype:
-        raise ValueError(f"smpl_frame_fused: {name} must be {dtype}, got {t.dtype}")
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError(f"smpl_frame_fused: {name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
-    if not t.is_contiguous():
-        raise ValueError(f"smpl_frame_fused: {name} must be contiguous")
+        return (_launch_smpl_frame_backward(ctx.par, ctx.V, pd, ids, saved, gA_obs, gd),) + (None,) * 10
 
 
 def smpl_frame_fused(body, params, t_params, vert_ids, correct_Rs=None):
@@ -335,60 +333,19 @@ def smpl_frame_fused(body, params, t_params, vert_ids, correct_Rs=None):
     (J-1,3,3) or None.  All float32, contiguous, on one GPU; J = 1..64.  The gradient flows to ``correct_Rs`` (from ``A_obs`` and
     ``d``); ``A_big`` and ``rot_mats`` come out detached, and ``poses``, ``shapes`` and the body model are data: one that requires
     grad raises ValueError.  Ids outside [0, V) give NaN rows of ``d``.  There is no CPU path."""
-    for key in ("v_template", "shapedirs", "posedirs", "J_regressor", "weights", "kintree_table"):
-        if not isinstance(body.get(key), torch.Tensor):
-            raise ValueError(f"smpl_frame_fused: body['{key}'] must be a tensor")
-    vt, sd, pd, jr = body["v_template"], body["shapedirs"], body["posedirs"], body["J_regressor"]
-    J = int(body["weights"].shape[-1])
-    if not 1 <= J <= MAX_JOINTS:
-        raise ValueError(f"smpl_frame_fused: J = {J} joints; the kernels take 1..{MAX_JOINTS}")
-    if vt.dim() != 2 or vt.shape[0] < 1:
-        raise ValueError("smpl_frame_fused: v_template must be (V, 3) with V >= 1")
-    V = int(vt.shape[0])
-    if sd.dim() != 3:
-        raise ValueError("smpl_frame_fused: shapedirs must be (V, 3, B)")
-    if not isinstance(vert_ids, torch.Tensor) or vert_ids.dim() != 1:
-        raise ValueError("smpl_frame_fused: vert_ids must be a (P,) tensor")
-    for name, p in (("params", params), ("t_params", t_params)):
-        for key in ("poses", "shapes"):
-            if not isinstance(p.get(key), torch.Tensor):
-                raise ValueError(f"smpl_frame_fused: {name}['{key}'] must be a tensor")
-    data = {"v_template": vt, "shapedirs": sd, "posedirs": pd, "J_regressor": jr, "params['poses']": params["poses"],
-            "params['shapes']": params["shapes"], "t_params['poses']": t_params["poses"], "t_params['shapes']": t_params["shapes"]}
-    for name, t in data.items():
-        if t.requires_grad:
-            raise ValueError(f"smpl_frame_fused: {name} requires grad, but it is data of the deformation (no gradient is formed for "
-                             "it); detach it")
-    nb_big, nb = int(t_params["shapes"].numel()), int(params["shapes"].numel())
-    if max(nb_big, nb) > sd.shape[2]:
-        raise ValueError(f"smpl_frame_fused: {max(nb_big, nb)} shape coefficients, but shapedirs stores {sd.shape[2]}")
-    _need_frame(vt, "v_template", (V, 3))
-    _need_frame(sd, "shapedirs", (V, 3, sd.shape[2]))
-    _need_frame(pd, "posedirs", (V, 3, 9 * (J - 1)))
-    _need_frame(jr, "J_regressor", (J, V))
-    _need_frame(vert_ids, "vert_ids", (vert_ids.shape[0],), torch.int64)
-    flat = {}
-    for name, t, n in (("t_params['poses']", t_params["poses"], 3 * J), ("t_params['shapes']", t_params["shapes"], nb_big),
-                       ("params['poses']", params["poses"], 3 * J), ("params['shapes']", params["shapes"], nb)):
-        if t.numel() != n:
-            raise ValueError(f"smpl_frame_fused: {name} must have {n} elements, got {t.numel()}")
-        _need_frame(t, name, t.shape)
-        flat[name] = t.reshape(-1)
+    who, why = "smpl_frame_fused", "it is data of the deformation (no gradient is formed for it)"
+    # (the "must be on a GPU" refusal comes after the frame's own checks: CPU tensors with another fault are told that fault)
+    _, J, par, dev = body_arrays(who, body, why)
+    B = int(body["shapedirs"].shape[2])
+    big = frame_params(who, t_params, ("poses", "shapes"), J, B, dev, name="t_params")
+    frame = frame_params(who, params, ("poses", "shapes"), J, B, dev)
+    no_grad(who, [(f"{name}['{k}']", t) for name, p in (("params", frame), ("t_params", big)) for k, t in p.items()], why)
+    need_ids(who, vert_ids, dev)
     if correct_Rs is not None:
-        _need_frame(correct_Rs, "correct_Rs", (J - 1, 3, 3))
-    dev = vt.device
-    if dev.type != "cuda":
-        raise ValueError("smpl_frame_fused runs the HIP per-frame kernels: its tensors must be on a GPU (smpl_joint_transforms and "
-                         "vertex_offsets are the torch form)")
-    for name, t in list(data.items()) + [("vert_ids", vert_ids)] + ([] if correct_Rs is None else [("correct_Rs", correct_Rs)]):
-        if t.device != dev:
-            raise ValueError(f"smpl_frame_fused: {name} must be on {dev}, got {t.device}")
-    par = _parents(body, dev)[0]
-    if len(par) != J or any(not 0 <= par[j] < j for j in range(1, J)):
-        raise ValueError("smpl_frame_fused: kintree_table[0] must list J parents with 0 <= parent[j] < j for j >= 1")
-    par = [-1] + list(par[1:])                                 # (SMPL files store joint 0's parent as 2^32 - 1; it is not read)
-    return _SmplFrame.apply(correct_Rs, par, vt, sd, pd, jr, flat["t_params['poses']"], flat["t_params['shapes']"],
-                            flat["params['poses']"], flat["params['shapes']"], vert_ids)
+        need(who, correct_Rs, "correct_Rs", (J - 1, 3, 3), device=dev)
+    need_gpu(who, dev, "per-frame kernels", "smpl_joint_transforms and vertex_offsets are the torch form")
+    return _SmplFrame.apply(correct_Rs, par, body["v_template"], body["shapedirs"], body["posedirs"], body["J_regressor"], big["poses"],
+                            big["shapes"], frame["poses"], frame["shapes"], vert_ids)
 
 
 def coarse_deform_c2source(model, query_pts, params, t_params, t_vertices, lbs_weights=None, correct_Rs=None, return_transl=False,

@@ -23,7 +23,7 @@ import torch
 from . import dist as mdist
 from . import loss as mloss
 from .diff_gaussian_rasterization import RasterContext
-from .gaussian_renderer import render
+from .gaussian_renderer import raw_pose_pipe, render
 from .graphs import GraphedStep
 from .optim import FlatAdamW
 
@@ -84,9 +84,7 @@ class MultiViewStep:
             sink = lambda n, flat=flat, where=where: flat[where[n][0]:where[n][0] + where[n][1]].view(where[n][2])
             cx.set_grad_sink(means3D=lambda k=sink: k("_xyz"), sh=lambda k=sink: k("_features"), opacity=lambda k=sink: k("_opacity"),
                              scales=lambda k=sink: k("_scaling"), rotations=lambda k=sink: k("_rotation"))
-            pipe = SimpleNamespace(convert_SHs_python=False, compute_cov3D_python=False, debug=False, fused_activations=False,
-                                   transforms_in_op=True, pose_in_op=True, raw_parameters_in_op=True, raster_context=cx)
-            self.views.append(SimpleNamespace(alias=alias, ctx=cx, pipe=pipe, terms=flat[bucket.tail:bucket.tail + 4],
+            self.views.append(SimpleNamespace(alias=alias, ctx=cx, pipe=raw_pose_pipe(cx), terms=flat[bucket.tail:bucket.tail + 4],
                                               stream=None if b == 0 else torch.cuda.Stream(dev)))
         self.images = [None] * self.B
         self.graphed = None

@@ -297,7 +297,8 @@ class MossPlayer:
                 self.bounds = FrameBounds(pc.SMPL_NEUTRAL, pairs, int(view.image_height), int(view.image_width), pad=bounds_pad,
                                           smpl_param=self.smpl_param)
                 self._bounds_index = {self._camera_key(pair): i for i, pair in reversed(list(enumerate(pairs)))}
-        self._intrinsics = self._intrinsics_of(view)
+        from .gaussian_renderer import intrinsics_of
+        self._intrinsics = intrinsics_of(view)
         self.captures = self.poses = self.pose_replays = 0
         self._dropped = self._recaptured = 0
         self._captured = False
@@ -404,14 +405,10 @@ class MossPlayer:
         return {"transforms": t["transforms"][0], "translation": t["translation"][0], "Rs": t["Rs"], "lbs_weights": t["lbs_weights"][0]}
 
     # ---- the camera half -------------------------------------------------------------------------------------------------------------
-    @staticmethod
-    def _intrinsics_of(camera):
-        return (int(camera.image_height), int(camera.image_width), float(camera.FoVx), float(camera.FoVy))
-
     def _entry(self, intrinsics):
         """The render graph (before ``capture()``: the eager render) of these intrinsics at the model's size and degree, most recently
         used last; the least recently used one goes when there are more than ``max_render_graphs``."""
-        from .diff_gaussian_rasterization import RasterContext
+        from .gaussian_renderer import static_view
         H, W, fovx, fovy = intrinsics
         key = (H, W, math.tan(fovx * 0.5), math.tan(fovy * 0.5), self._signed[1], self._signed[0])
         e = self._renders.get(key)
@@ -423,11 +420,7 @@ class MossPlayer:
             if old.graphed is not None:
                 torch.cuda.synchronize(self.device)              # (its last replay has ended before its pool goes)
             self._retire(old)
-        cx = RasterContext()
-        cx.set_async(True)                                       # (the first forward is synchronous and sizes the binning capacity)
-        camera = SimpleNamespace(FoVx=fovx, FoVy=fovy, image_height=H, image_width=W, **self._camera)
-        pipe = SimpleNamespace(convert_SHs_python=False, compute_cov3D_python=False, debug=False, fused_activations=False,
-                               transforms_in_op=True, pose_in_op=True, raw_parameters_in_op=True, raster_context=cx)
+        camera, cx, pipe = static_view(intrinsics, self._camera)
         e = self._renders[key] = SimpleNamespace(camera=camera, context=cx, pipe=pipe, graphed=None, outputs=None)
         return e
 
@@ -465,7 +458,8 @@ class MossPlayer:
                     src = getattr(camera, k)
                     if src is not t:
                         t.copy_(src)
-                self._intrinsics = self._intrinsics_of(camera)
+                from .gaussian_renderer import intrinsics_of
+                self._intrinsics = intrinsics_of(camera)
         if not self._posed:
             raise RuntimeError("MossPlayer.render: nothing is posed yet (pose() or frame() first, or give transforms and translation)")
         e = self._entry(self._intrinsics)

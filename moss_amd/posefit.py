@@ -24,14 +24,13 @@ Everything here imports without a GPU.
 """
 from __future__ import annotations
 
-import ctypes
 from types import SimpleNamespace
 
 import torch
 
-from ._lib import (LbsBackwardFrameArgs, LbsForwardArgs, SMPL_FRAME_SAVED_FLOATS_PER_JOINT, SmplFrameArgs, SmplFrameBackwardPoseArgs,
-                   call, lib, ptr)
-from .lbs import MAX_JOINTS, _parents, batch_rodrigues, deform_torch, smpl_joint_transforms, vertex_offsets
+from ._checks import body_arrays, frame_params, need, need_ids, no_grad
+from .lbs import (_launch_lbs_backward, _launch_lbs_forward, _launch_smpl_frame_backward, _launch_smpl_frame_forward, batch_rodrigues,
+                  deform_torch, smpl_joint_transforms, vertex_offsets)
 
 __all__ = ["posed_frame", "posed_frame_torch", "PoseFitter", "rotation_to_axis_angle"]
 
@@ -39,35 +38,16 @@ __all__ = ["posed_frame", "posed_frame_torch", "PoseFitter", "rotation_to_axis_a
 # ---- the op ---------------------------------------------------------------------------------------------------------------------------
 
 class _PosedFrame(torch.autograd.Function):
+    """``lbs._SmplFrame`` followed by ``lbs._LbsDeform`` in one node, with the backwards that also form ``g_poses``, ``g_R``, ``g_Th``."""
+
     @staticmethod
     def forward(ctx, poses, R, Th, par, vt, sd, pd, jr, W, poses_big, shapes_big, shapes, ids, x, L, cR):
-        V, J, P = int(vt.shape[0]), int(jr.shape[0]), int(ids.shape[0])
-        dev = vt.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        A_big, A_obs = torch.empty((J, 4, 4), **f32), torch.empty((J, 4, 4), **f32)
-        d, rot = torch.empty((P, 3), **f32), torch.empty((J, 3, 3), **f32)
-        saved = torch.empty(SMPL_FRAME_SAVED_FLOATS_PER_JOINT * J, **f32)
-        nbytes = int(lib().moss_smpl_frame_workspace_bytes(max(P, 1), V, J))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        a = SmplFrameArgs()
-        a.P, a.V, a.J = P, V, J
-        a.num_betas_big, a.num_betas, a.shapedirs_stride = int(shapes_big.shape[0]), int(shapes.shape[0]), int(sd.shape[2])
-        a.parents[:J] = par
-        a.v_template, a.shapedirs, a.posedirs, a.J_regressor = vt.data_ptr(), sd.data_ptr(), pd.data_ptr(), jr.data_ptr()
-        a.poses_big, a.shapes_big, a.poses, a.shapes = poses_big.data_ptr(), shapes_big.data_ptr(), poses.data_ptr(), shapes.data_ptr()
-        a.correct_Rs, a.vert_ids = ptr(cR), ids.data_ptr()
-        a.A_big, a.A_obs, a.d, a.rot_mats, a.saved = A_big.data_ptr(), A_obs.data_ptr(), d.data_ptr(), rot.data_ptr(), saved.data_ptr()
-        a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
-        call("moss_smpl_frame_forward", dev, ctypes.byref(a))
-        T, t, p = torch.empty((P, 3, 3), **f32), torch.empty((P, 3), **f32), torch.empty((P, 3), **f32)
-        if P > 0:
-            b = LbsForwardArgs()
-            _fill_lbs(b, ids, W, L, A_big, A_obs, d, R, Th, x)
-            b.T, b.t, b.p = T.data_ptr(), t.data_ptr(), p.data_ptr()
-            call("moss_lbs_deform_forward", dev, ctypes.byref(b))
+        A_big, A_obs, d, _, saved = _launch_smpl_frame_forward(cR, par, vt, sd, pd, jr, poses_big, shapes_big, poses, shapes, ids,
+                                                               want_saved=True)
+        T, t, p, _ = _launch_lbs_forward(ids, W, L, A_big, A_obs, d, R, Th, x, want_weights=False)
         ctx.set_materialize_grads(False)                        # (no zero-fill launches for the cotangents nobody formed)
         ctx.save_for_backward(poses, R, Th, pd, W, ids, x, L, cR, A_big, A_obs, d, saved)
-        ctx.par, ctx.V, ctx.has_L, ctx.has_cR = par, V, L is not None, cR is not None
+        ctx.par, ctx.V, ctx.has_L, ctx.has_cR = par, int(vt.shape[0]), L is not None, cR is not None
         return T, t, p
 
     @staticmethod
@@ -75,49 +55,10 @@ class _PosedFrame(torch.autograd.Function):
         poses, R, Th, pd, W, ids, x, L, cR, A_big, A_obs, d, saved = ctx.saved_tensors
         L = L if ctx.has_L else None
         cR = cR if ctx.has_cR else None
-        J, P, V = len(ctx.par), int(ids.shape[0]), ctx.V
-        dev = pd.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        c32 = lambda g: None if g is None else g.float().contiguous()                   # noqa: E731
-        gA, gd = torch.empty((J, 4, 4), **f32), torch.empty((P, 3), **f32)
-        gR, gTh, gposes = torch.empty((3, 3), **f32), torch.empty(3, **f32), torch.empty(3 * J, **f32)
-        a = LbsBackwardFrameArgs()
-        _fill_lbs(a, ids, W, L, A_big, A_obs, d, R, Th, x)
-        gT, gt, gp = c32(gT), c32(gt), c32(gp)
-        a.g_T, a.g_t, a.g_p = ptr(gT), ptr(gt), ptr(gp)
-        a.g_A_obs, a.g_d, a.g_R, a.g_Th = gA.data_ptr(), gd.data_ptr(), gR.data_ptr(), gTh.data_ptr()
-        nbytes = int(lib().moss_lbs_frame_workspace_bytes(P, J))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        a.workspace, a.workspace_bytes = ptr(ws) if nbytes else None, nbytes
-        call("moss_lbs_deform_backward_frame", dev, ctypes.byref(a))
-        b = SmplFrameBackwardPoseArgs()
-        b.P, b.V, b.J = P, V, J
-        b.parents[:J] = ctx.par
-        b.posedirs, b.vert_ids, b.saved = pd.data_ptr(), ids.data_ptr(), saved.data_ptr()
-        b.g_A_obs, b.g_d = (gA.data_ptr(), gd.data_ptr()) if P > 0 else (None, None)     # (P = 0: g_A_obs is not written, and is zero)
-        b.poses, b.correct_Rs, b.g_poses = poses.data_ptr(), ptr(cR), gposes.data_ptr()
-        nbytes2 = int(lib().moss_smpl_frame_workspace_bytes(max(P, 1), V, J))
-        ws2 = torch.empty(nbytes2, dtype=torch.uint8, device=dev)
-        b.workspace, b.workspace_bytes = ws2.data_ptr(), nbytes2
-        call("moss_smpl_frame_backward_pose", dev, ctypes.byref(b))
-        return (gposes.reshape(poses.shape), gR, gTh) + (None,) * 13
-
-
-def _fill_lbs(a, ids, W, L, A_big, A_obs, d, R, Th, x):
-    a.P, a.J, a.V = int(ids.shape[0]), int(W.shape[1]), int(W.shape[0])
-    a.vert_ids, a.weights, a.lbs_offsets = ids.data_ptr(), W.data_ptr(), ptr(L)
-    a.A_big, a.A_obs, a.d, a.R, a.Th, a.x = A_big.data_ptr(), A_obs.data_ptr(), d.data_ptr(), R.data_ptr(), Th.data_ptr(), x.data_ptr()
-
-
-def _need(t, name, shape, dtype=torch.float32):
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"posed_frame: {name} must be a tensor")
-    if t.dtype != dtype:
-        raise ValueError(f"posed_frame: {name} must be {dtype}, got {t.dtype}")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError(f"posed_frame: {name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
-    if not t.is_contiguous():
-        raise ValueError(f"posed_frame: {name} must be contiguous")
+        g = _launch_lbs_backward([ids, W, L, A_big, A_obs, d, R, Th, x], gT, gt, gp, ("g_A_obs", "g_d", "g_R", "g_Th"))
+        gA, gd = (g["g_A_obs"], g["g_d"]) if int(ids.shape[0]) > 0 else (None, None)     # (P = 0: g_A_obs is not written, and is zero)
+        gposes = _launch_smpl_frame_backward(ctx.par, ctx.V, pd, ids, saved, gA, gd, poses=poses, cR=cR)
+        return (gposes.reshape(poses.shape), g["g_R"], g["g_Th"]) + (None,) * 13
 
 
 def posed_frame(body, W, params, t_params, vert_ids, x, lbs_offsets=None, correct_Rs=None):
@@ -136,71 +77,21 @@ def posed_frame(body, W, params, t_params, vert_ids, x, lbs_offsets=None, correc
     and one that requires grad raises ``ValueError`` naming it.  The gradient of ``R`` is that of ``M = R O3`` as the header defines
     the op (the reference writes ``torch.inverse(R)`` of the transpose; the two agree on rotations).  A Gaussian with an id outside
     [0, V) gives NaN rows and adds nothing to the three gradients.  There is no CPU path (:func:`posed_frame_torch` is the torch form)."""
-    for key in ("v_template", "shapedirs", "posedirs", "J_regressor", "kintree_table"):
-        if not isinstance(body.get(key), torch.Tensor):
-            raise ValueError(f"posed_frame: body['{key}'] must be a tensor")
-    if not isinstance(W, torch.Tensor) or W.dim() != 2:
-        raise ValueError("posed_frame: W must be a (V, J) tensor")
-    vt, sd, pd, jr = body["v_template"], body["shapedirs"], body["posedirs"], body["J_regressor"]
-    V, J = int(W.shape[0]), int(W.shape[1])
-    if not 1 <= J <= MAX_JOINTS:
-        raise ValueError(f"posed_frame: J = {J} joints; the kernels take 1..{MAX_JOINTS}")
-    if not isinstance(vert_ids, torch.Tensor) or vert_ids.dim() != 1:
-        raise ValueError("posed_frame: vert_ids must be a (P,) tensor")
-    P = int(vert_ids.shape[0])
-    for name, p, keys in (("params", params, ("poses", "shapes", "R", "Th")), ("t_params", t_params, ("poses", "shapes"))):
-        for key in keys:
-            if not isinstance(p.get(key), torch.Tensor):
-                raise ValueError(f"posed_frame: {name}['{key}'] must be a tensor")
-    data = {"v_template": vt, "shapedirs": sd, "posedirs": pd, "J_regressor": jr, "W": W, "params['shapes']": params["shapes"],
-            "t_params['poses']": t_params["poses"], "t_params['shapes']": t_params["shapes"], "x": x}
-    if lbs_offsets is not None:
-        data["lbs_offsets"] = lbs_offsets
-    if correct_Rs is not None:
-        data["correct_Rs"] = correct_Rs
-    for name, t in data.items():
-        if isinstance(t, torch.Tensor) and t.requires_grad:
-            raise ValueError(f"posed_frame: {name} requires grad, but it is data of the fit (the avatar is frozen: gradients go to "
-                             "params['poses'], params['R'] and params['Th'] only); detach it")
-    dev = vt.device
-    if dev.type != "cuda":
-        raise ValueError("posed_frame runs the HIP deformation kernels: its tensors must be on a GPU (posed_frame_torch is the torch form)")
-    if sd.dim() != 3:
-        raise ValueError("posed_frame: shapedirs must be (V, 3, B)")
-    nb_big, nb = int(t_params["shapes"].numel()), int(params["shapes"].numel())
-    if max(nb_big, nb) > sd.shape[2]:
-        raise ValueError(f"posed_frame: {max(nb_big, nb)} shape coefficients, but shapedirs stores {sd.shape[2]}")
-    _need(vt, "v_template", (V, 3))
-    _need(sd, "shapedirs", (V, 3, sd.shape[2]))
-    _need(pd, "posedirs", (V, 3, 9 * (J - 1)))
-    _need(jr, "J_regressor", (J, V))
-    _need(W, "W", (V, J))
-    _need(vert_ids, "vert_ids", (P,), torch.int64)
-    _need(x, "x", (P, 3))
-    if lbs_offsets is not None:
-        _need(lbs_offsets, "lbs_offsets", (P, J))
-    if correct_Rs is not None:
-        _need(correct_Rs, "correct_Rs", (J - 1, 3, 3))
-    flat = {}
-    for name, t, n in (("t_params['poses']", t_params["poses"], 3 * J), ("t_params['shapes']", t_params["shapes"], nb_big),
-                       ("params['poses']", params["poses"], 3 * J), ("params['shapes']", params["shapes"], nb),
-                       ("params['R']", params["R"], 9), ("params['Th']", params["Th"], 3)):
-        if t.numel() != n:
-            raise ValueError(f"posed_frame: {name} must have {n} elements, got {t.numel()}")
-        _need(t, name, None)
-        flat[name] = t.reshape(-1)
-    everything = list(data.items()) + [("vert_ids", vert_ids), ("params['poses']", params["poses"]), ("params['R']", params["R"]),
-                                       ("params['Th']", params["Th"])]
-    for name, t in everything:
-        if t.device != dev:
-            raise ValueError(f"posed_frame: {name} must be on {dev}, got {t.device}")
-    par = _parents(body, dev)[0]
-    if len(par) != J or any(not 0 <= par[j] < j for j in range(1, J)):
-        raise ValueError("posed_frame: kintree_table[0] must list J parents with 0 <= parent[j] < j for j >= 1")
-    par = [-1] + list(par[1:])
-    return _PosedFrame.apply(flat["params['poses']"], flat["params['R']"].reshape(3, 3), flat["params['Th']"], par, vt, sd, pd, jr, W,
-                             flat["t_params['poses']"], flat["t_params['shapes']"], flat["params['shapes']"], vert_ids, x, lbs_offsets,
-                             correct_Rs)
+    who = "posed_frame"
+    why = "it is data of the fit (the avatar is frozen: gradients go to params['poses'], params['R'] and params['Th'] only)"
+    no_grad(who, {"params['shapes']": params.get("shapes"), "t_params['poses']": t_params.get("poses"),
+                  "t_params['shapes']": t_params.get("shapes"), "x": x, "lbs_offsets": lbs_offsets, "correct_Rs": correct_Rs}, why)
+    V, J, par, dev = body_arrays(who, body, why, "deformation kernels", "posed_frame_torch is the torch form", weights=W)
+    B = int(body["shapedirs"].shape[2])
+    big = frame_params(who, t_params, ("poses", "shapes"), J, B, dev, name="t_params")
+    frame = frame_params(who, params, ("poses", "shapes", "R", "Th"), J, B, dev)
+    P = int(need_ids(who, vert_ids, dev).shape[0])
+    for name, t, shape in (("x", x, (P, 3)), ("lbs_offsets", lbs_offsets, (P, J)), ("correct_Rs", correct_Rs, (J - 1, 3, 3))):
+        if t is not None or name == "x":
+            need(who, t, name, shape, device=dev)
+    return _PosedFrame.apply(frame["poses"], frame["R"].reshape(3, 3), frame["Th"], par, body["v_template"], body["shapedirs"],
+                             body["posedirs"], body["J_regressor"], W, big["poses"], big["shapes"], frame["shapes"], vert_ids, x,
+                             lbs_offsets, correct_Rs)
 
 
 def posed_frame_torch(body, W, params, t_params, vert_ids, x, lbs_offsets=None, correct_Rs=None):
@@ -321,28 +212,19 @@ class PoseFitter:
         self.captures = 0
 
     # ---- static inputs ----------------------------------------------------------------------------------------------------------------
-    @staticmethod
-    def _intrinsics_of(camera):
-        return (int(camera.image_height), int(camera.image_width), float(camera.FoVx), float(camera.FoVy))
-
     def _load_views(self, cameras, gt_images, regions):
-        from .diff_gaussian_rasterization import RasterContext
+        from .gaussian_renderer import intrinsics_of, static_view
         from .loss import ViewRegion
-        key = tuple(self._intrinsics_of(c) for c in cameras) + tuple(r is not None for r in regions) \
+        key = tuple(intrinsics_of(c) for c in cameras) + tuple(r is not None for r in regions) \
             + tuple(isinstance(g, (tuple, list)) for g in gt_images)
         if key != self._key:
             if self._graphed is not None:
                 torch.cuda.synchronize(self.device)
             self._graphed, self._views, self._key = None, [], key
             for cam, region in zip(cameras, regions):
-                H, W, fovx, fovy = self._intrinsics_of(cam)
-                cx = RasterContext()
-                cx.set_async(True)                               # (its first forward is synchronous and sizes the binning capacity)
-                camera = SimpleNamespace(FoVx=fovx, FoVy=fovy, image_height=H, image_width=W,
-                                         **{k: torch.empty_like(getattr(cam, k)) for k in
-                                            ("world_view_transform", "full_proj_transform", "camera_center")})
-                pipe = SimpleNamespace(convert_SHs_python=False, compute_cov3D_python=False, debug=False, fused_activations=False,
-                                       transforms_in_op=True, pose_in_op=True, raw_parameters_in_op=True, raster_context=cx)
+                H, W = intrinsics_of(cam)[:2]
+                camera, cx, pipe = static_view(intrinsics_of(cam), {k: torch.empty_like(getattr(cam, k)) for k in
+                                                                    ("world_view_transform", "full_proj_transform", "camera_center")})
                 static_region = None
                 if region is not None:
                     static_region = ViewRegion.from_device(torch.empty_like(region.bound), torch.empty_like(region.rect))

@@ -144,6 +144,28 @@ def _lib():
     return m.lib()
 
 
+def c_layout(tmp_path, cname, fields, cc="gcc", extra=()):
+    """``[sizeof(cname), offsetof(cname, f) for f in fields] + extra`` as a host C compile of include/moss_raster.h sees them.  A field
+    that ctypes spells with a trailing underscore because the name is a Python keyword (``in_``) is the C field without it; ``extra``:
+    further integer expressions (``"MOSS_ROWS_MAX_TENSORS"``, ``"offsetof(moss_rows_tensor, width)"``); ``cc``: a compiler command."""
+    import os
+    import subprocess
+    include = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
+    exprs = ["sizeof(%s)" % cname] + ["offsetof(%s, %s)" % (cname, f.rstrip("_")) for f in fields] + list(extra)
+    src = tmp_path / ("layout_%s.c" % cname)
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "moss_raster.h"\nint main(void) {\n'
+                   + "".join('    printf(" %%zu", (size_t)(%s));\n' % e for e in exprs) + "    return 0;\n}\n")
+    exe = tmp_path / ("layout_%s" % cname)
+    subprocess.run(cc.split() + ["-I", include, str(src), "-o", str(exe)], check=True)
+    return [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+
+
+def ctypes_layout(cls):
+    """``[sizeof, every field's offset]`` of a ``ctypes.Structure``: what :func:`c_layout` of its C struct and fields must equal."""
+    import ctypes
+    return [ctypes.sizeof(cls)] + [getattr(cls, f[0]).offset for f in cls._fields_]
+
+
 def image_grads(H, W, seed=5, zero_depth=False):
     g = torch.Generator().manual_seed(seed)
     dc = torch.randn(3, H, W, generator=g)

@@ -6,7 +6,6 @@ The vertex bar is the project's for this chain (tests/test_lbs_cpu.py): 64 eps32
 import ctypes
 import os
 import re
-import subprocess
 import sys
 import threading
 
@@ -16,6 +15,7 @@ import torch
 
 from moss_amd import bounds as mb
 from moss_amd.loss import ViewRegion, bounding_rect
+from tests.helpers import c_layout, ctypes_layout
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
@@ -188,15 +188,7 @@ def test_symbols_exported_and_declared(hip_lib):
 def test_ctypes_blocks_match_the_c_layout(tmp_path, cname, pyname):
     from moss_amd import _lib
     cls = getattr(_lib, pyname)
-    fields = [f[0] for f in cls._fields_]
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "moss_raster.h"\nint main(void) {\n'
-                   '    printf("%%zu", sizeof(%s));\n' % cname
-                   + "".join('    printf(" %%zu", offsetof(%s, %s));\n' % (cname, f) for f in fields) + "    return 0;\n}\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    assert got == [ctypes.sizeof(cls)] + [getattr(cls, f).offset for f in fields]
+    assert c_layout(tmp_path, cname, [f[0] for f in cls._fields_]) == ctypes_layout(cls)
 
 
 def test_workspace_sizes_are_monotonic_host_functions(hip_lib):

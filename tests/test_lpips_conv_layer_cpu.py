@@ -13,12 +13,12 @@ K = 8 (the project's parity factor: tests/test_gpu_pose.py, tests/test_gpu_lpips
 import ctypes
 import functools
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+from tests.helpers import c_layout, ctypes_layout
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 K = 8.0
@@ -197,15 +197,7 @@ def test_argument_block_mirrors_the_header(tmp_path):
     fields = [f[0] for f in cls._fields_]
     assert fields == ["in_", "weights", "bias", "out", "mask_in", "mask_out", "nimg", "H", "W", "cin", "cout", "mode", "shape", "bf16",
                       "rect", "cap_H", "cap_W", "level"]
-    cname = "moss_lpips_conv3x3_args"
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "moss_raster.h"\nint main(void) {\n'
-                   '    printf("%%zu", sizeof(%s));\n' % cname
-                   + "".join('    printf(" %%zu", offsetof(%s, %s));\n' % (cname, f.rstrip("_")) for f in fields) + "    return 0;\n}\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    assert got == [ctypes.sizeof(cls)] + [getattr(cls, f).offset for f in fields]
+    assert c_layout(tmp_path, "moss_lpips_conv3x3_args", fields) == ctypes_layout(cls)
     z = cls()
     assert z.shape == 0 and z.cap_H == 0 and z.cap_W == 0                 # zero-initialised: the launcher's choice, the static call
 

@@ -1,14 +1,13 @@
 """The LPIPS call whose crop size is read from the device (``capacity=``; ``cap_H``, ``cap_W`` of the C ABI), without a GPU: the ctypes
 mirrors of the two argument blocks against the header as a C compiler lays them out, ``crop_capacity``, and the host-side refusals
 of ``lpips_vgg_roi_fused(capacity=)``."""
-import ctypes
 import os
-import subprocess
 
 import pytest
 import torch
 
 from moss_amd import lpips as mlp
+from tests.helpers import c_layout, ctypes_layout
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -28,14 +27,7 @@ def test_argument_blocks_mirror_the_header(tmp_path, cname, pyname):
     cls = getattr(L, pyname)
     fields = [f[0] for f in cls._fields_]
     assert fields[-2:] == ["cap_H", "cap_W"] and fields[-3] == "workspace_bytes"
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "moss_raster.h"\nint main(void) {\n'
-                   '    printf("%%zu", sizeof(%s));\n' % cname
-                   + "".join('    printf(" %%zu", offsetof(%s, %s));\n' % (cname, f) for f in fields) + "    return 0;\n}\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    assert got == [ctypes.sizeof(cls)] + [getattr(cls, f).offset for f in fields]
+    assert c_layout(tmp_path, cname, fields) == ctypes_layout(cls)
     text = open(os.path.join(ROOT, "include", "moss_raster.h")).read()
     assert "#define MOSS_ABI_VERSION 7" in text                          # the version did not move
     assert cls().cap_H == 0 and cls().cap_W == 0                          # a caller who sets neither makes the static call

@@ -1,17 +1,16 @@
 """CPU side of the evaluation metrics (moss_amd.metrics, C ABI moss_eval_metrics): the torch composition against the reference's own
 numbers (tests/golden/eval_metrics.npz, tests/golden/make_golden_eval.py), the C declarations and their ctypes mirror, and the MOSS-side
 diff that uses them."""
-import ctypes
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 from tests.test_host_cpu import _apply_exactly, _diff_hunks
+from tests.helpers import c_layout, ctypes_layout
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "eval_metrics.npz")
@@ -126,14 +125,7 @@ def test_ctypes_struct_matches_the_c_layout(tmp_path):
     """moss_amd._lib.EvalMetricsArgs mirrors moss_eval_metrics_args field by field (compiled against the header with the host compiler)."""
     from moss_amd._lib import EvalMetricsArgs
     fields = [f[0] for f in EvalMetricsArgs._fields_]
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "moss_raster.h"\nint main(void) {\n'
-                   '    printf("%zu", sizeof(moss_eval_metrics_args));\n'
-                   + "".join('    printf(" %%zu", offsetof(moss_eval_metrics_args, %s));\n' % f for f in fields) + "    return 0;\n}\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    assert got == [ctypes.sizeof(EvalMetricsArgs)] + [getattr(EvalMetricsArgs, f).offset for f in fields]
+    assert c_layout(tmp_path, "moss_eval_metrics_args", fields) == ctypes_layout(EvalMetricsArgs)
 
 
 def test_report_refuses_a_cpu_device(hip_lib):

@@ -4,7 +4,6 @@ central finite differences, and the refusals of the Python surface (there is no 
 import ctypes
 import os
 import re
-import subprocess
 import threading
 from types import SimpleNamespace
 
@@ -14,6 +13,7 @@ import torch
 
 from moss_amd import lbs as mlbs
 from moss_amd import posefit
+from tests.helpers import c_layout, ctypes_layout
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("moss_lbs_deform_backward_frame", "moss_lbs_frame_workspace_bytes", "moss_smpl_frame_backward_pose")
@@ -46,15 +46,7 @@ def test_ctypes_blocks_match_the_c_layout(tmp_path, cname, pyname):
     """The ctypes mirrors have the header's size and field offsets (compiled against the header with the host compiler)."""
     from moss_amd import _lib
     cls = getattr(_lib, pyname)
-    fields = [f[0] for f in cls._fields_]
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "moss_raster.h"\nint main(void) {\n'
-                   '    printf("%%zu", sizeof(%s));\n' % cname
-                   + "".join('    printf(" %%zu", offsetof(%s, %s));\n' % (cname, f) for f in fields) + "    return 0;\n}\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    assert got == [ctypes.sizeof(cls)] + [getattr(cls, f).offset for f in fields]
+    assert c_layout(tmp_path, cname, [f[0] for f in cls._fields_]) == ctypes_layout(cls)
 
 
 def test_c_abi_refuses_bad_arguments_with_its_name(hip_lib):

@@ -5,13 +5,12 @@ offsets, and the Parameter objects.  The kernels themselves: tests/test_gpu_rows
 import ctypes
 import os
 import re
-import subprocess
-import tempfile
 
 import pytest
 import torch
 
 from tests.test_surgery_cpu import _fill_moments, _model, _new_rows, _scripted_event
+from tests.helpers import c_layout
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "moss_raster.h")
@@ -29,19 +28,14 @@ def test_library_exports_the_row_entry_points_and_the_header_declares_them(hip_l
     assert hip_lib.moss_rows_map_workspace_bytes(257) == 8 and hip_lib.moss_rows_map_workspace_bytes(65537) == 4 * 257
 
 
-def test_ctypes_structs_have_the_headers_sizes():
+def test_ctypes_structs_have_the_headers_sizes(tmp_path):
     """A C program that includes the header prints sizeof / offsetof; the ctypes mirrors must agree."""
     from moss_amd import _lib
-    cc = os.environ.get("CXX", "g++")                        # (the compiler the build uses for the torch extension)
-    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "moss_raster.h"\nint main(void) { printf("%zu %zu %zu %zu %zu %d\\n", '
-           'sizeof(moss_rows_tensor), sizeof(moss_rows_relayout_args), offsetof(moss_rows_relayout_args, tensors), '
-           'offsetof(moss_rows_relayout_args, map), offsetof(moss_rows_tensor, width), MOSS_ROWS_MAX_TENSORS); return 0; }\n')
-    with tempfile.TemporaryDirectory() as d:
-        open(os.path.join(d, "s.c"), "w").write(src)
-        subprocess.run([cc, "-x", "c++", "-I", os.path.join(ROOT, "include"), os.path.join(d, "s.c"), "-o", os.path.join(d, "s")], check=True)
-        got = [int(x) for x in subprocess.run([os.path.join(d, "s")], capture_output=True, text=True, check=True).stdout.split()]
-    assert got == [ctypes.sizeof(_lib.RowsTensor), ctypes.sizeof(_lib.RowsRelayoutArgs), _lib.RowsRelayoutArgs.tensors.offset,
-                   _lib.RowsRelayoutArgs.map.offset, _lib.RowsTensor.width.offset, _lib.ROWS_MAX_TENSORS]
+    cc = os.environ.get("CXX", "g++") + " -x c++"            # (the compiler the build uses for the torch extension)
+    got = c_layout(tmp_path, "moss_rows_relayout_args", ["tensors", "map"], cc=cc,
+                   extra=["sizeof(moss_rows_tensor)", "offsetof(moss_rows_tensor, width)", "MOSS_ROWS_MAX_TENSORS"])
+    assert got == [ctypes.sizeof(_lib.RowsRelayoutArgs), _lib.RowsRelayoutArgs.tensors.offset, _lib.RowsRelayoutArgs.map.offset,
+                   ctypes.sizeof(_lib.RowsTensor), _lib.RowsTensor.width.offset, _lib.ROWS_MAX_TENSORS]
 
 
 def _appended(pc, d):

@@ -5,12 +5,12 @@ import ctypes
 import inspect
 import os
 import re
-import subprocess
 
 import pytest
 import torch
 
 from moss_amd import lbs as mlbs
+from tests.helpers import c_layout, ctypes_layout
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("moss_smpl_frame_forward", "moss_smpl_frame_backward", "moss_smpl_frame_workspace_bytes")
@@ -40,15 +40,7 @@ def test_ctypes_blocks_match_the_c_layout(tmp_path, cname, pyname):
     """The ctypes mirrors have the header's size and field offsets (compiled against the header with the host compiler)."""
     from moss_amd import _lib
     cls = getattr(_lib, pyname)
-    fields = [f[0] for f in cls._fields_]
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "moss_raster.h"\nint main(void) {\n'
-                   '    printf("%%zu", sizeof(%s));\n' % cname
-                   + "".join('    printf(" %%zu", offsetof(%s, %s));\n' % (cname, f) for f in fields) + "    return 0;\n}\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    assert got == [ctypes.sizeof(cls)] + [getattr(cls, f).offset for f in fields]
+    assert c_layout(tmp_path, cname, [f[0] for f in cls._fields_]) == ctypes_layout(cls)
 
 
 def test_workspace_bytes_is_a_monotonic_host_function(hip_lib):

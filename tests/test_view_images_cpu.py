@@ -6,7 +6,6 @@ import ctypes
 import math
 import os
 import re
-import subprocess
 import threading
 
 import numpy as np
@@ -14,6 +13,7 @@ import pytest
 import torch
 
 from tests import view_images_oracle as vo
+from tests.helpers import c_layout, ctypes_layout
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("moss_view_images_prepare", "moss_view_images_load")
@@ -45,15 +45,7 @@ def test_symbols_exported_and_declared(hip_lib):
 def test_ctypes_blocks_match_the_c_layout(tmp_path, cname, pyname):
     from moss_amd import _lib
     cls = getattr(_lib, pyname)
-    fields = [f[0] for f in cls._fields_]
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "moss_raster.h"\nint main(void) {\n'
-                   '    printf("%%zu", sizeof(%s));\n' % cname
-                   + "".join('    printf(" %%zu", offsetof(%s, %s));\n' % (cname, f) for f in fields) + "    return 0;\n}\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    assert got == [ctypes.sizeof(cls)] + [getattr(cls, f).offset for f in fields]
+    assert c_layout(tmp_path, cname, [f[0] for f in cls._fields_]) == ctypes_layout(cls)
 
 
 def test_c_abi_refuses_bad_arguments(hip_lib):
