@@ -3,7 +3,7 @@
 // mask with its bounding rectangle (include/moss_raster.h moss_smpl_vertices / moss_bound_mask; the formulas are restated there).
 //
 // moss_smpl_vertices, 3 launches:
-//   posed          a grid over ranges of FB_VPB vertices (the form of smpl_frame.hip's offsets kernel: posedirs is the one large
+//   posed          a grid over ranges of SMPL_VPB vertices (the form of smpl_frame.hip's offsets kernel: posedirs is the one large
 //                  stream, 12 (J - 1) 9 V bytes, read once; one wave per 4 rows, lanes over the feature, a fixed butterfly).  Every
 //                  workgroup recomputes the J rotations in LDS, forms f = rot[1:] - I, its rows of v_posed = v_template + shapedirs beta
 //                  + posedirs f (kept in float64 in the workspace) and its share of J_regressor v_shaped.
@@ -28,17 +28,12 @@ namespace moss {
 
 namespace {
 
-constexpr int FB_MAX_J = MOSS_SMPL_FRAME_MAX_JOINTS;
-constexpr int FB_MAX_F = 9 * (FB_MAX_J - 1);
 constexpr int FB_BLOCK = 256;
-constexpr int FB_VPB = 16;                // vertices per workgroup of the posed kernel
 constexpr int FB_SKIN_BLOCK = 1024;
 constexpr int FB_SKIN_VPB = 256;          // vertices per workgroup of the skin kernel: four lanes each (three rows, one idle)
 constexpr int FB_TILE_W = 64, FB_TILE_H = 8;
 constexpr int FB_ROWS = FB_TILE_H / (FB_BLOCK / 64);    // rows of a tile per wave
 constexpr int FB_CLAMP = 1 << 20;
-
-struct FbParents { int32_t p[FB_MAX_J]; };
 
 struct FbIn {
     int V, J, nb, sd_stride;
@@ -53,120 +48,60 @@ struct FbIn {
     const float* Th;
 };
 
-// v_posed rows (float64) and regressor shares of vertices [FB_VPB b, FB_VPB (b + 1)); partials [workgroup][J][3]
+// v_posed rows (float64) and regressor shares of vertices [SMPL_VPB b, SMPL_VPB (b + 1)); partials [workgroup][J][3]
 __global__ void __launch_bounds__(FB_BLOCK)
 frame_bounds_posed_kernel(FbIn a, double* __restrict__ vposed, double* __restrict__ partials)
 {
-    __shared__ float s_rot[FB_MAX_J * 9];
-    __shared__ float s_f[FB_MAX_F + 1];
-    __shared__ double s_vs[FB_VPB * 3];                     // the shaped template
+    __shared__ float s_rot[SMPL_MAX_J * 9];
+    __shared__ float s_f[SMPL_MAX_F + 1];
+    __shared__ double s_vs[1][SMPL_VPB * 3];                  // the shaped template
     for (int j = threadIdx.x; j < a.J; j += FB_BLOCK) sf_rodrigues(a.poses + 3 * j, s_rot + 9 * j);
     __syncthreads();
     const int F = 9 * (a.J - 1);
     for (int k = threadIdx.x; k < F; k += FB_BLOCK) s_f[k] = s_rot[9 + k] - ((k % 9) % 4 == 0 ? 1.0f : 0.0f);
-    const int v0 = blockIdx.x * FB_VPB;
-    const int nv = min(FB_VPB, a.V - v0);
+    const int v0 = blockIdx.x * SMPL_VPB;
+    const int nv = min(SMPL_VPB, a.V - v0);
     const int nrows = nv * 3;
     if ((int)threadIdx.x < nrows) {
         const size_t row = (size_t)v0 * 3 + threadIdx.x;
         const float* sd = a.sd + row * a.sd_stride;
         double so = 0.0;
         for (int b = 0; b < a.nb; b++) so = fma((double)sd[b], (double)a.shapes[b], so);
-        s_vs[threadIdx.x] = (double)a.vt[row] + so;
+        s_vs[0][threadIdx.x] = (double)a.vt[row] + so;
     }
     __syncthreads();
-    for (int o = threadIdx.x; o < a.J * 3; o += FB_BLOCK) {
-        const int j = o / 3, c = o % 3;
-        const float* jr = a.jr + (size_t)j * a.V + v0;
-        double acc = 0.0;
-        for (int i = 0; i < nv; i++) acc = fma((double)jr[i], s_vs[3 * i + c], acc);
-        partials[(size_t)blockIdx.x * a.J * 3 + o] = acc;
-    }
-    if (F == 0) {                                             // (J = 1: no pose blend shapes, posedirs may be NULL)
-        if ((int)threadIdx.x < nrows) vposed[(size_t)v0 * 3 + threadIdx.x] = s_vs[threadIdx.x];
+    smpl_regressor_shares<1, FB_BLOCK>(a.jr, a.V, a.J, v0, nv, s_vs, partials);
+    if (F == 0) {                                             // (J = 1: no pose blend shapes, posedirs may be NULL; s_vs + 0.0 would lose a -0.0)
+        if ((int)threadIdx.x < nrows) vposed[(size_t)v0 * 3 + threadIdx.x] = s_vs[0][threadIdx.x];
         return;
     }
-    const int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
-    for (int r0 = wave * 4; r0 < nrows; r0 += 4 * (FB_BLOCK / 64)) {
-        const float* p0 = a.pd + ((size_t)v0 * 3 + r0) * F;
-        const float* p1 = a.pd + ((size_t)v0 * 3 + min(r0 + 1, nrows - 1)) * F;     // (rows past the range: read again, not written)
-        const float* p2 = a.pd + ((size_t)v0 * 3 + min(r0 + 2, nrows - 1)) * F;
-        const float* p3 = a.pd + ((size_t)v0 * 3 + min(r0 + 3, nrows - 1)) * F;
-        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-        for (int k = lane; k < F; k += 64) {
-            const double f = (double)s_f[k];
-            a0 = fma((double)p0[k], f, a0); a1 = fma((double)p1[k], f, a1);
-            a2 = fma((double)p2[k], f, a2); a3 = fma((double)p3[k], f, a3);
-        }
-        a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2); a3 = wave_sum(a3);
-        if (lane < 4 && r0 + lane < nrows) {
-            const double acc = lane == 0 ? a0 : lane == 1 ? a1 : lane == 2 ? a2 : a3;
-            vposed[(size_t)v0 * 3 + r0 + lane] = s_vs[r0 + lane] + acc;
-        }
-    }
+    smpl_pose_blend_rows<FB_BLOCK>(a.pd, s_f, F, v0, nrows, [&](int r, double acc) { vposed[(size_t)v0 * 3 + r] = s_vs[0][r] + acc; });
 }
 
 // every workgroup: the joints (the shares folded in a fixed order), the chain, A; then its vertices and their min / max record
 __global__ void __launch_bounds__(FB_SKIN_BLOCK)
-frame_bounds_skin_kernel(FbIn a, FbParents par, int nparts, const double* __restrict__ partials, const double* __restrict__ vposed,
+frame_bounds_skin_kernel(FbIn a, SmplParents par, int nparts, const double* __restrict__ partials, const double* __restrict__ vposed,
                          float* __restrict__ world_vertex, float* __restrict__ joints, float* __restrict__ records)
 {
-    __shared__ float s_rot[FB_MAX_J * 9];
+    __shared__ float s_rot[SMPL_MAX_J * 9];
     __shared__ double s_slice[FB_SKIN_BLOCK];
-    __shared__ double s_jt[FB_MAX_J * 3], s_rel[FB_MAX_J * 3];
-    __shared__ double s_G[FB_MAX_J * 12];                    // per joint: the chain's rotation (9, row-major), then its translation (3)
-    __shared__ double s_A[FB_MAX_J * 12];                    // per joint: rows 0..2 of A_j (3 x 4, row-major)
+    __shared__ double s_jt[1][SMPL_MAX_J * 3], s_rel[1][SMPL_MAX_J * 3];
+    __shared__ double s_G[SMPL_MAX_J * 12];                    // per joint: the chain's rotation (9, row-major), then its translation (3)
+    __shared__ double s_A[SMPL_MAX_J * 12];                    // per joint: rows 0..2 of A_j (3 x 4, row-major)
     __shared__ double s_p[FB_SKIN_VPB * 3];
     __shared__ float s_mm[FB_SKIN_BLOCK / 64][6];
     const int t = threadIdx.x;
     const int J = a.J, nout = J * 3;
     for (int j = t; j < J; j += FB_SKIN_BLOCK) sf_rodrigues(a.poses + 3 * j, s_rot + 9 * j);
-    const int nslice = FB_SKIN_BLOCK / nout;                  // >= 5: every output's shares are cut into nslice runs of workgroups,
-    const int per = (nparts + nslice - 1) / nslice;           // each summed in order, then the runs in order -- a function of V and J only
-    if (t < nout * nslice) {
-        const int o = t % nout, sl = t / nout;
-        const int b1 = min(nparts, (sl + 1) * per);
-        double acc = 0.0;
-        for (int b = sl * per; b < b1; b++) acc += partials[(size_t)b * nout + o];
-        s_slice[t] = acc;
-    }
-    __syncthreads();
-    if (t < nout) {
-        double acc = 0.0;
-        for (int sl = 0; sl < nslice; sl++) acc += s_slice[sl * nout + t];
-        s_jt[t] = acc;
-    }
-    __syncthreads();
-    if (t < nout) {
-        const int j = t / 3, c = t % 3;
-        s_rel[t] = j == 0 ? s_jt[t] : s_jt[t] - s_jt[3 * par.p[j] + c];
-    }
-    __syncthreads();
+    smpl_fold_shares<1, FB_SKIN_BLOCK>(J, nparts, partials, s_slice, s_jt);         // (nslice >= 5; its first barrier covers s_rot)
+    smpl_relative_joints<1>(J, par, s_jt, s_rel);
     for (int j = 0; j < J; j++) {
-        if (t < 12) {
-            const float* R = s_rot + 9 * j;
-            const double* rel = s_rel + 3 * j;
-            double* G = s_G + 12 * j;
-            if (j == 0) {
-                G[t] = t < 9 ? (double)R[t] : rel[t - 9];
-            } else {
-                const double* Gp = s_G + 12 * par.p[j];
-                if (t < 9) {
-                    const int r = t / 3, c = t % 3;
-                    G[t] = Gp[3 * r] * (double)R[c] + Gp[3 * r + 1] * (double)R[3 + c] + Gp[3 * r + 2] * (double)R[6 + c];
-                } else {
-                    const int r = t - 9;
-                    G[t] = Gp[3 * r] * rel[0] + Gp[3 * r + 1] * rel[1] + Gp[3 * r + 2] * rel[2] + Gp[9 + r];
-                }
-            }
-        }
+        if (t < 12) smpl_chain_step(j, t, par, s_rot + 9 * j, s_rel[0] + 3 * j, s_G);
         __syncthreads();
     }
     for (int o = t; o < J * 12; o += FB_SKIN_BLOCK) {
-        const int j = o / 12, r = (o % 12) / 4, c = o % 4;
-        const double* G = s_G + 12 * j;
-        const double* jt = s_jt + 3 * j;
-        s_A[o] = c < 3 ? G[3 * r + c] : G[9 + r] - (G[3 * r] * jt[0] + G[3 * r + 1] * jt[1] + G[3 * r + 2] * jt[2]);
+        const int j = o / 12;
+        s_A[o] = smpl_A_entry(s_G + 12 * j, s_jt[0] + 3 * j, (o % 12) / 4, o % 4);
     }
     if (joints && blockIdx.x == 0 && t < nout) joints[t] = (float)s_G[12 * (t / 3) + 9 + t % 3];
     __syncthreads();
@@ -222,29 +157,10 @@ frame_bounds_fold_kernel(int nrecords, const float* __restrict__ records, const 
     world_bound[t] = t < 3 ? m - p : m + p;
 }
 
-__device__ __forceinline__ int wave_min_i(int v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = min(v, __shfl_xor(v, d));
-    return v;
-}
-__device__ __forceinline__ int wave_max_i(int v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d));
-    return v;
-}
-__device__ __forceinline__ int wave_sum_i(int v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
 // (min x, min y, max x, max y, count) of a workgroup from its threads' values; valid in thread 0
 __device__ __forceinline__ void fb_block_record(int (*s_rec)[5], int& x0, int& y0, int& x1, int& y1, int& n)
 {
-    x0 = wave_min_i(x0); y0 = wave_min_i(y0); x1 = wave_max_i(x1); y1 = wave_max_i(y1); n = wave_sum_i(n);
+    x0 = wave_min(x0); y0 = wave_min(y0); x1 = wave_max(x1); y1 = wave_max(y1); n = wave_sum(n);
     const int wave = threadIdx.x / 64;
     if (threadIdx.x % 64 == 0) { s_rec[wave][0] = x0; s_rec[wave][1] = y0; s_rec[wave][2] = x1; s_rec[wave][3] = y1; s_rec[wave][4] = n; }
     __syncthreads();
@@ -381,7 +297,7 @@ frame_bounds_rect_kernel(int ntiles, const int32_t* __restrict__ records, int32_
 
 size_t fb_vertices_bytes(int V, int J)
 {
-    const size_t nparts = ((size_t)V + FB_VPB - 1) / FB_VPB, nskin = ((size_t)V + FB_SKIN_VPB - 1) / FB_SKIN_VPB;
+    const size_t nparts = ((size_t)V + SMPL_VPB - 1) / SMPL_VPB, nskin = ((size_t)V + FB_SKIN_VPB - 1) / FB_SKIN_VPB;
     return align_up((size_t)V * 3 * sizeof(double)) + align_up(nparts * (size_t)J * 3 * sizeof(double)) + align_up(nskin * 6 * sizeof(float));
 }
 
@@ -395,7 +311,7 @@ using namespace moss;
 
 extern "C" size_t moss_smpl_vertices_workspace_bytes(int V, int J)
 {
-    if (V <= 0 || J < 1 || J > FB_MAX_J) return 0;
+    if (V <= 0 || J < 1 || J > SMPL_MAX_J) return 0;
     return fb_vertices_bytes(V, J);
 }
 
@@ -404,23 +320,21 @@ extern "C" int moss_smpl_vertices(const moss_smpl_vertices_args* a, void* stream
     const char* who = "moss_smpl_vertices";
     if (!a) return invalid_arg(who, "null argument block");
     if (a->V < 1) return invalid_arg(who, "V must be >= 1");
-    if (a->J < 1 || a->J > FB_MAX_J) return invalid_arg(who, "J must be 1..64");
+    if (a->J < 1 || a->J > SMPL_MAX_J) return invalid_arg(who, "J must be 1..64");
     if (a->num_betas < 0 || a->num_betas > a->shapedirs_stride) return invalid_arg(who, "num_betas must be 0..shapedirs_stride");
     if (!a->v_template || !a->shapedirs || !a->J_regressor || !a->weights || (a->J > 1 && !a->posedirs))
         return invalid_arg(who, "null body-model array (v_template, shapedirs, posedirs, J_regressor, weights)");
     if (!a->poses || !a->R || !a->Th || !a->pad || (a->num_betas > 0 && !a->shapes))
         return invalid_arg(who, "null frame input (poses, shapes, R, Th, pad)");
     if (!a->world_vertex || !a->world_bound) return invalid_arg(who, "null output (world_vertex, world_bound)");
-    for (int j = 1; j < a->J; j++)
-        if (a->parents[j] < 0 || a->parents[j] >= j) return invalid_arg(who, "parents[j] must be in [0, j) for every j >= 1");
+    if (int rc = smpl_check_parents(who, a->J, a->parents)) return rc;
     if (!a->workspace || a->workspace_bytes < fb_vertices_bytes(a->V, a->J))
         return invalid_arg(who, "needs moss_smpl_vertices_workspace_bytes(V, J) bytes of workspace");
     hipStream_t s = (hipStream_t)stream;
     const FbIn in{a->V, a->J, a->num_betas, a->shapedirs_stride, a->v_template, a->shapedirs, a->posedirs, a->J_regressor, a->weights,
                   a->poses, a->shapes, a->R, a->Th};
-    FbParents par;
-    for (int j = 0; j < FB_MAX_J; j++) par.p[j] = j < a->J ? a->parents[j] : 0;
-    const int nparts = (a->V + FB_VPB - 1) / FB_VPB, nskin = (a->V + FB_SKIN_VPB - 1) / FB_SKIN_VPB;
+    const SmplParents par = smpl_parents(a);
+    const int nparts = (a->V + SMPL_VPB - 1) / SMPL_VPB, nskin = (a->V + FB_SKIN_VPB - 1) / FB_SKIN_VPB;
     char* p = a->workspace;
     double* vposed = carve<double>(p, (size_t)a->V * 3);
     double* partials = carve<double>(p, (size_t)nparts * a->J * 3);

@@ -24,7 +24,7 @@ namespace {
 
 constexpr int LBS_FWD_BLOCK = 256;
 constexpr int LBS_BWD_BLOCK = 128;
-constexpr int LBS_MAX_J = 64;
+constexpr int LBS_MAX_J = MOSS_SMPL_FRAME_MAX_JOINTS;
 constexpr int LBS_FOLD_WAVES = 4;
 
 struct LbsIn {
@@ -340,24 +340,6 @@ lbs_backward_kernel(LbsIn a, LbsGrad g)
     }
 }
 
-// gA_obs (J,4,4): one wave per element, the workgroup partials in workgroup order (lane l takes l, l + 64, ...) in float64, then a
-// fixed butterfly.  Row 3 of every 4x4 is written as zero.
-__global__ void __launch_bounds__(64 * LBS_FOLD_WAVES)
-lbs_fold_kernel(int J, int nblocks, const float* __restrict__ partials, float* __restrict__ gA)
-{
-    const int o = blockIdx.x * LBS_FOLD_WAVES + threadIdx.x / 64;
-    const int lane = threadIdx.x % 64;
-    if (o >= J * 16) return;
-    const int j = o / 16, r = (o % 16) / 4, c = o % 4;
-    double acc = 0.0;
-    if (r < 3) {
-        const size_t stride = (size_t)J * 12, off = (size_t)j * 12 + r * 4 + c;
-        for (int b = lane; b < nblocks; b += 64) acc += (double)partials[(size_t)b * stride + off];
-    }
-    acc = wave_sum(acc);
-    if (lane == 0) gA[o] = (float)acc;
-}
-
 // this workgroup's share of [g_R | g_Th]: one lane per Gaussian (the workgroups of lbs_backward_kernel), the forward recomputed;
 // fpartials [blocks][12] (g_R row-major, then g_Th).  Lanes past P and Gaussians with an id outside [0, V) stage zeros.
 template <int JB, bool VEC>
@@ -426,10 +408,12 @@ lbs_frame_terms_kernel(LbsIn a, const float* __restrict__ g_T, const float* __re
     }
 }
 
-// the fold of moss_lbs_deform_backward_frame: elements [0, 16 J) are gA_obs exactly as lbs_fold_kernel forms them (skipped without gA),
-// elements 16 J + [0, 12) are [g_R | g_Th] from the float64 partials, in workgroup order.  nblocks = 0 (P = 0) writes zeros.
+// the fold of both backwards, one wave per element: the workgroup partials in workgroup order (lane l takes l, l + 64, ...) in float64,
+// then a fixed butterfly.  Elements [0, 16 J) are gA_obs (J,4,4), row 3 of every 4x4 written as zero (skipped without gA); elements
+// 16 J + [0, 12) are [g_R | g_Th] from the float64 partials (moss_lbs_deform_backward's grid ends before them).  nblocks = 0 (P = 0)
+// writes zeros.
 __global__ void __launch_bounds__(64 * LBS_FOLD_WAVES)
-lbs_fold_frame_kernel(int J, int nblocks, const float* __restrict__ partials, float* __restrict__ gA,
+lbs_fold_kernel(int J, int nblocks, const float* __restrict__ partials, float* __restrict__ gA,
                       const double* __restrict__ fpartials, float* __restrict__ gR, float* __restrict__ gTh)
 {
     const int o = blockIdx.x * LBS_FOLD_WAVES + threadIdx.x / 64;
@@ -499,14 +483,14 @@ struct LaunchFrameTerms {
 bool aligned16(const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 template <typename A>
-int lbs_check_common(const A* a)
+int lbs_check_common(const char* who, const A* a)
 {
-    if (!a) return invalid_arg("lbs", "null argument block");
-    if (a->P < 0) return invalid_arg("lbs", "P must be >= 0");
-    if (a->J < 1 || a->J > LBS_MAX_J) return invalid_arg("lbs", "J must be 1..64");
-    if (a->V < 1) return invalid_arg("lbs", "V must be >= 1");
+    if (!a) return invalid_arg(who, "null argument block");
+    if (a->P < 0) return invalid_arg(who, "P must be >= 0");
+    if (a->J < 1 || a->J > LBS_MAX_J) return invalid_arg(who, "J must be 1..64");
+    if (a->V < 1) return invalid_arg(who, "V must be >= 1");
     if (!a->vert_ids || !a->weights || !a->A_big || !a->A_obs || !a->d || !a->R || !a->Th)
-        return invalid_arg("lbs", "null required input (vert_ids, weights, A_big, A_obs, d, R, Th)");
+        return invalid_arg(who, "null required input (vert_ids, weights, A_big, A_obs, d, R, Th)");
     return 0;
 }
 
@@ -514,6 +498,48 @@ template <typename A>
 LbsIn lbs_in(const A* a)
 {
     return LbsIn{a->P, a->J, a->V, a->vert_ids, a->weights, a->lbs_offsets, a->A_big, a->A_obs, a->d, a->R, a->Th, a->x};
+}
+
+// both backward entries.  FRAME (moss_lbs_deform_backward_frame): the block also has g_R and g_Th, the workspace rule is
+// moss_lbs_frame_workspace_bytes, the texts carry the entry's full name, and P = 0 still writes zero g_R / g_Th; the plain entry
+// returns at P = 0 before it looks at the workspace, launches its kernel whatever is wanted, and folds gA_obs's elements alone.
+template <bool FRAME, typename A>
+int lbs_backward_impl(const A* a, void* stream)
+{
+    const char* entry = FRAME ? "moss_lbs_deform_backward_frame" : "moss_lbs_deform_backward";
+    const char* who = FRAME ? entry : "lbs backward";
+    if (int rc = lbs_check_common(FRAME ? entry : "lbs", a)) return rc;
+    if ((a->g_p || a->g_x) && !a->x) return invalid_arg(who, "g_p and g_x need x");
+    if (a->g_L && !a->lbs_offsets) return invalid_arg(who, "g_L needs lbs_offsets");
+    float* g_R = nullptr;
+    float* g_Th = nullptr;
+    if constexpr (FRAME) { g_R = a->g_R; g_Th = a->g_Th; }
+    else if (a->P == 0) return 0;
+    const bool frame = g_R || g_Th;
+    if (a->P > 0 && (a->g_A_obs || frame)
+        && (!a->workspace || a->workspace_bytes < (FRAME ? moss_lbs_frame_workspace_bytes : moss_lbs_workspace_bytes)(a->P, a->J)))
+        return invalid_arg(who, FRAME ? "g_A_obs, g_R and g_Th need moss_lbs_frame_workspace_bytes(P, J) bytes of workspace"
+                                      : "g_A_obs needs moss_lbs_workspace_bytes(P, J) bytes of workspace");
+    hipStream_t s = (hipStream_t)stream;
+    const int nblocks = (a->P + LBS_BWD_BLOCK - 1) / LBS_BWD_BLOCK;
+    float* partials = nullptr;
+    double* fpartials = nullptr;
+    if (a->P > 0) {
+        partials = a->g_A_obs ? reinterpret_cast<float*>(a->workspace) : nullptr;
+        fpartials = frame ? reinterpret_cast<double*>(a->workspace + moss_lbs_workspace_bytes(a->P, a->J)) : nullptr;
+        const bool vec = aligned16(a->weights) && aligned16(a->lbs_offsets) && aligned16(a->g_L);
+        if (!FRAME || a->g_L || a->g_A_obs || a->g_d || a->g_x) {
+            const LbsGrad g{a->g_T, a->g_t, a->g_p, a->g_L, a->g_d, a->g_x, partials};
+            lbs_dispatch<LaunchBwd>(a->J, vec, dim3(nblocks), s, lbs_in(a), g);
+        }
+        if (frame) lbs_dispatch<LaunchFrameTerms>(a->J, vec, dim3(nblocks), s, lbs_in(a), a->g_T, a->g_t, a->g_p, fpartials);
+    }
+    // P = 0: nothing reads a Gaussian; g_R and g_Th are written as zero (g_A_obs is not written)
+    float* gA = a->P > 0 ? a->g_A_obs : nullptr;
+    if (gA || frame)
+        hipLaunchKernelGGL(lbs_fold_kernel, dim3((a->J * 16 + (FRAME ? 12 : 0) + LBS_FOLD_WAVES - 1) / LBS_FOLD_WAVES),
+                           dim3(64 * LBS_FOLD_WAVES), 0, s, a->J, nblocks, (const float*)partials, gA, (const double*)fpartials, g_R, g_Th);
+    return launch_status(entry);
 }
 
 }  // namespace
@@ -531,7 +557,7 @@ extern "C" size_t moss_lbs_workspace_bytes(int P, int J)
 
 extern "C" int moss_lbs_deform_forward(const moss_lbs_forward_args* a, void* stream)
 {
-    if (int rc = lbs_check_common(a)) return rc;
+    if (int rc = lbs_check_common("lbs", a)) return rc;
     if (!a->T || !a->t) return invalid_arg("lbs forward", "null T or t");
     if (a->p && !a->x) return invalid_arg("lbs forward", "p needs x");
     if (a->P == 0) return 0;
@@ -541,26 +567,6 @@ extern "C" int moss_lbs_deform_forward(const moss_lbs_forward_args* a, void* str
     return launch_status("moss_lbs_deform_forward");
 }
 
-extern "C" int moss_lbs_deform_backward(const moss_lbs_backward_args* a, void* stream)
-{
-    if (int rc = lbs_check_common(a)) return rc;
-    if ((a->g_p || a->g_x) && !a->x) return invalid_arg("lbs backward", "g_p and g_x need x");
-    if (a->g_L && !a->lbs_offsets) return invalid_arg("lbs backward", "g_L needs lbs_offsets");
-    if (a->P == 0) return 0;
-    if (a->g_A_obs && (!a->workspace || a->workspace_bytes < moss_lbs_workspace_bytes(a->P, a->J)))
-        return invalid_arg("lbs backward", "g_A_obs needs moss_lbs_workspace_bytes(P, J) bytes of workspace");
-    const bool vec = aligned16(a->weights) && aligned16(a->lbs_offsets) && aligned16(a->g_L);
-    const int nblocks = (a->P + LBS_BWD_BLOCK - 1) / LBS_BWD_BLOCK;
-    hipStream_t s = (hipStream_t)stream;
-    float* partials = a->g_A_obs ? reinterpret_cast<float*>(a->workspace) : nullptr;
-    const LbsGrad g{a->g_T, a->g_t, a->g_p, a->g_L, a->g_d, a->g_x, partials};
-    lbs_dispatch<LaunchBwd>(a->J, vec, dim3(nblocks), s, lbs_in(a), g);
-    if (a->g_A_obs)
-        hipLaunchKernelGGL(lbs_fold_kernel, dim3((a->J * 16 + LBS_FOLD_WAVES - 1) / LBS_FOLD_WAVES), dim3(64 * LBS_FOLD_WAVES), 0, s,
-                           a->J, nblocks, (const float*)partials, a->g_A_obs);
-    return launch_status("moss_lbs_deform_backward");
-}
-
 extern "C" size_t moss_lbs_frame_workspace_bytes(int P, int J)
 {
     if (P <= 0 || J < 1 || J > LBS_MAX_J) return 0;
@@ -568,38 +574,9 @@ extern "C" size_t moss_lbs_frame_workspace_bytes(int P, int J)
     return moss_lbs_workspace_bytes(P, J) + align_up(nb * 12 * sizeof(double));
 }
 
+extern "C" int moss_lbs_deform_backward(const moss_lbs_backward_args* a, void* stream) { return lbs_backward_impl<false>(a, stream); }
+
 extern "C" int moss_lbs_deform_backward_frame(const moss_lbs_backward_frame_args* a, void* stream)
 {
-    const char* who = "moss_lbs_deform_backward_frame";
-    if (!a) return invalid_arg(who, "null argument block");
-    if (a->P < 0) return invalid_arg(who, "P must be >= 0");
-    if (a->J < 1 || a->J > LBS_MAX_J) return invalid_arg(who, "J must be 1..64");
-    if (a->V < 1) return invalid_arg(who, "V must be >= 1");
-    if (!a->vert_ids || !a->weights || !a->A_big || !a->A_obs || !a->d || !a->R || !a->Th)
-        return invalid_arg(who, "null required input (vert_ids, weights, A_big, A_obs, d, R, Th)");
-    if ((a->g_p || a->g_x) && !a->x) return invalid_arg(who, "g_p and g_x need x");
-    if (a->g_L && !a->lbs_offsets) return invalid_arg(who, "g_L needs lbs_offsets");
-    const bool frame = a->g_R || a->g_Th;
-    if (a->P > 0 && (a->g_A_obs || frame) && (!a->workspace || a->workspace_bytes < moss_lbs_frame_workspace_bytes(a->P, a->J)))
-        return invalid_arg(who, "g_A_obs, g_R and g_Th need moss_lbs_frame_workspace_bytes(P, J) bytes of workspace");
-    hipStream_t s = (hipStream_t)stream;
-    const int nblocks = (a->P + LBS_BWD_BLOCK - 1) / LBS_BWD_BLOCK;
-    float* partials = nullptr;
-    double* fpartials = nullptr;
-    if (a->P > 0) {
-        partials = a->g_A_obs ? reinterpret_cast<float*>(a->workspace) : nullptr;
-        fpartials = frame ? reinterpret_cast<double*>(a->workspace + moss_lbs_workspace_bytes(a->P, a->J)) : nullptr;
-        const bool vec = aligned16(a->weights) && aligned16(a->lbs_offsets) && aligned16(a->g_L);
-        if (a->g_L || a->g_A_obs || a->g_d || a->g_x) {
-            const LbsGrad g{a->g_T, a->g_t, a->g_p, a->g_L, a->g_d, a->g_x, partials};
-            lbs_dispatch<LaunchBwd>(a->J, vec, dim3(nblocks), s, lbs_in(a), g);
-        }
-        if (frame) lbs_dispatch<LaunchFrameTerms>(a->J, vec, dim3(nblocks), s, lbs_in(a), a->g_T, a->g_t, a->g_p, fpartials);
-    }
-    // P = 0: nothing reads a Gaussian; g_R and g_Th are written as zero (g_A_obs is not written, as by moss_lbs_deform_backward)
-    float* gA = a->P > 0 ? a->g_A_obs : nullptr;
-    if (gA || frame)
-        hipLaunchKernelGGL(lbs_fold_frame_kernel, dim3((a->J * 16 + 12 + LBS_FOLD_WAVES - 1) / LBS_FOLD_WAVES), dim3(64 * LBS_FOLD_WAVES), 0,
-                           s, a->J, nblocks, (const float*)partials, gA, (const double*)fpartials, a->g_R, a->g_Th);
-    return launch_status(who);
+    return lbs_backward_impl<true>(a, stream);
 }

@@ -3,7 +3,7 @@
 // shapes, both kinematic chains, the per-vertex offset table D and its gather at the Gaussians' vertices.
 //
 // forward, 2 launches:
-//   offsets        a grid over ranges of SF_VPB vertices.  Every workgroup recomputes the 2 J rotations in LDS (48 sincos: cheaper than
+//   offsets        a grid over ranges of SMPL_VPB vertices.  Every workgroup recomputes the 2 J rotations in LDS (48 sincos: cheaper than
 //                  a launch that would hand them over), forms f = rot_obs[1:] - rot_big[1:], its rows of D = shapedirs beta_obs + posedirs f
 //                  (one wave per 4 rows, lanes over the feature, a fixed butterfly) and its share of J_regressor (v_template +
 //                  shapedirs beta) for both shapes, which goes to the workspace.
@@ -29,16 +29,11 @@ namespace moss {
 
 namespace {
 
-constexpr int SF_MAX_J = MOSS_SMPL_FRAME_MAX_JOINTS;
-constexpr int SF_MAX_F = 9 * (SF_MAX_J - 1);
 constexpr int SF_BLOCK = 256;
-constexpr int SF_VPB = 16;              // vertices per workgroup of the offsets kernel
 constexpr int SF_CHAIN_BLOCK = 1024;    // the chain / gather kernel: 1024 Gaussians per gathering workgroup
 constexpr int SF_GPW = 64;              // Gaussians per workgroup of the backward reduction
 constexpr int SF_FOLD_WAVES = 4;
 constexpr int SF_SAVED_PER_J = MOSS_SMPL_FRAME_SAVED_FLOATS_PER_JOINT;   // rot_raw 9, rot 9, chain rotation 9, relative joint 3, joint 3
-
-struct SfParents { int32_t p[SF_MAX_J]; };
 
 struct SfIn {
     int P, V, J, nb_big, nb, sd_stride;
@@ -75,19 +70,19 @@ __device__ __forceinline__ void sf_stage_rotations(const SfIn& a, float* s_big, 
     __syncthreads();
 }
 
-// D rows and regressor shares of vertices [SF_VPB b, SF_VPB (b + 1)); partials [workgroup][J][2 shapes][3]
+// D rows and regressor shares of vertices [SMPL_VPB b, SMPL_VPB (b + 1)); partials [workgroup][J][2 shapes][3]
 __global__ void __launch_bounds__(SF_BLOCK)
 smpl_frame_offsets_kernel(SfIn a, float* __restrict__ D, double* __restrict__ partials)
 {
-    __shared__ float s_big[SF_MAX_J * 9], s_raw[SF_MAX_J * 9], s_rot[SF_MAX_J * 9];
-    __shared__ float s_f[SF_MAX_F + 1];
-    __shared__ double s_vs[2][SF_VPB * 3];                  // the shaped template of the big pose's / the frame's betas
-    __shared__ double s_so[SF_VPB * 3];                     // shapedirs beta_obs
+    __shared__ float s_big[SMPL_MAX_J * 9], s_raw[SMPL_MAX_J * 9], s_rot[SMPL_MAX_J * 9];
+    __shared__ float s_f[SMPL_MAX_F + 1];
+    __shared__ double s_vs[2][SMPL_VPB * 3];                  // the shaped template of the big pose's / the frame's betas
+    __shared__ double s_so[SMPL_VPB * 3];                     // shapedirs beta_obs
     sf_stage_rotations(a, s_big, s_raw, s_rot);
     const int F = 9 * (a.J - 1);
     for (int k = threadIdx.x; k < F; k += SF_BLOCK) s_f[k] = s_rot[9 + k] - s_big[9 + k];
-    const int v0 = blockIdx.x * SF_VPB;
-    const int nv = min(SF_VPB, a.V - v0);
+    const int v0 = blockIdx.x * SMPL_VPB;
+    const int nv = min(SMPL_VPB, a.V - v0);
     const int nrows = nv * 3;
     if ((int)threadIdx.x < nrows) {
         const size_t row = (size_t)v0 * 3 + threadIdx.x;
@@ -101,36 +96,14 @@ smpl_frame_offsets_kernel(SfIn a, float* __restrict__ D, double* __restrict__ pa
         s_so[threadIdx.x] = so;
     }
     __syncthreads();
-    for (int o = threadIdx.x; o < a.J * 6; o += SF_BLOCK) {
-        const int j = o / 6, s = (o % 6) / 3, c = o % 3;
-        const float* jr = a.jr + (size_t)j * a.V + v0;
-        double acc = 0.0;
-        for (int i = 0; i < nv; i++) acc = fma((double)jr[i], s_vs[s][3 * i + c], acc);
-        partials[(size_t)blockIdx.x * a.J * 6 + o] = acc;
-    }
-    const int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
-    for (int r0 = wave * 4; r0 < nrows; r0 += 4 * (SF_BLOCK / 64)) {
-        const float* p0 = a.pd + ((size_t)v0 * 3 + r0) * F;
-        const float* p1 = a.pd + ((size_t)v0 * 3 + min(r0 + 1, nrows - 1)) * F;     // (rows past the range: read again, not written)
-        const float* p2 = a.pd + ((size_t)v0 * 3 + min(r0 + 2, nrows - 1)) * F;
-        const float* p3 = a.pd + ((size_t)v0 * 3 + min(r0 + 3, nrows - 1)) * F;
-        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-        for (int k = lane; k < F; k += 64) {
-            const double f = (double)s_f[k];
-            a0 = fma((double)p0[k], f, a0); a1 = fma((double)p1[k], f, a1);
-            a2 = fma((double)p2[k], f, a2); a3 = fma((double)p3[k], f, a3);
-        }
-        a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2); a3 = wave_sum(a3);
-        if (lane < 4 && r0 + lane < nrows) {
-            const double acc = lane == 0 ? a0 : lane == 1 ? a1 : lane == 2 ? a2 : a3;
-            D[(size_t)v0 * 3 + r0 + lane] = (float)(s_so[r0 + lane] + acc);
-        }
-    }
+    smpl_regressor_shares<2, SF_BLOCK>(a.jr, a.V, a.J, v0, nv, s_vs, partials);
+    smpl_pose_blend_rows<SF_BLOCK>(a.pd, s_f, F, v0, nrows,
+                                   [&](int r, double acc) { D[(size_t)v0 * 3 + r] = (float)(s_so[r] + acc); });
 }
 
 // workgroup 0: the joints (the shares folded in a fixed order), both chains, A_big, A_obs, rot_mats, saved; the others: d = D[ids]
 __global__ void __launch_bounds__(SF_CHAIN_BLOCK)
-smpl_frame_chain_gather_kernel(SfIn a, SfParents par, int nparts, const double* __restrict__ partials, const float* __restrict__ D,
+smpl_frame_chain_gather_kernel(SfIn a, SmplParents par, int nparts, const double* __restrict__ partials, const float* __restrict__ D,
                                float* __restrict__ A_big, float* __restrict__ A_obs, float* __restrict__ d, float* __restrict__ rot_out,
                                float* __restrict__ saved)
 {
@@ -145,62 +118,24 @@ smpl_frame_chain_gather_kernel(SfIn a, SfParents par, int nparts, const double* 
         for (int c = 0; c < 3; c++) d[(size_t)i * 3 + c] = ok ? D[(size_t)v * 3 + c] : nan;
         return;
     }
-    __shared__ float s_big[SF_MAX_J * 9], s_raw[SF_MAX_J * 9], s_rot[SF_MAX_J * 9];
+    __shared__ float s_big[SMPL_MAX_J * 9], s_raw[SMPL_MAX_J * 9], s_rot[SMPL_MAX_J * 9];
     __shared__ double s_slice[SF_CHAIN_BLOCK];
-    __shared__ double s_jt[2][SF_MAX_J * 3], s_rel[2][SF_MAX_J * 3];
-    __shared__ double s_G[2][SF_MAX_J * 12];                 // per joint: the chain's rotation (9, row-major), then its translation (3)
+    __shared__ double s_jt[2][SMPL_MAX_J * 3], s_rel[2][SMPL_MAX_J * 3];
+    __shared__ double s_G[2][SMPL_MAX_J * 12];                 // per joint: the chain's rotation (9, row-major), then its translation (3)
     sf_stage_rotations(a, s_big, s_raw, s_rot);
-    const int J = a.J, nout = J * 6;
-    const int nslice = SF_CHAIN_BLOCK / nout;                 // >= 2: every output's shares are cut into nslice runs of workgroups,
-    const int per = (nparts + nslice - 1) / nslice;           // each summed in order, then the runs in order -- a function of V and J only
-    if (t < nout * nslice) {
-        const int o = t % nout, sl = t / nout;
-        const int b1 = min(nparts, (sl + 1) * per);
-        double acc = 0.0;
-        for (int b = sl * per; b < b1; b++) acc += partials[(size_t)b * nout + o];
-        s_slice[t] = acc;
-    }
-    __syncthreads();
-    if (t < nout) {
-        double acc = 0.0;
-        for (int sl = 0; sl < nslice; sl++) acc += s_slice[sl * nout + t];
-        s_jt[(t % 6) / 3][3 * (t / 6) + t % 3] = acc;
-    }
-    __syncthreads();
-    if (t < 2 * J * 3) {
-        const int s = t / (J * 3), e = t % (J * 3), j = e / 3, c = e % 3;
-        s_rel[s][e] = j == 0 ? s_jt[s][e] : s_jt[s][e] - s_jt[s][3 * par.p[j] + c];
-    }
-    __syncthreads();
+    const int J = a.J;
+    smpl_fold_shares<2, SF_CHAIN_BLOCK>(J, nparts, partials, s_slice, s_jt);        // (nslice >= 2)
+    smpl_relative_joints<2>(J, par, s_jt, s_rel);
     for (int j = 0; j < J; j++) {
         if (t < 24) {
-            const int s = t / 12, e = t % 12;
-            const float* R = (s ? s_rot : s_big) + 9 * j;
-            const double* rel = s_rel[s] + 3 * j;
-            double* G = s_G[s] + 12 * j;
-            if (j == 0) {
-                G[e] = e < 9 ? (double)R[e] : rel[e - 9];
-            } else {
-                const double* Gp = s_G[s] + 12 * par.p[j];
-                if (e < 9) {
-                    const int r = e / 3, c = e % 3;
-                    G[e] = Gp[3 * r] * (double)R[c] + Gp[3 * r + 1] * (double)R[3 + c] + Gp[3 * r + 2] * (double)R[6 + c];
-                } else {
-                    const int r = e - 9;
-                    G[e] = Gp[3 * r] * rel[0] + Gp[3 * r + 1] * rel[1] + Gp[3 * r + 2] * rel[2] + Gp[9 + r];
-                }
-            }
+            const int s = t / 12;
+            smpl_chain_step(j, t % 12, par, (s ? s_rot : s_big) + 9 * j, s_rel[s] + 3 * j, s_G[s]);
         }
         __syncthreads();
     }
     for (int o = t; o < 2 * J * 16; o += SF_CHAIN_BLOCK) {
         const int s = o / (J * 16), e = o % (J * 16), j = e / 16, r = (e % 16) / 4, c = e % 4;
-        const double* G = s_G[s] + 12 * j;
-        const double* jt = s_jt[s] + 3 * j;
-        double v;
-        if (r == 3) v = c == 3 ? 1.0 : 0.0;
-        else if (c < 3) v = G[3 * r + c];
-        else v = G[9 + r] - (G[3 * r] * jt[0] + G[3 * r + 1] * jt[1] + G[3 * r + 2] * jt[2]);
+        const double v = r == 3 ? (c == 3 ? 1.0 : 0.0) : smpl_A_entry(s_G[s] + 12 * j, s_jt[s] + 3 * j, r, c);
         (s ? A_obs : A_big)[e] = (float)v;
     }
     for (int e = t; e < J * 9; e += SF_CHAIN_BLOCK) {
@@ -277,12 +212,12 @@ smpl_frame_fold_kernel(int F, int nblocks, const double* __restrict__ partials, 
 //   g_a = g_s cos a + g_c sin a - <g_k, r> / a^2,  g_r = g_k / a + g_a e / a.
 template <bool POSE>
 __global__ void __launch_bounds__(SF_BLOCK)
-smpl_frame_chain_backward_kernel(int J, SfParents par, const float* __restrict__ saved, const float* __restrict__ gA,
+smpl_frame_chain_backward_kernel(int J, SmplParents par, const float* __restrict__ saved, const float* __restrict__ gA,
                                  const double* __restrict__ g_feat, float* __restrict__ g_cR, const float* __restrict__ poses,
                                  const float* __restrict__ cR, float* __restrict__ g_poses)
 {
-    __shared__ float s_sv[SF_SAVED_PER_J * SF_MAX_J];
-    __shared__ double s_gGR[SF_MAX_J * 9], s_gGt[SF_MAX_J * 3], s_gR[SF_MAX_J * 9];
+    __shared__ float s_sv[SF_SAVED_PER_J * SMPL_MAX_J];
+    __shared__ double s_gGR[SMPL_MAX_J * 9], s_gGt[SMPL_MAX_J * 3], s_gR[SMPL_MAX_J * 9];
     const int t = threadIdx.x;
     for (int e = t; e < SF_SAVED_PER_J * J; e += SF_BLOCK) s_sv[e] = saved[e];
     __syncthreads();
@@ -378,7 +313,7 @@ smpl_frame_chain_backward_kernel(int J, SfParents par, const float* __restrict__
 
 size_t sf_forward_bytes(int V, int J)
 {
-    const size_t nparts = ((size_t)V + SF_VPB - 1) / SF_VPB;
+    const size_t nparts = ((size_t)V + SMPL_VPB - 1) / SMPL_VPB;
     return align_up((size_t)V * 3 * sizeof(float)) + align_up(nparts * (size_t)J * 6 * sizeof(double));
 }
 
@@ -388,11 +323,46 @@ size_t sf_backward_bytes(int P, int J)
     return align_up(nblocks * F * sizeof(double)) + align_up(F * sizeof(double));
 }
 
-int sf_check_parents(const char* who, int J, const int32_t* parents)
+// both backward entries: the checks, reduce -> fold (with g_d and Gaussians to read), the chain adjoint.  POSE: the block also has
+// poses, correct_Rs and g_poses, g_correct_Rs is optional, and J = 1 still has the root's pose to differentiate
+template <bool POSE, typename A>
+int sf_backward_impl(const char* who, const A* a, void* stream)
 {
-    for (int j = 1; j < J; j++)
-        if (parents[j] < 0 || parents[j] >= j) return invalid_arg(who, "parents[j] must be in [0, j) for every j >= 1");
-    return 0;
+    if (!a) return invalid_arg(who, "null argument block");
+    if (a->P < 0) return invalid_arg(who, "P must be >= 0");
+    if (a->V < 1) return invalid_arg(who, "V must be >= 1");
+    if (a->J < 1 || a->J > SMPL_MAX_J) return invalid_arg(who, "J must be 1..64");
+    const float* poses = nullptr;
+    const float* cR = nullptr;
+    float* g_poses = nullptr;
+    if constexpr (POSE) {
+        if (!a->g_poses) return invalid_arg(who, "null g_poses");
+        if (!a->saved || !a->poses) return invalid_arg(who, "null saved or poses");
+        poses = a->poses; cR = a->correct_Rs; g_poses = a->g_poses;
+    } else {
+        if (a->J == 1) return 0;                               // no joint has a correct_Rs: nothing to write
+        if (!a->saved || !a->g_correct_Rs) return invalid_arg(who, "null saved or g_correct_Rs");
+    }
+    if (int rc = smpl_check_parents(who, a->J, a->parents)) return rc;
+    const bool reduce = a->g_d && a->P > 0 && a->J > 1;
+    if (reduce && (!a->vert_ids || !a->posedirs)) return invalid_arg(who, "g_d needs vert_ids and posedirs");
+    if (reduce && (!a->workspace || a->workspace_bytes < sf_backward_bytes(a->P, a->J)))
+        return invalid_arg(who, "g_d needs moss_smpl_frame_workspace_bytes(P, V, J) bytes of workspace");
+    hipStream_t s = (hipStream_t)stream;
+    const int F = 9 * (a->J - 1);
+    double* g_feat = nullptr;
+    if (reduce) {
+        const int nblocks = (a->P + SF_GPW - 1) / SF_GPW;
+        double* partials = reinterpret_cast<double*>(a->workspace);
+        g_feat = reinterpret_cast<double*>(a->workspace + align_up((size_t)nblocks * F * sizeof(double)));
+        hipLaunchKernelGGL(smpl_frame_reduce_kernel, dim3(nblocks), dim3(SF_BLOCK), 0, s, a->P, a->V, F, a->vert_ids, a->posedirs, a->g_d,
+                           partials);
+        hipLaunchKernelGGL(smpl_frame_fold_kernel, dim3((F + SF_FOLD_WAVES - 1) / SF_FOLD_WAVES), dim3(64 * SF_FOLD_WAVES), 0, s, F,
+                           nblocks, (const double*)partials, g_feat);
+    }
+    hipLaunchKernelGGL(smpl_frame_chain_backward_kernel<POSE>, dim3(1), dim3(SF_BLOCK), 0, s, a->J, smpl_parents(a), a->saved, a->g_A_obs,
+                       (const double*)g_feat, a->J > 1 ? a->g_correct_Rs : nullptr, poses, cR, g_poses);
+    return launch_status(who);
 }
 
 }  // namespace
@@ -403,7 +373,7 @@ using namespace moss;
 
 extern "C" size_t moss_smpl_frame_workspace_bytes(int P, int V, int J)
 {
-    if (P <= 0 || V <= 0 || J < 1 || J > SF_MAX_J) return 0;
+    if (P <= 0 || V <= 0 || J < 1 || J > SMPL_MAX_J) return 0;
     return std::max(sf_forward_bytes(V, J), sf_backward_bytes(P, J));
 }
 
@@ -413,7 +383,7 @@ extern "C" int moss_smpl_frame_forward(const moss_smpl_frame_args* a, void* stre
     if (!a) return invalid_arg(who, "null argument block");
     if (a->P < 0) return invalid_arg(who, "P must be >= 0");
     if (a->V < 1) return invalid_arg(who, "V must be >= 1");
-    if (a->J < 1 || a->J > SF_MAX_J) return invalid_arg(who, "J must be 1..64");
+    if (a->J < 1 || a->J > SMPL_MAX_J) return invalid_arg(who, "J must be 1..64");
     if (a->num_betas_big < 0 || a->num_betas < 0 || a->num_betas_big > a->shapedirs_stride || a->num_betas > a->shapedirs_stride)
         return invalid_arg(who, "num_betas and num_betas_big must be 0..shapedirs_stride");
     if (!a->v_template || !a->shapedirs || !a->J_regressor || !a->poses_big || !a->poses || (a->J > 1 && !a->posedirs))
@@ -421,17 +391,16 @@ extern "C" int moss_smpl_frame_forward(const moss_smpl_frame_args* a, void* stre
     if ((a->num_betas_big > 0 && !a->shapes_big) || (a->num_betas > 0 && !a->shapes)) return invalid_arg(who, "null shapes");
     if (a->P > 0 && (!a->vert_ids || !a->d)) return invalid_arg(who, "null vert_ids or d");
     if (!a->A_big || !a->A_obs || !a->rot_mats) return invalid_arg(who, "null output (A_big, A_obs, rot_mats)");
-    if (int rc = sf_check_parents(who, a->J, a->parents)) return rc;
+    if (int rc = smpl_check_parents(who, a->J, a->parents)) return rc;
     if (!a->workspace || a->workspace_bytes < sf_forward_bytes(a->V, a->J))
         return invalid_arg(who, "needs moss_smpl_frame_workspace_bytes(max(P, 1), V, J) bytes of workspace");
     hipStream_t s = (hipStream_t)stream;
     const SfIn in{a->P, a->V, a->J, a->num_betas_big, a->num_betas, a->shapedirs_stride, a->v_template, a->shapedirs, a->posedirs,
                   a->J_regressor, a->poses_big, a->shapes_big, a->poses, a->shapes, a->correct_Rs, a->vert_ids};
-    SfParents par;
-    for (int j = 0; j < SF_MAX_J; j++) par.p[j] = j < a->J ? a->parents[j] : 0;
+    const SmplParents par = smpl_parents(a);
     float* D = reinterpret_cast<float*>(a->workspace);
     double* partials = reinterpret_cast<double*>(a->workspace + align_up((size_t)a->V * 3 * sizeof(float)));
-    const int nparts = (a->V + SF_VPB - 1) / SF_VPB;
+    const int nparts = (a->V + SMPL_VPB - 1) / SMPL_VPB;
     hipLaunchKernelGGL(smpl_frame_offsets_kernel, dim3(nparts), dim3(SF_BLOCK), 0, s, in, D, partials);
     hipLaunchKernelGGL(smpl_frame_chain_gather_kernel, dim3(1 + (a->P + SF_CHAIN_BLOCK - 1) / SF_CHAIN_BLOCK), dim3(SF_CHAIN_BLOCK), 0, s,
                        in, par, nparts, (const double*)partials, (const float*)D, a->A_big, a->A_obs, a->d, a->rot_mats, a->saved);
@@ -440,66 +409,10 @@ extern "C" int moss_smpl_frame_forward(const moss_smpl_frame_args* a, void* stre
 
 extern "C" int moss_smpl_frame_backward(const moss_smpl_frame_backward_args* a, void* stream)
 {
-    const char* who = "moss_smpl_frame_backward";
-    if (!a) return invalid_arg(who, "null argument block");
-    if (a->P < 0) return invalid_arg(who, "P must be >= 0");
-    if (a->V < 1) return invalid_arg(who, "V must be >= 1");
-    if (a->J < 1 || a->J > SF_MAX_J) return invalid_arg(who, "J must be 1..64");
-    if (a->J == 1) return 0;                                   // no joint has a correct_Rs: nothing to write
-    if (!a->saved || !a->g_correct_Rs) return invalid_arg(who, "null saved or g_correct_Rs");
-    if (int rc = sf_check_parents(who, a->J, a->parents)) return rc;
-    const bool reduce = a->g_d && a->P > 0;
-    if (reduce && (!a->vert_ids || !a->posedirs)) return invalid_arg(who, "g_d needs vert_ids and posedirs");
-    if (reduce && (!a->workspace || a->workspace_bytes < sf_backward_bytes(a->P, a->J)))
-        return invalid_arg(who, "g_d needs moss_smpl_frame_workspace_bytes(P, V, J) bytes of workspace");
-    hipStream_t s = (hipStream_t)stream;
-    SfParents par;
-    for (int j = 0; j < SF_MAX_J; j++) par.p[j] = j < a->J ? a->parents[j] : 0;
-    const int F = 9 * (a->J - 1);
-    double* g_feat = nullptr;
-    if (reduce) {
-        const int nblocks = (a->P + SF_GPW - 1) / SF_GPW;
-        double* partials = reinterpret_cast<double*>(a->workspace);
-        g_feat = reinterpret_cast<double*>(a->workspace + align_up((size_t)nblocks * F * sizeof(double)));
-        hipLaunchKernelGGL(smpl_frame_reduce_kernel, dim3(nblocks), dim3(SF_BLOCK), 0, s, a->P, a->V, F, a->vert_ids, a->posedirs, a->g_d,
-                           partials);
-        hipLaunchKernelGGL(smpl_frame_fold_kernel, dim3((F + SF_FOLD_WAVES - 1) / SF_FOLD_WAVES), dim3(64 * SF_FOLD_WAVES), 0, s, F,
-                           nblocks, (const double*)partials, g_feat);
-    }
-    hipLaunchKernelGGL(smpl_frame_chain_backward_kernel<false>, dim3(1), dim3(SF_BLOCK), 0, s, a->J, par, a->saved, a->g_A_obs,
-                       (const double*)g_feat, a->g_correct_Rs, (const float*)nullptr, (const float*)nullptr, (float*)nullptr);
-    return launch_status(who);
+    return sf_backward_impl<false>("moss_smpl_frame_backward", a, stream);
 }
 
 extern "C" int moss_smpl_frame_backward_pose(const moss_smpl_frame_backward_pose_args* a, void* stream)
 {
-    const char* who = "moss_smpl_frame_backward_pose";
-    if (!a) return invalid_arg(who, "null argument block");
-    if (a->P < 0) return invalid_arg(who, "P must be >= 0");
-    if (a->V < 1) return invalid_arg(who, "V must be >= 1");
-    if (a->J < 1 || a->J > SF_MAX_J) return invalid_arg(who, "J must be 1..64");
-    if (!a->g_poses) return invalid_arg(who, "null g_poses");
-    if (!a->saved || !a->poses) return invalid_arg(who, "null saved or poses");
-    if (int rc = sf_check_parents(who, a->J, a->parents)) return rc;
-    const bool reduce = a->g_d && a->P > 0 && a->J > 1;
-    if (reduce && (!a->vert_ids || !a->posedirs)) return invalid_arg(who, "g_d needs vert_ids and posedirs");
-    if (reduce && (!a->workspace || a->workspace_bytes < sf_backward_bytes(a->P, a->J)))
-        return invalid_arg(who, "g_d needs moss_smpl_frame_workspace_bytes(P, V, J) bytes of workspace");
-    hipStream_t s = (hipStream_t)stream;
-    SfParents par;
-    for (int j = 0; j < SF_MAX_J; j++) par.p[j] = j < a->J ? a->parents[j] : 0;
-    const int F = 9 * (a->J - 1);
-    double* g_feat = nullptr;
-    if (reduce) {
-        const int nblocks = (a->P + SF_GPW - 1) / SF_GPW;
-        double* partials = reinterpret_cast<double*>(a->workspace);
-        g_feat = reinterpret_cast<double*>(a->workspace + align_up((size_t)nblocks * F * sizeof(double)));
-        hipLaunchKernelGGL(smpl_frame_reduce_kernel, dim3(nblocks), dim3(SF_BLOCK), 0, s, a->P, a->V, F, a->vert_ids, a->posedirs, a->g_d,
-                           partials);
-        hipLaunchKernelGGL(smpl_frame_fold_kernel, dim3((F + SF_FOLD_WAVES - 1) / SF_FOLD_WAVES), dim3(64 * SF_FOLD_WAVES), 0, s, F,
-                           nblocks, (const double*)partials, g_feat);
-    }
-    hipLaunchKernelGGL(smpl_frame_chain_backward_kernel<true>, dim3(1), dim3(SF_BLOCK), 0, s, a->J, par, a->saved, a->g_A_obs,
-                       (const double*)g_feat, a->J > 1 ? a->g_correct_Rs : nullptr, a->poses, a->correct_Rs, a->g_poses);
-    return launch_status(who);
+    return sf_backward_impl<true>("moss_smpl_frame_backward_pose", a, stream);
 }

@@ -7,7 +7,7 @@
 
 namespace moss {
 
-template <typename T>                  // (float or double)
+template <typename T>                  // (float, double or int)
 __device__ __forceinline__ T wave_sum(T v)
 {
 #pragma unroll
@@ -24,6 +24,18 @@ __device__ __forceinline__ float wave_max(float v)
 {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d));
+    return v;
+}
+__device__ __forceinline__ int wave_min(int v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = min(v, __shfl_xor(v, d));
+    return v;
+}
+__device__ __forceinline__ int wave_max(int v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d));
     return v;
 }
 
