@@ -791,6 +791,103 @@ int moss_bound_mask(const moss_bound_mask_args* args, void* stream);   /* scene/
 size_t moss_bound_mask_workspace_bytes(int C, int H, int W);
 
 /*
+ * Backward of moss_smpl_vertices to the frame's poses, R and Th (additive in ABI 7): what fitting a frame's SMPL parameters to
+ * keypoints needs.  The body arrays, parents, poses (3J), shapes, R, Th with their meaning in moss_smpl_vertices_args, plus
+ * g_world_vertex (V,3).  Outputs, written and never accumulated into: g_poses (3J), g_R (3,3), g_Th (3).  shapes and the body model
+ * are data.  Nothing is saved by the forward: v_posed, the joints, the chain and A_j are recomputed here from the inputs (the forward
+ * entry keeps its outputs and its launches).  With the forward's names, g_v = g_world_vertex[v] and h_v = R^T g_v:
+ *     g_Th = sum_v g_v                      g_R = sum_v g_v y_v^T                       y_v = T_v [v_posed_v, 1],  T_v = sum_j w[v,j] A_j
+ *     g_A_j[:3,:3] = sum_v w[v,j] h_v v_posed_v^T          g_A_j[:3,3] = sum_v w[v,j] h_v
+ *     g_vposed_v = T_v[:3,:3]^T h_v        g_feat[k] = sum_v sum_c posedirs[v,c,k] g_vposed[v,c]        ONE pass over posedirs
+ * and from there the reverse walk of the tree and the adjoint of Rodrigues exactly as moss_smpl_frame_backward_pose states them, with
+ * correct_Rs = the identity: g_raw_0 = g_rot_0, g_raw_j = g_rot_j + g_feat[9(j-1) .. 9(j-1)+8]; e = r + 1e-8, 1 - cos a = 2 sin^2(a/2).
+ * Four launches on `stream`:
+ *   posed     moss_smpl_vertices' first kernel as it is: v_posed (float64) and the regressor shares, into `workspace`;
+ *   skin      a grid over ranges of 256 vertices: every workgroup folds the shares, walks the chain, then forms y_v, h_v and g_vposed_v of
+ *             its vertices and, walking them in index order, its partial sums of g_Th, g_R and g_A (12 + 12 J values per workgroup);
+ *   features  a grid over ranges of 32 vertices, threads over the 9 (J - 1) features: one partial vector per workgroup (not for J = 1);
+ *   chain     one workgroup folds both sets of partials in a fixed order (the skin partials in workgroup order; the feature partials in
+ *             1024 / (9 (J - 1)) runs of workgroups, each in order, then the runs in order), walks the tree in reverse, and one joint
+ *             per thread forms g_poses.
+ * Every sum is formed in float64 in a fixed order and rounded to float32 once; no atomics: bitwise reproducible.  Every device loop has
+ * a trip count fixed by the arguments (V, J, a workgroup's run of vertices, the number of workgroups): no convergence loop, no
+ * spin-wait, no hand-over between workgroups inside a launch.  No host synchronisation, no allocation, no memset, every output element
+ * written: capturable.  J = 1 works without posedirs.  workspace: moss_smpl_vertices_backward_workspace_bytes(V, J) device bytes
+ * (garbage afterwards).  Bad arguments return MOSS_ERR_INVALID_ARG with "moss_smpl_vertices_backward" and the field in moss_last_error().
+ */
+typedef struct moss_smpl_vertices_backward_args {
+    int32_t V, J;
+    int32_t num_betas, shapedirs_stride;
+    int32_t parents[MOSS_SMPL_FRAME_MAX_JOINTS];
+    const float* v_template;
+    const float* shapedirs;
+    const float* posedirs;                   /* may be NULL for J = 1 */
+    const float* J_regressor;
+    const float* weights;
+    const float* poses;
+    const float* shapes;                     /* may be NULL for num_betas = 0 */
+    const float* R;
+    const float* Th;
+    const float* g_world_vertex;             /* (V,3) */
+    float* g_poses;                          /* (3J) */
+    float* g_R;                              /* (3,3) */
+    float* g_Th;                             /* (3) */
+    char* workspace; size_t workspace_bytes;
+} moss_smpl_vertices_backward_args;
+int moss_smpl_vertices_backward(const moss_smpl_vertices_backward_args* args, void* stream);   /* the adjoint of smpl/smpl_numpy.py:46-98 and `xyz @ R^T + Th` */
+/* device bytes of the call's workspace (host-side arithmetic, monotonic); 0 for V <= 0 or J outside 1..64 */
+size_t moss_smpl_vertices_backward_workspace_bytes(int V, int J);
+
+/*
+ * A keypoint loss on posed vertices, value and vertex gradient in one call (additive in ABI 7).  Keypoints of any convention
+ * (OpenPose, COCO, H36M, markers glued to vertices) are a dense linear regressor over the vertices; they are compared with 2D
+ * detections in C cameras and / or with 3D points under a Geman-McClure robustifier:
+ *     X_k = sum_v regressor[k,v] world_vertex[v]
+ *     cam = RT_c [X_k, 1],  uvw = K_c cam,  u = (uvw_x / uvw_z, uvw_y / uvw_z),  r2 = |u - uv[c,k]|^2      (moss_bound_mask's cameras)
+ *     rho_s(r2) = s^2 r2 / (s^2 + r2)        (r2 itself for s <= 0: no robustifier)
+ *     loss = weight2d / (C Kp) sum_c sum_k conf[c,k] rho_sigma(r2)  +  weight3d / Kp sum_k conf3[k] rho_sigma3(|X_k - xyz_k|^2)
+ * An entry with uvw_z <= 0 contributes nothing to the value or the gradient and sets flags[c] |= 1 (moss_bound_mask's rule and bit).
+ * Inputs (DEVICE pointers, float32, contiguous): world_vertex (V,3); regressor (Kp,V); the 2D part, absent when C = 0: K (C,3,3),
+ * RT (C,3,4), uv (C,Kp,2) in pixels, conf (C,Kp) >= 0; the 3D part, absent when xyz is NULL: xyz (Kp,3), conf3 (Kp).  At least one
+ * part is present.  By value: sigma (pixels), sigma3 (metres), weight2d, weight3d; Kp = 1..MOSS_KEYPOINTS_MAX, V >= 1, C = 0..65535.
+ * Outputs: loss (1); g_world_vertex (V,3) = regressor^T g_X for a unit upstream gradient; keypoints (Kp,3) = X, or NULL; flags (C)
+ * int32, written whole (not read for C = 0).  The loss is a scalar: nothing is saved for a backward.
+ * Three launches on `stream`:
+ *   keypoints  one workgroup per keypoint sums its row of the regressor over the vertices (threads stride the vertices, then a fixed
+ *              butterfly and the waves in order); X goes to `workspace` in float64;
+ *   residuals  one workgroup per camera (one more for the 3D part), one thread per keypoint: the entry's value and its gradient to
+ *              X_k go to `workspace`, the camera's values are summed in keypoint order, flags[c] is written;
+ *   scatter    a grid over ranges of 256 vertices: every workgroup folds g_X over the cameras in camera order, workgroup 0 also the
+ *              loss; then g_world_vertex[v] = sum_k regressor[k,v] g_X[k] in keypoint order.
+ * Every sum is formed in float64 in a fixed order and rounded to float32 once; no atomics: bitwise reproducible.  Every device loop has
+ * a trip count fixed by the arguments (V, Kp, C).  No host synchronisation, no allocation, no memset, every output element written:
+ * capturable.  workspace: moss_keypoint_loss_workspace_bytes(C, Kp) device bytes (garbage afterwards).  Bad arguments return
+ * MOSS_ERR_INVALID_ARG with "moss_keypoint_loss" and the field in moss_last_error().
+ */
+#define MOSS_KEYPOINTS_MAX 128
+typedef struct moss_keypoint_loss_args {
+    int32_t V, Kp, C;
+    const float* world_vertex;
+    const float* regressor;
+    const float* K;                          /* (C,3,3); not read for C = 0 */
+    const float* RT;                         /* (C,3,4) */
+    const float* uv;                         /* (C,Kp,2) */
+    const float* conf;                       /* (C,Kp) */
+    const float* xyz;                        /* (Kp,3) or NULL: no 3D part */
+    const float* conf3;                      /* (Kp); needed with xyz */
+    float sigma, sigma3;
+    float weight2d, weight3d;
+    float* loss;
+    float* g_world_vertex;
+    float* keypoints;                        /* (Kp,3) or NULL */
+    int32_t* flags;                          /* (C) */
+    char* workspace; size_t workspace_bytes;
+} moss_keypoint_loss_args;
+int moss_keypoint_loss(const moss_keypoint_loss_args* args, void* stream);
+/* device bytes of the call's workspace (host-side arithmetic, monotonic); 0 for C outside 0..65535 or Kp outside 1..MOSS_KEYPOINTS_MAX */
+size_t moss_keypoint_loss_workspace_bytes(int C, int Kp);
+
+/*
  * MOSS's S3IM term and its gradient (additive in ABI 7): s3im_loss = s3im_fun(img_pred, img_gt) (train_ZJU.py:123, weighted 0.3 at
  * :131; utils/loss_utils.py:17-38).  MOSS hands it two (1,C,h,w) crops, so every randperm(1) is [0] and the term is deterministic:
  *     s3im = 1 - ssim(x~, y~),   x~ = the crop with every pixel repeated `repeat` times along a row (width repeat * w)

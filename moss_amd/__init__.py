@@ -3,7 +3,8 @@
 
 _LAZY = {"prepare_views": "images", "prepare_views_torch": "images",
          "BakedGaussians": "bake", "render_baked": "bake",
-         "PoseFitter": "posefit", "posed_frame": "posefit"}
+         "PoseFitter": "posefit", "posed_frame": "posefit",
+         "keypoint_loss": "keypoints", "posed_vertices_fn": "keypoints", "KeypointTargets": "keypoints"}
 
 __all__ = sorted(_LAZY)
 

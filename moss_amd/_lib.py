@@ -133,6 +133,14 @@ def _declare(lib):
     lib.moss_bound_mask_workspace_bytes.argtypes = [_i, _i, _i]
     lib.moss_bound_mask.restype = _i
     lib.moss_bound_mask.argtypes = [_p, _p]
+    lib.moss_smpl_vertices_backward_workspace_bytes.restype = C.c_size_t
+    lib.moss_smpl_vertices_backward_workspace_bytes.argtypes = [_i, _i]
+    lib.moss_smpl_vertices_backward.restype = _i
+    lib.moss_smpl_vertices_backward.argtypes = [_p, _p]
+    lib.moss_keypoint_loss_workspace_bytes.restype = C.c_size_t
+    lib.moss_keypoint_loss_workspace_bytes.argtypes = [_i, _i]
+    lib.moss_keypoint_loss.restype = _i
+    lib.moss_keypoint_loss.argtypes = [_p, _p]
     lib.moss_s3im_workspace_bytes.restype = C.c_size_t
     lib.moss_s3im_workspace_bytes.argtypes = [_i, _i, _i]
     lib.moss_s3im_loss.restype = _i
@@ -324,7 +332,30 @@ class BoundMaskArgs(C.Structure):
                 ("workspace_bytes", C.c_size_t)]
 
 
-POSE_HEAD_SAVED_FLOATS = 896                             # MOSS_POSE_HEAD_SAVED_FLOATS
+class SmplVerticesBackwardArgs(C.Structure):
+    """``moss_smpl_vertices_backward_args`` of include/moss_raster.h (``moss_smpl_vertices_backward``: the gradients of a frame's posed
+    vertices to ``poses``, ``R`` and ``Th``)."""
+    _fields_ = [("V", C.c_int32), ("J", C.c_int32), ("num_betas", C.c_int32), ("shapedirs_stride", C.c_int32),
+                ("parents", C.c_int32 * 64), ("v_template", C.c_void_p), ("shapedirs", C.c_void_p), ("posedirs", C.c_void_p),
+                ("J_regressor", C.c_void_p), ("weights", C.c_void_p), ("poses", C.c_void_p), ("shapes", C.c_void_p), ("R", C.c_void_p),
+                ("Th", C.c_void_p), ("g_world_vertex", C.c_void_p), ("g_poses", C.c_void_p), ("g_R", C.c_void_p), ("g_Th", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+KEYPOINTS_MAX = 128                                      # MOSS_KEYPOINTS_MAX
+
+
+class KeypointLossArgs(C.Structure):
+    """``moss_keypoint_loss_args`` of include/moss_raster.h (``moss_keypoint_loss``: a keypoint loss on posed vertices, value and vertex
+    gradient in one call)."""
+    _fields_ = [("V", C.c_int32), ("Kp", C.c_int32), ("C", C.c_int32), ("world_vertex", C.c_void_p), ("regressor", C.c_void_p),
+                ("K", C.c_void_p), ("RT", C.c_void_p), ("uv", C.c_void_p), ("conf", C.c_void_p), ("xyz", C.c_void_p),
+                ("conf3", C.c_void_p), ("sigma", C.c_float), ("sigma3", C.c_float), ("weight2d", C.c_float), ("weight3d", C.c_float),
+                ("loss", C.c_void_p), ("g_world_vertex", C.c_void_p), ("keypoints", C.c_void_p), ("flags", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+POSE_HEAD_SAVED_FLOATS = 896                            # MOSS_POSE_HEAD_SAVED_FLOATS
 _POSE_INPUTS = [("poses", C.c_void_p), ("target_R", C.c_void_p), ("params", C.c_void_p * 52), ("parents", C.c_int32 * 24),
                 ("fc_in", C.c_int32 * 23), ("overreg", C.c_float)]
 

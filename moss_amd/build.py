@@ -45,6 +45,7 @@ SOURCES = {
     "lbs.hip": [],
     "smpl_frame.hip": [],
     "frame_bounds.hip": [],
+    "keypoints.hip": [],
     "pose_head.hip": [],
     "lbs_weight_net.hip": [],
     "lpips.hip": [],

@@ -17,8 +17,16 @@
 //                  lanes), then tests its pixels against the six faces in int64 and writes bound; one (min x, min y, max x, max y,
 //                  count) record per workgroup.  Tile 0 of a camera writes its corners and flag.
 //   rect           one workgroup per camera folds its records.
+// moss_smpl_vertices_backward (g_poses, g_R, g_Th of a g_world_vertex), 4 launches; nothing is saved by the forward:
+//   posed          the forward's kernel as it is: v_posed and the regressor shares.
+//   skin adjoint   the skin kernel's grid and chain; one thread per vertex forms y_v, h_v = R^T g_v and g_vposed_v = T_v[:3,:3]^T h_v, then
+//                  one thread per output walks the workgroup's vertices in index order: its partial sums of g_Th, g_R and g_A.
+//   features       a grid over ranges of FB_FEAT_VPB vertices, threads over the pose features (the form of smpl_frame.hip's reduce
+//                  kernel): sum_v sum_c posedirs[v, c, k] g_vposed[v, c], one partial vector per workgroup; posedirs is read once.
+//   chain adjoint  one workgroup folds both sets of partials in a fixed order, walks the tree in reverse (smpl_frame.hip's walk on the
+//                  float64 chain recomputed here) and forms the adjoint of Rodrigues, one joint per thread.
 // Every sum is formed in float64 in a fixed order, nothing is atomic, every output element is written: bitwise reproducible.
-// Nothing is allocated, nothing synchronises, nothing is cleared with a memset.
+// Nothing is allocated, nothing synchronises, nothing is cleared with a memset.  Every loop's trip count is fixed by the arguments.
 #include "common.h"
 #include "smpl_math.h"
 #include "wave.h"
@@ -31,6 +39,7 @@ namespace {
 constexpr int FB_BLOCK = 256;
 constexpr int FB_SKIN_BLOCK = 1024;
 constexpr int FB_SKIN_VPB = 256;          // vertices per workgroup of the skin kernel: four lanes each (three rows, one idle)
+constexpr int FB_FEAT_VPB = 32;           // vertices per workgroup of the backward's feature kernel
 constexpr int FB_TILE_W = 64, FB_TILE_H = 8;
 constexpr int FB_ROWS = FB_TILE_H / (FB_BLOCK / 64);    // rows of a tile per wave
 constexpr int FB_CLAMP = 1 << 20;
@@ -78,6 +87,29 @@ frame_bounds_posed_kernel(FbIn a, double* __restrict__ vposed, double* __restric
     smpl_pose_blend_rows<FB_BLOCK>(a.pd, s_f, F, v0, nrows, [&](int r, double acc) { vposed[(size_t)v0 * 3 + r] = s_vs[0][r] + acc; });
 }
 
+// a workgroup of FB_SKIN_BLOCK threads: the rotations, the joints (the shares folded in a fixed order), the relative joints, the chain
+// s_G (per joint: the rotation (9, row-major), then the translation (3)) and, unless s_A is null, rows 0..2 of A_j (3 x 4, row-major).
+// The caller's next barrier publishes s_A.
+__device__ __forceinline__ void fb_stage_chain(const FbIn& a, const SmplParents& par, int nparts, const double* __restrict__ partials,
+                                               float* s_rot, double* s_slice, double (*s_jt)[SMPL_MAX_J * 3],
+                                               double (*s_rel)[SMPL_MAX_J * 3], double* s_G, double* s_A)
+{
+    const int t = threadIdx.x;
+    const int J = a.J;
+    for (int j = t; j < J; j += FB_SKIN_BLOCK) sf_rodrigues(a.poses + 3 * j, s_rot + 9 * j);
+    smpl_fold_shares<1, FB_SKIN_BLOCK>(J, nparts, partials, s_slice, s_jt);         // (nslice >= 5; its first barrier covers s_rot)
+    smpl_relative_joints<1>(J, par, s_jt, s_rel);
+    for (int j = 0; j < J; j++) {
+        if (t < 12) smpl_chain_step(j, t, par, s_rot + 9 * j, s_rel[0] + 3 * j, s_G);
+        __syncthreads();
+    }
+    if (!s_A) return;
+    for (int o = t; o < J * 12; o += FB_SKIN_BLOCK) {
+        const int j = o / 12;
+        s_A[o] = smpl_A_entry(s_G + 12 * j, s_jt[0] + 3 * j, (o % 12) / 4, o % 4);
+    }
+}
+
 // every workgroup: the joints (the shares folded in a fixed order), the chain, A; then its vertices and their min / max record
 __global__ void __launch_bounds__(FB_SKIN_BLOCK)
 frame_bounds_skin_kernel(FbIn a, SmplParents par, int nparts, const double* __restrict__ partials, const double* __restrict__ vposed,
@@ -86,23 +118,13 @@ frame_bounds_skin_kernel(FbIn a, SmplParents par, int nparts, const double* __re
     __shared__ float s_rot[SMPL_MAX_J * 9];
     __shared__ double s_slice[FB_SKIN_BLOCK];
     __shared__ double s_jt[1][SMPL_MAX_J * 3], s_rel[1][SMPL_MAX_J * 3];
-    __shared__ double s_G[SMPL_MAX_J * 12];                    // per joint: the chain's rotation (9, row-major), then its translation (3)
-    __shared__ double s_A[SMPL_MAX_J * 12];                    // per joint: rows 0..2 of A_j (3 x 4, row-major)
+    __shared__ double s_G[SMPL_MAX_J * 12];
+    __shared__ double s_A[SMPL_MAX_J * 12];
     __shared__ double s_p[FB_SKIN_VPB * 3];
     __shared__ float s_mm[FB_SKIN_BLOCK / 64][6];
     const int t = threadIdx.x;
     const int J = a.J, nout = J * 3;
-    for (int j = t; j < J; j += FB_SKIN_BLOCK) sf_rodrigues(a.poses + 3 * j, s_rot + 9 * j);
-    smpl_fold_shares<1, FB_SKIN_BLOCK>(J, nparts, partials, s_slice, s_jt);         // (nslice >= 5; its first barrier covers s_rot)
-    smpl_relative_joints<1>(J, par, s_jt, s_rel);
-    for (int j = 0; j < J; j++) {
-        if (t < 12) smpl_chain_step(j, t, par, s_rot + 9 * j, s_rel[0] + 3 * j, s_G);
-        __syncthreads();
-    }
-    for (int o = t; o < J * 12; o += FB_SKIN_BLOCK) {
-        const int j = o / 12;
-        s_A[o] = smpl_A_entry(s_G + 12 * j, s_jt[0] + 3 * j, (o % 12) / 4, o % 4);
-    }
+    fb_stage_chain(a, par, nparts, partials, s_rot, s_slice, s_jt, s_rel, s_G, s_A);
     if (joints && blockIdx.x == 0 && t < nout) joints[t] = (float)s_G[12 * (t / 3) + 9 + t % 3];
     __syncthreads();
     const int vl = t >> 2, r = t & 3;
@@ -155,6 +177,191 @@ frame_bounds_fold_kernel(int nrecords, const float* __restrict__ records, const 
     for (int b = 1; b < nrecords; b++) m = t < 3 ? fminf(m, records[(size_t)b * 6 + t]) : fmaxf(m, records[(size_t)b * 6 + t]);
     const float p = pad[0];
     world_bound[t] = t < 3 ? m - p : m + p;
+}
+
+// ---- moss_smpl_vertices_backward ---------------------------------------------------------------------------------------------------
+
+// the skin kernel's grid: g_vposed rows of vertices [FB_SKIN_VPB b, FB_SKIN_VPB (b + 1)) and sums [workgroup][12 J + 12]: the workgroup's
+// share of g_A (J x 3 x 4), then of g_R (9), then of g_Th (3), its vertices taken in index order
+__global__ void __launch_bounds__(FB_SKIN_BLOCK)
+frame_bounds_skin_backward_kernel(FbIn a, SmplParents par, int nparts, const double* __restrict__ partials, const double* __restrict__ vposed,
+                                  const float* __restrict__ g_world, double* __restrict__ g_vposed, double* __restrict__ sums)
+{
+    __shared__ float s_rot[SMPL_MAX_J * 9];
+    __shared__ double s_slice[FB_SKIN_BLOCK];
+    __shared__ double s_jt[1][SMPL_MAX_J * 3], s_rel[1][SMPL_MAX_J * 3];
+    __shared__ double s_G[SMPL_MAX_J * 12];
+    __shared__ double s_A[SMPL_MAX_J * 12];
+    __shared__ double s_vp[FB_SKIN_VPB * 3], s_y[FB_SKIN_VPB * 3], s_g[FB_SKIN_VPB * 3], s_h[FB_SKIN_VPB * 3];
+    const int t = threadIdx.x;
+    const int J = a.J;
+    fb_stage_chain(a, par, nparts, partials, s_rot, s_slice, s_jt, s_rel, s_G, s_A);
+    __syncthreads();
+    const int v0 = blockIdx.x * FB_SKIN_VPB;
+    const int nv = min(FB_SKIN_VPB, a.V - v0);
+    if (t < nv) {
+        const int v = v0 + t;
+        const float* w = a.w + (size_t)v * J;
+        double T[12];
+#pragma unroll
+        for (int e = 0; e < 12; e++) T[e] = 0.0;
+#pragma unroll 4
+        for (int j = 0; j < J; j++) {
+            const double wj = (double)w[j];
+            const double* A = s_A + 12 * j;
+#pragma unroll
+            for (int e = 0; e < 12; e++) T[e] = fma(wj, A[e], T[e]);
+        }
+        const double* vp = vposed + (size_t)v * 3;
+        const double p0 = vp[0], p1 = vp[1], p2 = vp[2];
+        const float* gw = g_world + (size_t)v * 3;
+        const double g0 = (double)gw[0], g1 = (double)gw[1], g2 = (double)gw[2];
+        double h[3];
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            h[c] = (double)a.R[c] * g0 + (double)a.R[3 + c] * g1 + (double)a.R[6 + c] * g2;                     // R^T g
+            s_y[3 * t + c] = T[4 * c] * p0 + T[4 * c + 1] * p1 + T[4 * c + 2] * p2 + T[4 * c + 3];
+        }
+        s_vp[3 * t] = p0; s_vp[3 * t + 1] = p1; s_vp[3 * t + 2] = p2;
+        s_g[3 * t] = g0; s_g[3 * t + 1] = g1; s_g[3 * t + 2] = g2;
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            s_h[3 * t + c] = h[c];
+            g_vposed[(size_t)v * 3 + c] = T[c] * h[0] + T[4 + c] * h[1] + T[8 + c] * h[2];                      // T[:3,:3]^T h
+        }
+    }
+    __syncthreads();
+    const int nsum = 12 * J + 12;
+    if (t >= nsum) return;
+    double acc = 0.0;
+    if (t < 12 * J) {                                          // g_A_j[r][c] = sum_v w[v, j] h_v[r] [v_posed_v, 1][c]
+        const int j = t / 12, r = (t % 12) / 4, c = t % 4;
+        const float* w = a.w + (size_t)v0 * J + j;
+#pragma unroll 8
+        for (int i = 0; i < nv; i++) {                        // (unrolled: eight weights in flight; the order of the sum is the loop's)
+            const double wh = (double)w[(size_t)i * J] * s_h[3 * i + r];
+            acc = c < 3 ? fma(wh, s_vp[3 * i + c], acc) : acc + wh;
+        }
+    } else if (t < 12 * J + 9) {                               // g_R[r][c] = sum_v g_v[r] y_v[c]
+        const int r = (t - 12 * J) / 3, c = (t - 12 * J) % 3;
+        for (int i = 0; i < nv; i++) acc = fma(s_g[3 * i + r], s_y[3 * i + c], acc);
+    } else {                                                   // g_Th[r] = sum_v g_v[r]
+        const int r = t - 12 * J - 9;
+        for (int i = 0; i < nv; i++) acc += s_g[3 * i + r];
+    }
+    sums[(size_t)blockIdx.x * nsum + t] = acc;
+}
+
+// fpartials[workgroup][k] = sum over the workgroup's vertices, in index order, of sum_c posedirs[v, c, k] g_vposed[v, c]
+__global__ void __launch_bounds__(FB_BLOCK)
+frame_bounds_feature_backward_kernel(int V, int F, const float* __restrict__ pd, const double* __restrict__ g_vposed,
+                                     double* __restrict__ fpartials)
+{
+    __shared__ double s_g[FB_FEAT_VPB * 3];
+    const int t = threadIdx.x;
+    const int v0 = blockIdx.x * FB_FEAT_VPB;
+    const int n = min(FB_FEAT_VPB, V - v0);
+    if (t < n * 3) s_g[t] = g_vposed[(size_t)v0 * 3 + t];
+    __syncthreads();
+    double acc[3] = {0.0, 0.0, 0.0};
+#pragma unroll 4
+    for (int q = 0; q < n; q++) {
+        const float* row = pd + (size_t)(v0 + q) * 3 * F;
+        const double g0 = s_g[3 * q], g1 = s_g[3 * q + 1], g2 = s_g[3 * q + 2];
+#pragma unroll
+        for (int s = 0; s < 3; s++) {
+            const int k = t + FB_BLOCK * s;
+            if (k < F) acc[s] = fma((double)row[k], g0, fma((double)row[F + k], g1, fma((double)row[2 * F + k], g2, acc[s])));
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < 3; s++) {
+        const int k = t + FB_BLOCK * s;
+        if (k < F) fpartials[(size_t)blockIdx.x * F + k] = acc[s];
+    }
+}
+
+// one workgroup: both sets of partials folded in a fixed order, g_R and g_Th written; then the adjoint of the chain as
+// smpl_frame.hip's chain adjoint states it (gGR_j = gA_j[:3,:3] - gA_j[:3,3] joint_j^T, gGt_j = gA_j[:3,3]; j = J-1 .. 1:
+// g_rot_j = GR_p^T gGR_j, gGR_p += gGR_j rot_j^T + gGt_j rel_j^T, gGt_p += gGt_j; g_rot_0 = gGR_0) on the chain recomputed here in
+// float64, g_raw_j = g_rot_j + g_feat_j, and the adjoint of Rodrigues, one joint per thread
+__global__ void __launch_bounds__(FB_SKIN_BLOCK)
+frame_bounds_chain_backward_kernel(FbIn a, SmplParents par, int nparts, const double* __restrict__ partials, int nskin,
+                                   const double* __restrict__ sums, int nfeat, const double* __restrict__ fpartials,
+                                   float* __restrict__ g_poses, float* __restrict__ g_R, float* __restrict__ g_Th)
+{
+    __shared__ float s_rot[SMPL_MAX_J * 9];
+    __shared__ double s_slice[FB_SKIN_BLOCK];
+    __shared__ double s_jt[1][SMPL_MAX_J * 3], s_rel[1][SMPL_MAX_J * 3];
+    __shared__ double s_G[SMPL_MAX_J * 12];
+    __shared__ double s_gA[SMPL_MAX_J * 12];
+    __shared__ double s_gGR[SMPL_MAX_J * 9], s_gGt[SMPL_MAX_J * 3], s_gR[SMPL_MAX_J * 9];
+    const int t = threadIdx.x;
+    const int J = a.J;
+    fb_stage_chain(a, par, nparts, partials, s_rot, s_slice, s_jt, s_rel, s_G, nullptr);
+    // g_feat as smpl_fold_shares folds the joints: the feature partials cut into nslice = FB_SKIN_BLOCK / F runs of workgroups, each
+    // summed in order (here), then the runs in order (after the walk) -- a function of V and J only
+    const int F = 9 * (J - 1);
+    const int nslice = F ? FB_SKIN_BLOCK / F : 0;
+    if (t < F * nslice) {
+        const int k = t % F, sl = t / F;
+        const int per = (nfeat + nslice - 1) / nslice;
+        const int b1 = min(nfeat, (sl + 1) * per);
+        double acc = 0.0;
+#pragma unroll 8
+        for (int b = sl * per; b < b1; b++) acc += fpartials[(size_t)b * F + k];
+        s_slice[t] = acc;
+    }
+    const int nsum = 12 * J + 12;
+    for (int o = t; o < nsum; o += FB_SKIN_BLOCK) {
+        double acc = 0.0;
+#pragma unroll 9
+        for (int b = 0; b < nskin; b++) acc += sums[(size_t)b * nsum + o];
+        if (o < 12 * J) s_gA[o] = acc;
+        else if (o < 12 * J + 9) g_R[o - 12 * J] = (float)acc;
+        else g_Th[o - 12 * J - 9] = (float)acc;
+    }
+    __syncthreads();
+    const double* jt = s_jt[0];
+    const double* rel = s_rel[0];
+    for (int e = t; e < J * 12; e += FB_SKIN_BLOCK) {
+        const int j = e / 12, q = e % 12;
+        if (q < 9) {
+            const int r = q / 3, c = q % 3;
+            s_gGR[9 * j + q] = s_gA[12 * j + 4 * r + c] - s_gA[12 * j + 4 * r + 3] * jt[3 * j + c];
+            s_gR[9 * j + q] = 0.0;
+        } else {
+            s_gGt[3 * j + q - 9] = s_gA[12 * j + 4 * (q - 9) + 3];
+        }
+    }
+    __syncthreads();
+    for (int j = J - 1; j >= 1; j--) {
+        const int p = par.p[j];
+        if (t < 9) {
+            const int r = t / 3, c = t % 3;
+            const double* g = s_gGR + 9 * j;
+            const double* GRp = s_G + 12 * p;
+            s_gR[9 * j + t] = GRp[r] * g[c] + GRp[3 + r] * g[3 + c] + GRp[6 + r] * g[6 + c];
+            const float* Rj = s_rot + 9 * j;
+            s_gGR[9 * p + t] += g[3 * r] * (double)Rj[3 * c] + g[3 * r + 1] * (double)Rj[3 * c + 1] + g[3 * r + 2] * (double)Rj[3 * c + 2]
+                              + s_gGt[3 * j + r] * rel[3 * j + c];
+        } else if (t < 12) {
+            s_gGt[3 * p + t - 9] += s_gGt[3 * j + t - 9];
+        }
+        __syncthreads();
+    }
+    for (int k = t; k < F; k += FB_SKIN_BLOCK) {
+        double acc = 0.0;
+        for (int sl = 0; sl < nslice; sl++) acc += s_slice[sl * F + k];
+        s_gR[9 + k] += acc;
+    }
+    if (t < 9) s_gR[t] = s_gGR[t];                            // (thread t wrote s_gGR[t] itself in the walk's last steps)
+    __syncthreads();
+    if (t >= J) return;
+    double G[9];
+#pragma unroll
+    for (int e = 0; e < 9; e++) G[e] = s_gR[9 * t + e];
+    smpl_rodrigues_adjoint(G, a.poses + 3 * t, g_poses + 3 * t);
 }
 
 // (min x, min y, max x, max y, count) of a workgroup from its threads' values; valid in thread 0
@@ -301,6 +508,23 @@ size_t fb_vertices_bytes(int V, int J)
     return align_up((size_t)V * 3 * sizeof(double)) + align_up(nparts * (size_t)J * 3 * sizeof(double)) + align_up(nskin * 6 * sizeof(float));
 }
 
+struct FbBackwardCounts { size_t nparts, nskin, nfeat, nsum, F; };
+
+FbBackwardCounts fb_backward_counts(int V, int J)
+{
+    const size_t F = 9 * (size_t)(J - 1);
+    return {((size_t)V + SMPL_VPB - 1) / SMPL_VPB, ((size_t)V + FB_SKIN_VPB - 1) / FB_SKIN_VPB,
+            F ? ((size_t)V + FB_FEAT_VPB - 1) / FB_FEAT_VPB : 0, 12 * (size_t)J + 12, F};
+}
+
+// v_posed, the regressor shares, g_vposed, the skin adjoint's sums, the feature partials
+size_t fb_backward_bytes(int V, int J)
+{
+    const FbBackwardCounts n = fb_backward_counts(V, J);
+    return 2 * align_up((size_t)V * 3 * sizeof(double)) + align_up(n.nparts * (size_t)J * 3 * sizeof(double))
+         + align_up(n.nskin * n.nsum * sizeof(double)) + align_up(n.nfeat * n.F * sizeof(double));
+}
+
 size_t fb_tiles(int H, int W) { return (((size_t)W + FB_TILE_W - 1) / FB_TILE_W) * (((size_t)H + FB_TILE_H - 1) / FB_TILE_H); }
 
 }  // namespace
@@ -343,6 +567,50 @@ extern "C" int moss_smpl_vertices(const moss_smpl_vertices_args* a, void* stream
     hipLaunchKernelGGL(frame_bounds_skin_kernel, dim3(nskin), dim3(FB_SKIN_BLOCK), 0, s, in, par, nparts, (const double*)partials,
                        (const double*)vposed, a->world_vertex, a->joints, records);
     hipLaunchKernelGGL(frame_bounds_fold_kernel, dim3(1), dim3(64), 0, s, nskin, (const float*)records, a->pad, a->world_bound);
+    return launch_status(who);
+}
+
+extern "C" size_t moss_smpl_vertices_backward_workspace_bytes(int V, int J)
+{
+    if (V <= 0 || J < 1 || J > SMPL_MAX_J) return 0;
+    return fb_backward_bytes(V, J);
+}
+
+extern "C" int moss_smpl_vertices_backward(const moss_smpl_vertices_backward_args* a, void* stream)
+{
+    const char* who = "moss_smpl_vertices_backward";
+    if (!a) return invalid_arg(who, "null argument block");
+    if (a->V < 1) return invalid_arg(who, "V must be >= 1");
+    if (a->J < 1 || a->J > SMPL_MAX_J) return invalid_arg(who, "J must be 1..64");
+    if (a->num_betas < 0 || a->num_betas > a->shapedirs_stride) return invalid_arg(who, "num_betas must be 0..shapedirs_stride");
+    if (!a->v_template || !a->shapedirs || !a->J_regressor || !a->weights || (a->J > 1 && !a->posedirs))
+        return invalid_arg(who, "null body-model array (v_template, shapedirs, posedirs, J_regressor, weights)");
+    if (!a->poses || !a->R || !a->Th || (a->num_betas > 0 && !a->shapes)) return invalid_arg(who, "null frame input (poses, shapes, R, Th)");
+    if (!a->g_world_vertex) return invalid_arg(who, "null g_world_vertex");
+    if (!a->g_poses || !a->g_R || !a->g_Th) return invalid_arg(who, "null output (g_poses, g_R, g_Th)");
+    if (int rc = smpl_check_parents(who, a->J, a->parents)) return rc;
+    if (!a->workspace || a->workspace_bytes < fb_backward_bytes(a->V, a->J))
+        return invalid_arg(who, "needs moss_smpl_vertices_backward_workspace_bytes(V, J) bytes of workspace");
+    hipStream_t s = (hipStream_t)stream;
+    const FbIn in{a->V, a->J, a->num_betas, a->shapedirs_stride, a->v_template, a->shapedirs, a->posedirs, a->J_regressor, a->weights,
+                  a->poses, a->shapes, a->R, a->Th};
+    const SmplParents par = smpl_parents(a);
+    const FbBackwardCounts n = fb_backward_counts(a->V, a->J);
+    char* p = a->workspace;
+    double* vposed = carve<double>(p, (size_t)a->V * 3);
+    double* partials = carve<double>(p, n.nparts * a->J * 3);
+    double* g_vposed = carve<double>(p, (size_t)a->V * 3);
+    double* sums = carve<double>(p, n.nskin * n.nsum);
+    double* fpartials = carve<double>(p, n.nfeat * n.F);
+    hipLaunchKernelGGL(frame_bounds_posed_kernel, dim3((unsigned)n.nparts), dim3(FB_BLOCK), 0, s, in, vposed, partials);
+    hipLaunchKernelGGL(frame_bounds_skin_backward_kernel, dim3((unsigned)n.nskin), dim3(FB_SKIN_BLOCK), 0, s, in, par, (int)n.nparts,
+                       (const double*)partials, (const double*)vposed, a->g_world_vertex, g_vposed, sums);
+    if (n.nfeat)
+        hipLaunchKernelGGL(frame_bounds_feature_backward_kernel, dim3((unsigned)n.nfeat), dim3(FB_BLOCK), 0, s, a->V, (int)n.F, a->posedirs,
+                           (const double*)g_vposed, fpartials);
+    hipLaunchKernelGGL(frame_bounds_chain_backward_kernel, dim3(1), dim3(FB_SKIN_BLOCK), 0, s, in, par, (int)n.nparts,
+                       (const double*)partials, (int)n.nskin, (const double*)sums, (int)n.nfeat, (const double*)fpartials, a->g_poses,
+                       a->g_R, a->g_Th);
     return launch_status(who);
 }
 

@@ -206,10 +206,7 @@ smpl_frame_fold_kernel(int F, int nblocks, const double* __restrict__ partials, 
 // g_rot_j = GR_p^T gGR_j, gGR_p += gGR_j rot_j^T + gGt_j rel_j^T, gGt_p += gGt_j.
 //
 // POSE (moss_smpl_frame_backward_pose; the other instantiation never reads poses, cR, g_poses): the root keeps g_rot_0 = gGR_0 (G_0.R = rot_0), and joint j (one per thread) forms
-// g_raw_j = g_rot_j cR_j^T (cR_0 = I; cR = NULL: all I) and the adjoint of r -> raw = I + s K + c K K, e = r + 1e-8, a = |e|, k = r / a,
-// s = sin a, c = 1 - cos a (K K = k k^T - |k|^2 I; the shift is in the norm only):
-//   g_s = <G, K>, g_c = <G, K K>, gK = s G + c (G K^T + K^T G), g_k = (gK_21 - gK_12, gK_02 - gK_20, gK_10 - gK_01),
-//   g_a = g_s cos a + g_c sin a - <g_k, r> / a^2,  g_r = g_k / a + g_a e / a.
+// g_raw_j = g_rot_j cR_j^T (cR_0 = I; cR = NULL: all I) and the adjoint of Rodrigues (smpl_math.h smpl_rodrigues_adjoint).
 template <bool POSE>
 __global__ void __launch_bounds__(SF_BLOCK)
 smpl_frame_chain_backward_kernel(int J, SmplParents par, const float* __restrict__ saved, const float* __restrict__ gA,
@@ -282,33 +279,7 @@ smpl_frame_chain_backward_kernel(int J, SmplParents par, const float* __restrict
             for (int e = 0; e < 9; e++) G[e] = g[e];
         }
     }
-    const double rx = (double)poses[3 * j], ry = (double)poses[3 * j + 1], rz = (double)poses[3 * j + 2];
-    const double ex = rx + 1e-8, ey = ry + 1e-8, ez = rz + 1e-8;
-    const double a = sqrt(ex * ex + ey * ey + ez * ez);
-    const double kx = rx / a, ky = ry / a, kz = rz / a;
-    const double sh = sin(0.5 * a), sn = sin(a), cs = cos(a);
-    const double cc = 2.0 * sh * sh;                           // 1 - cos a, without the cancellation at small angles
-    const double K[9] = {0.0, -kz, ky, kz, 0.0, -kx, -ky, kx, 0.0};
-    const double kk = kx * kx + ky * ky + kz * kz;
-    const double KK[9] = {kx * kx - kk, kx * ky, kx * kz, kx * ky, ky * ky - kk, ky * kz, kx * kz, ky * kz, kz * kz - kk};
-    double g_s = 0.0, g_c = 0.0;
-#pragma unroll
-    for (int e = 0; e < 9; e++) { g_s = fma(G[e], K[e], g_s); g_c = fma(G[e], KK[e], g_c); }
-    double gK[9];
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            // (G K^T)_rc = sum_q G_rq K_cq;  (K^T G)_rc = sum_q K_qr G_qc
-            const double gkt = G[3 * r] * K[3 * c] + G[3 * r + 1] * K[3 * c + 1] + G[3 * r + 2] * K[3 * c + 2];
-            const double ktg = K[r] * G[c] + K[3 + r] * G[3 + c] + K[6 + r] * G[6 + c];
-            gK[3 * r + c] = sn * G[3 * r + c] + cc * (gkt + ktg);
-        }
-    const double gkx = gK[7] - gK[5], gky = gK[2] - gK[6], gkz = gK[3] - gK[1];
-    const double g_a = g_s * cs + g_c * sn - (gkx * rx + gky * ry + gkz * rz) / (a * a);
-    g_poses[3 * j] = (float)(gkx / a + g_a * ex / a);
-    g_poses[3 * j + 1] = (float)(gky / a + g_a * ey / a);
-    g_poses[3 * j + 2] = (float)(gkz / a + g_a * ez / a);
+    smpl_rodrigues_adjoint(G, poses + 3 * j, g_poses + 3 * j);
 }
 
 size_t sf_forward_bytes(int V, int J)

@@ -1,4 +1,4 @@
-// smpl_math.h -- what the per-frame SMPL kernels (smpl_frame.hip, frame_bounds.hip) share: Rodrigues, the parents table and its check,
+// smpl_math.h -- what the per-frame SMPL kernels (smpl_frame.hip, frame_bounds.hip) share: Rodrigues and its adjoint, the parents table and its check,
 // and the steps of the skeleton that both files take -- the shaped template and regressor shares of a range of vertices, its
 // pose-blend rows, the fold of the shares into joints, the relative joints, a step of the chain and an entry of A.  The steps are
 // templated on S, the number of shape sets a kernel carries: 2 in smpl_frame.hip (the big pose's, the frame's), 1 in frame_bounds.hip.
@@ -41,6 +41,41 @@ __device__ __forceinline__ void sf_rodrigues(const float* r, float* R)
     R[0] = 1.0f - c * (ny * ny + nz * nz); R[1] = c * (nx * ny) - s * nz;          R[2] = c * (nx * nz) + s * ny;
     R[3] = c * (nx * ny) + s * nz;          R[4] = 1.0f - c * (nx * nx + nz * nz); R[5] = c * (ny * nz) - s * nx;
     R[6] = c * (nx * nz) - s * ny;          R[7] = c * (ny * nz) + s * nx;          R[8] = 1.0f - c * (nx * nx + ny * ny);
+}
+
+// the adjoint of r -> raw = I + s K + c K K, e = r + 1e-8, a = |e|, k = r / a, s = sin a, c = 1 - cos a (K K = k k^T - |k|^2 I; the
+// shift is in the norm only), for the cotangent G of raw:
+//   g_s = <G, K>, g_c = <G, K K>, gK = s G + c (G K^T + K^T G), g_k = (gK_21 - gK_12, gK_02 - gK_20, gK_10 - gK_01),
+//   g_a = g_s cos a + g_c sin a - <g_k, r> / a^2,  g_r = g_k / a + g_a e / a.
+__device__ __forceinline__ void smpl_rodrigues_adjoint(const double* G, const float* r, float* g_r)
+{
+    const double rx = (double)r[0], ry = (double)r[1], rz = (double)r[2];
+    const double ex = rx + 1e-8, ey = ry + 1e-8, ez = rz + 1e-8;
+    const double a = sqrt(ex * ex + ey * ey + ez * ez);
+    const double kx = rx / a, ky = ry / a, kz = rz / a;
+    const double sh = sin(0.5 * a), sn = sin(a), cs = cos(a);
+    const double cc = 2.0 * sh * sh;                           // 1 - cos a, without the cancellation at small angles
+    const double K[9] = {0.0, -kz, ky, kz, 0.0, -kx, -ky, kx, 0.0};
+    const double kk = kx * kx + ky * ky + kz * kz;
+    const double KK[9] = {kx * kx - kk, kx * ky, kx * kz, kx * ky, ky * ky - kk, ky * kz, kx * kz, ky * kz, kz * kz - kk};
+    double g_s = 0.0, g_c = 0.0;
+#pragma unroll
+    for (int e = 0; e < 9; e++) { g_s = fma(G[e], K[e], g_s); g_c = fma(G[e], KK[e], g_c); }
+    double gK[9];
+#pragma unroll
+    for (int r_ = 0; r_ < 3; r_++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            // (G K^T)_rc = sum_q G_rq K_cq;  (K^T G)_rc = sum_q K_qr G_qc
+            const double gkt = G[3 * r_] * K[3 * c] + G[3 * r_ + 1] * K[3 * c + 1] + G[3 * r_ + 2] * K[3 * c + 2];
+            const double ktg = K[r_] * G[c] + K[3 + r_] * G[3 + c] + K[6 + r_] * G[6 + c];
+            gK[3 * r_ + c] = sn * G[3 * r_ + c] + cc * (gkt + ktg);
+        }
+    const double gkx = gK[7] - gK[5], gky = gK[2] - gK[6], gkz = gK[3] - gK[1];
+    const double g_a = g_s * cs + g_c * sn - (gkx * rx + gky * ry + gkz * rz) / (a * a);
+    g_r[0] = (float)(gkx / a + g_a * ex / a);
+    g_r[1] = (float)(gky / a + g_a * ey / a);
+    g_r[2] = (float)(gkz / a + g_a * ez / a);
 }
 
 // this workgroup's share of J_regressor v_shaped for its nv vertices from v0, per shape set: partials [workgroup][J][S][3]

@@ -14,6 +14,7 @@ opposite: the avatar is data and the frame's parameters are the variables.
   :func:`posed_frame` has no CPU path.
 * :class:`PoseFitter` -- ``fit(cameras, gt_images, regions, smpl_param, steps)``: render through the rasterizer with ``transforms`` /
   ``translation`` in the op, MOSS's photometric loss on the view's region, one AdamW launch per step; eager or replayed from a hipGraph.
+  ``fit(..., keypoints=, photometric=)`` adds or substitutes the keypoint term of ``moss_amd.keypoints``.
 
 What is differentiated: the Rodrigues of ``poses``, the kinematic chain, the pose blend shapes' offsets gathered at the Gaussians'
 vertices, the blend of ``A_obs``, ``R`` and ``Th``.  What is held fixed: ``shapes``, the body model, the big pose, the Gaussians, and --
@@ -144,6 +145,11 @@ class PoseFitter:
     callable ``(image, alpha, gt_image, bkgd_mask, region) -> scalar``), the backward, and ``optim.AdamW`` (``weight_decay=0``): one
     launch for the leaves.
 
+    ``fit(..., keypoints=targets)`` adds ``keypoints.keypoint_loss(keypoints.posed_vertices_fn(body, params), targets)`` of the RAW
+    ``poses``, ``R`` and ``Th`` to the loss (the vertices ``player.frame``'s region uses and a detector saw: the refined rotations
+    and the LBS offsets do not enter it); ``photometric=False`` leaves that term alone -- no networks, no ``posed_frame``, no render:
+    the initialisation from far away, where the photometric term has no overlap to descend on.
+
     ``capture=True``: everything of the step but the update is a ``GraphedStep``; a replay followed by the (eager, one-launch) update
     equals the eager step bit for bit (``optim.AdamW`` takes its step count as a launch argument, so it stays outside the graph).  A
     new target, camera or start is loaded by ``copy_`` into static tensors; other intrinsics or another number of cameras capture again.
@@ -207,20 +213,25 @@ class PoseFitter:
                 _, ids = pc.knn(view.big_pose_world_vertex[None].float(), x[None])
                 self.vert_ids = ids.reshape(-1).contiguous()
         self._views = []                                         # per camera: SimpleNamespace(camera, context, pipe, gt, mask, region, has_mask)
+        self._kp = None                                          # the fit's static KeypointTargets, or None
+        self._photometric = True
         self._key = None
         self._graphed = None
         self.captures = 0
 
     # ---- static inputs ----------------------------------------------------------------------------------------------------------------
-    def _load_views(self, cameras, gt_images, regions):
+    def _load_views(self, cameras, gt_images, regions, keypoints=None, photometric=True):
         from .gaussian_renderer import intrinsics_of, static_view
         from .loss import ViewRegion
         key = tuple(intrinsics_of(c) for c in cameras) + tuple(r is not None for r in regions) \
             + tuple(isinstance(g, (tuple, list)) for g in gt_images)
+        if keypoints is not None or not photometric:             # (C, Kp, V, has 2D, has 3D, the four scalars), photometric
+            key += (None if keypoints is None else keypoints.key, photometric)
         if key != self._key:
             if self._graphed is not None:
                 torch.cuda.synchronize(self.device)
             self._graphed, self._views, self._key = None, [], key
+            self._kp, self._photometric = None if keypoints is None else keypoints.clone(), photometric
             for cam, region in zip(cameras, regions):
                 H, W = intrinsics_of(cam)[:2]
                 camera, cx, pipe = static_view(intrinsics_of(cam), {k: torch.empty_like(getattr(cam, k)) for k in
@@ -243,6 +254,8 @@ class PoseFitter:
                     v.mask.copy_(mask.reshape(v.mask.shape))
                 if region is not None:
                     v.region.copy_(region)
+        if keypoints is not None:
+            self._kp.copy_(keypoints)
 
     def _load_start(self, smpl_param):
         J = self.J
@@ -284,6 +297,8 @@ class PoseFitter:
 
     def _compute(self):
         """The loss of the static inputs and its gradients into the leaves' static ``.grad`` tensors; returns the detached loss."""
+        if not self._photometric:
+            return self._compute_keypoints_only()
         from .gaussian_renderer import render
         pc, J = self.pc, self.J
         frozen = self._frozen_model()
@@ -306,6 +321,23 @@ class PoseFitter:
             out = render(v.camera, frozen, v.pipe, self.bg, transforms=T, translation=t)
             term = self._view_loss(v, out)
             loss = term if loss is None else loss + term
+        if self._kp is not None:
+            loss = loss + self._keypoint_term(params)
+        for p in self._leaves:
+            p.grad.zero_()
+        loss.backward()
+        return loss.detach()
+
+    def _keypoint_term(self, params):
+        """The keypoint loss of the RAW ``poses``, ``R`` and ``Th`` (what ``player.frame``'s region uses and what a detector saw: the
+        refined rotations and the LBS offsets do not enter)."""
+        from .keypoints import keypoint_loss, posed_vertices_fn
+        return keypoint_loss(posed_vertices_fn(self.body, params), self._kp)
+
+    def _compute_keypoints_only(self):
+        """``_compute`` without the photometric term: no networks, no ``posed_frame``, no render."""
+        R = batch_rodrigues(self.Rh[None])[0] if self.fit_R else self.R
+        loss = self._keypoint_term({"poses": self.poses, "shapes": self.shapes, "R": R.contiguous(), "Th": self.Th})
         for p in self._leaves:
             p.grad.zero_()
         loss.backward()
@@ -318,11 +350,27 @@ class PoseFitter:
         self.optimizer.step()
         return loss
 
-    def fit(self, cameras, gt_images, regions, smpl_param, steps):
+    def fit(self, cameras, gt_images, regions, smpl_param, steps, keypoints=None, photometric=True):
         """Fit the frame seen by ``cameras`` (one camera or a list of cameras of the same frame) to ``gt_images`` (per camera a
         (3,H,W) image, or an ``(image, bkgd_mask)`` pair: without a mask the loss has no alpha term) on ``regions`` (per camera a
         ``loss.ViewRegion`` or None), starting from ``smpl_param`` (``poses``, ``shapes``, ``R``, ``Th``; ``Rh`` if it has one, else
-        the axis-angle of ``R``), for ``steps`` steps.  See the class for what comes back."""
+        the axis-angle of ``R``), for ``steps`` steps.  See the class for what comes back.
+
+        ``keypoints``: a ``keypoints.KeypointTargets`` on the model's GPU over the body's V vertices; the step then adds
+        ``keypoint_loss(posed_vertices_fn(body, params), keypoints)`` of the raw ``poses``, ``R`` and ``Th`` to the loss (its cameras
+        are the targets' own ``K`` / ``RT``).  ``photometric=False`` (needs ``keypoints``): the step is that term alone -- no networks,
+        no ``posed_frame``, no render; ``cameras``, ``gt_images`` and ``regions`` may be None: the initialisation from far away.  New
+        targets of the same sizes are loaded by ``copy_``; other sizes, parts or scalars capture again."""
+        photometric = bool(photometric)
+        if keypoints is not None:
+            from .keypoints import KeypointTargets
+            V = int(self.body["v_template"].shape[0])
+            if not isinstance(keypoints, KeypointTargets) or keypoints.device != self.device or keypoints.V != V:
+                raise ValueError(f"PoseFitter.fit: keypoints must be a KeypointTargets on {self.device} over the body's V = {V} vertices")
+        elif not photometric:
+            raise ValueError("PoseFitter.fit: photometric=False leaves no loss without keypoints")
+        if not photometric:
+            cameras, gt_images, regions = [], [], []
         single = not isinstance(cameras, (list, tuple))
         cameras = [cameras] if single else list(cameras)
         n = len(cameras)
@@ -330,16 +378,21 @@ class PoseFitter:
             gt_images, regions = [gt_images], [regions]
         gt_images = list(gt_images)
         regions = [None] * n if regions is None else list(regions)
-        if n == 0 or len(gt_images) != n or len(regions) != n:
+        if (n == 0 and photometric) or len(gt_images) != n or len(regions) != n:
             raise ValueError("PoseFitter.fit: one ground truth and one region (or None) per camera")
         steps = int(steps)
-        self._load_views(cameras, gt_images, regions)
+        self._load_views(cameras, gt_images, regions, keypoints, photometric)
         self._load_start(smpl_param)
         losses = torch.zeros(max(steps, 0), dtype=torch.float32, device=self.device)
         if self.capture and self._graphed is None and steps > 0:
             from .graphs import GraphedStep
             self._compute()                                      # (eager first: the synchronous forwards size the binning capacities)
-            self._graphed = GraphedStep(self._compute, warmup=2, device=self.device, context=self._views[0].context,
+            if self._views:
+                context = self._views[0].context
+            else:                                                # (no render is captured: a context of its own keeps the default one untouched)
+                from .diff_gaussian_rasterization._C import RasterContext
+                context = RasterContext()
+            self._graphed = GraphedStep(self._compute, warmup=2, device=self.device, context=context,
                                         extra_contexts=[v.context for v in self._views[1:]])
             self.captures += 1
         for k in range(steps):
